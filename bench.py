@@ -27,9 +27,20 @@ HBM, their count on the host (+ the count all-gather for N > 1).  Inputs are res
 before the timed region; nothing is cached between steps.
 
 One JSON line on rank 0; `roofline` is for the dominant kernel (K1) from HIP events recorded on
-the library's stream inside the timed region; `cpu_baseline` is the reference's algorithm on
-the host cores of this box (rank 0, N = 1): a genuine `ahocorasick_rs` wheel if one is
-importable, else the oracle's C restatement -- 1 core and all cores, 3 warm-ups, median of 7.
+the library's stream inside the timed region.  A plain run sets up, settles, warms up, times the
+K steps and prints the line; everything else it can measure runs only with --full:
+  --full  the cold number (config.value_no_settle: the same W + K steps without the settle phase),
+          config.secondary (K1a, word-shaped text, names over prose, dense stretches, the density sweep),
+          config.target_8gib, and `cpu_baseline`: the reference's algorithm on the host cores of this
+          box (rank 0, N = 1): a genuine `ahocorasick_rs` wheel if one is importable, else the oracle's
+          C restatement -- 1 core and all cores, 3 warm-ups, median of 7.  The --no-* switches below
+          turn single parts of it off.
+  --dump-outputs DIR  after the timed steps, what the last timed step returned to its caller, as
+          float64 .npy files (exact for offsets and ids below 2^53): count.npy (matches of the step),
+          pattern.npy / start.npy / end.npy (the match triples; at most 64 MB in all -- beyond that a
+          fixed, seeded sample of the rows, whose row numbers are in match_index.npy), counts.npy
+          (matches per haystack, batch configurations).  Ranks other than 0 of a multi-GPU run
+          prefix their files with rank<r>_.  The inputs depend on the arguments only.
 """
 from __future__ import annotations
 
@@ -89,7 +100,19 @@ def parse_args(argv=None):
                     help="prefix of the haystack the 1-core CPU leg scans per run")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / collective plumbing only: gloo on CPU, no device work (tests)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: the cold number, the secondary lines, the 8 GiB "
+                         "run and the CPU baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (float64 .npy, at most 64 MB) into DIR")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.callers > 1:
+        ap.error("--dump-outputs needs --callers 1 (concurrent callers have no single last step)")
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -337,8 +360,9 @@ def run(args) -> None:
         threading.Thread(target=gather_worker, daemon=True).start()
     last = {}
 
-    def hot() -> int:
-        """one pass of the hot path over this rank's batch (no collective)"""
+    def hot(hold: bool = False) -> int:
+        """one pass of the hot path over this rank's batch (no collective); hold: keep the device result
+        (last["held"]) instead of freeing it"""
         if args.dry_run:
             n = 1000 + rank
         elif args.host:
@@ -354,7 +378,7 @@ def run(args) -> None:
         else:
             # the same three C-ABI calls as capi.Automaton.find_device + DeviceResult.count / free, without the Python
             # objects in between (a step is ~350 us: ten microseconds of interpreter per step are three percent)
-            n = fast_step()
+            n = fast_step(hold)
         return n
 
     fast_step = None
@@ -365,20 +389,23 @@ def run(args) -> None:
         ptr_, ref_ = w["hay"].data_ptr(), ctypes.byref(out_)
         nh_, ul_, ov_, cp_ = w["n_hay"], w["uniform_len"], int(w["overlapping"]), int(w["codepoints"])
 
-        def fast_step() -> int:
+        def fast_step(hold: bool = False) -> int:
             rc = L_.acx_find_device(h_, ptr_, nbytes, None, nh_, ul_, ov_, cp_, ref_)
             if rc:
                 capi._check(rc)
             n_ = L_.acx_result_count(out_)
-            L_.acx_free_result(out_)
+            if hold:  # (--dump-outputs: the last timed step's result is read after the timed region)
+                last["held"] = capi.DeviceResult(out_.value, nh_ if ul_ else 0)
+            else:
+                L_.acx_free_result(out_)
             return n_
 
     def gather_wait() -> None:
         if gather_q is not None:
             gather_q.join()
 
-    def step() -> int:
-        n = hot()
+    def step(hold: bool = False) -> int:
+        n = hot(hold)
         if dist is not None:  # C1: per-shard match counts -> global output offsets
             k = pending[1] & 1
             pending[1] += 1
@@ -396,13 +423,14 @@ def run(args) -> None:
     n_gathers = [0]
     _step = step
 
-    def step() -> int:  # (counts the collectives: config.collective says what ran)
+    def step(hold: bool = False) -> int:  # (counts the collectives: config.collective says what ran)
         if dist is not None:
             n_gathers[0] += 1
-        return _step()
+        return _step(hold)
 
-    def timed_region(steps: int, warmup: int, profile: bool):
-        """W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides"""
+    def timed_region(steps: int, warmup: int, profile: bool, hold_last: bool = False):
+        """W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides
+        (hold_last: the K-th step keeps its result for --dump-outputs)"""
         n = 0
         for _ in range(warmup):
             n = step()
@@ -428,8 +456,10 @@ def run(args) -> None:
             for th in ths:
                 th.join()
         else:
-            for _ in range(steps):
+            for _ in range(steps - 1 if hold_last else steps):
                 n = step()
+            if hold_last:
+                n = step(True)
         gather_wait()
         sync()
         if dist is not None:
@@ -443,9 +473,9 @@ def run(args) -> None:
 
     # ---- (1) the cold number, on the record next to the settled one (config.value_no_settle): the very
     # same W warm-up + K timed steps WITHOUT the settle phase, from an idle GPU (2 s of idleness put the
-    # power controller back into its start-up transient: profiles/r02/step_times_cold_start.txt)
+    # power controller back into its start-up transient: profiles/r02/step_times_cold_start.txt); --full only
     cold = None
-    if not args.dry_run and not args.no_cold and args.settle_ms > 0:
+    if args.full and not args.dry_run and not args.no_cold and args.settle_ms > 0:
         n_matches = hot()  # the first call allocates the workspaces: tens of ms, part of neither region
         sync()
         time.sleep(2.0)
@@ -466,7 +496,9 @@ def run(args) -> None:
         while time.perf_counter() < t_end:
             n_matches = hot()
             settled += 1
-    elapsed, n_matches, prof = timed_region(args.steps, args.warmup, True)
+    elapsed, n_matches, prof = timed_region(args.steps, args.warmup, True, hold_last=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, n_matches, "" if rank == 0 else f"rank{rank}_", DUMP_LIMIT // world)
 
     total_matches = n_matches
     per_rank = [nbytes * args.steps / elapsed / 1e9]
@@ -545,14 +577,14 @@ def run(args) -> None:
                 "kernel_ms_samples": int(prof.scan_launches),
                 "algorithmic_bytes": int(algo_bytes),
             }
-            if (world == 1 and cfg == "cfg2" and args.dist == "T" and nbytes == GIB and not args.no_secondary
+            if (args.full and world == 1 and cfg == "cfg2" and args.dist == "T" and nbytes == GIB and not args.no_secondary
                     and not args.host and args.callers == 1 and not args.ablate and args.kernel == "auto"):
                 # (before the 8 GiB run: the lines that sit next to the headline are taken in the headline's own state)
                 out["config"]["secondary"] = secondary_runs(w, capi, gen, torch, dev)
-            if (world == 1 and cfg == "cfg2" and args.dist == "T" and nbytes == GIB and not args.no_target_size
+            if (args.full and world == 1 and cfg == "cfg2" and args.dist == "T" and nbytes == GIB and not args.no_target_size
                     and not args.host and args.callers == 1 and not args.ablate and args.kernel == "auto"):
                 out["config"]["target_8gib"] = target_size_run(w, torch, dev)
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 last["keep"] = True
                 step()  # one more pass, keeping the match stream for the SHA-256 comparison
                 out["cpu_baseline"] = cpu_baseline(w, last.get("matches"), args.cpu_sample_bytes)
@@ -778,6 +810,48 @@ def target_size_run(w, torch, dev, nbytes: int = 8 * GIB, steps: int = 5, warmup
                 "gbps": round(gbps, 2), "frac": round(gbps / HBM_PEAK_GBPS, 4), "matches": int(n), "paths": paths}
     except Exception as e:  # never take the headline down
         return {"skipped": f"failed: {e!r}"}
+
+
+DUMP_LIMIT = 64 * 10 ** 6  # --dump-outputs: bytes written at most, all ranks together
+
+
+def dump_outputs(d: str, last: dict, n: int, prefix: str, limit: int) -> None:
+    """--dump-outputs: what the last timed step returned to its caller, as float64 .npy files (exact below 2^53):
+    count, for a batch the matches per haystack (counts), and the match triples (pattern / start / end).  An array that
+    would not fit in `limit` is replaced by a fixed, seeded sample of its rows, whose row numbers go into
+    <name>_index (match_index for the triples)."""
+    import numpy as np
+    r = last.pop("held", None)  # (device path: the held result; host path: the last step's host array)
+    try:
+        matches = last.get("matches") if r is None else r.matches()
+        counts = r.counts() if r is not None and r.n_hay else None
+    finally:
+        if r is not None:
+            r.free()
+    out = {"count": np.array([n], dtype=np.float64)}
+
+    def fit(a, width: int, share: int, name: str):
+        """-> (the rows of `a` -- `width` float64 columns each -- that fit in `share` bytes: all, or a seeded sample whose
+        row numbers go into <name>_index; bytes used)"""
+        if len(a) * width * 8 <= share:
+            return a, len(a) * width * 8
+        keep = share // ((width + 1) * 8)
+        idx = np.sort(np.random.default_rng(1).choice(len(a), keep, replace=False))
+        out[name + "_index"] = idx.astype(np.float64)
+        return a[idx], keep * (width + 1) * 8
+
+    room = limit - 8 - 4096  # (the count, the .npy headers)
+    if counts is not None:  # (the per-haystack counts take at most half, the triples the rest)
+        counts, used = fit(counts, 1, room // 2, "counts")
+        room -= used
+        out["counts"] = counts.astype(np.float64)
+    if matches is not None:
+        matches, _ = fit(matches, 3, room, "match")
+        for c in ("pattern", "start", "end"):
+            out[c] = np.ascontiguousarray(matches[c]).astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, prefix + name + ".npy"), a)
 
 
 def measured_traffic(kernel: str, nbytes: int, dist_name: str, cfg: str):

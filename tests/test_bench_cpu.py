@@ -71,3 +71,69 @@ def test_genuine_wheel_probe_ignores_this_repository():
     before = sys.modules["ahocorasick_rs"]
     assert bench.probe_genuine_wheel() is None  # no Rust wheel in this image; ours is not mistaken for one
     assert sys.modules["ahocorasick_rs"] is before and ROOT in [os.path.abspath(p) for p in sys.path]
+
+
+def test_plain_run_options():
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert bench.parse_args(["--full"]).full
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--dump-outputs", "x", "--callers", "2"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dry_run_dumps_the_last_step(tmp_path):
+    p = run_bench("--dry-run", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out"))
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    c = np.load(tmp_path / "out" / "count.npy")
+    assert c.dtype == np.float64 and c.tolist() == [1000.0]
+
+
+class _Held:
+    """stands in for capi.DeviceResult"""
+
+    def __init__(self, m, counts=None):
+        self.m, self.c, self.n_hay, self.freed = m, counts, 0 if counts is None else len(counts), False
+
+    def matches(self):
+        return self.m
+
+    def counts(self):
+        return self.c
+
+    def free(self):
+        self.freed = True
+
+
+def _triples(n, seed):
+    m = np.zeros(n, dtype=[("pattern", "<u8"), ("start", "<u8"), ("end", "<u8")])
+    r = np.random.default_rng(seed)
+    m["pattern"] = r.integers(0, 10000, n)
+    m["start"] = np.sort(r.integers(0, 1 << 40, n))
+    m["end"] = m["start"] + 7
+    return m
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    m, counts = _triples(1000, 3), np.arange(50, dtype=np.uint64)
+    held = _Held(m, counts)
+    bench.dump_outputs(str(tmp_path / "a"), {"held": held}, 1000, "", bench.DUMP_LIMIT)
+    assert held.freed
+    ld = lambda d, n: np.load(tmp_path / d / (n + ".npy"))  # noqa: E731
+    for c in ("pattern", "start", "end"):
+        assert ld("a", c).dtype == np.float64 and np.array_equal(ld("a", c).astype(np.uint64), m[c])
+    assert np.array_equal(ld("a", "counts"), counts.astype(np.float64)) and ld("a", "count").tolist() == [1000.0]
+    assert not (tmp_path / "a" / "match_index.npy").exists()
+    # more than fits: a fixed, seeded sample of the rows, the same from run to run, within the limit
+    m = _triples(200_000, 4)
+    limit = 1 << 20
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"matches": m}, len(m), "r1_", limit)
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= limit
+    idx = ld("b", "r1_match_index").astype(np.int64)
+    assert 0 < len(idx) < len(m) and np.all(np.diff(idx) > 0)
+    for c in ("pattern", "start", "end"):
+        assert np.array_equal(ld("b", "r1_" + c), ld("c", "r1_" + c))
+        assert np.array_equal(ld("b", "r1_" + c).astype(np.uint64), m[c][idx])

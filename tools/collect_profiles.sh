@@ -29,36 +29,36 @@ mkdir -p $OUT
 cd /root/repo
 python tools/kernel_hash.py > $OUT/kernel_source_sha256.txt
 if [ "$PART" = all ] || [ "$PART" = bench ]; then
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_T.json 2> $OUT/bench_T.err
-timeout 300 python bench.py --dist U --no-cpu-baseline --no-secondary > $OUT/bench_U.json 2> $OUT/bench_U.err
-timeout 300 python bench.py --config cfg3 --no-cpu-baseline > $OUT/bench_cfg3_shape_n1.json 2> $OUT/bench_cfg3.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_T.json 2> $OUT/bench_T.err
+timeout 300 python bench.py --full --dist U --no-cpu-baseline --no-secondary > $OUT/bench_U.json 2> $OUT/bench_U.err
+timeout 300 python bench.py --full --config cfg3 --no-cpu-baseline > $OUT/bench_cfg3_shape_n1.json 2> $OUT/bench_cfg3.err
 for cfg in cfg4 cfg4b cfg5 cfg2b; do
-  timeout 900 python bench.py --config $cfg --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
+  timeout 900 python bench.py --full --config $cfg --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
 done
-timeout 900 python bench.py --config large --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_large_1M_patterns.json 2> $OUT/bench_large.err
-timeout 600 python bench.py --host --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_host_path.json 2> $OUT/bench_host.err
+timeout 900 python bench.py --full --config large --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_large_1M_patterns.json 2> $OUT/bench_large.err
+timeout 600 python bench.py --full --host --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_host_path.json 2> $OUT/bench_host.err
 for d in T U; do
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-target-size --dist $d --kernel dfa_walk > $OUT/bench_${d}_dfa_walk.json 2> $OUT/bench_${d}_dfa_walk.err
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-target-size --dist $d --kernel dfa_walk > $OUT/bench_${d}_dfa_walk.json 2> $OUT/bench_${d}_dfa_walk.err
   ACX_NO_PFAC=1 timeout 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-target-size --no-cold --dist $d --kernel dfa_walk > $OUT/bench_${d}_dfa_walk_chunked.json 2> $OUT/bench_${d}_dfa_walk_chunked.err
 done
 # mixed-length sets (round 4: K1b with its side test): rare short patterns, the round-2 VERDICT's example (dense
 # output), cfg5's set + short patterns (> 32 byte classes: the round-3 cliff); and the round-3 path for comparison
 for cfg in mixed mixedx mixedb; do
-  timeout 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-target-size --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
+  timeout 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-target-size --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
 done
-ACX_NO_SHORT_SPLIT=1 timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-target-size --config mixed > $OUT/bench_mixed_round3_path_k1a.json 2> $OUT/bench_mixed_round3_path_k1a.err
+ACX_NO_SHORT_SPLIT=1 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-target-size --config mixed > $OUT/bench_mixed_round3_path_k1a.json 2> $OUT/bench_mixed_round3_path_k1a.err
 # anchors off: cfg5 on the round-3 tables
-ACX_NO_ANCHORS=1 timeout 600 python bench.py --config cfg5 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg5_no_anchors.json 2> $OUT/bench_cfg5_no_anchors.err
+ACX_NO_ANCHORS=1 timeout 600 python bench.py --full --config cfg5 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg5_no_anchors.json 2> $OUT/bench_cfg5_no_anchors.err
 # dense stretches: ONE 64 KiB region / 1 % of the groups (the hot pipeline), and the curve from sparse to dense
 for d in H1 H100 P1024 P512 P256 P128 P64 P32; do
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-target-size --dist $d > $OUT/bench_hot_$d.json 2> $OUT/bench_hot_$d.err
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-target-size --dist $d > $OUT/bench_hot_$d.json 2> $OUT/bench_hot_$d.err
 done
 # the dense paths: a dense input through the tile-ordered form and through the radix-sort form, the headline input forced onto it
-timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-target-size --dist D > $OUT/bench_dense_D.json 2> $OUT/bench_dense_D.err
-ACX_NO_DENSE_TILES=1 timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-target-size --dist D > $OUT/bench_dense_D_radix_form.json 2> $OUT/bench_dense_D_radix_form.err
-ACX_NO_BUCKET=1 timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-target-size --no-secondary > $OUT/bench_T_forced_dense_path.json 2> $OUT/bench_T_forced_dense_path.err
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-target-size --dist D > $OUT/bench_dense_D.json 2> $OUT/bench_dense_D.err
+ACX_NO_DENSE_TILES=1 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-target-size --dist D > $OUT/bench_dense_D_radix_form.json 2> $OUT/bench_dense_D_radix_form.err
+ACX_NO_BUCKET=1 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-target-size --no-secondary > $OUT/bench_T_forced_dense_path.json 2> $OUT/bench_T_forced_dense_path.err
 # one rank under the launcher: RCCL init + the count all-gather on the device
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-target-size > $OUT/bench_T_one_rank_rccl.json 2> $OUT/bench_T_one_rank_rccl.err
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-target-size > $OUT/bench_T_one_rank_rccl.json 2> $OUT/bench_T_one_rank_rccl.err
 timeout 600 python benchmarks/bench_comparison.py > $OUT/bench_comparison.txt 2>&1
 ACX_SMALL_SYNC=1 timeout 600 python benchmarks/bench_comparison.py > $OUT/bench_comparison_stream_sync.txt 2>&1
 # round 6: without the resident K0 (a launch per small call) and without the in-place mid-size path, same box
