@@ -285,77 +285,6 @@ struct PinnedResults {
 };
 PinnedResults g_pinned_results;
 
-// Host threads that copy a caller's pageable bytes into pinned staging chunks (one thread moves
-// ~10 GB/s; the PCIe link wants ~55): created on the first large host-memory call.
-class CopyPool {
-public:
-    static CopyPool &get() {
-        static CopyPool p;
-        return p;
-    }
-    int threads() const { return (int)workers_.size() + 1; }
-    // memcpy(dst, src, n) by all threads; returns when done.  One job at a time.
-    void copy(void *dst, const void *src, size_t n) {
-        const int T = threads();
-        if (n < (1u << 20) || T == 1) { std::memcpy(dst, src, n); return; }
-        std::lock_guard<std::mutex> job(job_mu_);
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            dst_ = (uint8_t *)dst; src_ = (const uint8_t *)src; n_ = n;
-            pending_ = T - 1;
-            gen_++;
-        }
-        cv_.notify_all();
-        slice(0, T);
-        std::unique_lock<std::mutex> lk(mu_);
-        done_cv_.wait(lk, [&] { return pending_ == 0; });
-    }
-
-private:
-    CopyPool() {
-        int T = (int)std::thread::hardware_concurrency() / 2;
-        if (const char *e = std::getenv("ACX_COPY_THREADS")) T = std::atoi(e);
-        T = std::max(1, std::min(T, 16));
-        for (int i = 1; i < T; i++) workers_.emplace_back([this, i, T] { run(i, T); });
-    }
-    ~CopyPool() {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto &t : workers_) t.join();
-    }
-    void slice(int i, int T) {
-        const size_t per = ((n_ + T - 1) / T + 4095) & ~(size_t)4095;
-        const size_t lo = std::min(n_, per * i), hi = std::min(n_, per * (i + 1));
-        if (hi > lo) std::memcpy(dst_ + lo, src_ + lo, hi - lo);
-    }
-    void run(int i, int T) {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-            }
-            slice(i, T);
-            std::lock_guard<std::mutex> lk(mu_);
-            if (--pending_ == 0) done_cv_.notify_one();
-        }
-    }
-    std::vector<std::thread> workers_;
-    std::mutex mu_, job_mu_;
-    std::condition_variable cv_, done_cv_;
-    uint8_t *dst_ = nullptr;
-    const uint8_t *src_ = nullptr;
-    size_t n_ = 0;
-    int pending_ = 0;
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-};
-
 // ---------------------------------------------------------------------------
 // pinned host scratch of a context, in 64-bit words (Workspace::h_pinned)
 constexpr uint32_t PIN_TOTALS = 24, PIN_HOT_TOTALS = 32, PIN_SPEC_TOTALS = 40, PIN_RESIDENT = 48, PIN_K0 = 64, PINNED_WORDS = 96;
@@ -412,11 +341,6 @@ struct Workspace {
     uint64_t hay_cap = 0;
     uint64_t *offsets = nullptr;
     uint64_t offsets_cap = 0;
-    // pipelined host -> device staging: ring of pinned chunks
-    static constexpr int RING = 3;
-    uint8_t *pin_chunk[RING] = {nullptr, nullptr, nullptr};
-    hipEvent_t chunk_ev[RING] = {nullptr, nullptr, nullptr};
-    size_t chunk_bytes = 0;
 };
 
 // The resident K0 of a context (kernels.hip, k0_resident): one workgroup that stays on the device between the calls of a
@@ -439,7 +363,7 @@ struct Resident {
 
 // everything one in-flight call needs
 struct Ctx {
-    hipStream_t stream = nullptr, copy_stream = nullptr;
+    hipStream_t stream = nullptr, copy_stream = nullptr; // copy_stream: the second stream (the str API's code-point prefix)
     Resident res;
     // profiling: [0], [1] and [3], [4]: scan start / stop, two pairs used by the calls in turn (the time
     // of a call's scan is read while the NEXT call's kernels run, off the path between two calls);
@@ -450,7 +374,6 @@ struct Ctx {
     bool scan_pending = false; // a scan's time has not been read yet
     int pend_pair = 0;
     uint64_t pend_len = 0;
-    hipEvent_t copy_done = nullptr;                 // staging: the last chunk has landed
     hipEvent_t fork_ev = nullptr, join_ev = nullptr; // str API: the code-point prefix runs beside k_tile_main
     Workspace ws;
     bool post_pending = false; // profiling: ev[2] of the last call has not been read yet
@@ -597,10 +520,6 @@ void free_ws(Workspace &w, int device) {
     if (w.mailbox) (void)hipHostFree(w.mailbox);
     if (w.pin_mid) (void)hipHostFree(w.pin_mid);
     if (w.pin_out) (void)hipHostFree(w.pin_out);
-    for (int i = 0; i < Workspace::RING; i++) {
-        if (w.pin_chunk[i]) (void)hipHostFree(w.pin_chunk[i]);
-        if (w.chunk_ev[i]) (void)hipEventDestroy(w.chunk_ev[i]);
-    }
     w = Workspace();
 }
 
@@ -651,7 +570,6 @@ void destroy_ctx(Ctx *c, int device) {
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     free_ws(c->ws, device);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-    if (c->copy_done) (void)hipEventDestroy(c->copy_done);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->join_ev) (void)hipEventDestroy(c->join_ev);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -665,7 +583,6 @@ Ctx *create_ctx() { // the automaton's device is current
     bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) == hipSuccess;
     for (auto &e : c->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->copy_done, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->join_ev, hipEventDisableTiming) == hipSuccess;
     if (!ok) { destroy_ctx(c, 0); return nullptr; }
@@ -743,12 +660,6 @@ int ensure_occ_capacity(Ctx *c, uint64_t want) {
     Workspace &w = c->ws;
     if (want <= w.cap) return ACX_OK;
     uint64_t cap = std::max<uint64_t>(want, 1u << 16);
-    if (std::getenv("ACX_DEBUG_MEM")) {
-        size_t fr = 0, tot = 0;
-        (void)hipMemGetInfo(&fr, &tot);
-        std::fprintf(stderr, "acx: ensure_occ_capacity want %llu (old cap %llu), device free %.1f of %.1f GiB\n",
-                     (unsigned long long)want, (unsigned long long)w.cap, fr / 1073741824.0, tot / 1073741824.0);
-    }
     for (int i = 0; i < 2; i++) {
         (void)hipFree(w.keys[i]); (void)hipFree(w.pids[i]);
         w.keys[i] = nullptr; w.pids[i] = nullptr;
@@ -914,12 +825,6 @@ inline const DevAutomaton *d_view(const acx_automaton *a, bool overlapping) { //
     return (overlapping ? a->expand_ov : a->has_nov) ? a->d_dev_nov : a->d_dev;
 }
 
-// (ACX_SMALL_SYNC, measurements: always synchronise the stream -- and then the records are plain acx_match_t)
-bool small_polls() {
-    static const bool no_poll = std::getenv("ACX_SMALL_SYNC") != nullptr;
-    return !no_poll;
-}
-
 int wait_line(Ctx *c, uint32_t at, uint64_t seq, uint64_t line[8], const char *what); // (below)
 // the result lines behind the first that a polled K0 call with `n` matches wrote (kernels.hpp, K0_RESULT_LINES: the same
 // store instruction as the first): verified copies into the workspace
@@ -940,7 +845,7 @@ int run_small(acx_automaton *a, Ctx *c, const uint8_t *hay, uint64_t len, int ov
     if (rc) return rc;
     Workspace &w = c->ws;
     const int key_mode = overlapping ? 0 : a->host.match_kind;
-    const uint64_t seq = poll && small_polls() ? ++c->small_seq : 0;
+    const uint64_t seq = poll ? ++c->small_seq : 0;
     HIPCHK(launch_small(view(a, overlapping != 0), hay, (uint32_t)len, key_mode, overlapping != 0, codepoints != 0, out,
                         seq ? w.h_pinned + PIN_K0 : w.h_pinned + 8, seq, c->stream, !(overlapping && a->expand_ov)));
     if (seq) {
@@ -1043,10 +948,9 @@ int wait_line(Ctx *c, uint32_t at, uint64_t seq, uint64_t line[8], const char *w
 // switched off, or the loop alternates between kinds of call.  Otherwise as run_small with poll = true.
 bool resident_on() {
     static const bool off = std::getenv("ACX_NO_RESIDENT") != nullptr;
-    return !off && small_polls();
+    return !off;
 }
-uint64_t env_ticks(const char *name, uint64_t dflt_us) { // microseconds -> ticks of the device's 100 MHz clock
-    const char *e = std::getenv(name);
+uint64_t env_ticks(const char *e, uint64_t dflt_us) { // microseconds (an environment value) -> ticks of the device's 100 MHz clock
     const uint64_t us = e && *e ? std::strtoull(e, nullptr, 10) : dflt_us;
     return us * 100;
 }
@@ -1065,7 +969,8 @@ int run_resident(acx_automaton *a, Ctx *c, const uint8_t *hay, uint64_t len, int
     const int mode = small_mode(A, (uint32_t)len, !(overlapping && a->expand_ov));
     // (beyond 16 KiB a launch is as good or better -- 60 000 bytes: 28 us launched, 39 through the mailbox, measured; 16 000: 30 and 17)
     if (mode < 0 || len > SMALL_MAX_LEN) { stop_resident(c); return ACX_OK; }
-    static const uint64_t idle_ticks = env_ticks("ACX_RESIDENT_IDLE_US", 200), life_ticks = env_ticks("ACX_RESIDENT_LIFE_US", 1000);
+    static const uint64_t idle_ticks = env_ticks(std::getenv("ACX_RESIDENT_IDLE_US"), 200),
+                          life_ticks = env_ticks(std::getenv("ACX_RESIDENT_LIFE_US"), 1000);
     volatile uint64_t *status = w.h_pinned + PIN_RESIDENT;
     const int ov = overlapping ? 1 : 0;
     if (R.live && (R.mode != mode || R.overlapping != ov)) {
@@ -2104,12 +2009,9 @@ int run_chunked(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, in
 // ---------------------------------------------------------------------------
 // host memory -> device staging buffer
 // ---------------------------------------------------------------------------
-// Small inputs: one hipMemcpyAsync from the caller's (pageable) memory.  Large inputs: the
-// runtime's own pageable path moves 20-40 GB/s (one staging thread), so the bytes are copied by
-// several host threads into a ring of pinned chunks, each chunk DMA'd by its own asynchronous copy
-// while the threads fill the next one; the scan is queued behind the last chunk.
-constexpr uint64_t STAGE_DIRECT_MAX = 8ull << 20;
-
+// One hipMemcpyAsync from the caller's (pageable) memory, queued ahead of the scan.  The runtime's own pageable copy
+// moves 54 GB/s on the MI355X, the link's rate: pinning the caller's pages for the call (55 GB/s, synchronised) and a
+// ring of pinned chunks filled by host threads (51 GB/s) were measured and retired (DESIGN_HISTORY.md section 5).
 int stage_host(acx_automaton *a, Ctx *c, const uint8_t *hay, uint64_t len, const uint64_t *offsets,
                uint64_t n_off) {
     Workspace &w = c->ws;
@@ -2131,45 +2033,7 @@ int stage_host(acx_automaton *a, Ctx *c, const uint8_t *hay, uint64_t len, const
         }
         HIPCHK(hipMemcpyAsync(w.offsets, offsets, n_off * 8, hipMemcpyHostToDevice, st));
     }
-    // ACX_STAGE: 1 = the runtime's own pageable copy (default: measured 54 GB/s on the MI355X box, the
-    // link's rate, once the result no longer lands in freshly faulted pages), 2 = pin the caller's
-    // pages for the call (54.8 GB/s), 3 = the ring of pinned chunks below (51 GB/s; independent of the
-    // runtime's staging)
-    static const int mode = std::getenv("ACX_STAGE") ? std::atoi(std::getenv("ACX_STAGE")) : 1;
-    if (len <= STAGE_DIRECT_MAX || mode == 1) {
-        if (len) HIPCHK(hipMemcpyAsync(w.hay, hay, len, hipMemcpyHostToDevice, st));
-        return ACX_OK;
-    }
-    if (mode == 2) { // measurements: pin the caller's pages for the call, one DMA
-        HIPCHK(hipHostRegister((void *)hay, len, hipHostRegisterDefault));
-        hipError_t e = hipMemcpyAsync(w.hay, hay, len, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipHostUnregister((void *)hay);
-        if (e != hipSuccess) return hipfail(e, "registered host copy");
-        return ACX_OK;
-    }
-    static const size_t chunk = std::getenv("ACX_STAGE_CHUNK") ? (size_t)std::atoll(std::getenv("ACX_STAGE_CHUNK"))
-                                                                : ((size_t)16 << 20);
-    if (w.chunk_bytes != chunk) {
-        for (int i = 0; i < Workspace::RING; i++) {
-            if (w.pin_chunk[i]) { (void)hipHostFree(w.pin_chunk[i]); w.pin_chunk[i] = nullptr; }
-            HIPCHK(hipHostMalloc((void **)&w.pin_chunk[i], chunk, hipHostMallocDefault));
-            if (!w.chunk_ev[i]) HIPCHK(hipEventCreateWithFlags(&w.chunk_ev[i], hipEventDisableTiming));
-        }
-        w.chunk_bytes = chunk;
-    }
-    CopyPool &pool = CopyPool::get();
-    uint64_t k = 0;
-    for (uint64_t off = 0; off < len; off += chunk, k++) {
-        const int slot = (int)(k % Workspace::RING);
-        const size_t n = (size_t)std::min<uint64_t>(chunk, len - off);
-        if (k >= (uint64_t)Workspace::RING) HIPCHK(hipEventSynchronize(w.chunk_ev[slot])); // its last DMA has read it
-        pool.copy(w.pin_chunk[slot], hay + off, n);
-        HIPCHK(hipMemcpyAsync(w.hay + off, w.pin_chunk[slot], n, hipMemcpyHostToDevice, c->copy_stream));
-        HIPCHK(hipEventRecord(w.chunk_ev[slot], c->copy_stream));
-    }
-    HIPCHK(hipEventRecord(c->copy_done, c->copy_stream));
-    HIPCHK(hipStreamWaitEvent(st, c->copy_done, 0));
+    if (len) HIPCHK(hipMemcpyAsync(w.hay, hay, len, hipMemcpyHostToDevice, st));
     return ACX_OK;
 }
 
@@ -2475,8 +2339,7 @@ int acx_build(const uint8_t *blob, const uint64_t *offsets, uint64_t n_patterns,
     a->kernel = prefilter_ok ? ACX_KERNEL_PREFILTER : ACX_KERNEL_DFA_WALK;
     if (const char *envk = std::getenv("ACX_KERNEL")) {
         if (!std::strcmp(envk, "dfa_walk")) { a->kernel = ACX_KERNEL_DFA_WALK; a->kernel_forced = true; }
-        else if (!std::strcmp(envk, "prefilter") && H.filter_q >= 1 &&
-                 a->max_lds >= prefilter_lds_bytes()) {
+        else if (!std::strcmp(envk, "prefilter") && prefilter_ok) {
             a->kernel = ACX_KERNEL_PREFILTER;
             a->kernel_forced = true;
         }
@@ -2703,30 +2566,27 @@ int acx_find(acx_automaton_t *a, const uint8_t *hay, uint64_t len, int overlappi
                                                    : w.h_lines[1 + (i - ACX_K0_LINE_MATCHES) / K0_MORE_MATCHES][1 + (i - ACX_K0_LINE_MATCHES) % K0_MORE_MATCHES];
                 };
                 volatile const uint64_t *rest = (volatile const uint64_t *)w.pin_out;
-                if (!small_polls()) std::memcpy(m, w.pin_out, n * sizeof(acx_match_t));
-                else {
-                    // pin_out and the line are separate writes of the device to host memory: the line carries a hash of what
-                    // pin_out must hold (k0_rest_mix); what is read here is taken when it agrees, read again when not
-                    const uint32_t want = (uint32_t)(w.h_lines[0][1] >> K0_REST_HASH_SHIFT);
-                    const uint64_t sq = c->small_seq;
-                    const auto t0 = std::chrono::steady_clock::now();
-                    bool synced = false; // the stream has been synchronised: what is read now is what the kernel wrote
-                    for (;;) {
-                        uint32_t hx = 0;
-                        for (uint64_t i = 0; i < n; i++) {
-                            const uint64_t v = i < K0_LINES_MATCHES ? carried(i) : rest[i - K0_LINES_MATCHES];
-                            if (i >= K0_LINES_MATCHES) hx ^= k0_rest_mix(v, (uint32_t)(i - K0_LINES_MATCHES), sq);
-                            m[i].pattern = v & 0xFFFFFFFFull; m[i].start = (v >> 32) & 0xFFFF; m[i].end = (v >> 48) + 1;
-                        }
-                        if (n <= K0_LINES_MATCHES || hx == want) break;
-                        cpu_relax();
-                        // (once the kernel is known to be over its writes have arrived: ONE more reading decides -- a hash that
-                        // still disagrees is an error, not a reason to synchronise the stream a million times)
-                        if (synced) { std::free(m); return fail(ACX_EDEVICE, "K0's matches did not arrive"); }
-                        if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(8)) {
-                            if (hipStreamSynchronize(c->stream) != hipSuccess) { std::free(m); return fail(ACX_EDEVICE, "K0's matches did not arrive"); }
-                            synced = true;
-                        }
+                // pin_out and the line are separate writes of the device to host memory: the line carries a hash of what
+                // pin_out must hold (k0_rest_mix); what is read here is taken when it agrees, read again when not
+                const uint32_t want = (uint32_t)(w.h_lines[0][1] >> K0_REST_HASH_SHIFT);
+                const uint64_t sq = c->small_seq;
+                const auto t0 = std::chrono::steady_clock::now();
+                bool synced = false; // the stream has been synchronised: what is read now is what the kernel wrote
+                for (;;) {
+                    uint32_t hx = 0;
+                    for (uint64_t i = 0; i < n; i++) {
+                        const uint64_t v = i < K0_LINES_MATCHES ? carried(i) : rest[i - K0_LINES_MATCHES];
+                        if (i >= K0_LINES_MATCHES) hx ^= k0_rest_mix(v, (uint32_t)(i - K0_LINES_MATCHES), sq);
+                        m[i].pattern = v & 0xFFFFFFFFull; m[i].start = (v >> 32) & 0xFFFF; m[i].end = (v >> 48) + 1;
+                    }
+                    if (n <= K0_LINES_MATCHES || hx == want) break;
+                    cpu_relax();
+                    // (once the kernel is known to be over its writes have arrived: ONE more reading decides -- a hash that
+                    // still disagrees is an error, not a reason to synchronise the stream a million times)
+                    if (synced) { std::free(m); return fail(ACX_EDEVICE, "K0's matches did not arrive"); }
+                    if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(8)) {
+                        if (hipStreamSynchronize(c->stream) != hipSuccess) { std::free(m); return fail(ACX_EDEVICE, "K0's matches did not arrive"); }
+                        synced = true;
                     }
                 }
                 if (overlapping && a->expand_ov) { // (copies of a string: K0 reported the lowest ids -- expand_copies, on the host)

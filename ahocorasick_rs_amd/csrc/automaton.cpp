@@ -412,10 +412,8 @@ std::string compile(const uint8_t *blob, const uint64_t *offsets, uint64_t n,
     A.short_xy.clear(); A.short_codes.clear();
     if (n > 0) {
         // ---- the split (automaton.hpp): patterns of 1 and 2 bytes go to the side test, the prefilter tables
-        // are built from the others (ACX_NO_SHORT_SPLIT: measurements / the round-3 behaviour -- one set, Q from
-        // the shortest pattern whatever it is)
-        static const bool no_split = std::getenv("ACX_NO_SHORT_SPLIT") != nullptr;
-        const bool split = !no_split && A.min_len <= SHORT_MAX_LEN;
+        // are built from the others
+        const bool split = A.min_len <= SHORT_MAX_LEN;
         auto is_short = [&](uint64_t i) { return split && A.plen[i] <= SHORT_MAX_LEN; };
         uint32_t long_min = split ? 0xFFFFFFFFu : A.min_len;
         if (split)
@@ -457,8 +455,7 @@ std::string compile(const uint8_t *blob, const uint64_t *offsets, uint64_t n,
                 for (uint32_t k = 1; k < Q; k++) v -= lb[(size_t)x[k - 1] * 256 + x[k]];
                 return v;
             };
-            const char *gain_env = std::getenv("ACX_SHIFT_GAIN"); // measurements: how much rarer an offset must be
-            const float gain_bits = std::log2(gain_env ? std::max(1.0f, (float)std::atof(gain_env)) : (float)SHIFT_GAIN);
+            const float gain_bits = std::log2((float)SHIFT_GAIN);
             for (uint64_t i = 0; i < n; i++) {
                 if (is_short(i)) continue;
                 const uint8_t *pp = pb + A.offsets[i];
@@ -574,12 +571,10 @@ std::string compile(const uint8_t *blob, const uint64_t *offsets, uint64_t n,
         for (uint64_t i = 0; i < n; i++)
             for (uint32_t k = 0; k < Q2 && !is_short(i); k++)
                 if (abytes(i)[k] >= 0xC0) { multibyte++; break; }
-        const char *inv_env = std::getenv("ACX_PTAB_INV_LOAD"); // measurements: slots per key
-        const size_t inv_load = inv_env ? (size_t)std::max(2, std::atoi(inv_env))
-                                        : A.max_shift                                        ? 8 // (anchored sets: the hot beginnings are gone)
-                                        : 20 * multibyte > n && keys.size() <= 65536         ? 32
-                                          : (A.filter_q == 5 && A.filter_density > 0.2) || 20 * multibyte > n ? 8
-                                                                                                : 4;
+        const size_t inv_load = A.max_shift                                                  ? 8 // (anchored sets: the hot beginnings are gone)
+                                : 20 * multibyte > n && keys.size() <= 65536                 ? 32
+                                : (A.filter_q == 5 && A.filter_density > 0.2) || 20 * multibyte > n ? 8
+                                                                                             : 4;
         while ((1u << lg) < inv_load * keys.size()) lg++;
         A.ptab_log2 = lg;
         A.ptab.assign((size_t)4 << lg, 0);

@@ -176,7 +176,7 @@ struct Automaton {
     std::vector<uint32_t> plen;        // n_patterns
     std::vector<uint32_t> rank;        // n_patterns: rank in (len desc, pid asc)
     // prefilter
-    uint32_t filter_q = 0;             // level-1 prefix length Q (3..5; 1..2 only with ACX_NO_SHORT_SPLIT), 0 = no patterns
+    uint32_t filter_q = 0;             // level-1 prefix length Q (3..5), 0 = no patterns
     uint32_t filter_q2 = 0;            // level-2 prefix length Q2 (3..8)
     uint32_t max_shift = 0;            // largest anchor offset in use (0: every pattern is filed under its beginning)
     std::vector<uint8_t> shift;        // n_patterns: the anchor offset d of every pattern (automaton.hpp, anchors)

@@ -1559,10 +1559,7 @@ hipError_t launch_prefilter(const DevAutomaton &A, const Sink &K, const uint8_t 
     else ACX_K1B_LAUNCH(Q, false, false, B, H)
 #define ACX_K1B_SH(Q, B)                                                                                   \
     if (sh) { ACX_K1B(Q, B, true); } else { ACX_K1B(Q, B, false); }
-    switch (A.filter_q) {
-    // (Q = 1, 2: only with ACX_NO_SHORT_SPLIT -- the split keeps such patterns out of these tables)
-    case 1: ACX_K1B(1, 0, false); break;
-    case 2: ACX_K1B(2, 0, false); break;
+    switch (A.filter_q) { // (3 .. 5: patterns of 1 or 2 bytes are the side test's -- automaton.hpp, the split)
     case 3: ACX_K1B_SH(3, 0) break;
     case 4: ACX_K1B_SH(4, 0) break;
     default:
@@ -4103,20 +4100,16 @@ __global__ __launch_bounds__(1024) void k0_resident(const DevAutomaton *A, const
 }
 
 int small_mode(const DevAutomaton &A, uint32_t len, bool direct_ok) {
-    // (ACX_K0_NO_LDS_TABLE: measurements)
-    static const bool no_lt = std::getenv("ACX_K0_NO_LDS_TABLE") != nullptr;
-    static const bool no_dc = std::getenv("ACX_K0_NO_DIRECT") != nullptr;
     const bool lt = A.table && ((uint64_t)A.n_states << A.stride2) <= K0_LT_ENTRIES && A.n_states <= K0_LT_IDS &&
-                    A.n_patterns <= K0_LT_IDS && A.max_len < 256 && !no_lt;
+                    A.n_patterns <= K0_LT_IDS && A.max_len < 256;
     const bool dc = A.n_patterns <= K0_DC_PATTERNS && A.min_len >= 1 && A.max_len <= 16 && A.pat_blob && A.pat_off &&
-                    (uint64_t)len * A.n_patterns <= K0_DC_WORK && !no_dc && direct_ok;
+                    (uint64_t)len * A.n_patterns <= K0_DC_WORK && direct_ok;
     // the prefilter (MODE 3): beyond SMALL_MAX_LEN the only way; below it for automata whose tables do not fit the LDS
     // from 1 KiB on (shorter: the walk's handful of gathers is as good).  Measured again in round 6 with the resident kernel
-    // (ACX_K0_PF_MIN=0: from the first byte): a haystack WITH a match gains -- 64 bytes with one match 8.9 -> 7.4 us, the walk
+    // (the prefilter from the first byte): a haystack WITH a match gains -- 64 bytes with one match 8.9 -> 7.4 us, the walk
     // that finds it is a chain of a dozen dependent gathers --, one without loses: the reference's long dataset (1 haystack
     // in 90 holds a match) 6.1-6.3 -> 6.6-6.9 us per call.  The reference's own loop decides: 1 KiB stays.
-    static const uint32_t pf_min = std::getenv("ACX_K0_PF_MIN") ? (uint32_t)std::atoi(std::getenv("ACX_K0_PF_MIN")) : 1024u;
-    const bool pf = small_prefilter_ok(A) && (len > SMALL_MAX_LEN || (!dc && !lt && len > pf_min));
+    const bool pf = small_prefilter_ok(A) && (len > SMALL_MAX_LEN || (!dc && !lt && len > 1024u));
     if (len > SMALL_MAX_LEN && !pf) return -1;
     return pf ? 3 : dc ? 2 : lt ? 1 : 0;
 }
@@ -4289,8 +4282,7 @@ __global__ __launch_bounds__(BP_THREADS) void k_block_prefix(const uint64_t *__r
 hipError_t block_prefix(const uint8_t *sub, uint64_t *cnt, uint64_t *pre, uint64_t nblocks, void *temp, size_t temp_bytes,
                         hipStream_t st) {
     const uint64_t n = nblocks + 1, nwg = (n + BP_BLOCKS - 1) / BP_BLOCKS;
-    static const bool lib = std::getenv("ACX_BLOCK_PREFIX_LIBRARY") != nullptr; // (measurements: the round-5 way)
-    if (nwg > BP_MAX_WGS || temp_bytes < nwg * 8 || lib) {
+    if (nwg > BP_MAX_WGS || temp_bytes < nwg * 8) { // (more than 4 GiB, or a short temp: the library's scan)
         if (sub) {
             hipError_t e = block_totals(sub, cnt, nblocks, st);
             if (e != hipSuccess) return e;

@@ -42,11 +42,10 @@ for d in T U; do
   ACX_NO_PFAC=1 timeout 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-target-size --no-cold --dist $d --kernel dfa_walk > $OUT/bench_${d}_dfa_walk_chunked.json 2> $OUT/bench_${d}_dfa_walk_chunked.err
 done
 # mixed-length sets (round 4: K1b with its side test): rare short patterns, the round-2 VERDICT's example (dense
-# output), cfg5's set + short patterns (> 32 byte classes: the round-3 cliff); and the round-3 path for comparison
+# output), cfg5's set + short patterns (> 32 byte classes: the round-3 cliff)
 for cfg in mixed mixedx mixedb; do
   timeout 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-target-size --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
 done
-ACX_NO_SHORT_SPLIT=1 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-target-size --config mixed > $OUT/bench_mixed_round3_path_k1a.json 2> $OUT/bench_mixed_round3_path_k1a.err
 # anchors off: cfg5 on the round-3 tables
 ACX_NO_ANCHORS=1 timeout 600 python bench.py --full --config cfg5 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_cfg5_no_anchors.json 2> $OUT/bench_cfg5_no_anchors.err
 # dense stretches: ONE 64 KiB region / 1 % of the groups (the hot pipeline), and the curve from sparse to dense
@@ -60,7 +59,6 @@ ACX_NO_BUCKET=1 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cp
 # one rank under the launcher: RCCL init + the count all-gather on the device
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-target-size > $OUT/bench_T_one_rank_rccl.json 2> $OUT/bench_T_one_rank_rccl.err
 timeout 600 python benchmarks/bench_comparison.py > $OUT/bench_comparison.txt 2>&1
-ACX_SMALL_SYNC=1 timeout 600 python benchmarks/bench_comparison.py > $OUT/bench_comparison_stream_sync.txt 2>&1
 # round 6: without the resident K0 (a launch per small call) and without the in-place mid-size path, same box
 ACX_NO_RESIDENT=1 ACX_INPLACE_MAX=0 timeout 600 python benchmarks/bench_comparison.py < /dev/null > $OUT/exp_no_resident_no_inplace_bench_comparison.txt 2>&1
 # K0 without its prefilter mode (round 4's K0: the walks, 16 KiB at most), same box

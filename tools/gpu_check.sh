@@ -72,7 +72,6 @@ fi
 if [ "$WHAT" = full ]; then
   timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json | cut -c1-3000; tail -3 $OUT/bench_default.err
   timeout 600 python bench.py --full --host --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_host.json 2> $OUT/bench_host.err; cut -c1-600 $OUT/bench_host.json; tail -3 $OUT/bench_host.err
-  for m in 1 2; do ACX_STAGE=$m timeout 600 python bench.py --full --host --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_host_stage$m.json 2> $OUT/bench_host_stage$m.err; echo "ACX_STAGE=$m"; cut -c1-200 $OUT/bench_host_stage$m.json; done
   timeout 900 python bench.py --full --bytes 8589934592 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_8g.json 2> $OUT/bench_8g.err; cut -c1-400 $OUT/bench_8g.json; tail -3 $OUT/bench_8g.err
 fi
 if [ "$WHAT" = k1a ]; then
