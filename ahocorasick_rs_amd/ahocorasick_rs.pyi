@@ -36,6 +36,10 @@ class AhoCorasick:
     def find_matches_as_indexes_batch(
         self, haystacks: Sequence[str], overlapping: bool = False, devices: Optional[Sequence[int]] = None
     ) -> list[list[tuple[int, int, int]]]: ...
+    def replace_all(self, haystack: str, replace_with: Iterable[str]) -> str: ...
+    def replace_all_batch(self, haystacks: Sequence[str], replace_with: Iterable[str]) -> list[str]: ...
+    def replace_all(self, haystack: str, replace_with: Iterable[str]) -> str: ...
+    def replace_all_batch(self, haystacks: Sequence[str], replace_with: Iterable[str]) -> list[str]: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -51,4 +55,8 @@ class BytesAhoCorasick:
     def find_matches_as_indexes_batch(
         self, haystacks: Sequence[Buffer], overlapping: bool = False, devices: Optional[Sequence[int]] = None
     ) -> list[list[tuple[int, int, int]]]: ...
+    def replace_all(self, haystack: Buffer, replace_with: Iterable[Buffer]) -> bytes: ...
+    def replace_all_batch(self, haystacks: Sequence[Buffer], replace_with: Iterable[Buffer]) -> list[bytes]: ...
+    def replace_all(self, haystack: Buffer, replace_with: Iterable[Buffer]) -> bytes: ...
+    def replace_all_batch(self, haystacks: Sequence[Buffer], replace_with: Iterable[Buffer]) -> list[bytes]: ...
     def _info(self) -> dict[str, Any]: ...

@@ -26,7 +26,7 @@ MATCH_STANDARD, MATCH_LEFTMOST_FIRST, MATCH_LEFTMOST_LONGEST = 0, 1, 2
 IMPL_AUTO, IMPL_NONCONTIGUOUS_NFA, IMPL_CONTIGUOUS_NFA, IMPL_DFA = -1, 0, 1, 2
 KERNEL_AUTO, KERNEL_DFA_WALK, KERNEL_PREFILTER = 0, 1, 2
 KERNEL_NAMES = {1: "dfa_walk", 2: "prefilter"}
-ABI_VERSION = 9  # ACX_VERSION of include/acx.h this binding was written against
+ABI_VERSION = 10  # ACX_VERSION of include/acx.h this binding was written against
 
 MATCH_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u8"), ("end", "<u8")])
 
@@ -159,6 +159,17 @@ def lib() -> ctypes.CDLL:
     L.acx_output_offsets.argtypes = [vp, i32, vp]
     L.acx_output_offsets.restype = None
     L.acx_generate_haystack.argtypes = [vp, vp, u64, i32, u64, u64]
+    L.acx_replace.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, ctypes.POINTER(vp)]
+    L.acx_replace_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, vp, u64, ctypes.POINTER(vp)]
+    L.acx_replaced_len.argtypes = [vp]
+    L.acx_replaced_len.restype = u64
+    L.acx_replaced_offsets.argtypes = [vp, vp]
+    L.acx_replaced_copy.argtypes = [vp, vp]
+    L.acx_replaced_device_bytes.argtypes = [vp]
+    L.acx_replaced_device_bytes.restype = vp
+    L.acx_free_replaced.argtypes = [vp]
+    L.acx_free_replaced.restype = None
+    L.acx_splice_host.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, ctypes.POINTER(u64)]
     _lib = L
     return L
 
@@ -426,6 +437,65 @@ class DeviceResult:
             pass
 
 
+class DeviceReplaced:
+    """The output of Automaton.replace_device, resident in HBM (acx_replaced_t)."""
+
+    def __init__(self, handle: int, n_hay: int):
+        self._h = handle
+        self.n_hay = n_hay
+
+    @property
+    def nbytes(self) -> int:
+        return int(lib().acx_replaced_len(self._h))
+
+    @property
+    def device_ptr(self) -> int:
+        """the output bytes in HBM (waits for the splice)"""
+        return lib().acx_replaced_device_bytes(self._h) or 0
+
+    def offsets(self) -> np.ndarray:
+        """every haystack's output bounds (n_hay + 1 entries; one haystack: [0, nbytes])"""
+        out = np.zeros(max(self.n_hay, 1) + 1, dtype=np.uint64)
+        _check(lib().acx_replaced_offsets(self._h, out.ctypes.data))
+        return out
+
+    def download(self) -> bytes:
+        return _replaced_bytes(self._h)
+
+    def free(self) -> None:
+        if self._h:
+            lib().acx_free_replaced(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _replaced_bytes(h: int) -> bytes:
+    buf = bytearray(int(lib().acx_replaced_len(h)))
+    if buf:
+        _check(lib().acx_replaced_copy(h, (ctypes.c_uint8 * len(buf)).from_buffer(buf)))
+    return bytes(buf)
+
+
+def splice_host(hay, matches, replace_with: Sequence[bytes]) -> bytes:
+    """acx_splice_host: `hay` with every match (pattern, start, end) replaced by replace_with[pattern] -- on the host,
+    no device involved.  ValueError (code EINVAL) for unsorted, overlapping or out-of-range matches."""
+    h = np.frombuffer(bytes(hay), dtype=np.uint8)
+    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+    blob, off = pack(replace_with)
+    n = ctypes.c_uint64()
+    args = (h.ctypes.data if h.size else None, h.size, m.ctypes.data if len(m) else None, len(m),
+            blob.ctypes.data, off.ctypes.data, len(replace_with))
+    _check(lib().acx_splice_host(*args, None, ctypes.byref(n)))
+    out = np.empty(int(n.value) + 1, dtype=np.uint8)
+    _check(lib().acx_splice_host(*args, out.ctypes.data, ctypes.byref(n)))
+    return out[:int(n.value)].tobytes()
+
+
 def _take_matches(ptr: Optional[int], n: int) -> np.ndarray:
     """The library-owned host array of an acx_find* call as a numpy structured array, without a
     copy (a large result sits in pinned host memory): acx_free_matches runs when the array and
@@ -530,6 +600,43 @@ class Automaton:
                                      ctypes.byref(out)))
         return DeviceResult(out.value, n_hay if (uniform_len or d_offsets) else 0)
 
+    # ---- replacement (acx_replace / acx_replace_device)
+    def replace(self, hay, replace_with: Sequence[bytes]) -> bytes:
+        """every non-overlapping match of `hay` replaced by replace_with[pattern]"""
+        a = np.ascontiguousarray(np.frombuffer(hay, dtype=np.uint8) if not isinstance(hay, np.ndarray) else hay)
+        blob, off = pack(replace_with)
+        out = ctypes.c_void_p()
+        _check(lib().acx_replace(self._h, a.ctypes.data if a.size else None, a.size, None, 0, blob.ctypes.data,
+                                 off.ctypes.data, len(replace_with), ctypes.byref(out)))
+        try:
+            return _replaced_bytes(out.value)
+        finally:
+            lib().acx_free_replaced(out.value)
+
+    def replace_batch(self, haystacks: Sequence[bytes], replace_with: Sequence[bytes]) -> List[bytes]:
+        """[self.replace(h, replace_with) for h in haystacks] in one call"""
+        hb, hoff = pack(haystacks)
+        blob, off = pack(replace_with)
+        out = ctypes.c_void_p()
+        _check(lib().acx_replace(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks),
+                                 blob.ctypes.data, off.ctypes.data, len(replace_with), ctypes.byref(out)))
+        try:
+            whole = _replaced_bytes(out.value)
+            bounds = np.zeros(len(haystacks) + 1, dtype=np.uint64)
+            _check(lib().acx_replaced_offsets(out.value, bounds.ctypes.data))
+        finally:
+            lib().acx_free_replaced(out.value)
+        return [whole[int(bounds[i]):int(bounds[i + 1])] for i in range(len(haystacks))]
+
+    def replace_device(self, d_ptr: int, nbytes: int, replace_with: Sequence[bytes], *, d_offsets: int = 0,
+                       n_hay: int = 0, uniform_len: int = 0) -> DeviceReplaced:
+        """the haystack in HBM searched and spliced there; the output stays in HBM"""
+        blob, off = pack(replace_with)
+        out = ctypes.c_void_p()
+        _check(lib().acx_replace_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, blob.ctypes.data,
+                                        off.ctypes.data, len(replace_with), ctypes.byref(out)))
+        return DeviceReplaced(out.value, n_hay if (uniform_len or d_offsets) else 1)
+
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:
         _check(lib().acx_generate_haystack(self._h, d_ptr, nbytes, kind, seed, stream_offset))
@@ -539,11 +646,13 @@ class Automaton:
         """True / 1: time every call's scan kernel; N > 1: every N-th call; False / 0: off."""
         _check(lib().acx_profile_enable(self._h, int(on)))
 
-    PATH_STATS = ("sparse", "hot_calls", "hot_groups", "overflow_hits", "dense_tiles", "dense_radix", "overflow_regrown", "k0", "byte_ranges", "wide_redone", "resident_launches", "in_place")
+    PATH_STATS = ("sparse", "hot_calls", "hot_groups", "overflow_hits", "dense_tiles", "dense_radix", "overflow_regrown", "k0", "byte_ranges", "wide_redone", "resident_launches", "in_place",
+                  "replaced_on_device")
 
     def path_stats(self, reset: bool = True) -> dict:
         """which way this handle's calls went (acx_path_stats): {sparse, hot_calls, hot_groups, overflow_hits,
-        dense_tiles, dense_radix, overflow_regrown, k0, byte_ranges, wide_redone, resident_launches, in_place}"""
+        dense_tiles, dense_radix, overflow_regrown, k0, byte_ranges, wide_redone, resident_launches, in_place,
+        replaced_on_device}"""
         out = (ctypes.c_uint64 * len(self.PATH_STATS))()
         _check(lib().acx_path_stats(self._h, out, int(reset)))
         return dict(zip(self.PATH_STATS, [int(v) for v in out]))

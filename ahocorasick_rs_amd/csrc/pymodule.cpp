@@ -407,6 +407,115 @@ bool str_view(PyObject *hay, const char **s, Py_ssize_t *len) {
     return *s != nullptr;
 }
 
+// ---------------------------------------------------------------------------
+// replace_all (the crate's AhoCorasick::replace_all / replace_all_bytes; the reference binding stops at finding)
+// ---------------------------------------------------------------------------
+// replace_with -> blob + offsets (materialised once per call): str items as UTF-8 (utf8) or buffers
+bool replacements(PyObject *replace_with, bool utf8, std::vector<uint8_t> *blob, std::vector<uint64_t> *off) {
+    PyObject *iter = PyObject_GetIter(replace_with);
+    if (!iter) return false;
+    off->assign(1, 0);
+    PyObject *item;
+    while ((item = PyIter_Next(iter))) {
+        if (utf8) {
+            if (!PyUnicode_Check(item)) {
+                PyErr_Format(PyExc_TypeError, "argument 'replace_with': '%.100s' object cannot be converted to 'PyString'",
+                             Py_TYPE(item)->tp_name);
+                Py_DECREF(item); Py_DECREF(iter); return false;
+            }
+            Py_ssize_t len;
+            const char *s = PyUnicode_AsUTF8AndSize(item, &len);
+            if (!s) { Py_DECREF(item); Py_DECREF(iter); return false; }
+            blob->insert(blob->end(), s, s + len);
+        } else {
+            Py_buffer v;
+            if (!get_bytes_view(item, &v)) { Py_DECREF(item); Py_DECREF(iter); return false; }
+            blob->insert(blob->end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
+            PyBuffer_Release(&v);
+        }
+        off->push_back(blob->size());
+        Py_DECREF(item);
+    }
+    Py_DECREF(iter);
+    blob->push_back(0);
+    return !PyErr_Occurred();
+}
+
+// a finished acx_replace -> bytes (allocated at its final size, the library copies straight into it) or, utf8, str.
+// Frees r.  bounds != null: the haystacks' output offsets (n_hay + 1) are written there.
+PyObject *replaced_result(acx_replaced_t *r, bool utf8, std::vector<uint64_t> *bounds = nullptr) {
+    const uint64_t n = acx_replaced_len(r);
+    if (bounds && acx_replaced_offsets(r, bounds->data()) != ACX_OK) { acx_free_replaced(r); return raise_acx(ACX_EINVAL); }
+    PyObject *b = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)n);
+    if (!b) { acx_free_replaced(r); return nullptr; }
+    int rc;
+    char *dst = PyBytes_AS_STRING(b);
+    Py_BEGIN_ALLOW_THREADS
+    rc = acx_replaced_copy(r, dst);
+    acx_free_replaced(r);
+    Py_END_ALLOW_THREADS
+    if (rc != ACX_OK) { Py_DECREF(b); return raise_acx(rc); }
+    if (!utf8) return b;
+    PyObject *s = PyUnicode_DecodeUTF8(dst, (Py_ssize_t)n, "strict");
+    Py_DECREF(b);
+    return s;
+}
+
+// one host haystack (or a batch: offsets != null) -> acx_replace with the GIL released
+int replace_nogil(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
+                  const std::vector<uint8_t> &blob, const std::vector<uint64_t> &off, acx_replaced_t **out) {
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = acx_replace(a, hay, len, offsets, n_hay, blob.data(), off.data(), off.size() - 1, out);
+    Py_END_ALLOW_THREADS
+    return rc;
+}
+
+// replace_all_batch of both classes: list[str] / list[bytes], [replace_all(h, replace_with) for h in haystacks]
+PyObject *replace_batch_impl(acx_automaton_t *a, PyObject *haystacks, PyObject *replace_with, bool utf8) {
+    PyObject *seq = PySequence_Fast(haystacks, "haystacks must be a sequence");
+    if (!seq) return nullptr;
+    const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
+    std::vector<uint64_t> hoff((size_t)n + 1, 0);
+    std::vector<uint8_t> hblob;
+    for (Py_ssize_t i = 0; i < n; i++) {
+        PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
+        if (utf8) {
+            const char *s; Py_ssize_t len;
+            if (!str_view(it, &s, &len)) { Py_DECREF(seq); return nullptr; }
+            hblob.insert(hblob.end(), s, s + len);
+        } else {
+            Py_buffer v;
+            if (!get_bytes_view(it, &v)) { Py_DECREF(seq); return nullptr; }
+            hblob.insert(hblob.end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
+            PyBuffer_Release(&v);
+        }
+        hoff[(size_t)i + 1] = hblob.size();
+    }
+    Py_DECREF(seq);
+    std::vector<uint8_t> blob;
+    std::vector<uint64_t> off;
+    if (!replacements(replace_with, utf8, &blob, &off)) return nullptr;
+    hblob.push_back(0);
+    acx_replaced_t *r = nullptr;
+    const int rc = replace_nogil(a, hblob.data(), hoff[(size_t)n], hoff.data(), (uint64_t)n, blob, off, &r);
+    if (rc != ACX_OK) return raise_acx(rc);
+    std::vector<uint64_t> bounds((size_t)n + 1, 0);
+    PyObject *whole = replaced_result(r, false, &bounds);
+    if (!whole) return nullptr;
+    const char *w = PyBytes_AS_STRING(whole);
+    PyObject *list = PyList_New(n);
+    for (Py_ssize_t i = 0; list && i < n; i++) {
+        const char *p = w + bounds[(size_t)i];
+        const Py_ssize_t len = (Py_ssize_t)(bounds[(size_t)i + 1] - bounds[(size_t)i]);
+        PyObject *item = utf8 ? PyUnicode_DecodeUTF8(p, len, "strict") : PyBytes_FromStringAndSize(p, len);
+        if (!item) { Py_CLEAR(list); break; }
+        PyList_SET_ITEM(list, i, item);
+    }
+    Py_DECREF(whole);
+    return list;
+}
+
 // src/lib.rs:229-249: code-point offsets
 PyObject *ac_find_indexes(PyObject *self_, PyObject *args, PyObject *kwargs) {
     AcObject *self = reinterpret_cast<AcObject *>(self_);
@@ -463,6 +572,29 @@ PyObject *ac_find_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
     return find_batch_impl(self->ac, hs, overlapping, true, devs, &self->replicas);
 }
 
+PyObject *ac_replace_all(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    static const char *kw[] = {"haystack", "replace_with", nullptr};
+    PyObject *hay, *rw;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "OO:replace_all", const_cast<char **>(kw), &hay, &rw)) return nullptr;
+    const char *s; Py_ssize_t len;
+    if (!str_view(hay, &s, &len)) return nullptr;
+    std::vector<uint8_t> blob;
+    std::vector<uint64_t> off;
+    if (!replacements(rw, true, &blob, &off)) return nullptr;
+    acx_replaced_t *r = nullptr;
+    const int rc = replace_nogil(reinterpret_cast<AcObject *>(self_)->ac, reinterpret_cast<const uint8_t *>(s),
+                                 (uint64_t)len, nullptr, 0, blob, off, &r);
+    if (rc != ACX_OK) return raise_acx(rc);
+    return replaced_result(r, true);
+}
+
+PyObject *ac_replace_all_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    static const char *kw[] = {"haystacks", "replace_with", nullptr};
+    PyObject *hs, *rw;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "OO:replace_all_batch", const_cast<char **>(kw), &hs, &rw)) return nullptr;
+    return replace_batch_impl(reinterpret_cast<AcObject *>(self_)->ac, hs, rw, true);
+}
+
 PyObject *ac_info(PyObject *self_, PyObject *) {
     return info_dict(reinterpret_cast<AcObject *>(self_)->ac);
 }
@@ -483,6 +615,11 @@ PyMethodDef ac_methods[] = {
      "[self.find_matches_as_indexes(h, overlapping) for h in haystacks].  devices=[ordinals]: the batch "
      "is cut into contiguous ranges of haystacks, one per device (replicas of the automaton are built on "
      "first use), scanned side by side from one host thread each."},
+    {"replace_all", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_replace_all)), METH_VARARGS | METH_KEYWORDS,
+     "[extension] the haystack with every non-overlapping match (as find_matches_as_indexes reports them) replaced by "
+     "replace_with[pattern index]; replace_with has one str per pattern (ValueError otherwise)."},
+    {"replace_all_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_replace_all_batch)),
+     METH_VARARGS | METH_KEYWORDS, "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
     {"_info", ac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -681,6 +818,49 @@ PyObject *bac_find_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
     return find_batch_impl(self->ac, hs, overlapping, false, devs, &self->replicas);
 }
 
+PyObject *bac_replace_all(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    static const char *kw[] = {"haystack", "replace_with", nullptr};
+    PyObject *hay, *rw;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "OO:replace_all", const_cast<char **>(kw), &hay, &rw)) return nullptr;
+    acx_automaton_t *a = reinterpret_cast<BacObject *>(self_)->ac;
+    std::vector<uint8_t> blob;
+    std::vector<uint64_t> off;
+    if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
+        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
+        PyObject *cap = dlpack_view(hay, acx_automaton_device(a), &p, &len, &on_device);
+        if (!cap) return nullptr;
+        if (!replacements(rw, false, &blob, &off)) { dlpack_release(cap); return nullptr; }
+        acx_replaced_t *r = nullptr;
+        int rc;
+        if (on_device) { // searched and spliced where it lies; only the output crosses to the host
+            Py_BEGIN_ALLOW_THREADS
+            rc = acx_device_synchronize_on(acx_automaton_device(a)); // (the producer's kernels may still write it)
+            if (rc == ACX_OK) rc = acx_replace_device(a, p, len, nullptr, 0, 0, blob.data(), off.data(), off.size() - 1, &r);
+            Py_END_ALLOW_THREADS
+        } else {
+            rc = replace_nogil(a, p, len, nullptr, 0, blob, off, &r);
+        }
+        PyObject *res = rc != ACX_OK ? raise_acx(rc) : replaced_result(r, false);
+        dlpack_release(cap);
+        return res;
+    }
+    Py_buffer v;
+    if (!get_bytes_view(hay, &v)) return nullptr;
+    if (!replacements(rw, false, &blob, &off)) { PyBuffer_Release(&v); return nullptr; }
+    acx_replaced_t *r = nullptr;
+    const int rc = replace_nogil(a, (const uint8_t *)v.buf, (uint64_t)v.len, nullptr, 0, blob, off, &r);
+    PyBuffer_Release(&v);
+    if (rc != ACX_OK) return raise_acx(rc);
+    return replaced_result(r, false);
+}
+
+PyObject *bac_replace_all_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    static const char *kw[] = {"haystacks", "replace_with", nullptr};
+    PyObject *hs, *rw;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "OO:replace_all_batch", const_cast<char **>(kw), &hs, &rw)) return nullptr;
+    return replace_batch_impl(reinterpret_cast<BacObject *>(self_)->ac, hs, rw, false);
+}
+
 PyObject *bac_info(PyObject *self_, PyObject *) {
     return info_dict(reinterpret_cast<BacObject *>(self_)->ac);
 }
@@ -697,6 +877,11 @@ PyMethodDef bac_methods[] = {
      "[self.find_matches_as_indexes(h, overlapping) for h in haystacks].  devices=[ordinals]: the batch "
      "is cut into contiguous ranges of haystacks, one per device (replicas of the automaton are built on "
      "first use), scanned side by side from one host thread each."},
+    {"replace_all", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(bac_replace_all)), METH_VARARGS | METH_KEYWORDS,
+     "[extension] the haystack (a buffer, or a __dlpack__ tensor on the automaton's device) as bytes with every "
+     "non-overlapping match replaced by replace_with[pattern index]; replace_with has one buffer per pattern."},
+    {"replace_all_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(bac_replace_all_batch)),
+     METH_VARARGS | METH_KEYWORDS, "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
     {"_info", bac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };

@@ -23,7 +23,8 @@
 extern "C" {
 #endif
 
-/* 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
+/* 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
+ * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
  * 7: acx_path_stats gained [8] (byte ranges of calls that were cut); K0's result line carries end - 1 and a hash of the
  *    matches beside it (round 5);
@@ -33,7 +34,7 @@ extern "C" {
  * 3: acx_replicate / acx_find_batch_multi / acx_shard_range / acx_automaton_device added (round 3);
  * 2: acx_prefix_slot gained `salt`, acx_host_tables_t grew (round 2).  A binding built against another
  * header must refuse to load: compare acx_version() with the ACX_VERSION it was compiled with. */
-#define ACX_VERSION 9
+#define ACX_VERSION 10
 
 /* status codes */
 #define ACX_OK 0
@@ -311,6 +312,35 @@ int acx_result_copy(const acx_result_t *r, acx_match_t *host_out);
 int acx_result_copy_counts(const acx_result_t *r, uint64_t *host_counts);
 void acx_free_result(acx_result_t *r);
 
+/* ---- replacement: the crate's AhoCorasick::replace_all / replace_all_bytes (a feature the reference binding does not
+ * expose).  For a haystack h, its NON-overlapping matches (p_i, s_i, e_i) in the order acx_find reports them and one
+ * replacement r[p] per pattern: out = h[0:s_0] + r[p_0] + h[e_0:s_1] + ... + r[p_last] + h[e_last:].  `repl_blob` +
+ * `repl_offsets[n_repl + 1]` delimit the replacements (host memory, uploaded per call); n_repl must equal the number of
+ * patterns (ACX_EINVAL otherwise).  Batches: offsets[n_hay + 1] (host) / d_offsets (device, from 0 to len) or uniform_len,
+ * as for acx_find_batch / acx_find_device; every haystack is replaced on its own, the outputs lie behind one another.
+ * Two routes: up to ACX_REPLACE_HOST_MAX bytes (default 1 MiB, read per call) acx_replace runs acx_find / acx_find_batch
+ * and splices on the host; beyond, and always for acx_replace_device, the haystack is searched and spliced in HBM
+ * (acx_path_stats [12]) and the output stays there until acx_replaced_copy moves it.  Outputs may exceed 2^32 bytes. */
+typedef struct acx_replaced acx_replaced_t;
+int acx_replace(acx_automaton_t *a, const uint8_t *hay, uint64_t len,
+                const uint64_t *offsets /* NULL: one haystack; else n_hay + 1 */, uint64_t n_hay,
+                const uint8_t *repl_blob, const uint64_t *repl_offsets, uint64_t n_repl,
+                acx_replaced_t **out);
+int acx_replace_device(acx_automaton_t *a, const void *d_hay, uint64_t len,
+                       const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
+                       const uint8_t *repl_blob, const uint64_t *repl_offsets, uint64_t n_repl,
+                       acx_replaced_t **out);                 /* output stays in HBM */
+uint64_t acx_replaced_len(const acx_replaced_t *r);           /* total output bytes (known when the call returns) */
+int acx_replaced_offsets(const acx_replaced_t *r, uint64_t *host_offsets /* n_hay + 1 */);
+int acx_replaced_copy(const acx_replaced_t *r, void *host_dst); /* waits for the device's splice */
+const void *acx_replaced_device_bytes(const acx_replaced_t *r); /* NULL if spliced on the host */
+void acx_free_replaced(acx_replaced_t *r);
+/* host only, no device: the splice itself (the host route).  ACX_EINVAL when the matches are unsorted, overlap, lie
+ * beyond the haystack or name a pattern >= n_repl. */
+int acx_splice_host(const uint8_t *hay, uint64_t len, const acx_match_t *m, uint64_t n_m,
+                    const uint8_t *repl_blob, const uint64_t *repl_offsets, uint64_t n_repl,
+                    uint8_t *dst /* NULL: size only */, uint64_t *dst_len);
+
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
  * a context does (the pair costs the dispatch ~6 us: a sampled measurement leaves the other calls
@@ -327,8 +357,8 @@ int acx_profile_read(acx_automaton_t *a, acx_profile_t *out, int reset);
  * [10] launches of a context's RESIDENT K0 (acx_find on short haystacks: one workgroup stays on the device between the
  * calls of a loop and is fed through pinned host memory -- [7] counts the calls, [10] the launches they cost), [11] calls
  * of acx_find whose haystack (beyond K0's sizes, up to 1 MiB) the scan read IN PLACE from pinned host memory instead of
- * a copy in HBM.  reset != 0 clears the counters. */
-#define ACX_PATH_STATS 12
+ * a copy in HBM, [12] calls of acx_replace / acx_replace_device spliced on the device.  reset != 0 clears the counters. */
+#define ACX_PATH_STATS 13
 int acx_path_stats(acx_automaton_t *a, uint64_t out[ACX_PATH_STATS], int reset);
 
 /* ---- device memory helpers so that a host without torch can stage data ---- */
