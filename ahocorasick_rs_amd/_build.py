@@ -23,8 +23,8 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(HERE, "libacx_hip.so")
 EXT = os.path.join(HERE, "ahocorasick_rs" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 
-LIB_SOURCES = ["kernels.hip", "replace.hip", "acx_api.cpp", "automaton.cpp", "comm.cpp"]
-LIB_HEADERS = ["kernels.hpp", "replace.hpp", "automaton.hpp", "device_types.hpp", os.path.join(INCLUDE, "acx.h")]
+LIB_SOURCES = ["kernels.hip", "replace.hip", "fold.hip", "acx_api.cpp", "automaton.cpp", "comm.cpp"]
+LIB_HEADERS = ["kernels.hpp", "replace.hpp", "fold.hpp", "automaton.hpp", "device_types.hpp", os.path.join(INCLUDE, "acx.h")]
 EXT_SOURCES = ["pymodule.cpp"]
 
 

@@ -25,6 +25,7 @@ class AhoCorasick:
         matchkind: MatchKind = MatchKind.Standard,
         store_patterns: Optional[bool] = None,
         implementation: Optional[Implementation] = None,
+        ascii_case_insensitive: bool = False,
     ) -> None: ...
     def find_matches_as_indexes(
         self, haystack: str, overlapping: bool = False
@@ -38,8 +39,6 @@ class AhoCorasick:
     ) -> list[list[tuple[int, int, int]]]: ...
     def replace_all(self, haystack: str, replace_with: Iterable[str]) -> str: ...
     def replace_all_batch(self, haystacks: Sequence[str], replace_with: Iterable[str]) -> list[str]: ...
-    def replace_all(self, haystack: str, replace_with: Iterable[str]) -> str: ...
-    def replace_all_batch(self, haystacks: Sequence[str], replace_with: Iterable[str]) -> list[str]: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -48,6 +47,7 @@ class BytesAhoCorasick:
         patterns: Iterable[Buffer],
         matchkind: MatchKind = MatchKind.Standard,
         implementation: Optional[Implementation] = None,
+        ascii_case_insensitive: bool = False,
     ) -> None: ...
     def find_matches_as_indexes(
         self, haystack: Buffer, overlapping: bool = False
@@ -55,8 +55,6 @@ class BytesAhoCorasick:
     def find_matches_as_indexes_batch(
         self, haystacks: Sequence[Buffer], overlapping: bool = False, devices: Optional[Sequence[int]] = None
     ) -> list[list[tuple[int, int, int]]]: ...
-    def replace_all(self, haystack: Buffer, replace_with: Iterable[Buffer]) -> bytes: ...
-    def replace_all_batch(self, haystacks: Sequence[Buffer], replace_with: Iterable[Buffer]) -> list[bytes]: ...
     def replace_all(self, haystack: Buffer, replace_with: Iterable[Buffer]) -> bytes: ...
     def replace_all_batch(self, haystacks: Sequence[Buffer], replace_with: Iterable[Buffer]) -> list[bytes]: ...
     def _info(self) -> dict[str, Any]: ...

@@ -26,7 +26,8 @@ MATCH_STANDARD, MATCH_LEFTMOST_FIRST, MATCH_LEFTMOST_LONGEST = 0, 1, 2
 IMPL_AUTO, IMPL_NONCONTIGUOUS_NFA, IMPL_CONTIGUOUS_NFA, IMPL_DFA = -1, 0, 1, 2
 KERNEL_AUTO, KERNEL_DFA_WALK, KERNEL_PREFILTER = 0, 1, 2
 KERNEL_NAMES = {1: "dfa_walk", 2: "prefilter"}
-ABI_VERSION = 10  # ACX_VERSION of include/acx.h this binding was written against
+BUILD_ASCII_CASE_INSENSITIVE = 1  # build flag (acx_build_ex)
+ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
 MATCH_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u8"), ("end", "<u8")])
 
@@ -37,7 +38,7 @@ class Info(ctypes.Structure):
                 ("min_pattern_len", ctypes.c_uint32), ("max_pattern_len", ctypes.c_uint32),
                 ("table_bytes", ctypes.c_uint64), ("lds_hot_rows", ctypes.c_uint32),
                 ("kernel", ctypes.c_int32), ("match_kind", ctypes.c_int32),
-                ("device", ctypes.c_int32), ("filter_q", ctypes.c_uint32)]
+                ("device", ctypes.c_int32), ("filter_q", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
 class HostTables(ctypes.Structure):
@@ -106,11 +107,13 @@ def lib() -> ctypes.CDLL:
     L.acx_device_count.argtypes = [ctypes.POINTER(i32)]
     L.acx_set_device.argtypes = [i32]
     L.acx_build.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(vp)]
+    L.acx_build_ex.argtypes = [vp, vp, u64, i32, i32, ctypes.c_uint32, ctypes.POINTER(vp)]
     L.acx_free_automaton.argtypes = [vp]
     L.acx_free_automaton.restype = None
     L.acx_automaton_info.argtypes = [vp, ctypes.POINTER(Info)]
     L.acx_set_kernel.argtypes = [vp, i32]
     L.acx_compile_host.argtypes = [vp, vp, u64, i32, ctypes.POINTER(vp)]
+    L.acx_compile_host_ex.argtypes = [vp, vp, u64, i32, ctypes.c_uint32, ctypes.POINTER(vp)]
     L.acx_host_tables.argtypes = [vp, ctypes.POINTER(HostTables)]
     L.acx_filter_hash.argtypes = [ctypes.c_uint32]
     L.acx_filter_hash.restype = ctypes.c_uint32
@@ -221,11 +224,11 @@ class HostAutomaton:
     """acx_host_automaton_t: the compiled tables on the host (no device needed).
     Arrays are numpy views valid while this object is alive."""
 
-    def __init__(self, patterns: Sequence[bytes], match_kind: int = MATCH_STANDARD):
+    def __init__(self, patterns: Sequence[bytes], match_kind: int = MATCH_STANDARD, flags: int = 0):
         blob, off = pack(patterns)
         h = ctypes.c_void_p()
-        _check(lib().acx_compile_host(blob.ctypes.data, off.ctypes.data, len(patterns),
-                                      match_kind, ctypes.byref(h)))
+        _check(lib().acx_compile_host_ex(blob.ctypes.data, off.ctypes.data, len(patterns),
+                                         match_kind, flags, ctypes.byref(h)))
         self._h = h.value
         t = HostTables()
         _check(lib().acx_host_tables(self._h, ctypes.byref(t)))
@@ -511,11 +514,12 @@ class Automaton:
     """acx_automaton_t: compiled patterns + device tables."""
 
     def __init__(self, patterns: Sequence[bytes], match_kind: int = MATCH_STANDARD,
-                 implementation: int = IMPL_AUTO, kernel: Optional[int] = None):
+                 implementation: int = IMPL_AUTO, kernel: Optional[int] = None, ascii_case_insensitive: bool = False):
         blob, off = pack(patterns)
         h = ctypes.c_void_p()
-        _check(lib().acx_build(blob.ctypes.data, off.ctypes.data, len(patterns), match_kind,
-                               implementation, ctypes.byref(h)))
+        flags = BUILD_ASCII_CASE_INSENSITIVE if ascii_case_insensitive else 0
+        _check(lib().acx_build_ex(blob.ctypes.data, off.ctypes.data, len(patterns), match_kind,
+                                  implementation, flags, ctypes.byref(h)))
         self._h = h.value
         if kernel is not None:
             self.set_kernel(kernel)
@@ -647,12 +651,12 @@ class Automaton:
         _check(lib().acx_profile_enable(self._h, int(on)))
 
     PATH_STATS = ("sparse", "hot_calls", "hot_groups", "overflow_hits", "dense_tiles", "dense_radix", "overflow_regrown", "k0", "byte_ranges", "wide_redone", "resident_launches", "in_place",
-                  "replaced_on_device")
+                  "replaced_on_device", "folded_on_device")
 
     def path_stats(self, reset: bool = True) -> dict:
         """which way this handle's calls went (acx_path_stats): {sparse, hot_calls, hot_groups, overflow_hits,
         dense_tiles, dense_radix, overflow_regrown, k0, byte_ranges, wide_redone, resident_launches, in_place,
-        replaced_on_device}"""
+        replaced_on_device, folded_on_device}"""
         out = (ctypes.c_uint64 * len(self.PATH_STATS))()
         _check(lib().acx_path_stats(self._h, out, int(reset)))
         return dict(zip(self.PATH_STATS, [int(v) for v in out]))

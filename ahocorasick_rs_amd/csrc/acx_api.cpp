@@ -30,6 +30,7 @@
 #include "../../include/acx.h"
 #include "automaton.hpp"
 #include "kernels.hpp"
+#include "fold.hpp"
 #include "replace.hpp"
 
 using namespace acx;
@@ -340,6 +341,8 @@ struct Workspace {
     uint64_t final_cap = 0;
     uint8_t *hay = nullptr;           // device staging buffer of the host-memory entry points
     uint64_t hay_cap = 0;
+    uint8_t *fold = nullptr;          // case-insensitive handles: the folded copy of a device haystack (grow-only: as large as
+    uint64_t fold_cap = 0;            //   the largest device haystack of the context)
     uint64_t *offsets = nullptr;
     uint64_t offsets_cap = 0;
 };
@@ -429,6 +432,7 @@ struct acx_automaton {
     std::vector<void *> allocs;
     int kernel = ACX_KERNEL_DFA_WALK;
     int implementation = ACX_IMPL_AUTO; // the caller's hint (replicas are built with the same one)
+    uint32_t flags = 0;                 // ACX_BUILD_* (acx_build_ex; replicas are built with the same ones)
     int n_cus = 1;
     size_t max_lds = 65536;
     uint64_t table_bytes = 0;
@@ -477,6 +481,14 @@ struct acx_replaced {
 };
 
 namespace {
+
+// A case-insensitive handle (acx_build_ex): compiled from the folded patterns, it searches folded haystacks (fold.hpp).
+inline bool folds(const acx_automaton *a) { return (a->flags & ACX_BUILD_ASCII_CASE_INSENSITIVE) != 0; }
+// the calling thread's copy of a host haystack into pinned memory the device reads: a folding copy for such a handle
+inline void copy_in(const acx_automaton *a, uint8_t *dst, const uint8_t *src, uint64_t len) {
+    if (folds(a)) fold_host(dst, src, len);
+    else std::memcpy(dst, src, len);
+}
 
 // the result's buffers are complete after this
 int result_wait(const acx_result *r) {
@@ -529,7 +541,7 @@ void free_ws(Workspace &w, int device) {
     free_tiles(w);
     g_bufs.put(w.final, device);
     (void)hipFree(w.blockcnt); (void)hipFree(w.blockpre); (void)hipFree(w.blocksub);
-    (void)hipFree(w.hay); (void)hipFree(w.offsets);
+    (void)hipFree(w.hay); (void)hipFree(w.offsets); (void)hipFree(w.fold);
     if (w.h_pinned) (void)hipHostFree(w.h_pinned);
     if (w.pin_final) (void)hipHostFree(w.pin_final);
     if (w.mailbox) (void)hipHostFree(w.mailbox);
@@ -1019,10 +1031,13 @@ int run_resident(acx_automaton *a, Ctx *c, const uint8_t *hay, uint64_t len, int
         rc = launch();
         if (rc) return rc;
     }
-    // (nothing between the three writes: a poll that reads the mailbox while they are under way fails its check and reads again)
-    const uint64_t check = k0_hay_check(hay, (uint32_t)len, seq, R.secret), word = k0_mailbox_word(seq, (uint32_t)len, codepoints != 0, false);
-    std::memcpy(w.pin_hay, hay, len);
+    // (nothing between the three writes: a poll that reads the mailbox while they are under way fails its check and reads again;
+    // the check is of the bytes the kernel reads -- for a case-insensitive handle the folded copy, hashed behind the copy)
+    const uint64_t word = k0_mailbox_word(seq, (uint32_t)len, codepoints != 0, false);
+    uint64_t check = folds(a) ? 0 : k0_hay_check(hay, (uint32_t)len, seq, R.secret);
+    copy_in(a, w.pin_hay, hay, len);
     std::memset(w.pin_hay + len, 0, (16 - (len & 15)) & 15); // (the check covers whole 16-byte pieces)
+    if (folds(a)) check = k0_hay_check(w.pin_hay, (uint32_t)len, seq, R.secret);
     w.mailbox[1] = check;
     __atomic_store_n(w.mailbox, word, __ATOMIC_RELEASE);
     // the result line, as run_small waits for it -- and the kernel's epoch: a kernel that has left (idle, end of its life)
@@ -2027,11 +2042,12 @@ int run_chunked(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, in
 // One hipMemcpyAsync from the caller's (pageable) memory, queued ahead of the scan.  The runtime's own pageable copy
 // moves 54 GB/s on the MI355X, the link's rate: pinning the caller's pages for the call (55 GB/s, synchronised) and a
 // ring of pinned chunks filled by host threads (51 GB/s) were measured and retired (DESIGN_HISTORY.md section 5).
+// A case-insensitive handle's haystack is folded in place behind the copy, on the same stream -- unless the caller keeps
+// the original bytes there (fold_in_place = false: acx_replace's splice reads them) and folds a copy of its own.
 int stage_host(acx_automaton *a, Ctx *c, const uint8_t *hay, uint64_t len, const uint64_t *offsets,
-               uint64_t n_off) {
+               uint64_t n_off, bool fold_in_place = true) {
     Workspace &w = c->ws;
     hipStream_t st = c->stream;
-    (void)a;
     if (len > w.hay_cap) {
         HIPCHK(hipStreamSynchronize(st));
         (void)hipFree(w.hay); w.hay = nullptr; w.hay_cap = 0;
@@ -2049,6 +2065,30 @@ int stage_host(acx_automaton *a, Ctx *c, const uint8_t *hay, uint64_t len, const
         HIPCHK(hipMemcpyAsync(w.offsets, offsets, n_off * 8, hipMemcpyHostToDevice, st));
     }
     if (len) HIPCHK(hipMemcpyAsync(w.hay, hay, len, hipMemcpyHostToDevice, st));
+    if (len && fold_in_place && folds(a)) {
+        HIPCHK(fold_device(w.hay, w.hay, len, a->n_cus, st));
+        a->path[13]++;
+    }
+    return ACX_OK;
+}
+
+// A case-insensitive handle's device haystack: folded into the context's grow-only buffer on its stream, at the same address
+// modulo 16 (the caller's memory is never written); *d_search = what the find reads.  Other handles search d_hay itself.
+int fold_copy(acx_automaton *a, Ctx *c, const uint8_t *d_hay, uint64_t len, const uint8_t **d_search) {
+    *d_search = d_hay;
+    if (!folds(a) || !len) return ACX_OK;
+    Workspace &w = c->ws;
+    const uint64_t shift = (uintptr_t)d_hay & 15;
+    if (shift + len > w.fold_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream)); // (the kernels of an earlier call may still read the old buffer)
+        (void)hipFree(w.fold); w.fold = nullptr; w.fold_cap = 0;
+        const uint64_t cap = (shift + len + 4095) & ~4095ull;
+        HIPCHK(hipMalloc((void **)&w.fold, cap));
+        w.fold_cap = cap;
+    }
+    HIPCHK(fold_device(d_hay, w.fold + shift, len, a->n_cus, c->stream));
+    a->path[13]++;
+    *d_search = w.fold + shift;
     return ACX_OK;
 }
 
@@ -2076,10 +2116,11 @@ int download_matches(const acx_result *r, acx_match_t **out, uint64_t *n_out) {
 
 // The device route of a replacement (replace.hpp): the find pipeline as acx_find_device runs it (byte ranges and batch
 // splits included), then the splice on the same stream -- the kernels follow the find's write kernel in stream order.
-// Returns when the output's length is known; the gather may still run (out->done).  d_hay / G.offsets must stay valid
-// until then.
-int run_replace(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, const uint8_t *repl_blob,
-                const uint64_t *repl_offsets, uint64_t n_repl, acx_replaced **out) {
+// Returns when the output's length is known; the gather may still run (out->done).  d_hay: the bytes the find reads (a
+// case-insensitive handle's folded copy), d_orig: the caller's bytes the splice takes; they, and G.offsets, must stay
+// valid until then.
+int run_replace(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_orig, uint64_t len, const Segments &G,
+                const uint8_t *repl_blob, const uint64_t *repl_offsets, uint64_t n_repl, acx_replaced **out) {
     *out = nullptr;
     acx_result *r = nullptr;
     int rc = run_find(a, x, d_hay, len, G, 0, 0, &r, true, false);
@@ -2125,10 +2166,10 @@ int run_replace(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, co
         R->len = R->offsets[n_hay];
         HIPCHK(g_bufs.get((void **)&R->d_out, std::max<uint64_t>((R->len + 15) / 16 * 16, 16), a->device));
         if (!n) { // nothing matched: the output is the input
-            if (len) HIPCHK(hipMemcpyAsync(R->d_out, d_hay, len, hipMemcpyDeviceToDevice, st));
+            if (len) HIPCHK(hipMemcpyAsync(R->d_out, d_orig, len, hipMemcpyDeviceToDevice, st));
         } else {
             HIPCHK(get((void **)&tiles, replace_tile_words(R->len) * 8));
-            HIPCHK(replace_gather(d_hay, len, r->d_matches, n, o, P, d_blob, blob_len + 32, d_roff, tiles, R->d_out, R->len, st));
+            HIPCHK(replace_gather(d_orig, len, r->d_matches, n, o, P, d_blob, blob_len + 32, d_roff, tiles, R->d_out, R->len, st));
         }
         R->done = g_events.get(a->device);
         if (!R->done) HIPCHK(hipStreamSynchronize(st));
@@ -2175,20 +2216,52 @@ int acx_set_device(int ordinal) {
     return ACX_OK;
 }
 
+} // extern "C"
+
+namespace {
+// ACX_BUILD_ASCII_CASE_INSENSITIVE: the pattern bytes folded into fb, fo the offsets rebased to it -- what the compiler reads
+// instead of the caller's (fold.hpp: the automaton of fold(P) is the crate's case-insensitive automaton of P).  false:
+// nothing to fold (no flag, no patterns, or offsets the compiler refuses anyway).
+bool fold_patterns(const uint8_t *blob, const uint64_t *offsets, uint64_t n, uint32_t flags, std::vector<uint8_t> &fb,
+                   std::vector<uint64_t> &fo) {
+    if (!(flags & ACX_BUILD_ASCII_CASE_INSENSITIVE) || !n) return false;
+    for (uint64_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) return false;
+    const uint64_t total = offsets[n] - offsets[0];
+    fb.assign(total + 1, 0);
+    if (total) fold_host(fb.data(), blob + offsets[0], total);
+    fo.resize(n + 1);
+    for (uint64_t i = 0; i <= n; i++) fo[i] = offsets[i] - offsets[0];
+    return true;
+}
+} // namespace
+
+extern "C" {
+
 int acx_build(const uint8_t *blob, const uint64_t *offsets, uint64_t n_patterns, int match_kind,
               int implementation, acx_automaton_t **out) {
+    return acx_build_ex(blob, offsets, n_patterns, match_kind, implementation, 0, out);
+}
+
+int acx_build_ex(const uint8_t *blob, const uint64_t *offsets, uint64_t n_patterns, int match_kind, int implementation,
+                 uint32_t flags, acx_automaton_t **out) {
     if (!out) return fail(ACX_EINVAL, "null output pointer");
     *out = nullptr;
+    if (flags & ~(uint32_t)ACX_BUILD_ASCII_CASE_INSENSITIVE) return fail(ACX_EINVAL, "unknown build flags");
     if (n_patterns && (!offsets || (!blob && offsets[n_patterns] != offsets[0])))
         return fail(ACX_EINVAL, "null pattern buffer");
     if (implementation < ACX_IMPL_AUTO || implementation > ACX_IMPL_DFA)
         return fail(ACX_EINVAL, "unknown implementation hint");
     acx_automaton *a = new (std::nothrow) acx_automaton();
     if (!a) return fail(ACX_ENOMEM, "out of memory");
+    a->flags = flags;
     static const uint64_t zero_off[1] = {0};
     int code = ACX_OK;
     std::string err;
     try {
+        std::vector<uint8_t> fb;
+        std::vector<uint64_t> fo;
+        if (fold_patterns(blob, offsets, n_patterns, flags, fb, fo)) { blob = fb.data(); offsets = fo.data(); }
         // implementation=DFA asks for the dense table outright (the reference's DFA, README.md:173-177,
         // has no size limit either): keep it up to 16 GiB of the 288 GB
         err = compile(blob, n_patterns ? offsets : zero_off, n_patterns, match_kind, a->host, code,
@@ -2438,8 +2511,14 @@ int acx_build(const uint8_t *blob, const uint64_t *offsets, uint64_t n_patterns,
 
 int acx_compile_host(const uint8_t *blob, const uint64_t *offsets, uint64_t n_patterns,
                      int match_kind, acx_host_automaton_t **out) {
+    return acx_compile_host_ex(blob, offsets, n_patterns, match_kind, 0, out);
+}
+
+int acx_compile_host_ex(const uint8_t *blob, const uint64_t *offsets, uint64_t n_patterns, int match_kind, uint32_t flags,
+                        acx_host_automaton_t **out) {
     if (!out) return fail(ACX_EINVAL, "null output pointer");
     *out = nullptr;
+    if (flags & ~(uint32_t)ACX_BUILD_ASCII_CASE_INSENSITIVE) return fail(ACX_EINVAL, "unknown build flags");
     if (n_patterns && (!offsets || (!blob && offsets[n_patterns] != offsets[0])))
         return fail(ACX_EINVAL, "null pattern buffer");
     acx_host_automaton *h = new (std::nothrow) acx_host_automaton();
@@ -2448,6 +2527,9 @@ int acx_compile_host(const uint8_t *blob, const uint64_t *offsets, uint64_t n_pa
     int code = ACX_OK;
     std::string err;
     try {
+        std::vector<uint8_t> fb;
+        std::vector<uint64_t> fo;
+        if (fold_patterns(blob, offsets, n_patterns, flags, fb, fo)) { blob = fb.data(); offsets = fo.data(); }
         err = compile(blob, n_patterns ? offsets : zero_off, n_patterns, match_kind, h->host, code);
     } catch (const std::bad_alloc &) {
         delete h;
@@ -2522,6 +2604,7 @@ int acx_automaton_info(const acx_automaton_t *a, acx_info_t *out) {
     out->match_kind = a->host.match_kind;
     out->device = a->device;
     out->filter_q = a->host.filter_q;
+    out->flags = a->flags;
     return ACX_OK;
 }
 
@@ -2563,8 +2646,10 @@ int acx_find_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const u
     {
         Lease lease(a);
         g_trace.mark(1);
+        const uint8_t *d_search = (const uint8_t *)d_hay;
+        rc = lease.c ? fold_copy(a, lease.c, (const uint8_t *)d_hay, len, &d_search) : ACX_OK;
         // returns when the totals are known; accessors of the result wait for the rest of its device work
-        rc = run_find(a, lease.c, (const uint8_t *)d_hay, len, G, overlapping, codepoints, out, true, false);
+        if (rc == ACX_OK) rc = run_find(a, lease.c, d_search, len, G, overlapping, codepoints, out, true, false);
     }
     g_trace.mark(7);
     return rc;
@@ -2638,7 +2723,7 @@ int acx_find(acx_automaton_t *a, const uint8_t *hay, uint64_t len, int overlappi
         rc = run_resident(a, c, hay, len, overlapping, codepoints, &n, &done, &taken);
         if (rc != ACX_OK) return rc;
         if (!taken) {
-            std::memcpy(w.pin_hay, hay, len);
+            copy_in(a, w.pin_hay, hay, len);
             rc = run_small(a, c, w.pin_hay, len, overlapping, codepoints, w.pin_out, &n, &done, true);
         }
         if (rc != ACX_OK) return rc;
@@ -2718,7 +2803,7 @@ int acx_find(acx_automaton_t *a, const uint8_t *hay, uint64_t len, int overlappi
             HIPCHK(hipHostMalloc((void **)&w.pin_mid, cap, hipHostMallocDefault));
             w.pin_mid_cap = cap;
         }
-        std::memcpy(w.pin_mid, hay, len);
+        copy_in(a, w.pin_mid, hay, len);
         std::memset(w.pin_mid + len, 0, 64);
         d_hay = w.pin_mid;
         rc = ACX_OK;
@@ -2810,9 +2895,10 @@ int acx_replicate(const acx_automaton_t *a, int device, acx_automaton_t **out) {
         return fail(ACX_EINVAL, "device ordinal out of range");
     const int saved = g_device;
     g_device = device;
-    // (the host copy keeps the pattern bytes and offsets: the replica is compiled from them)
-    const int rc = acx_build(a->host.blob.data(), a->host.offsets.data(), a->host.n_patterns, a->host.match_kind,
-                             a->implementation, out);
+    // (the host copy keeps the pattern bytes and offsets -- folded ones for a case-insensitive handle: folding is
+    // idempotent -- and the replica is compiled from them)
+    const int rc = acx_build_ex(a->host.blob.data(), a->host.offsets.data(), a->host.n_patterns, a->host.match_kind,
+                                a->implementation, a->flags, out);
     g_device = saved;
     if (rc == ACX_OK && a->kernel_forced) (void)acx_set_kernel(*out, a->kernel);
     return rc;
@@ -3029,10 +3115,12 @@ int acx_replace(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint
     Lease lease(a);
     Ctx *c = lease.c;
     if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    rc = stage_host(a, c, h, len, offsets ? rel.data() : nullptr, offsets ? n_hay + 1 : 0);
+    rc = stage_host(a, c, h, len, offsets ? rel.data() : nullptr, offsets ? n_hay + 1 : 0, false);
     if (rc != ACX_OK) return rc;
+    const uint8_t *d_search = nullptr;
+    if ((rc = fold_copy(a, c, c->ws.hay, len, &d_search)) != ACX_OK) return rc;
     const Segments G = offsets ? Segments{c->ws.offsets, n_hay, 0} : Segments{nullptr, 1, 0};
-    return run_replace(a, c, c->ws.hay, len, G, repl_blob, repl_offsets, n_repl, out);
+    return run_replace(a, c, d_search, c->ws.hay, len, G, repl_blob, repl_offsets, n_repl, out);
 }
 
 int acx_replace_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
@@ -3052,7 +3140,10 @@ int acx_replace_device(acx_automaton_t *a, const void *d_hay, uint64_t len, cons
     }
     Lease lease(a);
     if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    return run_replace(a, lease.c, (const uint8_t *)d_hay, len, G, repl_blob, repl_offsets, n_repl, out);
+    const uint8_t *d_search = nullptr;
+    rc = fold_copy(a, lease.c, (const uint8_t *)d_hay, len, &d_search);
+    if (rc != ACX_OK) return rc;
+    return run_replace(a, lease.c, d_search, (const uint8_t *)d_hay, len, G, repl_blob, repl_offsets, n_repl, out);
 }
 
 uint64_t acx_replaced_len(const acx_replaced_t *r) { return r ? r->len : 0; }

@@ -194,13 +194,14 @@ bool utf8_is_ascii(const char *s, Py_ssize_t n, PyObject *str) {
 PyObject *info_dict(acx_automaton_t *a) {
     acx_info_t i;
     if (acx_automaton_info(a, &i) != ACX_OK) return raise_acx(ACX_EINVAL);
-    return Py_BuildValue("{s:K,s:K,s:I,s:I,s:I,s:I,s:K,s:I,s:s,s:i,s:i,s:I}", "n_patterns",
+    return Py_BuildValue("{s:K,s:K,s:I,s:I,s:I,s:I,s:K,s:I,s:s,s:i,s:i,s:I,s:O}", "n_patterns",
                          (unsigned long long)i.n_patterns, "n_states", (unsigned long long)i.n_states,
                          "n_classes", i.n_classes, "stride", i.stride, "min_pattern_len",
                          i.min_pattern_len, "max_pattern_len", i.max_pattern_len, "table_bytes",
                          (unsigned long long)i.table_bytes, "lds_hot_rows", i.lds_hot_rows, "kernel",
                          i.kernel == ACX_KERNEL_PREFILTER ? "prefilter" : "dfa_walk", "match_kind",
-                         i.match_kind, "device", i.device, "filter_q", i.filter_q);
+                         i.match_kind, "device", i.device, "filter_q", i.filter_q, "ascii_case_insensitive",
+                         (i.flags & ACX_BUILD_ASCII_CASE_INSENSITIVE) ? Py_True : Py_False);
 }
 
 // Replicas of an object's automaton on other devices (find_matches_as_indexes_batch(devices=[...])):
@@ -320,15 +321,17 @@ void ac_dealloc(PyObject *self) {
 
 // src/lib.rs:134-224
 PyObject *ac_new(PyTypeObject *type, PyObject *args, PyObject *kwargs) {
-    static const char *kw[] = {"patterns", "matchkind", "store_patterns", "implementation", nullptr};
-    PyObject *patterns = nullptr, *mk_o = nullptr, *store_o = Py_None, *impl_o = Py_None;
-    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|OOO:AhoCorasick", const_cast<char **>(kw),
-                                     &patterns, &mk_o, &store_o, &impl_o))
+    static const char *kw[] = {"patterns", "matchkind", "store_patterns", "implementation", "ascii_case_insensitive", nullptr};
+    PyObject *patterns = nullptr, *mk_o = nullptr, *store_o = Py_None, *impl_o = Py_None, *ci_o = Py_False;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|OOOO:AhoCorasick", const_cast<char **>(kw),
+                                     &patterns, &mk_o, &store_o, &impl_o, &ci_o))
         return nullptr;
-    int mk, impl;
+    int mk, impl, ci;
     if (!parse_matchkind(mk_o, &mk) || !parse_implementation(impl_o, &impl)) return nullptr;
     int store = -1; // None -> heuristic
     if (store_o != Py_None && !parse_bool(store_o, "store_patterns", &store)) return nullptr;
+    // the crate's AhoCorasickBuilder::ascii_case_insensitive: a real bool, as store_patterns
+    if (!parse_bool(ci_o, "ascii_case_insensitive", &ci)) return nullptr;
     PyObject *iter = PyObject_GetIter(patterns); // non-iterable -> TypeError (tests/test_ac.py:79-80)
     if (!iter) return nullptr;
     PyObject *kept = PyList_New(0);
@@ -376,7 +379,7 @@ PyObject *ac_new(PyTypeObject *type, PyObject *args, PyObject *kwargs) {
     int rc;
     blob.push_back(0);
     Py_BEGIN_ALLOW_THREADS // the reference yields the GIL while building, src/lib.rs:198
-    rc = acx_build(blob.data(), off.data(), off.size() - 1, mk, impl, &ac);
+    rc = acx_build_ex(blob.data(), off.data(), off.size() - 1, mk, impl, ci ? ACX_BUILD_ASCII_CASE_INSENSITIVE : 0, &ac);
     Py_END_ALLOW_THREADS
     if (rc != ACX_OK) { Py_DECREF(kept); return raise_acx(rc); }
     AcObject *self = reinterpret_cast<AcObject *>(type->tp_alloc(type, 0));
@@ -630,7 +633,8 @@ PyType_Slot ac_slots[] = {
     {Py_tp_methods, ac_methods},
     {Py_tp_doc, const_cast<char *>(
         "Search for multiple pattern strings against a single haystack string.\n\n"
-        "AhoCorasick(patterns, matchkind=MatchKind.Standard, store_patterns=None, implementation=None)")},
+        "AhoCorasick(patterns, matchkind=MatchKind.Standard, store_patterns=None, implementation=None, "
+        "ascii_case_insensitive=False)")},
     {0, nullptr},
 };
 
@@ -654,13 +658,14 @@ void bac_dealloc(PyObject *self) {
 
 // src/lib.rs:369-413
 PyObject *bac_new(PyTypeObject *type, PyObject *args, PyObject *kwargs) {
-    static const char *kw[] = {"patterns", "matchkind", "implementation", nullptr};
-    PyObject *patterns = nullptr, *mk_o = nullptr, *impl_o = Py_None;
-    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|OO:BytesAhoCorasick", const_cast<char **>(kw),
-                                     &patterns, &mk_o, &impl_o))
+    static const char *kw[] = {"patterns", "matchkind", "implementation", "ascii_case_insensitive", nullptr};
+    PyObject *patterns = nullptr, *mk_o = nullptr, *impl_o = Py_None, *ci_o = Py_False;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|OOO:BytesAhoCorasick", const_cast<char **>(kw),
+                                     &patterns, &mk_o, &impl_o, &ci_o))
         return nullptr;
-    int mk, impl;
+    int mk, impl, ci;
     if (!parse_matchkind(mk_o, &mk) || !parse_implementation(impl_o, &impl)) return nullptr;
+    if (!parse_bool(ci_o, "ascii_case_insensitive", &ci)) return nullptr;
     PyObject *iter = PyObject_GetIter(patterns);
     if (!iter) return nullptr;
     std::vector<uint8_t> blob;
@@ -686,7 +691,7 @@ PyObject *bac_new(PyTypeObject *type, PyObject *args, PyObject *kwargs) {
     int rc;
     blob.push_back(0);
     Py_BEGIN_ALLOW_THREADS
-    rc = acx_build(blob.data(), off.data(), off.size() - 1, mk, impl, &ac);
+    rc = acx_build_ex(blob.data(), off.data(), off.size() - 1, mk, impl, ci ? ACX_BUILD_ASCII_CASE_INSENSITIVE : 0, &ac);
     Py_END_ALLOW_THREADS
     if (rc != ACX_OK) return raise_acx(rc);
     BacObject *self = reinterpret_cast<BacObject *>(type->tp_alloc(type, 0));
@@ -892,7 +897,7 @@ PyType_Slot bac_slots[] = {
     {Py_tp_methods, bac_methods},
     {Py_tp_doc, const_cast<char *>(
         "Search for multiple pattern bytes against a single bytes haystack.\n\n"
-        "BytesAhoCorasick(patterns, matchkind=MatchKind.Standard, implementation=None)")},
+        "BytesAhoCorasick(patterns, matchkind=MatchKind.Standard, implementation=None, ascii_case_insensitive=False)")},
     {0, nullptr},
 };
 

@@ -23,7 +23,9 @@
 extern "C" {
 #endif
 
-/* 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
+/* 11: acx_build_ex / acx_compile_host_ex (build flags: ACX_BUILD_ASCII_CASE_INSENSITIVE) added; acx_info_t gained `flags`;
+ *     acx_path_stats gained [13];
+ * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
  * 7: acx_path_stats gained [8] (byte ranges of calls that were cut); K0's result line carries end - 1 and a hash of the
@@ -34,7 +36,7 @@ extern "C" {
  * 3: acx_replicate / acx_find_batch_multi / acx_shard_range / acx_automaton_device added (round 3);
  * 2: acx_prefix_slot gained `salt`, acx_host_tables_t grew (round 2).  A binding built against another
  * header must refuse to load: compare acx_version() with the ACX_VERSION it was compiled with. */
-#define ACX_VERSION 10
+#define ACX_VERSION 11
 
 /* status codes */
 #define ACX_OK 0
@@ -57,6 +59,13 @@ extern "C" {
 #define ACX_MATCH_STANDARD 0
 #define ACX_MATCH_LEFTMOST_FIRST 1
 #define ACX_MATCH_LEFTMOST_LONGEST 2
+
+/* build flags (acx_build_ex, acx_compile_host_ex).  ASCII_CASE_INSENSITIVE: the crate's
+ * AhoCorasickBuilder::ascii_case_insensitive -- an ASCII letter of a pattern matches either case of that letter in the
+ * haystack; no other byte folds.  Pattern ids, match kinds and overlapping keep their meaning; patterns that are equal
+ * after folding are copies of one string.  Offsets are the caller's, and a replacement splices the caller's own bytes
+ * around its matches.  Other bits: ACX_EINVAL. */
+#define ACX_BUILD_ASCII_CASE_INSENSITIVE 1
 
 /* enum Implementation (+ None), src/lib.rs:111-128.  A hint only: every value
  * yields identical results (tests/test_ac.py:23-31) and NO value selects a slower
@@ -107,6 +116,7 @@ typedef struct acx_info {
     int32_t match_kind;
     int32_t device;       /* HIP device ordinal the tables live on             */
     uint32_t filter_q;    /* q-gram length of the K1b prefilter (0 = none)     */
+    uint32_t flags;       /* ACX_BUILD_* the handle was built with             */
 } acx_info_t;
 
 typedef struct acx_profile {
@@ -133,6 +143,14 @@ int acx_set_device(int ordinal); /* device for subsequent acx_build on this thre
  * `offsets[n_patterns + 1]` delimits them.  Patterns are copied. */
 int acx_build(const uint8_t *blob, const uint64_t *offsets, uint64_t n_patterns,
               int match_kind, int implementation, acx_automaton_t **out);
+/* acx_build with build flags (ACX_BUILD_*; acx_build is flags = 0).  ACX_BUILD_ASCII_CASE_INSENSITIVE: the patterns are
+ * folded (A-Z -> a-z) before they are compiled, and every haystack of the handle is searched in a folded copy: the pinned
+ * host copy the calling thread makes anyway (K0, the resident K0, mid-size haystacks read in place) is a folding copy,
+ * the staging buffer of larger host haystacks is folded in place on the device, and a device haystack is folded into a
+ * grow-only buffer of the calling context (as large as the largest device haystack that context has searched).  The
+ * caller's memory is never written.  acx_replicate carries the flags. */
+int acx_build_ex(const uint8_t *blob, const uint64_t *offsets, uint64_t n_patterns, int match_kind, int implementation,
+                 uint32_t flags, acx_automaton_t **out);
 void acx_free_automaton(acx_automaton_t *a);
 int acx_automaton_info(const acx_automaton_t *a, acx_info_t *out);
 int acx_set_kernel(acx_automaton_t *a, int kernel); /* override the selection  */
@@ -211,6 +229,10 @@ typedef struct acx_host_tables {
 } acx_host_tables_t;
 int acx_compile_host(const uint8_t *blob, const uint64_t *offsets, uint64_t n_patterns,
                      int match_kind, acx_host_automaton_t **out);
+/* the same with build flags: the tables acx_build_ex uploads (ACX_BUILD_ASCII_CASE_INSENSITIVE: those of the folded
+ * patterns) */
+int acx_compile_host_ex(const uint8_t *blob, const uint64_t *offsets, uint64_t n_patterns, int match_kind, uint32_t flags,
+                        acx_host_automaton_t **out);
 int acx_host_tables(const acx_host_automaton_t *h, acx_host_tables_t *out);
 uint32_t acx_filter_hash(uint32_t gram);   /* level-1 hash of a little-endian (Q-1)-gram   */
 uint32_t acx_prefix_slot(uint64_t gram, uint32_t salt, uint32_t log2); /* home slot of the `salt` low
@@ -357,8 +379,10 @@ int acx_profile_read(acx_automaton_t *a, acx_profile_t *out, int reset);
  * [10] launches of a context's RESIDENT K0 (acx_find on short haystacks: one workgroup stays on the device between the
  * calls of a loop and is fed through pinned host memory -- [7] counts the calls, [10] the launches they cost), [11] calls
  * of acx_find whose haystack (beyond K0's sizes, up to 1 MiB) the scan read IN PLACE from pinned host memory instead of
- * a copy in HBM, [12] calls of acx_replace / acx_replace_device spliced on the device.  reset != 0 clears the counters. */
-#define ACX_PATH_STATS 13
+ * a copy in HBM, [12] calls of acx_replace / acx_replace_device spliced on the device, [13] calls whose haystack a
+ * case-insensitive handle folded on the device (the staging buffer in place, or a device haystack into the context's
+ * buffer; the calling thread's folding copy into pinned host memory is not counted).  reset != 0 clears the counters. */
+#define ACX_PATH_STATS 14
 int acx_path_stats(acx_automaton_t *a, uint64_t out[ACX_PATH_STATS], int reset);
 
 /* ---- device memory helpers so that a host without torch can stage data ---- */
