@@ -23,8 +23,11 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(HERE, "libacx_hip.so")
 EXT = os.path.join(HERE, "ahocorasick_rs" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 
-LIB_SOURCES = ["kernels.hip", "replace.hip", "fold.hip", "acx_api.cpp", "automaton.cpp", "comm.cpp"]
-LIB_HEADERS = ["kernels.hpp", "replace.hpp", "fold.hpp", "automaton.hpp", "device_types.hpp", os.path.join(INCLUDE, "acx.h")]
+# the one list of what libacx_hip.so is compiled from (tools/build_variant.sh asks for it: --print-sources)
+LIB_SOURCES = ["kernels.hip", "replace.hip", "fold.hip", "acx_api.cpp", "workspace.cpp", "small_calls.cpp", "find_attempts.cpp",
+               "find_pipeline.cpp", "build_upload.cpp", "replace_api.cpp", "automaton.cpp", "comm.cpp"]
+LIB_HEADERS = ["kernels.hpp", "replace.hpp", "fold.hpp", "automaton.hpp", "device_types.hpp", "host_common.hpp", "workspace.hpp",
+               "small_calls.hpp", "find_attempts.hpp", "find_pipeline.hpp", os.path.join(INCLUDE, "acx.h")]
 EXT_SOURCES = ["pymodule.cpp"]
 
 
@@ -78,4 +81,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
 
 
 if __name__ == "__main__":
+    if "--print-sources" in sys.argv:  # the library's sources, relative to the repository root, on one line
+        print(" ".join(os.path.relpath(os.path.join(CSRC, f), ROOT) for f in LIB_SOURCES))
+        sys.exit(0)
     build_all(force="--force" in sys.argv, verbose=True)

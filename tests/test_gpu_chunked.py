@@ -4,7 +4,7 @@ The reference's loop is an iterator: it has no limit on what it reports (/root/r
 the device pipeline indexes its occurrences with 32 bits; until round 5 a call beyond that raised ACX_ETOOBIG.  Now the
 haystack is searched in byte ranges, one after the other -- overlapping: a range reports what ENDS in it; non-overlapping:
 a range reports what STARTS in it, and the iteration resumes where the last match of the ranges in front ended -- and the
-pieces are spliced with global offsets (acx_api.cpp, run_chunked).  2^32 occurrences need > 100 GB of matches: the tests
+pieces are spliced with global offsets (find_pipeline.cpp, run_chunked).  2^32 occurrences need > 100 GB of matches: the tests
 lower the limit of one pass (ACX_MAX_OCC) or force the cut (ACX_CHUNK_BYTES), both read per call; acx_path_stats counts the
 ranges.  Everything is compared with the oracle, element-wise."""
 import numpy as np

@@ -5,7 +5,7 @@ The reference keeps every copy of a string and an overlapping search reports the
 Until round 5 the device enumerated, verified, staged and sorted every copy's occurrence: hundreds of copies of every
 string on text where every position matches sent every call to the radix-sort form (and against the 2^32 limit of one
 pass).  Now the search runs on the view without the later copies -- one occurrence per string, under the lowest id, the
-view non-overlapping searches take since round 4 -- and the complete result is expanded (acx_api.cpp expand_copies: a
+view non-overlapping searches take since round 4 -- and the complete result is expanded (find_pipeline.cpp expand_copies: a
 prefix sum over the copies' counts, one thread per output record; K0's pinned result on the host; a batch's per-haystack
 counts follow).  Every case against the oracle, element-wise, through every entry point."""
 import random

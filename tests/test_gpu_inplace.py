@@ -1,4 +1,4 @@
-"""GPU: mid-size host haystacks read IN PLACE (round 6, acx_api.cpp acx_find): beyond K0's sizes and up to 1 MiB the calling
+"""GPU: mid-size host haystacks read IN PLACE (round 6, workspace.cpp place_host_haystack): beyond K0's sizes and up to 1 MiB the calling
 thread copies the haystack into pinned host memory and the scan reads it there -- no staging copy of the runtime, no DMA the
 scan's launch waits for.  Every kind, bytes and code points, against the oracle; path_stats["in_place"] says the call went
 that way.  Reference path: /root/reference/src/lib.rs:422-434 (bytes), 229-249 (str)."""

@@ -553,7 +553,7 @@ def test_k0_direct_comparison_work_limit():
 def test_copies_of_a_pattern_cost_a_non_overlapping_search_nothing(kernel):
     """Hundreds of copies of every string (tools/gpu_fuzz.py seed 40404: 22 264 patterns = 30 distinct strings) on
     text where every position matches: a non-overlapping search reports the lowest id of a string and must not pay
-    for the others (acx_api.cpp: dev_nov, the view without the later copies); an overlapping one reports every copy.
+    for the others (workspace.hpp: dev_nov, the view without the later copies); an overlapping one reports every copy.
     Short strings (own lists / K0), longer ones (K1b's candidate lists), 1- and 2-byte ones (the side test's lists)."""
     import random
     import time

@@ -6,7 +6,7 @@ set -eu
 cd "$(dirname "$0")/.."
 name=$1; shift
 mkdir -p variants
-C=ahocorasick_rs_amd/csrc
+# (the sources: the build script's own list)
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Iinclude "$@" -o variants/libacx_$name.so \
-  $C/kernels.hip $C/acx_api.cpp $C/automaton.cpp $C/comm.cpp -ldl
+  $(python3 ahocorasick_rs_amd/_build.py --print-sources) -ldl
 echo "built variants/libacx_$name.so ($*)"
