@@ -27,6 +27,8 @@ IMPL_AUTO, IMPL_NONCONTIGUOUS_NFA, IMPL_CONTIGUOUS_NFA, IMPL_DFA = -1, 0, 1, 2
 KERNEL_AUTO, KERNEL_DFA_WALK, KERNEL_PREFILTER = 0, 1, 2
 KERNEL_NAMES = {1: "dfa_walk", 2: "prefilter"}
 BUILD_ASCII_CASE_INSENSITIVE = 1  # build flag (acx_build_ex)
+SUM_FIRST, SUM_BY_PATTERN = 1, 2  # acx_summarize: the parts beyond the total and the counts (ACX_SUM_*)
+NO_MATCH = (1 << 64) - 1  # the pattern of a haystack's first match when it has none
 ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
 MATCH_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u8"), ("end", "<u8")])
@@ -173,6 +175,18 @@ def lib() -> ctypes.CDLL:
     L.acx_free_replaced.argtypes = [vp]
     L.acx_free_replaced.restype = None
     L.acx_splice_host.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, ctypes.POINTER(u64)]
+    L.acx_summarize.argtypes = [vp, vp, u64, vp, u64, i32, i32, ctypes.c_uint32, ctypes.POINTER(vp)]
+    L.acx_summarize_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, i32, ctypes.c_uint32, ctypes.POINTER(vp)]
+    L.acx_summary_total.argtypes = [vp]
+    L.acx_summary_total.restype = u64
+    L.acx_summary_on_device.argtypes = [vp]
+    for name in ("counts", "any", "first", "by_pattern"):
+        getattr(L, "acx_summary_" + name).argtypes = [vp, vp]
+        getattr(L, "acx_summary_device_" + name).argtypes = [vp]
+        getattr(L, "acx_summary_device_" + name).restype = vp
+    L.acx_free_summary.argtypes = [vp]
+    L.acx_free_summary.restype = None
+    L.acx_summarize_host.argtypes = [vp, u64, vp, u64, u64, ctypes.c_uint32, vp, vp, vp]
     _lib = L
     return L
 
@@ -477,6 +491,86 @@ class DeviceReplaced:
             pass
 
 
+class DeviceSummary:
+    """The summaries of Automaton.summarize / summarize_batch / summarize_device (acx_summary_t): reduced in HBM
+    (on_device) or on the host; every part is copied out when it is asked for.  A part that `what` did not name raises
+    ValueError (code EINVAL)."""
+
+    def __init__(self, handle: int, n_hay: int, n_patterns: int):
+        self._h = handle
+        self.n_hay = n_hay
+        self.n_patterns = n_patterns
+
+    @property
+    def total(self) -> int:
+        return int(lib().acx_summary_total(self._h))
+
+    @property
+    def on_device(self) -> bool:
+        return bool(lib().acx_summary_on_device(self._h))
+
+    def _part(self, name: str, n: int, dtype) -> np.ndarray:
+        out = np.zeros(n, dtype=dtype)
+        _check(getattr(lib(), "acx_summary_" + name)(self._h, out.ctypes.data if n else None))
+        return out
+
+    def counts(self) -> np.ndarray:
+        """matches per haystack"""
+        return self._part("counts", self.n_hay, np.uint64)
+
+    def any_bits(self) -> np.ndarray:
+        """the bitmap as the library keeps it: (n_hay + 63) // 64 words, LSB first"""
+        return self._part("any", (self.n_hay + 63) // 64, np.uint64)
+
+    def any(self) -> np.ndarray:
+        """one bool per haystack: it has a match"""
+        bits = np.unpackbits(self.any_bits().view(np.uint8), bitorder="little")
+        return bits[:self.n_hay].astype(bool)
+
+    def first(self) -> np.ndarray:
+        """every haystack's first match (MATCH_DTYPE; pattern == NO_MATCH: none)"""
+        return self._part("first", self.n_hay, MATCH_DTYPE)
+
+    def by_pattern(self) -> np.ndarray:
+        """matches of the whole call per pattern"""
+        return self._part("by_pattern", self.n_patterns, np.uint64)
+
+    def device_ptr(self, name: str) -> int:
+        """where the part ("counts", "any", "first", "by_pattern") lies in HBM (waits for the reduction); 0 on the host route"""
+        return getattr(lib(), "acx_summary_device_" + name)(self._h) or 0
+
+    def free(self) -> None:
+        if self._h:
+            lib().acx_free_summary(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def summarize_host(matches, counts: Optional[Sequence[int]], n_patterns: int, what: int = SUM_FIRST | SUM_BY_PATTERN):
+    """acx_summarize_host: the reduction of a match list (rows of pattern, start, end; all haystacks behind one another,
+    counts[h] rows each -- None: one haystack) on the host, no device involved -> (any, first, by_pattern): one bool per
+    haystack, MATCH_DTYPE rows, one count per pattern; a part `what` does not name is None.  ValueError (code EINVAL) when
+    the counts do not sum to the rows or a row names a pattern >= n_patterns."""
+    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    n_hay = 1 if c is None else len(c)
+    bits = np.zeros((n_hay + 63) // 64 + 1, dtype=np.uint64)
+    first = np.zeros(n_hay + 1, dtype=MATCH_DTYPE)
+    hist = np.zeros(n_patterns + 1, dtype=np.uint64)
+    pad = np.zeros(1, dtype=np.uint64)  # (an empty batch is still a batch: a non-null counts pointer)
+    _check(lib().acx_summarize_host(m.ctypes.data if len(m) else None, len(m),
+                                    None if c is None else (c.ctypes.data if len(c) else pad.ctypes.data), n_hay, n_patterns,
+                                    what, bits.ctypes.data, first.ctypes.data, hist.ctypes.data))
+    any_ = np.unpackbits(bits.view(np.uint8), bitorder="little")[:n_hay].astype(bool)
+    return (any_ if what & SUM_FIRST else None, first[:n_hay] if what & SUM_FIRST else None,
+            hist[:n_patterns] if what & SUM_BY_PATTERN else None)
+
+
 def _replaced_bytes(h: int) -> bytes:
     buf = bytearray(int(lib().acx_replaced_len(h)))
     if buf:
@@ -640,6 +734,34 @@ class Automaton:
         _check(lib().acx_replace_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, blob.ctypes.data,
                                         off.ctypes.data, len(replace_with), ctypes.byref(out)))
         return DeviceReplaced(out.value, n_hay if (uniform_len or d_offsets) else 1)
+
+    # ---- summaries (acx_summarize / acx_summarize_device)
+    def summarize(self, hay, what: int = SUM_FIRST | SUM_BY_PATTERN, overlapping: bool = False,
+                  codepoints: bool = False) -> DeviceSummary:
+        """is there a match, the first one, how many, how many per pattern -- without the match list"""
+        a = np.ascontiguousarray(np.frombuffer(hay, dtype=np.uint8) if not isinstance(hay, np.ndarray) else hay)
+        out = ctypes.c_void_p()
+        _check(lib().acx_summarize(self._h, a.ctypes.data if a.size else None, a.size, None, 0, int(overlapping),
+                                   int(codepoints), what, ctypes.byref(out)))
+        return DeviceSummary(out.value, 1, int(self.info.n_patterns))
+
+    def summarize_batch(self, haystacks: Sequence[bytes], what: int = SUM_FIRST | SUM_BY_PATTERN, overlapping: bool = False,
+                        codepoints: bool = False) -> DeviceSummary:
+        """the same per haystack (by_pattern: over the whole batch); entry i equals summarize(haystacks[i])"""
+        hb, hoff = pack(haystacks)
+        out = ctypes.c_void_p()
+        _check(lib().acx_summarize(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
+                                   int(codepoints), what, ctypes.byref(out)))
+        return DeviceSummary(out.value, len(haystacks), int(self.info.n_patterns))
+
+    def summarize_device(self, d_ptr: int, nbytes: int, what: int = SUM_FIRST | SUM_BY_PATTERN, *, d_offsets: int = 0,
+                         n_hay: int = 0, uniform_len: int = 0, overlapping: bool = False,
+                         codepoints: bool = False) -> DeviceSummary:
+        """the haystack in HBM searched and its result reduced there; the summaries stay in HBM until they are asked for"""
+        out = ctypes.c_void_p()
+        _check(lib().acx_summarize_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
+                                          int(codepoints), what, ctypes.byref(out)))
+        return DeviceSummary(out.value, n_hay if (uniform_len or d_offsets) else 1, int(self.info.n_patterns))
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

@@ -602,6 +602,33 @@ PyObject *ac_info(PyObject *self_, PyObject *) {
     return info_dict(reinterpret_cast<AcObject *>(self_)->ac);
 }
 
+// summaries (defined behind the DLPack adapter below): K = SUM_IS_MATCH .. SUM_BY_PATTERN, BATCH: the *_batch form
+enum { SUM_IS_MATCH = 0, SUM_FIND_FIRST = 1, SUM_COUNT = 2, SUM_BY_PATTERN = 3 };
+template <int K, bool BATCH> PyObject *ac_summary(PyObject *self_, PyObject *args, PyObject *kwargs);
+template <int K, bool BATCH> PyObject *bac_summary(PyObject *self_, PyObject *args, PyObject *kwargs);
+#define ACX_SUMMARY_METHODS(fn)                                                                                                 \
+    {"is_match", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_IS_MATCH, false>)),                         \
+     METH_VARARGS | METH_KEYWORDS,                                                                                              \
+     "[extension] bool(find_matches_as_indexes(haystack)) without the match list (the crate's is_match).  No early exit: "     \
+     "one search over the whole haystack."},                                                                                    \
+    {"find_first", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_FIND_FIRST, false>)),                     \
+     METH_VARARGS | METH_KEYWORDS,                                                                                              \
+     "[extension] find_matches_as_indexes(haystack)[0], or None (the crate's find for the object's match kind)."},            \
+    {"count_matches", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_COUNT, false>)),                       \
+     METH_VARARGS | METH_KEYWORDS, "[extension] len(find_matches_as_indexes(haystack, overlapping))."},                        \
+    {"count_by_pattern", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_BY_PATTERN, false>)),               \
+     METH_VARARGS | METH_KEYWORDS,                                                                                              \
+     "[extension] one int per pattern: how many of find_matches_as_indexes(haystack, overlapping) name it."},                  \
+    {"is_match_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_IS_MATCH, true>)),                    \
+     METH_VARARGS | METH_KEYWORDS, "[extension] [self.is_match(h) for h in haystacks] in one call."},                          \
+    {"find_first_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_FIND_FIRST, true>)),                \
+     METH_VARARGS | METH_KEYWORDS, "[extension] [self.find_first(h) for h in haystacks] in one call."},                        \
+    {"count_matches_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_COUNT, true>)),                  \
+     METH_VARARGS | METH_KEYWORDS, "[extension] [self.count_matches(h, overlapping) for h in haystacks] in one call."},        \
+    {"count_by_pattern_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_BY_PATTERN, true>)),          \
+     METH_VARARGS | METH_KEYWORDS,                                                                                              \
+     "[extension] the per-pattern totals over all haystacks: the sum of self.count_by_pattern(h, overlapping)."}
+
 PyMethodDef ac_methods[] = {
     {"find_matches_as_indexes", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_find_indexes)),
      METH_VARARGS | METH_KEYWORDS,
@@ -623,6 +650,7 @@ PyMethodDef ac_methods[] = {
      "replace_with[pattern index]; replace_with has one str per pattern (ValueError otherwise)."},
     {"replace_all_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_replace_all_batch)),
      METH_VARARGS | METH_KEYWORDS, "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
+    ACX_SUMMARY_METHODS(ac_summary),
     {"_info", ac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -759,6 +787,161 @@ void dlpack_release(PyObject *cap) { // we consumed the capsule: rename it and r
     Py_DECREF(cap);
 }
 
+// ---------------------------------------------------------------------------
+// summaries: is_match / find_first / count_matches / count_by_pattern and their batch forms (acx_summarize: the crate's
+// AhoCorasick::is_match and ::find, and the counts of its iterators; the reference binding stops at the match list)
+// ---------------------------------------------------------------------------
+struct Summary {
+    uint64_t total = 0;
+    std::vector<uint64_t> counts, any, hist;
+    std::vector<acx_match_t> first;
+};
+
+// one acx_summarize call (on_device: acx_summarize_device on a tensor in HBM) and the copies of the parts the method
+// returns, with the GIL released
+int summarize_nogil(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
+                    bool on_device, int overlapping, int codepoints, int kind, bool batch, Summary *out) {
+    const uint32_t what = kind == SUM_FIND_FIRST || (kind == SUM_IS_MATCH && batch) ? ACX_SUM_FIRST
+                          : kind == SUM_BY_PATTERN ? ACX_SUM_BY_PATTERN : 0;
+    int rc = ACX_OK;
+    Py_BEGIN_ALLOW_THREADS
+    acx_summary_t *r = nullptr;
+    if (on_device) { // (the producer's kernels may still be writing the tensor on its own stream: find_on_device)
+        rc = acx_device_synchronize_on(acx_automaton_device(a));
+        if (rc == ACX_OK) rc = acx_summarize_device(a, hay, len, nullptr, 0, 0, overlapping, codepoints, what, &r);
+    } else {
+        rc = acx_summarize(a, hay, len, offsets, n_hay, overlapping, codepoints, what, &r);
+    }
+    if (rc == ACX_OK) {
+        const uint64_t n = offsets ? n_hay : 1;
+        out->total = acx_summary_total(r);
+        if (kind == SUM_COUNT && batch) {
+            out->counts.assign((size_t)n, 0);
+            rc = acx_summary_counts(r, out->counts.data());
+        } else if (kind == SUM_IS_MATCH && batch) {
+            out->any.assign((size_t)((n + 63) / 64), 0);
+            rc = acx_summary_any(r, out->any.data());
+        } else if (kind == SUM_FIND_FIRST) {
+            out->first.resize((size_t)n);
+            rc = acx_summary_first(r, out->first.data());
+        } else if (kind == SUM_BY_PATTERN) {
+            acx_info_t info;
+            rc = acx_automaton_info(a, &info);
+            if (rc == ACX_OK) {
+                out->hist.assign((size_t)info.n_patterns, 0);
+                rc = acx_summary_by_pattern(r, out->hist.data());
+            }
+        }
+    }
+    acx_free_summary(r);
+    Py_END_ALLOW_THREADS
+    return rc;
+}
+
+PyObject *first_to_object(const acx_match_t &m) {
+    if (m.pattern == UINT64_MAX) Py_RETURN_NONE;
+    return Py_BuildValue("(KKK)", (unsigned long long)m.pattern, (unsigned long long)m.start, (unsigned long long)m.end);
+}
+
+PyObject *u64_list(const std::vector<uint64_t> &v) {
+    PyObject *list = PyList_New((Py_ssize_t)v.size());
+    for (size_t i = 0; list && i < v.size(); i++) {
+        PyObject *x = PyLong_FromUnsignedLongLong(v[i]);
+        if (!x) { Py_CLEAR(list); break; }
+        PyList_SET_ITEM(list, (Py_ssize_t)i, x);
+    }
+    return list;
+}
+
+PyObject *summary_to_object(const Summary &s, int kind, bool batch, Py_ssize_t n) {
+    if (kind == SUM_BY_PATTERN) return u64_list(s.hist);
+    if (!batch) {
+        if (kind == SUM_IS_MATCH) return PyBool_FromLong(s.total != 0);
+        if (kind == SUM_COUNT) return PyLong_FromUnsignedLongLong(s.total);
+        return first_to_object(s.first[0]);
+    }
+    if (kind == SUM_COUNT) return u64_list(s.counts);
+    PyObject *list = PyList_New(n);
+    for (Py_ssize_t i = 0; list && i < n; i++) {
+        PyObject *x = kind == SUM_IS_MATCH ? PyBool_FromLong((long)((s.any[(size_t)i >> 6] >> (i & 63)) & 1))
+                                           : first_to_object(s.first[(size_t)i]);
+        if (!x) { Py_CLEAR(list); break; }
+        PyList_SET_ITEM(list, i, x);
+    }
+    return list;
+}
+
+const char *const SUMMARY_FMT[2][4] = {{"O:is_match", "O:find_first", "O|O:count_matches", "O|O:count_by_pattern"},
+                                       {"O:is_match_batch", "O:find_first_batch", "O|O:count_matches_batch",
+                                        "O|O:count_by_pattern_batch"}};
+
+// every summary method of both classes: utf8 = the str class.  Code points are asked for only where offsets are returned
+// (find_first) and the text is not ASCII; find_first is always a non-overlapping search.
+PyObject *summary_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, int kind, bool batch, bool utf8) {
+    // (is_match and find_first take no `overlapping`: the one does not depend on it, the other is the crate's find)
+    const bool has_ov = kind == SUM_COUNT || kind == SUM_BY_PATTERN;
+    const char *kw[] = {batch ? "haystacks" : "haystack", has_ov ? "overlapping" : nullptr, nullptr};
+    PyObject *hay = nullptr, *ov = nullptr;
+    int overlapping = 0;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, SUMMARY_FMT[batch][kind], const_cast<char **>(kw), &hay, &ov)) return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    Summary s;
+    int rc;
+    Py_ssize_t n = 1;
+    if (batch) {
+        PyObject *seq = PySequence_Fast(hay, "haystacks must be a sequence");
+        if (!seq) return nullptr;
+        n = PySequence_Fast_GET_SIZE(seq);
+        std::vector<uint64_t> off((size_t)n + 1, 0);
+        std::vector<uint8_t> blob;
+        bool all_ascii = true;
+        for (Py_ssize_t i = 0; i < n; i++) {
+            PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
+            if (utf8) {
+                const char *p; Py_ssize_t len;
+                if (!str_view(it, &p, &len)) { Py_DECREF(seq); return nullptr; }
+                all_ascii = all_ascii && PyUnicode_IS_ASCII(it);
+                blob.insert(blob.end(), p, p + len);
+            } else {
+                Py_buffer v;
+                if (!get_bytes_view(it, &v)) { Py_DECREF(seq); return nullptr; }
+                blob.insert(blob.end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
+                PyBuffer_Release(&v);
+            }
+            off[(size_t)i + 1] = blob.size();
+        }
+        Py_DECREF(seq);
+        blob.push_back(0);
+        rc = summarize_nogil(a, blob.data(), off[(size_t)n], off.data(), (uint64_t)n, false, overlapping,
+                             utf8 && !all_ascii && kind == SUM_FIND_FIRST, kind, true, &s);
+    } else if (utf8) {
+        const char *p; Py_ssize_t len;
+        if (!str_view(hay, &p, &len)) return nullptr;
+        rc = summarize_nogil(a, reinterpret_cast<const uint8_t *>(p), (uint64_t)len, nullptr, 0, false, overlapping,
+                             kind == SUM_FIND_FIRST && !PyUnicode_IS_ASCII(hay), kind, false, &s);
+    } else if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
+        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
+        PyObject *cap = dlpack_view(hay, acx_automaton_device(a), &p, &len, &on_device);
+        if (!cap) return nullptr;
+        rc = summarize_nogil(a, p, len, nullptr, 0, on_device, overlapping, 0, kind, false, &s); // (in HBM: reduced where it lies)
+        dlpack_release(cap);
+    } else {
+        Py_buffer v;
+        if (!get_bytes_view(hay, &v)) return nullptr;
+        rc = summarize_nogil(a, (const uint8_t *)v.buf, (uint64_t)v.len, nullptr, 0, false, overlapping, 0, kind, false, &s);
+        PyBuffer_Release(&v);
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    return summary_to_object(s, kind, batch, n);
+}
+
+template <int K, bool BATCH> PyObject *ac_summary(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return summary_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, K, BATCH, true);
+}
+template <int K, bool BATCH> PyObject *bac_summary(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return summary_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, K, BATCH, false);
+}
+
 // device-resident search -> list of tuples (the records come back with ONE D2H copy of the result)
 PyObject *find_on_device(acx_automaton_t *a, const uint8_t *d_hay, uint64_t len, int overlapping) {
     acx_result_t *r = nullptr;
@@ -887,6 +1070,7 @@ PyMethodDef bac_methods[] = {
      "non-overlapping match replaced by replace_with[pattern index]; replace_with has one buffer per pattern."},
     {"replace_all_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(bac_replace_all_batch)),
      METH_VARARGS | METH_KEYWORDS, "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
+    ACX_SUMMARY_METHODS(bac_summary),
     {"_info", bac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };

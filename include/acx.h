@@ -25,6 +25,9 @@ extern "C" {
 
 /* 11: acx_build_ex / acx_compile_host_ex (build flags: ACX_BUILD_ASCII_CASE_INSENSITIVE) added; acx_info_t gained `flags`;
  *     acx_path_stats gained [13];
+ *     addendum (additive: the number stays, a binding written against 11 still loads): acx_summarize / acx_summarize_device /
+ *     acx_summarize_host, ACX_SUM_FIRST / ACX_SUM_BY_PATTERN and the acx_summary_t accessors (acx_summary_total, _on_device,
+ *     _counts, _any, _first, _by_pattern, _device_counts, _device_any, _device_first, _device_by_pattern, acx_free_summary);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -362,6 +365,54 @@ void acx_free_replaced(acx_replaced_t *r);
 int acx_splice_host(const uint8_t *hay, uint64_t len, const acx_match_t *m, uint64_t n_m,
                     const uint8_t *repl_blob, const uint64_t *repl_offsets, uint64_t n_repl,
                     uint8_t *dst /* NULL: size only */, uint64_t *dst_len);
+
+/* ---- summaries: what most callers want of a find, without its match list.  For a haystack h and M = the matches acx_find
+ * reports for it (same match kind, `overlapping`, `codepoints`):
+ *   total / counts[h]   len(M): every haystack's number of matches (always present; the crate has no single call for it --
+ *                       AhoCorasick::find_iter(..).count(), find_overlapping_iter for overlapping)
+ *   any bit h           M is not empty: the crate's AhoCorasick::is_match (it depends neither on the match kind nor on
+ *                       `overlapping`)
+ *   first[h]            M[0]; with overlapping = 0 the crate's AhoCorasick::find for the handle's match kind (what the
+ *                       Python find_first asks for); pattern = UINT64_MAX (start = end = 0) when there is none
+ *   by_pattern[p]       the matches of the whole call whose pattern is p (find_iter / find_overlapping_iter folded by
+ *                       Match::pattern); an overlapping search over a set with copies of a string counts every copy
+ * `what` selects the parts beyond the counts (ACX_SUM_*; 0: the total and the counts only; other bits: ACX_EINVAL); the
+ * accessor of a part that was not asked for returns ACX_EINVAL.  Batches as for acx_find_batch / acx_find_device; the `any`
+ * bitmap has (n_hay + 63) / 64 words, bit h & 63 of word h >> 6 (LSB first).  An overlapping search on a non-Standard handle
+ * fails with ACX_EOVERLAP as the find does.
+ * There is NO early exit: a summary costs one find over the whole input (plus a pass over its result); what it saves is
+ * the match list -- 24 bytes per match in HBM that are never copied to the host.
+ * Two routes, as for acx_replace: up to ACX_SUMMARY_HOST_MAX bytes (default 1 MiB, read per call) acx_summarize runs
+ * acx_find / acx_find_batch and reduces on the host (acx_summarize_host); beyond, and always for acx_summarize_device, the
+ * result is reduced in HBM behind the find on the same stream, its records are given back as soon as the reduction is
+ * queued, and only the parts an accessor asks for cross to the host.  acx_summary_on_device tells which route ran. */
+#define ACX_SUM_FIRST 1       /* any-bitmap + first match per haystack */
+#define ACX_SUM_BY_PATTERN 2  /* per-pattern totals over the call      */
+typedef struct acx_summary acx_summary_t;
+int acx_summarize(acx_automaton_t *a, const uint8_t *hay, uint64_t len,
+                  const uint64_t *offsets /* NULL: one haystack */, uint64_t n_hay,
+                  int overlapping, int codepoints, uint32_t what, acx_summary_t **out);
+int acx_summarize_device(acx_automaton_t *a, const void *d_hay, uint64_t len,
+                         const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
+                         int overlapping, int codepoints, uint32_t what, acx_summary_t **out);
+uint64_t acx_summary_total(const acx_summary_t *r);            /* matches of the call; valid at return */
+int acx_summary_on_device(const acx_summary_t *r);             /* 1: reduced in HBM, 0: on the host    */
+int acx_summary_counts(const acx_summary_t *r, uint64_t *host_counts /* n_hay */);
+int acx_summary_any(const acx_summary_t *r, uint64_t *host_bits /* (n_hay + 63) / 64 */);
+int acx_summary_first(const acx_summary_t *r, acx_match_t *host_first /* n_hay */);
+int acx_summary_by_pattern(const acx_summary_t *r, uint64_t *host_hist /* n_patterns */);
+/* the same parts where they lie in HBM (each waits for the reduction); NULL on the host route or for a part not asked for */
+const uint64_t *acx_summary_device_counts(const acx_summary_t *r);
+const uint64_t *acx_summary_device_any(const acx_summary_t *r);
+const acx_match_t *acx_summary_device_first(const acx_summary_t *r);
+const uint64_t *acx_summary_device_by_pattern(const acx_summary_t *r);
+void acx_free_summary(acx_summary_t *r);
+/* host only, no device: the reduction itself (the host route).  m: the matches of all haystacks behind one another,
+ * counts[n_hay] how many each has (NULL: one haystack).  Outputs that `what` does not ask for may be NULL.  ACX_EINVAL when
+ * the counts do not sum to n_m or a match names a pattern >= n_patterns. */
+int acx_summarize_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts /* NULL: one haystack */,
+                       uint64_t n_hay, uint64_t n_patterns, uint32_t what,
+                       uint64_t *any_bits, acx_match_t *first, uint64_t *by_pattern);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of

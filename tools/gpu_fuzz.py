@@ -7,8 +7,12 @@ usage: gpu_fuzz.py [seconds] [seed]   -- prints one line per case, exits non-zer
        gpu_fuzz.py surface [n] [seed] [--plan-only]   -- the whole call surface (plan_surface / run_surface below): batches,
        find_device, replace*, the case-insensitive build flag, device pointer residues; --plan-only prints the coverage
        table of the plan with the oracle alone (no GPU).
+       gpu_fuzz.py summary [n] [seed] [--plan-only]   -- the summaries (plan_summary / run_summary below): acx_summarize on the
+       host and the device route, batches, acx_summarize_device in its three forms at odd and even pointer residues, both
+       build flags, every match kind, overlapping counts, code points; each against the oracle's matches reduced in Python.
 tests/test_gpu_fuzz.py runs a bounded, seeded slice of it (fuzz(budget, seed, max_size_log2)) under -m gpu,
-tests/test_gpu_fuzz_surface.py a fixed number of surface cases; tests/test_fuzz_plan_cpu.py checks what that plan covers.
+tests/test_gpu_fuzz_surface.py a fixed number of surface cases; tests/test_fuzz_plan_cpu.py checks what that plan covers;
+tests/test_gpu_summary.py a slice of the summary cases, tests/test_summary_cpu.py what their plan covers.
 UTF-8 cases only ever hold patterns made of whole characters (a str pattern cannot end inside one:
 the precondition of codepoints = 1, include/acx.h)."""
 import os, random, sys, time
@@ -409,7 +413,207 @@ def run_surface(cases):
 SURFACE_N, SURFACE_SEED = 176, 20261016  # what tests/test_gpu_fuzz_surface.py runs and tests/test_fuzz_plan_cpu.py checks
 
 
+# ---------------------------------------------------------------------------
+# the summaries (acx_summarize*): a plan of their own, reduced from the same reference
+# ---------------------------------------------------------------------------
+SUMMARY_OPS = ("summarize_host", "summarize_device_route", "summarize_batch", "summarize_device_one", "summarize_device_uniform",
+               "summarize_device_ragged")
+_SUMMARY_SHAPE = {"summarize_host": "find", "summarize_device_route": "find", "summarize_batch": "find_batch",  # (_cut's names)
+                  "summarize_device_one": "find_device_one", "summarize_device_uniform": "find_device_uniform",
+                  "summarize_device_ragged": "find_device_ragged"}
+SUMMARY_WHATS = (3, 3, 1, 2, 0)  # ACX_SUM_FIRST | ACX_SUM_BY_PATTERN
+
+
+def plan_summary(n_cases: int, seed: int):
+    """-> n_cases cases over the summary entry points; deterministic in (n_cases, seed); no GPU and no capi.Automaton.  Built as
+    plan_surface builds its cases -- make_case()'s shapes with the surface's caps, the op, the match kind and the build flag
+    dealt from a deck (every block of len(SUMMARY_OPS) cases holds every op once, an op's (kind, flag) pair moves on with every
+    block), a haystack halved until its reference has at most SURFACE_ROWS rows -- with make_case()'s generator borrowed and
+    put back.  The pointer residue of a device case alternates between odd and even with the blocks."""
+    global rng, MAX_SIZE_LOG2
+    saved = (rng, MAX_SIZE_LOG2)
+    rng, MAX_SIZE_LOG2 = random.Random(seed), SURFACE_SIZE_LOG2
+    cases = []
+    try:
+        order = []
+        while len(cases) < n_cases:
+            i, k = len(cases), len(SUMMARY_OPS)
+            if i % k == 0:
+                order = list(range(k))
+                rng.shuffle(order)
+            j = order[i % k]
+            deal = (i // k + j) % 6
+            op, mk, ci = SUMMARY_OPS[j], deal % 3, deal >= 3
+            name, kind, pats, hay = make_case(SURFACE_PAT_LOG10)
+            utf8 = name == "utf8"
+            c = {"i": i, "op": op, "name": name, "kind": kind, "mk": mk, "ci": ci, "kernel": rng.choice([None, 1, 2]),
+                 "ov": mk == 0 and rng.random() < 0.4,
+                 "cp": utf8 and not op.endswith("_uniform") and rng.random() < 0.7,
+                 "off": 2 * rng.randrange(8) + (i // k + j) % 2,
+                 "route": rng.choice(["host", "device"]) if op == "summarize_batch" else None,
+                 "what": rng.choice(SUMMARY_WHATS), "repl": None}
+            if ci:
+                pats = [_upper_some(p, rng.randrange(1 << 30)) for p in pats]
+                hay = _upper_some(hay, rng.randrange(1 << 30))
+            c["pats"] = pats
+            cut_state = rng.getstate()
+            while True:
+                rng.setstate(cut_state)
+                c["hays"], c["uniform_len"] = _cut(hay, utf8, _SUMMARY_SHAPE[op])
+                ref = reference(c)
+                if len(ref["rows"]) <= SURFACE_ROWS:
+                    break
+                hay = hay[:_char_start(hay, len(hay) // 2)] if utf8 else hay[:len(hay) // 2]
+            c["rows"], c["out_bytes"], c["zero_used"] = len(ref["rows"]), 0, False
+            cases.append(c)
+    finally:
+        rng, MAX_SIZE_LOG2 = saved
+    return cases
+
+
+def summary_coverage_table(cases) -> str:
+    lines = [f"{len(cases)} cases; most rows {max(c['rows'] for c in cases)} (limit {ROW_LIMIT})",
+             f"{'op':26s} {'n':>3s}  ci=0 ci=1   mk0 mk1 mk2   ov  cp  odd even  empty-hay  what 0/1/2/3"]
+    for op in SUMMARY_OPS:
+        cs = [c for c in cases if c["op"] == op]
+        lines.append(f"{op:26s} {len(cs):3d}  {sum(not c['ci'] for c in cs):4d} {sum(c['ci'] for c in cs):4d}   "
+                     + " ".join(f"{sum(c['mk'] == k for c in cs):3d}" for k in range(3))
+                     + f"  {sum(c['ov'] for c in cs):3d} {sum(c['cp'] for c in cs):3d}  {sum(c['off'] % 2 for c in cs):3d} "
+                     + f"{sum(1 - c['off'] % 2 for c in cs):4d}  {sum(any(len(h) == 0 for h in c['hays']) for c in cs):9d}  "
+                     + "/".join(str(sum(c['what'] == w for c in cs)) for w in range(4)))
+    for c in cases:
+        lines.append(f"  case {c['i']:3d} {c['op']:26s} {c['name']:7s} {c['kind']:8s} pats {len(c['pats']):5d} hays {len(c['hays']):5d} "
+                     f"bytes {sum(len(h) for h in c['hays']):8d} rows {c['rows']:8d}")
+    return "\n".join(lines)
+
+
+def reduce_reference(ref: dict, n_patterns: int) -> dict:
+    """the summaries of reference(case), reduced here: any / first per haystack (None: no match), the per-pattern totals"""
+    rows, counts = ref["rows"], ref["counts"]
+    at = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return {"total": len(rows), "counts": counts, "any": [n > 0 for n in counts],
+            "first": [tuple(int(v) for v in rows[at[h]]) if counts[h] else None for h in range(len(counts))],
+            "hist": np.bincount(rows[:, 0].astype(np.int64), minlength=n_patterns).astype(np.uint64)}
+
+
+def _run_summary_case(a, c: dict, ref: dict):
+    """-> None, or the first difference as text"""
+    hays, off, L, what = c["hays"], c["off"], c["uniform_len"], c["what"]
+    whole = b"".join(hays)
+    bounds = np.cumsum([0] + [len(h) for h in hays]).astype(np.uint64)
+    op, kw = c["op"], {"overlapping": c["ov"], "codepoints": c["cp"]}
+    want = reduce_reference(ref, len(c["pats"]))
+    bufs, s = [], None
+    try:
+        if op.startswith("summarize_device_") and op != "summarize_device_route":
+            bufs.append(_on_device(whole, off))
+            seg = {}
+            if op.endswith("_uniform"):
+                seg = {"n_hay": len(hays), "uniform_len": L}
+            elif op.endswith("_ragged"):
+                bufs.append(capi.DeviceBuffer(bounds.nbytes).upload(bounds.view(np.uint8)))
+                seg = {"n_hay": len(hays), "d_offsets": bufs[1].ptr}
+            s = a.summarize_device(bufs[0].ptr + off, len(whole), what, **seg, **kw)
+            device = True
+        else:
+            to_device = op == "summarize_device_route" or c["route"] == "device"
+            before = os.environ.get("ACX_SUMMARY_HOST_MAX")
+            os.environ["ACX_SUMMARY_HOST_MAX"] = "0" if to_device else str(1 << 40)
+            try:
+                if op == "summarize_batch":
+                    s = a.summarize_batch(hays, what, **kw)
+                else:
+                    s = a.summarize(np.frombuffer(b"x" * off + whole, dtype=np.uint8)[off:], what, **kw)
+            finally:  # (the caller's own setting comes back)
+                if before is None:
+                    del os.environ["ACX_SUMMARY_HOST_MAX"]
+                else:
+                    os.environ["ACX_SUMMARY_HOST_MAX"] = before
+            device = to_device and len(whole) > 0  # (nothing is beyond a limit of 0 bytes but a non-empty input)
+        if s.on_device != device:
+            return f"on_device is {s.on_device}, the call should have been reduced {'in HBM' if device else 'on the host'}"
+        if s.total != want["total"]:
+            return f"total {s.total}, the reference has {want['total']} matches"
+        counts = [int(v) for v in s.counts()]
+        if counts != want["counts"]:
+            k = next((i for i in range(min(len(counts), len(want["counts"]))) if counts[i] != want["counts"][i]), -1)
+            return f"{len(counts)} counts for {len(want['counts'])} haystacks; haystack {k}: {counts[k]} matches, the reference has {want['counts'][k]}"
+        for part, bit in (("any", 1), ("first", 1), ("by_pattern", 2)):
+            if not what & bit:
+                try:
+                    getattr(s, part)()
+                except ValueError:
+                    continue
+                return f"{part}() of a summary made with what = {what} did not fail"
+        if what & 1:
+            got_any = [bool(v) for v in s.any()]
+            if got_any != want["any"]:
+                k = next(i for i in range(len(got_any)) if got_any[i] != want["any"][i])
+                return f"any[{k}] is {got_any[k]}, haystack {k} ({len(hays[k])} bytes) has {want['counts'][k]} matches"
+            f = s.first()
+            got_first = [None if int(r["pattern"]) == capi.NO_MATCH else (int(r["pattern"]), int(r["start"]), int(r["end"])) for r in f]
+            if got_first != want["first"]:
+                k = next(i for i in range(len(got_first)) if got_first[i] != want["first"][i])
+                return f"first[{k}] is {got_first[k]}, the reference has {want['first'][k]}"
+        if what & 2:
+            h = s.by_pattern()
+            if not np.array_equal(h, want["hist"]):
+                p = int(np.nonzero(h != want["hist"])[0][0]) if len(h) == len(want["hist"]) else -1
+                return f"by_pattern[{p}] is {int(h[p])}, the reference has {int(want['hist'][p])} ({len(h)} entries for {len(want['hist'])} patterns)"
+        if bufs and not np.array_equal(bufs[0].download(off + len(whole)), np.frombuffer(bytes(off) + whole, dtype=np.uint8)):
+            return "the caller's device buffer was written"
+    finally:
+        if s is not None:
+            s.free()
+        for b in bufs:
+            b.free()
+    return None
+
+
+def run_summary(cases):
+    """-> (ran, failures, skipped, build_errors), as run_surface: every case through the C ABI against the reduced reference"""
+    ran = fails = skipped = build_errors = 0
+    for c in cases:
+        tag = (f"{c['i']:3d} {c['op']:24s} {c['name']:7s} {c['kind']:8s} pats {len(c['pats']):5d} hays {len(c['hays']):5d} bytes "
+               f"{sum(len(h) for h in c['hays']):8d} mk {c['mk']} ci {int(c['ci'])} ov {int(c['ov'])} cp {int(c['cp'])} off {c['off']:2d} "
+               f"what {c['what']} kernel {c['kernel']} rows {c['rows']}")
+        if c["rows"] > ROW_LIMIT:
+            print("skip", tag, flush=True)
+            skipped += 1
+            continue
+        try:
+            a = capi.Automaton(c["pats"], c["mk"], kernel=c["kernel"], ascii_case_insensitive=c["ci"])
+        except (capi.AcxError, ValueError, MemoryError) as e:
+            print("FAIL", tag, "build error:", e, flush=True)
+            build_errors += 1; fails += 1
+            continue
+        t0 = time.time()
+        try:
+            diff = _run_summary_case(a, c, reference(c))
+        except (capi.AcxError, ValueError, MemoryError) as e:
+            diff = f"error: {e}"
+        a.close()
+        ran += 1
+        print(f"{'FAIL' if diff else 'ok  '} {tag} {time.time() - t0:.2f} s", flush=True)
+        if diff:
+            print("    ", diff, flush=True)
+            fails += 1
+    return ran, fails, skipped, build_errors
+
+
+SUMMARY_N, SUMMARY_SEED = 72, 20261017  # what tests/test_gpu_summary.py runs a slice of and tests/test_summary_cpu.py checks
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "summary":
+        args = [x for x in sys.argv[2:] if x != "--plan-only"]
+        plan = plan_summary(int(args[0]) if args else SUMMARY_N, int(args[1]) if len(args) > 1 else SUMMARY_SEED)
+        print(summary_coverage_table(plan), flush=True)
+        if "--plan-only" in sys.argv:
+            sys.exit(0)
+        ran, n_fails, skipped, build_errors = run_summary(plan)
+        print(f"{ran} cases ran, {n_fails} failures, {skipped} skipped, {build_errors} build errors")
+        sys.exit(1 if n_fails or skipped else 0)
     if len(sys.argv) > 1 and sys.argv[1] == "surface":
         args = [x for x in sys.argv[2:] if x != "--plan-only"]
         plan = plan_surface(int(args[0]) if args else SURFACE_N, int(args[1]) if len(args) > 1 else SURFACE_SEED)
