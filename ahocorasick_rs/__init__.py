@@ -16,6 +16,8 @@ from .ahocorasick_rs import (
     BytesAhoCorasick,
     MatchKind,
     Implementation,
+    MatchColumns,
+    Column,
 )
 
 __acx_amd__ = True
@@ -30,6 +32,9 @@ __all__ = [
     "BytesAhoCorasick",
     "MatchKind",
     "Implementation",
+    # Extension: the result of find_matches_as_columns / find_matches_as_columns_batch
+    "MatchColumns",
+    "Column",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

@@ -21,6 +21,8 @@ try:
         BytesAhoCorasick,
         MatchKind,
         Implementation,
+        MatchColumns,
+        Column,
     )
 except ImportError as e:  # pragma: no cover - build problem, fail loudly
     raise ImportError(
@@ -38,6 +40,9 @@ __all__ = [
     "BytesAhoCorasick",
     "MatchKind",
     "Implementation",
+    # Extension: the result of find_matches_as_columns / find_matches_as_columns_batch
+    "MatchColumns",
+    "Column",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

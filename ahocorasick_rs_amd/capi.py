@@ -29,6 +29,7 @@ KERNEL_NAMES = {1: "dfa_walk", 2: "prefilter"}
 BUILD_ASCII_CASE_INSENSITIVE = 1  # build flag (acx_build_ex)
 SUM_FIRST, SUM_BY_PATTERN = 1, 2  # acx_summarize: the parts beyond the total and the counts (ACX_SUM_*)
 NO_MATCH = (1 << 64) - 1  # the pattern of a haystack's first match when it has none
+COL_PATTERN, COL_START, COL_END, COL_ROW_OFFSETS = 0, 1, 2, 3  # acx_columns_data / acx_columns_copy (ACX_COL_*)
 ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
 MATCH_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u8"), ("end", "<u8")])
@@ -187,6 +188,19 @@ def lib() -> ctypes.CDLL:
     L.acx_free_summary.argtypes = [vp]
     L.acx_free_summary.restype = None
     L.acx_summarize_host.argtypes = [vp, u64, vp, u64, u64, ctypes.c_uint32, vp, vp, vp]
+    L.acx_find_columns.argtypes = [vp, vp, u64, vp, u64, i32, i32, ctypes.POINTER(vp)]
+    L.acx_find_columns_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, i32, ctypes.POINTER(vp)]
+    for name in ("count", "rows"):
+        getattr(L, "acx_columns_" + name).argtypes = [vp]
+        getattr(L, "acx_columns_" + name).restype = u64
+    L.acx_columns_on_device.argtypes = [vp]
+    L.acx_columns_data.argtypes = [vp, i32]
+    L.acx_columns_data.restype = vp
+    L.acx_columns_copy.argtypes = [vp, i32, vp]
+    L.acx_free_columns.argtypes = [vp]
+    L.acx_free_columns.restype = None
+    L.acx_split_host.argtypes = [vp, u64, vp, vp, vp]
+    L.acx_split_device.argtypes = [vp, u64, vp, vp, vp]
     _lib = L
     return L
 
@@ -571,6 +585,77 @@ def summarize_host(matches, counts: Optional[Sequence[int]], n_patterns: int, wh
             hist[:n_patterns] if what & SUM_BY_PATTERN else None)
 
 
+class DeviceColumns:
+    """The columns of Automaton.find_columns / find_columns_batch / find_columns_device (acx_columns_t): three int64
+    columns of `count` words and, for a batch, n_hay + 1 row offsets -- in HBM (on_device) or in host memory.  column()
+    copies one out; data_ptr() is where it lies (both wait for the split kernel)."""
+
+    def __init__(self, handle: int, batch: bool):
+        self._h = handle
+        self.batch = batch
+
+    @property
+    def count(self) -> int:
+        return int(lib().acx_columns_count(self._h))
+
+    @property
+    def rows(self) -> int:
+        return int(lib().acx_columns_rows(self._h))
+
+    @property
+    def on_device(self) -> bool:
+        return bool(lib().acx_columns_on_device(self._h))
+
+    def _words(self, which: int) -> int:
+        return self.rows + 1 if which == COL_ROW_OFFSETS else self.count
+
+    def data_ptr(self, which: int) -> int:
+        """host or device address of the column (by on_device); 0: the single form has no row offsets"""
+        return lib().acx_columns_data(self._h, which) or 0
+
+    def column(self, which: int) -> np.ndarray:
+        out = np.zeros(self._words(which), dtype=np.int64)
+        _check(lib().acx_columns_copy(self._h, which, out.ctypes.data if out.size else None))
+        return out
+
+    def pattern(self) -> np.ndarray:
+        return self.column(COL_PATTERN)
+
+    def start(self) -> np.ndarray:
+        return self.column(COL_START)
+
+    def end(self) -> np.ndarray:
+        return self.column(COL_END)
+
+    def row_offsets(self) -> Optional[np.ndarray]:
+        return self.column(COL_ROW_OFFSETS) if self.batch else None
+
+    def free(self) -> None:
+        if self._h:
+            lib().acx_free_columns(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def split_host(matches) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """acx_split_host: rows of (pattern, start, end) -> the three int64 columns, on the host, no device involved"""
+    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+    cols = [np.zeros(len(m), dtype=np.int64) for _ in range(3)]
+    _check(lib().acx_split_host(m.ctypes.data if len(m) else None, len(m), *[c.ctypes.data if len(m) else None for c in cols]))
+    return cols[0], cols[1], cols[2]
+
+
+def split_device(d_matches: int, n: int, d_pattern: int, d_start: int, d_end: int) -> None:
+    """acx_split_device: n records of 24 bytes at d_matches -> n words at each of the three device addresses (8-byte
+    alignment is all any of them needs); complete when it returns"""
+    _check(lib().acx_split_device(d_matches or None, n, d_pattern or None, d_start or None, d_end or None))
+
+
 def _replaced_bytes(h: int) -> bytes:
     buf = bytearray(int(lib().acx_replaced_len(h)))
     if buf:
@@ -762,6 +847,32 @@ class Automaton:
         _check(lib().acx_summarize_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
                                           int(codepoints), what, ctypes.byref(out)))
         return DeviceSummary(out.value, n_hay if (uniform_len or d_offsets) else 1, int(self.info.n_patterns))
+
+    # ---- matches as columns (acx_find_columns / acx_find_columns_device)
+    def find_columns(self, hay, overlapping: bool = False, codepoints: bool = False) -> DeviceColumns:
+        """find()'s matches as three int64 columns in host memory"""
+        a = np.ascontiguousarray(np.frombuffer(hay, dtype=np.uint8) if not isinstance(hay, np.ndarray) else hay)
+        out = ctypes.c_void_p()
+        _check(lib().acx_find_columns(self._h, a.ctypes.data if a.size else None, a.size, None, 0, int(overlapping),
+                                      int(codepoints), ctypes.byref(out)))
+        return DeviceColumns(out.value, False)
+
+    def find_columns_batch(self, haystacks: Sequence[bytes], overlapping: bool = False,
+                           codepoints: bool = False) -> DeviceColumns:
+        """find_batch()'s matches as columns in host memory, with the row offsets of the haystacks"""
+        hb, hoff = pack(haystacks)
+        out = ctypes.c_void_p()
+        _check(lib().acx_find_columns(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks),
+                                      int(overlapping), int(codepoints), ctypes.byref(out)))
+        return DeviceColumns(out.value, True)
+
+    def find_columns_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
+                            overlapping: bool = False, codepoints: bool = False) -> DeviceColumns:
+        """the haystack in HBM searched and its matches split into columns there; nothing but the total crosses the bus"""
+        out = ctypes.c_void_p()
+        _check(lib().acx_find_columns_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len,
+                                             int(overlapping), int(codepoints), ctypes.byref(out)))
+        return DeviceColumns(out.value, bool(uniform_len or d_offsets))
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

@@ -629,6 +629,22 @@ template <int K, bool BATCH> PyObject *bac_summary(PyObject *self_, PyObject *ar
      METH_VARARGS | METH_KEYWORDS,                                                                                              \
      "[extension] the per-pattern totals over all haystacks: the sum of self.count_by_pattern(h, overlapping)."}
 
+// matches as columns (defined behind the DLPack adapter below)
+template <bool BATCH> PyObject *ac_columns(PyObject *self_, PyObject *args, PyObject *kwargs);
+template <bool BATCH> PyObject *bac_columns(PyObject *self_, PyObject *args, PyObject *kwargs);
+#define ACX_COLUMNS_METHODS(fn)                                                                                                 \
+    {"find_matches_as_columns", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)),                        \
+     METH_VARARGS | METH_KEYWORDS,                                                                                              \
+     "[extension] find_matches_as_indexes(haystack, overlapping) as a MatchColumns: three int64 columns (pattern, start, "     \
+     "end) exported through DLPack, in host memory for a host haystack and in HBM on the automaton's device for a "            \
+     "__dlpack__ tensor there -- no tuple list, and for a tensor nothing but the number of matches crosses the bus.  The "     \
+     "call returns once that number is known; every accessor of a column, __dlpack__ included, waits for the split kernel "    \
+     "first, so a consumer on any stream sees finished data."},                                                                \
+    {"find_matches_as_columns_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<true>)),                   \
+     METH_VARARGS | METH_KEYWORDS,                                                                                              \
+     "[extension] find_matches_as_indexes_batch(haystacks, overlapping) as a MatchColumns with row_offsets: rows "             \
+     "row_offsets[h] .. row_offsets[h + 1] are haystack h's matches, their offsets local to it."}
+
 PyMethodDef ac_methods[] = {
     {"find_matches_as_indexes", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_find_indexes)),
      METH_VARARGS | METH_KEYWORDS,
@@ -651,6 +667,7 @@ PyMethodDef ac_methods[] = {
     {"replace_all_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_replace_all_batch)),
      METH_VARARGS | METH_KEYWORDS, "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
     ACX_SUMMARY_METHODS(ac_summary),
+    ACX_COLUMNS_METHODS(ac_columns),
     {"_info", ac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -942,6 +959,343 @@ template <int K, bool BATCH> PyObject *bac_summary(PyObject *self_, PyObject *ar
     return summary_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, K, BATCH, false);
 }
 
+// ---------------------------------------------------------------------------
+// matches as columns: find_matches_as_columns / _batch -> MatchColumns (acx_find_columns / acx_find_columns_device).
+// A MatchColumns owns the acx_columns_t; a Column is a view of one of its parts and keeps the MatchColumns alive; a DLPack
+// capsule -- and whatever tensor a consumer makes of it -- keeps the Column alive until the consumer calls its deleter.
+// ---------------------------------------------------------------------------
+PyTypeObject *MatchColumnsType = nullptr;
+PyTypeObject *ColumnType = nullptr;
+
+struct MatchColumnsObject {
+    PyObject_HEAD
+    acx_columns_t *c;
+    bool batch;
+    int device; // the automaton's ordinal (where device columns lie)
+};
+
+struct ColumnObject {
+    PyObject_HEAD
+    PyObject *owner; // the MatchColumns
+    int which;       // ACX_COL_*
+    int64_t len;
+};
+
+void mc_dealloc(PyObject *self) {
+    MatchColumnsObject *o = reinterpret_cast<MatchColumnsObject *>(self);
+    if (o->c) acx_free_columns(o->c); // (waits for the split kernel if nobody has: microseconds to a millisecond)
+    PyTypeObject *tp = Py_TYPE(self);
+    tp->tp_free(self);
+    Py_DECREF(tp);
+}
+
+void col_dealloc(PyObject *self) {
+    Py_XDECREF(reinterpret_cast<ColumnObject *>(self)->owner);
+    PyTypeObject *tp = Py_TYPE(self);
+    tp->tp_free(self);
+    Py_DECREF(tp);
+}
+
+acx_columns_t *col_handle(ColumnObject *o) { return reinterpret_cast<MatchColumnsObject *>(o->owner)->c; }
+int col_device(ColumnObject *o) { return reinterpret_cast<MatchColumnsObject *>(o->owner)->device; }
+
+// the part's address once the split is done (GIL released around the wait); sets the exception
+const int64_t *col_data(ColumnObject *o) {
+    const int64_t *p;
+    Py_BEGIN_ALLOW_THREADS
+    p = acx_columns_data(col_handle(o), o->which);
+    Py_END_ALLOW_THREADS
+    if (!p) PyErr_SetString(PyExc_RuntimeError, "the column's device work failed");
+    return p;
+}
+
+PyObject *mc_column(PyObject *self_, int which) {
+    MatchColumnsObject *self = reinterpret_cast<MatchColumnsObject *>(self_);
+    if (which == ACX_COL_ROW_OFFSETS && !self->batch) Py_RETURN_NONE;
+    ColumnObject *col = reinterpret_cast<ColumnObject *>(ColumnType->tp_alloc(ColumnType, 0));
+    if (!col) return nullptr;
+    Py_INCREF(self_);
+    col->owner = self_;
+    col->which = which;
+    col->len = (int64_t)(which == ACX_COL_ROW_OFFSETS ? acx_columns_rows(self->c) + 1 : acx_columns_count(self->c));
+    return reinterpret_cast<PyObject *>(col);
+}
+PyObject *mc_get_pattern(PyObject *s, void *) { return mc_column(s, ACX_COL_PATTERN); }
+PyObject *mc_get_start(PyObject *s, void *) { return mc_column(s, ACX_COL_START); }
+PyObject *mc_get_end(PyObject *s, void *) { return mc_column(s, ACX_COL_END); }
+PyObject *mc_get_row_offsets(PyObject *s, void *) { return mc_column(s, ACX_COL_ROW_OFFSETS); }
+PyObject *mc_get_device(PyObject *s, void *) {
+    acx_columns_t *c = reinterpret_cast<MatchColumnsObject *>(s)->c;
+    if (!acx_columns_on_device(c)) Py_RETURN_NONE;
+    return PyLong_FromLong(reinterpret_cast<MatchColumnsObject *>(s)->device);
+}
+Py_ssize_t mc_len(PyObject *s) { return (Py_ssize_t)acx_columns_count(reinterpret_cast<MatchColumnsObject *>(s)->c); }
+
+// exactly what find_matches_as_indexes / _batch returns for the same arguments
+PyObject *mc_tolist(PyObject *self_, PyObject *) {
+    MatchColumnsObject *self = reinterpret_cast<MatchColumnsObject *>(self_);
+    const uint64_t n = acx_columns_count(self->c), rows = acx_columns_rows(self->c);
+    std::vector<int64_t> col[3], ro;
+    int rc = ACX_OK;
+    Py_BEGIN_ALLOW_THREADS
+    for (int k = 0; k < 3 && rc == ACX_OK; k++) {
+        col[k].resize((size_t)n);
+        rc = acx_columns_copy(self->c, k, col[k].data());
+    }
+    if (rc == ACX_OK && self->batch) {
+        ro.resize((size_t)rows + 1);
+        rc = acx_columns_copy(self->c, ACX_COL_ROW_OFFSETS, ro.data());
+    }
+    Py_END_ALLOW_THREADS
+    if (rc != ACX_OK) return raise_acx(rc);
+    auto rows_list = [&](uint64_t b, uint64_t e) -> PyObject * {
+        PyObject *list = PyList_New((Py_ssize_t)(e - b));
+        for (uint64_t i = b; list && i < e; i++) {
+            PyObject *t = Py_BuildValue("(KKK)", (unsigned long long)col[0][i], (unsigned long long)col[1][i],
+                                        (unsigned long long)col[2][i]);
+            if (!t) { Py_CLEAR(list); break; }
+            PyList_SET_ITEM(list, (Py_ssize_t)(i - b), t);
+        }
+        return list;
+    };
+    if (!self->batch) return rows_list(0, n);
+    PyObject *outer = PyList_New((Py_ssize_t)rows);
+    for (uint64_t h = 0; outer && h < rows; h++) {
+        PyObject *inner = rows_list((uint64_t)ro[h], (uint64_t)ro[h + 1]);
+        if (!inner) { Py_CLEAR(outer); break; }
+        PyList_SET_ITEM(outer, (Py_ssize_t)h, inner);
+    }
+    return outer;
+}
+
+PyGetSetDef mc_getset[] = {
+    {"pattern", mc_get_pattern, nullptr, "Column: the pattern index of every match", nullptr},
+    {"start", mc_get_start, nullptr, "Column: where every match starts", nullptr},
+    {"end", mc_get_end, nullptr, "Column: where every match ends", nullptr},
+    {"row_offsets", mc_get_row_offsets, nullptr,
+     "None for one haystack; for a batch a Column of len(haystacks) + 1 entries: rows row_offsets[h] .. row_offsets[h + 1] "
+     "are haystack h's matches", nullptr},
+    {"device", mc_get_device, nullptr, "None: the columns are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+PyMethodDef mc_methods[] = {
+    {"tolist", mc_tolist, METH_NOARGS,
+     "what find_matches_as_indexes / find_matches_as_indexes_batch returns for the same arguments (copies device columns "
+     "to the host)"},
+    {nullptr, nullptr, 0, nullptr},
+};
+PyType_Slot mc_slots[] = {
+    {Py_tp_dealloc, reinterpret_cast<void *>(mc_dealloc)},
+    {Py_tp_methods, mc_methods},
+    {Py_tp_getset, mc_getset},
+    {Py_sq_length, reinterpret_cast<void *>(mc_len)},
+    {Py_tp_doc, const_cast<char *>(
+        "The matches of find_matches_as_columns / _batch: .pattern, .start, .end (and .row_offsets for a batch) are Column "
+        "objects of len(self) int64 entries, where the search ran (.device).  Every accessor of a column waits for the "
+        "split kernel first.")},
+    {0, nullptr},
+};
+
+Py_ssize_t col_len(PyObject *s) { return (Py_ssize_t)reinterpret_cast<ColumnObject *>(s)->len; }
+
+PyObject *col_dlpack_device(PyObject *self_, PyObject *) {
+    acx_columns_t *c = col_handle(reinterpret_cast<ColumnObject *>(self_));
+    if (!acx_columns_on_device(c)) return Py_BuildValue("(ii)", (int)kDLCPU, 0);
+    return Py_BuildValue("(ii)", (int)kDLROCM, col_device(reinterpret_cast<ColumnObject *>(self_)));
+}
+
+// what a capsule points at: the tensor, its shape and stride, and the reference that keeps the data alive
+struct ColumnExport {
+    DLManagedTensorC mt;
+    int64_t shape[1], strides[1];
+    PyObject *column;
+};
+
+void column_export_deleter(DLManagedTensorC *mt) { // (called by the consumer, from any thread, with or without the GIL)
+    ColumnExport *e = static_cast<ColumnExport *>(mt->manager_ctx);
+    if (Py_IsInitialized()) { // (a tensor that outlives the interpreter: its column goes with the process)
+        const PyGILState_STATE g = PyGILState_Ensure();
+        Py_DECREF(e->column);
+        PyGILState_Release(g);
+    }
+    delete e;
+}
+
+void column_capsule_destructor(PyObject *cap) { // a capsule nobody consumed still owns the export
+    if (!PyCapsule_IsValid(cap, "dltensor")) return;
+    DLManagedTensorC *mt = static_cast<DLManagedTensorC *>(PyCapsule_GetPointer(cap, "dltensor"));
+    if (mt && mt->deleter) mt->deleter(mt);
+}
+
+// __dlpack__(stream=None, **ignored): the split is waited for on the host before the capsule is made, so the data is
+// finished for a consumer on any stream and `stream` needs no work
+PyObject *col_dlpack(PyObject *self_, PyObject *args, PyObject *) {
+    if (PyTuple_GET_SIZE(args) > 1) {
+        PyErr_SetString(PyExc_TypeError, "__dlpack__ takes at most one positional argument (stream)");
+        return nullptr;
+    }
+    ColumnObject *self = reinterpret_cast<ColumnObject *>(self_);
+    const int64_t *p = col_data(self);
+    if (!p) return nullptr;
+    acx_columns_t *c = col_handle(self);
+    ColumnExport *e = new (std::nothrow) ColumnExport();
+    if (!e) return PyErr_NoMemory();
+    e->shape[0] = self->len;
+    e->strides[0] = 1;
+    e->mt.dl_tensor.data = const_cast<int64_t *>(p);
+    e->mt.dl_tensor.device = acx_columns_on_device(c) ? DLDeviceC{kDLROCM, col_device(self)} : DLDeviceC{kDLCPU, 0};
+    e->mt.dl_tensor.ndim = 1;
+    e->mt.dl_tensor.dtype = DLDataTypeC{0 /* kDLInt */, 64, 1};
+    e->mt.dl_tensor.shape = e->shape;
+    e->mt.dl_tensor.strides = e->strides;
+    e->mt.dl_tensor.byte_offset = 0;
+    e->mt.manager_ctx = e;
+    e->mt.deleter = column_export_deleter;
+    e->column = self_;
+    PyObject *cap = PyCapsule_New(&e->mt, "dltensor", column_capsule_destructor);
+    if (!cap) { delete e; return nullptr; }
+    Py_INCREF(self_);
+    return cap;
+}
+
+// the buffer protocol of a host column: read-only, format "q"
+int col_getbuffer(PyObject *self_, Py_buffer *view, int flags) {
+    ColumnObject *self = reinterpret_cast<ColumnObject *>(self_);
+    view->obj = nullptr;
+    if (acx_columns_on_device(col_handle(self))) {
+        PyErr_SetString(PyExc_BufferError, "the column is in device memory: use __dlpack__");
+        return -1;
+    }
+    if (flags & PyBUF_WRITABLE) {
+        PyErr_SetString(PyExc_BufferError, "the column is read-only");
+        return -1;
+    }
+    const int64_t *p = col_data(self);
+    if (!p) return -1;
+    static Py_ssize_t one_stride = 8;
+    view->buf = const_cast<int64_t *>(p);
+    view->len = (Py_ssize_t)self->len * 8;
+    view->itemsize = 8;
+    view->readonly = 1;
+    view->ndim = 1;
+    view->format = (flags & PyBUF_FORMAT) ? const_cast<char *>("q") : nullptr;
+    view->shape = (flags & PyBUF_ND) ? reinterpret_cast<Py_ssize_t *>(&self->len) : nullptr;
+    view->strides = (flags & PyBUF_STRIDES) == PyBUF_STRIDES ? &one_stride : nullptr;
+    view->suboffsets = nullptr;
+    view->internal = nullptr;
+    Py_INCREF(self_);
+    view->obj = self_;
+    return 0;
+}
+
+PyMethodDef col_methods[] = {
+    {"__dlpack__", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(col_dlpack)), METH_VARARGS | METH_KEYWORDS,
+     "__dlpack__(stream=None, **ignored) -> a 'dltensor' capsule of the column: 1-D, int64, contiguous.  Waits for the split "
+     "kernel first: the data is finished for a consumer on any stream.  The capsule, and the tensor made of it, keep the "
+     "result alive."},
+    {"__dlpack_device__", col_dlpack_device, METH_NOARGS, "(kDLCPU, 0) or (kDLROCM, ordinal)"},
+    {nullptr, nullptr, 0, nullptr},
+};
+PyType_Slot col_slots[] = {
+    {Py_tp_dealloc, reinterpret_cast<void *>(col_dealloc)},
+    {Py_tp_methods, col_methods},
+    {Py_sq_length, reinterpret_cast<void *>(col_len)},
+    {Py_bf_getbuffer, reinterpret_cast<void *>(col_getbuffer)},
+    {Py_tp_doc, const_cast<char *>(
+        "One int64 column of a MatchColumns: len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
+        "copy) and, in host memory, the buffer protocol (format 'q', read-only).")},
+    {0, nullptr},
+};
+
+PyObject *columns_object(acx_columns_t *c, bool batch, int device) {
+    MatchColumnsObject *o = reinterpret_cast<MatchColumnsObject *>(MatchColumnsType->tp_alloc(MatchColumnsType, 0));
+    if (!o) { acx_free_columns(c); return nullptr; }
+    o->c = c;
+    o->batch = batch;
+    o->device = device;
+    return reinterpret_cast<PyObject *>(o);
+}
+
+// find_matches_as_columns / _batch of both classes: utf8 = the str class (code-point offsets when the text is not ASCII).
+// The haystack arguments and their errors are find_matches_as_indexes' / _batch's.
+PyObject *columns_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool batch, bool utf8) {
+    const char *kw[] = {batch ? "haystacks" : "haystack", "overlapping", nullptr};
+    PyObject *hay = nullptr, *ov = nullptr;
+    int overlapping = 0;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, batch ? "O|O:find_matches_as_columns_batch" : "O|O:find_matches_as_columns",
+                                     const_cast<char **>(kw), &hay, &ov))
+        return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    acx_columns_t *c = nullptr;
+    int rc;
+    auto host = [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t n, int codepoints) {
+        Py_BEGIN_ALLOW_THREADS
+        rc = acx_find_columns(a, p, len, off, n, overlapping, codepoints, &c);
+        Py_END_ALLOW_THREADS
+    };
+    if (batch) {
+        PyObject *seq = PySequence_Fast(hay, "haystacks must be a sequence");
+        if (!seq) return nullptr;
+        const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
+        std::vector<uint64_t> off((size_t)n + 1, 0);
+        std::vector<uint8_t> blob;
+        bool all_ascii = true;
+        for (Py_ssize_t i = 0; i < n; i++) {
+            PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
+            if (utf8) {
+                if (!PyUnicode_Check(it)) {
+                    PyErr_Format(PyExc_TypeError, "'%.100s' object cannot be converted to 'PyString'", Py_TYPE(it)->tp_name);
+                    Py_DECREF(seq); return nullptr;
+                }
+                Py_ssize_t len; const char *s = PyUnicode_AsUTF8AndSize(it, &len);
+                if (!s) { Py_DECREF(seq); return nullptr; }
+                all_ascii = all_ascii && PyUnicode_IS_ASCII(it);
+                blob.insert(blob.end(), s, s + len);
+            } else {
+                Py_buffer v;
+                if (!get_bytes_view(it, &v)) { Py_DECREF(seq); return nullptr; }
+                blob.insert(blob.end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
+                PyBuffer_Release(&v);
+            }
+            off[(size_t)i + 1] = blob.size();
+        }
+        Py_DECREF(seq);
+        blob.push_back(0);
+        host(blob.data(), off[(size_t)n], off.data(), (uint64_t)n, (utf8 && !all_ascii) ? 1 : 0);
+    } else if (utf8) {
+        const char *p; Py_ssize_t len;
+        if (!str_view(hay, &p, &len)) return nullptr;
+        host(reinterpret_cast<const uint8_t *>(p), (uint64_t)len, nullptr, 0, PyUnicode_IS_ASCII(hay) ? 0 : 1);
+    } else if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
+        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
+        PyObject *cap = dlpack_view(hay, acx_automaton_device(a), &p, &len, &on_device);
+        if (!cap) return nullptr;
+        if (on_device) { // searched and split where it lies
+            Py_BEGIN_ALLOW_THREADS
+            rc = acx_device_synchronize_on(acx_automaton_device(a)); // (the producer's kernels may still write it)
+            if (rc == ACX_OK) rc = acx_find_columns_device(a, p, len, nullptr, 0, 0, overlapping, 0, &c);
+            Py_END_ALLOW_THREADS
+        } else {
+            host(p, len, nullptr, 0, 0);
+        }
+        dlpack_release(cap);
+    } else {
+        Py_buffer v;
+        if (!get_bytes_view(hay, &v)) return nullptr;
+        host((const uint8_t *)v.buf, (uint64_t)v.len, nullptr, 0, 0);
+        PyBuffer_Release(&v);
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    return columns_object(c, batch, acx_automaton_device(a));
+}
+
+template <bool BATCH> PyObject *ac_columns(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return columns_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, BATCH, true);
+}
+template <bool BATCH> PyObject *bac_columns(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return columns_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, BATCH, false);
+}
+
 // device-resident search -> list of tuples (the records come back with ONE D2H copy of the result)
 PyObject *find_on_device(acx_automaton_t *a, const uint8_t *d_hay, uint64_t len, int overlapping) {
     acx_result_t *r = nullptr;
@@ -1071,6 +1425,7 @@ PyMethodDef bac_methods[] = {
     {"replace_all_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(bac_replace_all_batch)),
      METH_VARARGS | METH_KEYWORDS, "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
     ACX_SUMMARY_METHODS(bac_summary),
+    ACX_COLUMNS_METHODS(bac_columns),
     {"_info", bac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -1110,6 +1465,20 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
                             bac_slots};
     PyObject *ac_t = PyType_FromSpec(&ac_spec);
     PyObject *bac_t = PyType_FromSpec(&bac_spec);
+    PyType_Spec mc_spec = {"ahocorasick_rs.MatchColumns", sizeof(MatchColumnsObject), 0,
+                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, mc_slots};
+    PyType_Spec col_spec = {"ahocorasick_rs.Column", sizeof(ColumnObject), 0,
+                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, col_slots};
+    MatchColumnsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mc_spec));
+    ColumnType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&col_spec));
+    if (!MatchColumnsType || !ColumnType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
+    for (PyTypeObject *tp : {MatchColumnsType, ColumnType}) { // (the module holds one reference, the globals the other)
+        Py_INCREF(tp);
+        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : "MatchColumns", reinterpret_cast<PyObject *>(tp)) < 0) {
+            Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);
+            return nullptr;
+        }
+    }
     if (!ac_t || !bac_t || PyModule_AddObject(m, "AhoCorasick", ac_t) < 0 ||
         PyModule_AddObject(m, "BytesAhoCorasick", bac_t) < 0) {
         Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);

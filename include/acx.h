@@ -28,6 +28,8 @@ extern "C" {
  *     addendum (additive: the number stays, a binding written against 11 still loads): acx_summarize / acx_summarize_device /
  *     acx_summarize_host, ACX_SUM_FIRST / ACX_SUM_BY_PATTERN and the acx_summary_t accessors (acx_summary_total, _on_device,
  *     _counts, _any, _first, _by_pattern, _device_counts, _device_any, _device_first, _device_by_pattern, acx_free_summary);
+ *     second addendum (additive as well): acx_find_columns / acx_find_columns_device, ACX_COL_*, the acx_columns_t accessors
+ *     (acx_columns_count, _rows, _on_device, _data, _copy, acx_free_columns), acx_split_host / acx_split_device;
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -413,6 +415,49 @@ void acx_free_summary(acx_summary_t *r);
 int acx_summarize_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts /* NULL: one haystack */,
                        uint64_t n_hay, uint64_t n_patterns, uint32_t what,
                        uint64_t *any_bits, acx_match_t *first, uint64_t *by_pattern);
+
+/* ---- columns: the matches of a find as three int64 columns (pattern, start, end) instead of records, where the search
+ * ran.  Row i of the columns is match i of acx_find / acx_find_batch / acx_find_device for the same arguments (same match
+ * kind, `overlapping`, `codepoints`).  A batch (offsets != NULL; d_offsets or uniform_len on the device) also has
+ * ACX_COL_ROW_OFFSETS: n_hay + 1 words, rows row_offsets[h] .. row_offsets[h + 1] are haystack h's matches, their offsets
+ * local to it (the CSR form; the exclusive prefix of acx_find_batch's counts).
+ * Two routes.  acx_find_columns: the find runs as acx_find / acx_find_batch do (the small-call kernel, the in-place read,
+ * the staged pipeline), the records are split on the host (acx_split_host) and the columns are host memory.
+ * acx_find_columns_device: acx_find_device's pipeline, then a split kernel (and, for a batch, the scan of the counts) on
+ * the same stream; the columns and the row offsets are in HBM on the automaton's device and only the number of matches
+ * crosses to the host.  The call returns when that number is known; the kernels may still run, and acx_columns_data /
+ * acx_columns_copy wait for them -- a pointer they return is to finished data, whatever stream reads it.
+ * Memory in HBM: the find writes its records (24 bytes per match) and the split writes the columns (24 bytes per match)
+ * before the records go back to the library's buffer cache -- which happens as soon as the split is queued, behind an
+ * event, never later than acx_free_columns.  The peak is therefore TWICE the result (until the find's write kernel writes
+ * columns itself), the steady state once.
+ * An empty column still has a valid, non-null address.  acx_columns_rows is 0 in the single form (and for an empty
+ * batch: there acx_columns_data(c, ACX_COL_ROW_OFFSETS) is non-null and holds one 0). */
+#define ACX_COL_PATTERN 0
+#define ACX_COL_START 1
+#define ACX_COL_END 2
+#define ACX_COL_ROW_OFFSETS 3
+typedef struct acx_columns acx_columns_t;
+int acx_find_columns(acx_automaton_t *a, const uint8_t *hay, uint64_t len,
+                     const uint64_t *offsets /* NULL: one haystack */, uint64_t n_hay,
+                     int overlapping, int codepoints, acx_columns_t **out);
+int acx_find_columns_device(acx_automaton_t *a, const void *d_hay, uint64_t len,
+                            const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
+                            int overlapping, int codepoints, acx_columns_t **out);
+uint64_t acx_columns_count(const acx_columns_t *c);   /* matches = words per column; valid at return */
+uint64_t acx_columns_rows(const acx_columns_t *c);    /* haystacks of a batch; 0: single form        */
+int acx_columns_on_device(const acx_columns_t *c);    /* 1: the columns are in HBM, 0: host memory   */
+/* host or device pointer by acx_columns_on_device; waits for the split.  NULL: no such column (row offsets of the single
+ * form) or the wait failed.  Valid until acx_free_columns. */
+const int64_t *acx_columns_data(const acx_columns_t *c, int which);
+int acx_columns_copy(const acx_columns_t *c, int which, int64_t *host_dst);
+void acx_free_columns(acx_columns_t *c);
+/* the split itself.  acx_split_host: host memory, no device needed.  acx_split_device: the kernel's raw entry point for
+ * callers that hold the result of acx_find_device (its records: acx_result_device_matches) -- records and columns in HBM on one device, 8-byte
+ * alignment is all either needs (a sub-range that begins at an odd record lies at 8 mod 16), nothing may overlap;
+ * synchronous: the columns are complete when it returns.  n = 0: nothing is touched. */
+int acx_split_host(const acx_match_t *m, uint64_t n, int64_t *pattern, int64_t *start, int64_t *end);
+int acx_split_device(const acx_match_t *d_m, uint64_t n, int64_t *d_pattern, int64_t *d_start, int64_t *d_end);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
