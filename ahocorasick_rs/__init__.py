@@ -18,6 +18,7 @@ from .ahocorasick_rs import (
     Implementation,
     MatchColumns,
     Column,
+    PatternCounts,
 )
 
 __acx_amd__ = True
@@ -35,6 +36,8 @@ __all__ = [
     # Extension: the result of find_matches_as_columns / find_matches_as_columns_batch
     "MatchColumns",
     "Column",
+    # Extension: the result of count_by_pattern_sparse_batch
+    "PatternCounts",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

@@ -23,6 +23,7 @@ try:
         Implementation,
         MatchColumns,
         Column,
+        PatternCounts,
     )
 except ImportError as e:  # pragma: no cover - build problem, fail loudly
     raise ImportError(
@@ -43,6 +44,8 @@ __all__ = [
     # Extension: the result of find_matches_as_columns / find_matches_as_columns_batch
     "MatchColumns",
     "Column",
+    # Extension: the result of count_by_pattern_sparse_batch
+    "PatternCounts",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

@@ -30,6 +30,7 @@ BUILD_ASCII_CASE_INSENSITIVE = 1  # build flag (acx_build_ex)
 SUM_FIRST, SUM_BY_PATTERN = 1, 2  # acx_summarize: the parts beyond the total and the counts (ACX_SUM_*)
 NO_MATCH = (1 << 64) - 1  # the pattern of a haystack's first match when it has none
 COL_PATTERN, COL_START, COL_END, COL_ROW_OFFSETS = 0, 1, 2, 3  # acx_columns_data / acx_columns_copy (ACX_COL_*)
+TALLY_ROW_OFFSETS, TALLY_PATTERN, TALLY_COUNT = 0, 1, 2  # acx_tally_data / acx_tally_copy (ACX_TALLY_*)
 ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
 MATCH_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u8"), ("end", "<u8")])
@@ -201,6 +202,19 @@ def lib() -> ctypes.CDLL:
     L.acx_free_columns.restype = None
     L.acx_split_host.argtypes = [vp, u64, vp, vp, vp]
     L.acx_split_device.argtypes = [vp, u64, vp, vp, vp]
+    L.acx_tally.argtypes = [vp, vp, u64, vp, u64, i32, ctypes.POINTER(vp)]
+    L.acx_tally_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, ctypes.POINTER(vp)]
+    for name in ("nnz", "rows"):
+        getattr(L, "acx_tally_" + name).argtypes = [vp]
+        getattr(L, "acx_tally_" + name).restype = u64
+    L.acx_tally_on_device.argtypes = [vp]
+    L.acx_tally_data.argtypes = [vp, i32]
+    L.acx_tally_data.restype = vp
+    L.acx_tally_copy.argtypes = [vp, i32, vp]
+    L.acx_free_tally.argtypes = [vp]
+    L.acx_free_tally.restype = None
+    L.acx_tally_host.argtypes = [vp, u64, vp, u64, vp, vp, vp, ctypes.POINTER(u64)]
+    L.acx_tally_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, ctypes.POINTER(u64)]
     _lib = L
     return L
 
@@ -656,6 +670,82 @@ def split_device(d_matches: int, n: int, d_pattern: int, d_start: int, d_end: in
     _check(lib().acx_split_device(d_matches or None, n, d_pattern or None, d_start or None, d_end or None))
 
 
+class DeviceTally:
+    """The result of Automaton.tally / tally_device (acx_tally_t): per-haystack pattern counts in CSR form -- rows + 1 row
+    offsets, nnz patterns (ascending within a row) and nnz counts, int64 -- in HBM (on_device) or in host memory.  part()
+    copies one out; data_ptr() is where it lies (both wait for the device stage)."""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    @property
+    def nnz(self) -> int:
+        return int(lib().acx_tally_nnz(self._h))
+
+    @property
+    def rows(self) -> int:
+        return int(lib().acx_tally_rows(self._h))
+
+    @property
+    def on_device(self) -> bool:
+        return bool(lib().acx_tally_on_device(self._h))
+
+    def data_ptr(self, which: int) -> int:
+        """host or device address of the part (by on_device)"""
+        return lib().acx_tally_data(self._h, which) or 0
+
+    def part(self, which: int) -> np.ndarray:
+        out = np.zeros(self.rows + 1 if which == TALLY_ROW_OFFSETS else self.nnz, dtype=np.int64)
+        _check(lib().acx_tally_copy(self._h, which, out.ctypes.data if out.size else None))
+        return out
+
+    def row_offsets(self) -> np.ndarray:
+        return self.part(TALLY_ROW_OFFSETS)
+
+    def pattern(self) -> np.ndarray:
+        return self.part(TALLY_PATTERN)
+
+    def count(self) -> np.ndarray:
+        return self.part(TALLY_COUNT)
+
+    def free(self) -> None:
+        if self._h:
+            lib().acx_free_tally(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def tally_host(matches, counts: Sequence[int]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """acx_tally_host: rows of (pattern, start, end), counts[h] of them haystack h's -> (row_offsets, pattern, count) of the
+    CSR matrix of per-haystack pattern counts, on the host, no device involved.  ValueError (code EINVAL) when the counts do
+    not sum to the rows."""
+    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+    c = np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    ro = np.zeros(len(c) + 1, dtype=np.int64)
+    pat, cnt = np.zeros(len(m), dtype=np.int64), np.zeros(len(m), dtype=np.int64)
+    nnz = ctypes.c_uint64()
+    _check(lib().acx_tally_host(m.ctypes.data if len(m) else None, len(m), c.ctypes.data if len(c) else None, len(c),
+                                ro.ctypes.data, pat.ctypes.data if len(m) else None, cnt.ctypes.data if len(m) else None,
+                                ctypes.byref(nnz)))
+    return ro, pat[:nnz.value], cnt[:nnz.value]
+
+
+def tally_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, n_patterns: int, d_row_offsets: int, d_pattern: int,
+                      d_count: int) -> int:
+    """acx_tally_rows_device: the device stage alone -- n records of 24 bytes at d_records, n_hay counts at d_counts -> n_hay
+    + 1 row offsets and nnz patterns and counts at the three device addresses (room for n words each); returns nnz;
+    complete when it returns"""
+    nnz = ctypes.c_uint64()
+    _check(lib().acx_tally_rows_device(d_records or None, n, d_counts or None, n_hay, n_patterns, d_row_offsets or None,
+                                       d_pattern or None, d_count or None, ctypes.byref(nnz)))
+    return int(nnz.value)
+
+
 def _replaced_bytes(h: int) -> bytes:
     buf = bytearray(int(lib().acx_replaced_len(h)))
     if buf:
@@ -873,6 +963,23 @@ class Automaton:
         _check(lib().acx_find_columns_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len,
                                              int(overlapping), int(codepoints), ctypes.byref(out)))
         return DeviceColumns(out.value, bool(uniform_len or d_offsets))
+
+    # ---- per-haystack pattern counts as a CSR matrix (acx_tally / acx_tally_device)
+    def tally(self, haystacks: Sequence[bytes], overlapping: bool = False) -> DeviceTally:
+        """which patterns occur in which haystack, and how often: host haystacks, a host result"""
+        hb, hoff = pack(haystacks)
+        out = ctypes.c_void_p()
+        _check(lib().acx_tally(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
+                               ctypes.byref(out)))
+        return DeviceTally(out.value)
+
+    def tally_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
+                     overlapping: bool = False) -> DeviceTally:
+        """the batch in HBM searched and reduced there; nothing but nnz crosses the bus"""
+        out = ctypes.c_void_p()
+        _check(lib().acx_tally_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
+                                      ctypes.byref(out)))
+        return DeviceTally(out.value)
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

@@ -632,6 +632,19 @@ template <int K, bool BATCH> PyObject *bac_summary(PyObject *self_, PyObject *ar
 // matches as columns (defined behind the DLPack adapter below)
 template <bool BATCH> PyObject *ac_columns(PyObject *self_, PyObject *args, PyObject *kwargs);
 template <bool BATCH> PyObject *bac_columns(PyObject *self_, PyObject *args, PyObject *kwargs);
+// per-haystack pattern counts as a CSR matrix (defined behind MatchColumns below)
+PyObject *ac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs);
+PyObject *bac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs);
+#define ACX_SPARSE_COUNTS_METHOD(fn)                                                                                           \
+    {"count_by_pattern_sparse_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn)),                         \
+     METH_VARARGS | METH_KEYWORDS,                                                                                             \
+     "[extension] count_by_pattern_sparse_batch(haystacks, overlapping=False, *, offsets=None, row_length=None) -> "           \
+     "PatternCounts: which patterns occur in which haystack and how often, as a CSR matrix of len(haystacks) x patterns "      \
+     "(row_offsets, pattern ascending within a row, count: int64 Columns that torch.sparse_csr_tensor takes as they are).  "   \
+     "haystacks: a sequence, as in every other _batch method, or ONE 1-D contiguous uint8 __dlpack__ tensor that holds the "   \
+     "rows back to back, cut by exactly one of offsets (a 1-D int64 __dlpack__ tensor of rows + 1 entries on the haystack's "  \
+     "device) and row_length (an int that divides the tensor's length).  A tensor on the automaton's device is searched and "  \
+     "reduced there and the result stays there; nothing but its size crosses the bus."}
 #define ACX_COLUMNS_METHODS(fn)                                                                                                 \
     {"find_matches_as_columns", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)),                        \
      METH_VARARGS | METH_KEYWORDS,                                                                                              \
@@ -668,6 +681,7 @@ PyMethodDef ac_methods[] = {
      METH_VARARGS | METH_KEYWORDS, "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
     ACX_SUMMARY_METHODS(ac_summary),
     ACX_COLUMNS_METHODS(ac_columns),
+    ACX_SPARSE_COUNTS_METHOD(ac_sparse_counts),
     {"_info", ac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -996,14 +1010,30 @@ void col_dealloc(PyObject *self) {
     Py_DECREF(tp);
 }
 
+// A Column's owner is a MatchColumns (which: ACX_COL_*) or a PatternCounts (which: ACX_TALLY_*; defined further down).
+PyTypeObject *PatternCountsType = nullptr;
+struct PatternCountsObject {
+    PyObject_HEAD
+    acx_tally_t *t;
+    int device;          // the automaton's ordinal (where device parts lie)
+    uint64_t n_patterns; // the matrix has this many columns
+};
+bool col_of_counts(ColumnObject *o) { return Py_TYPE(o->owner) == PatternCountsType; }
 acx_columns_t *col_handle(ColumnObject *o) { return reinterpret_cast<MatchColumnsObject *>(o->owner)->c; }
-int col_device(ColumnObject *o) { return reinterpret_cast<MatchColumnsObject *>(o->owner)->device; }
+acx_tally_t *col_tally(ColumnObject *o) { return reinterpret_cast<PatternCountsObject *>(o->owner)->t; }
+int col_device(ColumnObject *o) {
+    return col_of_counts(o) ? reinterpret_cast<PatternCountsObject *>(o->owner)->device
+                            : reinterpret_cast<MatchColumnsObject *>(o->owner)->device;
+}
+bool col_on_device(ColumnObject *o) {
+    return col_of_counts(o) ? acx_tally_on_device(col_tally(o)) != 0 : acx_columns_on_device(col_handle(o)) != 0;
+}
 
-// the part's address once the split is done (GIL released around the wait); sets the exception
+// the part's address once the device work is done (GIL released around the wait); sets the exception
 const int64_t *col_data(ColumnObject *o) {
     const int64_t *p;
     Py_BEGIN_ALLOW_THREADS
-    p = acx_columns_data(col_handle(o), o->which);
+    p = col_of_counts(o) ? acx_tally_data(col_tally(o), o->which) : acx_columns_data(col_handle(o), o->which);
     Py_END_ALLOW_THREADS
     if (!p) PyErr_SetString(PyExc_RuntimeError, "the column's device work failed");
     return p;
@@ -1099,8 +1129,7 @@ PyType_Slot mc_slots[] = {
 Py_ssize_t col_len(PyObject *s) { return (Py_ssize_t)reinterpret_cast<ColumnObject *>(s)->len; }
 
 PyObject *col_dlpack_device(PyObject *self_, PyObject *) {
-    acx_columns_t *c = col_handle(reinterpret_cast<ColumnObject *>(self_));
-    if (!acx_columns_on_device(c)) return Py_BuildValue("(ii)", (int)kDLCPU, 0);
+    if (!col_on_device(reinterpret_cast<ColumnObject *>(self_))) return Py_BuildValue("(ii)", (int)kDLCPU, 0);
     return Py_BuildValue("(ii)", (int)kDLROCM, col_device(reinterpret_cast<ColumnObject *>(self_)));
 }
 
@@ -1137,13 +1166,12 @@ PyObject *col_dlpack(PyObject *self_, PyObject *args, PyObject *) {
     ColumnObject *self = reinterpret_cast<ColumnObject *>(self_);
     const int64_t *p = col_data(self);
     if (!p) return nullptr;
-    acx_columns_t *c = col_handle(self);
     ColumnExport *e = new (std::nothrow) ColumnExport();
     if (!e) return PyErr_NoMemory();
     e->shape[0] = self->len;
     e->strides[0] = 1;
     e->mt.dl_tensor.data = const_cast<int64_t *>(p);
-    e->mt.dl_tensor.device = acx_columns_on_device(c) ? DLDeviceC{kDLROCM, col_device(self)} : DLDeviceC{kDLCPU, 0};
+    e->mt.dl_tensor.device = col_on_device(self) ? DLDeviceC{kDLROCM, col_device(self)} : DLDeviceC{kDLCPU, 0};
     e->mt.dl_tensor.ndim = 1;
     e->mt.dl_tensor.dtype = DLDataTypeC{0 /* kDLInt */, 64, 1};
     e->mt.dl_tensor.shape = e->shape;
@@ -1162,7 +1190,7 @@ PyObject *col_dlpack(PyObject *self_, PyObject *args, PyObject *) {
 int col_getbuffer(PyObject *self_, Py_buffer *view, int flags) {
     ColumnObject *self = reinterpret_cast<ColumnObject *>(self_);
     view->obj = nullptr;
-    if (acx_columns_on_device(col_handle(self))) {
+    if (col_on_device(self)) {
         PyErr_SetString(PyExc_BufferError, "the column is in device memory: use __dlpack__");
         return -1;
     }
@@ -1296,6 +1324,283 @@ template <bool BATCH> PyObject *bac_columns(PyObject *self_, PyObject *args, PyO
     return columns_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, BATCH, false);
 }
 
+// ---------------------------------------------------------------------------
+// per-haystack pattern counts: count_by_pattern_sparse_batch -> PatternCounts (acx_tally / acx_tally_device).  A
+// PatternCounts owns the acx_tally_t; its three parts are Columns with the lifetime chain of a MatchColumns' columns.
+// ---------------------------------------------------------------------------
+void pc_dealloc(PyObject *self) {
+    PatternCountsObject *o = reinterpret_cast<PatternCountsObject *>(self);
+    if (o->t) acx_free_tally(o->t); // (waits for the device stage's last kernel if nobody has)
+    PyTypeObject *tp = Py_TYPE(self);
+    tp->tp_free(self);
+    Py_DECREF(tp);
+}
+
+PyObject *pc_column(PyObject *self_, int which) {
+    PatternCountsObject *self = reinterpret_cast<PatternCountsObject *>(self_);
+    ColumnObject *col = reinterpret_cast<ColumnObject *>(ColumnType->tp_alloc(ColumnType, 0));
+    if (!col) return nullptr;
+    Py_INCREF(self_);
+    col->owner = self_;
+    col->which = which;
+    col->len = (int64_t)(which == ACX_TALLY_ROW_OFFSETS ? acx_tally_rows(self->t) + 1 : acx_tally_nnz(self->t));
+    return reinterpret_cast<PyObject *>(col);
+}
+PyObject *pc_get_row_offsets(PyObject *s, void *) { return pc_column(s, ACX_TALLY_ROW_OFFSETS); }
+PyObject *pc_get_pattern(PyObject *s, void *) { return pc_column(s, ACX_TALLY_PATTERN); }
+PyObject *pc_get_count(PyObject *s, void *) { return pc_column(s, ACX_TALLY_COUNT); }
+PyObject *pc_get_shape(PyObject *s, void *) {
+    PatternCountsObject *o = reinterpret_cast<PatternCountsObject *>(s);
+    return Py_BuildValue("(KK)", (unsigned long long)acx_tally_rows(o->t), (unsigned long long)o->n_patterns);
+}
+PyObject *pc_get_device(PyObject *s, void *) {
+    PatternCountsObject *o = reinterpret_cast<PatternCountsObject *>(s);
+    if (!acx_tally_on_device(o->t)) Py_RETURN_NONE;
+    return PyLong_FromLong(o->device);
+}
+Py_ssize_t pc_len(PyObject *s) { return (Py_ssize_t)acx_tally_nnz(reinterpret_cast<PatternCountsObject *>(s)->t); }
+
+// one list per haystack of (pattern, count), patterns ascending
+PyObject *pc_tolist(PyObject *self_, PyObject *) {
+    PatternCountsObject *self = reinterpret_cast<PatternCountsObject *>(self_);
+    const uint64_t nnz = acx_tally_nnz(self->t), rows = acx_tally_rows(self->t);
+    std::vector<int64_t> ro((size_t)rows + 1), pat((size_t)nnz), cnt((size_t)nnz);
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = acx_tally_copy(self->t, ACX_TALLY_ROW_OFFSETS, ro.data());
+    if (rc == ACX_OK) rc = acx_tally_copy(self->t, ACX_TALLY_PATTERN, pat.data());
+    if (rc == ACX_OK) rc = acx_tally_copy(self->t, ACX_TALLY_COUNT, cnt.data());
+    Py_END_ALLOW_THREADS
+    if (rc != ACX_OK) return raise_acx(rc);
+    PyObject *outer = PyList_New((Py_ssize_t)rows);
+    for (uint64_t h = 0; outer && h < rows; h++) {
+        const uint64_t b = (uint64_t)ro[h], e = (uint64_t)ro[h + 1];
+        PyObject *inner = PyList_New((Py_ssize_t)(e - b));
+        for (uint64_t i = b; inner && i < e; i++) {
+            PyObject *t = Py_BuildValue("(KK)", (unsigned long long)pat[i], (unsigned long long)cnt[i]);
+            if (!t) { Py_CLEAR(inner); break; }
+            PyList_SET_ITEM(inner, (Py_ssize_t)(i - b), t);
+        }
+        if (!inner) { Py_CLEAR(outer); break; }
+        PyList_SET_ITEM(outer, (Py_ssize_t)h, inner);
+    }
+    return outer;
+}
+
+PyGetSetDef pc_getset[] = {
+    {"row_offsets", pc_get_row_offsets, nullptr,
+     "Column of shape[0] + 1 entries from 0: entries row_offsets[h] .. row_offsets[h + 1] of pattern and count are haystack h's",
+     nullptr},
+    {"pattern", pc_get_pattern, nullptr, "Column of len(self) pattern indexes, strictly ascending within a row", nullptr},
+    {"count", pc_get_count, nullptr, "Column of len(self) counts, all >= 1", nullptr},
+    {"shape", pc_get_shape, nullptr, "(haystacks, patterns): the size of the matrix", nullptr},
+    {"device", pc_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+PyMethodDef pc_methods[] = {
+    {"tolist", pc_tolist, METH_NOARGS,
+     "one list per haystack of (pattern, count) tuples, patterns ascending (copies device parts to the host)"},
+    {nullptr, nullptr, 0, nullptr},
+};
+PyType_Slot pc_slots[] = {
+    {Py_tp_dealloc, reinterpret_cast<void *>(pc_dealloc)},
+    {Py_tp_methods, pc_methods},
+    {Py_tp_getset, pc_getset},
+    {Py_sq_length, reinterpret_cast<void *>(pc_len)},
+    {Py_tp_doc, const_cast<char *>(
+        "The result of count_by_pattern_sparse_batch: the CSR form of the haystacks x patterns matrix of match counts.  "
+        ".row_offsets, .pattern and .count are Column objects (int64) where the search ran (.device); len(self) is the "
+        "number of non-zero entries.  torch.sparse_csr_tensor(*map(torch.from_dlpack, (pc.row_offsets, pc.pattern, pc.count)), "
+        "size=pc.shape) is the matrix, without a copy.")},
+    {0, nullptr},
+};
+
+// The haystacks of a _batch method: a sequence of str (utf8) / buffers packed into one blob with its offsets, or one 1-D
+// uint8 __dlpack__ tensor that holds the rows back to back, cut by `offsets` (a 1-D int64 __dlpack__ tensor on the same
+// device) or by `row_length`.  Kept in one place so that the other _batch methods can take it.
+struct BatchInput {
+    // a sequence
+    std::vector<uint8_t> blob;
+    std::vector<uint64_t> off;
+    // a tensor: `len` bytes at `p`, `rows` rows; d_off (its device's offsets) or row_length
+    bool tensor = false, on_device = false;
+    const uint8_t *p = nullptr;
+    uint64_t len = 0, rows = 0, row_length = 0;
+    const uint64_t *t_off = nullptr;
+    PyObject *cap = nullptr, *cap_off = nullptr;
+    BatchInput() = default;
+    BatchInput(const BatchInput &) = delete;
+    BatchInput &operator=(const BatchInput &) = delete;
+    ~BatchInput() { dlpack_release(cap); dlpack_release(cap_off); }
+};
+
+bool batch_input(PyObject *hay, PyObject *offsets, PyObject *row_length, bool utf8, int want_device, BatchInput *in) {
+    if (offsets == Py_None) offsets = nullptr;
+    if (row_length == Py_None) row_length = nullptr;
+    const bool has_dlpack = !PyUnicode_Check(hay) && PyObject_HasAttrString(hay, "__dlpack__");
+    in->tensor = has_dlpack && (!PyObject_CheckBuffer(hay) || offsets || row_length);
+    if (!in->tensor) {
+        if (offsets || row_length) {
+            PyErr_SetString(PyExc_TypeError, "offsets / row_length cut ONE __dlpack__ tensor into rows: a sequence of haystacks takes neither");
+            return false;
+        }
+        PyObject *seq = PySequence_Fast(hay, "haystacks must be a sequence");
+        if (!seq) return false;
+        const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
+        in->off.assign((size_t)n + 1, 0);
+        for (Py_ssize_t i = 0; i < n; i++) {
+            PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
+            if (utf8) {
+                if (!PyUnicode_Check(it)) {
+                    PyErr_Format(PyExc_TypeError, "'%.100s' object cannot be converted to 'PyString'", Py_TYPE(it)->tp_name);
+                    Py_DECREF(seq); return false;
+                }
+                Py_ssize_t len; const char *s = PyUnicode_AsUTF8AndSize(it, &len);
+                if (!s) { Py_DECREF(seq); return false; }
+                in->blob.insert(in->blob.end(), s, s + len);
+            } else {
+                Py_buffer v;
+                if (!get_bytes_view(it, &v)) { Py_DECREF(seq); return false; }
+                in->blob.insert(in->blob.end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
+                PyBuffer_Release(&v);
+            }
+            in->off[(size_t)i + 1] = in->blob.size();
+        }
+        Py_DECREF(seq);
+        in->rows = (uint64_t)n;
+        in->blob.push_back(0);
+        return true;
+    }
+    if ((offsets != nullptr) == (row_length != nullptr)) {
+        PyErr_SetString(PyExc_TypeError, "a tensor of haystacks needs exactly one of offsets and row_length");
+        return false;
+    }
+    in->cap = dlpack_view(hay, want_device, &in->p, &in->len, &in->on_device);
+    if (!in->cap) return false;
+    {
+        const DLTensorC &t = static_cast<DLManagedTensorC *>(PyCapsule_GetPointer(in->cap, "dltensor"))->dl_tensor;
+        if (t.ndim != 1) {
+            PyErr_SetString(PyExc_TypeError, "Only one-dimensional sequences are supported");
+            return false;
+        }
+    }
+    if (row_length) {
+        if (!PyLong_Check(row_length) || PyBool_Check(row_length)) {
+            PyErr_Format(PyExc_TypeError, "argument 'row_length': '%.100s' object cannot be converted to 'PyInt'",
+                         Py_TYPE(row_length)->tp_name);
+            return false;
+        }
+        const long long rl = PyLong_AsLongLong(row_length);
+        if (rl == -1 && PyErr_Occurred()) return false;
+        if (rl <= 0 || in->len % (uint64_t)rl) {
+            PyErr_SetString(PyExc_ValueError, "row_length must be positive and divide the tensor's length");
+            return false;
+        }
+        in->row_length = (uint64_t)rl;
+        in->rows = in->len / (uint64_t)rl;
+        return true;
+    }
+    if (!PyObject_HasAttrString(offsets, "__dlpack__")) {
+        PyErr_Format(PyExc_TypeError, "argument 'offsets': '%.100s' object has no __dlpack__", Py_TYPE(offsets)->tp_name);
+        return false;
+    }
+    in->cap_off = PyObject_CallMethod(offsets, "__dlpack__", nullptr);
+    if (!in->cap_off) return false;
+    DLManagedTensorC *mt = PyCapsule_IsValid(in->cap_off, "dltensor")
+                               ? static_cast<DLManagedTensorC *>(PyCapsule_GetPointer(in->cap_off, "dltensor")) : nullptr;
+    if (!mt) {
+        PyErr_SetString(PyExc_TypeError, "__dlpack__ did not return a 'dltensor' capsule");
+        return false;
+    }
+    const DLTensorC &t = mt->dl_tensor;
+    if (t.ndim != 1 || t.dtype.code != 0 || t.dtype.bits != 64 || t.dtype.lanes != 1 ||
+        (t.strides && t.shape[0] > 1 && t.strides[0] != 1)) {
+        PyErr_SetString(PyExc_TypeError, "offsets must be a 1-D contiguous int64 tensor");
+        return false;
+    }
+    const bool dev = t.device.device_type == kDLROCM || t.device.device_type == kDLCUDA;
+    const bool host = t.device.device_type == kDLCPU || t.device.device_type == kDLROCMHost || t.device.device_type == kDLCUDAHost;
+    if ((!dev && !host) || dev != in->on_device || (dev && t.device.device_id != want_device)) {
+        PyErr_SetString(PyExc_ValueError, "the offsets tensor lies on another device than the haystack tensor");
+        return false;
+    }
+    if (t.shape[0] < 1) {
+        PyErr_SetString(PyExc_ValueError, "offsets needs rows + 1 entries: at least one");
+        return false;
+    }
+    in->t_off = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(t.data) + t.byte_offset);
+    in->rows = (uint64_t)t.shape[0] - 1;
+    if (!in->on_device) { // (device offsets: their ends are checked behind the producer's kernels, by the caller)
+        const int64_t *o = reinterpret_cast<const int64_t *>(in->t_off);
+        bool ok = o[0] == 0 && (uint64_t)o[in->rows] == in->len;
+        for (uint64_t i = 0; ok && i < in->rows; i++) ok = o[i] <= o[i + 1];
+        if (!ok) {
+            PyErr_SetString(PyExc_ValueError, "offsets must rise from 0 to the tensor's length");
+            return false;
+        }
+    }
+    return true;
+}
+
+// count_by_pattern_sparse_batch of both classes: utf8 = the str class (no offset is reported: the search is on bytes)
+PyObject *sparse_counts_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool utf8) {
+    static const char *kw[] = {"haystacks", "overlapping", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *ov = nullptr, *offsets = nullptr, *row_length = nullptr;
+    int overlapping = 0;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$OO:count_by_pattern_sparse_batch", const_cast<char **>(kw), &hay, &ov,
+                                     &offsets, &row_length))
+        return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    const int device = acx_automaton_device(a);
+    BatchInput in;
+    if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
+    acx_info_t info;
+    if (acx_automaton_info(a, &info) != ACX_OK) return raise_acx(ACX_EINVAL);
+    acx_tally_t *t = nullptr;
+    int rc;
+    bool bad_offsets = false;
+    std::vector<uint64_t> cut;
+    if (in.tensor && !in.on_device && in.row_length) {
+        cut.resize((size_t)in.rows + 1);
+        for (uint64_t i = 0; i <= in.rows; i++) cut[(size_t)i] = i * in.row_length;
+    }
+    Py_BEGIN_ALLOW_THREADS
+    if (!in.tensor) {
+        rc = acx_tally(a, in.blob.data(), in.off[(size_t)in.rows], in.off.data(), in.rows, overlapping, &t);
+    } else if (!in.on_device) {
+        rc = acx_tally(a, in.p, in.len, in.row_length ? cut.data() : in.t_off, in.rows, overlapping, &t);
+    } else {
+        rc = acx_device_synchronize_on(device); // (the producer's kernels may still write the tensors)
+        if (rc == ACX_OK && in.t_off) { // where the offsets begin and end; between the two they are the caller's word
+            uint64_t ends[2] = {1, 0};
+            rc = acx_device_download(&ends[0], in.t_off, 8);
+            if (rc == ACX_OK) rc = acx_device_download(&ends[1], in.t_off + in.rows, 8);
+            bad_offsets = rc == ACX_OK && (ends[0] != 0 || ends[1] != in.len);
+        }
+        if (rc == ACX_OK && !bad_offsets)
+            rc = acx_tally_device(a, in.p, in.len, in.t_off, in.rows, in.row_length, overlapping, &t);
+    }
+    Py_END_ALLOW_THREADS
+    if (bad_offsets) {
+        PyErr_SetString(PyExc_ValueError, "offsets must rise from 0 to the tensor's length");
+        return nullptr;
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    PatternCountsObject *o = reinterpret_cast<PatternCountsObject *>(PatternCountsType->tp_alloc(PatternCountsType, 0));
+    if (!o) { acx_free_tally(t); return nullptr; }
+    o->t = t;
+    o->device = device;
+    o->n_patterns = info.n_patterns;
+    return reinterpret_cast<PyObject *>(o);
+}
+
+PyObject *ac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return sparse_counts_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, true);
+}
+PyObject *bac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return sparse_counts_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false);
+}
+
 // device-resident search -> list of tuples (the records come back with ONE D2H copy of the result)
 PyObject *find_on_device(acx_automaton_t *a, const uint8_t *d_hay, uint64_t len, int overlapping) {
     acx_result_t *r = nullptr;
@@ -1426,6 +1731,7 @@ PyMethodDef bac_methods[] = {
      METH_VARARGS | METH_KEYWORDS, "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
     ACX_SUMMARY_METHODS(bac_summary),
     ACX_COLUMNS_METHODS(bac_columns),
+    ACX_SPARSE_COUNTS_METHOD(bac_sparse_counts),
     {"_info", bac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -1469,12 +1775,16 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, mc_slots};
     PyType_Spec col_spec = {"ahocorasick_rs.Column", sizeof(ColumnObject), 0,
                             Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, col_slots};
+    PyType_Spec pc_spec = {"ahocorasick_rs.PatternCounts", sizeof(PatternCountsObject), 0,
+                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, pc_slots};
     MatchColumnsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mc_spec));
     ColumnType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&col_spec));
-    if (!MatchColumnsType || !ColumnType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
-    for (PyTypeObject *tp : {MatchColumnsType, ColumnType}) { // (the module holds one reference, the globals the other)
+    PatternCountsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&pc_spec));
+    if (!MatchColumnsType || !ColumnType || !PatternCountsType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
+    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType}) { // (the module holds one reference, the globals the other)
         Py_INCREF(tp);
-        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : "MatchColumns", reinterpret_cast<PyObject *>(tp)) < 0) {
+        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : "MatchColumns",
+                               reinterpret_cast<PyObject *>(tp)) < 0) {
             Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);
             return nullptr;
         }

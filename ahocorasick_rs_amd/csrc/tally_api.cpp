@@ -1,0 +1,418 @@
+// tally_api.cpp -- per-haystack pattern counts as a CSR matrix (tally.hpp): the host reduction, the device stage behind the
+// find pipeline, the acx_tally* entry points and the accessors of their result.
+#include "find_pipeline.hpp"
+#include "replace.hpp"
+#include "tally.hpp"
+
+using namespace acxh;
+
+// acx_tally / acx_tally_device: row offsets (rows + 1 words), patterns and counts (nnz words each) in ONE block.  Device
+// route: a block of the buffer cache (g_bufs, workspace.cpp), written by kernels that may still run when the call returns
+// (done); the find's records and the stage's temporaries have gone back to the cache behind the same kernels.  Host route:
+// a block of host memory.
+struct ACX_HIDDEN acx_tally {
+    int device = 0;
+    int on_device = 0;
+    uint64_t rows = 0, nnz = 0;
+    int64_t *part[3] = {nullptr, nullptr, nullptr}; // ACX_TALLY_*
+    int64_t *h_block = nullptr;
+    void *d_block = nullptr;
+    hipEvent_t done = nullptr;
+    std::vector<void *> scratch;
+};
+
+namespace {
+
+// where the parts of a block begin, in words: every part at least one word long and a multiple of 32 words (256 bytes)
+// behind the previous one (the rules of the columns' block, columns_api.cpp)
+struct Layout {
+    uint64_t at[3], words;
+    Layout(uint64_t rows, uint64_t nnz) {
+        const uint64_t r = (rows + 1 + 31) / 32 * 32, c = (std::max<uint64_t>(nnz, 1) + 31) / 32 * 32;
+        at[ACX_TALLY_ROW_OFFSETS] = 0;
+        at[ACX_TALLY_PATTERN] = r;
+        at[ACX_TALLY_COUNT] = r + c;
+        words = r + 2 * c;
+    }
+};
+
+uint64_t part_words(const acx_tally_t *t, int which) { return which == ACX_TALLY_ROW_OFFSETS ? t->rows + 1 : t->nnz; }
+
+// ACX_TALLY_HOST_MAX (bytes, read per call): batches up to this size reduce on the host, behind acx_find_batch.  The
+// default is ACX_SUMMARY_HOST_MAX's, which is itself not a measured crossover.
+uint64_t tally_host_max() {
+    const char *e = std::getenv("ACX_TALLY_HOST_MAX");
+    return e ? std::strtoull(e, nullptr, 10) : (1ull << 20);
+}
+
+// ACX_TALLY_ROW_MAX (records, read per call): rows longer than this take the radix-sort form.  It only ever lowers
+// acx::TALLY_ROW_MAX; 0 sends every row that way (the tests' seam for that form at small sizes, and the baseline the tile
+// kernel is measured against).
+uint32_t tally_row_max() {
+    const char *e = std::getenv("ACX_TALLY_ROW_MAX");
+    if (!e || !*e) return acx::TALLY_ROW_MAX;
+    return (uint32_t)std::min<uint64_t>(std::strtoull(e, nullptr, 10), acx::TALLY_ROW_MAX);
+}
+
+// The temporaries of one run of the device stage: one block of the buffer cache (and a second one when there are long rows).
+struct Stage {
+    int device = 0;
+    void *block = nullptr, *long_block = nullptr;
+    int64_t *rec_off = nullptr, *roff = nullptr, *tmp_pattern = nullptr, *tmp_count = nullptr;
+    uint64_t *nnz_row = nullptr, *scan_tmp = nullptr;
+    uint64_t n = 0, rows = 0;
+};
+
+// The stage up to the point where nnz is known: the scans, the tile kernel, the long rows' form when there are any.
+// S->roff then holds the row offsets (rows + 1 words); d_m: n records, d_counts: rows words (rows > 0).  check_sum: the
+// counts are a caller's (acx_tally_rows_device) -- they must sum to n before a kernel reads a record by them.
+int stage_count(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, const uint64_t *d_counts, uint64_t rows,
+                uint64_t n_patterns, bool check_sum, Stage *S, uint64_t *nnz) {
+    S->device = device;
+    S->n = n;
+    S->rows = rows;
+    *nnz = 0;
+    const uint32_t row_max = tally_row_max();
+    // [rec_off: rows + 1][roff: rows + 1, then the long rows' records: 1][nnz_row: rows][scan][tmp_pattern: n][tmp_count: n]
+    uint64_t at = 0;
+    auto part = [&](uint64_t w) { const uint64_t here = at; at += (w + 31) / 32 * 32; return here; };
+    const uint64_t o_rec = part(rows + 1), o_roff = part(rows + 2), o_nnz = part(rows), o_scan = part(replace_scan_words(rows)),
+                   o_tp = part(n), o_tc = part(n);
+    HIPCHK(g_bufs.get(&S->block, std::max<uint64_t>(at, 32) * 8, device));
+    uint64_t *b = (uint64_t *)S->block;
+    S->rec_off = (int64_t *)(b + o_rec);
+    S->roff = (int64_t *)(b + o_roff);
+    S->nnz_row = b + o_nnz;
+    S->scan_tmp = b + o_scan;
+    S->tmp_pattern = (int64_t *)(b + o_tp);
+    S->tmp_count = (int64_t *)(b + o_tc);
+    uint64_t *n_long = (uint64_t *)S->roff + rows + 1; // (behind the scan's last entry: one readback brings both)
+    HIPCHK(acx::replace_scan(nullptr, nullptr, d_counts, rows, S->rec_off, S->scan_tmp, st));
+    if (check_sum) {
+        uint64_t sum = 0;
+        HIPCHK(hipMemcpyAsync(&sum, S->rec_off + rows, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (sum != n) return fail(ACX_EINVAL, "the counts do not sum to the number of records");
+    }
+    if (!n) { // every row is empty
+        HIPCHK(hipMemsetAsync(S->roff, 0, (rows + 1) * 8, st));
+        return ACX_OK;
+    }
+    HIPCHK(hipMemsetAsync(S->nnz_row, 0, rows * 8, st));
+    HIPCHK(hipMemsetAsync(n_long, 0, 8, st));
+    HIPCHK(acx::tally_tiles(d_m, n, S->rec_off, rows, n_patterns, row_max, S->tmp_pattern, S->tmp_count, S->nnz_row, n_long, st));
+    HIPCHK(acx::replace_scan(nullptr, nullptr, S->nnz_row, rows, S->roff, S->scan_tmp, st));
+    uint64_t back[2] = {0, 0}; // nnz (of the short rows, until the long ones are in), the long rows' records
+    HIPCHK(hipMemcpyAsync(back, S->roff + rows, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (back[1]) {
+        if (back[1] > n) return fail(ACX_EDEVICE, "the tile kernel counted more long-row records than there are records");
+        HIPCHK(g_bufs.get(&S->long_block, acx::tally_long_words(rows, back[1], row_max) * 8, device));
+        HIPCHK(acx::tally_long(d_m, S->rec_off, rows, row_max, back[1], (uint64_t *)S->long_block, S->tmp_pattern, S->tmp_count,
+                               S->nnz_row, st));
+        HIPCHK(acx::replace_scan(nullptr, nullptr, S->nnz_row, rows, S->roff, S->scan_tmp, st));
+        HIPCHK(hipMemcpyAsync(back, S->roff + rows, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if (back[0] > n) return fail(ACX_EDEVICE, "more runs than records");
+    *nnz = back[0];
+    return ACX_OK;
+}
+
+// ... and from there: the row offsets and the compact columns into their places (device memory, 8-byte aligned)
+int stage_finish(const Stage *S, uint64_t nnz, int64_t *row_offsets, int64_t *pattern, int64_t *count, hipStream_t st) {
+    HIPCHK(hipMemcpyAsync(row_offsets, S->roff, (S->rows + 1) * 8, hipMemcpyDeviceToDevice, st));
+    HIPCHK(acx::tally_compact(S->roff, S->rows, S->rec_off, nnz, S->tmp_pattern, S->tmp_count, pattern, count, st));
+    return ACX_OK;
+}
+
+// The device route: the find pipeline as acx_find_device runs it (batch splits and the expansion of copies included, byte
+// offsets: no offset is reported), then the stage on the same stream.  Returns when nnz is known; tally_compact may still
+// run (out->done).  d_hay, and G.offsets, must stay valid until then.
+int run_tally(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping, acx_tally_t **out) {
+    *out = nullptr;
+    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
+    const uint64_t rows = segmented ? G.n_hay : 1;
+    acx_result *r = nullptr;
+    if (rows) { // (an empty batch: nothing to search, one row offset)
+        int rc = run_find(a, x, d_hay, len, G, overlapping, 0, &r);
+        if (rc != ACX_OK) return rc;
+    }
+    acx_tally_t *R = new (std::nothrow) acx_tally_t();
+    if (!R) { acx_free_result(r); return fail(ACX_ENOMEM, "out of memory"); }
+    hipStream_t st = x->stream;
+    R->device = a->device;
+    R->on_device = 1;
+    R->rows = rows;
+    Stage S;
+    uint64_t *one_count = nullptr; // (one haystack that is no batch: the find kept no counts)
+    auto body = [&]() -> int {
+        uint64_t nnz = 0;
+        if (rows) {
+            const uint64_t *d_counts = r->d_counts;
+            if (!d_counts) {
+                HIPCHK(g_bufs.get((void **)&one_count, 16, a->device));
+                HIPCHK(hipMemcpyAsync(one_count, &r->n, 8, hipMemcpyHostToDevice, st));
+                d_counts = one_count;
+            }
+            int rc = stage_count(a->device, st, r->d_matches, r->n, d_counts, rows, a->host.n_patterns, false, &S, &nnz);
+            if (rc != ACX_OK) return rc;
+        }
+        R->nnz = nnz;
+        const Layout L(rows, nnz);
+        HIPCHK(g_bufs.get(&R->d_block, L.words * 8, a->device));
+        for (int k = 0; k < 3; k++) R->part[k] = (int64_t *)R->d_block + L.at[k];
+        if (rows) {
+            int rc = stage_finish(&S, nnz, R->part[0], R->part[1], R->part[2], st);
+            if (rc != ACX_OK) return rc;
+        } else {
+            HIPCHK(hipMemsetAsync(R->part[0], 0, 8, st));
+        }
+        // The find's records and counts and the stage's temporaries are not needed beyond this point of the stream: they go
+        // back to the buffer cache, which holds them until an event recorded HERE has fired.
+        hipEvent_t freed = g_events.get(a->device), freed2 = g_events.get(a->device);
+        R->done = g_events.get(a->device);
+        if (!freed || !freed2 || !R->done) {
+            HIPCHK(hipStreamSynchronize(st));
+            g_events.put(a->device, freed);
+            g_events.put(a->device, freed2);
+            g_events.put(a->device, R->done);
+            freed = freed2 = R->done = nullptr;
+        } else {
+            HIPCHK(hipEventRecord(freed, st));
+            HIPCHK(hipEventRecord(freed2, st));
+            HIPCHK(hipEventRecord(R->done, st));
+        }
+        if (r) {
+            g_events.put(a->device, r->done);
+            r->done = nullptr;
+            g_bufs.put(r->borrowed ? nullptr : r->d_matches, a->device, freed, r->d_counts);
+            r->d_matches = nullptr;
+            r->d_counts = nullptr;
+        } else {
+            g_events.put(a->device, freed);
+        }
+        g_bufs.put(S.block, a->device, freed2, one_count);
+        S.block = nullptr;
+        one_count = nullptr;
+        if (S.long_block) R->scratch.push_back(S.long_block); // (the rare form: kept until acx_free_tally)
+        S.long_block = nullptr;
+        return ACX_OK;
+    };
+    int rc = body();
+    if (rc != ACX_OK) {
+        (void)hipStreamSynchronize(st);
+        g_bufs.put(S.block, a->device);
+        g_bufs.put(S.long_block, a->device);
+        g_bufs.put(one_count, a->device);
+    }
+    acx_free_result(r); // (emptied above when all went well)
+    if (rc != ACX_OK) { acx_free_tally(R); return rc; }
+    *out = R;
+    return ACX_OK;
+}
+
+// every accessor's wait for the stage's last kernel
+int tally_wait(const acx_tally_t *t) {
+    if (!t->on_device || !t->done) return ACX_OK;
+    DeviceScope ds(t->device);
+    HIPCHK(hipEventSynchronize(t->done));
+    return ACX_OK;
+}
+
+acx_tally_t *host_tally(int device, uint64_t rows, uint64_t nnz_room) {
+    acx_tally_t *R = new (std::nothrow) acx_tally_t();
+    const Layout L(rows, nnz_room);
+    if (R) R->h_block = new (std::nothrow) int64_t[L.words];
+    if (!R || !R->h_block) { delete R; return nullptr; }
+    R->device = device;
+    R->rows = rows;
+    for (int k = 0; k < 3; k++) { R->part[k] = R->h_block + L.at[k]; R->part[k][0] = 0; }
+    return R;
+}
+
+} // namespace
+
+extern "C" {
+
+int acx_tally_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts, uint64_t n_hay, int64_t *row_offsets,
+                   int64_t *pattern, int64_t *count, uint64_t *nnz) {
+    if (!row_offsets || !nnz || (n_m && (!m || !pattern || !count)) || (n_hay && !counts)) return fail(ACX_EINVAL, "null argument");
+    uint64_t sum = 0;
+    for (uint64_t h = 0; h < n_hay; h++) {
+        if (counts[h] > n_m - sum) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+        sum += counts[h];
+    }
+    if (sum != n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+    std::vector<uint64_t> row;
+    uint64_t at = 0, w = 0;
+    try {
+        for (uint64_t h = 0; h < n_hay; h++) {
+            row_offsets[h] = (int64_t)w;
+            row.resize(counts[h]);
+            for (uint64_t i = 0; i < counts[h]; i++) row[i] = m[at + i].pattern;
+            at += counts[h];
+            std::sort(row.begin(), row.end());
+            for (uint64_t i = 0; i < row.size();) {
+                uint64_t j = i + 1;
+                while (j < row.size() && row[j] == row[i]) j++;
+                pattern[w] = (int64_t)row[i];
+                count[w] = (int64_t)(j - i);
+                w++;
+                i = j;
+            }
+        }
+    } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
+    row_offsets[n_hay] = (int64_t)w;
+    *nnz = w;
+    return ACX_OK;
+}
+
+int acx_tally(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
+              acx_tally_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    int rc = overlapping ? check_overlapping(a) : ACX_OK; // (the error, no device state)
+    if (rc != ACX_OK) return rc;
+    uint64_t base = 0;
+    if (offsets) {
+        for (uint64_t i = 0; i < n_hay; i++)
+            if (offsets[i + 1] < offsets[i]) return fail(ACX_EINVAL, "offsets not monotone");
+        base = offsets[0];
+        len = offsets[n_hay] - base;
+    } else {
+        n_hay = 1;
+    }
+    if (len && !hay) return fail(ACX_EINVAL, "null haystack");
+    const uint8_t *h = len ? hay + base : nullptr;
+    std::vector<uint64_t> rel;
+    try {
+        rel.resize(n_hay + 1);
+    } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
+    for (uint64_t i = 0; i <= n_hay; i++) rel[i] = offsets ? offsets[i] - base : (i ? len : 0);
+    if (len <= tally_host_max() || !n_hay) {
+        // host route: acx_find_batch as it is (the small-call kernel, the in-place read, the staged pipeline), then the
+        // reduction here
+        acx_match_t *m = nullptr;
+        uint64_t nm = 0;
+        std::vector<uint64_t> counts(n_hay, 0);
+        if (n_hay) rc = acx_find_batch(a, h, rel.data(), n_hay, overlapping, 0, &m, &nm, counts.data());
+        if (rc != ACX_OK) return rc;
+        acx_tally_t *R = host_tally(a->device, n_hay, nm);
+        if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
+        rc = acx_tally_host(m, nm, counts.data(), n_hay, R->part[0], R->part[1], R->part[2], &R->nnz);
+        acx_free_matches(m);
+        if (rc != ACX_OK) { acx_free_tally(R); return rc; }
+        *out = R;
+        return ACX_OK;
+    }
+    // device route: staged, searched and reduced under one lease; the compact block comes back in one copy
+    acx_tally_t *D = nullptr;
+    {
+        Lease lease(a);
+        Ctx *c = lease.c;
+        if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
+        rc = stage_host(a, c, h, len, rel.data(), n_hay + 1, false);
+        if (rc != ACX_OK) return rc;
+        const uint8_t *d_search = nullptr;
+        if ((rc = fold_copy(a, c, c->ws.hay, len, &d_search)) != ACX_OK) return rc;
+        rc = run_tally(a, c, d_search, len, Segments{c->ws.offsets, n_hay, 0}, overlapping, &D);
+        if (rc != ACX_OK) return rc;
+        rc = tally_wait(D); // (the staging buffers are the context's: the lease ends behind the kernels)
+    }
+    acx_tally_t *R = rc == ACX_OK ? host_tally(a->device, D->rows, D->nnz) : nullptr;
+    if (rc == ACX_OK && !R) rc = fail(ACX_ENOMEM, "out of memory");
+    if (rc == ACX_OK) {
+        R->nnz = D->nnz;
+        DeviceScope ds(a->device);
+        const hipError_t e = hipMemcpy(R->h_block, D->d_block, Layout(D->rows, D->nnz).words * 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hipfail(e, "copying the tally to the host");
+    }
+    acx_free_tally(D);
+    if (rc != ACX_OK) { acx_free_tally(R); return rc; }
+    *out = R;
+    return ACX_OK;
+}
+
+int acx_tally_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                     uint64_t uniform_len, int overlapping, acx_tally_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
+    Segments G;
+    int rc = make_segments(d_offsets, n_hay, uniform_len, len, &G);
+    if (rc == ACX_OK && overlapping) rc = check_overlapping(a); // (the error, no device state)
+    if (rc != ACX_OK) return rc;
+    Lease lease(a);
+    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
+    const uint8_t *d_search = nullptr;
+    rc = fold_copy(a, lease.c, (const uint8_t *)d_hay, len, &d_search);
+    if (rc != ACX_OK) return rc;
+    return run_tally(a, lease.c, d_search, len, G, overlapping, out);
+}
+
+int acx_tally_rows_device(const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint64_t n_hay, uint64_t n_patterns,
+                          int64_t *d_row_offsets, int64_t *d_pattern, int64_t *d_count, uint64_t *nnz) {
+    if (!d_row_offsets || !nnz) return fail(ACX_EINVAL, "null argument");
+    *nnz = 0;
+    if ((n && (!d_records || !d_pattern || !d_count)) || (n_hay && !d_counts)) return fail(ACX_EINVAL, "null argument");
+    if (((uintptr_t)d_records | (uintptr_t)d_counts | (uintptr_t)d_row_offsets | (uintptr_t)d_pattern | (uintptr_t)d_count) & 7)
+        return fail(ACX_EINVAL, "records, counts and outputs must be 8-byte aligned");
+    if (n_patterns > (1ull << acx::TALLY_PATTERN_BITS)) return fail(ACX_EINVAL, "more than 2^24 patterns");
+    if (n && !n_hay) return fail(ACX_EINVAL, "the counts do not sum to the number of records");
+    hipPointerAttribute_t at;
+    HIPCHK(hipPointerGetAttributes(&at, d_row_offsets));
+    DeviceScope ds(at.device);
+    if (!n_hay) {
+        HIPCHK(hipMemsetAsync(d_row_offsets, 0, 8, nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+        return ACX_OK;
+    }
+    Stage S;
+    int rc = stage_count(at.device, nullptr, d_records, n, d_counts, n_hay, n_patterns, true, &S, nnz);
+    if (rc == ACX_OK) rc = stage_finish(&S, *nnz, d_row_offsets, d_pattern, d_count, nullptr);
+    const hipError_t e = hipStreamSynchronize(nullptr);
+    g_bufs.put(S.block, at.device);
+    g_bufs.put(S.long_block, at.device);
+    if (rc == ACX_OK && e != hipSuccess) rc = hipfail(e, "hipStreamSynchronize");
+    return rc;
+}
+
+uint64_t acx_tally_nnz(const acx_tally_t *t) { return t ? t->nnz : 0; }
+uint64_t acx_tally_rows(const acx_tally_t *t) { return t ? t->rows : 0; }
+int acx_tally_on_device(const acx_tally_t *t) { return t ? t->on_device : 0; }
+
+const int64_t *acx_tally_data(const acx_tally_t *t, int which) {
+    if (!t || which < 0 || which > ACX_TALLY_COUNT) return nullptr;
+    if (tally_wait(t) != ACX_OK) return nullptr;
+    return t->part[which];
+}
+
+int acx_tally_copy(const acx_tally_t *t, int which, int64_t *host_dst) {
+    if (!t || which < 0 || which > ACX_TALLY_COUNT) return fail(ACX_EINVAL, "no such part");
+    const uint64_t words = part_words(t, which);
+    if (!words) return ACX_OK;
+    if (!host_dst) return fail(ACX_EINVAL, "null argument");
+    if (!t->on_device) { std::memcpy(host_dst, t->part[which], words * 8); return ACX_OK; }
+    int rc = tally_wait(t);
+    if (rc != ACX_OK) return rc;
+    DeviceScope ds(t->device);
+    HIPCHK(hipMemcpy(host_dst, t->part[which], words * 8, hipMemcpyDeviceToHost));
+    return ACX_OK;
+}
+
+void acx_free_tally(acx_tally_t *t) {
+    if (!t) return;
+    if (t->on_device) {
+        DeviceScope ds(t->device);
+        // (the kernels write the block and read the scratch: nothing goes back to the pool before they are done)
+        if (t->done) (void)hipEventSynchronize(t->done);
+        for (void *p : t->scratch) g_bufs.put(p, t->device);
+        g_bufs.put(t->d_block, t->device);
+        g_events.put(t->device, t->done);
+    }
+    delete[] t->h_block;
+    delete t;
+}
+
+} // extern "C"

@@ -30,6 +30,8 @@ extern "C" {
  *     _counts, _any, _first, _by_pattern, _device_counts, _device_any, _device_first, _device_by_pattern, acx_free_summary);
  *     second addendum (additive as well): acx_find_columns / acx_find_columns_device, ACX_COL_*, the acx_columns_t accessors
  *     (acx_columns_count, _rows, _on_device, _data, _copy, acx_free_columns), acx_split_host / acx_split_device;
+ *     third addendum (additive as well): acx_tally / acx_tally_device / acx_tally_host / acx_tally_rows_device, ACX_TALLY_*,
+ *     the acx_tally_t accessors (acx_tally_nnz, _rows, _on_device, _data, _copy, acx_free_tally);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -458,6 +460,50 @@ void acx_free_columns(acx_columns_t *c);
  * synchronous: the columns are complete when it returns.  n = 0: nothing is touched. */
 int acx_split_host(const acx_match_t *m, uint64_t n, int64_t *pattern, int64_t *start, int64_t *end);
 int acx_split_device(const acx_match_t *d_m, uint64_t n, int64_t *d_pattern, int64_t *d_start, int64_t *d_end);
+
+/* ---- tally: which patterns occur in which haystack of a batch, and how often, as a sparse matrix in CSR form.
+ * C[h][p] = the number of haystack h's matches (acx_find_batch / acx_find_device for the same arguments) with pattern p:
+ *   ACX_TALLY_ROW_OFFSETS  rows + 1 words from 0; entries row_offsets[h] .. row_offsets[h + 1] are haystack h's
+ *   ACX_TALLY_PATTERN      nnz words, STRICTLY ASCENDING within a row (the canonical form: torch.sparse_csr_tensor takes the
+ *                          three parts as they are)
+ *   ACX_TALLY_COUNT        nnz words, all >= 1
+ * nnz = the number of distinct (haystack, pattern) pairs.  Every match kind; an overlapping search over a set with copies
+ * counts every copy.  No offset is reported, so the search runs on bytes whatever the caller's strings are.
+ * acx_tally: host haystacks (offsets: n_hay + 1, or null: one haystack of len bytes), a host result.  Up to
+ * ACX_TALLY_HOST_MAX bytes (environment, read per call; default 1 MiB -- ACX_SUMMARY_HOST_MAX's default, not a measured
+ * crossover) acx_find_batch runs and acx_tally_host reduces; beyond that the batch is staged, searched and reduced on the
+ * device and the compact block comes back in one copy.
+ * acx_tally_device: acx_find_device's pipeline (d_offsets / uniform_len as there), then the device stage on the same
+ * stream; the result stays in HBM on the automaton's device and only nnz (and the number of records in rows too long for
+ * the tile kernel) crosses to the host.  The call returns when nnz is known; the last kernel may still run, and
+ * acx_tally_data / acx_tally_copy wait for it.  ACX_TALLY_ROW_MAX (environment, read per call) lowers the longest row the
+ * tile kernel takes (2048 records); 0 sends every row through the radix-sort form.
+ * An empty part still has a valid, non-null address; an empty batch has one row offset, 0. */
+#define ACX_TALLY_ROW_OFFSETS 0
+#define ACX_TALLY_PATTERN 1
+#define ACX_TALLY_COUNT 2
+typedef struct acx_tally acx_tally_t;
+int acx_tally(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
+              int overlapping, acx_tally_t **out);
+int acx_tally_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                     uint64_t uniform_len, int overlapping, acx_tally_t **out);
+uint64_t acx_tally_nnz(const acx_tally_t *t);      /* entries of pattern / count; valid at return        */
+uint64_t acx_tally_rows(const acx_tally_t *t);     /* haystacks                                          */
+int acx_tally_on_device(const acx_tally_t *t);     /* 1: the parts are in HBM, 0: host memory            */
+/* host or device pointer by acx_tally_on_device; waits for the device stage.  NULL: no such part or the wait failed.
+ * Valid until acx_free_tally. */
+const int64_t *acx_tally_data(const acx_tally_t *t, int which);
+int acx_tally_copy(const acx_tally_t *t, int which, int64_t *host_dst);
+void acx_free_tally(acx_tally_t *t);
+/* the reduction itself.  acx_tally_host: host memory, no device needed; m: n_m matches, all haystacks behind one another,
+ * counts[h] of them haystack h's (they must sum to n_m); row_offsets: n_hay + 1 words, pattern and count: room for n_m.
+ * acx_tally_rows_device: the device stage alone on records and counts in HBM on one device (8-byte alignment is all they
+ * and the outputs need; d_pattern and d_count: room for n words; pattern ids below n_patterns <= 2^24; the counts must sum
+ * to n); synchronous: the outputs are complete when it returns. */
+int acx_tally_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts, uint64_t n_hay, int64_t *row_offsets,
+                   int64_t *pattern, int64_t *count, uint64_t *nnz);
+int acx_tally_rows_device(const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint64_t n_hay,
+                          uint64_t n_patterns, int64_t *d_row_offsets, int64_t *d_pattern, int64_t *d_count, uint64_t *nnz);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
