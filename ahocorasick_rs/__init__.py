@@ -19,6 +19,7 @@ from .ahocorasick_rs import (
     MatchColumns,
     Column,
     PatternCounts,
+    FilteredRows,
 )
 
 __acx_amd__ = True
@@ -38,6 +39,7 @@ __all__ = [
     "Column",
     # Extension: the result of count_by_pattern_sparse_batch
     "PatternCounts",
+    "FilteredRows",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

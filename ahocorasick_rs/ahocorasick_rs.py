@@ -11,6 +11,7 @@ from ahocorasick_rs_amd.ahocorasick_rs import (  # noqa: F401
     MatchColumns,
     MatchKind,
     PatternCounts,
+    FilteredRows,
 )
 
-__all__ = ["AhoCorasick", "BytesAhoCorasick", "Column", "Implementation", "MatchColumns", "MatchKind", "PatternCounts"]
+__all__ = ["AhoCorasick", "BytesAhoCorasick", "Column", "FilteredRows", "Implementation", "MatchColumns", "MatchKind", "PatternCounts"]

@@ -24,6 +24,7 @@ try:
         MatchColumns,
         Column,
         PatternCounts,
+        FilteredRows,
     )
 except ImportError as e:  # pragma: no cover - build problem, fail loudly
     raise ImportError(
@@ -46,6 +47,7 @@ __all__ = [
     "Column",
     # Extension: the result of count_by_pattern_sparse_batch
     "PatternCounts",
+    "FilteredRows",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

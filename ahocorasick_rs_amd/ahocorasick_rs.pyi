@@ -20,11 +20,12 @@ class MatchKind:
 
 # extension: the result of find_matches_as_columns / find_matches_as_columns_batch
 class Column:
-    """One int64 column, 1-D and contiguous, in host memory or in HBM.  Every accessor waits for the split kernel first."""
+    """One column, 1-D and contiguous, in host memory or in HBM: int64, or uint8 for a FilteredRows' data.  Every accessor
+    waits for the device work that writes it first."""
     def __len__(self) -> int: ...
     def __dlpack__(self, stream: Any = None, **ignored: Any) -> Any: ...
     def __dlpack_device__(self) -> tuple[int, int]: ...
-    def __buffer__(self, flags: int) -> memoryview: ...  # host columns only: format "q", read-only
+    def __buffer__(self, flags: int) -> memoryview: ...  # host columns only: format "q" (uint8: "B"), read-only
 
 class MatchColumns:
     @property
@@ -54,6 +55,23 @@ class PatternCounts:
     def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
     def __len__(self) -> int: ...  # the number of non-zero entries
     def tolist(self) -> list[list[tuple[int, int]]]: ...  # per haystack: (pattern, count), patterns ascending
+
+# extension: the result of filter_batch -- the kept rows of a batch as a compacted batch, where the search ran
+class FilteredRows:
+    @property
+    def rows(self) -> Column: ...  # len(self) int64 entries: the kept source row indexes, strictly ascending
+    @property
+    def offsets(self) -> Column: ...  # len(self) + 1 int64 entries from 0
+    @property
+    def data(self) -> Column: ...  # nbytes uint8 entries: kept row i is data[offsets[i]:offsets[i + 1]], the caller's bytes
+    @property
+    def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
+    @property
+    def nbytes(self) -> int: ...  # the size of data
+    @property
+    def source_rows(self) -> int: ...  # the rows of the batch that was filtered
+    def __len__(self) -> int: ...  # the number of kept rows
+    def tolist(self) -> Any: ...  # the kept rows: list[str] of AhoCorasick, list[bytes] of BytesAhoCorasick
 
 class AhoCorasick:
     def __init__(
@@ -94,6 +112,13 @@ class AhoCorasick:
     def count_by_pattern_sparse_batch(
         self, haystacks: Any, overlapping: bool = False, *, offsets: Any = None, row_length: Optional[int] = None
     ) -> PatternCounts: ...
+    # extension: drop the rows that contain a pattern (keep="unmatched") or keep only those that do (keep="matched"; a row
+    # is matched when it has at least min_matches matches), compacted where the search ran.  haystacks as for
+    # count_by_pattern_sparse_batch: a sequence, or ONE uint8 __dlpack__ tensor cut by exactly one of offsets and row_length
+    def filter_batch(
+        self, haystacks: Any, overlapping: bool = False, *, keep: str = "unmatched", min_matches: int = 1,
+        offsets: Any = None, row_length: Optional[int] = None
+    ) -> FilteredRows: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -131,4 +156,11 @@ class BytesAhoCorasick:
     def count_by_pattern_sparse_batch(
         self, haystacks: Any, overlapping: bool = False, *, offsets: Any = None, row_length: Optional[int] = None
     ) -> PatternCounts: ...
+    # extension: drop the rows that contain a pattern (keep="unmatched") or keep only those that do (keep="matched"; a row
+    # is matched when it has at least min_matches matches), compacted where the search ran.  haystacks as for
+    # count_by_pattern_sparse_batch: a sequence, or ONE uint8 __dlpack__ tensor cut by exactly one of offsets and row_length
+    def filter_batch(
+        self, haystacks: Any, overlapping: bool = False, *, keep: str = "unmatched", min_matches: int = 1,
+        offsets: Any = None, row_length: Optional[int] = None
+    ) -> FilteredRows: ...
     def _info(self) -> dict[str, Any]: ...

@@ -31,6 +31,8 @@ SUM_FIRST, SUM_BY_PATTERN = 1, 2  # acx_summarize: the parts beyond the total an
 NO_MATCH = (1 << 64) - 1  # the pattern of a haystack's first match when it has none
 COL_PATTERN, COL_START, COL_END, COL_ROW_OFFSETS = 0, 1, 2, 3  # acx_columns_data / acx_columns_copy (ACX_COL_*)
 TALLY_ROW_OFFSETS, TALLY_PATTERN, TALLY_COUNT = 0, 1, 2  # acx_tally_data / acx_tally_copy (ACX_TALLY_*)
+FILT_ROWS, FILT_OFFSETS, FILT_DATA = 0, 1, 2  # acx_filtered_data / acx_filtered_copy (ACX_FILT_*)
+FILTER_KEEP_MATCHED = 1  # acx_filter* flags (ACX_FILTER_KEEP_MATCHED); 0 keeps the unmatched rows
 ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
 MATCH_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u8"), ("end", "<u8")])
@@ -215,6 +217,21 @@ def lib() -> ctypes.CDLL:
     L.acx_free_tally.restype = None
     L.acx_tally_host.argtypes = [vp, u64, vp, u64, vp, vp, vp, ctypes.POINTER(u64)]
     L.acx_tally_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, ctypes.POINTER(u64)]
+    u32 = ctypes.c_uint32
+    L.acx_filter.argtypes = [vp, vp, u64, vp, u64, i32, u64, u32, ctypes.POINTER(vp)]
+    L.acx_filter_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, u64, u32, ctypes.POINTER(vp)]
+    for name in ("rows", "bytes"):
+        getattr(L, "acx_filtered_" + name).argtypes = [vp]
+        getattr(L, "acx_filtered_" + name).restype = u64
+    L.acx_filtered_on_device.argtypes = [vp]
+    L.acx_filtered_data.argtypes = [vp, i32]
+    L.acx_filtered_data.restype = vp
+    L.acx_filtered_copy.argtypes = [vp, i32, vp]
+    L.acx_free_filtered.argtypes = [vp]
+    L.acx_free_filtered.restype = None
+    L.acx_filter_host.argtypes = [vp, u64, vp, u64, vp, u64, u32, vp, vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.acx_filter_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, u64, u32, vp, vp, vp, ctypes.POINTER(u64),
+                                         ctypes.POINTER(u64)]
     _lib = L
     return L
 
@@ -746,6 +763,96 @@ def tally_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, n_patte
     return int(nnz.value)
 
 
+class DeviceFiltered:
+    """The result of Automaton.filter / filter_device (acx_filtered_t): the kept rows of a batch -- k source row indexes
+    and k + 1 offsets (int64) and the rows' bytes back to back (uint8) -- in HBM (on_device) or in host memory.  part()
+    copies one out; data_ptr() is where it lies (both wait for the device stage)."""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    @property
+    def n_rows(self) -> int:
+        return int(lib().acx_filtered_rows(self._h))
+
+    @property
+    def nbytes(self) -> int:
+        return int(lib().acx_filtered_bytes(self._h))
+
+    @property
+    def on_device(self) -> bool:
+        return bool(lib().acx_filtered_on_device(self._h))
+
+    def data_ptr(self, which: int) -> int:
+        """host or device address of the part (by on_device)"""
+        return lib().acx_filtered_data(self._h, which) or 0
+
+    def part(self, which: int) -> np.ndarray:
+        if which == FILT_DATA:
+            out = np.zeros(self.nbytes, dtype=np.uint8)
+        else:
+            out = np.zeros(self.n_rows + (which == FILT_OFFSETS), dtype=np.int64)
+        _check(lib().acx_filtered_copy(self._h, which, out.ctypes.data if out.size else None))
+        return out
+
+    def rows(self) -> np.ndarray:
+        return self.part(FILT_ROWS)
+
+    def offsets(self) -> np.ndarray:
+        return self.part(FILT_OFFSETS)
+
+    def data(self) -> np.ndarray:
+        return self.part(FILT_DATA)
+
+    def free(self) -> None:
+        if self._h:
+            lib().acx_free_filtered(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def filter_host(hay, offsets: Optional[Sequence[int]], counts: Sequence[int], min_matches: int = 1, flags: int = 0, *,
+                sizes_only: bool = False):
+    """acx_filter_host: the definition of the row filter on the host, no device involved.  hay: bytes-like; offsets: n + 1
+    from 0 to len(hay), or None (one row); counts[h]: row h's matches.  Returns (rows, offsets, data) as int64 / int64 /
+    uint8 arrays, or (n_rows, n_bytes) with sizes_only.  ValueError (code EINVAL) for a bad flag, min_matches = 0 or
+    offsets that do not rise from 0 to len(hay)."""
+    h = np.frombuffer(bytes(hay), dtype=np.uint8)
+    c = np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    off = None if offsets is None else np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+    n = len(c)
+    if off is not None and len(off) != n + 1:
+        raise ValueError("offsets needs len(counts) + 1 entries")
+    k, nb = ctypes.c_uint64(), ctypes.c_uint64()
+    args = (h.ctypes.data if len(h) else None, len(h), None if off is None else off.ctypes.data, n,
+            c.ctypes.data if n else None, min_matches, flags)
+    _check(lib().acx_filter_host(*args, None, None, None, ctypes.byref(k), ctypes.byref(nb)))
+    if sizes_only:
+        return int(k.value), int(nb.value)
+    rows, oo = np.zeros(max(n, 1), dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+    data = np.zeros(max(len(h), 1), dtype=np.uint8)
+    _check(lib().acx_filter_host(*args, rows.ctypes.data, oo.ctypes.data, data.ctypes.data, ctypes.byref(k), ctypes.byref(nb)))
+    return rows[:k.value], oo[:k.value + 1], data[:nb.value]
+
+
+def filter_rows_device(d_hay: int, nbytes: int, d_offsets: int, n_hay: int, uniform_len: int, d_counts: int,
+                       min_matches: int, flags: int, d_rows: int, d_out_offsets: int, d_data: int) -> Tuple[int, int]:
+    """acx_filter_rows_device: the device stage alone -- nbytes at d_hay (any address) cut by n_hay + 1 offsets at d_offsets
+    or by uniform_len, n_hay counts at d_counts -> the kept rows' indexes, offsets and bytes at the three device addresses
+    (room for n_hay words, n_hay + 1 words and round_up(nbytes, 16) bytes; 8-, 8- and 16-byte aligned); returns (n_rows,
+    n_bytes); complete when it returns"""
+    k, nb = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib().acx_filter_rows_device(d_hay or None, nbytes, d_offsets or None, n_hay, uniform_len, d_counts or None,
+                                        min_matches, flags, d_rows or None, d_out_offsets or None, d_data or None,
+                                        ctypes.byref(k), ctypes.byref(nb)))
+    return int(k.value), int(nb.value)
+
+
 def _replaced_bytes(h: int) -> bytes:
     buf = bytearray(int(lib().acx_replaced_len(h)))
     if buf:
@@ -980,6 +1087,29 @@ class Automaton:
         _check(lib().acx_tally_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
                                       ctypes.byref(out)))
         return DeviceTally(out.value)
+
+    # ---- keep or drop the rows of a batch by match (acx_filter / acx_filter_device)
+    def filter(self, haystacks: Optional[Sequence[bytes]], overlapping: bool = False, min_matches: int = 1, flags: int = 0, *,
+               single: Optional[bytes] = None) -> DeviceFiltered:
+        """the kept rows of host haystacks, a host result; single=...: one haystack that is no batch (offsets = NULL)"""
+        out = ctypes.c_void_p()
+        if single is not None:
+            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
+            _check(lib().acx_filter(self._h, hb.ctypes.data, len(single), None, 1, int(overlapping), min_matches, flags,
+                                    ctypes.byref(out)))
+            return DeviceFiltered(out.value)
+        hb, hoff = pack(haystacks)
+        _check(lib().acx_filter(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
+                                min_matches, flags, ctypes.byref(out)))
+        return DeviceFiltered(out.value)
+
+    def filter_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
+                      overlapping: bool = False, min_matches: int = 1, flags: int = 0) -> DeviceFiltered:
+        """the batch in HBM searched and compacted there; nothing but the result's two sizes crosses the bus"""
+        out = ctypes.c_void_p()
+        _check(lib().acx_filter_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
+                                       min_matches, flags, ctypes.byref(out)))
+        return DeviceFiltered(out.value)
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

@@ -645,6 +645,18 @@ PyObject *bac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs);
      "rows back to back, cut by exactly one of offsets (a 1-D int64 __dlpack__ tensor of rows + 1 entries on the haystack's "  \
      "device) and row_length (an int that divides the tensor's length).  A tensor on the automaton's device is searched and "  \
      "reduced there and the result stays there; nothing but its size crosses the bus."}
+// the rows of a batch kept or dropped by match (defined behind the PatternCounts below)
+PyObject *ac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
+PyObject *bac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
+#define ACX_FILTER_METHOD(fn)                                                                                                  \
+    {"filter_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn)), METH_VARARGS | METH_KEYWORDS,            \
+     "[extension] filter_batch(haystacks, overlapping=False, *, keep='unmatched', min_matches=1, offsets=None, "               \
+     "row_length=None) -> FilteredRows: the rows of the batch with fewer than min_matches matches (keep='unmatched': drop "    \
+     "every row that contains a pattern) or with at least that many (keep='matched'), compacted where the search ran: "        \
+     ".rows (the kept source row indexes), .offsets and .data (the kept rows' own bytes back to back).  haystacks: a "          \
+     "sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "           \
+     "count_by_pattern_sparse_batch.  A tensor on the automaton's device is searched and compacted there and the result "      \
+     "stays there; nothing but its two sizes crosses the bus."}
 #define ACX_COLUMNS_METHODS(fn)                                                                                                 \
     {"find_matches_as_columns", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)),                        \
      METH_VARARGS | METH_KEYWORDS,                                                                                              \
@@ -682,6 +694,7 @@ PyMethodDef ac_methods[] = {
     ACX_SUMMARY_METHODS(ac_summary),
     ACX_COLUMNS_METHODS(ac_columns),
     ACX_SPARSE_COUNTS_METHOD(ac_sparse_counts),
+    ACX_FILTER_METHOD(ac_filter_batch),
     {"_info", ac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -993,6 +1006,7 @@ struct ColumnObject {
     PyObject *owner; // the MatchColumns
     int which;       // ACX_COL_*
     int64_t len;
+    int elem;        // 0: int64 words; 1: uint8 bytes (a FilteredRows' data)
 };
 
 void mc_dealloc(PyObject *self) {
@@ -1018,22 +1032,37 @@ struct PatternCountsObject {
     int device;          // the automaton's ordinal (where device parts lie)
     uint64_t n_patterns; // the matrix has this many columns
 };
+// ... or a FilteredRows (which: ACX_FILT_*; defined behind the PatternCounts)
+PyTypeObject *FilteredRowsType = nullptr;
+struct FilteredRowsObject {
+    PyObject_HEAD
+    acx_filtered_t *f;
+    int device;      // the automaton's ordinal (where device parts lie)
+    uint64_t n_src;  // the rows of the batch that was filtered
+    bool utf8;       // made by the str class: tolist() decodes
+};
 bool col_of_counts(ColumnObject *o) { return Py_TYPE(o->owner) == PatternCountsType; }
+bool col_of_filtered(ColumnObject *o) { return Py_TYPE(o->owner) == FilteredRowsType; }
+acx_filtered_t *col_filtered(ColumnObject *o) { return reinterpret_cast<FilteredRowsObject *>(o->owner)->f; }
 acx_columns_t *col_handle(ColumnObject *o) { return reinterpret_cast<MatchColumnsObject *>(o->owner)->c; }
 acx_tally_t *col_tally(ColumnObject *o) { return reinterpret_cast<PatternCountsObject *>(o->owner)->t; }
 int col_device(ColumnObject *o) {
+    if (col_of_filtered(o)) return reinterpret_cast<FilteredRowsObject *>(o->owner)->device;
     return col_of_counts(o) ? reinterpret_cast<PatternCountsObject *>(o->owner)->device
                             : reinterpret_cast<MatchColumnsObject *>(o->owner)->device;
 }
 bool col_on_device(ColumnObject *o) {
+    if (col_of_filtered(o)) return acx_filtered_on_device(col_filtered(o)) != 0;
     return col_of_counts(o) ? acx_tally_on_device(col_tally(o)) != 0 : acx_columns_on_device(col_handle(o)) != 0;
 }
 
 // the part's address once the device work is done (GIL released around the wait); sets the exception
-const int64_t *col_data(ColumnObject *o) {
-    const int64_t *p;
+const void *col_data(ColumnObject *o) {
+    const void *p;
     Py_BEGIN_ALLOW_THREADS
-    p = col_of_counts(o) ? acx_tally_data(col_tally(o), o->which) : acx_columns_data(col_handle(o), o->which);
+    p = col_of_filtered(o) ? acx_filtered_data(col_filtered(o), o->which)
+        : col_of_counts(o) ? (const void *)acx_tally_data(col_tally(o), o->which)
+                           : (const void *)acx_columns_data(col_handle(o), o->which);
     Py_END_ALLOW_THREADS
     if (!p) PyErr_SetString(PyExc_RuntimeError, "the column's device work failed");
     return p;
@@ -1164,16 +1193,16 @@ PyObject *col_dlpack(PyObject *self_, PyObject *args, PyObject *) {
         return nullptr;
     }
     ColumnObject *self = reinterpret_cast<ColumnObject *>(self_);
-    const int64_t *p = col_data(self);
+    const void *p = col_data(self);
     if (!p) return nullptr;
     ColumnExport *e = new (std::nothrow) ColumnExport();
     if (!e) return PyErr_NoMemory();
     e->shape[0] = self->len;
     e->strides[0] = 1;
-    e->mt.dl_tensor.data = const_cast<int64_t *>(p);
+    e->mt.dl_tensor.data = const_cast<void *>(p);
     e->mt.dl_tensor.device = col_on_device(self) ? DLDeviceC{kDLROCM, col_device(self)} : DLDeviceC{kDLCPU, 0};
     e->mt.dl_tensor.ndim = 1;
-    e->mt.dl_tensor.dtype = DLDataTypeC{0 /* kDLInt */, 64, 1};
+    e->mt.dl_tensor.dtype = self->elem ? DLDataTypeC{1 /* kDLUInt */, 8, 1} : DLDataTypeC{0 /* kDLInt */, 64, 1};
     e->mt.dl_tensor.shape = e->shape;
     e->mt.dl_tensor.strides = e->strides;
     e->mt.dl_tensor.byte_offset = 0;
@@ -1186,7 +1215,7 @@ PyObject *col_dlpack(PyObject *self_, PyObject *args, PyObject *) {
     return cap;
 }
 
-// the buffer protocol of a host column: read-only, format "q"
+// the buffer protocol of a host column: read-only, format "q" (a FilteredRows' data: "B")
 int col_getbuffer(PyObject *self_, Py_buffer *view, int flags) {
     ColumnObject *self = reinterpret_cast<ColumnObject *>(self_);
     view->obj = nullptr;
@@ -1198,17 +1227,18 @@ int col_getbuffer(PyObject *self_, Py_buffer *view, int flags) {
         PyErr_SetString(PyExc_BufferError, "the column is read-only");
         return -1;
     }
-    const int64_t *p = col_data(self);
+    const void *p = col_data(self);
     if (!p) return -1;
-    static Py_ssize_t one_stride = 8;
-    view->buf = const_cast<int64_t *>(p);
-    view->len = (Py_ssize_t)self->len * 8;
-    view->itemsize = 8;
+    static Py_ssize_t word_stride = 8, byte_stride = 1;
+    const Py_ssize_t item = self->elem ? 1 : 8;
+    view->buf = const_cast<void *>(p);
+    view->len = (Py_ssize_t)self->len * item;
+    view->itemsize = item;
     view->readonly = 1;
     view->ndim = 1;
-    view->format = (flags & PyBUF_FORMAT) ? const_cast<char *>("q") : nullptr;
+    view->format = (flags & PyBUF_FORMAT) ? const_cast<char *>(self->elem ? "B" : "q") : nullptr;
     view->shape = (flags & PyBUF_ND) ? reinterpret_cast<Py_ssize_t *>(&self->len) : nullptr;
-    view->strides = (flags & PyBUF_STRIDES) == PyBUF_STRIDES ? &one_stride : nullptr;
+    view->strides = (flags & PyBUF_STRIDES) == PyBUF_STRIDES ? (self->elem ? &byte_stride : &word_stride) : nullptr;
     view->suboffsets = nullptr;
     view->internal = nullptr;
     Py_INCREF(self_);
@@ -1230,8 +1260,8 @@ PyType_Slot col_slots[] = {
     {Py_sq_length, reinterpret_cast<void *>(col_len)},
     {Py_bf_getbuffer, reinterpret_cast<void *>(col_getbuffer)},
     {Py_tp_doc, const_cast<char *>(
-        "One int64 column of a MatchColumns: len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
-        "copy) and, in host memory, the buffer protocol (format 'q', read-only).")},
+        "One int64 column of a MatchColumns or a PatternCounts, or one part of a FilteredRows (int64; its data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
+        "copy) and, in host memory, the buffer protocol (format 'q', or 'B' for uint8; read-only).")},
     {0, nullptr},
 };
 
@@ -1601,6 +1631,183 @@ PyObject *bac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs) {
     return sparse_counts_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false);
 }
 
+// ---------------------------------------------------------------------------
+// rows kept or dropped by match: filter_batch -> FilteredRows (acx_filter / acx_filter_device).  A FilteredRows owns the
+// acx_filtered_t; its three parts are Columns (rows and offsets int64, data uint8) with the lifetime chain of a
+// MatchColumns' columns.
+// ---------------------------------------------------------------------------
+void fr_dealloc(PyObject *self) {
+    FilteredRowsObject *o = reinterpret_cast<FilteredRowsObject *>(self);
+    if (o->f) acx_free_filtered(o->f); // (waits for the device stage's last kernel if nobody has)
+    PyTypeObject *tp = Py_TYPE(self);
+    tp->tp_free(self);
+    Py_DECREF(tp);
+}
+
+PyObject *fr_column(PyObject *self_, int which) {
+    FilteredRowsObject *self = reinterpret_cast<FilteredRowsObject *>(self_);
+    ColumnObject *col = reinterpret_cast<ColumnObject *>(ColumnType->tp_alloc(ColumnType, 0));
+    if (!col) return nullptr;
+    Py_INCREF(self_);
+    col->owner = self_;
+    col->which = which;
+    col->elem = which == ACX_FILT_DATA ? 1 : 0;
+    col->len = (int64_t)(which == ACX_FILT_DATA ? acx_filtered_bytes(self->f)
+                                                 : acx_filtered_rows(self->f) + (which == ACX_FILT_OFFSETS ? 1 : 0));
+    return reinterpret_cast<PyObject *>(col);
+}
+PyObject *fr_get_rows(PyObject *s, void *) { return fr_column(s, ACX_FILT_ROWS); }
+PyObject *fr_get_offsets(PyObject *s, void *) { return fr_column(s, ACX_FILT_OFFSETS); }
+PyObject *fr_get_data(PyObject *s, void *) { return fr_column(s, ACX_FILT_DATA); }
+PyObject *fr_get_device(PyObject *s, void *) {
+    FilteredRowsObject *o = reinterpret_cast<FilteredRowsObject *>(s);
+    if (!acx_filtered_on_device(o->f)) Py_RETURN_NONE;
+    return PyLong_FromLong(o->device);
+}
+PyObject *fr_get_nbytes(PyObject *s, void *) {
+    return PyLong_FromUnsignedLongLong(acx_filtered_bytes(reinterpret_cast<FilteredRowsObject *>(s)->f));
+}
+PyObject *fr_get_source_rows(PyObject *s, void *) {
+    return PyLong_FromUnsignedLongLong(reinterpret_cast<FilteredRowsObject *>(s)->n_src);
+}
+Py_ssize_t fr_len(PyObject *s) { return (Py_ssize_t)acx_filtered_rows(reinterpret_cast<FilteredRowsObject *>(s)->f); }
+
+// the kept rows: list[str] of the str class (UTF-8 decoded), list[bytes] of the bytes class
+PyObject *fr_tolist(PyObject *self_, PyObject *) {
+    FilteredRowsObject *self = reinterpret_cast<FilteredRowsObject *>(self_);
+    const uint64_t k = acx_filtered_rows(self->f), nb = acx_filtered_bytes(self->f);
+    std::vector<int64_t> off((size_t)k + 1);
+    std::vector<uint8_t> data((size_t)nb + 1);
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = acx_filtered_copy(self->f, ACX_FILT_OFFSETS, off.data());
+    if (rc == ACX_OK) rc = acx_filtered_copy(self->f, ACX_FILT_DATA, data.data());
+    Py_END_ALLOW_THREADS
+    if (rc != ACX_OK) return raise_acx(rc);
+    PyObject *list = PyList_New((Py_ssize_t)k);
+    for (uint64_t i = 0; list && i < k; i++) {
+        const char *b = reinterpret_cast<const char *>(data.data()) + off[(size_t)i];
+        const Py_ssize_t n = (Py_ssize_t)(off[(size_t)i + 1] - off[(size_t)i]);
+        PyObject *it = self->utf8 ? PyUnicode_DecodeUTF8(b, n, nullptr) : PyBytes_FromStringAndSize(b, n);
+        if (!it) { Py_CLEAR(list); break; }
+        PyList_SET_ITEM(list, (Py_ssize_t)i, it);
+    }
+    return list;
+}
+
+PyGetSetDef fr_getset[] = {
+    {"rows", fr_get_rows, nullptr, "Column of len(self) int64 entries: the kept source row indexes, strictly ascending", nullptr},
+    {"offsets", fr_get_offsets, nullptr, "Column of len(self) + 1 int64 entries from 0: kept row i is data[offsets[i]:offsets[i + 1]]",
+     nullptr},
+    {"data", fr_get_data, nullptr, "Column of nbytes uint8 entries: the kept rows' own bytes back to back", nullptr},
+    {"device", fr_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {"nbytes", fr_get_nbytes, nullptr, "the size of data", nullptr},
+    {"source_rows", fr_get_source_rows, nullptr, "the rows of the batch that was filtered", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+PyMethodDef fr_methods[] = {
+    {"tolist", fr_tolist, METH_NOARGS,
+     "the kept rows as list[str] (the str class: UTF-8 decoded) or list[bytes] (copies device parts to the host)"},
+    {nullptr, nullptr, 0, nullptr},
+};
+PyType_Slot fr_slots[] = {
+    {Py_tp_dealloc, reinterpret_cast<void *>(fr_dealloc)},
+    {Py_tp_methods, fr_methods},
+    {Py_tp_getset, fr_getset},
+    {Py_sq_length, reinterpret_cast<void *>(fr_len)},
+    {Py_tp_doc, const_cast<char *>(
+        "The result of filter_batch: the kept rows of a batch as a compacted batch.  .rows and .offsets are int64 Column "
+        "objects, .data a uint8 one, where the search ran (.device); len(self) is the number of kept rows, .nbytes the size "
+        "of .data, .source_rows the rows of the batch.  Kept row i is source row rows[i] = data[offsets[i]:offsets[i + 1]].")},
+    {0, nullptr},
+};
+
+// filter_batch of both classes: utf8 = the str class (no offset into a row is reported: the search is on bytes)
+PyObject *filter_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool utf8) {
+    static const char *kw[] = {"haystacks", "overlapping", "keep", "min_matches", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *ov = nullptr, *keep = nullptr, *mm = nullptr, *offsets = nullptr, *row_length = nullptr;
+    int overlapping = 0;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$OOOO:filter_batch", const_cast<char **>(kw), &hay, &ov, &keep, &mm,
+                                     &offsets, &row_length))
+        return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    uint32_t flags = 0;
+    if (keep) {
+        if (!PyUnicode_Check(keep)) {
+            PyErr_Format(PyExc_TypeError, "argument 'keep': '%.100s' object cannot be converted to 'PyString'", Py_TYPE(keep)->tp_name);
+            return nullptr;
+        }
+        if (PyUnicode_CompareWithASCIIString(keep, "matched") == 0) flags = ACX_FILTER_KEEP_MATCHED;
+        else if (PyUnicode_CompareWithASCIIString(keep, "unmatched") != 0) {
+            PyErr_SetString(PyExc_ValueError, "keep must be 'unmatched' or 'matched'");
+            return nullptr;
+        }
+    }
+    unsigned long long min_matches = 1;
+    if (mm) {
+        if (!PyLong_Check(mm) || PyBool_Check(mm)) {
+            PyErr_Format(PyExc_TypeError, "argument 'min_matches': '%.100s' object cannot be converted to 'PyInt'",
+                         Py_TYPE(mm)->tp_name);
+            return nullptr;
+        }
+        int overflow = 0;
+        const long long v = PyLong_AsLongLongAndOverflow(mm, &overflow);
+        if (v == -1 && !overflow && PyErr_Occurred()) return nullptr;
+        if (overflow < 0 || (!overflow && v < 1)) {
+            PyErr_SetString(PyExc_ValueError, "min_matches must be at least 1");
+            return nullptr;
+        }
+        min_matches = overflow ? ~0ull : (unsigned long long)v; // (more than any row can have)
+    }
+    const int device = acx_automaton_device(a);
+    BatchInput in;
+    if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
+    acx_filtered_t *f = nullptr;
+    int rc;
+    bool bad_offsets = false;
+    std::vector<uint64_t> cut;
+    if (in.tensor && !in.on_device && in.row_length) {
+        cut.resize((size_t)in.rows + 1);
+        for (uint64_t i = 0; i <= in.rows; i++) cut[(size_t)i] = i * in.row_length;
+    }
+    Py_BEGIN_ALLOW_THREADS
+    if (!in.tensor) {
+        rc = acx_filter(a, in.blob.data(), in.off[(size_t)in.rows], in.off.data(), in.rows, overlapping, min_matches, flags, &f);
+    } else if (!in.on_device) {
+        rc = acx_filter(a, in.p, in.len, in.row_length ? cut.data() : in.t_off, in.rows, overlapping, min_matches, flags, &f);
+    } else {
+        rc = acx_device_synchronize_on(device); // (the producer's kernels may still write the tensors)
+        if (rc == ACX_OK && in.t_off) { // where the offsets begin and end; between the two they are the caller's word
+            uint64_t ends[2] = {1, 0};
+            rc = acx_device_download(&ends[0], in.t_off, 8);
+            if (rc == ACX_OK) rc = acx_device_download(&ends[1], in.t_off + in.rows, 8);
+            bad_offsets = rc == ACX_OK && (ends[0] != 0 || ends[1] != in.len);
+        }
+        if (rc == ACX_OK && !bad_offsets)
+            rc = acx_filter_device(a, in.p, in.len, in.t_off, in.rows, in.row_length, overlapping, min_matches, flags, &f);
+    }
+    Py_END_ALLOW_THREADS
+    if (bad_offsets) {
+        PyErr_SetString(PyExc_ValueError, "offsets must rise from 0 to the tensor's length");
+        return nullptr;
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    FilteredRowsObject *o = reinterpret_cast<FilteredRowsObject *>(FilteredRowsType->tp_alloc(FilteredRowsType, 0));
+    if (!o) { acx_free_filtered(f); return nullptr; }
+    o->f = f;
+    o->device = device;
+    o->n_src = in.rows;
+    o->utf8 = utf8;
+    return reinterpret_cast<PyObject *>(o);
+}
+
+PyObject *ac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return filter_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, true);
+}
+PyObject *bac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return filter_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false);
+}
+
 // device-resident search -> list of tuples (the records come back with ONE D2H copy of the result)
 PyObject *find_on_device(acx_automaton_t *a, const uint8_t *d_hay, uint64_t len, int overlapping) {
     acx_result_t *r = nullptr;
@@ -1732,6 +1939,7 @@ PyMethodDef bac_methods[] = {
     ACX_SUMMARY_METHODS(bac_summary),
     ACX_COLUMNS_METHODS(bac_columns),
     ACX_SPARSE_COUNTS_METHOD(bac_sparse_counts),
+    ACX_FILTER_METHOD(bac_filter_batch),
     {"_info", bac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -1777,13 +1985,16 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
                             Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, col_slots};
     PyType_Spec pc_spec = {"ahocorasick_rs.PatternCounts", sizeof(PatternCountsObject), 0,
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, pc_slots};
+    PyType_Spec fr_spec = {"ahocorasick_rs.FilteredRows", sizeof(FilteredRowsObject), 0,
+                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, fr_slots};
+    FilteredRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&fr_spec));
     MatchColumnsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mc_spec));
     ColumnType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&col_spec));
     PatternCountsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&pc_spec));
-    if (!MatchColumnsType || !ColumnType || !PatternCountsType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
-    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType}) { // (the module holds one reference, the globals the other)
+    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
+    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType}) { // (the module holds one reference, the globals the other)
         Py_INCREF(tp);
-        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : "MatchColumns",
+        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : "MatchColumns",
                                reinterpret_cast<PyObject *>(tp)) < 0) {
             Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);
             return nullptr;

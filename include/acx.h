@@ -32,6 +32,9 @@ extern "C" {
  *     (acx_columns_count, _rows, _on_device, _data, _copy, acx_free_columns), acx_split_host / acx_split_device;
  *     third addendum (additive as well): acx_tally / acx_tally_device / acx_tally_host / acx_tally_rows_device, ACX_TALLY_*,
  *     the acx_tally_t accessors (acx_tally_nnz, _rows, _on_device, _data, _copy, acx_free_tally);
+ *     fourth addendum (additive as well): acx_filter / acx_filter_device / acx_filter_host / acx_filter_rows_device,
+ *     ACX_FILTER_KEEP_MATCHED, ACX_FILT_*, the acx_filtered_t accessors (acx_filtered_rows, _bytes, _on_device, _data, _copy,
+ *     acx_free_filtered);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -504,6 +507,59 @@ int acx_tally_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts, u
                    int64_t *pattern, int64_t *count, uint64_t *nnz);
 int acx_tally_rows_device(const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint64_t n_hay,
                           uint64_t n_patterns, int64_t *d_row_offsets, int64_t *d_pattern, int64_t *d_count, uint64_t *nnz);
+
+/* ---- filter: keep or drop the rows of a batch by match -- "drop every document that contains a blocked term", "keep the
+ * rows that mention one of these names" -- as a compacted batch where the search ran.  For a batch of n rows, c[h] = the
+ * number of row h's matches (acx_find_batch / acx_find_device for the same arguments): row h is MATCHED iff c[h] >=
+ * min_matches (>= 1; 0: ACX_EINVAL), and KEPT iff matched == (flags & ACX_FILTER_KEEP_MATCHED != 0) -- flags = 0 keeps the
+ * unmatched rows; any other bit: ACX_EINVAL.  The result is
+ *   ACX_FILT_ROWS     k words: the kept source row indexes, strictly ascending
+ *   ACX_FILT_OFFSETS  k + 1 words from 0
+ *   ACX_FILT_DATA     offsets[k] bytes: the kept rows back to back, row rows[i] = data[offsets[i] .. offsets[i + 1]), the
+ *                     caller's own bytes (a case-insensitive handle matches on a folded copy and copies the unfolded row)
+ * Empty rows are rows: a kept one is an entry of rows and a repeated offset.  Every match kind; an overlapping search on a
+ * non-Standard handle fails with ACX_EOVERLAP as the find does, and one over a set with copies counts every copy.  No offset
+ * into a row is reported, so the search runs on bytes whatever the caller's strings are.
+ * acx_filter: host haystacks (offsets: n_hay + 1, or null: one haystack of len bytes -- a batch of one row), a host result.
+ * The counts come from acx_summarize (what = 0), which chooses its own route: 8 bytes per row come back; the rows are then
+ * copied from the caller's memory by acx_filter_host, so the output never crosses the bus.
+ * acx_filter_device: acx_find_device's pipeline (d_offsets / uniform_len as there; neither: a batch of one row), then the
+ * device stage on the same stream -- two scans of the per-row counts and a ragged gather; the result stays in HBM on the
+ * automaton's device and only its two sizes (16 bytes) cross to the host.  The call returns when they are known; the gather
+ * may still run, and acx_filtered_data / acx_filtered_copy wait for it.  d_hay and d_offsets must stay valid until then.
+ * Nothing kept: the offsets part holds one 0.  Everything kept: the data is a device-to-device copy of the input.
+ * An empty part still has a valid, non-null address. */
+#define ACX_FILTER_KEEP_MATCHED 1
+#define ACX_FILT_ROWS 0
+#define ACX_FILT_OFFSETS 1
+#define ACX_FILT_DATA 2
+typedef struct acx_filtered acx_filtered_t;
+int acx_filter(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
+               int overlapping, uint64_t min_matches, uint32_t flags, acx_filtered_t **out);
+int acx_filter_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                      uint64_t uniform_len, int overlapping, uint64_t min_matches, uint32_t flags, acx_filtered_t **out);
+uint64_t acx_filtered_rows(const acx_filtered_t *f);   /* k: the kept rows; valid at return                      */
+uint64_t acx_filtered_bytes(const acx_filtered_t *f);  /* offsets[k]: the kept rows' bytes; valid at return      */
+int acx_filtered_on_device(const acx_filtered_t *f);   /* 1: the parts are in HBM, 0: host memory                */
+/* host or device pointer by acx_filtered_on_device (ROWS, OFFSETS: int64 words; DATA: bytes); waits for the device stage.
+ * NULL: no such part or the wait failed.  Valid until acx_free_filtered. */
+const void *acx_filtered_data(const acx_filtered_t *f, int which);
+int acx_filtered_copy(const acx_filtered_t *f, int which, void *host_dst);
+void acx_free_filtered(acx_filtered_t *f);
+/* the filter itself.  acx_filter_host: host memory, no device needed -- the definition above inside the library; counts:
+ * n_hay words; offsets: n_hay + 1 from 0 to len (ACX_EINVAL when they do not rise from 0 to len), or null: one row of len
+ * bytes; rows: room for n_hay, out_offsets: n_hay + 1, dst: len bytes -- any of the three may be NULL (dst = NULL: sizes
+ * only); *n_rows = k, *n_bytes = offsets[k].
+ * acx_filter_rows_device: the device stage alone on a caller's bytes, offsets (or uniform_len, or neither: one row) and
+ * counts in HBM on one device; needs no automaton; synchronous: the outputs are complete when it returns.  d_rows: room
+ * for n_hay words, d_out_offsets: n_hay + 1, d_data: round_up(len, 16) bytes -- the bytes behind *n_bytes up to the next
+ * multiple of 16 may be written.  The word arrays need 8-byte alignment, d_data 16-byte alignment, d_hay none. */
+int acx_filter_host(const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, const uint64_t *counts,
+                    uint64_t min_matches, uint32_t flags, int64_t *rows, int64_t *out_offsets,
+                    uint8_t *dst /* NULL: sizes only */, uint64_t *n_rows, uint64_t *n_bytes);
+int acx_filter_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
+                           const uint64_t *d_counts, uint64_t min_matches, uint32_t flags, int64_t *d_rows,
+                           int64_t *d_out_offsets, uint8_t *d_data, uint64_t *n_rows, uint64_t *n_bytes);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
