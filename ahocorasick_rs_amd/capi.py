@@ -616,13 +616,49 @@ def summarize_host(matches, counts: Optional[Sequence[int]], n_patterns: int, wh
             hist[:n_patterns] if what & SUM_BY_PATTERN else None)
 
 
-class DeviceColumns:
+class _PartsResult:
+    """What DeviceColumns, DeviceTally and DeviceFiltered share: a handle of the C ABI whose parts lie in HBM (on_device) or
+    in host memory.  A subclass names its three C functions (_ON_DEVICE, _DATA, _COPY, _FREE) and, in _part_shape(which), a
+    part's length and element type."""
+    _ON_DEVICE = _DATA = _COPY = _FREE = ""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    @property
+    def on_device(self) -> bool:
+        return bool(getattr(lib(), self._ON_DEVICE)(self._h))
+
+    def data_ptr(self, which: int) -> int:
+        """host or device address of the part (by on_device), behind the device work; 0: the result has no such part"""
+        return getattr(lib(), self._DATA)(self._h, which) or 0
+
+    def _copy_part(self, which: int) -> np.ndarray:
+        n, dtype = self._part_shape(which)
+        out = np.zeros(n, dtype=dtype)
+        _check(getattr(lib(), self._COPY)(self._h, which, out.ctypes.data if out.size else None))
+        return out
+
+    def free(self) -> None:
+        if self._h:
+            getattr(lib(), self._FREE)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DeviceColumns(_PartsResult):
     """The columns of Automaton.find_columns / find_columns_batch / find_columns_device (acx_columns_t): three int64
     columns of `count` words and, for a batch, n_hay + 1 row offsets -- in HBM (on_device) or in host memory.  column()
     copies one out; data_ptr() is where it lies (both wait for the split kernel)."""
+    _ON_DEVICE, _DATA, _COPY, _FREE = "acx_columns_on_device", "acx_columns_data", "acx_columns_copy", "acx_free_columns"
 
     def __init__(self, handle: int, batch: bool):
-        self._h = handle
+        super().__init__(handle)
         self.batch = batch
 
     @property
@@ -633,21 +669,11 @@ class DeviceColumns:
     def rows(self) -> int:
         return int(lib().acx_columns_rows(self._h))
 
-    @property
-    def on_device(self) -> bool:
-        return bool(lib().acx_columns_on_device(self._h))
-
-    def _words(self, which: int) -> int:
-        return self.rows + 1 if which == COL_ROW_OFFSETS else self.count
-
-    def data_ptr(self, which: int) -> int:
-        """host or device address of the column (by on_device); 0: the single form has no row offsets"""
-        return lib().acx_columns_data(self._h, which) or 0
+    def _part_shape(self, which: int):
+        return (self.rows + 1 if which == COL_ROW_OFFSETS else self.count), np.int64
 
     def column(self, which: int) -> np.ndarray:
-        out = np.zeros(self._words(which), dtype=np.int64)
-        _check(lib().acx_columns_copy(self._h, which, out.ctypes.data if out.size else None))
-        return out
+        return self._copy_part(which)
 
     def pattern(self) -> np.ndarray:
         return self.column(COL_PATTERN)
@@ -660,17 +686,6 @@ class DeviceColumns:
 
     def row_offsets(self) -> Optional[np.ndarray]:
         return self.column(COL_ROW_OFFSETS) if self.batch else None
-
-    def free(self) -> None:
-        if self._h:
-            lib().acx_free_columns(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def split_host(matches) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -687,13 +702,11 @@ def split_device(d_matches: int, n: int, d_pattern: int, d_start: int, d_end: in
     _check(lib().acx_split_device(d_matches or None, n, d_pattern or None, d_start or None, d_end or None))
 
 
-class DeviceTally:
+class DeviceTally(_PartsResult):
     """The result of Automaton.tally / tally_device (acx_tally_t): per-haystack pattern counts in CSR form -- rows + 1 row
     offsets, nnz patterns (ascending within a row) and nnz counts, int64 -- in HBM (on_device) or in host memory.  part()
     copies one out; data_ptr() is where it lies (both wait for the device stage)."""
-
-    def __init__(self, handle: int):
-        self._h = handle
+    _ON_DEVICE, _DATA, _COPY, _FREE = "acx_tally_on_device", "acx_tally_data", "acx_tally_copy", "acx_free_tally"
 
     @property
     def nnz(self) -> int:
@@ -703,18 +716,11 @@ class DeviceTally:
     def rows(self) -> int:
         return int(lib().acx_tally_rows(self._h))
 
-    @property
-    def on_device(self) -> bool:
-        return bool(lib().acx_tally_on_device(self._h))
-
-    def data_ptr(self, which: int) -> int:
-        """host or device address of the part (by on_device)"""
-        return lib().acx_tally_data(self._h, which) or 0
+    def _part_shape(self, which: int):
+        return (self.rows + 1 if which == TALLY_ROW_OFFSETS else self.nnz), np.int64
 
     def part(self, which: int) -> np.ndarray:
-        out = np.zeros(self.rows + 1 if which == TALLY_ROW_OFFSETS else self.nnz, dtype=np.int64)
-        _check(lib().acx_tally_copy(self._h, which, out.ctypes.data if out.size else None))
-        return out
+        return self._copy_part(which)
 
     def row_offsets(self) -> np.ndarray:
         return self.part(TALLY_ROW_OFFSETS)
@@ -724,17 +730,6 @@ class DeviceTally:
 
     def count(self) -> np.ndarray:
         return self.part(TALLY_COUNT)
-
-    def free(self) -> None:
-        if self._h:
-            lib().acx_free_tally(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def tally_host(matches, counts: Sequence[int]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -763,13 +758,11 @@ def tally_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, n_patte
     return int(nnz.value)
 
 
-class DeviceFiltered:
+class DeviceFiltered(_PartsResult):
     """The result of Automaton.filter / filter_device (acx_filtered_t): the kept rows of a batch -- k source row indexes
     and k + 1 offsets (int64) and the rows' bytes back to back (uint8) -- in HBM (on_device) or in host memory.  part()
     copies one out; data_ptr() is where it lies (both wait for the device stage)."""
-
-    def __init__(self, handle: int):
-        self._h = handle
+    _ON_DEVICE, _DATA, _COPY, _FREE = "acx_filtered_on_device", "acx_filtered_data", "acx_filtered_copy", "acx_free_filtered"
 
     @property
     def n_rows(self) -> int:
@@ -779,21 +772,11 @@ class DeviceFiltered:
     def nbytes(self) -> int:
         return int(lib().acx_filtered_bytes(self._h))
 
-    @property
-    def on_device(self) -> bool:
-        return bool(lib().acx_filtered_on_device(self._h))
-
-    def data_ptr(self, which: int) -> int:
-        """host or device address of the part (by on_device)"""
-        return lib().acx_filtered_data(self._h, which) or 0
+    def _part_shape(self, which: int):
+        return (self.nbytes, np.uint8) if which == FILT_DATA else (self.n_rows + (which == FILT_OFFSETS), np.int64)
 
     def part(self, which: int) -> np.ndarray:
-        if which == FILT_DATA:
-            out = np.zeros(self.nbytes, dtype=np.uint8)
-        else:
-            out = np.zeros(self.n_rows + (which == FILT_OFFSETS), dtype=np.int64)
-        _check(lib().acx_filtered_copy(self._h, which, out.ctypes.data if out.size else None))
-        return out
+        return self._copy_part(which)
 
     def rows(self) -> np.ndarray:
         return self.part(FILT_ROWS)
@@ -803,17 +786,6 @@ class DeviceFiltered:
 
     def data(self) -> np.ndarray:
         return self.part(FILT_DATA)
-
-    def free(self) -> None:
-        if self._h:
-            lib().acx_free_filtered(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def filter_host(hay, offsets: Optional[Sequence[int]], counts: Sequence[int], min_matches: int = 1, flags: int = 0, *,

@@ -1,39 +1,28 @@
 // columns_api.cpp -- a find's matches as columns (columns.hpp): the host split, the device route behind the find pipeline,
 // the acx_find_columns* entry points and the accessors of their result.
 #include "columns.hpp"
-#include "find_pipeline.hpp"
 #include "replace.hpp"
+#include "result_block.hpp"
 
 using namespace acxh;
 
 // acx_find_columns / acx_find_columns_device: three columns of `n` words and, for a batch, rows + 1 row offsets, in ONE
-// block.  Device route: a block of the buffer cache (g_bufs, workspace.cpp), written by kernels that may still run when the
-// call returns (done); the find's records have gone back to the cache behind the same kernels, only the columns and the
-// scan's scratch are kept until acx_free_columns.  Host route: a block of host memory.
-struct ACX_HIDDEN acx_columns {
-    int device = 0;
-    int on_device = 0;
+// block (result_block.hpp).  Device route: the find's records have gone back to the cache behind the split, only the
+// columns and the scan's scratch are kept until acx_free_columns.
+struct ACX_HIDDEN acx_columns : ResultBlock {
     bool batch = false;
     uint64_t n = 0, rows = 0;
     int64_t *col[4] = {nullptr, nullptr, nullptr, nullptr}; // ACX_COL_*; [3]: null in the single form
-    int64_t *h_block = nullptr;
-    void *d_block = nullptr;
-    hipEvent_t done = nullptr;
-    std::vector<void *> scratch;
+
+    int alloc() { // the block (by on_device) and the columns' places in it
+        const Layout L = batch ? block_layout({n * 8, n * 8, n * 8, (rows + 1) * 8}) : block_layout({n * 8, n * 8, n * 8});
+        int rc = ResultBlock::alloc(L.bytes);
+        for (int k = 0; rc == ACX_OK && k < 3 + (batch ? 1 : 0); k++) col[k] = (int64_t *)(base() + L.at[k]);
+        return rc;
+    }
 };
 
 namespace {
-
-// where the parts of a block begin, in words: every part at least one word long (a column of no matches still has an
-// address that DLPack consumers accept) and a multiple of 32 words (256 bytes) behind the previous one
-struct Layout {
-    uint64_t at[4], words;
-    Layout(uint64_t n, uint64_t rows, bool batch) {
-        const uint64_t c = (std::max<uint64_t>(n, 1) + 31) / 32 * 32;
-        for (int k = 0; k < 4; k++) at[k] = (uint64_t)k * c;
-        words = 3 * c + (batch ? (rows + 1 + 31) / 32 * 32 : 0);
-    }
-};
 
 // The device route: the find pipeline as acx_find_device runs it (byte ranges, batch splits and the expansion of copies
 // included), then the split -- and, for a batch, the scan of the counts -- on the same stream.  Returns when the number of
@@ -55,10 +44,9 @@ int run_columns(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, co
     R->batch = segmented;
     R->rows = segmented ? G.n_hay : 0;
     R->n = r ? r->n : 0;
-    const Layout L(R->n, R->rows, R->batch);
     auto body = [&]() -> int {
-        HIPCHK(g_bufs.get(&R->d_block, L.words * 8, a->device));
-        for (int k = 0; k < 3 + (R->batch ? 1 : 0); k++) R->col[k] = (int64_t *)R->d_block + L.at[k];
+        int rc = R->alloc();
+        if (rc != ACX_OK) return rc;
         if (r) HIPCHK(acx::col_split(r->d_matches, R->n, R->col[0], R->col[1], R->col[2], st));
         if (R->batch && R->rows) { // where every haystack's records begin, from the counts
             uint64_t *temp = nullptr;
@@ -68,43 +56,11 @@ int run_columns(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, co
         } else if (R->batch) {
             HIPCHK(hipMemsetAsync(R->col[3], 0, 8, st));
         }
-        // The find's records and counts are not needed beyond this point of the stream: they go back to the buffer cache,
-        // which holds them until an event recorded HERE has fired (the result's own event lies in front of the split).
-        hipEvent_t freed = g_events.get(a->device);
-        R->done = g_events.get(a->device);
-        if (!freed || !R->done) {
-            HIPCHK(hipStreamSynchronize(st));
-            g_events.put(a->device, freed);
-            g_events.put(a->device, R->done);
-            freed = R->done = nullptr;
-        } else {
-            HIPCHK(hipEventRecord(freed, st));
-            HIPCHK(hipEventRecord(R->done, st));
-        }
-        if (r) {
-            g_events.put(a->device, r->done);
-            r->done = nullptr;
-            g_bufs.put(r->borrowed ? nullptr : r->d_matches, a->device, freed, r->d_counts);
-            r->d_matches = nullptr;
-            r->d_counts = nullptr;
-        } else {
-            g_events.put(a->device, freed);
-        }
         return ACX_OK;
     };
-    int rc = body();
-    if (rc != ACX_OK) (void)hipStreamSynchronize(st);
-    acx_free_result(r); // (emptied above when all went well)
+    int rc = retire_find(body(), st, r, R);
     if (rc != ACX_OK) { acx_free_columns(R); return rc; }
     *out = R;
-    return ACX_OK;
-}
-
-// every accessor's wait for the split (and the scan)
-int columns_wait(const acx_columns *c) {
-    if (!c->on_device || !c->done) return ACX_OK;
-    DeviceScope ds(c->device);
-    HIPCHK(hipEventSynchronize(c->done));
     return ACX_OK;
 }
 
@@ -154,14 +110,12 @@ int acx_find_columns(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const
     }
     if (rc != ACX_OK) return rc;
     acx_columns *R = new (std::nothrow) acx_columns();
-    const Layout L(nm, offsets ? n_hay : 0, offsets != nullptr);
-    if (R) R->h_block = new (std::nothrow) int64_t[L.words];
-    if (!R || !R->h_block) { acx_free_matches(m); delete R; return fail(ACX_ENOMEM, "out of memory"); }
+    if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
     R->device = a->device;
     R->batch = offsets != nullptr;
     R->rows = R->batch ? n_hay : 0;
     R->n = nm;
-    for (int k = 0; k < 3 + (R->batch ? 1 : 0); k++) R->col[k] = R->h_block + L.at[k];
+    if ((rc = R->alloc()) != ACX_OK) { acx_free_matches(m); delete R; return rc; }
     for (int k = 0; k < 3; k++) R->col[k][0] = 0; // (the one word of an empty column)
     rc = acx_split_host(m, nm, R->col[0], R->col[1], R->col[2]);
     acx_free_matches(m);
@@ -179,17 +133,9 @@ int acx_find_columns_device(acx_automaton_t *a, const void *d_hay, uint64_t len,
                             uint64_t uniform_len, int overlapping, int codepoints, acx_columns_t **out) {
     if (!a || !out) return fail(ACX_EINVAL, "null argument");
     *out = nullptr;
-    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
-    Segments G;
-    int rc = make_segments(d_offsets, n_hay, uniform_len, len, &G);
-    if (rc == ACX_OK && overlapping) rc = check_overlapping(a); // (the error, no device state)
-    if (rc != ACX_OK) return rc;
-    Lease lease(a);
-    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    const uint8_t *d_search = nullptr;
-    rc = fold_copy(a, lease.c, (const uint8_t *)d_hay, len, &d_search);
-    if (rc != ACX_OK) return rc;
-    return run_columns(a, lease.c, d_search, len, G, overlapping, codepoints, out);
+    return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, overlapping, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_columns(a, c, d_search, len, G, overlapping, codepoints, out);
+    });
 }
 
 uint64_t acx_columns_count(const acx_columns_t *c) { return c ? c->n : 0; }
@@ -197,36 +143,21 @@ uint64_t acx_columns_rows(const acx_columns_t *c) { return c ? c->rows : 0; }
 int acx_columns_on_device(const acx_columns_t *c) { return c ? c->on_device : 0; }
 
 const int64_t *acx_columns_data(const acx_columns_t *c, int which) {
-    if (!c || which < 0 || which > ACX_COL_ROW_OFFSETS || !c->col[which]) return nullptr;
-    if (columns_wait(c) != ACX_OK) return nullptr;
-    return c->col[which];
+    if (!c || which < 0 || which > ACX_COL_ROW_OFFSETS) return nullptr;
+    return (const int64_t *)c->ptr_after_wait(c->col[which]);
 }
 
 int acx_columns_copy(const acx_columns_t *c, int which, int64_t *host_dst) {
     if (!c || which < 0 || which > ACX_COL_ROW_OFFSETS) return fail(ACX_EINVAL, "no such column");
     if (!c->col[which]) return fail(ACX_EINVAL, "the single form has no row offsets");
     const uint64_t words = part_words(c, which);
-    if (!words) return ACX_OK;
-    if (!host_dst) return fail(ACX_EINVAL, "null argument");
-    if (!c->on_device) { std::memcpy(host_dst, c->col[which], words * 8); return ACX_OK; }
-    int rc = columns_wait(c);
-    if (rc != ACX_OK) return rc;
-    DeviceScope ds(c->device);
-    HIPCHK(hipMemcpy(host_dst, c->col[which], words * 8, hipMemcpyDeviceToHost));
-    return ACX_OK;
+    if (words && !host_dst) return fail(ACX_EINVAL, "null argument");
+    return c->copy_out(host_dst, c->col[which], words * 8);
 }
 
 void acx_free_columns(acx_columns_t *c) {
     if (!c) return;
-    if (c->on_device) {
-        DeviceScope ds(c->device);
-        // (the kernels write the columns and read the scratch: nothing goes back to the pool before they are done)
-        if (c->done) (void)hipEventSynchronize(c->done);
-        for (void *p : c->scratch) g_bufs.put(p, c->device);
-        g_bufs.put(c->d_block, c->device);
-        g_events.put(c->device, c->done);
-    }
-    delete[] c->h_block;
+    c->release();
     delete c;
 }
 

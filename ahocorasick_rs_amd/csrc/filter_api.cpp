@@ -1,40 +1,27 @@
 // filter_api.cpp -- keep or drop the rows of a batch by match (filter.hpp): the host form, the device stage behind the find
 // pipeline, the acx_filter* entry points and the accessors of their result.
 #include "filter.hpp"
-#include "find_pipeline.hpp"
 #include "replace.hpp"
+#include "result_block.hpp"
 
 using namespace acxh;
 
 // acx_filter / acx_filter_device: the kept rows' source indexes (k words), their offsets (k + 1 words) and their bytes in ONE
-// block.  Device route: a block of the buffer cache (g_bufs, workspace.cpp), written by kernels that may still run when the
-// call returns (done); the find's records and counts and the stage's temporaries have gone back to the cache behind the
-// same kernels.  Host route: a block of host memory.
-struct ACX_HIDDEN acx_filtered {
-    int device = 0;
-    int on_device = 0;
+// block (result_block.hpp), the data part rounded up to 16 bytes for the tile's stores.  Device route: the find's records
+// and counts and the stage's temporaries have gone back to the cache behind the stage's kernels.
+struct ACX_HIDDEN acx_filtered : ResultBlock {
     uint64_t n_src = 0, rows = 0, bytes = 0;
     uint8_t *part[3] = {nullptr, nullptr, nullptr}; // ACX_FILT_*
-    uint8_t *h_block = nullptr;
-    void *d_block = nullptr;
-    hipEvent_t done = nullptr;
+
+    int alloc() { // the block (by on_device) and the parts' places in it
+        const Layout L = block_layout({rows * 8, (rows + 1) * 8, std::max<uint64_t>((bytes + 15) / 16 * 16, 16)}, 16);
+        int rc = ResultBlock::alloc(L.bytes);
+        for (int p = 0; rc == ACX_OK && p < 3; p++) part[p] = base() + L.at[p];
+        return rc;
+    }
 };
 
 namespace {
-
-// where the parts of a block begin, in bytes: every part at least one word long (an empty part still has an address that
-// DLPack consumers accept) and a multiple of 256 bytes behind the previous one (the rules of the columns' block,
-// columns_api.cpp); the data part rounded up to 16 bytes for the tile's stores
-struct Layout {
-    uint64_t at[3], bytes;
-    Layout(uint64_t k, uint64_t total) {
-        const uint64_t r = (std::max<uint64_t>(k, 1) * 8 + 255) / 256 * 256, o = ((k + 1) * 8 + 255) / 256 * 256;
-        at[ACX_FILT_ROWS] = 0;
-        at[ACX_FILT_OFFSETS] = r;
-        at[ACX_FILT_DATA] = r + o;
-        bytes = r + o + std::max<uint64_t>((total + 15) / 16 * 16, 16);
-    }
-};
 
 uint64_t part_bytes(const acx_filtered_t *f, int which) {
     return which == ACX_FILT_ROWS ? f->rows * 8 : which == ACX_FILT_OFFSETS ? (f->rows + 1) * 8 : f->bytes;
@@ -54,11 +41,10 @@ int stage_sizes(int device, hipStream_t st, const acx::FilterRows &R, const uint
     S->R = R;
     const uint64_t n = R.n;
     // [klen: n][kflag: n][A: n + 1][B: n + 1][scan][src: n][tiles], every part 256-byte aligned
-    uint64_t at = 0;
-    auto part = [&](uint64_t w) { const uint64_t here = at; at += (w + 31) / 32 * 32; return here; };
-    const uint64_t o_len = part(n), o_flag = part(n), o_a = part(n + 1), o_b = part(n + 1), o_scan = part(replace_scan_words(n)),
-                   o_src = part(n), o_tiles = part(acx::filter_tile_words(R.len));
-    HIPCHK(g_bufs.get(&S->block, std::max<uint64_t>(at, 32) * 8, device));
+    Carver C;
+    const uint64_t o_len = C.part(n), o_flag = C.part(n), o_a = C.part(n + 1), o_b = C.part(n + 1),
+                   o_scan = C.part(replace_scan_words(n)), o_src = C.part(n), o_tiles = C.part(acx::filter_tile_words(R.len));
+    HIPCHK(g_bufs.get(&S->block, C.bytes(), device));
     uint64_t *b = (uint64_t *)S->block;
     S->klen = b + o_len;
     S->kflag = b + o_flag;
@@ -125,73 +111,22 @@ int run_filter(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_
     R->on_device = 1;
     R->n_src = n;
     Stage S;
-    uint64_t *one_count = nullptr; // (one haystack that is no batch: the find kept no counts)
+    uint64_t *one_count = nullptr;
     auto body = [&]() -> int {
-        uint64_t k = 0, total = 0;
+        int rc;
         if (n) {
-            const uint64_t *d_counts = r->d_counts;
-            if (!d_counts) {
-                HIPCHK(g_bufs.get((void **)&one_count, 16, a->device));
-                HIPCHK(hipMemcpyAsync(one_count, &r->n, 8, hipMemcpyHostToDevice, st));
-                d_counts = one_count;
-            }
+            const uint64_t *d_counts = nullptr;
+            if ((rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
             const acx::FilterRows rows{G.offsets, G.uniform_len, n, len};
-            int rc = stage_sizes(a->device, st, rows, d_counts, min_matches, (flags & ACX_FILTER_KEEP_MATCHED) != 0, &S, &k, &total);
+            rc = stage_sizes(a->device, st, rows, d_counts, min_matches, (flags & ACX_FILTER_KEEP_MATCHED) != 0, &S, &R->rows, &R->bytes);
             if (rc != ACX_OK) return rc;
         }
-        R->rows = k;
-        R->bytes = total;
-        const Layout L(k, total);
-        HIPCHK(g_bufs.get(&R->d_block, L.bytes, a->device));
-        for (int p = 0; p < 3; p++) R->part[p] = (uint8_t *)R->d_block + L.at[p];
-        int rc = stage_finish(&S, d_hay, k, total, (int64_t *)R->part[0], (int64_t *)R->part[1], R->part[2], st);
-        if (rc != ACX_OK) return rc;
-        // The find's records and counts and the stage's temporaries are not needed beyond this point of the stream: they go
-        // back to the buffer cache, which holds them until an event recorded HERE has fired.
-        hipEvent_t freed = g_events.get(a->device), freed2 = g_events.get(a->device);
-        R->done = g_events.get(a->device);
-        if (!freed || !freed2 || !R->done) {
-            HIPCHK(hipStreamSynchronize(st));
-            g_events.put(a->device, freed);
-            g_events.put(a->device, freed2);
-            g_events.put(a->device, R->done);
-            freed = freed2 = R->done = nullptr;
-        } else {
-            HIPCHK(hipEventRecord(freed, st));
-            HIPCHK(hipEventRecord(freed2, st));
-            HIPCHK(hipEventRecord(R->done, st));
-        }
-        if (r) {
-            g_events.put(a->device, r->done);
-            r->done = nullptr;
-            g_bufs.put(r->borrowed ? nullptr : r->d_matches, a->device, freed, r->d_counts);
-            r->d_matches = nullptr;
-            r->d_counts = nullptr;
-        } else {
-            g_events.put(a->device, freed);
-        }
-        g_bufs.put(S.block, a->device, freed2, one_count);
-        S.block = nullptr;
-        one_count = nullptr;
-        return ACX_OK;
+        if ((rc = R->alloc()) != ACX_OK) return rc;
+        return stage_finish(&S, d_hay, R->rows, R->bytes, (int64_t *)R->part[0], (int64_t *)R->part[1], R->part[2], st);
     };
-    int rc = body();
-    if (rc != ACX_OK) {
-        (void)hipStreamSynchronize(st);
-        g_bufs.put(S.block, a->device);
-        g_bufs.put(one_count, a->device);
-    }
-    acx_free_result(r); // (emptied above when all went well)
+    int rc = retire_find(body(), st, r, R, S.block, one_count);
     if (rc != ACX_OK) { acx_free_filtered(R); return rc; }
     *out = R;
-    return ACX_OK;
-}
-
-// every accessor's wait for the stage's last kernel
-int filtered_wait(const acx_filtered_t *f) {
-    if (!f->on_device || !f->done) return ACX_OK;
-    DeviceScope ds(f->device);
-    HIPCHK(hipEventSynchronize(f->done));
     return ACX_OK;
 }
 
@@ -236,42 +171,31 @@ int acx_filter(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint6
     int rc = check_args(min_matches, flags);
     if (rc == ACX_OK && overlapping) rc = check_overlapping(a); // (the error, no device state)
     if (rc != ACX_OK) return rc;
-    uint64_t base = 0;
-    if (offsets) {
-        for (uint64_t i = 0; i < n_hay; i++)
-            if (offsets[i + 1] < offsets[i]) return fail(ACX_EINVAL, "offsets not monotone");
-        base = offsets[0];
-        len = offsets[n_hay] - base;
-    } else {
-        n_hay = 1;
-    }
-    if (len && !hay) return fail(ACX_EINVAL, "null haystack");
-    const uint8_t *h = len ? hay + base : nullptr;
-    std::vector<uint64_t> rel, counts;
+    HostBatch B;
+    if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
+    std::vector<uint64_t> counts;
     try {
-        rel.resize(n_hay + 1);
         counts.assign(n_hay + 1, 0);
     } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
-    for (uint64_t i = 0; i <= n_hay; i++) rel[i] = offsets ? offsets[i] - base : (i ? len : 0);
     if (n_hay) { // the counts: the summary chooses its own route, 8 bytes per row come back
         acx_summary_t *s = nullptr;
-        rc = acx_summarize(a, h, len, offsets ? rel.data() : nullptr, n_hay, overlapping, 0, 0, &s);
+        rc = acx_summarize(a, B.hay, len, offsets ? B.rel.data() : nullptr, n_hay, overlapping, 0, 0, &s);
         if (rc == ACX_OK) rc = acx_summary_counts(s, counts.data());
         acx_free_summary(s);
         if (rc != ACX_OK) return rc;
     }
     // the gather: a memcpy per kept row from the caller's memory (the output never crosses the bus)
     uint64_t k = 0, total = 0;
-    rc = acx_filter_host(h, len, rel.data(), n_hay, counts.data(), min_matches, flags, nullptr, nullptr, nullptr, &k, &total);
+    rc = acx_filter_host(B.hay, len, B.rel.data(), n_hay, counts.data(), min_matches, flags, nullptr, nullptr, nullptr, &k, &total);
     if (rc != ACX_OK) return rc;
     acx_filtered_t *R = new (std::nothrow) acx_filtered_t();
-    const Layout L(k, total);
-    if (R) R->h_block = new (std::nothrow) uint8_t[L.bytes];
-    if (!R || !R->h_block) { delete R; return fail(ACX_ENOMEM, "out of memory"); }
+    if (!R) return fail(ACX_ENOMEM, "out of memory");
     R->device = a->device;
     R->n_src = n_hay;
-    for (int p = 0; p < 3; p++) R->part[p] = R->h_block + L.at[p];
-    rc = acx_filter_host(h, len, rel.data(), n_hay, counts.data(), min_matches, flags, (int64_t *)R->part[0], (int64_t *)R->part[1],
+    R->rows = k;
+    R->bytes = total;
+    if ((rc = R->alloc()) != ACX_OK) { delete R; return rc; }
+    rc = acx_filter_host(B.hay, len, B.rel.data(), n_hay, counts.data(), min_matches, flags, (int64_t *)R->part[0], (int64_t *)R->part[1],
                          R->part[2], &R->rows, &R->bytes);
     if (rc != ACX_OK) { acx_free_filtered(R); return rc; }
     *out = R;
@@ -284,17 +208,10 @@ int acx_filter_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const
     *out = nullptr;
     int rc = check_args(min_matches, flags);
     if (rc != ACX_OK) return rc;
-    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
-    Segments G;
-    rc = make_segments(d_offsets, n_hay, uniform_len, len, &G);
-    if (rc == ACX_OK && overlapping) rc = check_overlapping(a); // (the error, no device state)
-    if (rc != ACX_OK) return rc;
-    Lease lease(a);
-    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    const uint8_t *d_search = nullptr; // (a case-insensitive handle: the folded copy is searched, the caller's bytes are copied)
-    rc = fold_copy(a, lease.c, (const uint8_t *)d_hay, len, &d_search);
-    if (rc != ACX_OK) return rc;
-    return run_filter(a, lease.c, (const uint8_t *)d_hay, d_search, len, G, overlapping, min_matches, flags, out);
+    // (a case-insensitive handle: the folded copy is searched, the caller's bytes are copied)
+    return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, overlapping, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_filter(a, c, (const uint8_t *)d_hay, d_search, len, G, overlapping, min_matches, flags, out);
+    });
 }
 
 int acx_filter_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
@@ -343,33 +260,19 @@ int acx_filtered_on_device(const acx_filtered_t *f) { return f ? f->on_device : 
 
 const void *acx_filtered_data(const acx_filtered_t *f, int which) {
     if (!f || which < 0 || which > ACX_FILT_DATA) return nullptr;
-    if (filtered_wait(f) != ACX_OK) return nullptr;
-    return f->part[which];
+    return f->ptr_after_wait(f->part[which]);
 }
 
 int acx_filtered_copy(const acx_filtered_t *f, int which, void *host_dst) {
     if (!f || which < 0 || which > ACX_FILT_DATA) return fail(ACX_EINVAL, "no such part");
     const uint64_t bytes = part_bytes(f, which);
-    if (!bytes) return ACX_OK;
-    if (!host_dst) return fail(ACX_EINVAL, "null argument");
-    if (!f->on_device) { std::memcpy(host_dst, f->part[which], bytes); return ACX_OK; }
-    int rc = filtered_wait(f);
-    if (rc != ACX_OK) return rc;
-    DeviceScope ds(f->device);
-    HIPCHK(hipMemcpy(host_dst, f->part[which], bytes, hipMemcpyDeviceToHost));
-    return ACX_OK;
+    if (bytes && !host_dst) return fail(ACX_EINVAL, "null argument");
+    return f->copy_out(host_dst, f->part[which], bytes);
 }
 
 void acx_free_filtered(acx_filtered_t *f) {
     if (!f) return;
-    if (f->on_device) {
-        DeviceScope ds(f->device);
-        // (the kernels write the block: it does not go back to the pool before they are done)
-        if (f->done) (void)hipEventSynchronize(f->done);
-        g_bufs.put(f->d_block, f->device);
-        g_events.put(f->device, f->done);
-    }
-    delete[] f->h_block;
+    f->release();
     delete f;
 }
 

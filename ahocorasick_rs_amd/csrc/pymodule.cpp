@@ -244,6 +244,46 @@ bool batch_handles(acx_automaton_t *a, PyObject *devices, Replicas **replicas, s
     return true;
 }
 
+// The haystacks of a _batch method: a sequence of str (utf8, as UTF-8) or buffers, back to back in one blob with n + 1
+// offsets and a trailing 0 byte (the blob of an empty batch still has an address).  named: a str class's TypeError names the
+// argument, as `haystack` does in the single forms (the summaries, replace_all_batch); else it is PyO3's for a list item.
+struct Packed {
+    std::vector<uint8_t> blob;
+    std::vector<uint64_t> off;
+    bool all_ascii = true;
+    Py_ssize_t n = 0;
+};
+
+bool pack_sequence(PyObject *haystacks, bool utf8, bool named, Packed *out) {
+    PyObject *seq = PySequence_Fast(haystacks, "haystacks must be a sequence");
+    if (!seq) return false;
+    out->n = PySequence_Fast_GET_SIZE(seq);
+    out->off.assign((size_t)out->n + 1, 0);
+    for (Py_ssize_t i = 0; i < out->n; i++) {
+        PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
+        if (utf8) {
+            if (!PyUnicode_Check(it)) {
+                PyErr_Format(PyExc_TypeError, named ? "argument 'haystack': '%.100s' object cannot be converted to 'PyString'"
+                                                    : "'%.100s' object cannot be converted to 'PyString'", Py_TYPE(it)->tp_name);
+                Py_DECREF(seq); return false;
+            }
+            Py_ssize_t len; const char *s = PyUnicode_AsUTF8AndSize(it, &len);
+            if (!s) { Py_DECREF(seq); return false; }
+            out->all_ascii = out->all_ascii && PyUnicode_IS_ASCII(it);
+            out->blob.insert(out->blob.end(), s, s + len);
+        } else {
+            Py_buffer v;
+            if (!get_bytes_view(it, &v)) { Py_DECREF(seq); return false; }
+            out->blob.insert(out->blob.end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
+            PyBuffer_Release(&v);
+        }
+        out->off[(size_t)i + 1] = out->blob.size();
+    }
+    Py_DECREF(seq);
+    out->blob.push_back(0);
+    return true;
+}
+
 // Batched search shared by both classes: `items` are str (utf8 = true) or
 // buffers.  Returns list[list[tuple]].  devices: None = the object's own device; a sequence of
 // ordinals = the batch is cut into that many contiguous ranges of haystacks, one host thread per
@@ -252,40 +292,16 @@ PyObject *find_batch_impl(acx_automaton_t *a, PyObject *haystacks, int overlappi
                           PyObject *devices, Replicas **replicas) {
     std::vector<acx_automaton_t *> handles;
     if (!batch_handles(a, devices, replicas, &handles)) return nullptr;
-    PyObject *seq = PySequence_Fast(haystacks, "haystacks must be a sequence");
-    if (!seq) return nullptr;
-    Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
-    std::vector<uint64_t> off((size_t)n + 1, 0);
-    std::vector<uint8_t> blob;
-    bool all_ascii = true;
-    for (Py_ssize_t i = 0; i < n; i++) {
-        PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
-        if (utf8) {
-            if (!PyUnicode_Check(it)) {
-                PyErr_Format(PyExc_TypeError, "'%.100s' object cannot be converted to 'PyString'",
-                             Py_TYPE(it)->tp_name);
-                Py_DECREF(seq); return nullptr;
-            }
-            Py_ssize_t len; const char *s = PyUnicode_AsUTF8AndSize(it, &len);
-            if (!s) { Py_DECREF(seq); return nullptr; }
-            all_ascii = all_ascii && PyUnicode_IS_ASCII(it);
-            blob.insert(blob.end(), s, s + len);
-        } else {
-            Py_buffer v;
-            if (!get_bytes_view(it, &v)) { Py_DECREF(seq); return nullptr; }
-            blob.insert(blob.end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
-            PyBuffer_Release(&v);
-        }
-        off[(size_t)i + 1] = blob.size();
-    }
+    Packed in;
+    if (!pack_sequence(haystacks, utf8, false, &in)) return nullptr;
+    const Py_ssize_t n = in.n;
     std::vector<uint64_t> counts((size_t)n, 0);
     acx_match_t *m = nullptr; uint64_t total = 0;
     int rc;
     Py_BEGIN_ALLOW_THREADS
-    rc = acx_find_batch_multi(handles.data(), (int)handles.size(), blob.data(), off.data(), (uint64_t)n, overlapping,
-                              (utf8 && !all_ascii) ? 1 : 0, &m, &total, counts.data());
+    rc = acx_find_batch_multi(handles.data(), (int)handles.size(), in.blob.data(), in.off.data(), (uint64_t)n, overlapping,
+                              (utf8 && !in.all_ascii) ? 1 : 0, &m, &total, counts.data());
     Py_END_ALLOW_THREADS
-    Py_DECREF(seq);
     if (rc != ACX_OK) return raise_acx(rc);
     PyObject *outer = PyList_New(n);
     uint64_t pos = 0;
@@ -476,32 +492,14 @@ int replace_nogil(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const ui
 
 // replace_all_batch of both classes: list[str] / list[bytes], [replace_all(h, replace_with) for h in haystacks]
 PyObject *replace_batch_impl(acx_automaton_t *a, PyObject *haystacks, PyObject *replace_with, bool utf8) {
-    PyObject *seq = PySequence_Fast(haystacks, "haystacks must be a sequence");
-    if (!seq) return nullptr;
-    const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
-    std::vector<uint64_t> hoff((size_t)n + 1, 0);
-    std::vector<uint8_t> hblob;
-    for (Py_ssize_t i = 0; i < n; i++) {
-        PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
-        if (utf8) {
-            const char *s; Py_ssize_t len;
-            if (!str_view(it, &s, &len)) { Py_DECREF(seq); return nullptr; }
-            hblob.insert(hblob.end(), s, s + len);
-        } else {
-            Py_buffer v;
-            if (!get_bytes_view(it, &v)) { Py_DECREF(seq); return nullptr; }
-            hblob.insert(hblob.end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
-            PyBuffer_Release(&v);
-        }
-        hoff[(size_t)i + 1] = hblob.size();
-    }
-    Py_DECREF(seq);
+    Packed in;
+    if (!pack_sequence(haystacks, utf8, true, &in)) return nullptr;
+    const Py_ssize_t n = in.n;
     std::vector<uint8_t> blob;
     std::vector<uint64_t> off;
     if (!replacements(replace_with, utf8, &blob, &off)) return nullptr;
-    hblob.push_back(0);
     acx_replaced_t *r = nullptr;
-    const int rc = replace_nogil(a, hblob.data(), hoff[(size_t)n], hoff.data(), (uint64_t)n, blob, off, &r);
+    const int rc = replace_nogil(a, in.blob.data(), in.off[(size_t)n], in.off.data(), (uint64_t)n, blob, off, &r);
     if (rc != ACX_OK) return raise_acx(rc);
     std::vector<uint64_t> bounds((size_t)n + 1, 0);
     PyObject *whole = replaced_result(r, false, &bounds);
@@ -933,31 +931,11 @@ PyObject *summary_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, int
     int rc;
     Py_ssize_t n = 1;
     if (batch) {
-        PyObject *seq = PySequence_Fast(hay, "haystacks must be a sequence");
-        if (!seq) return nullptr;
-        n = PySequence_Fast_GET_SIZE(seq);
-        std::vector<uint64_t> off((size_t)n + 1, 0);
-        std::vector<uint8_t> blob;
-        bool all_ascii = true;
-        for (Py_ssize_t i = 0; i < n; i++) {
-            PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
-            if (utf8) {
-                const char *p; Py_ssize_t len;
-                if (!str_view(it, &p, &len)) { Py_DECREF(seq); return nullptr; }
-                all_ascii = all_ascii && PyUnicode_IS_ASCII(it);
-                blob.insert(blob.end(), p, p + len);
-            } else {
-                Py_buffer v;
-                if (!get_bytes_view(it, &v)) { Py_DECREF(seq); return nullptr; }
-                blob.insert(blob.end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
-                PyBuffer_Release(&v);
-            }
-            off[(size_t)i + 1] = blob.size();
-        }
-        Py_DECREF(seq);
-        blob.push_back(0);
-        rc = summarize_nogil(a, blob.data(), off[(size_t)n], off.data(), (uint64_t)n, false, overlapping,
-                             utf8 && !all_ascii && kind == SUM_FIND_FIRST, kind, true, &s);
+        Packed in;
+        if (!pack_sequence(hay, utf8, true, &in)) return nullptr;
+        n = in.n;
+        rc = summarize_nogil(a, in.blob.data(), in.off[(size_t)n], in.off.data(), (uint64_t)n, false, overlapping,
+                             utf8 && !in.all_ascii && kind == SUM_FIND_FIRST, kind, true, &s);
     } else if (utf8) {
         const char *p; Py_ssize_t len;
         if (!str_view(hay, &p, &len)) return nullptr;
@@ -993,28 +971,86 @@ template <int K, bool BATCH> PyObject *bac_summary(PyObject *self_, PyObject *ar
 // ---------------------------------------------------------------------------
 PyTypeObject *MatchColumnsType = nullptr;
 PyTypeObject *ColumnType = nullptr;
+PyTypeObject *PatternCountsType = nullptr;
+PyTypeObject *FilteredRowsType = nullptr;
 
-struct MatchColumnsObject {
-    PyObject_HEAD
-    acx_columns_t *c;
-    bool batch;
-    int device; // the automaton's ordinal (where device columns lie)
+// What a Column's owner -- a MatchColumns, a PatternCounts or a FilteredRows (`which`: ACX_COL_*, ACX_TALLY_*, ACX_FILT_*)
+// -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
+struct OwnerOps {
+    int (*on_device)(const void *h);
+    const void *(*data)(const void *h, int which); // (waits for the device work)
+    void (*free)(void *h);
 };
+struct OwnerObject {
+    PyObject_HEAD
+    const OwnerOps *ops;
+    void *h;
+    int device; // the automaton's ordinal (where device parts lie)
+};
+struct MatchColumnsObject : OwnerObject {
+    bool batch;
+};
+struct PatternCountsObject : OwnerObject {
+    uint64_t n_patterns; // the matrix has this many columns
+};
+struct FilteredRowsObject : OwnerObject {
+    uint64_t n_src;  // the rows of the batch that was filtered
+    bool utf8;       // made by the str class: tolist() decodes
+};
+const OwnerOps MC_OPS = {[](const void *h) { return acx_columns_on_device(static_cast<const acx_columns_t *>(h)); },
+                         [](const void *h, int w) -> const void * { return acx_columns_data(static_cast<const acx_columns_t *>(h), w); },
+                         [](void *h) { acx_free_columns(static_cast<acx_columns_t *>(h)); }};
+const OwnerOps PC_OPS = {[](const void *h) { return acx_tally_on_device(static_cast<const acx_tally_t *>(h)); },
+                         [](const void *h, int w) -> const void * { return acx_tally_data(static_cast<const acx_tally_t *>(h), w); },
+                         [](void *h) { acx_free_tally(static_cast<acx_tally_t *>(h)); }};
+const OwnerOps FR_OPS = {[](const void *h) { return acx_filtered_on_device(static_cast<const acx_filtered_t *>(h)); },
+                         [](const void *h, int w) { return acx_filtered_data(static_cast<const acx_filtered_t *>(h), w); },
+                         [](void *h) { acx_free_filtered(static_cast<acx_filtered_t *>(h)); }};
+OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
+acx_columns_t *mc_handle(PyObject *s) { return static_cast<acx_columns_t *>(owner_of(s)->h); }
+acx_tally_t *pc_handle(PyObject *s) { return static_cast<acx_tally_t *>(owner_of(s)->h); }
+acx_filtered_t *fr_handle(PyObject *s) { return static_cast<acx_filtered_t *>(owner_of(s)->h); }
+
+// a new owner of `type` around the result h; frees h when the object cannot be made
+OwnerObject *new_owner(PyTypeObject *type, const OwnerOps *ops, void *h, int device) {
+    OwnerObject *o = reinterpret_cast<OwnerObject *>(type->tp_alloc(type, 0));
+    if (!o) { ops->free(h); return nullptr; }
+    o->ops = ops;
+    o->h = h;
+    o->device = device;
+    return o;
+}
+
+void owner_dealloc(PyObject *self) {
+    OwnerObject *o = owner_of(self);
+    if (o->h) o->ops->free(o->h); // (waits for the device work if nobody has: microseconds to a millisecond)
+    PyTypeObject *tp = Py_TYPE(self);
+    tp->tp_free(self);
+    Py_DECREF(tp);
+}
+
+PyObject *owner_get_device(PyObject *s, void *) {
+    if (!owner_of(s)->ops->on_device(owner_of(s)->h)) Py_RETURN_NONE;
+    return PyLong_FromLong(owner_of(s)->device);
+}
 
 struct ColumnObject {
     PyObject_HEAD
-    PyObject *owner; // the MatchColumns
-    int which;       // ACX_COL_*
+    PyObject *owner;
+    int which;
     int64_t len;
     int elem;        // 0: int64 words; 1: uint8 bytes (a FilteredRows' data)
 };
 
-void mc_dealloc(PyObject *self) {
-    MatchColumnsObject *o = reinterpret_cast<MatchColumnsObject *>(self);
-    if (o->c) acx_free_columns(o->c); // (waits for the split kernel if nobody has: microseconds to a millisecond)
-    PyTypeObject *tp = Py_TYPE(self);
-    tp->tp_free(self);
-    Py_DECREF(tp);
+PyObject *new_column(PyObject *owner, int which, uint64_t len, int elem = 0) {
+    ColumnObject *col = reinterpret_cast<ColumnObject *>(ColumnType->tp_alloc(ColumnType, 0));
+    if (!col) return nullptr;
+    Py_INCREF(owner);
+    col->owner = owner;
+    col->which = which;
+    col->len = (int64_t)len;
+    col->elem = elem;
+    return reinterpret_cast<PyObject *>(col);
 }
 
 void col_dealloc(PyObject *self) {
@@ -1024,86 +1060,44 @@ void col_dealloc(PyObject *self) {
     Py_DECREF(tp);
 }
 
-// A Column's owner is a MatchColumns (which: ACX_COL_*) or a PatternCounts (which: ACX_TALLY_*; defined further down).
-PyTypeObject *PatternCountsType = nullptr;
-struct PatternCountsObject {
-    PyObject_HEAD
-    acx_tally_t *t;
-    int device;          // the automaton's ordinal (where device parts lie)
-    uint64_t n_patterns; // the matrix has this many columns
-};
-// ... or a FilteredRows (which: ACX_FILT_*; defined behind the PatternCounts)
-PyTypeObject *FilteredRowsType = nullptr;
-struct FilteredRowsObject {
-    PyObject_HEAD
-    acx_filtered_t *f;
-    int device;      // the automaton's ordinal (where device parts lie)
-    uint64_t n_src;  // the rows of the batch that was filtered
-    bool utf8;       // made by the str class: tolist() decodes
-};
-bool col_of_counts(ColumnObject *o) { return Py_TYPE(o->owner) == PatternCountsType; }
-bool col_of_filtered(ColumnObject *o) { return Py_TYPE(o->owner) == FilteredRowsType; }
-acx_filtered_t *col_filtered(ColumnObject *o) { return reinterpret_cast<FilteredRowsObject *>(o->owner)->f; }
-acx_columns_t *col_handle(ColumnObject *o) { return reinterpret_cast<MatchColumnsObject *>(o->owner)->c; }
-acx_tally_t *col_tally(ColumnObject *o) { return reinterpret_cast<PatternCountsObject *>(o->owner)->t; }
-int col_device(ColumnObject *o) {
-    if (col_of_filtered(o)) return reinterpret_cast<FilteredRowsObject *>(o->owner)->device;
-    return col_of_counts(o) ? reinterpret_cast<PatternCountsObject *>(o->owner)->device
-                            : reinterpret_cast<MatchColumnsObject *>(o->owner)->device;
-}
-bool col_on_device(ColumnObject *o) {
-    if (col_of_filtered(o)) return acx_filtered_on_device(col_filtered(o)) != 0;
-    return col_of_counts(o) ? acx_tally_on_device(col_tally(o)) != 0 : acx_columns_on_device(col_handle(o)) != 0;
-}
+int col_device(ColumnObject *o) { return owner_of(o->owner)->device; }
+bool col_on_device(ColumnObject *o) { return owner_of(o->owner)->ops->on_device(owner_of(o->owner)->h) != 0; }
 
 // the part's address once the device work is done (GIL released around the wait); sets the exception
 const void *col_data(ColumnObject *o) {
     const void *p;
     Py_BEGIN_ALLOW_THREADS
-    p = col_of_filtered(o) ? acx_filtered_data(col_filtered(o), o->which)
-        : col_of_counts(o) ? (const void *)acx_tally_data(col_tally(o), o->which)
-                           : (const void *)acx_columns_data(col_handle(o), o->which);
+    p = owner_of(o->owner)->ops->data(owner_of(o->owner)->h, o->which);
     Py_END_ALLOW_THREADS
     if (!p) PyErr_SetString(PyExc_RuntimeError, "the column's device work failed");
     return p;
 }
 
-PyObject *mc_column(PyObject *self_, int which) {
-    MatchColumnsObject *self = reinterpret_cast<MatchColumnsObject *>(self_);
-    if (which == ACX_COL_ROW_OFFSETS && !self->batch) Py_RETURN_NONE;
-    ColumnObject *col = reinterpret_cast<ColumnObject *>(ColumnType->tp_alloc(ColumnType, 0));
-    if (!col) return nullptr;
-    Py_INCREF(self_);
-    col->owner = self_;
-    col->which = which;
-    col->len = (int64_t)(which == ACX_COL_ROW_OFFSETS ? acx_columns_rows(self->c) + 1 : acx_columns_count(self->c));
-    return reinterpret_cast<PyObject *>(col);
+PyObject *mc_column(PyObject *self, int which) {
+    if (which == ACX_COL_ROW_OFFSETS && !static_cast<MatchColumnsObject *>(owner_of(self))->batch) Py_RETURN_NONE;
+    return new_column(self, which, which == ACX_COL_ROW_OFFSETS ? acx_columns_rows(mc_handle(self)) + 1 : acx_columns_count(mc_handle(self)));
 }
 PyObject *mc_get_pattern(PyObject *s, void *) { return mc_column(s, ACX_COL_PATTERN); }
 PyObject *mc_get_start(PyObject *s, void *) { return mc_column(s, ACX_COL_START); }
 PyObject *mc_get_end(PyObject *s, void *) { return mc_column(s, ACX_COL_END); }
 PyObject *mc_get_row_offsets(PyObject *s, void *) { return mc_column(s, ACX_COL_ROW_OFFSETS); }
-PyObject *mc_get_device(PyObject *s, void *) {
-    acx_columns_t *c = reinterpret_cast<MatchColumnsObject *>(s)->c;
-    if (!acx_columns_on_device(c)) Py_RETURN_NONE;
-    return PyLong_FromLong(reinterpret_cast<MatchColumnsObject *>(s)->device);
-}
-Py_ssize_t mc_len(PyObject *s) { return (Py_ssize_t)acx_columns_count(reinterpret_cast<MatchColumnsObject *>(s)->c); }
+Py_ssize_t mc_len(PyObject *s) { return (Py_ssize_t)acx_columns_count(mc_handle(s)); }
 
 // exactly what find_matches_as_indexes / _batch returns for the same arguments
 PyObject *mc_tolist(PyObject *self_, PyObject *) {
-    MatchColumnsObject *self = reinterpret_cast<MatchColumnsObject *>(self_);
-    const uint64_t n = acx_columns_count(self->c), rows = acx_columns_rows(self->c);
+    acx_columns_t *c = mc_handle(self_);
+    const bool batch = static_cast<MatchColumnsObject *>(owner_of(self_))->batch;
+    const uint64_t n = acx_columns_count(c), rows = acx_columns_rows(c);
     std::vector<int64_t> col[3], ro;
     int rc = ACX_OK;
     Py_BEGIN_ALLOW_THREADS
     for (int k = 0; k < 3 && rc == ACX_OK; k++) {
         col[k].resize((size_t)n);
-        rc = acx_columns_copy(self->c, k, col[k].data());
+        rc = acx_columns_copy(c, k, col[k].data());
     }
-    if (rc == ACX_OK && self->batch) {
+    if (rc == ACX_OK && batch) {
         ro.resize((size_t)rows + 1);
-        rc = acx_columns_copy(self->c, ACX_COL_ROW_OFFSETS, ro.data());
+        rc = acx_columns_copy(c, ACX_COL_ROW_OFFSETS, ro.data());
     }
     Py_END_ALLOW_THREADS
     if (rc != ACX_OK) return raise_acx(rc);
@@ -1117,7 +1111,7 @@ PyObject *mc_tolist(PyObject *self_, PyObject *) {
         }
         return list;
     };
-    if (!self->batch) return rows_list(0, n);
+    if (!batch) return rows_list(0, n);
     PyObject *outer = PyList_New((Py_ssize_t)rows);
     for (uint64_t h = 0; outer && h < rows; h++) {
         PyObject *inner = rows_list((uint64_t)ro[h], (uint64_t)ro[h + 1]);
@@ -1134,7 +1128,7 @@ PyGetSetDef mc_getset[] = {
     {"row_offsets", mc_get_row_offsets, nullptr,
      "None for one haystack; for a batch a Column of len(haystacks) + 1 entries: rows row_offsets[h] .. row_offsets[h + 1] "
      "are haystack h's matches", nullptr},
-    {"device", mc_get_device, nullptr, "None: the columns are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {"device", owner_get_device, nullptr, "None: the columns are in host memory; otherwise the HIP ordinal they lie on", nullptr},
     {nullptr, nullptr, nullptr, nullptr, nullptr},
 };
 PyMethodDef mc_methods[] = {
@@ -1144,7 +1138,7 @@ PyMethodDef mc_methods[] = {
     {nullptr, nullptr, 0, nullptr},
 };
 PyType_Slot mc_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(mc_dealloc)},
+    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
     {Py_tp_methods, mc_methods},
     {Py_tp_getset, mc_getset},
     {Py_sq_length, reinterpret_cast<void *>(mc_len)},
@@ -1266,11 +1260,8 @@ PyType_Slot col_slots[] = {
 };
 
 PyObject *columns_object(acx_columns_t *c, bool batch, int device) {
-    MatchColumnsObject *o = reinterpret_cast<MatchColumnsObject *>(MatchColumnsType->tp_alloc(MatchColumnsType, 0));
-    if (!o) { acx_free_columns(c); return nullptr; }
-    o->c = c;
-    o->batch = batch;
-    o->device = device;
+    OwnerObject *o = new_owner(MatchColumnsType, &MC_OPS, c, device);
+    if (o) static_cast<MatchColumnsObject *>(o)->batch = batch;
     return reinterpret_cast<PyObject *>(o);
 }
 
@@ -1292,34 +1283,9 @@ PyObject *columns_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, boo
         Py_END_ALLOW_THREADS
     };
     if (batch) {
-        PyObject *seq = PySequence_Fast(hay, "haystacks must be a sequence");
-        if (!seq) return nullptr;
-        const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
-        std::vector<uint64_t> off((size_t)n + 1, 0);
-        std::vector<uint8_t> blob;
-        bool all_ascii = true;
-        for (Py_ssize_t i = 0; i < n; i++) {
-            PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
-            if (utf8) {
-                if (!PyUnicode_Check(it)) {
-                    PyErr_Format(PyExc_TypeError, "'%.100s' object cannot be converted to 'PyString'", Py_TYPE(it)->tp_name);
-                    Py_DECREF(seq); return nullptr;
-                }
-                Py_ssize_t len; const char *s = PyUnicode_AsUTF8AndSize(it, &len);
-                if (!s) { Py_DECREF(seq); return nullptr; }
-                all_ascii = all_ascii && PyUnicode_IS_ASCII(it);
-                blob.insert(blob.end(), s, s + len);
-            } else {
-                Py_buffer v;
-                if (!get_bytes_view(it, &v)) { Py_DECREF(seq); return nullptr; }
-                blob.insert(blob.end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
-                PyBuffer_Release(&v);
-            }
-            off[(size_t)i + 1] = blob.size();
-        }
-        Py_DECREF(seq);
-        blob.push_back(0);
-        host(blob.data(), off[(size_t)n], off.data(), (uint64_t)n, (utf8 && !all_ascii) ? 1 : 0);
+        Packed in;
+        if (!pack_sequence(hay, utf8, false, &in)) return nullptr;
+        host(in.blob.data(), in.off[(size_t)in.n], in.off.data(), (uint64_t)in.n, (utf8 && !in.all_ascii) ? 1 : 0);
     } else if (utf8) {
         const char *p; Py_ssize_t len;
         if (!str_view(hay, &p, &len)) return nullptr;
@@ -1358,48 +1324,28 @@ template <bool BATCH> PyObject *bac_columns(PyObject *self_, PyObject *args, PyO
 // per-haystack pattern counts: count_by_pattern_sparse_batch -> PatternCounts (acx_tally / acx_tally_device).  A
 // PatternCounts owns the acx_tally_t; its three parts are Columns with the lifetime chain of a MatchColumns' columns.
 // ---------------------------------------------------------------------------
-void pc_dealloc(PyObject *self) {
-    PatternCountsObject *o = reinterpret_cast<PatternCountsObject *>(self);
-    if (o->t) acx_free_tally(o->t); // (waits for the device stage's last kernel if nobody has)
-    PyTypeObject *tp = Py_TYPE(self);
-    tp->tp_free(self);
-    Py_DECREF(tp);
-}
-
-PyObject *pc_column(PyObject *self_, int which) {
-    PatternCountsObject *self = reinterpret_cast<PatternCountsObject *>(self_);
-    ColumnObject *col = reinterpret_cast<ColumnObject *>(ColumnType->tp_alloc(ColumnType, 0));
-    if (!col) return nullptr;
-    Py_INCREF(self_);
-    col->owner = self_;
-    col->which = which;
-    col->len = (int64_t)(which == ACX_TALLY_ROW_OFFSETS ? acx_tally_rows(self->t) + 1 : acx_tally_nnz(self->t));
-    return reinterpret_cast<PyObject *>(col);
+PyObject *pc_column(PyObject *self, int which) {
+    return new_column(self, which, which == ACX_TALLY_ROW_OFFSETS ? acx_tally_rows(pc_handle(self)) + 1 : acx_tally_nnz(pc_handle(self)));
 }
 PyObject *pc_get_row_offsets(PyObject *s, void *) { return pc_column(s, ACX_TALLY_ROW_OFFSETS); }
 PyObject *pc_get_pattern(PyObject *s, void *) { return pc_column(s, ACX_TALLY_PATTERN); }
 PyObject *pc_get_count(PyObject *s, void *) { return pc_column(s, ACX_TALLY_COUNT); }
 PyObject *pc_get_shape(PyObject *s, void *) {
-    PatternCountsObject *o = reinterpret_cast<PatternCountsObject *>(s);
-    return Py_BuildValue("(KK)", (unsigned long long)acx_tally_rows(o->t), (unsigned long long)o->n_patterns);
+    return Py_BuildValue("(KK)", (unsigned long long)acx_tally_rows(pc_handle(s)),
+                         (unsigned long long)static_cast<PatternCountsObject *>(owner_of(s))->n_patterns);
 }
-PyObject *pc_get_device(PyObject *s, void *) {
-    PatternCountsObject *o = reinterpret_cast<PatternCountsObject *>(s);
-    if (!acx_tally_on_device(o->t)) Py_RETURN_NONE;
-    return PyLong_FromLong(o->device);
-}
-Py_ssize_t pc_len(PyObject *s) { return (Py_ssize_t)acx_tally_nnz(reinterpret_cast<PatternCountsObject *>(s)->t); }
+Py_ssize_t pc_len(PyObject *s) { return (Py_ssize_t)acx_tally_nnz(pc_handle(s)); }
 
 // one list per haystack of (pattern, count), patterns ascending
 PyObject *pc_tolist(PyObject *self_, PyObject *) {
-    PatternCountsObject *self = reinterpret_cast<PatternCountsObject *>(self_);
-    const uint64_t nnz = acx_tally_nnz(self->t), rows = acx_tally_rows(self->t);
+    acx_tally_t *t = pc_handle(self_);
+    const uint64_t nnz = acx_tally_nnz(t), rows = acx_tally_rows(t);
     std::vector<int64_t> ro((size_t)rows + 1), pat((size_t)nnz), cnt((size_t)nnz);
     int rc;
     Py_BEGIN_ALLOW_THREADS
-    rc = acx_tally_copy(self->t, ACX_TALLY_ROW_OFFSETS, ro.data());
-    if (rc == ACX_OK) rc = acx_tally_copy(self->t, ACX_TALLY_PATTERN, pat.data());
-    if (rc == ACX_OK) rc = acx_tally_copy(self->t, ACX_TALLY_COUNT, cnt.data());
+    rc = acx_tally_copy(t, ACX_TALLY_ROW_OFFSETS, ro.data());
+    if (rc == ACX_OK) rc = acx_tally_copy(t, ACX_TALLY_PATTERN, pat.data());
+    if (rc == ACX_OK) rc = acx_tally_copy(t, ACX_TALLY_COUNT, cnt.data());
     Py_END_ALLOW_THREADS
     if (rc != ACX_OK) return raise_acx(rc);
     PyObject *outer = PyList_New((Py_ssize_t)rows);
@@ -1424,7 +1370,7 @@ PyGetSetDef pc_getset[] = {
     {"pattern", pc_get_pattern, nullptr, "Column of len(self) pattern indexes, strictly ascending within a row", nullptr},
     {"count", pc_get_count, nullptr, "Column of len(self) counts, all >= 1", nullptr},
     {"shape", pc_get_shape, nullptr, "(haystacks, patterns): the size of the matrix", nullptr},
-    {"device", pc_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {"device", owner_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
     {nullptr, nullptr, nullptr, nullptr, nullptr},
 };
 PyMethodDef pc_methods[] = {
@@ -1433,7 +1379,7 @@ PyMethodDef pc_methods[] = {
     {nullptr, nullptr, 0, nullptr},
 };
 PyType_Slot pc_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(pc_dealloc)},
+    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
     {Py_tp_methods, pc_methods},
     {Py_tp_getset, pc_getset},
     {Py_sq_length, reinterpret_cast<void *>(pc_len)},
@@ -1449,9 +1395,7 @@ PyType_Slot pc_slots[] = {
 // uint8 __dlpack__ tensor that holds the rows back to back, cut by `offsets` (a 1-D int64 __dlpack__ tensor on the same
 // device) or by `row_length`.  Kept in one place so that the other _batch methods can take it.
 struct BatchInput {
-    // a sequence
-    std::vector<uint8_t> blob;
-    std::vector<uint64_t> off;
+    Packed seq; // a sequence
     // a tensor: `len` bytes at `p`, `rows` rows; d_off (its device's offsets) or row_length
     bool tensor = false, on_device = false;
     const uint8_t *p = nullptr;
@@ -1474,31 +1418,8 @@ bool batch_input(PyObject *hay, PyObject *offsets, PyObject *row_length, bool ut
             PyErr_SetString(PyExc_TypeError, "offsets / row_length cut ONE __dlpack__ tensor into rows: a sequence of haystacks takes neither");
             return false;
         }
-        PyObject *seq = PySequence_Fast(hay, "haystacks must be a sequence");
-        if (!seq) return false;
-        const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
-        in->off.assign((size_t)n + 1, 0);
-        for (Py_ssize_t i = 0; i < n; i++) {
-            PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
-            if (utf8) {
-                if (!PyUnicode_Check(it)) {
-                    PyErr_Format(PyExc_TypeError, "'%.100s' object cannot be converted to 'PyString'", Py_TYPE(it)->tp_name);
-                    Py_DECREF(seq); return false;
-                }
-                Py_ssize_t len; const char *s = PyUnicode_AsUTF8AndSize(it, &len);
-                if (!s) { Py_DECREF(seq); return false; }
-                in->blob.insert(in->blob.end(), s, s + len);
-            } else {
-                Py_buffer v;
-                if (!get_bytes_view(it, &v)) { Py_DECREF(seq); return false; }
-                in->blob.insert(in->blob.end(), (const uint8_t *)v.buf, (const uint8_t *)v.buf + v.len);
-                PyBuffer_Release(&v);
-            }
-            in->off[(size_t)i + 1] = in->blob.size();
-        }
-        Py_DECREF(seq);
-        in->rows = (uint64_t)n;
-        in->blob.push_back(0);
+        if (!pack_sequence(hay, utf8, false, &in->seq)) return false;
+        in->rows = (uint64_t)in->seq.n;
         return true;
     }
     if ((offsets != nullptr) == (row_length != nullptr)) {
@@ -1572,6 +1493,41 @@ bool batch_input(PyObject *hay, PyObject *offsets, PyObject *row_length, bool ut
     return true;
 }
 
+// One call on a BatchInput with the GIL released: host(p, len, offsets, rows) on a sequence or a host tensor,
+// device(p, len, d_offsets, rows, row_length) on a tensor in HBM, behind the producer's kernels and the check of where its
+// offsets begin and end (between the two they are the caller's word).  Returns the call's status; BAD_OFFSETS with the
+// ValueError set for offsets that do not span the tensor.
+constexpr int BAD_OFFSETS = -1000;
+template <typename Host, typename Device>
+int batch_dispatch(int device_ordinal, const BatchInput &in, Host &&host, Device &&device) {
+    int rc;
+    bool bad_offsets = false;
+    std::vector<uint64_t> cut;
+    if (in.tensor && !in.on_device && in.row_length) {
+        cut.resize((size_t)in.rows + 1);
+        for (uint64_t i = 0; i <= in.rows; i++) cut[(size_t)i] = i * in.row_length;
+    }
+    Py_BEGIN_ALLOW_THREADS
+    if (!in.tensor) {
+        rc = host(in.seq.blob.data(), in.seq.off[(size_t)in.rows], in.seq.off.data(), in.rows);
+    } else if (!in.on_device) {
+        rc = host(in.p, in.len, in.row_length ? cut.data() : in.t_off, in.rows);
+    } else {
+        rc = acx_device_synchronize_on(device_ordinal); // (the producer's kernels may still write the tensors)
+        if (rc == ACX_OK && in.t_off) {
+            uint64_t ends[2] = {1, 0};
+            rc = acx_device_download(&ends[0], in.t_off, 8);
+            if (rc == ACX_OK) rc = acx_device_download(&ends[1], in.t_off + in.rows, 8);
+            bad_offsets = rc == ACX_OK && (ends[0] != 0 || ends[1] != in.len);
+        }
+        if (rc == ACX_OK && !bad_offsets) rc = device(in.p, in.len, in.t_off, in.rows, in.row_length);
+    }
+    Py_END_ALLOW_THREADS
+    if (!bad_offsets) return rc;
+    PyErr_SetString(PyExc_ValueError, "offsets must rise from 0 to the tensor's length");
+    return BAD_OFFSETS;
+}
+
 // count_by_pattern_sparse_batch of both classes: utf8 = the str class (no offset is reported: the search is on bytes)
 PyObject *sparse_counts_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool utf8) {
     static const char *kw[] = {"haystacks", "overlapping", "offsets", "row_length", nullptr};
@@ -1587,40 +1543,16 @@ PyObject *sparse_counts_impl(acx_automaton_t *a, PyObject *args, PyObject *kwarg
     acx_info_t info;
     if (acx_automaton_info(a, &info) != ACX_OK) return raise_acx(ACX_EINVAL);
     acx_tally_t *t = nullptr;
-    int rc;
-    bool bad_offsets = false;
-    std::vector<uint64_t> cut;
-    if (in.tensor && !in.on_device && in.row_length) {
-        cut.resize((size_t)in.rows + 1);
-        for (uint64_t i = 0; i <= in.rows; i++) cut[(size_t)i] = i * in.row_length;
-    }
-    Py_BEGIN_ALLOW_THREADS
-    if (!in.tensor) {
-        rc = acx_tally(a, in.blob.data(), in.off[(size_t)in.rows], in.off.data(), in.rows, overlapping, &t);
-    } else if (!in.on_device) {
-        rc = acx_tally(a, in.p, in.len, in.row_length ? cut.data() : in.t_off, in.rows, overlapping, &t);
-    } else {
-        rc = acx_device_synchronize_on(device); // (the producer's kernels may still write the tensors)
-        if (rc == ACX_OK && in.t_off) { // where the offsets begin and end; between the two they are the caller's word
-            uint64_t ends[2] = {1, 0};
-            rc = acx_device_download(&ends[0], in.t_off, 8);
-            if (rc == ACX_OK) rc = acx_device_download(&ends[1], in.t_off + in.rows, 8);
-            bad_offsets = rc == ACX_OK && (ends[0] != 0 || ends[1] != in.len);
-        }
-        if (rc == ACX_OK && !bad_offsets)
-            rc = acx_tally_device(a, in.p, in.len, in.t_off, in.rows, in.row_length, overlapping, &t);
-    }
-    Py_END_ALLOW_THREADS
-    if (bad_offsets) {
-        PyErr_SetString(PyExc_ValueError, "offsets must rise from 0 to the tensor's length");
-        return nullptr;
-    }
+    const int rc = batch_dispatch(
+        device, in,
+        [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) { return acx_tally(a, p, len, off, rows, overlapping, &t); },
+        [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_length) {
+            return acx_tally_device(a, p, len, d_off, rows, row_length, overlapping, &t);
+        });
+    if (rc == BAD_OFFSETS) return nullptr;
     if (rc != ACX_OK) return raise_acx(rc);
-    PatternCountsObject *o = reinterpret_cast<PatternCountsObject *>(PatternCountsType->tp_alloc(PatternCountsType, 0));
-    if (!o) { acx_free_tally(t); return nullptr; }
-    o->t = t;
-    o->device = device;
-    o->n_patterns = info.n_patterns;
+    OwnerObject *o = new_owner(PatternCountsType, &PC_OPS, t, device);
+    if (o) static_cast<PatternCountsObject *>(o)->n_patterns = info.n_patterns;
     return reinterpret_cast<PyObject *>(o);
 }
 
@@ -1636,59 +1568,38 @@ PyObject *bac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs) {
 // acx_filtered_t; its three parts are Columns (rows and offsets int64, data uint8) with the lifetime chain of a
 // MatchColumns' columns.
 // ---------------------------------------------------------------------------
-void fr_dealloc(PyObject *self) {
-    FilteredRowsObject *o = reinterpret_cast<FilteredRowsObject *>(self);
-    if (o->f) acx_free_filtered(o->f); // (waits for the device stage's last kernel if nobody has)
-    PyTypeObject *tp = Py_TYPE(self);
-    tp->tp_free(self);
-    Py_DECREF(tp);
-}
-
-PyObject *fr_column(PyObject *self_, int which) {
-    FilteredRowsObject *self = reinterpret_cast<FilteredRowsObject *>(self_);
-    ColumnObject *col = reinterpret_cast<ColumnObject *>(ColumnType->tp_alloc(ColumnType, 0));
-    if (!col) return nullptr;
-    Py_INCREF(self_);
-    col->owner = self_;
-    col->which = which;
-    col->elem = which == ACX_FILT_DATA ? 1 : 0;
-    col->len = (int64_t)(which == ACX_FILT_DATA ? acx_filtered_bytes(self->f)
-                                                 : acx_filtered_rows(self->f) + (which == ACX_FILT_OFFSETS ? 1 : 0));
-    return reinterpret_cast<PyObject *>(col);
+PyObject *fr_column(PyObject *self, int which) {
+    acx_filtered_t *f = fr_handle(self);
+    return new_column(self, which, which == ACX_FILT_DATA ? acx_filtered_bytes(f) : acx_filtered_rows(f) + (which == ACX_FILT_OFFSETS ? 1 : 0),
+                      which == ACX_FILT_DATA ? 1 : 0);
 }
 PyObject *fr_get_rows(PyObject *s, void *) { return fr_column(s, ACX_FILT_ROWS); }
 PyObject *fr_get_offsets(PyObject *s, void *) { return fr_column(s, ACX_FILT_OFFSETS); }
 PyObject *fr_get_data(PyObject *s, void *) { return fr_column(s, ACX_FILT_DATA); }
-PyObject *fr_get_device(PyObject *s, void *) {
-    FilteredRowsObject *o = reinterpret_cast<FilteredRowsObject *>(s);
-    if (!acx_filtered_on_device(o->f)) Py_RETURN_NONE;
-    return PyLong_FromLong(o->device);
-}
-PyObject *fr_get_nbytes(PyObject *s, void *) {
-    return PyLong_FromUnsignedLongLong(acx_filtered_bytes(reinterpret_cast<FilteredRowsObject *>(s)->f));
-}
+PyObject *fr_get_nbytes(PyObject *s, void *) { return PyLong_FromUnsignedLongLong(acx_filtered_bytes(fr_handle(s))); }
 PyObject *fr_get_source_rows(PyObject *s, void *) {
-    return PyLong_FromUnsignedLongLong(reinterpret_cast<FilteredRowsObject *>(s)->n_src);
+    return PyLong_FromUnsignedLongLong(static_cast<FilteredRowsObject *>(owner_of(s))->n_src);
 }
-Py_ssize_t fr_len(PyObject *s) { return (Py_ssize_t)acx_filtered_rows(reinterpret_cast<FilteredRowsObject *>(s)->f); }
+Py_ssize_t fr_len(PyObject *s) { return (Py_ssize_t)acx_filtered_rows(fr_handle(s)); }
 
 // the kept rows: list[str] of the str class (UTF-8 decoded), list[bytes] of the bytes class
 PyObject *fr_tolist(PyObject *self_, PyObject *) {
-    FilteredRowsObject *self = reinterpret_cast<FilteredRowsObject *>(self_);
-    const uint64_t k = acx_filtered_rows(self->f), nb = acx_filtered_bytes(self->f);
+    acx_filtered_t *f = fr_handle(self_);
+    const bool utf8 = static_cast<FilteredRowsObject *>(owner_of(self_))->utf8;
+    const uint64_t k = acx_filtered_rows(f), nb = acx_filtered_bytes(f);
     std::vector<int64_t> off((size_t)k + 1);
     std::vector<uint8_t> data((size_t)nb + 1);
     int rc;
     Py_BEGIN_ALLOW_THREADS
-    rc = acx_filtered_copy(self->f, ACX_FILT_OFFSETS, off.data());
-    if (rc == ACX_OK) rc = acx_filtered_copy(self->f, ACX_FILT_DATA, data.data());
+    rc = acx_filtered_copy(f, ACX_FILT_OFFSETS, off.data());
+    if (rc == ACX_OK) rc = acx_filtered_copy(f, ACX_FILT_DATA, data.data());
     Py_END_ALLOW_THREADS
     if (rc != ACX_OK) return raise_acx(rc);
     PyObject *list = PyList_New((Py_ssize_t)k);
     for (uint64_t i = 0; list && i < k; i++) {
         const char *b = reinterpret_cast<const char *>(data.data()) + off[(size_t)i];
         const Py_ssize_t n = (Py_ssize_t)(off[(size_t)i + 1] - off[(size_t)i]);
-        PyObject *it = self->utf8 ? PyUnicode_DecodeUTF8(b, n, nullptr) : PyBytes_FromStringAndSize(b, n);
+        PyObject *it = utf8 ? PyUnicode_DecodeUTF8(b, n, nullptr) : PyBytes_FromStringAndSize(b, n);
         if (!it) { Py_CLEAR(list); break; }
         PyList_SET_ITEM(list, (Py_ssize_t)i, it);
     }
@@ -1700,7 +1611,7 @@ PyGetSetDef fr_getset[] = {
     {"offsets", fr_get_offsets, nullptr, "Column of len(self) + 1 int64 entries from 0: kept row i is data[offsets[i]:offsets[i + 1]]",
      nullptr},
     {"data", fr_get_data, nullptr, "Column of nbytes uint8 entries: the kept rows' own bytes back to back", nullptr},
-    {"device", fr_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {"device", owner_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
     {"nbytes", fr_get_nbytes, nullptr, "the size of data", nullptr},
     {"source_rows", fr_get_source_rows, nullptr, "the rows of the batch that was filtered", nullptr},
     {nullptr, nullptr, nullptr, nullptr, nullptr},
@@ -1711,7 +1622,7 @@ PyMethodDef fr_methods[] = {
     {nullptr, nullptr, 0, nullptr},
 };
 PyType_Slot fr_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(fr_dealloc)},
+    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
     {Py_tp_methods, fr_methods},
     {Py_tp_getset, fr_getset},
     {Py_sq_length, reinterpret_cast<void *>(fr_len)},
@@ -1763,41 +1674,21 @@ PyObject *filter_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool
     BatchInput in;
     if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
     acx_filtered_t *f = nullptr;
-    int rc;
-    bool bad_offsets = false;
-    std::vector<uint64_t> cut;
-    if (in.tensor && !in.on_device && in.row_length) {
-        cut.resize((size_t)in.rows + 1);
-        for (uint64_t i = 0; i <= in.rows; i++) cut[(size_t)i] = i * in.row_length;
-    }
-    Py_BEGIN_ALLOW_THREADS
-    if (!in.tensor) {
-        rc = acx_filter(a, in.blob.data(), in.off[(size_t)in.rows], in.off.data(), in.rows, overlapping, min_matches, flags, &f);
-    } else if (!in.on_device) {
-        rc = acx_filter(a, in.p, in.len, in.row_length ? cut.data() : in.t_off, in.rows, overlapping, min_matches, flags, &f);
-    } else {
-        rc = acx_device_synchronize_on(device); // (the producer's kernels may still write the tensors)
-        if (rc == ACX_OK && in.t_off) { // where the offsets begin and end; between the two they are the caller's word
-            uint64_t ends[2] = {1, 0};
-            rc = acx_device_download(&ends[0], in.t_off, 8);
-            if (rc == ACX_OK) rc = acx_device_download(&ends[1], in.t_off + in.rows, 8);
-            bad_offsets = rc == ACX_OK && (ends[0] != 0 || ends[1] != in.len);
-        }
-        if (rc == ACX_OK && !bad_offsets)
-            rc = acx_filter_device(a, in.p, in.len, in.t_off, in.rows, in.row_length, overlapping, min_matches, flags, &f);
-    }
-    Py_END_ALLOW_THREADS
-    if (bad_offsets) {
-        PyErr_SetString(PyExc_ValueError, "offsets must rise from 0 to the tensor's length");
-        return nullptr;
-    }
+    const int rc = batch_dispatch(
+        device, in,
+        [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+            return acx_filter(a, p, len, off, rows, overlapping, min_matches, flags, &f);
+        },
+        [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_length) {
+            return acx_filter_device(a, p, len, d_off, rows, row_length, overlapping, min_matches, flags, &f);
+        });
+    if (rc == BAD_OFFSETS) return nullptr;
     if (rc != ACX_OK) return raise_acx(rc);
-    FilteredRowsObject *o = reinterpret_cast<FilteredRowsObject *>(FilteredRowsType->tp_alloc(FilteredRowsType, 0));
-    if (!o) { acx_free_filtered(f); return nullptr; }
-    o->f = f;
-    o->device = device;
-    o->n_src = in.rows;
-    o->utf8 = utf8;
+    OwnerObject *o = new_owner(FilteredRowsType, &FR_OPS, f, device);
+    if (o) {
+        static_cast<FilteredRowsObject *>(o)->n_src = in.rows;
+        static_cast<FilteredRowsObject *>(o)->utf8 = utf8;
+    }
     return reinterpret_cast<PyObject *>(o);
 }
 

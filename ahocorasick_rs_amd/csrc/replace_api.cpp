@@ -1,22 +1,19 @@
 // replace_api.cpp -- replace_all (replace.hpp): the host splice, the device route behind the find pipeline, the acx_replace*
 // entry points and the accessors of their result.
-#include "find_pipeline.hpp"
 #include "replace.hpp"
+#include "result_block.hpp"
 
 using namespace acxh;
 
-// acx_replace / acx_replace_device: the spliced output.  Device route: d_out in HBM (round_up(len, 16) bytes), written by
-// kernels that may still run when the call returns (done); the find result and the scratch they read are kept until
-// acx_free_replaced.  Host route: h_out.
-struct ACX_HIDDEN acx_replaced {
-    int device = 0;
+// acx_replace / acx_replace_device: the spliced output.  Device route: the owner's block in HBM (round_up(len, 16) bytes),
+// written by kernels that may still run when the call returns (done); the find result and the scratch they read are kept
+// until acx_free_replaced.  Host route: h_out.
+struct ACX_HIDDEN acx_replaced : ResultBlock {
     uint64_t len = 0;
     std::vector<uint64_t> offsets; // n_hay + 1: every haystack's output bounds
-    uint8_t *d_out = nullptr;
     std::vector<uint8_t> h_out;
-    hipEvent_t done = nullptr;
     acx_result *find = nullptr;
-    std::vector<void *> scratch;
+    const uint8_t *bytes() const { return on_device ? (const uint8_t *)d_block : h_out.data(); }
 };
 
 namespace {
@@ -35,6 +32,7 @@ int run_replace(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d
     acx_replaced *R = new (std::nothrow) acx_replaced();
     if (!R) { acx_free_result(r); return fail(ACX_ENOMEM, "out of memory"); }
     R->device = a->device;
+    R->on_device = 1;
     R->find = r;
     hipStream_t st = x->stream;
     const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
@@ -71,24 +69,19 @@ int run_replace(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d
         HIPCHK(hipMemcpyAsync(R->offsets.data(), out_off, (n_hay + 1) * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st)); // (the output's length sizes its buffer; roff is read by then)
         R->len = R->offsets[n_hay];
-        HIPCHK(g_bufs.get((void **)&R->d_out, std::max<uint64_t>((R->len + 15) / 16 * 16, 16), a->device));
+        int rc = R->alloc(std::max<uint64_t>((R->len + 15) / 16 * 16, 16));
+        if (rc != ACX_OK) return rc;
+        uint8_t *d_out = (uint8_t *)R->d_block;
         if (!n) { // nothing matched: the output is the input
-            if (len) HIPCHK(hipMemcpyAsync(R->d_out, d_orig, len, hipMemcpyDeviceToDevice, st));
+            if (len) HIPCHK(hipMemcpyAsync(d_out, d_orig, len, hipMemcpyDeviceToDevice, st));
         } else {
             HIPCHK(get((void **)&tiles, replace_tile_words(R->len) * 8));
-            HIPCHK(replace_gather(d_orig, len, r->d_matches, n, o, P, d_blob, blob_len + 32, d_roff, tiles, R->d_out, R->len, st));
+            HIPCHK(replace_gather(d_orig, len, r->d_matches, n, o, P, d_blob, blob_len + 32, d_roff, tiles, d_out, R->len, st));
         }
-        R->done = g_events.get(a->device);
-        if (!R->done) HIPCHK(hipStreamSynchronize(st));
-        else HIPCHK(hipEventRecord(R->done, st));
         return ACX_OK;
     };
-    rc = body();
-    if (rc != ACX_OK) {
-        (void)hipStreamSynchronize(st);
-        acx_free_replaced(R);
-        return rc;
-    }
+    rc = retire_find(body(), st, nullptr, R); // (the find result stays whole: the gather reads it)
+    if (rc != ACX_OK) { acx_free_replaced(R); return rc; }
     a->path[12]++;
     *out = R;
     return ACX_OK;
@@ -152,19 +145,10 @@ int acx_replace(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint
     *out = nullptr;
     int rc = check_repl(a, repl_offsets, n_repl);
     if (rc != ACX_OK) return rc;
-    uint64_t base = 0;
-    if (offsets) {
-        for (uint64_t i = 0; i < n_hay; i++)
-            if (offsets[i + 1] < offsets[i]) return fail(ACX_EINVAL, "offsets not monotone");
-        base = offsets[0];
-        len = offsets[n_hay] - base;
-    } else {
-        n_hay = 1;
-    }
-    if (len && !hay) return fail(ACX_EINVAL, "null haystack");
-    const uint8_t *h = len ? hay + base : nullptr;
-    std::vector<uint64_t> rel(n_hay + 1);
-    for (uint64_t i = 0; i <= n_hay; i++) rel[i] = offsets ? offsets[i] - base : (i ? len : 0);
+    HostBatch B;
+    if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
+    const uint8_t *h = B.hay;
+    const std::vector<uint64_t> &rel = B.rel;
     if (len <= replace_host_max()) {
         // host route: the find entry points as they are (K0, the resident K0, the in-place read), then the splice here
         acx_match_t *m = nullptr;
@@ -245,31 +229,14 @@ int acx_replaced_offsets(const acx_replaced_t *r, uint64_t *host_offsets) {
 
 int acx_replaced_copy(const acx_replaced_t *r, void *host_dst) {
     if (!r || (!host_dst && r->len)) return fail(ACX_EINVAL, "null argument");
-    if (!r->len) return ACX_OK;
-    if (!r->d_out) { std::memcpy(host_dst, r->h_out.data(), r->len); return ACX_OK; }
-    DeviceScope ds(r->device);
-    if (r->done) HIPCHK(hipEventSynchronize(r->done));
-    HIPCHK(hipMemcpy(host_dst, r->d_out, r->len, hipMemcpyDeviceToHost));
-    return ACX_OK;
+    return r->copy_out(host_dst, r->bytes(), r->len);
 }
 
-const void *acx_replaced_device_bytes(const acx_replaced_t *r) {
-    if (!r || !r->d_out) return nullptr;
-    if (r->done) {
-        DeviceScope ds(r->device);
-        if (hipEventSynchronize(r->done) != hipSuccess) return nullptr;
-    }
-    return r->d_out;
-}
+const void *acx_replaced_device_bytes(const acx_replaced_t *r) { return r && r->on_device ? r->ptr_after_wait(r->d_block) : nullptr; }
 
 void acx_free_replaced(acx_replaced_t *r) {
     if (!r) return;
-    DeviceScope ds(r->device);
-    // (the gather reads the find result and the scratch: nothing goes back to the pool before it is done)
-    if (r->done) (void)hipEventSynchronize(r->done);
-    for (void *p : r->scratch) g_bufs.put(p, r->device);
-    g_bufs.put(r->d_out, r->device);
-    g_events.put(r->device, r->done);
+    r->release(); // (the gather reads the find result as well: it goes after the wait)
     acx_free_result(r->find);
     delete r;
 }

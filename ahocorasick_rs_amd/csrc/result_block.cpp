@@ -1,0 +1,151 @@
+// result_block.cpp -- the owner of a post-find result's memory and the end of a post-find stage (result_block.hpp).
+#include "result_block.hpp"
+
+namespace acxh ACX_HIDDEN {
+
+// The layout rule against the formulas the three block results were written with, at the sizes where (x + 31) / 32 * 32
+// and max(x, 1) change.
+namespace {
+constexpr uint64_t r32(uint64_t words) { return (words + 31) / 32 * 32; }
+constexpr uint64_t least1(uint64_t x) { return x > 1 ? x : 1; }
+constexpr bool same(const Layout &L, uint64_t a0, uint64_t a1, uint64_t a2, uint64_t a3, uint64_t bytes) {
+    return L.at[0] == a0 && L.at[1] == a1 && L.at[2] == a2 && L.at[3] == a3 && L.bytes == bytes;
+}
+// columns: three columns of n words and, for a batch, rows + 1 row offsets
+constexpr bool columns_ok(uint64_t n, uint64_t rows) {
+    const uint64_t c = r32(least1(n)) * 8;
+    return same(block_layout({n * 8, n * 8, n * 8}), 0, c, 2 * c, 0, 3 * c) &&
+           same(block_layout({n * 8, n * 8, n * 8, (rows + 1) * 8}), 0, c, 2 * c, 3 * c, 3 * c + r32(rows + 1) * 8);
+}
+// tally: rows + 1 row offsets, then patterns and counts of nnz words
+constexpr bool tally_ok(uint64_t rows, uint64_t nnz) {
+    const uint64_t r = r32(rows + 1) * 8, c = r32(least1(nnz)) * 8;
+    return same(block_layout({(rows + 1) * 8, nnz * 8, nnz * 8}), 0, r, r + c, 0, r + 2 * c);
+}
+// filter: k rows, k + 1 offsets, then the data, rounded up to 16 bytes for the tile's stores
+constexpr bool filter_ok(uint64_t k, uint64_t total) {
+    const uint64_t r = (least1(k) * 8 + 255) / 256 * 256, o = ((k + 1) * 8 + 255) / 256 * 256;
+    const uint64_t data = (total + 15) / 16 * 16 > 16 ? (total + 15) / 16 * 16 : 16;
+    return same(block_layout({k * 8, (k + 1) * 8, data}, 16), 0, r, r + o, 0, r + o + data);
+}
+constexpr bool all_ok() {
+    for (const uint64_t x : {0, 1, 32, 33})
+        for (const uint64_t y : {0, 1, 32, 33})
+            if (!columns_ok(x, y) || !tally_ok(x, y) || !filter_ok(x, y)) return false;
+    return true;
+}
+static_assert(all_ok(), "block_layout no longer places the parts where the results' blocks had them");
+static_assert(filter_ok(33, 15) && filter_ok(33, 16) && filter_ok(33, 17) && filter_ok(0, 257), "the filter's data part");
+} // namespace
+
+int ResultBlock::alloc(uint64_t bytes) {
+    if (on_device) {
+        HIPCHK(g_bufs.get(&d_block, bytes, device));
+        return ACX_OK;
+    }
+    h_block = new (std::nothrow) uint8_t[bytes];
+    return h_block ? ACX_OK : fail(ACX_ENOMEM, "out of memory");
+}
+
+int ResultBlock::wait() const {
+    if (!on_device || !done) return ACX_OK;
+    DeviceScope ds(device);
+    HIPCHK(hipEventSynchronize(done));
+    return ACX_OK;
+}
+
+int ResultBlock::copy_out(void *dst, const void *src, uint64_t bytes) const {
+    if (!bytes) return ACX_OK;
+    if (!on_device) { std::memcpy(dst, src, bytes); return ACX_OK; }
+    int rc = wait();
+    if (rc != ACX_OK) return rc;
+    DeviceScope ds(device);
+    HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return ACX_OK;
+}
+
+void ResultBlock::release() {
+    if (on_device) {
+        DeviceScope ds(device);
+        if (done) (void)hipEventSynchronize(done);
+        for (void *p : scratch) g_bufs.put(p, device);
+        g_bufs.put(d_block, device);
+        g_events.put(device, done);
+    }
+    delete[] h_block;
+    scratch.clear();
+    d_block = nullptr;
+    done = nullptr;
+    h_block = nullptr;
+}
+
+int retire_find(int rc, hipStream_t st, acx_result *r, ResultBlock *R, void *t1, void *t2) {
+    const int dev = R->device;
+    const bool temps = t1 || t2;
+    if (rc == ACX_OK) {
+        hipEvent_t freed = r ? g_events.get(dev) : nullptr, freed2 = temps ? g_events.get(dev) : nullptr;
+        R->done = g_events.get(dev);
+        hipError_t e = hipSuccess;
+        const bool have = R->done && (freed || !r) && (freed2 || !temps);
+        if (have) {
+            if (freed) e = hipEventRecord(freed, st);
+            if (e == hipSuccess && freed2) e = hipEventRecord(freed2, st);
+            if (e == hipSuccess) e = hipEventRecord(R->done, st);
+        }
+        if (!have || e != hipSuccess) { // a dry pool: the wait takes the events' place; a failed record: the failure path
+            g_events.put(dev, freed);
+            g_events.put(dev, freed2);
+            g_events.put(dev, R->done);
+            freed = freed2 = R->done = nullptr;
+            if (e != hipSuccess) rc = hipfail(e, "hipEventRecord");
+            else if ((e = hipStreamSynchronize(st)) != hipSuccess) rc = hipfail(e, "hipStreamSynchronize(st)");
+        }
+        if (rc == ACX_OK) {
+            if (r) {
+                g_events.put(dev, r->done);
+                r->done = nullptr;
+                g_bufs.put(r->borrowed ? nullptr : r->d_matches, dev, freed, r->d_counts);
+                r->d_matches = nullptr;
+                r->d_counts = nullptr;
+            }
+            g_bufs.put(t1, dev, freed2, t2);
+            acx_free_result(r); // (emptied)
+            return ACX_OK;
+        }
+    }
+    (void)hipStreamSynchronize(st);
+    g_bufs.put(t1, dev);
+    g_bufs.put(t2, dev);
+    acx_free_result(r);
+    return rc;
+}
+
+int counts_of(const acx_result *r, hipStream_t st, uint64_t **one, const uint64_t **d_counts) {
+    *d_counts = r->d_counts;
+    if (r->d_counts) return ACX_OK;
+    HIPCHK(g_bufs.get((void **)one, 16, r->device));
+    HIPCHK(hipMemcpyAsync(*one, &r->n, 8, hipMemcpyHostToDevice, st));
+    *d_counts = *one;
+    return ACX_OK;
+}
+
+int host_batch(const uint8_t *hay, uint64_t *len, const uint64_t *offsets, uint64_t *n_hay, HostBatch *B) {
+    uint64_t base = 0;
+    if (offsets) {
+        for (uint64_t i = 0; i < *n_hay; i++)
+            if (offsets[i + 1] < offsets[i]) return fail(ACX_EINVAL, "offsets not monotone");
+        base = offsets[0];
+        *len = offsets[*n_hay] - base;
+    } else {
+        *n_hay = 1;
+    }
+    if (*len && !hay) return fail(ACX_EINVAL, "null haystack");
+    B->hay = *len ? hay + base : nullptr;
+    try {
+        B->rel.resize(*n_hay + 1);
+    } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
+    for (uint64_t i = 0; i <= *n_hay; i++) B->rel[i] = offsets ? offsets[i] - base : (i ? *len : 0);
+    return ACX_OK;
+}
+
+} // namespace acxh

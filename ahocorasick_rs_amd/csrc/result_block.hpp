@@ -1,0 +1,105 @@
+// result_block.hpp -- what the stages behind the find pipeline (summaries, splice, columns, tally, row filter) share: the
+// owner of a result's memory, the layout of its block, the end of a stage (retire_find) and the frame of its entry points.
+// The stages' middles are their own (summary_api.cpp .. filter_api.cpp); no kernel includes this.
+#pragma once
+#include <initializer_list>
+
+#include "find_pipeline.hpp"
+
+namespace acxh ACX_HIDDEN {
+
+// The owner of a result's memory.  Device route: blocks of the buffer cache (g_bufs, workspace.cpp), written by kernels that
+// may still run when the call returns -- `done` fires behind the last of them; `scratch` is what those kernels still read.
+// Host route: a block of host memory, nothing to wait for.
+struct ResultBlock {
+    int device = 0;
+    int on_device = 0;
+    uint8_t *h_block = nullptr;
+    void *d_block = nullptr;
+    hipEvent_t done = nullptr;
+    std::vector<void *> scratch;
+
+    int alloc(uint64_t bytes); // the block: of the cache (on_device) or of host memory
+    uint8_t *base() const { return on_device ? (uint8_t *)d_block : h_block; }
+    // every accessor's wait for the stage's last kernel
+    int wait() const;
+    // `bytes` at `src` (a part of this result) to host memory, behind the kernels; zero bytes: nothing
+    int copy_out(void *dst, const void *src, uint64_t bytes) const;
+    // p once the kernels are done; null when the wait fails
+    const void *ptr_after_wait(const void *p) const { return p && wait() == ACX_OK ? p : nullptr; }
+    // waits, then gives scratch, block and event back to their pools and frees the host block (the kernels write the block
+    // and read the scratch: nothing goes back to a pool before they are done)
+    void release();
+};
+
+// Where the parts of a block begin, in bytes, and the block's size: every part at least one word long (an empty part still
+// has an address that DLPack consumers accept) and a multiple of 256 bytes behind the previous one.  The last part is
+// rounded up to `tail` bytes.
+struct Layout {
+    uint64_t at[4] = {0, 0, 0, 0}, bytes = 0;
+};
+constexpr Layout block_layout(std::initializer_list<uint64_t> part_bytes, uint64_t tail = 256) {
+    Layout L;
+    int k = 0;
+    for (const uint64_t b : part_bytes) {
+        const uint64_t step = k + 1 < (int)part_bytes.size() ? 256 : tail;
+        L.at[k++] = L.bytes;
+        L.bytes += ((b > 8 ? b : 8) + step - 1) / step * step;
+    }
+    return L;
+}
+
+// Carves one block of the cache into a stage's temporaries, in words: every part 256 bytes behind the previous one.
+struct Carver {
+    uint64_t at = 0;
+    uint64_t part(uint64_t words) {
+        const uint64_t here = at;
+        at += (words + 31) / 32 * 32;
+        return here;
+    }
+    uint64_t bytes() const { return std::max<uint64_t>(at, 32) * 8; }
+};
+
+// The end of a stage behind a find, whatever its outcome `rc`.  st: the stream the find and the stage ran on; r: the find's
+// result (null: an empty batch; a stage that keeps the counts has taken them out of r); R: the stage's result; t1, t2: the
+// stage's temporaries (or null).
+// rc == ACX_OK: events are recorded HERE, behind the stage's last launch, and every buffer is returned WITH such an event:
+// the records and counts of r behind one, the temporaries behind another -- the cache holds them until it has fired -- and
+// R->done is a third.  A dry event pool costs a stream synchronisation instead.
+// Otherwise, and when recording fails: the stream is synchronised first, then the temporaries and r's buffers go back.
+// Either way r is freed, every event taken from g_events is R's, the cache's or back in the pool, and R stays the caller's.
+int retire_find(int rc, hipStream_t st, acx_result *r, ResultBlock *R, void *t1 = nullptr, void *t2 = nullptr);
+
+// The per-haystack counts of a find, on the device: the result's own or, for one haystack that is no batch (the find kept
+// none), its total uploaded to *one -- a temporary for retire_find.
+int counts_of(const acx_result *r, hipStream_t st, uint64_t **one, const uint64_t **d_counts);
+
+// A host entry point's haystacks as the stages take them: offsets (n_hay + 1 of them, monotone; null: ONE haystack of *len
+// bytes, *n_hay becomes 1) cut `hay`; afterwards *len bytes at B->hay (null when there are none) are the haystacks, cut by
+// B->rel: *n_hay + 1 offsets from 0.
+struct HostBatch {
+    const uint8_t *hay = nullptr;
+    std::vector<uint64_t> rel;
+};
+int host_batch(const uint8_t *hay, uint64_t *len, const uint64_t *offsets, uint64_t *n_hay, HostBatch *B);
+
+// The frame of a *_device entry point behind its own argument checks: the haystack's and the segments' checks, the
+// overlapping check (the error, no device state), the lease and the folded copy of a case-insensitive handle; then
+// run(ctx, d_search, segments) under the lease.
+template <typename Run>
+int device_call(acx_automaton *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                uint64_t uniform_len, int overlapping, Run &&run) {
+    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
+    Segments G;
+    int rc = make_segments(d_offsets, n_hay, uniform_len, len, &G);
+    if (rc == ACX_OK && overlapping) rc = check_overlapping(a);
+    if (rc != ACX_OK) return rc;
+    Lease lease(a);
+    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
+    const uint8_t *d_search = nullptr;
+    rc = fold_copy(a, lease.c, (const uint8_t *)d_hay, len, &d_search);
+    if (rc != ACX_OK) return rc;
+    return run(lease.c, d_search, G);
+}
+
+} // namespace acxh

@@ -1,25 +1,21 @@
 // summary_api.cpp -- the summaries of a find (summary.hpp): the host reduction, the device route behind the find pipeline,
 // the acx_summarize* entry points and the accessors of their result.
-#include "find_pipeline.hpp"
 #include "replace.hpp"
+#include "result_block.hpp"
 #include "summary.hpp"
 
 using namespace acxh;
 
-// acx_summarize / acx_summarize_device: what is left of a find.  Device route: the reductions in HBM, written by kernels
-// that may still run when the call returns (done); the find's records have gone back to the buffer cache behind the same
-// kernels, only the summaries and the scan's scratch are kept until acx_free_summary.  Host route: the vectors.
-struct ACX_HIDDEN acx_summary {
-    int device = 0;
-    int on_device = 0;
+// acx_summarize / acx_summarize_device: what is left of a find.  Device route: the reductions in HBM, each in a buffer of its
+// own -- all of them the owner's scratch (result_block.hpp), d_* are views; the find's records have gone back to the buffer
+// cache behind the reductions.  Host route: the vectors.
+struct ACX_HIDDEN acx_summary : ResultBlock {
     uint32_t what = 0;
     uint64_t n_hay = 0, n_patterns = 0, total = 0;
     std::vector<uint64_t> counts, any, hist;
     std::vector<acx_match_t> first;
     uint64_t *d_counts = nullptr, *d_any = nullptr, *d_hist = nullptr;
     acx_match_t *d_first = nullptr;
-    hipEvent_t done = nullptr;
-    std::vector<void *> scratch;
 };
 
 namespace {
@@ -46,9 +42,14 @@ int run_summary(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, co
     R->n_patterns = a->host.n_patterns;
     R->total = r->n;
     const uint64_t n_hay = R->n_hay, n = r->n;
-    auto get = [&](void **p, uint64_t bytes) -> hipError_t { return g_bufs.get(p, std::max<uint64_t>(bytes, 16), a->device); };
+    auto get = [&](void **p, uint64_t bytes) -> hipError_t { // (kept until acx_free_summary)
+        const hipError_t e = g_bufs.get(p, std::max<uint64_t>(bytes, 16), a->device);
+        if (e == hipSuccess) R->scratch.push_back(*p);
+        return e;
+    };
     auto body = [&]() -> int {
         if (segmented) { // the per-haystack counts are the summary's from here on
+            R->scratch.push_back(r->d_counts);
             R->d_counts = r->d_counts;
             r->d_counts = nullptr;
         } else {
@@ -60,9 +61,7 @@ int run_summary(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, co
             if (segmented) { // where every haystack's records begin, from the counts
                 uint64_t *temp = nullptr;
                 HIPCHK(get((void **)&temp, replace_scan_words(n_hay) * 8));
-                R->scratch.push_back(temp);
                 HIPCHK(get((void **)&prefix, (n_hay + 1) * 8));
-                R->scratch.push_back(prefix);
                 HIPCHK(acx::replace_scan(nullptr, nullptr, R->d_counts, n_hay, prefix, temp, st));
             }
             HIPCHK(get((void **)&R->d_first, n_hay * sizeof(acx_match_t)));
@@ -73,28 +72,9 @@ int run_summary(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, co
             HIPCHK(get((void **)&R->d_hist, R->n_patterns * 8));
             HIPCHK(acx::summary_hist(r->d_matches, n, R->n_patterns, R->d_hist, st));
         }
-        // The find's records are not needed beyond this point of the stream: they go back to the buffer cache, which holds
-        // them until an event recorded HERE has fired (the result's own event lies in front of the reductions).
-        hipEvent_t freed = g_events.get(a->device);
-        R->done = g_events.get(a->device);
-        if (!freed || !R->done) {
-            HIPCHK(hipStreamSynchronize(st));
-            g_events.put(a->device, freed);
-            g_events.put(a->device, R->done);
-            freed = R->done = nullptr;
-        } else {
-            HIPCHK(hipEventRecord(freed, st));
-            HIPCHK(hipEventRecord(R->done, st));
-        }
-        g_events.put(a->device, r->done);
-        r->done = nullptr;
-        g_bufs.put(r->borrowed ? nullptr : r->d_matches, a->device, freed);
-        r->d_matches = nullptr;
         return ACX_OK;
     };
-    rc = body();
-    if (rc != ACX_OK) (void)hipStreamSynchronize(st);
-    acx_free_result(r); // (emptied above when all went well)
+    rc = retire_find(body(), st, r, R);
     if (rc != ACX_OK) { acx_free_summary(R); return rc; }
     *out = R;
     return ACX_OK;
@@ -106,23 +86,7 @@ uint64_t summary_host_max() {
     return e ? std::strtoull(e, nullptr, 10) : (1ull << 20);
 }
 
-// device words -> the caller's, behind the reductions
-int copy_back(const acx_summary *r, void *dst, const void *d_src, uint64_t bytes) {
-    if (!bytes) return ACX_OK;
-    DeviceScope ds(r->device);
-    if (r->done) HIPCHK(hipEventSynchronize(r->done));
-    HIPCHK(hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost));
-    return ACX_OK;
-}
-
-const void *device_part(const acx_summary *r, const void *p) {
-    if (!r || !r->on_device || !p) return nullptr;
-    if (r->done) {
-        DeviceScope ds(r->device);
-        if (hipEventSynchronize(r->done) != hipSuccess) return nullptr;
-    }
-    return p;
-}
+const void *device_part(const acx_summary *r, const void *p) { return r && r->on_device ? r->ptr_after_wait(p) : nullptr; }
 
 } // namespace
 
@@ -169,29 +133,18 @@ int acx_summarize(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const ui
     if (what & ~SUM_ALL) return fail(ACX_EINVAL, "unknown summary bits");
     int rc = overlapping ? check_overlapping(a) : ACX_OK; // (the error, no device state)
     if (rc != ACX_OK) return rc;
-    uint64_t base = 0;
-    if (offsets) {
-        for (uint64_t i = 0; i < n_hay; i++)
-            if (offsets[i + 1] < offsets[i]) return fail(ACX_EINVAL, "offsets not monotone");
-        base = offsets[0];
-        len = offsets[n_hay] - base;
-    } else {
-        n_hay = 1;
-    }
-    if (len && !hay) return fail(ACX_EINVAL, "null haystack");
-    const uint8_t *h = len ? hay + base : nullptr;
-    std::vector<uint64_t> rel(n_hay + 1);
-    for (uint64_t i = 0; i <= n_hay; i++) rel[i] = offsets ? offsets[i] - base : (i ? len : 0);
+    HostBatch B;
+    if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
     if (len <= summary_host_max()) {
         // host route: the find entry points as they are (K0, the resident K0, the in-place read), then the reduction here
         acx_match_t *m = nullptr;
         uint64_t nm = 0;
         std::vector<uint64_t> counts(n_hay, 0);
         if (!offsets) {
-            rc = acx_find(a, h, len, overlapping, codepoints, &m, &nm);
+            rc = acx_find(a, B.hay, len, overlapping, codepoints, &m, &nm);
             counts[0] = nm;
         } else if (n_hay) {
-            rc = acx_find_batch(a, h, rel.data(), n_hay, overlapping, codepoints, &m, &nm, counts.data());
+            rc = acx_find_batch(a, B.hay, B.rel.data(), n_hay, overlapping, codepoints, &m, &nm, counts.data());
         }
         if (rc != ACX_OK) return rc;
         acx_summary *R = new (std::nothrow) acx_summary();
@@ -219,7 +172,7 @@ int acx_summarize(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const ui
     Lease lease(a);
     Ctx *c = lease.c;
     if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    rc = stage_host(a, c, h, len, offsets ? rel.data() : nullptr, offsets ? n_hay + 1 : 0, false);
+    rc = stage_host(a, c, B.hay, len, offsets ? B.rel.data() : nullptr, offsets ? n_hay + 1 : 0, false);
     if (rc != ACX_OK) return rc;
     const uint8_t *d_search = nullptr;
     if ((rc = fold_copy(a, c, c->ws.hay, len, &d_search)) != ACX_OK) return rc;
@@ -232,17 +185,9 @@ int acx_summarize_device(acx_automaton_t *a, const void *d_hay, uint64_t len, co
     if (!a || !out) return fail(ACX_EINVAL, "null argument");
     *out = nullptr;
     if (what & ~SUM_ALL) return fail(ACX_EINVAL, "unknown summary bits");
-    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
-    Segments G;
-    int rc = make_segments(d_offsets, n_hay, uniform_len, len, &G);
-    if (rc == ACX_OK && overlapping) rc = check_overlapping(a); // (the error, no device state)
-    if (rc != ACX_OK) return rc;
-    Lease lease(a);
-    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    const uint8_t *d_search = nullptr;
-    rc = fold_copy(a, lease.c, (const uint8_t *)d_hay, len, &d_search);
-    if (rc != ACX_OK) return rc;
-    return run_summary(a, lease.c, d_search, len, G, overlapping, codepoints, what, out);
+    return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, overlapping, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_summary(a, c, d_search, len, G, overlapping, codepoints, what, out);
+    });
 }
 
 uint64_t acx_summary_total(const acx_summary_t *r) { return r ? r->total : 0; }
@@ -250,35 +195,27 @@ int acx_summary_on_device(const acx_summary_t *r) { return r ? r->on_device : 0;
 
 int acx_summary_counts(const acx_summary_t *r, uint64_t *host_counts) {
     if (!r || (!host_counts && r->n_hay)) return fail(ACX_EINVAL, "null argument");
-    if (r->on_device) return copy_back(r, host_counts, r->d_counts, r->n_hay * 8);
-    if (r->n_hay) std::memcpy(host_counts, r->counts.data(), r->n_hay * 8);
-    return ACX_OK;
+    return r->copy_out(host_counts, r->on_device ? (const void *)r->d_counts : r->counts.data(), r->n_hay * 8);
 }
 
 int acx_summary_any(const acx_summary_t *r, uint64_t *host_bits) {
     if (!r || (!host_bits && r->n_hay)) return fail(ACX_EINVAL, "null argument");
     if (!(r->what & ACX_SUM_FIRST)) return fail(ACX_EINVAL, "the summary was made without ACX_SUM_FIRST");
     const uint64_t bytes = (r->n_hay + 63) / 64 * 8;
-    if (r->on_device) return copy_back(r, host_bits, r->d_any, bytes);
-    if (bytes) std::memcpy(host_bits, r->any.data(), bytes);
-    return ACX_OK;
+    return r->copy_out(host_bits, r->on_device ? (const void *)r->d_any : r->any.data(), bytes);
 }
 
 int acx_summary_first(const acx_summary_t *r, acx_match_t *host_first) {
     if (!r || (!host_first && r->n_hay)) return fail(ACX_EINVAL, "null argument");
     if (!(r->what & ACX_SUM_FIRST)) return fail(ACX_EINVAL, "the summary was made without ACX_SUM_FIRST");
     const uint64_t bytes = r->n_hay * sizeof(acx_match_t);
-    if (r->on_device) return copy_back(r, host_first, r->d_first, bytes);
-    if (bytes) std::memcpy(host_first, r->first.data(), bytes);
-    return ACX_OK;
+    return r->copy_out(host_first, r->on_device ? (const void *)r->d_first : r->first.data(), bytes);
 }
 
 int acx_summary_by_pattern(const acx_summary_t *r, uint64_t *host_hist) {
     if (!r || (!host_hist && r->n_patterns)) return fail(ACX_EINVAL, "null argument");
     if (!(r->what & ACX_SUM_BY_PATTERN)) return fail(ACX_EINVAL, "the summary was made without ACX_SUM_BY_PATTERN");
-    if (r->on_device) return copy_back(r, host_hist, r->d_hist, r->n_patterns * 8);
-    if (r->n_patterns) std::memcpy(host_hist, r->hist.data(), r->n_patterns * 8);
-    return ACX_OK;
+    return r->copy_out(host_hist, r->on_device ? (const void *)r->d_hist : r->hist.data(), r->n_patterns * 8);
 }
 
 const uint64_t *acx_summary_device_counts(const acx_summary_t *r) { return (const uint64_t *)device_part(r, r ? r->d_counts : nullptr); }
@@ -292,17 +229,7 @@ const uint64_t *acx_summary_device_by_pattern(const acx_summary_t *r) {
 
 void acx_free_summary(acx_summary_t *r) {
     if (!r) return;
-    if (r->on_device) {
-        DeviceScope ds(r->device);
-        // (the reductions write the summaries and read the scratch: nothing goes back to the pool before they are done)
-        if (r->done) (void)hipEventSynchronize(r->done);
-        for (void *p : r->scratch) g_bufs.put(p, r->device);
-        g_bufs.put(r->d_counts, r->device);
-        g_bufs.put(r->d_any, r->device);
-        g_bufs.put(r->d_first, r->device);
-        g_bufs.put(r->d_hist, r->device);
-        g_events.put(r->device, r->done);
-    }
+    r->release();
     delete r;
 }
 

@@ -1,40 +1,28 @@
 // tally_api.cpp -- per-haystack pattern counts as a CSR matrix (tally.hpp): the host reduction, the device stage behind the
 // find pipeline, the acx_tally* entry points and the accessors of their result.
-#include "find_pipeline.hpp"
 #include "replace.hpp"
+#include "result_block.hpp"
 #include "tally.hpp"
 
 using namespace acxh;
 
-// acx_tally / acx_tally_device: row offsets (rows + 1 words), patterns and counts (nnz words each) in ONE block.  Device
-// route: a block of the buffer cache (g_bufs, workspace.cpp), written by kernels that may still run when the call returns
-// (done); the find's records and the stage's temporaries have gone back to the cache behind the same kernels.  Host route:
-// a block of host memory.
-struct ACX_HIDDEN acx_tally {
-    int device = 0;
-    int on_device = 0;
+// acx_tally / acx_tally_device: row offsets (rows + 1 words), patterns and counts (nnz words each) in ONE block
+// (result_block.hpp).  Device route: the find's records and the stage's temporaries have gone back to the cache behind the
+// stage's kernels.
+struct ACX_HIDDEN acx_tally : ResultBlock {
     uint64_t rows = 0, nnz = 0;
     int64_t *part[3] = {nullptr, nullptr, nullptr}; // ACX_TALLY_*
-    int64_t *h_block = nullptr;
-    void *d_block = nullptr;
-    hipEvent_t done = nullptr;
-    std::vector<void *> scratch;
+
+    static Layout layout(uint64_t rows, uint64_t nnz) { return block_layout({(rows + 1) * 8, nnz * 8, nnz * 8}); }
+    int alloc(uint64_t nnz_room) { // the block (by on_device) and the parts' places in it
+        const Layout L = layout(rows, nnz_room);
+        int rc = ResultBlock::alloc(L.bytes);
+        for (int k = 0; rc == ACX_OK && k < 3; k++) part[k] = (int64_t *)(base() + L.at[k]);
+        return rc;
+    }
 };
 
 namespace {
-
-// where the parts of a block begin, in words: every part at least one word long and a multiple of 32 words (256 bytes)
-// behind the previous one (the rules of the columns' block, columns_api.cpp)
-struct Layout {
-    uint64_t at[3], words;
-    Layout(uint64_t rows, uint64_t nnz) {
-        const uint64_t r = (rows + 1 + 31) / 32 * 32, c = (std::max<uint64_t>(nnz, 1) + 31) / 32 * 32;
-        at[ACX_TALLY_ROW_OFFSETS] = 0;
-        at[ACX_TALLY_PATTERN] = r;
-        at[ACX_TALLY_COUNT] = r + c;
-        words = r + 2 * c;
-    }
-};
 
 uint64_t part_words(const acx_tally_t *t, int which) { return which == ACX_TALLY_ROW_OFFSETS ? t->rows + 1 : t->nnz; }
 
@@ -74,11 +62,10 @@ int stage_count(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, 
     *nnz = 0;
     const uint32_t row_max = tally_row_max();
     // [rec_off: rows + 1][roff: rows + 1, then the long rows' records: 1][nnz_row: rows][scan][tmp_pattern: n][tmp_count: n]
-    uint64_t at = 0;
-    auto part = [&](uint64_t w) { const uint64_t here = at; at += (w + 31) / 32 * 32; return here; };
-    const uint64_t o_rec = part(rows + 1), o_roff = part(rows + 2), o_nnz = part(rows), o_scan = part(replace_scan_words(rows)),
-                   o_tp = part(n), o_tc = part(n);
-    HIPCHK(g_bufs.get(&S->block, std::max<uint64_t>(at, 32) * 8, device));
+    Carver C;
+    const uint64_t o_rec = C.part(rows + 1), o_roff = C.part(rows + 2), o_nnz = C.part(rows),
+                   o_scan = C.part(replace_scan_words(rows)), o_tp = C.part(n), o_tc = C.part(n);
+    HIPCHK(g_bufs.get(&S->block, C.bytes(), device));
     uint64_t *b = (uint64_t *)S->block;
     S->rec_off = (int64_t *)(b + o_rec);
     S->roff = (int64_t *)(b + o_roff);
@@ -145,89 +132,35 @@ int run_tally(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, cons
     R->on_device = 1;
     R->rows = rows;
     Stage S;
-    uint64_t *one_count = nullptr; // (one haystack that is no batch: the find kept no counts)
+    uint64_t *one_count = nullptr;
     auto body = [&]() -> int {
-        uint64_t nnz = 0;
+        int rc;
         if (rows) {
-            const uint64_t *d_counts = r->d_counts;
-            if (!d_counts) {
-                HIPCHK(g_bufs.get((void **)&one_count, 16, a->device));
-                HIPCHK(hipMemcpyAsync(one_count, &r->n, 8, hipMemcpyHostToDevice, st));
-                d_counts = one_count;
-            }
-            int rc = stage_count(a->device, st, r->d_matches, r->n, d_counts, rows, a->host.n_patterns, false, &S, &nnz);
+            const uint64_t *d_counts = nullptr;
+            if ((rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
+            rc = stage_count(a->device, st, r->d_matches, r->n, d_counts, rows, a->host.n_patterns, false, &S, &R->nnz);
             if (rc != ACX_OK) return rc;
         }
-        R->nnz = nnz;
-        const Layout L(rows, nnz);
-        HIPCHK(g_bufs.get(&R->d_block, L.words * 8, a->device));
-        for (int k = 0; k < 3; k++) R->part[k] = (int64_t *)R->d_block + L.at[k];
-        if (rows) {
-            int rc = stage_finish(&S, nnz, R->part[0], R->part[1], R->part[2], st);
-            if (rc != ACX_OK) return rc;
-        } else {
-            HIPCHK(hipMemsetAsync(R->part[0], 0, 8, st));
-        }
-        // The find's records and counts and the stage's temporaries are not needed beyond this point of the stream: they go
-        // back to the buffer cache, which holds them until an event recorded HERE has fired.
-        hipEvent_t freed = g_events.get(a->device), freed2 = g_events.get(a->device);
-        R->done = g_events.get(a->device);
-        if (!freed || !freed2 || !R->done) {
-            HIPCHK(hipStreamSynchronize(st));
-            g_events.put(a->device, freed);
-            g_events.put(a->device, freed2);
-            g_events.put(a->device, R->done);
-            freed = freed2 = R->done = nullptr;
-        } else {
-            HIPCHK(hipEventRecord(freed, st));
-            HIPCHK(hipEventRecord(freed2, st));
-            HIPCHK(hipEventRecord(R->done, st));
-        }
-        if (r) {
-            g_events.put(a->device, r->done);
-            r->done = nullptr;
-            g_bufs.put(r->borrowed ? nullptr : r->d_matches, a->device, freed, r->d_counts);
-            r->d_matches = nullptr;
-            r->d_counts = nullptr;
-        } else {
-            g_events.put(a->device, freed);
-        }
-        g_bufs.put(S.block, a->device, freed2, one_count);
-        S.block = nullptr;
-        one_count = nullptr;
-        if (S.long_block) R->scratch.push_back(S.long_block); // (the rare form: kept until acx_free_tally)
-        S.long_block = nullptr;
+        if ((rc = R->alloc(R->nnz)) != ACX_OK) return rc;
+        if (rows) return stage_finish(&S, R->nnz, R->part[0], R->part[1], R->part[2], st);
+        HIPCHK(hipMemsetAsync(R->part[0], 0, 8, st));
         return ACX_OK;
     };
     int rc = body();
-    if (rc != ACX_OK) {
-        (void)hipStreamSynchronize(st);
-        g_bufs.put(S.block, a->device);
-        g_bufs.put(S.long_block, a->device);
-        g_bufs.put(one_count, a->device);
-    }
-    acx_free_result(r); // (emptied above when all went well)
+    if (S.long_block) R->scratch.push_back(S.long_block); // (the rare form: kept until acx_free_tally)
+    rc = retire_find(rc, st, r, R, S.block, one_count);
     if (rc != ACX_OK) { acx_free_tally(R); return rc; }
     *out = R;
     return ACX_OK;
 }
 
-// every accessor's wait for the stage's last kernel
-int tally_wait(const acx_tally_t *t) {
-    if (!t->on_device || !t->done) return ACX_OK;
-    DeviceScope ds(t->device);
-    HIPCHK(hipEventSynchronize(t->done));
-    return ACX_OK;
-}
-
 acx_tally_t *host_tally(int device, uint64_t rows, uint64_t nnz_room) {
     acx_tally_t *R = new (std::nothrow) acx_tally_t();
-    const Layout L(rows, nnz_room);
-    if (R) R->h_block = new (std::nothrow) int64_t[L.words];
-    if (!R || !R->h_block) { delete R; return nullptr; }
+    if (!R) return nullptr;
     R->device = device;
     R->rows = rows;
-    for (int k = 0; k < 3; k++) { R->part[k] = R->h_block + L.at[k]; R->part[k][0] = 0; }
+    if (R->alloc(nnz_room) != ACX_OK) { delete R; return nullptr; }
+    for (int k = 0; k < 3; k++) R->part[k][0] = 0;
     return R;
 }
 
@@ -274,29 +207,15 @@ int acx_tally(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64
     *out = nullptr;
     int rc = overlapping ? check_overlapping(a) : ACX_OK; // (the error, no device state)
     if (rc != ACX_OK) return rc;
-    uint64_t base = 0;
-    if (offsets) {
-        for (uint64_t i = 0; i < n_hay; i++)
-            if (offsets[i + 1] < offsets[i]) return fail(ACX_EINVAL, "offsets not monotone");
-        base = offsets[0];
-        len = offsets[n_hay] - base;
-    } else {
-        n_hay = 1;
-    }
-    if (len && !hay) return fail(ACX_EINVAL, "null haystack");
-    const uint8_t *h = len ? hay + base : nullptr;
-    std::vector<uint64_t> rel;
-    try {
-        rel.resize(n_hay + 1);
-    } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
-    for (uint64_t i = 0; i <= n_hay; i++) rel[i] = offsets ? offsets[i] - base : (i ? len : 0);
+    HostBatch B;
+    if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
     if (len <= tally_host_max() || !n_hay) {
         // host route: acx_find_batch as it is (the small-call kernel, the in-place read, the staged pipeline), then the
         // reduction here
         acx_match_t *m = nullptr;
         uint64_t nm = 0;
         std::vector<uint64_t> counts(n_hay, 0);
-        if (n_hay) rc = acx_find_batch(a, h, rel.data(), n_hay, overlapping, 0, &m, &nm, counts.data());
+        if (n_hay) rc = acx_find_batch(a, B.hay, B.rel.data(), n_hay, overlapping, 0, &m, &nm, counts.data());
         if (rc != ACX_OK) return rc;
         acx_tally_t *R = host_tally(a->device, n_hay, nm);
         if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
@@ -312,20 +231,20 @@ int acx_tally(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64
         Lease lease(a);
         Ctx *c = lease.c;
         if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-        rc = stage_host(a, c, h, len, rel.data(), n_hay + 1, false);
+        rc = stage_host(a, c, B.hay, len, B.rel.data(), n_hay + 1, false);
         if (rc != ACX_OK) return rc;
         const uint8_t *d_search = nullptr;
         if ((rc = fold_copy(a, c, c->ws.hay, len, &d_search)) != ACX_OK) return rc;
         rc = run_tally(a, c, d_search, len, Segments{c->ws.offsets, n_hay, 0}, overlapping, &D);
         if (rc != ACX_OK) return rc;
-        rc = tally_wait(D); // (the staging buffers are the context's: the lease ends behind the kernels)
+        rc = D->wait(); // (the staging buffers are the context's: the lease ends behind the kernels)
     }
     acx_tally_t *R = rc == ACX_OK ? host_tally(a->device, D->rows, D->nnz) : nullptr;
     if (rc == ACX_OK && !R) rc = fail(ACX_ENOMEM, "out of memory");
     if (rc == ACX_OK) {
         R->nnz = D->nnz;
         DeviceScope ds(a->device);
-        const hipError_t e = hipMemcpy(R->h_block, D->d_block, Layout(D->rows, D->nnz).words * 8, hipMemcpyDeviceToHost);
+        const hipError_t e = hipMemcpy(R->h_block, D->d_block, acx_tally::layout(D->rows, D->nnz).bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = hipfail(e, "copying the tally to the host");
     }
     acx_free_tally(D);
@@ -338,17 +257,9 @@ int acx_tally_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const 
                      uint64_t uniform_len, int overlapping, acx_tally_t **out) {
     if (!a || !out) return fail(ACX_EINVAL, "null argument");
     *out = nullptr;
-    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
-    Segments G;
-    int rc = make_segments(d_offsets, n_hay, uniform_len, len, &G);
-    if (rc == ACX_OK && overlapping) rc = check_overlapping(a); // (the error, no device state)
-    if (rc != ACX_OK) return rc;
-    Lease lease(a);
-    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    const uint8_t *d_search = nullptr;
-    rc = fold_copy(a, lease.c, (const uint8_t *)d_hay, len, &d_search);
-    if (rc != ACX_OK) return rc;
-    return run_tally(a, lease.c, d_search, len, G, overlapping, out);
+    return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, overlapping, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_tally(a, c, d_search, len, G, overlapping, out);
+    });
 }
 
 int acx_tally_rows_device(const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint64_t n_hay, uint64_t n_patterns,
@@ -384,34 +295,19 @@ int acx_tally_on_device(const acx_tally_t *t) { return t ? t->on_device : 0; }
 
 const int64_t *acx_tally_data(const acx_tally_t *t, int which) {
     if (!t || which < 0 || which > ACX_TALLY_COUNT) return nullptr;
-    if (tally_wait(t) != ACX_OK) return nullptr;
-    return t->part[which];
+    return (const int64_t *)t->ptr_after_wait(t->part[which]);
 }
 
 int acx_tally_copy(const acx_tally_t *t, int which, int64_t *host_dst) {
     if (!t || which < 0 || which > ACX_TALLY_COUNT) return fail(ACX_EINVAL, "no such part");
     const uint64_t words = part_words(t, which);
-    if (!words) return ACX_OK;
-    if (!host_dst) return fail(ACX_EINVAL, "null argument");
-    if (!t->on_device) { std::memcpy(host_dst, t->part[which], words * 8); return ACX_OK; }
-    int rc = tally_wait(t);
-    if (rc != ACX_OK) return rc;
-    DeviceScope ds(t->device);
-    HIPCHK(hipMemcpy(host_dst, t->part[which], words * 8, hipMemcpyDeviceToHost));
-    return ACX_OK;
+    if (words && !host_dst) return fail(ACX_EINVAL, "null argument");
+    return t->copy_out(host_dst, t->part[which], words * 8);
 }
 
 void acx_free_tally(acx_tally_t *t) {
     if (!t) return;
-    if (t->on_device) {
-        DeviceScope ds(t->device);
-        // (the kernels write the block and read the scratch: nothing goes back to the pool before they are done)
-        if (t->done) (void)hipEventSynchronize(t->done);
-        for (void *p : t->scratch) g_bufs.put(p, t->device);
-        g_bufs.put(t->d_block, t->device);
-        g_events.put(t->device, t->done);
-    }
-    delete[] t->h_block;
+    t->release();
     delete t;
 }
 

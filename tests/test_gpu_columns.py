@@ -286,6 +286,31 @@ def test_batches_host_and_device(mk, ov):
     a.close()
 
 
+def test_results_freed_unread_and_in_reverse_order():
+    """the seams of the result's owner: a result freed with no accessor ever called (the free waits for the stage) and the
+    identical call after it, whose blocks come from the cache; eight results alive at once, four freed unread in the opposite
+    order to their creation, a result made where their blocks went, and the other four read afterwards"""
+    pats = [b"ab", b"abab", b"bab", b"needle", b"hay", b"stack", b"a", b"zz", b"0123", b"ab"]
+    o, a = Oracle(pats, 0, KIND_DFA), capi.Automaton(pats, 0)
+    batches = [[gen.gen_textlike([0, 7, 64, 255][(i + k) % 4], 50 + 8 * k + i, pats).tobytes() for i in range(5 + 7 * k)] for k in range(8)]
+    per = [[o.find_raw(h, overlapping=True) for h in hays] for hays in batches]
+    want = [(np.concatenate(p), [len(r) for r in p]) for p in per]
+    c, keep = device_batch(a, batches[3], 0, overlapping=True)
+    c.free()
+    c, keep2 = device_batch(a, batches[3], 0, overlapping=True)
+    check_device_columns(c, *want[3])
+    made = [device_batch(a, hays, 0, overlapping=True) for hays in batches]
+    for k in (7, 6, 5, 4):
+        made[k][0].free()
+    c, keep3 = device_batch(a, batches[6], 0, overlapping=True)
+    check_device_columns(c, *want[6])
+    for k in (3, 2, 1, 0):
+        check_device_columns(made[k][0], *want[k])
+    for d in [*keep, *keep2, *keep3] + [d for _, ks in made for d in ks]:
+        d.free()
+    a.close()
+
+
 def test_empty_batches_and_no_match_at_all():
     import ahocorasick_rs as ar
     b, s = ar.BytesAhoCorasick(PATS), ar.AhoCorasick(["ab", "é"])

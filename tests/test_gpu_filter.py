@@ -365,6 +365,31 @@ def test_one_haystack_that_is_no_batch_and_empty_batches():
     a.close()
 
 
+def test_results_freed_unread_and_in_reverse_order():
+    """the seams of the result's owner: a result freed with no accessor ever called (the free waits for the stage) and the
+    identical call after it, whose blocks come from the cache; eight results alive at once, four freed unread in the opposite
+    order to their creation, a result made where their blocks went, and the other four read afterwards"""
+    pats = [b"ab", b"abab", b"bab", b"needle", b"hay", b"stack", b"a", b"zz", b"0123", b"ab"]
+    o, a = Oracle(pats, 0, KIND_DFA), capi.Automaton(pats, 0)
+    batches = [[gen.gen_textlike([0, 7, 64, 255][(i + k) % 4], 50 + 8 * k + i, pats).tobytes() for i in range(5 + 7 * k)] for k in range(8)]
+    want = [definition(hays, oracle_counts(o, hays, True), 2, bool(k % 2)) for k, hays in enumerate(batches)]
+    kw = [dict(overlapping=True, min_matches=2, flags=MATCHED * (k % 2)) for k in range(8)]
+    f, keep = device_filter(a, batches[3], 0, **kw[3])
+    f.free()
+    f, keep2 = device_filter(a, batches[3], 0, **kw[3])
+    check_filtered(f, want[3], True, "the second call")
+    made = [device_filter(a, hays, 0, **kw[k]) for k, hays in enumerate(batches)]
+    for k in (7, 6, 5, 4):
+        made[k][0].free()
+    f, keep3 = device_filter(a, batches[6], 0, **kw[6])
+    check_filtered(f, want[6], True, "behind the four freed")
+    for k in (3, 2, 1, 0):
+        check_filtered(made[k][0], want[k], True, k)
+    for d in [*keep, *keep2, *keep3] + [d for _, ks in made for d in ks]:
+        d.free()
+    a.close()
+
+
 def test_case_insensitive_handle_keeps_the_callers_case():
     pats = [b"Needle", b"hay", b"STACK"]
     o = Oracle([p.translate(FOLD) for p in pats], 1, KIND_DFA)

@@ -303,6 +303,34 @@ def test_long_rows_form_end_to_end(monkeypatch):
     a.close()
 
 
+def test_results_freed_unread_and_in_reverse_order():
+    """the seams of the result's owner: a result freed with no accessor ever called (the free waits for the stage) and the
+    identical call after it, whose blocks come from the cache; eight results alive at once, four freed unread in the opposite
+    order to their creation, a result made where their blocks went, and the other four read afterwards"""
+    pats = [b"ab", b"abab", b"bab", b"needle", b"hay", b"stack", b"a", b"zz", b"0123", b"ab"]
+    o, a = Oracle(pats, 0, KIND_DFA), capi.Automaton(pats, 0)
+    batches = [[gen.gen_textlike([0, 7, 64, 255][(i + k) % 4], 50 + 8 * k + i, pats).tobytes() for i in range(5 + 7 * k)] for k in range(8)]
+    want = [oracle_rows(o, hays, True) for hays in batches]
+    t, keep = device_tally(a, batches[3], 0, overlapping=True)
+    t.free()
+    t, keep2 = device_tally(a, batches[3], 0, overlapping=True)
+    check_tally(t, want[3], True, "the second call")
+    made = [device_tally(a, hays, 0, overlapping=True) for hays in batches]
+    for k in (7, 6, 5, 4):
+        made[k][0].free()
+    t, keep3 = device_tally(a, batches[6], 0, overlapping=True)
+    check_tally(t, want[6], True, "behind the four freed")
+    for k in (3, 2, 1, 0):
+        check_tally(made[k][0], want[k], True, k)
+    # one haystack that is no batch: the find kept no counts
+    hay = b"".join(batches[7])
+    dev = capi.DeviceBuffer(len(hay) + 16).upload(np.frombuffer(hay + b"\0", dtype=np.uint8))
+    check_tally(a.tally_device(dev.ptr, len(hay), overlapping=True), oracle_rows(o, [hay], True), True, "no batch")
+    for d in [dev, *keep, *keep2, *keep3] + [d for _, ks in made for d in ks]:
+        d.free()
+    a.close()
+
+
 def test_case_insensitive_handle():
     pats = [b"Needle", b"hay", b"STACK"]
     o = Oracle([p.translate(FOLD) for p in pats], 1, KIND_DFA)
