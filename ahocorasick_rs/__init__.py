@@ -20,6 +20,7 @@ from .ahocorasick_rs import (
     Column,
     PatternCounts,
     FilteredRows,
+    RowScores,
 )
 
 __acx_amd__ = True
@@ -40,6 +41,8 @@ __all__ = [
     # Extension: the result of count_by_pattern_sparse_batch
     "PatternCounts",
     "FilteredRows",
+    # Extension: the result of score_batch
+    "RowScores",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

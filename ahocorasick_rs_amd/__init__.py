@@ -25,6 +25,7 @@ try:
         Column,
         PatternCounts,
         FilteredRows,
+    RowScores,
     )
 except ImportError as e:  # pragma: no cover - build problem, fail loudly
     raise ImportError(
@@ -48,6 +49,8 @@ __all__ = [
     # Extension: the result of count_by_pattern_sparse_batch
     "PatternCounts",
     "FilteredRows",
+    # Extension: the result of score_batch
+    "RowScores",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

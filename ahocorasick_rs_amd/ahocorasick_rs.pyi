@@ -73,6 +73,15 @@ class FilteredRows:
     def __len__(self) -> int: ...  # the number of kept rows
     def tolist(self) -> Any: ...  # the kept rows: list[str] of AhoCorasick, list[bytes] of BytesAhoCorasick
 
+# extension: the result of score_batch -- one int64 score per row of the batch, where the search ran
+class RowScores:
+    @property
+    def score(self) -> Column: ...  # len(self) int64 entries
+    @property
+    def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
+    def __len__(self) -> int: ...  # the rows of the batch
+    def tolist(self) -> list[int]: ...
+
 class AhoCorasick:
     def __init__(
         self,
@@ -119,6 +128,18 @@ class AhoCorasick:
         self, haystacks: Any, overlapping: bool = False, *, keep: str = "unmatched", min_matches: int = 1,
         offsets: Any = None, row_length: Optional[int] = None
     ) -> FilteredRows: ...
+    # extension: per-pattern weights (one int per pattern, |w| < 2^31: a sequence of ints or an int64 / int32 buffer).  A row's
+    # score is the sum of weights[pattern] over the matches find_matches_as_indexes_batch reports for it (int64, wraps modulo
+    # 2^64); filter_by_score_batch is filter_batch with a row matched when its score is at least min_score (any int64).
+    # haystacks as for count_by_pattern_sparse_batch
+    def score_batch(
+        self, haystacks: Any, weights: Any, overlapping: bool = False, *, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> RowScores: ...
+    def filter_by_score_batch(
+        self, haystacks: Any, weights: Any, overlapping: bool = False, *, keep: str = "unmatched", min_score: int = 1,
+        offsets: Any = None, row_length: Optional[int] = None
+    ) -> FilteredRows: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -161,6 +182,18 @@ class BytesAhoCorasick:
     # count_by_pattern_sparse_batch: a sequence, or ONE uint8 __dlpack__ tensor cut by exactly one of offsets and row_length
     def filter_batch(
         self, haystacks: Any, overlapping: bool = False, *, keep: str = "unmatched", min_matches: int = 1,
+        offsets: Any = None, row_length: Optional[int] = None
+    ) -> FilteredRows: ...
+    # extension: per-pattern weights (one int per pattern, |w| < 2^31: a sequence of ints or an int64 / int32 buffer).  A row's
+    # score is the sum of weights[pattern] over the matches find_matches_as_indexes_batch reports for it (int64, wraps modulo
+    # 2^64); filter_by_score_batch is filter_batch with a row matched when its score is at least min_score (any int64).
+    # haystacks as for count_by_pattern_sparse_batch
+    def score_batch(
+        self, haystacks: Any, weights: Any, overlapping: bool = False, *, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> RowScores: ...
+    def filter_by_score_batch(
+        self, haystacks: Any, weights: Any, overlapping: bool = False, *, keep: str = "unmatched", min_score: int = 1,
         offsets: Any = None, row_length: Optional[int] = None
     ) -> FilteredRows: ...
     def _info(self) -> dict[str, Any]: ...

@@ -232,6 +232,21 @@ def lib() -> ctypes.CDLL:
     L.acx_filter_host.argtypes = [vp, u64, vp, u64, vp, u64, u32, vp, vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.acx_filter_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, u64, u32, vp, vp, vp, ctypes.POINTER(u64),
                                          ctypes.POINTER(u64)]
+    i64 = ctypes.c_int64
+    L.acx_score.argtypes = [vp, vp, u64, vp, u64, i32, vp, u64, ctypes.POINTER(vp)]
+    L.acx_score_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, vp, u64, ctypes.POINTER(vp)]
+    L.acx_scores_rows.argtypes = [vp]
+    L.acx_scores_rows.restype = u64
+    L.acx_scores_on_device.argtypes = [vp]
+    L.acx_scores_data.argtypes = [vp]
+    L.acx_scores_data.restype = vp
+    L.acx_scores_copy.argtypes = [vp, vp]
+    L.acx_free_scores.argtypes = [vp]
+    L.acx_free_scores.restype = None
+    L.acx_score_host.argtypes = [vp, u64, vp, u64, vp, u64, vp]
+    L.acx_score_rows_device.argtypes = [vp, u64, vp, u64, vp, u64, vp]
+    L.acx_filter_scored.argtypes = [vp, vp, u64, vp, u64, i32, vp, u64, i64, u32, ctypes.POINTER(vp)]
+    L.acx_filter_scored_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, vp, u64, i64, u32, ctypes.POINTER(vp)]
     _lib = L
     return L
 
@@ -825,6 +840,72 @@ def filter_rows_device(d_hay: int, nbytes: int, d_offsets: int, n_hay: int, unif
     return int(k.value), int(nb.value)
 
 
+class DeviceScores:
+    """The result of Automaton.score / score_device (acx_scores_t): one int64 score per row of the batch, in HBM (on_device)
+    or in host memory.  scores() copies them out; data_ptr() is where they lie (both wait for the device stage)."""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    @property
+    def on_device(self) -> bool:
+        return bool(lib().acx_scores_on_device(self._h))
+
+    @property
+    def rows(self) -> int:
+        return int(lib().acx_scores_rows(self._h))
+
+    def data_ptr(self) -> int:
+        return lib().acx_scores_data(self._h) or 0
+
+    def scores(self) -> np.ndarray:
+        out = np.zeros(self.rows, dtype=np.int64)
+        _check(lib().acx_scores_copy(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def free(self) -> None:
+        if self._h:
+            lib().acx_free_scores(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _weights(weights) -> np.ndarray:
+    """one int32 per pattern, contiguous; ValueError for a weight outside |w| < 2^31"""
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.int64).reshape(-1))
+    if len(w) and int(np.abs(w).max()) >= 1 << 31:
+        raise ValueError("a weight is outside int32: |w| < 2^31 is needed")
+    return np.ascontiguousarray(w.astype(np.int32))
+
+
+def score_host(matches, counts: Optional[Sequence[int]], weights) -> np.ndarray:
+    """acx_score_host: rows of (pattern, start, end), counts[h] of them haystack h's (None: one row holds them all) -> the
+    int64 score of every row, on the host, no device involved.  ValueError (code EINVAL) when the counts do not sum to the
+    rows."""
+    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    w = _weights(weights)
+    n_hay = 1 if c is None else len(c)
+    out = np.zeros(n_hay, dtype=np.int64)
+    pad = np.zeros(1, dtype=np.uint64)  # (an empty batch is still a batch: a non-null counts pointer)
+    _check(lib().acx_score_host(m.ctypes.data if len(m) else None, len(m),
+                                None if c is None else (c.ctypes.data if len(c) else pad.ctypes.data), n_hay,
+                                w.ctypes.data if len(w) else None, len(w), out.ctypes.data if n_hay else None))
+    return out
+
+
+def score_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, d_weights: int, n_weights: int, d_scores: int) -> None:
+    """acx_score_rows_device: the device stage alone -- n records of 24 bytes at d_records, n_hay counts at d_counts, n_weights
+    int32 weights at d_weights -> n_hay int64 scores at d_scores; complete when it returns"""
+    _check(lib().acx_score_rows_device(d_records or None, n, d_counts or None, n_hay, d_weights or None, n_weights,
+                                       d_scores or None))
+
+
 def _replaced_bytes(h: int) -> bytes:
     buf = bytearray(int(lib().acx_replaced_len(h)))
     if buf:
@@ -1081,6 +1162,57 @@ class Automaton:
         out = ctypes.c_void_p()
         _check(lib().acx_filter_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
                                        min_matches, flags, ctypes.byref(out)))
+        return DeviceFiltered(out.value)
+
+    # ---- per-pattern weights: a score per row, and the row filter by score (acx_score* / acx_filter_scored*)
+    def score(self, haystacks: Optional[Sequence[bytes]], weights, overlapping: bool = False, *,
+              single: Optional[bytes] = None) -> DeviceScores:
+        """every row's sum of weights[pattern] over its matches: host haystacks, a host result; single=...: one haystack
+        that is no batch (offsets = NULL)"""
+        w = _weights(weights)
+        out = ctypes.c_void_p()
+        if single is not None:
+            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
+            _check(lib().acx_score(self._h, hb.ctypes.data, len(single), None, 1, int(overlapping), w.ctypes.data, len(w),
+                                   ctypes.byref(out)))
+            return DeviceScores(out.value)
+        hb, hoff = pack(haystacks)
+        _check(lib().acx_score(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
+                               w.ctypes.data, len(w), ctypes.byref(out)))
+        return DeviceScores(out.value)
+
+    def score_device(self, d_ptr: int, nbytes: int, weights, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
+                     overlapping: bool = False) -> DeviceScores:
+        """the batch in HBM searched and scored there; the scores stay there"""
+        w = _weights(weights)
+        out = ctypes.c_void_p()
+        _check(lib().acx_score_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
+                                      w.ctypes.data, len(w), ctypes.byref(out)))
+        return DeviceScores(out.value)
+
+    def filter_scored(self, haystacks: Optional[Sequence[bytes]], weights, overlapping: bool = False, min_score: int = 1,
+                      flags: int = 0, *, single: Optional[bytes] = None) -> DeviceFiltered:
+        """filter() with a row matched when its score is at least min_score"""
+        w = _weights(weights)
+        out = ctypes.c_void_p()
+        if single is not None:
+            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
+            _check(lib().acx_filter_scored(self._h, hb.ctypes.data, len(single), None, 1, int(overlapping), w.ctypes.data,
+                                           len(w), min_score, flags, ctypes.byref(out)))
+            return DeviceFiltered(out.value)
+        hb, hoff = pack(haystacks)
+        _check(lib().acx_filter_scored(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks),
+                                       int(overlapping), w.ctypes.data, len(w), min_score, flags, ctypes.byref(out)))
+        return DeviceFiltered(out.value)
+
+    def filter_scored_device(self, d_ptr: int, nbytes: int, weights, *, d_offsets: int = 0, n_hay: int = 0,
+                             uniform_len: int = 0, overlapping: bool = False, min_score: int = 1,
+                             flags: int = 0) -> DeviceFiltered:
+        """filter_device() with a row matched when its score is at least min_score"""
+        w = _weights(weights)
+        out = ctypes.c_void_p()
+        _check(lib().acx_filter_scored_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
+                                              w.ctypes.data, len(w), min_score, flags, ctypes.byref(out)))
         return DeviceFiltered(out.value)
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,

@@ -3,6 +3,7 @@
 #include "filter.hpp"
 #include "replace.hpp"
 #include "result_block.hpp"
+#include "score.hpp"
 
 using namespace acxh;
 
@@ -84,6 +85,20 @@ int stage_finish(const Stage *S, const uint8_t *d_hay, uint64_t k, uint64_t tota
     return ACX_OK;
 }
 
+// acx_filter_scored*: the verdict on a row is its score (score.hpp) against min_score, not its number of matches
+struct ScoreBy {
+    const int32_t *weights; // host memory, n_weights of them
+    uint64_t n_weights;
+    int64_t min_score;
+};
+
+int check_scored(const acx_automaton *a, const ScoreBy &sc, uint32_t flags) {
+    if (flags & ~(uint32_t)ACX_FILTER_KEEP_MATCHED) return fail(ACX_EINVAL, "unknown filter flags");
+    if (sc.n_weights != a->host.n_patterns) return fail(ACX_EINVAL, "one weight per pattern is needed");
+    if (sc.n_weights && !sc.weights) return fail(ACX_EINVAL, "null argument");
+    return ACX_OK;
+}
+
 int check_args(uint64_t min_matches, uint32_t flags) {
     if (flags & ~(uint32_t)ACX_FILTER_KEEP_MATCHED) return fail(ACX_EINVAL, "unknown filter flags");
     if (!min_matches) return fail(ACX_EINVAL, "min_matches must be at least 1");
@@ -93,9 +108,10 @@ int check_args(uint64_t min_matches, uint32_t flags) {
 // The device route: the find pipeline as acx_find_device runs it (batch splits and the expansion of copies included, byte
 // offsets: no offset is reported) on d_search, then the stage on the same stream over d_hay -- the caller's own bytes.
 // Returns when the result's size is known; the gather may still run (out->done).  d_hay, d_search and G.offsets must stay
-// valid until then.
+// valid until then.  by != null: the rows' scores and their 0 / 1 verdicts are made between the find and the stage, on the
+// same stream, and the stage runs on the verdicts as its counts with min_matches = 1.
 int run_filter(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_search, uint64_t len, const Segments &G,
-               int overlapping, uint64_t min_matches, uint32_t flags, acx_filtered_t **out) {
+               int overlapping, uint64_t min_matches, uint32_t flags, acx_filtered_t **out, const ScoreBy *by = nullptr) {
     *out = nullptr;
     const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
     const uint64_t n = segmented ? G.n_hay : 1;
@@ -111,12 +127,20 @@ int run_filter(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_
     R->on_device = 1;
     R->n_src = n;
     Stage S;
+    ScoreTemps T;
     uint64_t *one_count = nullptr;
     auto body = [&]() -> int {
         int rc;
         if (n) {
             const uint64_t *d_counts = nullptr;
             if ((rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
+            if (by) { // (stage_sizes waits for the stream: the caller's weights are uploaded when it returns)
+                rc = score_stage(a->device, st, r->d_matches, r->n, d_counts, n, by->weights, nullptr, by->n_weights, false, nullptr,
+                                 &by->min_score, &T);
+                if (rc != ACX_OK) return rc;
+                d_counts = T.flags;
+                min_matches = 1;
+            }
             const acx::FilterRows rows{G.offsets, G.uniform_len, n, len};
             rc = stage_sizes(a->device, st, rows, d_counts, min_matches, (flags & ACX_FILTER_KEEP_MATCHED) != 0, &S, &R->rows, &R->bytes);
             if (rc != ACX_OK) return rc;
@@ -124,7 +148,30 @@ int run_filter(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_
         if ((rc = R->alloc()) != ACX_OK) return rc;
         return stage_finish(&S, d_hay, R->rows, R->bytes, (int64_t *)R->part[0], (int64_t *)R->part[1], R->part[2], st);
     };
-    int rc = retire_find(body(), st, r, R, S.block, one_count);
+    int rc = body();
+    if (T.block) R->scratch.push_back(T.block); // (the scored form: kept until acx_free_filtered)
+    rc = retire_find(rc, st, r, R, S.block, one_count);
+    if (rc != ACX_OK) { acx_free_filtered(R); return rc; }
+    *out = R;
+    return ACX_OK;
+}
+
+// The host route's end: the rows kept by counts[h] >= min_matches, copied from the caller's memory (the output never crosses
+// the bus)
+int host_filtered(const acx_automaton *a, const HostBatch &B, uint64_t len, uint64_t n_hay, const uint64_t *counts,
+                  uint64_t min_matches, uint32_t flags, acx_filtered_t **out) {
+    uint64_t k = 0, total = 0;
+    int rc = acx_filter_host(B.hay, len, B.rel.data(), n_hay, counts, min_matches, flags, nullptr, nullptr, nullptr, &k, &total);
+    if (rc != ACX_OK) return rc;
+    acx_filtered_t *R = new (std::nothrow) acx_filtered_t();
+    if (!R) return fail(ACX_ENOMEM, "out of memory");
+    R->device = a->device;
+    R->n_src = n_hay;
+    R->rows = k;
+    R->bytes = total;
+    if ((rc = R->alloc()) != ACX_OK) { delete R; return rc; }
+    rc = acx_filter_host(B.hay, len, B.rel.data(), n_hay, counts, min_matches, flags, (int64_t *)R->part[0], (int64_t *)R->part[1],
+                         R->part[2], &R->rows, &R->bytes);
     if (rc != ACX_OK) { acx_free_filtered(R); return rc; }
     *out = R;
     return ACX_OK;
@@ -184,22 +231,33 @@ int acx_filter(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint6
         acx_free_summary(s);
         if (rc != ACX_OK) return rc;
     }
-    // the gather: a memcpy per kept row from the caller's memory (the output never crosses the bus)
-    uint64_t k = 0, total = 0;
-    rc = acx_filter_host(B.hay, len, B.rel.data(), n_hay, counts.data(), min_matches, flags, nullptr, nullptr, nullptr, &k, &total);
+    return host_filtered(a, B, len, n_hay, counts.data(), min_matches, flags, out);
+}
+
+int acx_filter_scored(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
+                      const int32_t *weights, uint64_t n_weights, int64_t min_score, uint32_t flags, acx_filtered_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    int rc = check_scored(a, ScoreBy{weights, n_weights, min_score}, flags);
+    if (rc == ACX_OK && overlapping) rc = check_overlapping(a); // (the error, no device state)
     if (rc != ACX_OK) return rc;
-    acx_filtered_t *R = new (std::nothrow) acx_filtered_t();
-    if (!R) return fail(ACX_ENOMEM, "out of memory");
-    R->device = a->device;
-    R->n_src = n_hay;
-    R->rows = k;
-    R->bytes = total;
-    if ((rc = R->alloc()) != ACX_OK) { delete R; return rc; }
-    rc = acx_filter_host(B.hay, len, B.rel.data(), n_hay, counts.data(), min_matches, flags, (int64_t *)R->part[0], (int64_t *)R->part[1],
-                         R->part[2], &R->rows, &R->bytes);
-    if (rc != ACX_OK) { acx_free_filtered(R); return rc; }
-    *out = R;
-    return ACX_OK;
+    HostBatch B;
+    if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
+    std::vector<uint64_t> verdict;
+    std::vector<int64_t> score;
+    try {
+        verdict.assign(n_hay + 1, 0);
+        score.assign(n_hay + 1, 0);
+    } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
+    if (n_hay) { // the scores: acx_score chooses its own route, 8 bytes per row come back
+        acx_scores_t *s = nullptr;
+        rc = acx_score(a, B.hay, len, B.rel.data(), n_hay, overlapping, weights, n_weights, &s);
+        if (rc == ACX_OK) rc = acx_scores_copy(s, score.data());
+        acx_free_scores(s);
+        if (rc != ACX_OK) return rc;
+    }
+    for (uint64_t h = 0; h < n_hay; h++) verdict[h] = score[h] >= min_score ? 1 : 0;
+    return host_filtered(a, B, len, n_hay, verdict.data(), 1, flags, out);
 }
 
 int acx_filter_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
@@ -211,6 +269,19 @@ int acx_filter_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const
     // (a case-insensitive handle: the folded copy is searched, the caller's bytes are copied)
     return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, overlapping, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
         return run_filter(a, c, (const uint8_t *)d_hay, d_search, len, G, overlapping, min_matches, flags, out);
+    });
+}
+
+int acx_filter_scored_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                             uint64_t uniform_len, int overlapping, const int32_t *weights, uint64_t n_weights, int64_t min_score,
+                             uint32_t flags, acx_filtered_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    const ScoreBy by{weights, n_weights, min_score};
+    int rc = check_scored(a, by, flags);
+    if (rc != ACX_OK) return rc;
+    return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, overlapping, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_filter(a, c, (const uint8_t *)d_hay, d_search, len, G, overlapping, 1, flags, out, &by);
     });
 }
 

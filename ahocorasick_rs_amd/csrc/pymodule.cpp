@@ -655,6 +655,24 @@ PyObject *bac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
      "sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "           \
      "count_by_pattern_sparse_batch.  A tensor on the automaton's device is searched and compacted there and the result "      \
      "stays there; nothing but its two sizes crosses the bus."}
+// per-pattern weights: a score per row, and the rows kept or dropped by score (defined behind the FilteredRows below)
+PyObject *ac_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
+PyObject *bac_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
+PyObject *ac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
+PyObject *bac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
+#define ACX_SCORE_METHODS(score_fn, filter_fn)                                                                                 \
+    {"score_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(score_fn)), METH_VARARGS | METH_KEYWORDS,       \
+     "[extension] score_batch(haystacks, weights, overlapping=False, *, offsets=None, row_length=None) -> RowScores: for "     \
+     "every row the sum of weights[pattern] over the matches find_matches_as_indexes_batch reports for it (int64; it wraps "   \
+     "modulo 2^64).  weights: one int per pattern, |w| < 2^31 -- a sequence of ints or an int64 / int32 buffer.  haystacks: "  \
+     "a sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "         \
+     "count_by_pattern_sparse_batch.  A tensor on the automaton's device is searched and scored there and the result stays "   \
+     "there."},                                                                                                                \
+    {"filter_by_score_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(filter_fn)),                          \
+     METH_VARARGS | METH_KEYWORDS,                                                                                             \
+     "[extension] filter_by_score_batch(haystacks, weights, overlapping=False, *, keep='unmatched', min_score=1, "             \
+     "offsets=None, row_length=None) -> FilteredRows: filter_batch with the verdict on a row taken from its score -- a row "   \
+     "is matched when score_batch's value for it is at least min_score (any int64)."}
 #define ACX_COLUMNS_METHODS(fn)                                                                                                 \
     {"find_matches_as_columns", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)),                        \
      METH_VARARGS | METH_KEYWORDS,                                                                                              \
@@ -693,6 +711,7 @@ PyMethodDef ac_methods[] = {
     ACX_COLUMNS_METHODS(ac_columns),
     ACX_SPARSE_COUNTS_METHOD(ac_sparse_counts),
     ACX_FILTER_METHOD(ac_filter_batch),
+    ACX_SCORE_METHODS(ac_score_batch, ac_filter_by_score_batch),
     {"_info", ac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -973,9 +992,10 @@ PyTypeObject *MatchColumnsType = nullptr;
 PyTypeObject *ColumnType = nullptr;
 PyTypeObject *PatternCountsType = nullptr;
 PyTypeObject *FilteredRowsType = nullptr;
+PyTypeObject *RowScoresType = nullptr;
 
-// What a Column's owner -- a MatchColumns, a PatternCounts or a FilteredRows (`which`: ACX_COL_*, ACX_TALLY_*, ACX_FILT_*)
-// -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
+// What a Column's owner -- a MatchColumns, a PatternCounts, a FilteredRows (`which`: ACX_COL_*, ACX_TALLY_*, ACX_FILT_*) or a
+// RowScores (its one part) -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
 struct OwnerOps {
     int (*on_device)(const void *h);
     const void *(*data)(const void *h, int which); // (waits for the device work)
@@ -1006,10 +1026,14 @@ const OwnerOps PC_OPS = {[](const void *h) { return acx_tally_on_device(static_c
 const OwnerOps FR_OPS = {[](const void *h) { return acx_filtered_on_device(static_cast<const acx_filtered_t *>(h)); },
                          [](const void *h, int w) { return acx_filtered_data(static_cast<const acx_filtered_t *>(h), w); },
                          [](void *h) { acx_free_filtered(static_cast<acx_filtered_t *>(h)); }};
+const OwnerOps RS_OPS = {[](const void *h) { return acx_scores_on_device(static_cast<const acx_scores_t *>(h)); },
+                         [](const void *h, int) -> const void * { return acx_scores_data(static_cast<const acx_scores_t *>(h)); },
+                         [](void *h) { acx_free_scores(static_cast<acx_scores_t *>(h)); }};
 OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
 acx_columns_t *mc_handle(PyObject *s) { return static_cast<acx_columns_t *>(owner_of(s)->h); }
 acx_tally_t *pc_handle(PyObject *s) { return static_cast<acx_tally_t *>(owner_of(s)->h); }
 acx_filtered_t *fr_handle(PyObject *s) { return static_cast<acx_filtered_t *>(owner_of(s)->h); }
+acx_scores_t *rs_handle(PyObject *s) { return static_cast<acx_scores_t *>(owner_of(s)->h); }
 
 // a new owner of `type` around the result h; frees h when the object cannot be made
 OwnerObject *new_owner(PyTypeObject *type, const OwnerOps *ops, void *h, int device) {
@@ -1254,7 +1278,7 @@ PyType_Slot col_slots[] = {
     {Py_sq_length, reinterpret_cast<void *>(col_len)},
     {Py_bf_getbuffer, reinterpret_cast<void *>(col_getbuffer)},
     {Py_tp_doc, const_cast<char *>(
-        "One int64 column of a MatchColumns or a PatternCounts, or one part of a FilteredRows (int64; its data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
+        "One int64 column of a MatchColumns, a PatternCounts or a RowScores, or one part of a FilteredRows (int64; its data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
         "copy) and, in host memory, the buffer protocol (format 'q', or 'B' for uint8; read-only).")},
     {0, nullptr},
 };
@@ -1633,6 +1657,20 @@ PyType_Slot fr_slots[] = {
     {0, nullptr},
 };
 
+// keep = 'unmatched' | 'matched' -> the acx_filter* flags; sets the exception
+bool parse_keep(PyObject *keep, uint32_t *flags) {
+    if (!PyUnicode_Check(keep)) {
+        PyErr_Format(PyExc_TypeError, "argument 'keep': '%.100s' object cannot be converted to 'PyString'", Py_TYPE(keep)->tp_name);
+        return false;
+    }
+    if (PyUnicode_CompareWithASCIIString(keep, "matched") == 0) *flags = ACX_FILTER_KEEP_MATCHED;
+    else if (PyUnicode_CompareWithASCIIString(keep, "unmatched") != 0) {
+        PyErr_SetString(PyExc_ValueError, "keep must be 'unmatched' or 'matched'");
+        return false;
+    }
+    return true;
+}
+
 // filter_batch of both classes: utf8 = the str class (no offset into a row is reported: the search is on bytes)
 PyObject *filter_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool utf8) {
     static const char *kw[] = {"haystacks", "overlapping", "keep", "min_matches", "offsets", "row_length", nullptr};
@@ -1643,17 +1681,7 @@ PyObject *filter_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool
         return nullptr;
     if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
     uint32_t flags = 0;
-    if (keep) {
-        if (!PyUnicode_Check(keep)) {
-            PyErr_Format(PyExc_TypeError, "argument 'keep': '%.100s' object cannot be converted to 'PyString'", Py_TYPE(keep)->tp_name);
-            return nullptr;
-        }
-        if (PyUnicode_CompareWithASCIIString(keep, "matched") == 0) flags = ACX_FILTER_KEEP_MATCHED;
-        else if (PyUnicode_CompareWithASCIIString(keep, "unmatched") != 0) {
-            PyErr_SetString(PyExc_ValueError, "keep must be 'unmatched' or 'matched'");
-            return nullptr;
-        }
-    }
+    if (keep && !parse_keep(keep, &flags)) return nullptr;
     unsigned long long min_matches = 1;
     if (mm) {
         if (!PyLong_Check(mm) || PyBool_Check(mm)) {
@@ -1697,6 +1725,187 @@ PyObject *ac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
 }
 PyObject *bac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
     return filter_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false);
+}
+
+// ---------------------------------------------------------------------------
+// per-pattern weights: score_batch -> RowScores (acx_score / acx_score_device), filter_by_score_batch -> FilteredRows
+// (acx_filter_scored / acx_filter_scored_device).  A RowScores owns the acx_scores_t; .score is a Column with the lifetime
+// chain of a MatchColumns' columns.
+// ---------------------------------------------------------------------------
+PyObject *rs_get_score(PyObject *s, void *) { return new_column(s, 0, acx_scores_rows(rs_handle(s))); }
+Py_ssize_t rs_len(PyObject *s) { return (Py_ssize_t)acx_scores_rows(rs_handle(s)); }
+
+PyObject *rs_tolist(PyObject *self_, PyObject *) {
+    acx_scores_t *h = rs_handle(self_);
+    const uint64_t rows = acx_scores_rows(h);
+    std::vector<int64_t> v((size_t)rows + 1);
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = acx_scores_copy(h, v.data());
+    Py_END_ALLOW_THREADS
+    if (rc != ACX_OK) return raise_acx(rc);
+    PyObject *list = PyList_New((Py_ssize_t)rows);
+    for (uint64_t i = 0; list && i < rows; i++) {
+        PyObject *it = PyLong_FromLongLong((long long)v[(size_t)i]);
+        if (!it) { Py_CLEAR(list); break; }
+        PyList_SET_ITEM(list, (Py_ssize_t)i, it);
+    }
+    return list;
+}
+
+PyGetSetDef rs_getset[] = {
+    {"score", rs_get_score, nullptr, "Column of len(self) int64 entries: every row's score", nullptr},
+    {"device", owner_get_device, nullptr, "None: the scores are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+PyMethodDef rs_methods[] = {
+    {"tolist", rs_tolist, METH_NOARGS, "the scores as list[int] (copies device scores to the host)"},
+    {nullptr, nullptr, 0, nullptr},
+};
+PyType_Slot rs_slots[] = {
+    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
+    {Py_tp_methods, rs_methods},
+    {Py_tp_getset, rs_getset},
+    {Py_sq_length, reinterpret_cast<void *>(rs_len)},
+    {Py_tp_doc, const_cast<char *>(
+        "The result of score_batch: .score is an int64 Column of len(self) entries, one per row of the batch, where the "
+        "search ran (.device).")},
+    {0, nullptr},
+};
+
+// weights: one int per pattern, |w| < 2^31 -- an int64 / int32 buffer or a sequence of ints; sets the exception
+bool parse_weights(PyObject *w, uint64_t n_patterns, std::vector<int32_t> *out) {
+    std::vector<long long> wide;
+    if (PyObject_CheckBuffer(w) && !PyBytes_Check(w) && !PyByteArray_Check(w)) {
+        Py_buffer view;
+        if (PyObject_GetBuffer(w, &view, PyBUF_FORMAT | PyBUF_C_CONTIGUOUS) < 0) return false;
+        const char *f = view.format ? view.format : "B";
+        if (*f == '@' || *f == '=' || *f == '<') f++;
+        const bool i64 = (f[0] == 'q' || f[0] == 'l') && !f[1] && view.itemsize == 8;
+        const bool i32 = (f[0] == 'i' || f[0] == 'l') && !f[1] && view.itemsize == 4;
+        if (view.ndim != 1 || (!i64 && !i32)) {
+            PyBuffer_Release(&view);
+            PyErr_SetString(PyExc_TypeError, "argument 'weights': a buffer of weights must be 1-D int64 or int32");
+            return false;
+        }
+        const size_t n = (size_t)(view.len / view.itemsize);
+        wide.resize(n);
+        for (size_t i = 0; i < n; i++)
+            wide[i] = i64 ? (long long)static_cast<const int64_t *>(view.buf)[i] : (long long)static_cast<const int32_t *>(view.buf)[i];
+        PyBuffer_Release(&view);
+    } else {
+        PyObject *seq = PyUnicode_Check(w) || PyBytes_Check(w) || PyByteArray_Check(w)
+                            ? nullptr : PySequence_Fast(w, "argument 'weights': a sequence of ints or an int64 / int32 buffer is needed");
+        if (!seq) {
+            if (!PyErr_Occurred()) PyErr_SetString(PyExc_TypeError, "argument 'weights': a sequence of ints or an int64 / int32 buffer is needed");
+            return false;
+        }
+        const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
+        wide.resize((size_t)n);
+        for (Py_ssize_t i = 0; i < n; i++) {
+            PyObject *it = PySequence_Fast_GET_ITEM(seq, i);
+            if (PyBool_Check(it) || !PyIndex_Check(it)) {
+                PyErr_Format(PyExc_TypeError, "argument 'weights': '%.100s' object cannot be interpreted as an integer", Py_TYPE(it)->tp_name);
+                Py_DECREF(seq);
+                return false;
+            }
+            PyObject *ix = PyNumber_Index(it);
+            if (!ix) { Py_DECREF(seq); return false; }
+            int overflow = 0;
+            const long long v = PyLong_AsLongLongAndOverflow(ix, &overflow);
+            Py_DECREF(ix);
+            if (v == -1 && !overflow && PyErr_Occurred()) { Py_DECREF(seq); return false; }
+            wide[(size_t)i] = overflow ? (overflow > 0 ? LLONG_MAX : LLONG_MIN) : v;
+        }
+        Py_DECREF(seq);
+    }
+    if (wide.size() != n_patterns) {
+        PyErr_Format(PyExc_ValueError, "weights has %zu entries for %llu patterns: one per pattern is needed", wide.size(),
+                     (unsigned long long)n_patterns);
+        return false;
+    }
+    out->resize(wide.size());
+    for (size_t i = 0; i < wide.size(); i++) {
+        if (wide[i] > 2147483647LL || wide[i] < -2147483647LL) {
+            PyErr_Format(PyExc_ValueError, "weights[%zu] is outside int32: |w| < 2^31 is needed", i);
+            return false;
+        }
+        (*out)[i] = (int32_t)wide[i];
+    }
+    return true;
+}
+
+// score_batch (filter = false) and filter_by_score_batch of both classes: utf8 = the str class (no offset into a row is
+// reported: the search is on bytes)
+PyObject *scored_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool utf8, bool filter) {
+    static const char *kw_s[] = {"haystacks", "weights", "overlapping", "offsets", "row_length", nullptr};
+    static const char *kw_f[] = {"haystacks", "weights", "overlapping", "keep", "min_score", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *wts = nullptr, *ov = nullptr, *keep = nullptr, *ms = nullptr, *offsets = nullptr, *row_length = nullptr;
+    int overlapping = 0;
+    if (filter ? !PyArg_ParseTupleAndKeywords(args, kwargs, "OO|O$OOOO:filter_by_score_batch", const_cast<char **>(kw_f), &hay, &wts,
+                                              &ov, &keep, &ms, &offsets, &row_length)
+               : !PyArg_ParseTupleAndKeywords(args, kwargs, "OO|O$OO:score_batch", const_cast<char **>(kw_s), &hay, &wts, &ov, &offsets,
+                                              &row_length))
+        return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    uint32_t flags = 0;
+    if (keep && !parse_keep(keep, &flags)) return nullptr;
+    long long min_score = 1;
+    if (ms) {
+        if (!PyLong_Check(ms) || PyBool_Check(ms)) {
+            PyErr_Format(PyExc_TypeError, "argument 'min_score': '%.100s' object cannot be converted to 'PyInt'", Py_TYPE(ms)->tp_name);
+            return nullptr;
+        }
+        int overflow = 0;
+        min_score = PyLong_AsLongLongAndOverflow(ms, &overflow);
+        if (min_score == -1 && !overflow && PyErr_Occurred()) return nullptr;
+        if (overflow) {
+            PyErr_SetString(PyExc_ValueError, "min_score must fit an int64");
+            return nullptr;
+        }
+    }
+    acx_info_t info;
+    if (acx_automaton_info(a, &info) != ACX_OK) return raise_acx(ACX_EINVAL);
+    std::vector<int32_t> w;
+    if (!parse_weights(wts, info.n_patterns, &w)) return nullptr;
+    const int device = acx_automaton_device(a);
+    BatchInput in;
+    if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
+    acx_scores_t *s = nullptr;
+    acx_filtered_t *f = nullptr;
+    const int rc = batch_dispatch(
+        device, in,
+        [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+            return filter ? acx_filter_scored(a, p, len, off, rows, overlapping, w.data(), w.size(), min_score, flags, &f)
+                          : acx_score(a, p, len, off, rows, overlapping, w.data(), w.size(), &s);
+        },
+        [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_length) {
+            return filter ? acx_filter_scored_device(a, p, len, d_off, rows, row_length, overlapping, w.data(), w.size(), min_score,
+                                                     flags, &f)
+                          : acx_score_device(a, p, len, d_off, rows, row_length, overlapping, w.data(), w.size(), &s);
+        });
+    if (rc == BAD_OFFSETS) return nullptr;
+    if (rc != ACX_OK) return raise_acx(rc);
+    if (!filter) return reinterpret_cast<PyObject *>(new_owner(RowScoresType, &RS_OPS, s, device));
+    OwnerObject *o = new_owner(FilteredRowsType, &FR_OPS, f, device);
+    if (o) {
+        static_cast<FilteredRowsObject *>(o)->n_src = in.rows;
+        static_cast<FilteredRowsObject *>(o)->utf8 = utf8;
+    }
+    return reinterpret_cast<PyObject *>(o);
+}
+
+PyObject *ac_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return scored_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, true, false);
+}
+PyObject *bac_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return scored_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false, false);
+}
+PyObject *ac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return scored_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, true, true);
+}
+PyObject *bac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return scored_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false, true);
 }
 
 // device-resident search -> list of tuples (the records come back with ONE D2H copy of the result)
@@ -1831,6 +2040,7 @@ PyMethodDef bac_methods[] = {
     ACX_COLUMNS_METHODS(bac_columns),
     ACX_SPARSE_COUNTS_METHOD(bac_sparse_counts),
     ACX_FILTER_METHOD(bac_filter_batch),
+    ACX_SCORE_METHODS(bac_score_batch, bac_filter_by_score_batch),
     {"_info", bac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -1878,14 +2088,17 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, pc_slots};
     PyType_Spec fr_spec = {"ahocorasick_rs.FilteredRows", sizeof(FilteredRowsObject), 0,
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, fr_slots};
+    PyType_Spec rs_spec = {"ahocorasick_rs.RowScores", sizeof(OwnerObject), 0,
+                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, rs_slots};
     FilteredRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&fr_spec));
+    RowScoresType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&rs_spec));
     MatchColumnsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mc_spec));
     ColumnType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&col_spec));
     PatternCountsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&pc_spec));
-    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
-    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType}) { // (the module holds one reference, the globals the other)
+    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType || !RowScoresType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
+    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType, RowScoresType}) { // (the module holds one reference, the globals the other)
         Py_INCREF(tp);
-        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : "MatchColumns",
+        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : tp == RowScoresType ? "RowScores" : "MatchColumns",
                                reinterpret_cast<PyObject *>(tp)) < 0) {
             Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);
             return nullptr;

@@ -1,4 +1,4 @@
-// result_block.hpp -- what the stages behind the find pipeline (summaries, splice, columns, tally, row filter) share: the
+// result_block.hpp -- what the stages behind the find pipeline (summaries, splice, columns, tally, row filter, scores) share: the
 // owner of a result's memory, the layout of its block, the end of a stage (retire_find) and the frame of its entry points.
 // The stages' middles are their own (summary_api.cpp .. filter_api.cpp); no kernel includes this.
 #pragma once
@@ -73,6 +73,21 @@ int retire_find(int rc, hipStream_t st, acx_result *r, ResultBlock *R, void *t1 
 // The per-haystack counts of a find, on the device: the result's own or, for one haystack that is no batch (the find kept
 // none), its total uploaded to *one -- a temporary for retire_find.
 int counts_of(const acx_result *r, hipStream_t st, uint64_t **one, const uint64_t **d_counts);
+
+// The score stage (score.hpp; score_api.cpp) behind a find's records and counts, for acx_score_device, acx_score_rows_device
+// and the hook of acx_filter_scored_device.  Its temporaries are one block of the buffer cache -- the caller's to return,
+// behind the stage's kernels.
+struct ScoreTemps {
+    void *block = nullptr;
+    int64_t *score = nullptr;  // the scores: d_score, or a part of the block
+    uint64_t *flags = nullptr; // score >= *min_score as 0 / 1 words (min_score != null): the row filter's counts
+};
+// d_m: n records; d_counts: rows words (rows > 0) that sum to n (check_sum: they are a caller's -- read back and compared
+// before a kernel reads a record by them).  The weights, n_patterns of them: h_weights (host memory that stays valid until
+// the stream has passed the copy) or d_weights (device memory).  d_score: rows words, or null: in the block.
+int score_stage(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, const uint64_t *d_counts, uint64_t rows,
+                const int32_t *h_weights, const int32_t *d_weights, uint64_t n_patterns, bool check_sum, int64_t *d_score,
+                const int64_t *min_score, ScoreTemps *T);
 
 // A host entry point's haystacks as the stages take them: offsets (n_hay + 1 of them, monotone; null: ONE haystack of *len
 // bytes, *n_hay becomes 1) cut `hay`; afterwards *len bytes at B->hay (null when there are none) are the haystacks, cut by

@@ -1,0 +1,250 @@
+// score_api.cpp -- per-row scores from per-pattern weights (score.hpp): the host form, the device stage behind the find
+// pipeline, the acx_score* entry points and the accessors of their result.  acx_filter_scored* are filter_api.cpp's: they
+// return its result.
+#include "replace.hpp"
+#include "result_block.hpp"
+#include "score.hpp"
+
+using namespace acxh;
+
+// acx_score / acx_score_device: rows int64 words in ONE block (result_block.hpp).  Device route: the find's records and the
+// stage's temporaries have gone back to the cache behind the stage's kernels; `weights` is the call's copy of the caller's
+// weights, which the upload reads until `done`.
+struct ACX_HIDDEN acx_scores : ResultBlock {
+    uint64_t rows = 0;
+    int64_t *score = nullptr;
+    std::vector<int32_t> weights;
+
+    static Layout layout(uint64_t rows) { return block_layout({rows * 8}); }
+    int alloc() { // the block (by on_device)
+        int rc = ResultBlock::alloc(layout(rows).bytes);
+        if (rc == ACX_OK) score = (int64_t *)base();
+        return rc;
+    }
+};
+
+namespace acxh ACX_HIDDEN {
+
+int score_stage(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, const uint64_t *d_counts, uint64_t rows,
+                const int32_t *h_weights, const int32_t *d_weights, uint64_t n_patterns, bool check_sum, int64_t *d_score,
+                const int64_t *min_score, ScoreTemps *T) {
+    // [rec_off: rows + 1][scan][tiles][weights: n_patterns int32][score: rows][flags: rows], every part 256-byte aligned
+    Carver C;
+    const uint64_t o_rec = C.part(rows + 1), o_scan = C.part(replace_scan_words(rows)), o_tiles = C.part(acx::score_tile_words(n)),
+                   o_w = C.part(h_weights ? (n_patterns + 1) / 2 : 0), o_score = C.part(d_score ? 0 : rows),
+                   o_flags = C.part(min_score ? rows : 0);
+    HIPCHK(g_bufs.get(&T->block, C.bytes(), device));
+    uint64_t *b = (uint64_t *)T->block;
+    int64_t *rec_off = (int64_t *)(b + o_rec);
+    T->score = d_score ? d_score : (int64_t *)(b + o_score);
+    if (h_weights) {
+        if (n_patterns) HIPCHK(hipMemcpyAsync(b + o_w, h_weights, n_patterns * 4, hipMemcpyHostToDevice, st));
+        d_weights = (const int32_t *)(b + o_w);
+    }
+    HIPCHK(acx::replace_scan(nullptr, nullptr, d_counts, rows, rec_off, b + o_scan, st));
+    if (check_sum) {
+        uint64_t sum = 0;
+        HIPCHK(hipMemcpyAsync(&sum, rec_off + rows, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (sum != n) return fail(ACX_EINVAL, "the counts do not sum to the number of records");
+    }
+    HIPCHK(acx::score_rows(d_m, n, rec_off, rows, d_weights, n_patterns, b + o_tiles, T->score, st));
+    if (min_score) {
+        T->flags = b + o_flags;
+        HIPCHK(acx::score_flags(T->score, rows, *min_score, T->flags, st));
+    }
+    return ACX_OK;
+}
+
+} // namespace acxh
+
+namespace {
+
+// ACX_SCORE_HOST_MAX (bytes, read per call): batches up to this size are scored on the host, behind acx_find_batch.  The
+// default is ACX_SUMMARY_HOST_MAX's, which is itself not a measured crossover.
+uint64_t score_host_max() {
+    const char *e = std::getenv("ACX_SCORE_HOST_MAX");
+    return e ? std::strtoull(e, nullptr, 10) : (1ull << 20);
+}
+
+int check_weights(const acx_automaton *a, const int32_t *weights, uint64_t n_weights) {
+    if (n_weights != a->host.n_patterns) return fail(ACX_EINVAL, "one weight per pattern is needed");
+    if (n_weights && !weights) return fail(ACX_EINVAL, "null argument");
+    return ACX_OK;
+}
+
+// The device route: the find pipeline as acx_find_device runs it (batch splits and the expansion of copies included, byte
+// offsets: no offset is reported), then the stage on the same stream.  Returns with the stage in flight (out->done).
+// d_hay, and G.offsets, must stay valid until then; the weights are copied here.
+int run_score(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping,
+              const int32_t *weights, uint64_t n_weights, acx_scores_t **out) {
+    *out = nullptr;
+    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
+    const uint64_t rows = segmented ? G.n_hay : 1;
+    acx_scores_t *R = new (std::nothrow) acx_scores_t();
+    if (!R) return fail(ACX_ENOMEM, "out of memory");
+    try {
+        R->weights.assign(weights, weights + n_weights);
+    } catch (...) { delete R; return fail(ACX_ENOMEM, "out of memory"); }
+    acx_result *r = nullptr;
+    if (rows) { // (an empty batch: nothing to search, no score)
+        int rc = run_find(a, x, d_hay, len, G, overlapping, 0, &r);
+        if (rc != ACX_OK) { delete R; return rc; }
+    }
+    hipStream_t st = x->stream;
+    R->device = a->device;
+    R->on_device = 1;
+    R->rows = rows;
+    ScoreTemps T;
+    uint64_t *one_count = nullptr;
+    auto body = [&]() -> int {
+        int rc;
+        if ((rc = R->alloc()) != ACX_OK || !rows) return rc;
+        const uint64_t *d_counts = nullptr;
+        if ((rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
+        return score_stage(a->device, st, r->d_matches, r->n, d_counts, rows, R->weights.data(), nullptr, n_weights, false, R->score,
+                           nullptr, &T);
+    };
+    int rc = retire_find(body(), st, r, R, T.block, one_count);
+    if (rc != ACX_OK) { acx_free_scores(R); return rc; }
+    *out = R;
+    return ACX_OK;
+}
+
+acx_scores_t *host_scores(int device, uint64_t rows) {
+    acx_scores_t *R = new (std::nothrow) acx_scores_t();
+    if (!R) return nullptr;
+    R->device = device;
+    R->rows = rows;
+    if (R->alloc() != ACX_OK) { delete R; return nullptr; }
+    R->score[0] = 0;
+    return R;
+}
+
+} // namespace
+
+extern "C" {
+
+int acx_score_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts, uint64_t n_hay, const int32_t *weights,
+                   uint64_t n_weights, int64_t *scores) {
+    if ((n_m && !m) || (n_weights && !weights) || (n_hay && !scores)) return fail(ACX_EINVAL, "null argument");
+    if (!counts && n_hay > 1) return fail(ACX_EINVAL, "several haystacks need counts");
+    if (!counts && !n_hay && n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+    uint64_t sum = 0;
+    for (uint64_t h = 0; counts && h < n_hay; h++) {
+        if (counts[h] > n_m - sum) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+        sum += counts[h];
+    }
+    if (counts && sum != n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+    uint64_t at = 0;
+    for (uint64_t h = 0; h < n_hay; h++) {
+        const uint64_t end = counts ? at + counts[h] : n_m;
+        uint64_t s = 0; // (unsigned: the sum wraps modulo 2^64)
+        for (; at < end; at++)
+            if (m[at].pattern < n_weights) s += (uint64_t)(int64_t)weights[m[at].pattern];
+        scores[h] = (int64_t)s;
+    }
+    return ACX_OK;
+}
+
+int acx_score(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
+              const int32_t *weights, uint64_t n_weights, acx_scores_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    int rc = check_weights(a, weights, n_weights);
+    if (rc == ACX_OK && overlapping) rc = check_overlapping(a); // (the error, no device state)
+    if (rc != ACX_OK) return rc;
+    HostBatch B;
+    if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
+    if (len <= score_host_max() || !n_hay) {
+        // host route: acx_find_batch as it is (the small-call kernel, the in-place read, the staged pipeline), then the sums here
+        acx_match_t *m = nullptr;
+        uint64_t nm = 0;
+        std::vector<uint64_t> counts(n_hay, 0);
+        if (n_hay) rc = acx_find_batch(a, B.hay, B.rel.data(), n_hay, overlapping, 0, &m, &nm, counts.data());
+        if (rc != ACX_OK) return rc;
+        acx_scores_t *R = host_scores(a->device, n_hay);
+        if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
+        if (n_hay) rc = acx_score_host(m, nm, counts.data(), n_hay, weights, n_weights, R->score);
+        acx_free_matches(m);
+        if (rc != ACX_OK) { acx_free_scores(R); return rc; }
+        *out = R;
+        return ACX_OK;
+    }
+    // device route: staged, searched and scored under one lease; 8 bytes per row come back
+    acx_scores_t *D = nullptr;
+    {
+        Lease lease(a);
+        Ctx *c = lease.c;
+        if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
+        rc = stage_host(a, c, B.hay, len, B.rel.data(), n_hay + 1, false);
+        if (rc != ACX_OK) return rc;
+        const uint8_t *d_search = nullptr;
+        if ((rc = fold_copy(a, c, c->ws.hay, len, &d_search)) != ACX_OK) return rc;
+        rc = run_score(a, c, d_search, len, Segments{c->ws.offsets, n_hay, 0}, overlapping, weights, n_weights, &D);
+        if (rc != ACX_OK) return rc;
+        rc = D->wait(); // (the staging buffers are the context's: the lease ends behind the kernels)
+    }
+    acx_scores_t *R = rc == ACX_OK ? host_scores(a->device, D->rows) : nullptr;
+    if (rc == ACX_OK && !R) rc = fail(ACX_ENOMEM, "out of memory");
+    if (rc == ACX_OK) {
+        DeviceScope ds(a->device);
+        const hipError_t e = hipMemcpy(R->h_block, D->d_block, D->rows * 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hipfail(e, "copying the scores to the host");
+    }
+    acx_free_scores(D);
+    if (rc != ACX_OK) { acx_free_scores(R); return rc; }
+    *out = R;
+    return ACX_OK;
+}
+
+int acx_score_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                     uint64_t uniform_len, int overlapping, const int32_t *weights, uint64_t n_weights, acx_scores_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    int rc = check_weights(a, weights, n_weights);
+    if (rc != ACX_OK) return rc;
+    return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, overlapping, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_score(a, c, d_search, len, G, overlapping, weights, n_weights, out);
+    });
+}
+
+int acx_score_rows_device(const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint64_t n_hay,
+                          const int32_t *d_weights, uint64_t n_weights, int64_t *d_scores) {
+    if (!n_hay) return n ? fail(ACX_EINVAL, "the counts do not sum to the number of records") : ACX_OK;
+    if (!d_scores || !d_counts || (n && !d_records) || (n_weights && !d_weights)) return fail(ACX_EINVAL, "null argument");
+    if (((uintptr_t)d_records | (uintptr_t)d_counts | (uintptr_t)d_scores) & 7)
+        return fail(ACX_EINVAL, "records, counts and scores must be 8-byte aligned");
+    if ((uintptr_t)d_weights & 3) return fail(ACX_EINVAL, "the weights must be 4-byte aligned");
+    hipPointerAttribute_t at;
+    HIPCHK(hipPointerGetAttributes(&at, d_scores));
+    DeviceScope ds(at.device);
+    ScoreTemps T;
+    int rc = score_stage(at.device, nullptr, d_records, n, d_counts, n_hay, nullptr, d_weights, n_weights, true, d_scores, nullptr, &T);
+    const hipError_t e = hipStreamSynchronize(nullptr);
+    g_bufs.put(T.block, at.device);
+    if (rc == ACX_OK && e != hipSuccess) rc = hipfail(e, "hipStreamSynchronize");
+    return rc;
+}
+
+uint64_t acx_scores_rows(const acx_scores_t *s) { return s ? s->rows : 0; }
+int acx_scores_on_device(const acx_scores_t *s) { return s ? s->on_device : 0; }
+
+const int64_t *acx_scores_data(const acx_scores_t *s) {
+    if (!s) return nullptr;
+    return (const int64_t *)s->ptr_after_wait(s->score);
+}
+
+int acx_scores_copy(const acx_scores_t *s, int64_t *host_dst) {
+    if (!s) return fail(ACX_EINVAL, "null argument");
+    if (s->rows && !host_dst) return fail(ACX_EINVAL, "null argument");
+    return s->copy_out(host_dst, s->score, s->rows * 8);
+}
+
+void acx_free_scores(acx_scores_t *s) {
+    if (!s) return;
+    s->release();
+    delete s;
+}
+
+} // extern "C"

@@ -35,6 +35,9 @@ extern "C" {
  *     fourth addendum (additive as well): acx_filter / acx_filter_device / acx_filter_host / acx_filter_rows_device,
  *     ACX_FILTER_KEEP_MATCHED, ACX_FILT_*, the acx_filtered_t accessors (acx_filtered_rows, _bytes, _on_device, _data, _copy,
  *     acx_free_filtered);
+ *     fifth addendum (additive as well): acx_score / acx_score_device / acx_score_host / acx_score_rows_device, the
+ *     acx_scores_t accessors (acx_scores_rows, _on_device, _data, _copy, acx_free_scores), acx_filter_scored /
+ *     acx_filter_scored_device;
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -560,6 +563,58 @@ int acx_filter_host(const uint8_t *hay, uint64_t len, const uint64_t *offsets, u
 int acx_filter_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
                            const uint64_t *d_counts, uint64_t min_matches, uint32_t flags, int64_t *d_rows,
                            int64_t *d_out_offsets, uint8_t *d_data, uint64_t *n_rows, uint64_t *n_bytes);
+
+/* ---- scores: per-pattern weights, a score per row, and the row filter by score -- a block list with exceptions, a weighted
+ * lexicon, a threshold on "how much" of a row matched.  A handle has P patterns; weights: P int32 (host memory; n_weights
+ * != P: ACX_EINVAL).  score[h] = the sum of weights[pattern] over the matches acx_find_batch / acx_find_device reports for
+ * row h with the same `overlapping`: an int64, two's complement (it wraps modulo 2^64, which no row of fewer than 2^32
+ * matches reaches).  An overlapping search over a set with copies counts every copy with its own weight; a
+ * case-insensitive handle matches on the folded copy; no offset is reported, so the search runs on bytes whatever the
+ * caller's strings are; an empty row scores 0; a record whose pattern is >= P adds nothing and never indexes the weights.
+ * An overlapping search on a non-Standard handle fails with ACX_EOVERLAP before any device state is touched.
+ * acx_score: host haystacks (offsets: n_hay + 1, or null: one haystack of len bytes -- a batch of one row), a host result.
+ * Up to ACX_SCORE_HOST_MAX bytes (environment, read per call; default 1 MiB, ACX_SUMMARY_HOST_MAX's: not a measured
+ * crossover) acx_find / acx_find_batch runs and acx_score_host sums; beyond that the batch is staged, searched and scored in
+ * HBM and only 8 bytes per row come back.
+ * acx_score_device: acx_find_device's pipeline (d_offsets / uniform_len as there; neither: a batch of one row), then the
+ * device stage on the same stream -- one pass over the records, no sort; the result stays in HBM on the automaton's device.
+ * The call may return with the stage in flight: acx_scores_data / acx_scores_copy wait for it.  d_hay and d_offsets must
+ * stay valid until then; the weights are copied before the call returns.
+ * An empty result still has a valid, non-null address. */
+typedef struct acx_scores acx_scores_t;
+int acx_score(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
+              int overlapping, const int32_t *weights, uint64_t n_weights, acx_scores_t **out);
+int acx_score_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                     uint64_t uniform_len, int overlapping, const int32_t *weights /* host */, uint64_t n_weights,
+                     acx_scores_t **out);
+uint64_t acx_scores_rows(const acx_scores_t *s);     /* haystacks = int64 words of the result              */
+int acx_scores_on_device(const acx_scores_t *s);     /* 1: the scores are in HBM, 0: host memory           */
+/* host or device pointer by acx_scores_on_device; waits for the device stage.  NULL: the wait failed.  Valid until
+ * acx_free_scores. */
+const int64_t *acx_scores_data(const acx_scores_t *s);
+int acx_scores_copy(const acx_scores_t *s, int64_t *host_dst);
+void acx_free_scores(acx_scores_t *s);
+/* the sum itself.  acx_score_host: host memory, no device needed -- the definition above inside the library; m: n_m matches,
+ * all haystacks behind one another, counts[h] of them haystack h's (ACX_EINVAL when they do not sum to n_m), or counts =
+ * NULL: one row holds them all (n_hay = 1); scores: n_hay words.
+ * acx_score_rows_device: the device stage alone on records, counts (they must sum to n) and int32 weights in HBM on one
+ * device (8-byte alignment is all the records need, the weights 4-byte); needs no automaton; synchronous: d_scores (n_hay
+ * words) is complete when it returns.  n_hay = 0 launches nothing; n = 0 clears the scores. */
+int acx_score_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts /* NULL: one row */, uint64_t n_hay,
+                   const int32_t *weights, uint64_t n_weights, int64_t *scores);
+int acx_score_rows_device(const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint64_t n_hay,
+                          const int32_t *d_weights, uint64_t n_weights, int64_t *d_scores);
+/* the row filter by score: row h is MATCHED iff score[h] >= min_score (signed, any int64) and KEPT iff matched == (flags &
+ * ACX_FILTER_KEEP_MATCHED != 0); the result is an acx_filtered_t exactly as acx_filter / acx_filter_device make it.
+ * acx_filter_scored: the scores from acx_score (its own choice of route), then acx_filter_host over their 0 / 1 verdicts.
+ * acx_filter_scored_device: between the find and the filter's device stage, on the same stream, the scores and their
+ * verdicts are made in HBM, and the stage runs on the verdicts as its counts with min_matches = 1. */
+int acx_filter_scored(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
+                      int overlapping, const int32_t *weights, uint64_t n_weights, int64_t min_score, uint32_t flags,
+                      acx_filtered_t **out);
+int acx_filter_scored_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                             uint64_t uniform_len, int overlapping, const int32_t *weights /* host */, uint64_t n_weights,
+                             int64_t min_score, uint32_t flags, acx_filtered_t **out);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
