@@ -21,6 +21,7 @@ from .ahocorasick_rs import (
     PatternCounts,
     FilteredRows,
     RowScores,
+    MaskedRows,
 )
 
 __acx_amd__ = True
@@ -43,6 +44,8 @@ __all__ = [
     "FilteredRows",
     # Extension: the result of score_batch
     "RowScores",
+    # Extension: the result of mask_all_batch / match_mask_batch
+    "MaskedRows",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

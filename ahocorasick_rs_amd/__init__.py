@@ -26,6 +26,7 @@ try:
         PatternCounts,
         FilteredRows,
     RowScores,
+        MaskedRows,
     )
 except ImportError as e:  # pragma: no cover - build problem, fail loudly
     raise ImportError(
@@ -51,6 +52,8 @@ __all__ = [
     "FilteredRows",
     # Extension: the result of score_batch
     "RowScores",
+    # Extension: the result of mask_all_batch / match_mask_batch
+    "MaskedRows",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

@@ -20,7 +20,7 @@ class MatchKind:
 
 # extension: the result of find_matches_as_columns / find_matches_as_columns_batch
 class Column:
-    """One column, 1-D and contiguous, in host memory or in HBM: int64, or uint8 for a FilteredRows' data.  Every accessor
+    """One column, 1-D and contiguous, in host memory or in HBM: int64, or uint8 for a FilteredRows' or a MaskedRows' data.  Every accessor
     waits for the device work that writes it first."""
     def __len__(self) -> int: ...
     def __dlpack__(self, stream: Any = None, **ignored: Any) -> Any: ...
@@ -82,6 +82,22 @@ class RowScores:
     def __len__(self) -> int: ...  # the rows of the batch
     def tolist(self) -> list[int]: ...
 
+# extension: the result of mask_all_batch / match_mask_batch -- the batch's bytes with every byte that a match covers filled
+# (mask_all_batch) or the 0 / 1 mask (match_mask_batch), in the input's own layout, where the search ran
+class MaskedRows:
+    @property
+    def data(self) -> Column: ...  # nbytes uint8 entries, one per byte of the input
+    @property
+    def offsets(self) -> Column: ...  # len(self) + 1 int64 entries from 0: row i is data[offsets[i]:offsets[i + 1]]
+    @property
+    def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
+    @property
+    def nbytes(self) -> int: ...  # the size of data: the input's
+    def __len__(self) -> int: ...  # the rows of the batch
+    # the rows: list[str] (AhoCorasick.mask_all_batch) or list[bytes].  A sequence of str gives one entry per CHARACTER (the
+    # entries of continuation bytes are dropped on the host); a tensor gives the bytes as they are (decoded for list[str])
+    def tolist(self) -> Any: ...
+
 class AhoCorasick:
     def __init__(
         self,
@@ -140,6 +156,22 @@ class AhoCorasick:
         self, haystacks: Any, weights: Any, overlapping: bool = False, *, keep: str = "unmatched", min_score: int = 1,
         offsets: Any = None, row_length: Optional[int] = None
     ) -> FilteredRows: ...
+    # extension: the cover of a search's matches.  mask_all: the haystack with every character that a match covers replaced by
+    # fill -- a one-character ASCII str, so the output stays valid UTF-8 (anything else that is a str: ValueError; not a str:
+    # TypeError) -- and every other character where it was; match_mask: bytes, 1 where a match covers the character, else 0.
+    # Both have one entry per CHARACTER: len(result) == len(haystack).  overlapping=True (Standard only) covers the union of
+    # all occurrences.  The _batch forms take haystacks as count_by_pattern_sparse_batch does and return a MaskedRows whose
+    # .data and .offsets are in UTF-8 BYTES (a covered k-byte character is k fills): with a tensor the result is byte for
+    # byte, since the layout is the point; tolist() of a sequence of str gives one entry per character again
+    def mask_all(self, haystack: str, fill: str, overlapping: bool = False) -> str: ...
+    def match_mask(self, haystack: str, overlapping: bool = False) -> bytes: ...
+    def mask_all_batch(
+        self, haystacks: Any, fill: str, overlapping: bool = False, *, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> MaskedRows: ...
+    def match_mask_batch(
+        self, haystacks: Any, overlapping: bool = False, *, offsets: Any = None, row_length: Optional[int] = None
+    ) -> MaskedRows: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -196,4 +228,18 @@ class BytesAhoCorasick:
         self, haystacks: Any, weights: Any, overlapping: bool = False, *, keep: str = "unmatched", min_score: int = 1,
         offsets: Any = None, row_length: Optional[int] = None
     ) -> FilteredRows: ...
+    # extension: the cover of a search's matches.  mask_all: the haystack with every byte that a match covers replaced by fill
+    # -- an int in range(256) or a one-byte buffer (an int outside the range or a longer buffer: ValueError; anything else:
+    # TypeError) -- and every other byte where it was; match_mask: 1 where a match covers the byte, else 0.  overlapping=True
+    # (Standard only) covers the union of all occurrences.  The _batch forms take haystacks as
+    # count_by_pattern_sparse_batch does and return a MaskedRows in the input's own layout
+    def mask_all(self, haystack: Buffer, fill: Any, overlapping: bool = False) -> bytes: ...
+    def match_mask(self, haystack: Buffer, overlapping: bool = False) -> bytes: ...
+    def mask_all_batch(
+        self, haystacks: Any, fill: Any, overlapping: bool = False, *, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> MaskedRows: ...
+    def match_mask_batch(
+        self, haystacks: Any, overlapping: bool = False, *, offsets: Any = None, row_length: Optional[int] = None
+    ) -> MaskedRows: ...
     def _info(self) -> dict[str, Any]: ...

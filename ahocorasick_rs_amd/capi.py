@@ -33,6 +33,7 @@ COL_PATTERN, COL_START, COL_END, COL_ROW_OFFSETS = 0, 1, 2, 3  # acx_columns_dat
 TALLY_ROW_OFFSETS, TALLY_PATTERN, TALLY_COUNT = 0, 1, 2  # acx_tally_data / acx_tally_copy (ACX_TALLY_*)
 FILT_ROWS, FILT_OFFSETS, FILT_DATA = 0, 1, 2  # acx_filtered_data / acx_filtered_copy (ACX_FILT_*)
 FILTER_KEEP_MATCHED = 1  # acx_filter* flags (ACX_FILTER_KEEP_MATCHED); 0 keeps the unmatched rows
+MASK_ZERO = 1  # acx_mask* flags (ACX_MASK_ZERO): uncovered bytes become 0 instead of the haystack's own
 ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
 MATCH_DTYPE = np.dtype([("pattern", "<u8"), ("start", "<u8"), ("end", "<u8")])
@@ -247,6 +248,22 @@ def lib() -> ctypes.CDLL:
     L.acx_score_rows_device.argtypes = [vp, u64, vp, u64, vp, u64, vp]
     L.acx_filter_scored.argtypes = [vp, vp, u64, vp, u64, i32, vp, u64, i64, u32, ctypes.POINTER(vp)]
     L.acx_filter_scored_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, vp, u64, i64, u32, ctypes.POINTER(vp)]
+    u8 = ctypes.c_uint8
+    L.acx_mask.argtypes = [vp, vp, u64, vp, u64, i32, u8, u32, ctypes.POINTER(vp)]
+    L.acx_mask_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, u8, u32, ctypes.POINTER(vp)]
+    for name in ("bytes", "rows"):
+        getattr(L, "acx_masked_" + name).argtypes = [vp]
+        getattr(L, "acx_masked_" + name).restype = u64
+    L.acx_masked_on_device.argtypes = [vp]
+    for name in ("data", "offsets"):
+        getattr(L, "acx_masked_" + name).argtypes = [vp]
+        getattr(L, "acx_masked_" + name).restype = vp
+    L.acx_masked_copy.argtypes = [vp, vp]
+    L.acx_masked_copy_offsets.argtypes = [vp, vp]
+    L.acx_free_masked.argtypes = [vp]
+    L.acx_free_masked.restype = None
+    L.acx_mask_host.argtypes = [vp, u64, vp, u64, vp, u64, vp, u8, u32, vp]
+    L.acx_mask_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, u64, vp, u8, u32, vp]
     _lib = L
     return L
 
@@ -906,6 +923,87 @@ def score_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, d_weigh
                                        d_scores or None))
 
 
+class DeviceMasked:
+    """The result of Automaton.mask / mask_device (acx_masked_t): the batch's bytes with every covered byte filled (or the
+    0 / 1 mask), nbytes of them in the input's own layout, and the rows' offsets (rows + 1 int64 words from 0) -- in HBM
+    (on_device) or in host memory.  data() / offsets() copy them out; data_ptr() / offsets_ptr() are where they lie (all
+    wait for the device stage)."""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    @property
+    def on_device(self) -> bool:
+        return bool(lib().acx_masked_on_device(self._h))
+
+    @property
+    def rows(self) -> int:
+        return int(lib().acx_masked_rows(self._h))
+
+    @property
+    def nbytes(self) -> int:
+        return int(lib().acx_masked_bytes(self._h))
+
+    def data_ptr(self) -> int:
+        return lib().acx_masked_data(self._h) or 0
+
+    def offsets_ptr(self) -> int:
+        return lib().acx_masked_offsets(self._h) or 0
+
+    def data(self) -> np.ndarray:
+        out = np.zeros(self.nbytes, dtype=np.uint8)
+        _check(lib().acx_masked_copy(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def offsets(self) -> np.ndarray:
+        out = np.zeros(self.rows + 1, dtype=np.int64)
+        _check(lib().acx_masked_copy_offsets(self._h, out.ctypes.data))
+        return out
+
+    def free(self) -> None:
+        if self._h:
+            lib().acx_free_masked(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def mask_host(hay, offsets: Optional[Sequence[int]], matches, counts: Optional[Sequence[int]], fill: int,
+              flags: int = 0) -> np.ndarray:
+    """acx_mask_host: the definition of the cover on the host, no device involved.  hay: bytes-like; offsets: n + 1 from 0 to
+    len(hay), or None (one row); matches: rows of (pattern, start, end), counts[h] of them row h's (None: one row holds them
+    all), every one clipped to its row.  Returns len(hay) uint8: `fill` where a match covers a byte, elsewhere the haystack's
+    own byte (flags = 0) or 0 (MASK_ZERO).  ValueError (code EINVAL) for a bad flag, offsets that do not rise from 0 to
+    len(hay) or counts that do not sum to the rows."""
+    h = np.frombuffer(bytes(hay), dtype=np.uint8)
+    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    off = None if offsets is None else np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+    n_hay = (1 if c is None else len(c)) if off is None else len(off) - 1
+    if c is not None and off is not None and len(c) != n_hay:
+        raise ValueError("offsets needs len(counts) + 1 entries")
+    out = np.zeros(max(len(h), 1), dtype=np.uint8)
+    pad = np.zeros(1, dtype=np.uint64)  # (an empty batch is still a batch: a non-null counts pointer)
+    _check(lib().acx_mask_host(h.ctypes.data if len(h) else None, len(h), None if off is None else off.ctypes.data, n_hay,
+                               m.ctypes.data if len(m) else None, len(m),
+                               None if c is None else (c.ctypes.data if len(c) else pad.ctypes.data), fill, flags,
+                               out.ctypes.data))
+    return out[:len(h)]
+
+
+def mask_rows_device(d_hay: int, nbytes: int, d_offsets: int, n_hay: int, uniform_len: int, d_records: int, n: int,
+                     d_counts: int, fill: int, flags: int, d_out: int) -> None:
+    """acx_mask_rows_device: the device stage alone -- nbytes at d_hay (any address) cut by n_hay + 1 offsets at d_offsets, by
+    uniform_len or not at all (one row), n records of 24 bytes at d_records, n_hay counts at d_counts -> exactly nbytes at
+    d_out (any address; d_out == d_hay: in place); complete when it returns"""
+    _check(lib().acx_mask_rows_device(d_hay or None, nbytes, d_offsets or None, n_hay, uniform_len, d_records or None, n,
+                                      d_counts or None, fill, flags, d_out or None))
+
+
 def _replaced_bytes(h: int) -> bytes:
     buf = bytearray(int(lib().acx_replaced_len(h)))
     if buf:
@@ -1214,6 +1312,30 @@ class Automaton:
         _check(lib().acx_filter_scored_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
                                               w.ctypes.data, len(w), min_score, flags, ctypes.byref(out)))
         return DeviceFiltered(out.value)
+
+    # ---- cover / mask: every byte a match covers becomes `fill` (acx_mask*)
+    def mask(self, haystacks: Optional[Sequence[bytes]], fill: int, overlapping: bool = False, flags: int = 0, *,
+             single: Optional[bytes] = None) -> DeviceMasked:
+        """host haystacks with their matches' bytes filled, a host result; single=...: one haystack that is no batch
+        (offsets = NULL)"""
+        out = ctypes.c_void_p()
+        if single is not None:
+            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
+            _check(lib().acx_mask(self._h, hb.ctypes.data, len(single), None, 1, int(overlapping), fill, flags,
+                                  ctypes.byref(out)))
+            return DeviceMasked(out.value)
+        hb, hoff = pack(haystacks)
+        _check(lib().acx_mask(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
+                              fill, flags, ctypes.byref(out)))
+        return DeviceMasked(out.value)
+
+    def mask_device(self, d_ptr: int, nbytes: int, fill: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
+                    overlapping: bool = False, flags: int = 0) -> DeviceMasked:
+        """the batch in HBM searched and painted there; the output stays there"""
+        out = ctypes.c_void_p()
+        _check(lib().acx_mask_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
+                                     fill, flags, ctypes.byref(out)))
+        return DeviceMasked(out.value)
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

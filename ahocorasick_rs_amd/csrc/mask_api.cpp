@@ -1,0 +1,253 @@
+// mask_api.cpp -- the cover of a search's matches (mask.hpp): the host form, the device stage behind the find pipeline, the
+// acx_mask* entry points and the accessors of their result.
+#include "mask.hpp"
+#include "replace.hpp"
+#include "result_block.hpp"
+
+using namespace acxh;
+
+// acx_mask / acx_mask_device: the rows' offsets (rows + 1 words from 0) and the output's bytes in ONE block
+// (result_block.hpp).  Device route: the find's records and the stage's temporaries have gone back to the cache behind the
+// stage's kernels.
+struct ACX_HIDDEN acx_masked : ResultBlock {
+    uint64_t rows = 0, bytes = 0;
+    int64_t *offsets = nullptr;
+    uint8_t *data = nullptr;
+
+    int alloc() { // the block (by on_device) and the parts' places in it
+        const Layout L = block_layout({(rows + 1) * 8, bytes});
+        int rc = ResultBlock::alloc(L.bytes);
+        if (rc == ACX_OK) {
+            offsets = (int64_t *)(base() + L.at[0]);
+            data = base() + L.at[1];
+        }
+        return rc;
+    }
+};
+
+namespace {
+
+int check_flags(uint32_t flags) {
+    return flags & ~(uint32_t)ACX_MASK_ZERO ? fail(ACX_EINVAL, "unknown mask flags") : ACX_OK;
+}
+
+// The device stage on stream st: d_out becomes a copy of d_hay (or zeros: ACX_MASK_ZERO; or stays as it is: d_out == d_hay),
+// then the records' bytes are painted.  d_m: n records; d_counts: R.rows words that sum to n (check_sum: they are a caller's
+// -- read back and compared before a kernel reads a record by them).  No record, no row or no byte: nothing beyond the copy
+// or the clear.  *block: the stage's temporaries, one block of the buffer cache -- the caller's to return, behind the
+// stage's kernels.
+int mask_stage(int device, hipStream_t st, const uint8_t *d_hay, const acx::MaskRows &R, const acx_match_t *d_m, uint64_t n,
+               const uint64_t *d_counts, bool check_sum, uint8_t fill, uint32_t flags, uint8_t *d_out, void **block) {
+    if (R.len && d_out != d_hay) {
+        if (flags & ACX_MASK_ZERO) HIPCHK(hipMemsetAsync(d_out, 0, R.len, st));
+        else HIPCHK(hipMemcpyAsync(d_out, d_hay, R.len, hipMemcpyDeviceToDevice, st));
+    }
+    if (!n || !R.rows || !R.len) return ACX_OK;
+    // [rec_off: rows + 1][scan][tiles], every part 256-byte aligned
+    Carver C;
+    const uint64_t o_rec = C.part(R.rows + 1), o_scan = C.part(replace_scan_words(R.rows)), o_tiles = C.part(acx::mask_tile_words(n));
+    HIPCHK(g_bufs.get(block, C.bytes(), device));
+    uint64_t *b = (uint64_t *)*block;
+    int64_t *rec_off = (int64_t *)(b + o_rec);
+    HIPCHK(acx::replace_scan(nullptr, nullptr, d_counts, R.rows, rec_off, b + o_scan, st));
+    if (check_sum) {
+        uint64_t sum = 0;
+        HIPCHK(hipMemcpyAsync(&sum, rec_off + R.rows, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (sum != n) return fail(ACX_EINVAL, "the counts do not sum to the number of records");
+    }
+    HIPCHK(acx::mask_paint(d_m, n, rec_off, R, fill, b + o_tiles, d_out, st));
+    return ACX_OK;
+}
+
+// The device route: the find pipeline as acx_find_device runs it (batch splits and the expansion of copies included, byte
+// offsets: no offset is reported) on d_search, then the stage on the same stream over d_hay -- the caller's own bytes.
+// Returns with the stage in flight (out->done).  d_hay, d_search and G.offsets must stay valid until then.
+int run_mask(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_search, uint64_t len, const Segments &G,
+             int overlapping, uint8_t fill, uint32_t flags, acx_masked_t **out) {
+    *out = nullptr;
+    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
+    const uint64_t rows = segmented ? G.n_hay : 1;
+    acx_masked_t *R = new (std::nothrow) acx_masked_t();
+    if (!R) return fail(ACX_ENOMEM, "out of memory");
+    acx_result *r = nullptr;
+    if (rows && len) { // (an empty batch, or empty rows only: nothing to search)
+        int rc = run_find(a, x, d_search, len, G, overlapping, 0, &r);
+        if (rc != ACX_OK) { delete R; return rc; }
+    }
+    hipStream_t st = x->stream;
+    R->device = a->device;
+    R->on_device = 1;
+    R->rows = rows;
+    R->bytes = len;
+    void *block = nullptr;
+    uint64_t *one_count = nullptr;
+    auto body = [&]() -> int {
+        int rc;
+        if ((rc = R->alloc()) != ACX_OK) return rc;
+        const acx::MaskRows MR{segmented ? G.offsets : nullptr, segmented ? G.uniform_len : 0, rows, len};
+        if (!rows) {
+            HIPCHK(hipMemsetAsync(R->offsets, 0, 8, st));
+        } else {
+            HIPCHK(acx::mask_offsets(MR, R->offsets, st));
+        }
+        const uint64_t *d_counts = nullptr;
+        if (r && (rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
+        return mask_stage(a->device, st, d_hay, MR, r ? r->d_matches : nullptr, r ? r->n : 0, d_counts, false, fill, flags, R->data,
+                          &block);
+    };
+    int rc = retire_find(body(), st, r, R, block, one_count);
+    if (rc != ACX_OK) { acx_free_masked(R); return rc; }
+    *out = R;
+    return ACX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int acx_mask_host(const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, const acx_match_t *m, uint64_t n_m,
+                  const uint64_t *counts, uint8_t fill, uint32_t flags, uint8_t *dst) {
+    int rc = check_flags(flags);
+    if (rc != ACX_OK) return rc;
+    const bool zero = (flags & ACX_MASK_ZERO) != 0;
+    if ((n_m && !m) || (len && (!dst || (!hay && !zero)))) return fail(ACX_EINVAL, "null argument");
+    if (zero && len && dst == hay) return fail(ACX_EINVAL, "ACX_MASK_ZERO cannot be made in place");
+    if (!offsets) {
+        if (n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
+        n_hay = 1;
+    } else {
+        if (offsets[0] != 0 || offsets[n_hay] != len) return fail(ACX_EINVAL, "offsets must rise from 0 to the batch's length");
+        for (uint64_t h = 0; h < n_hay; h++)
+            if (offsets[h + 1] < offsets[h]) return fail(ACX_EINVAL, "offsets must rise from 0 to the batch's length");
+    }
+    if (!counts && n_hay > 1) return fail(ACX_EINVAL, "several haystacks need counts");
+    if (!counts && !n_hay && n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+    uint64_t sum = 0;
+    for (uint64_t h = 0; counts && h < n_hay; h++) {
+        if (counts[h] > n_m - sum) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+        sum += counts[h];
+    }
+    if (counts && sum != n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+    if (len) {
+        if (zero) std::memset(dst, 0, len);
+        else if (dst != hay) std::memmove(dst, hay, len);
+    }
+    uint64_t at = 0;
+    for (uint64_t h = 0; h < n_hay; h++) {
+        const uint64_t b = offsets ? offsets[h] : 0, rowlen = (offsets ? offsets[h + 1] : len) - b;
+        for (const uint64_t end = counts ? at + counts[h] : n_m; at < end; at++) {
+            const uint64_t e = std::min<uint64_t>(m[at].end, rowlen), s = std::min<uint64_t>(m[at].start, e); // clipped to the row
+            if (e > s) std::memset(dst + b + s, fill, e - s);
+        }
+    }
+    return ACX_OK;
+}
+
+int acx_mask(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
+             uint8_t fill, uint32_t flags, acx_masked_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    int rc = check_flags(flags);
+    if (rc == ACX_OK && overlapping) rc = check_overlapping(a); // (the error, no device state)
+    if (rc != ACX_OK) return rc;
+    HostBatch B;
+    if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
+    // the find as it is (the small-call kernel, its resident form, the in-place read, the staged pipeline all still apply):
+    // the records cross the bus, the output never does
+    acx_match_t *m = nullptr;
+    uint64_t nm = 0;
+    std::vector<uint64_t> counts;
+    try {
+        counts.assign(n_hay + 1, 0);
+    } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
+    if (n_hay && len) {
+        rc = offsets ? acx_find_batch(a, B.hay, B.rel.data(), n_hay, overlapping, 0, &m, &nm, counts.data())
+                     : acx_find(a, B.hay, len, overlapping, 0, &m, &nm);
+        if (rc != ACX_OK) return rc;
+        if (!offsets) counts[0] = nm;
+    }
+    acx_masked_t *R = new (std::nothrow) acx_masked_t();
+    if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
+    R->device = a->device;
+    R->rows = n_hay;
+    R->bytes = len;
+    if ((rc = R->alloc()) == ACX_OK) {
+        for (uint64_t h = 0; h <= n_hay; h++) R->offsets[h] = (int64_t)B.rel[h];
+        rc = acx_mask_host(B.hay, len, B.rel.data(), n_hay, m, nm, counts.data(), fill, flags, R->data);
+    }
+    acx_free_matches(m);
+    if (rc != ACX_OK) { acx_free_masked(R); return rc; }
+    *out = R;
+    return ACX_OK;
+}
+
+int acx_mask_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                    uint64_t uniform_len, int overlapping, uint8_t fill, uint32_t flags, acx_masked_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    int rc = check_flags(flags);
+    if (rc != ACX_OK) return rc;
+    // (a case-insensitive handle: the folded copy is searched, the caller's bytes are copied)
+    return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, overlapping, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_mask(a, c, (const uint8_t *)d_hay, d_search, len, G, overlapping, fill, flags, out);
+    });
+}
+
+int acx_mask_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
+                         const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint8_t fill, uint32_t flags,
+                         void *d_out) {
+    int rc = check_flags(flags);
+    if (rc != ACX_OK) return rc;
+    const bool zero = (flags & ACX_MASK_ZERO) != 0;
+    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
+    if (!d_offsets && !uniform_len) n_hay = 1;
+    if (uniform_len && n_hay * uniform_len != len) return fail(ACX_EINVAL, "n_hay * uniform_len is not the batch's length");
+    if ((len && (!d_out || (!d_hay && !zero))) || (n && (!d_records || !d_counts))) return fail(ACX_EINVAL, "null argument");
+    if (zero && len && d_out == d_hay) return fail(ACX_EINVAL, "ACX_MASK_ZERO cannot be made in place");
+    if (!n_hay && n) return fail(ACX_EINVAL, "the counts do not sum to the number of records");
+    if (((uintptr_t)d_offsets | (uintptr_t)d_records | (uintptr_t)d_counts) & 7)
+        return fail(ACX_EINVAL, "offsets, records and counts must be 8-byte aligned");
+    if (!len) return ACX_OK; // (no byte to write)
+    hipPointerAttribute_t at;
+    HIPCHK(hipPointerGetAttributes(&at, d_out));
+    DeviceScope ds(at.device);
+    if (d_offsets) { // where the offsets begin and end; between the two they are the caller's word
+        uint64_t ends[2] = {1, 0};
+        HIPCHK(hipMemcpy(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&ends[1], d_offsets + n_hay, 8, hipMemcpyDeviceToHost));
+        if (ends[0] != 0 || ends[1] != len) return fail(ACX_EINVAL, "offsets must rise from 0 to the batch's length");
+    }
+    void *block = nullptr;
+    const acx::MaskRows R{d_offsets, uniform_len, n_hay, len};
+    rc = mask_stage(at.device, nullptr, (const uint8_t *)d_hay, R, d_records, n, d_counts, true, fill, flags, (uint8_t *)d_out, &block);
+    const hipError_t e = hipStreamSynchronize(nullptr);
+    g_bufs.put(block, at.device);
+    if (rc == ACX_OK && e != hipSuccess) rc = hipfail(e, "hipStreamSynchronize");
+    return rc;
+}
+
+uint64_t acx_masked_rows(const acx_masked_t *m) { return m ? m->rows : 0; }
+uint64_t acx_masked_bytes(const acx_masked_t *m) { return m ? m->bytes : 0; }
+int acx_masked_on_device(const acx_masked_t *m) { return m ? m->on_device : 0; }
+
+const void *acx_masked_data(const acx_masked_t *m) { return m ? m->ptr_after_wait(m->data) : nullptr; }
+const int64_t *acx_masked_offsets(const acx_masked_t *m) { return m ? (const int64_t *)m->ptr_after_wait(m->offsets) : nullptr; }
+
+int acx_masked_copy(const acx_masked_t *m, void *host_dst) {
+    if (!m || (m->bytes && !host_dst)) return fail(ACX_EINVAL, "null argument");
+    return m->copy_out(host_dst, m->data, m->bytes);
+}
+
+int acx_masked_copy_offsets(const acx_masked_t *m, int64_t *host_dst) {
+    if (!m || !host_dst) return fail(ACX_EINVAL, "null argument");
+    return m->copy_out(host_dst, m->offsets, (m->rows + 1) * 8);
+}
+
+void acx_free_masked(acx_masked_t *m) {
+    if (!m) return;
+    m->release();
+    delete m;
+}
+
+} // extern "C"

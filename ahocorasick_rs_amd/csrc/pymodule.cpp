@@ -673,6 +673,32 @@ PyObject *bac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *k
      "[extension] filter_by_score_batch(haystacks, weights, overlapping=False, *, keep='unmatched', min_score=1, "             \
      "offsets=None, row_length=None) -> FilteredRows: filter_batch with the verdict on a row taken from its score -- a row "   \
      "is matched when score_batch's value for it is at least min_score (any int64)."}
+// the cover of a search's matches (defined behind the RowScores below): TEXT = mask_all (the haystack with its matches
+// filled), else match_mask (the 0 / 1 mask); BATCH: the *_batch form
+template <bool TEXT, bool BATCH> PyObject *ac_mask(PyObject *self_, PyObject *args, PyObject *kwargs);
+template <bool TEXT, bool BATCH> PyObject *bac_mask(PyObject *self_, PyObject *args, PyObject *kwargs);
+#define ACX_MASK_METHODS(fn)                                                                                                   \
+    {"mask_all", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<true, false>)), METH_VARARGS | METH_KEYWORDS,   \
+     "[extension] mask_all(haystack, fill, overlapping=False) -> the haystack with every byte that a match covers replaced "   \
+     "by fill and every other byte where it was: fixed-fill redaction.  fill: an int 0..255 or a one-byte buffer "             \
+     "(BytesAhoCorasick), a one-character ASCII str (AhoCorasick: a covered character becomes ONE fill, so the result has "    \
+     "len(haystack) characters).  overlapping=True on a Standard object covers the union of all occurrences."},               \
+    {"match_mask", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false, false>)),                              \
+     METH_VARARGS | METH_KEYWORDS,                                                                                             \
+     "[extension] match_mask(haystack, overlapping=False) -> bytes: 1 where a match covers the haystack's byte "               \
+     "(AhoCorasick: its character), else 0; len(haystack) entries."},                                                         \
+    {"mask_all_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<true, true>)),                            \
+     METH_VARARGS | METH_KEYWORDS,                                                                                             \
+     "[extension] mask_all_batch(haystacks, fill, overlapping=False, *, offsets=None, row_length=None) -> MaskedRows: "        \
+     "mask_all of every row in one call, as one uint8 .data in the input's own layout with its .offsets.  haystacks: a "       \
+     "sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "           \
+     "count_by_pattern_sparse_batch.  A tensor on the automaton's device is searched and painted there and the result "        \
+     "stays there.  AhoCorasick: .data is in UTF-8 bytes (a covered k-byte character is k fills); tolist() gives one fill "    \
+     "per character for a sequence of str and the bytes as they are, decoded, for a tensor."},                                \
+    {"match_mask_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false, true>)),                         \
+     METH_VARARGS | METH_KEYWORDS,                                                                                             \
+     "[extension] match_mask_batch(haystacks, overlapping=False, *, offsets=None, row_length=None) -> MaskedRows: "            \
+     "match_mask of every row in one call: .data is 1 where a match covers the byte, else 0."}
 #define ACX_COLUMNS_METHODS(fn)                                                                                                 \
     {"find_matches_as_columns", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)),                        \
      METH_VARARGS | METH_KEYWORDS,                                                                                              \
@@ -712,6 +738,7 @@ PyMethodDef ac_methods[] = {
     ACX_SPARSE_COUNTS_METHOD(ac_sparse_counts),
     ACX_FILTER_METHOD(ac_filter_batch),
     ACX_SCORE_METHODS(ac_score_batch, ac_filter_by_score_batch),
+    ACX_MASK_METHODS(ac_mask),
     {"_info", ac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -993,9 +1020,10 @@ PyTypeObject *ColumnType = nullptr;
 PyTypeObject *PatternCountsType = nullptr;
 PyTypeObject *FilteredRowsType = nullptr;
 PyTypeObject *RowScoresType = nullptr;
+PyTypeObject *MaskedRowsType = nullptr;
 
-// What a Column's owner -- a MatchColumns, a PatternCounts, a FilteredRows (`which`: ACX_COL_*, ACX_TALLY_*, ACX_FILT_*) or a
-// RowScores (its one part) -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
+// What a Column's owner -- a MatchColumns, a PatternCounts, a FilteredRows (`which`: ACX_COL_*, ACX_TALLY_*, ACX_FILT_*), a
+// RowScores (its one part) or a MaskedRows (`which`: MR_*) -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
 struct OwnerOps {
     int (*on_device)(const void *h);
     const void *(*data)(const void *h, int which); // (waits for the device work)
@@ -1017,6 +1045,12 @@ struct FilteredRowsObject : OwnerObject {
     uint64_t n_src;  // the rows of the batch that was filtered
     bool utf8;       // made by the str class: tolist() decodes
 };
+enum { MR_OFFSETS = 0, MR_DATA = 1 };
+struct MaskedRowsObject : OwnerObject {
+    bool utf8;                 // made by the str class
+    bool text;                 // mask_all_batch: the rows are the input's text; false: match_mask_batch, 0 / 1 bytes
+    std::vector<uint8_t> *src; // a sequence of str with a non-ASCII one: its UTF-8 bytes, for tolist()'s entry per character
+};
 const OwnerOps MC_OPS = {[](const void *h) { return acx_columns_on_device(static_cast<const acx_columns_t *>(h)); },
                          [](const void *h, int w) -> const void * { return acx_columns_data(static_cast<const acx_columns_t *>(h), w); },
                          [](void *h) { acx_free_columns(static_cast<acx_columns_t *>(h)); }};
@@ -1029,7 +1063,14 @@ const OwnerOps FR_OPS = {[](const void *h) { return acx_filtered_on_device(stati
 const OwnerOps RS_OPS = {[](const void *h) { return acx_scores_on_device(static_cast<const acx_scores_t *>(h)); },
                          [](const void *h, int) -> const void * { return acx_scores_data(static_cast<const acx_scores_t *>(h)); },
                          [](void *h) { acx_free_scores(static_cast<acx_scores_t *>(h)); }};
+const OwnerOps MR_OPS = {[](const void *h) { return acx_masked_on_device(static_cast<const acx_masked_t *>(h)); },
+                         [](const void *h, int w) -> const void * {
+                             return w == MR_OFFSETS ? static_cast<const void *>(acx_masked_offsets(static_cast<const acx_masked_t *>(h)))
+                                                    : acx_masked_data(static_cast<const acx_masked_t *>(h));
+                         },
+                         [](void *h) { acx_free_masked(static_cast<acx_masked_t *>(h)); }};
 OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
+acx_masked_t *mr_handle(PyObject *s) { return static_cast<acx_masked_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
 acx_columns_t *mc_handle(PyObject *s) { return static_cast<acx_columns_t *>(owner_of(s)->h); }
 acx_tally_t *pc_handle(PyObject *s) { return static_cast<acx_tally_t *>(owner_of(s)->h); }
 acx_filtered_t *fr_handle(PyObject *s) { return static_cast<acx_filtered_t *>(owner_of(s)->h); }
@@ -1063,7 +1104,7 @@ struct ColumnObject {
     PyObject *owner;
     int which;
     int64_t len;
-    int elem;        // 0: int64 words; 1: uint8 bytes (a FilteredRows' data)
+    int elem;        // 0: int64 words; 1: uint8 bytes (a FilteredRows' or a MaskedRows' data)
 };
 
 PyObject *new_column(PyObject *owner, int which, uint64_t len, int elem = 0) {
@@ -1278,7 +1319,7 @@ PyType_Slot col_slots[] = {
     {Py_sq_length, reinterpret_cast<void *>(col_len)},
     {Py_bf_getbuffer, reinterpret_cast<void *>(col_getbuffer)},
     {Py_tp_doc, const_cast<char *>(
-        "One int64 column of a MatchColumns, a PatternCounts or a RowScores, or one part of a FilteredRows (int64; its data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
+        "One int64 column of a MatchColumns, a PatternCounts or a RowScores, or one part of a FilteredRows or a MaskedRows (int64; their data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
         "copy) and, in host memory, the buffer protocol (format 'q', or 'B' for uint8; read-only).")},
     {0, nullptr},
 };
@@ -1908,6 +1949,225 @@ PyObject *bac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *k
     return scored_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false, true);
 }
 
+// ---------------------------------------------------------------------------
+// the cover of a search's matches: mask_all / match_mask and their _batch forms -> str / bytes / MaskedRows (acx_mask /
+// acx_mask_device).  A MaskedRows owns the acx_masked_t; .data (uint8) and .offsets (int64) are Columns with the lifetime
+// chain of a MatchColumns' columns.
+// ---------------------------------------------------------------------------
+
+// fill: an int 0..255 or a one-byte buffer (the bytes class), a one-character ASCII str (the str class: the output stays
+// valid UTF-8); sets the exception
+bool parse_fill(PyObject *fill, bool utf8, uint8_t *out) {
+    if (utf8) {
+        if (!PyUnicode_Check(fill)) {
+            PyErr_Format(PyExc_TypeError, "argument 'fill': '%.100s' object cannot be converted to 'PyString'", Py_TYPE(fill)->tp_name);
+            return false;
+        }
+        if (PyUnicode_GET_LENGTH(fill) != 1 || PyUnicode_READ_CHAR(fill, 0) > 0x7F) {
+            PyErr_SetString(PyExc_ValueError, "fill must be one ASCII character");
+            return false;
+        }
+        *out = (uint8_t)PyUnicode_READ_CHAR(fill, 0);
+        return true;
+    }
+    if (PyLong_Check(fill) && !PyBool_Check(fill)) {
+        int overflow = 0;
+        const long long v = PyLong_AsLongLongAndOverflow(fill, &overflow);
+        if (v == -1 && !overflow && PyErr_Occurred()) return false;
+        if (overflow || v < 0 || v > 255) {
+            PyErr_SetString(PyExc_ValueError, "fill must be in range(256)");
+            return false;
+        }
+        *out = (uint8_t)v;
+        return true;
+    }
+    if (PyUnicode_Check(fill) || PyBool_Check(fill) || !PyObject_CheckBuffer(fill)) {
+        PyErr_Format(PyExc_TypeError, "argument 'fill': an int in range(256) or a one-byte buffer is needed, not '%.100s'",
+                     Py_TYPE(fill)->tp_name);
+        return false;
+    }
+    Py_buffer v;
+    if (!get_bytes_view(fill, &v)) return false;
+    const bool one = v.len == 1;
+    if (one) *out = *static_cast<const uint8_t *>(v.buf);
+    PyBuffer_Release(&v);
+    if (!one) PyErr_SetString(PyExc_ValueError, "fill must be one byte");
+    return one;
+}
+
+// One entry per CHARACTER of a str haystack.  row: what the library made of hay's UTF-8 bytes, one entry per byte.  text: the
+// entries of a covered character's continuation bytes are dropped (fill is ASCII, so a continuation byte that differs from
+// the haystack's is a covered one) and the rest is decoded; else (the 0 / 1 mask) the entry of every continuation byte is.
+PyObject *per_character(const uint8_t *hay, const uint8_t *row, size_t len, bool text) {
+    std::string s;
+    s.reserve(len);
+    for (size_t i = 0; i < len; i++) {
+        const bool cont = (hay[i] & 0xC0) == 0x80;
+        if (cont && (!text || row[i] != hay[i])) continue;
+        s.push_back((char)row[i]);
+    }
+    return text ? PyUnicode_DecodeUTF8(s.data(), (Py_ssize_t)s.size(), nullptr) : PyBytes_FromStringAndSize(s.data(), (Py_ssize_t)s.size());
+}
+
+// the two argument checks and the per-character rule without an automaton (the CPU tests; module functions)
+PyObject *mod_mask_fill(PyObject *, PyObject *args) {
+    PyObject *fill = nullptr;
+    int text = 0;
+    if (!PyArg_ParseTuple(args, "Op:_mask_fill", &fill, &text)) return nullptr;
+    uint8_t f = 0;
+    if (!parse_fill(fill, text != 0, &f)) return nullptr;
+    return PyLong_FromLong(f);
+}
+PyObject *mod_mask_per_character(PyObject *, PyObject *args) {
+    PyObject *hay = nullptr;
+    Py_buffer row;
+    int text = 0;
+    if (!PyArg_ParseTuple(args, "Uy*p:_mask_per_character", &hay, &row, &text)) return nullptr;
+    Py_ssize_t len = 0;
+    const char *p = PyUnicode_AsUTF8AndSize(hay, &len);
+    PyObject *out = nullptr;
+    if (p && row.len != len) PyErr_SetString(PyExc_ValueError, "row needs one entry per UTF-8 byte of haystack");
+    else if (p) out = per_character(reinterpret_cast<const uint8_t *>(p), static_cast<const uint8_t *>(row.buf), (size_t)len, text != 0);
+    PyBuffer_Release(&row);
+    return out;
+}
+
+void mr_dealloc(PyObject *self) {
+    delete static_cast<MaskedRowsObject *>(owner_of(self))->src;
+    owner_dealloc(self);
+}
+PyObject *mr_get_data(PyObject *s, void *) { return new_column(s, MR_DATA, acx_masked_bytes(mr_handle(s)), 1); }
+PyObject *mr_get_offsets(PyObject *s, void *) { return new_column(s, MR_OFFSETS, acx_masked_rows(mr_handle(s)) + 1); }
+PyObject *mr_get_nbytes(PyObject *s, void *) { return PyLong_FromUnsignedLongLong(acx_masked_bytes(mr_handle(s))); }
+Py_ssize_t mr_len(PyObject *s) { return (Py_ssize_t)acx_masked_rows(mr_handle(s)); }
+
+// the rows: list[str] for mask_all_batch of the str class (a sequence of str: one entry per character), else list[bytes]
+PyObject *mr_tolist(PyObject *self_, PyObject *) {
+    acx_masked_t *m = mr_handle(self_);
+    const MaskedRowsObject *o = static_cast<MaskedRowsObject *>(owner_of(self_));
+    const uint64_t k = acx_masked_rows(m), nb = acx_masked_bytes(m);
+    std::vector<int64_t> off((size_t)k + 1);
+    std::vector<uint8_t> data((size_t)nb + 1);
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = acx_masked_copy_offsets(m, off.data());
+    if (rc == ACX_OK) rc = acx_masked_copy(m, data.data());
+    Py_END_ALLOW_THREADS
+    if (rc != ACX_OK) return raise_acx(rc);
+    PyObject *list = PyList_New((Py_ssize_t)k);
+    for (uint64_t i = 0; list && i < k; i++) {
+        const uint8_t *b = data.data() + off[(size_t)i];
+        const Py_ssize_t n = (Py_ssize_t)(off[(size_t)i + 1] - off[(size_t)i]);
+        PyObject *it = o->src ? per_character(o->src->data() + off[(size_t)i], b, (size_t)n, o->text)
+                              : o->utf8 && o->text ? PyUnicode_DecodeUTF8(reinterpret_cast<const char *>(b), n, nullptr)
+                                                   : PyBytes_FromStringAndSize(reinterpret_cast<const char *>(b), n);
+        if (!it) { Py_CLEAR(list); break; }
+        PyList_SET_ITEM(list, (Py_ssize_t)i, it);
+    }
+    return list;
+}
+
+PyGetSetDef mr_getset[] = {
+    {"data", mr_get_data, nullptr, "Column of nbytes uint8 entries: the rows back to back, in the input's own layout", nullptr},
+    {"offsets", mr_get_offsets, nullptr, "Column of len(self) + 1 int64 entries from 0: row i is data[offsets[i]:offsets[i + 1]]", nullptr},
+    {"device", owner_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {"nbytes", mr_get_nbytes, nullptr, "the size of data: the input's", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+PyMethodDef mr_methods[] = {
+    {"tolist", mr_tolist, METH_NOARGS,
+     "the rows as list[str] (mask_all_batch of the str class) or list[bytes] (copies device parts to the host); for a sequence "
+     "of str one entry per character"},
+    {nullptr, nullptr, 0, nullptr},
+};
+PyType_Slot mr_slots[] = {
+    {Py_tp_dealloc, reinterpret_cast<void *>(mr_dealloc)},
+    {Py_tp_methods, mr_methods},
+    {Py_tp_getset, mr_getset},
+    {Py_sq_length, reinterpret_cast<void *>(mr_len)},
+    {Py_tp_doc, const_cast<char *>(
+        "The result of mask_all_batch / match_mask_batch: .data is a uint8 Column of nbytes entries in the input's own layout "
+        "-- fill (or 1) where a match covers a byte -- and .offsets an int64 Column of len(self) + 1 entries from 0, where the "
+        "search ran (.device); len(self) is the number of rows.  For a tensor input the caller's own offsets cut .data as well.")},
+    {0, nullptr},
+};
+
+// mask_all / match_mask / mask_all_batch / match_mask_batch of both classes: utf8 = the str class (no offset is reported:
+// the search is on bytes), text = the mask_all forms
+PyObject *mask_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool utf8, bool text, bool batch) {
+    static const char *kw_t[] = {"haystack", "fill", "overlapping", nullptr};
+    static const char *kw_m[] = {"haystack", "overlapping", nullptr};
+    static const char *kw_tb[] = {"haystacks", "fill", "overlapping", "offsets", "row_length", nullptr};
+    static const char *kw_mb[] = {"haystacks", "overlapping", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *fill_o = nullptr, *ov = nullptr, *offsets = nullptr, *row_length = nullptr;
+    int overlapping = 0;
+    if (batch ? (text ? !PyArg_ParseTupleAndKeywords(args, kwargs, "OO|O$OO:mask_all_batch", const_cast<char **>(kw_tb), &hay, &fill_o,
+                                                     &ov, &offsets, &row_length)
+                      : !PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$OO:match_mask_batch", const_cast<char **>(kw_mb), &hay, &ov,
+                                                     &offsets, &row_length))
+              : (text ? !PyArg_ParseTupleAndKeywords(args, kwargs, "OO|O:mask_all", const_cast<char **>(kw_t), &hay, &fill_o, &ov)
+                      : !PyArg_ParseTupleAndKeywords(args, kwargs, "O|O:match_mask", const_cast<char **>(kw_m), &hay, &ov)))
+        return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    uint8_t fill = 1;
+    if (text && !parse_fill(fill_o, utf8, &fill)) return nullptr;
+    const uint32_t flags = text ? 0 : ACX_MASK_ZERO;
+    acx_masked_t *m = nullptr;
+    int rc;
+    if (!batch) {
+        const char *p = nullptr;
+        Py_ssize_t len = 0;
+        Py_buffer v;
+        if (utf8 ? !str_view(hay, &p, &len) : !get_bytes_view(hay, &v)) return nullptr;
+        if (!utf8) { p = static_cast<const char *>(v.buf); len = v.len; }
+        Py_BEGIN_ALLOW_THREADS
+        rc = acx_mask(a, reinterpret_cast<const uint8_t *>(p), (uint64_t)len, nullptr, 1, overlapping, fill, flags, &m);
+        Py_END_ALLOW_THREADS
+        PyObject *out = nullptr;
+        if (rc != ACX_OK) raise_acx(rc);
+        else {
+            const uint8_t *row = static_cast<const uint8_t *>(acx_masked_data(m)); // (a host result)
+            out = !row ? raise_acx(ACX_EDEVICE)
+                  : utf8 ? per_character(reinterpret_cast<const uint8_t *>(p), row, (size_t)len, text)
+                         : PyBytes_FromStringAndSize(reinterpret_cast<const char *>(row), len);
+        }
+        acx_free_masked(m);
+        if (!utf8) PyBuffer_Release(&v);
+        return out;
+    }
+    const int device = acx_automaton_device(a);
+    BatchInput in;
+    if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
+    rc = batch_dispatch(
+        device, in,
+        [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+            return acx_mask(a, p, len, off, rows, overlapping, fill, flags, &m);
+        },
+        [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_length) {
+            return acx_mask_device(a, p, len, d_off, rows, row_length, overlapping, fill, flags, &m);
+        });
+    if (rc == BAD_OFFSETS) return nullptr;
+    if (rc != ACX_OK) return raise_acx(rc);
+    std::vector<uint8_t> *src = nullptr;
+    if (utf8 && !in.tensor && !in.seq.all_ascii) {
+        src = new (std::nothrow) std::vector<uint8_t>(std::move(in.seq.blob));
+        if (!src) { acx_free_masked(m); return PyErr_NoMemory(); }
+    }
+    OwnerObject *o = new_owner(MaskedRowsType, &MR_OPS, m, device);
+    if (!o) { delete src; return nullptr; }
+    static_cast<MaskedRowsObject *>(o)->utf8 = utf8;
+    static_cast<MaskedRowsObject *>(o)->text = text;
+    static_cast<MaskedRowsObject *>(o)->src = src;
+    return reinterpret_cast<PyObject *>(o);
+}
+
+template <bool TEXT, bool BATCH> PyObject *ac_mask(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return mask_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, true, TEXT, BATCH);
+}
+template <bool TEXT, bool BATCH> PyObject *bac_mask(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return mask_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false, TEXT, BATCH);
+}
+
 // device-resident search -> list of tuples (the records come back with ONE D2H copy of the result)
 PyObject *find_on_device(acx_automaton_t *a, const uint8_t *d_hay, uint64_t len, int overlapping) {
     acx_result_t *r = nullptr;
@@ -2041,6 +2301,7 @@ PyMethodDef bac_methods[] = {
     ACX_SPARSE_COUNTS_METHOD(bac_sparse_counts),
     ACX_FILTER_METHOD(bac_filter_batch),
     ACX_SCORE_METHODS(bac_score_batch, bac_filter_by_score_batch),
+    ACX_MASK_METHODS(bac_mask),
     {"_info", bac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -2055,10 +2316,19 @@ PyType_Slot bac_slots[] = {
     {0, nullptr},
 };
 
+PyMethodDef module_methods[] = {
+    {"_mask_fill", mod_mask_fill, METH_VARARGS,
+     "_mask_fill(fill, text) -> int: the fill byte mask_all takes from `fill` (text: the str class's rule), or its error"},
+    {"_mask_per_character", mod_mask_per_character, METH_VARARGS,
+     "_mask_per_character(haystack, row, text) -> str | bytes: a str haystack's masked row (one entry per UTF-8 byte) as "
+     "mask_all (text) / match_mask return it: one entry per character"},
+    {nullptr, nullptr, 0, nullptr},
+};
+
 PyModuleDef moduledef = {
     PyModuleDef_HEAD_INIT, "ahocorasick_rs",
     "MI355X-native Aho-Corasick matcher behind the ahocorasick_rs API (HIP kernels via libacx_hip.so).",
-    -1, nullptr, nullptr, nullptr, nullptr, nullptr,
+    -1, module_methods, nullptr, nullptr, nullptr, nullptr,
 };
 
 } // namespace
@@ -2090,15 +2360,18 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, fr_slots};
     PyType_Spec rs_spec = {"ahocorasick_rs.RowScores", sizeof(OwnerObject), 0,
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, rs_slots};
+    PyType_Spec mr_spec = {"ahocorasick_rs.MaskedRows", sizeof(MaskedRowsObject), 0,
+                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, mr_slots};
+    MaskedRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mr_spec));
     FilteredRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&fr_spec));
     RowScoresType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&rs_spec));
     MatchColumnsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mc_spec));
     ColumnType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&col_spec));
     PatternCountsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&pc_spec));
-    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType || !RowScoresType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
-    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType, RowScoresType}) { // (the module holds one reference, the globals the other)
+    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType || !RowScoresType || !MaskedRowsType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
+    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType, RowScoresType, MaskedRowsType}) { // (the module holds one reference, the globals the other)
         Py_INCREF(tp);
-        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : tp == RowScoresType ? "RowScores" : "MatchColumns",
+        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : tp == RowScoresType ? "RowScores" : tp == MaskedRowsType ? "MaskedRows" : "MatchColumns",
                                reinterpret_cast<PyObject *>(tp)) < 0) {
             Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);
             return nullptr;

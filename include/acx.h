@@ -38,6 +38,9 @@ extern "C" {
  *     fifth addendum (additive as well): acx_score / acx_score_device / acx_score_host / acx_score_rows_device, the
  *     acx_scores_t accessors (acx_scores_rows, _on_device, _data, _copy, acx_free_scores), acx_filter_scored /
  *     acx_filter_scored_device;
+ *     sixth addendum (additive as well): acx_mask / acx_mask_device / acx_mask_host / acx_mask_rows_device, ACX_MASK_ZERO,
+ *     the acx_masked_t accessors (acx_masked_bytes, _rows, _on_device, _data, _offsets, _copy, _copy_offsets,
+ *     acx_free_masked);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -615,6 +618,62 @@ int acx_filter_scored(acx_automaton_t *a, const uint8_t *hay, uint64_t len, cons
 int acx_filter_scored_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
                              uint64_t uniform_len, int overlapping, const int32_t *weights /* host */, uint64_t n_weights,
                              int64_t min_score, uint32_t flags, acx_filtered_t **out);
+
+/* ---- cover / mask: every byte that a match covers becomes one fill byte, every other byte stays where it was -- fixed-fill
+ * redaction, a highlight map, a loss mask -- as a same-length output in the caller's own layout.  For a batch of rows, row h
+ * = hay[off[h] .. off[h + 1]) and M_h = the matches acx_find_batch / acx_find_device reports for row h with the same
+ * `overlapping`: byte i of row h is COVERED iff some m in M_h has m.start <= i < m.end (an empty match covers nothing), and
+ *   out[off[h] + i] = covered ? fill : (flags & ACX_MASK_ZERO ? 0 : hay[off[h] + i])
+ * -- exactly len bytes.  flags = 0 is the haystack with its matches blanked; ACX_MASK_ZERO with fill = 1 is the 0 / 1 mask;
+ * any other flag bit: ACX_EINVAL.  The uncovered bytes are the caller's own (a case-insensitive handle matches on a folded
+ * copy and writes the unfolded bytes).  Every match kind; an overlapping search on a Standard handle covers the union of all
+ * occurrences, one on a non-Standard handle fails with ACX_EOVERLAP before any device state is touched, and copies of a
+ * pattern cover the same bytes once.  No offset is reported, so the search runs on bytes whatever the caller's strings are
+ * (a str set's matches cover whole characters anyway).
+ * acx_mask: host haystacks (offsets: n_hay + 1, or null: one haystack of len bytes -- a batch of one row), a host result.
+ * acx_find / acx_find_batch runs as it is and chooses its own route; acx_mask_host then paints a copy of the caller's bytes:
+ * the records cross the bus, the output never does (painting in HBM and sending len bytes back wins only for inputs denser
+ * than one match per 24 bytes; the choice is not measured).
+ * acx_mask_device: acx_find_device's pipeline (d_offsets / uniform_len as there; neither: a batch of one row), then the
+ * device stage on the same stream -- a device-to-device copy (or a clear) and one pass over the records; the result stays in
+ * HBM on the automaton's device.  The call may return with the stage in flight: acx_masked_data / _offsets / _copy wait for
+ * it.  d_hay and d_offsets must stay valid until then.
+ * The result carries the rows' offsets beside the bytes: rows + 1 int64 words from 0 to len, in the same memory.
+ * An empty part still has a valid, non-null address. */
+#define ACX_MASK_ZERO 1
+typedef struct acx_masked acx_masked_t;
+int acx_mask(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
+             int overlapping, uint8_t fill, uint32_t flags, acx_masked_t **out);
+int acx_mask_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                    uint64_t uniform_len, int overlapping, uint8_t fill, uint32_t flags, acx_masked_t **out);
+uint64_t acx_masked_bytes(const acx_masked_t *m);    /* len: the output's bytes                               */
+uint64_t acx_masked_rows(const acx_masked_t *m);     /* the rows of the batch                                 */
+int acx_masked_on_device(const acx_masked_t *m);     /* 1: the parts are in HBM, 0: host memory               */
+/* host or device pointer by acx_masked_on_device (the bytes; the offsets: rows + 1 int64 words); waits for the device stage.
+ * NULL: the wait failed.  Valid until acx_free_masked. */
+const void *acx_masked_data(const acx_masked_t *m);
+const int64_t *acx_masked_offsets(const acx_masked_t *m);
+int acx_masked_copy(const acx_masked_t *m, void *host_dst);
+int acx_masked_copy_offsets(const acx_masked_t *m, int64_t *host_dst);
+void acx_free_masked(acx_masked_t *m);
+/* the cover itself.  Both take records from a caller, so both CLIP: a record's [start, end) is cut to its row first (end' =
+ * min(end, row length), start' = min(start, end')) -- no record writes outside its own row, whatever it says.
+ * acx_mask_host: host memory, no device needed -- the definition above inside the library; m: n_m matches, all haystacks
+ * behind one another, counts[h] of them haystack h's (ACX_EINVAL when they do not sum to n_m), or counts = NULL: one row
+ * holds them all; offsets: n_hay + 1 from 0 to len (ACX_EINVAL when they do not rise from 0 to len), or null: one row of len
+ * bytes; dst: len bytes (dst == hay: in place, not with ACX_MASK_ZERO).
+ * acx_mask_rows_device: the device stage alone on a caller's bytes, offsets (or uniform_len, or neither: one row), records
+ * and counts (they must sum to n: checked before a kernel reads a record by them) in HBM on one device; needs no automaton;
+ * synchronous: d_out is complete when it returns.  It writes exactly len bytes at d_out and nothing beyond them -- there is
+ * no round-up.  No pointer needs any alignment except the word arrays (offsets, records, counts: 8 bytes).  d_out == d_hay:
+ * in place -- no copy, only the covered bytes are written; not together with ACX_MASK_ZERO (ACX_EINVAL).  Any other overlap
+ * of d_hay and d_out is the caller's error: it is not detected.  len = 0, n_hay = 0 and n = 0 launch nothing beyond the copy
+ * or the clear (and with n = 0 the counts are not read). */
+int acx_mask_host(const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, const acx_match_t *m,
+                  uint64_t n_m, const uint64_t *counts /* NULL: one row */, uint8_t fill, uint32_t flags, uint8_t *dst);
+int acx_mask_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
+                         const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint8_t fill, uint32_t flags,
+                         void *d_out);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
