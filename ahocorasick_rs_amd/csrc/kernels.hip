@@ -43,6 +43,7 @@
 #include <hip/hip_ext.h>
 
 #include "automaton.hpp"
+#include "k1b_bounds.hpp"
 #include "kernels.hpp"
 
 namespace acx {
@@ -992,6 +993,15 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
     // nxtL = the 8 bytes that follow the tile (lane 63's look-ahead), read by all
     // lanes from one address.
     const uint64_t last_block = total16 - 16;
+    // The tile loop's wave-uniform tests are made on 32-bit TILE INDICES (tiles < 2^32: launch_prefilter), against
+    // bounds derived once: the scalar unit orders 32-bit words (s_cmp_lt_u32) but not 64-bit ones, so the same tests on
+    // byte offsets were v_cmp_*_u64 on copies of scalar registers, several per tile.
+    const uint32_t tile0 = (uint32_t)gw, tstep = (uint32_t)nw; // the wave's first tile, its stride
+    const uint32_t tiles32 = (uint32_t)ntiles;
+    const uint32_t t_int_lo = lead ? 1u : 0u;                      // interior tiles: tbase >= lead ...
+    const uint32_t t_int_hi = (uint32_t)(last_start >> TILE_BITS); // ... and tbase + tile_bytes <= last_start
+    const uint32_t t_full = (uint32_t)(last_block >> TILE_BITS);   // tiles below it end at or in front of the stream's last 16-byte block
+    const uint32_t t_inside = total >= 16 ? (uint32_t)((total - 16) >> TILE_BITS) : 0u; // ... end 16 bytes inside the stream
     // (ONE set of registers for the tile: the prefetch of the wave's next tile is issued when level 1
     // has finished with the rows and lands in the same registers -- round 2 kept a second set and copied)
     u32x4 nxt0, nxt1, nxt2, nxt3; // the tile's rows ("nxt": loaded one iteration ahead)
@@ -1001,7 +1011,7 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
 #define K1B_LOAD16(PTR) (*(const u32x4 *)(PTR))
 #define K1B_ISSUE_ROW(DST, TILE, R)                                                              \
     {                                                                                            \
-        uint64_t off_ = (TILE) * tile_bytes + (uint64_t)(R) * 1024 + lane * 16;                  \
+        uint64_t off_ = (uint64_t)(TILE) * tile_bytes + (uint64_t)(R) * 1024 + lane * 16;        \
         DST = K1B_LOAD16(hay + (off_ < last_block ? off_ : last_block));                         \
     }
     // The tile index is wave-uniform (SGPRs): a tile that lies wholly inside the stream -- all
@@ -1009,8 +1019,8 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
     // VALU address arithmetic; both branches issue the same five loads.
 #define K1B_ISSUE_TILE(TILE)                                                                     \
     {                                                                                            \
-        const uint64_t tb_ = (TILE) * tile_bytes;                                                \
-        if (tb_ + tile_bytes <= last_block) {                                                    \
+        const uint64_t tb_ = (uint64_t)(TILE) * tile_bytes;                                      \
+        if ((TILE) < t_full) {                                                                   \
             const uint8_t *tp_ = hay + tb_ + lane * 16;                                          \
             nxt0 = K1B_LOAD16(tp_); nxt1 = K1B_LOAD16(tp_ + 1024);                               \
             nxt2 = K1B_LOAD16(tp_ + 2048); nxt3 = K1B_LOAD16(tp_ + 3072);                        \
@@ -1022,7 +1032,7 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
             nxtL = *(const uint2 *)(hay + (off_ < last_block ? off_ : last_block));              \
         }                                                                                        \
     }
-    K1B_ISSUE_TILE(gw)
+    K1B_ISSUE_TILE(tile0)
 
     // ---- level-2 pipeline (one entry per lane per stage).  A *batch* is up to 64 survivors of one
     // tile.  Q1 collects the survivors of the tile under compaction (stage A); advance() moves every
@@ -1166,7 +1176,7 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
             // ---- stage A -> B: fetch the 16-byte windows of the queued survivors
             if (q1c) {
                 // (wave-uniform: every window of a tile that ends 16 bytes inside the stream is one unaligned load)
-                const bool inside = ((uint64_t)tileQ + 1) * tile_bytes + 16 <= total;
+                const bool inside = tileQ < t_inside;
                 if (lane < q1c) {
                     offB = q1[lane];
                     const uint64_t p_ = (uint64_t)tileQ * tile_bytes + (offB & OFFMASK) - lead;
@@ -1198,35 +1208,42 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
     // behind an s_waitcnt vmcnt(0) at the end of every advance().  Out of the tree; profiles/r05/exp_pair_*.)
     constexpr uint64_t DRAIN = BIG && !STAGED ? 4 : 3; // extra iterations that empty the pipeline (A -> B -> C; BIG: A -> B -> M -> C; STAGED: A -> M -> C)
 
-    for (uint64_t tile = gw; tile < ntiles + DRAIN * nw; tile += nw) {
+    const uint32_t tend = (uint32_t)(ntiles + DRAIN * nw);
+    for (uint32_t tile = tile0; tile < tend; tile += tstep) {
         // Everything loaded during the previous iteration (the tile prefetch and the level-2
         // windows / slots) is consumed from here on.  Passing the tile through an empty asm makes
         // the compiler wait for those loads HERE, not with a vmcnt(0) somewhere in the middle of level 1.
-        asm volatile("" : "+v"(nxt0), "+v"(nxt1), "+v"(nxt2), "+v"(nxt3), "+v"(nxtL.x), "+v"(nxtL.y));
+        // (nxtL.y: bytes 20 .. 23 behind the tile, which only BIG's windows reach.  The other instantiations never read
+        // it, and left out of this asm it is dead: the compiler narrows their load of nxtL to the one dword)
+        if (BIG) asm volatile("" : "+v"(nxt0), "+v"(nxt1), "+v"(nxt2), "+v"(nxt3), "+v"(nxtL.x), "+v"(nxtL.y));
+        else asm volatile("" : "+v"(nxt0), "+v"(nxt1), "+v"(nxt2), "+v"(nxt3), "+v"(nxtL.x));
         // the previous tile's remaining survivors: its last batch (possibly empty)
-        advance((uint32_t)(tile - nw), tile >= gw + nw && tile - nw < ntiles ? 2u : 0u);
-        if (tile >= ntiles) continue;
+        advance(tile - tstep, tile != tile0 && tile - tstep < tiles32 ? 2u : 0u);
+        if (tile >= tiles32) continue;
 
         // ---- level 1 on this tile
-        const uint64_t tbase = tile * tile_bytes;
+        const uint64_t tbase = (uint64_t)tile * tile_bytes;
         uint32_t mrow0 = 0, mrow1 = 0, mrow2 = 0, mrow3 = 0;
-        // a register whose LOW byte is byte k of the lane's 24-byte view: an odd window,
-        // a dword, or a dword shifted by 16 (only bits [4:0] are consumed)
+        // a register whose LOW byte is byte k of the lane's 20-byte view: an odd window,
+        // a dword, or a dword shifted by 16 (only bits [4:0] are consumed).  Bytes 17 and 19 start no
+        // gram: they are shifted out of their dword, not cut out of a window that would need the dword
+        // behind it (>> 24 becomes a byte select of the shift that consumes it, like the >> 16; >> 8 is
+        // one shift, as the window was) -- the row needs ONE look-ahead dword, bytes 16 .. 19
 #define K1B_SCHED_BARRIER __builtin_amdgcn_sched_barrier(0);
-#define K1B_BYTE_REG(k) (((k) & 1) ? w_[(k)] : (((k) & 2) ? d_[(k) >> 2] >> 16 : d_[(k) >> 2]))
-#define K1B_ROW(RI, VR, RX, RY, MROW)                                                            \
+#define K1B_BYTE_REG(k) ((k) == 17 ? d_[4] >> 8 : (k) == 19 ? d_[4] >> 24 :                      \
+                         ((k) & 1) ? w_[(k)] : (((k) & 2) ? d_[(k) >> 2] >> 16 : d_[(k) >> 2]))
+#define K1B_ROW(VR, RX, MROW)                                                                \
         {                                                                                        \
-            /* look-ahead dwords: lane l+1's first two dwords by DPP wave_shl:1 (one VALU op   */\
-            /* each, no LDS); lane 63 takes them from the next row's lane 0 (scalar)          */\
-            uint32_t nx_ = __builtin_amdgcn_update_dpp(0u, VR.x, 0x130, 0xf, 0xf, true);         \
-            uint32_t ny_ = __builtin_amdgcn_update_dpp(0u, VR.y, 0x130, 0xf, 0xf, true);         \
-            const uint32_t rx_ = (RX), ry_ = (RY); /* evaluated by ALL lanes (readfirstlane) */  \
-            uint32_t d4_ = lane == 63 ? rx_ : nx_, d5_ = lane == 63 ? ry_ : ny_;                 \
-            uint32_t d_[6] = {VR.x, VR.y, VR.z, VR.w, d4_, d5_};                                 \
+            /* look-ahead dword: lane l+1's first dword by DPP wave_shl:1 (no LDS).  Lane 63    */\
+            /* has no source lane, and without bound_ctrl a DPP move leaves such a lane its OLD */\
+            /* value: the next row's lane 0 (scalar) -- no select on lane == 63                */\
+            const uint32_t rx_ = (RX); /* evaluated by ALL lanes (readfirstlane) */              \
+            const uint32_t d4_ = __builtin_amdgcn_update_dpp(rx_, VR.x, 0x130, 0xf, 0xf, false); \
+            uint32_t d_[5] = {VR.x, VR.y, VR.z, VR.w, d4_};                                      \
             /* w_[j] (odd j): the 4 bytes starting at byte j (4-gram of pair j-1; its low     */\
             /* byte is also the Y signature byte of pair j-5)                                 */\
-            uint32_t w_[20];                                                                     \
-            _Pragma("unroll") for (int j = 1; j < 20; j += 2)                                    \
+            uint32_t w_[16];                                                                     \
+            _Pragma("unroll") for (int j = 1; j < 16; j += 2)                                    \
                 w_[j] = __builtin_amdgcn_alignbyte(d_[(j >> 2) + 1], d_[j >> 2], j & 3);         \
             uint32_t m_ = 0, mg_ = 0;                                                            \
             /* (round 5: the mask that aligns the address to the 8-byte entries is one instruction */\
@@ -1258,24 +1275,15 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
                 m_ = __builtin_amdgcn_alignbit(e_.x >> (bx_ & 31), m_, 1); /* position j:   X, byte j   */ \
                 m_ = __builtin_amdgcn_alignbit(e_.y >> (by_ & 31), m_, 1); /* position j+1: Y, byte j+Q */ \
             }                                                                                    \
-            m_ = (m_ & mg_) >> 16;                                                               \
-            if (!interior) { /* wave-uniform: a scalar branch */                                 \
-                const uint64_t p0_ = tbase + (uint64_t)(RI) * 1024 + lane * 16;                  \
-                uint32_t keep_ = 0;                                                              \
-                _Pragma("unroll") for (int j = 0; j < 16; j++)                                   \
-                    if (any_start && p0_ + j >= lead && p0_ + j <= last_start) keep_ |= 1u << j; \
-                m_ &= keep_;                                                                     \
-            }                                                                                    \
-            MROW = m_;                                                                           \
+            MROW = (m_ & mg_) >> 16;                                                             \
         }
         // BIG: position j passes iff the gram at j + 1 vouches for byte j in front of it (X) AND the
         // gram at j vouches for byte j + 4 behind it (Y); one table row per gram j = 0 .. 16
-#define K1B_ROW_BIG(RI, VR, RX, RY, MROW)                                                        \
+#define K1B_ROW_BIG(VR, RX, RY, MROW)                                                        \
         {                                                                                        \
-            uint32_t nx_ = __builtin_amdgcn_update_dpp(0u, VR.x, 0x130, 0xf, 0xf, true);         \
-            uint32_t ny_ = __builtin_amdgcn_update_dpp(0u, VR.y, 0x130, 0xf, 0xf, true);         \
             const uint32_t rx_ = (RX), ry_ = (RY); /* evaluated by ALL lanes (readfirstlane) */  \
-            uint32_t d4_ = lane == 63 ? rx_ : nx_, d5_ = lane == 63 ? ry_ : ny_;                 \
+            const uint32_t d4_ = __builtin_amdgcn_update_dpp(rx_, VR.x, 0x130, 0xf, 0xf, false); \
+            const uint32_t d5_ = __builtin_amdgcn_update_dpp(ry_, VR.y, 0x130, 0xf, 0xf, false); \
             uint32_t d_[6] = {VR.x, VR.y, VR.z, VR.w, d4_, d5_};                                 \
             uint32_t w_[21]; /* w_[j]: the 4 bytes starting at byte j */                         \
             _Pragma("unroll") for (int j = 0; j < 21; j++)                                       \
@@ -1292,37 +1300,37 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
                 const uint32_t ty_ = (e_[j].y >> (w_[j + 4] & 31)) & (e_[j].x >> (w_[j] & 31));  \
                 m_ = __builtin_amdgcn_alignbit(tx_ & ty_, m_, 1);                                \
             }                                                                                    \
-            m_ >>= 16;                                                                           \
-            if (!interior) { /* wave-uniform: a scalar branch */                                 \
-                const uint64_t p0_ = tbase + (uint64_t)(RI) * 1024 + lane * 16;                  \
-                uint32_t keep_ = 0;                                                              \
-                _Pragma("unroll") for (int j = 0; j < 16; j++)                                   \
-                    if (any_start && p0_ + j >= lead && p0_ + j <= last_start) keep_ |= 1u << j; \
-                m_ &= keep_;                                                                     \
-            }                                                                                    \
-            MROW = m_;                                                                           \
+            MROW = m_ >> 16;                                                                     \
         }
-        // every position of an interior tile is a legal start: no per-row masking
-        const bool interior = tbase >= lead && tbase + tile_bytes <= last_start;
+        // every position of an interior tile is a legal start (two scalar compares); the first and the last
+        // tiles of the stream mask their rows BEHIND level 1, out of its line: K1B_BOUNDS
+        const bool interior = tile >= t_int_lo && tile < t_int_hi;
         if (BIG && Q == 5) {
-            K1B_ROW_BIG(0, nxt0, __builtin_amdgcn_readfirstlane(nxt1.x), __builtin_amdgcn_readfirstlane(nxt1.y), mrow0)
-            K1B_ROW_BIG(1, nxt1, __builtin_amdgcn_readfirstlane(nxt2.x), __builtin_amdgcn_readfirstlane(nxt2.y), mrow1)
-            K1B_ROW_BIG(2, nxt2, __builtin_amdgcn_readfirstlane(nxt3.x), __builtin_amdgcn_readfirstlane(nxt3.y), mrow2)
-            K1B_ROW_BIG(3, nxt3, nxtL.x, nxtL.y, mrow3)
+            K1B_ROW_BIG(nxt0, __builtin_amdgcn_readfirstlane(nxt1.x), __builtin_amdgcn_readfirstlane(nxt1.y), mrow0)
+            K1B_ROW_BIG(nxt1, __builtin_amdgcn_readfirstlane(nxt2.x), __builtin_amdgcn_readfirstlane(nxt2.y), mrow1)
+            K1B_ROW_BIG(nxt2, __builtin_amdgcn_readfirstlane(nxt3.x), __builtin_amdgcn_readfirstlane(nxt3.y), mrow2)
+            K1B_ROW_BIG(nxt3, nxtL.x, nxtL.y, mrow3)
         } else {
-            K1B_ROW(0, nxt0, __builtin_amdgcn_readfirstlane(nxt1.x), __builtin_amdgcn_readfirstlane(nxt1.y), mrow0)
-            K1B_ROW(1, nxt1, __builtin_amdgcn_readfirstlane(nxt2.x), __builtin_amdgcn_readfirstlane(nxt2.y), mrow1)
-            K1B_ROW(2, nxt2, __builtin_amdgcn_readfirstlane(nxt3.x), __builtin_amdgcn_readfirstlane(nxt3.y), mrow2)
-            K1B_ROW(3, nxt3, nxtL.x, nxtL.y, mrow3)
+            K1B_ROW(nxt0, __builtin_amdgcn_readfirstlane(nxt1.x), mrow0)
+            K1B_ROW(nxt1, __builtin_amdgcn_readfirstlane(nxt2.x), mrow1)
+            K1B_ROW(nxt2, __builtin_amdgcn_readfirstlane(nxt3.x), mrow2)
+            K1B_ROW(nxt3, nxtL.x, mrow3)
+        }
+        // the positions of row RI that lie in [LO, HI] (k1b_bounds.hpp)
+#define K1B_BOUNDS(RI, LO, HI) keep_mask16(tbase + (uint64_t)(RI) * 1024 + lane * 16, LO, HI)
+        if (!interior) { // wave-uniform: a scalar branch
+            if (!any_start) mrow0 = mrow1 = mrow2 = mrow3 = 0;
+            mrow0 &= K1B_BOUNDS(0, lead, last_start); mrow1 &= K1B_BOUNDS(1, lead, last_start);
+            mrow2 &= K1B_BOUNDS(2, lead, last_start); mrow3 &= K1B_BOUNDS(3, lead, last_start);
         }
         // SH: the side test for patterns of 1 and 2 bytes.  Positions j, j+1 share the read of sxy[byte j+1]:
         // bit (byte j) of X, bit (byte j+2) of Y (the shifts take the low five bits of their operand by themselves)
         uint32_t srow0 = 0, srow1 = 0, srow2 = 0, srow3 = 0;
-#define K1B_ROW_SHORT(RI, VR, RX, MROW)                                                          \
+#define K1B_ROW_SHORT(VR, RX, MROW)                                                          \
         {                                                                                        \
-            const uint32_t nx_ = __builtin_amdgcn_update_dpp(0u, VR.x, 0x130, 0xf, 0xf, true);   \
             const uint32_t rx_ = (RX);                                                           \
-            const uint32_t d_[5] = {VR.x, VR.y, VR.z, VR.w, lane == 63 ? rx_ : nx_};             \
+            const uint32_t d4_ = __builtin_amdgcn_update_dpp(rx_, VR.x, 0x130, 0xf, 0xf, false); \
+            const uint32_t d_[5] = {VR.x, VR.y, VR.z, VR.w, d4_};                                \
             uint2 e8_[8];                                                                        \
             _Pragma("unroll") for (int j = 0; j < 16; j += 2) {                                  \
                 const uint32_t mid_ = (d_[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 0xFFu;         \
@@ -1335,22 +1343,21 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
                 m_ = __builtin_amdgcn_alignbit(e8_[j >> 1].x >> (bx_ & 31), m_, 1);              \
                 m_ = __builtin_amdgcn_alignbit(e8_[j >> 1].y >> (by_ & 31), m_, 1);              \
             }                                                                                    \
-            m_ >>= 16;                                                                           \
-            if (!interior) { /* wave-uniform: a scalar branch */                                 \
-                const uint64_t p0_ = tbase + (uint64_t)(RI) * 1024 + lane * 16;                  \
-                uint32_t keep_ = 0;                                                              \
-                _Pragma("unroll") for (int j = 0; j < 16; j++)                                   \
-                    if (p0_ + j >= lead && p0_ + j + A.short_min <= total) keep_ |= 1u << j;     \
-                m_ &= keep_;                                                                     \
-            }                                                                                    \
-            MROW = m_;                                                                           \
+            MROW = m_ >> 16;                                                                     \
         }
         if (SH) {
-            K1B_ROW_SHORT(0, nxt0, __builtin_amdgcn_readfirstlane(nxt1.x), srow0)
-            K1B_ROW_SHORT(1, nxt1, __builtin_amdgcn_readfirstlane(nxt2.x), srow1)
-            K1B_ROW_SHORT(2, nxt2, __builtin_amdgcn_readfirstlane(nxt3.x), srow2)
-            K1B_ROW_SHORT(3, nxt3, nxtL.x, srow3)
+            K1B_ROW_SHORT(nxt0, __builtin_amdgcn_readfirstlane(nxt1.x), srow0)
+            K1B_ROW_SHORT(nxt1, __builtin_amdgcn_readfirstlane(nxt2.x), srow1)
+            K1B_ROW_SHORT(nxt2, __builtin_amdgcn_readfirstlane(nxt3.x), srow2)
+            K1B_ROW_SHORT(nxt3, nxtL.x, srow3)
+            if (!interior) { // (a short pattern starts wherever it still fits the stream)
+                const uint64_t slast_ = total - A.short_min;
+                if (total < A.short_min) srow0 = srow1 = srow2 = srow3 = 0;
+                srow0 &= K1B_BOUNDS(0, lead, slast_); srow1 &= K1B_BOUNDS(1, lead, slast_);
+                srow2 &= K1B_BOUNDS(2, lead, slast_); srow3 &= K1B_BOUNDS(3, lead, slast_);
+            }
         }
+#undef K1B_BOUNDS
 #undef K1B_ROW_SHORT
         if (CP) { // lead bytes of the lane's 16 bytes of every row: one count byte per lane, 64 per row (coalesced)
 #define K1B_LEADS(RI, VR)                                                                        \
@@ -1366,7 +1373,7 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
                             if (p0_ + k_ < total && ((w_[k_ >> 2] >> (8 * (k_ & 3))) & 0xC0) != 0x80) c_++; \
                     }                                                                            \
                 }                                                                                \
-                A.cp_sub[(tile * 4 + (RI)) * 64 + lane] = (uint8_t)c_;                           \
+                A.cp_sub[((uint64_t)tile * 4 + (RI)) * 64 + lane] = (uint8_t)c_;                 \
             }
             K1B_LEADS(0, nxt0) K1B_LEADS(1, nxt1) K1B_LEADS(2, nxt2) K1B_LEADS(3, nxt3)
 #undef K1B_LEADS
@@ -1378,8 +1385,8 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
             // K1bLds comment).  Nothing of the haystack is read a second time.
             uint8_t *const stg = L.u.b.stage[wave];
             uint64_t *const q1w = L.u.b.q1w[wave];
-            const uint64_t ntb_ = (tile + nw) * tile_bytes;
-            const bool nfast_ = ntb_ + tile_bytes <= last_block; // (wave-uniform: the next tile lies wholly inside the stream)
+            const uint64_t ntb_ = (uint64_t)(tile + tstep) * tile_bytes;
+            const bool nfast_ = tile + tstep < t_full; // (wave-uniform: the next tile lies wholly inside the stream)
             const uint8_t *const ntp_ = hay + ntb_ + lane * 16;
             // (two loops: the first one -- the one that runs -- never moves the pipeline: with advance() inside it the whole
             // pipeline state is loop-carried, and the compiler copied it from register to register in EVERY round, behind
@@ -1432,7 +1439,7 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
                 if (lane == 0) *(uint2 *)(stg + 1024) = make_uint2(rx_, ry_);                        \
                 __builtin_amdgcn_wave_barrier();                                                     \
                 if (nfast_) VR = K1B_LOAD16(ntp_ + (R) * 1024);                                      \
-                else K1B_ISSUE_ROW(VR, tile + nw, R)                                                 \
+                else K1B_ISSUE_ROW(VR, tile + tstep, R)                                                \
                 compact_row(MROW, R, 0u);                                                            \
                 if (SH) compact_row(SROW, R, SHFLAG); /* the side test's survivors, flagged */       \
             }
@@ -1455,7 +1462,7 @@ __global__ __launch_bounds__(1024) void k1b_prefilter(K1bTables A, Sink GK,
         // of the next iteration and the three other waves of the SIMD cover its latency.  Measured
         // (round 1, T): issued before row 0: 310 us; after row 1: 299; after row 2: 293; here: 291;
         // no prefetch at all (loads at the top of the tile's own iteration): 308.
-        K1B_ISSUE_TILE(tile + nw)
+        K1B_ISSUE_TILE(tile + tstep)
         // ---- ballot-compact the survivors of the tile into Q1, one per lane per round
         // (one 64-bit mask per lane; the round is branch-free: the lowest set bit by two v_ffbl, lanes
         // without a survivor compute along and do not store)
@@ -1550,6 +1557,8 @@ hipError_t launch_prefilter(const DevAutomaton &A, const Sink &K, const uint8_t 
                       A.short_xy, A.short_codes, A.short_min_len};
     const bool sh = A.short_min_len != 0; // the set has patterns of 1 or 2 bytes: the side test runs too
     if (cp_sub && (lead != 0 || !K.hslots)) return hipErrorInvalidValue;
+    // (the kernel counts tiles in 32 bits, the iterations that drain its pipeline included)
+    if (prefilter_tiles(d_hay, len) + 5ull * 16 * grid >= (1ull << 32)) return hipErrorInvalidValue;
     // the events (measurement only) ride on the dispatch itself: no barrier packets, no gaps
 #define ACX_K1B_LAUNCH(Q, S, C, B, H)                                                                      \
     hipExtLaunchKernelGGL((k1b_prefilter<Q, S, C, B, H>), g, b, 0, st, ev_start, ev_stop, 0, T, K, base, len, lead)
@@ -1793,9 +1802,9 @@ __global__ __launch_bounds__(1024) void k1a_scan(const uint32_t *__restrict__ t3
 #define K1A_BYTE(R, k) ((R[(k) >> 2] >> (8 * ((k) & 3))) & 0xFFu)
 #define K1A_ROW(RI, VR, RX, MROW)                                                                \
         {                                                                                        \
-            const uint32_t nx_ = __builtin_amdgcn_update_dpp(0u, VR.x, 0x130, 0xf, 0xf, true);   \
-            const uint32_t rx_ = (RX);                                                           \
-            const uint32_t d_[5] = {VR.x, VR.y, VR.z, VR.w, lane == 63 ? rx_ : nx_};             \
+            const uint32_t rx_ = (RX); /* lane 63 keeps it: a DPP move without bound_ctrl (K1B_ROW) */ \
+            const uint32_t d4_ = __builtin_amdgcn_update_dpp(rx_, VR.x, 0x130, 0xf, 0xf, false); \
+            const uint32_t d_[5] = {VR.x, VR.y, VR.z, VR.w, d4_};                                \
             uint32_t t_[5];                                                                      \
             _Pragma("unroll") for (int k = 0; k < 5; k++) t_[k] = (d_[k] << 2) & 0x7C7C7C7Cu;    \
             uint32_t s2_[19], y2_[17];                                                           \
