@@ -22,6 +22,8 @@ from .ahocorasick_rs import (
     FilteredRows,
     RowScores,
     MaskedRows,
+    RowOffsets,
+    split_rows,
 )
 
 __acx_amd__ = True
@@ -46,6 +48,9 @@ __all__ = [
     "RowScores",
     # Extension: the result of mask_all_batch / match_mask_batch
     "MaskedRows",
+    # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
+    "split_rows",
+    "RowOffsets",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

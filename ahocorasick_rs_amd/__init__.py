@@ -27,6 +27,8 @@ try:
         FilteredRows,
     RowScores,
         MaskedRows,
+        RowOffsets,
+        split_rows,
     )
 except ImportError as e:  # pragma: no cover - build problem, fail loudly
     raise ImportError(
@@ -54,6 +56,9 @@ __all__ = [
     "RowScores",
     # Extension: the result of mask_all_batch / match_mask_batch
     "MaskedRows",
+    # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
+    "split_rows",
+    "RowOffsets",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

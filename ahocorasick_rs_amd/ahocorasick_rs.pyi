@@ -98,6 +98,24 @@ class MaskedRows:
     # entries of continuation bytes are dropped on the host); a tensor gives the bytes as they are (decoded for list[str])
     def tolist(self) -> Any: ...
 
+# extension: the result of split_rows -- the offsets that cut a delimited buffer into rows, where the data lies
+class RowOffsets:
+    @property
+    def offsets(self) -> Column: ...  # len(self) + 1 int64 entries that rise strictly from 0 to nbytes
+    @property
+    def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
+    @property
+    def nbytes(self) -> int: ...  # the length of the data that was cut
+    def __len__(self) -> int: ...  # the rows
+    def tolist(self) -> list[int]: ...  # the offsets
+
+# extension: 0, then p + 1 for every byte p of data that equals the delimiter, then len(data) if the last byte is not one: the
+# delimiter ends its row (splitlines(keepends=True) for "\n") and no row is empty.  data: one 1-D contiguous uint8 __dlpack__
+# tensor (on a ROCm device it is cut where it lies, and the offsets stay there) or any contiguous byte buffer; never written.
+# delimiter: an int in range(256), a one-byte buffer or a one-character ASCII str (ValueError otherwise; TypeError for
+# anything else).  The result's .offsets is what the _batch methods take as offsets= beside the same tensor.
+def split_rows(data: Any, delimiter: Any = b"\n") -> RowOffsets: ...
+
 class AhoCorasick:
     def __init__(
         self,

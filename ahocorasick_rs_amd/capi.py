@@ -264,6 +264,20 @@ def lib() -> ctypes.CDLL:
     L.acx_free_masked.restype = None
     L.acx_mask_host.argtypes = [vp, u64, vp, u64, vp, u64, vp, u8, u32, vp]
     L.acx_mask_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, u64, vp, u8, u32, vp]
+    L.acx_split_rows.argtypes = [vp, u64, u8, ctypes.POINTER(vp)]
+    L.acx_split_rows_device.argtypes = [vp, u64, u8, ctypes.POINTER(vp)]
+    for name in ("count", "bytes"):
+        getattr(L, "acx_rows_" + name).argtypes = [vp]
+        getattr(L, "acx_rows_" + name).restype = u64
+    L.acx_rows_on_device.argtypes = [vp]
+    L.acx_rows_device.argtypes = [vp]
+    L.acx_rows_offsets.argtypes = [vp]
+    L.acx_rows_offsets.restype = vp
+    L.acx_rows_copy.argtypes = [vp, vp]
+    L.acx_free_rows.argtypes = [vp]
+    L.acx_free_rows.restype = None
+    L.acx_split_rows_host.argtypes = [vp, u64, u8, vp, u64, ctypes.POINTER(u64)]
+    L.acx_split_rows_into_device.argtypes = [vp, u64, u8, vp, u64, ctypes.POINTER(u64)]
     _lib = L
     return L
 
@@ -1002,6 +1016,89 @@ def mask_rows_device(d_hay: int, nbytes: int, d_offsets: int, n_hay: int, unifor
     d_out (any address; d_out == d_hay: in place); complete when it returns"""
     _check(lib().acx_mask_rows_device(d_hay or None, nbytes, d_offsets or None, n_hay, uniform_len, d_records or None, n,
                                       d_counts or None, fill, flags, d_out or None))
+
+
+class DeviceRows:
+    """The result of split_rows / split_rows_device (acx_rows_t): the offsets that cut nbytes of delimited data into rows --
+    rows + 1 int64 words from 0 to nbytes, in HBM (on_device, on `device`) or in host memory.  `rows` is valid at once;
+    offsets() copies the words out and offsets_ptr() is where they lie (both wait for the device stage)."""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    @property
+    def on_device(self) -> bool:
+        return bool(lib().acx_rows_on_device(self._h))
+
+    @property
+    def device(self) -> int:
+        return int(lib().acx_rows_device(self._h))
+
+    @property
+    def rows(self) -> int:
+        return int(lib().acx_rows_count(self._h))
+
+    @property
+    def nbytes(self) -> int:
+        return int(lib().acx_rows_bytes(self._h))
+
+    def offsets_ptr(self) -> int:
+        return lib().acx_rows_offsets(self._h) or 0
+
+    def offsets(self) -> np.ndarray:
+        out = np.zeros(self.rows + 1, dtype=np.int64)
+        _check(lib().acx_rows_copy(self._h, out.ctypes.data))
+        return out
+
+    def free(self) -> None:
+        if self._h:
+            lib().acx_free_rows(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def split_rows(hay, delimiter: int = 10) -> DeviceRows:
+    """acx_split_rows: host bytes cut at every `delimiter` byte (the delimiter ends its row), a host result"""
+    h = np.frombuffer(bytes(hay), dtype=np.uint8)
+    out = ctypes.c_void_p()
+    _check(lib().acx_split_rows(h.ctypes.data if len(h) else None, len(h), delimiter, ctypes.byref(out)))
+    return DeviceRows(out.value)
+
+
+def split_rows_device(d_hay: int, nbytes: int, delimiter: int = 10) -> DeviceRows:
+    """acx_split_rows_device: nbytes at d_hay (HBM, any address) -> the offsets in HBM on the same device; `rows` is known
+    when it returns, the offsets may still be written (their accessors wait)"""
+    out = ctypes.c_void_p()
+    _check(lib().acx_split_rows_device(d_hay or None, nbytes, delimiter, ctypes.byref(out)))
+    return DeviceRows(out.value)
+
+
+def split_rows_host(hay, delimiter: int = 10, *, count_only: bool = False):
+    """acx_split_rows_host: the definition on the host, no device involved -> rows + 1 int64 offsets (count_only: the number
+    of rows)"""
+    h = np.frombuffer(bytes(hay), dtype=np.uint8)
+    p = h.ctypes.data if len(h) else None
+    n = ctypes.c_uint64()
+    _check(lib().acx_split_rows_host(p, len(h), delimiter, None, 0, ctypes.byref(n)))
+    if count_only:
+        return int(n.value)
+    out = np.zeros(n.value + 1, dtype=np.int64)
+    _check(lib().acx_split_rows_host(p, len(h), delimiter, out.ctypes.data, len(out), ctypes.byref(n)))
+    return out
+
+
+def split_rows_into_device(d_hay: int, nbytes: int, delimiter: int, d_offsets: int, capacity: int) -> int:
+    """acx_split_rows_into_device: the device stage alone -- nbytes at d_hay (any address) -> rows + 1 int64 words at d_offsets
+    (8-byte aligned, `capacity` words; 0: count only); complete when it returns.  Returns the number of rows; ValueError (code
+    EINVAL) when the buffer is too small -- nothing was written then"""
+    n = ctypes.c_uint64()
+    _check(lib().acx_split_rows_into_device(d_hay or None, nbytes, delimiter, d_offsets or None, capacity, ctypes.byref(n)))
+    return int(n.value)
 
 
 def _replaced_bytes(h: int) -> bytes:

@@ -826,7 +826,8 @@ struct DLTensorC { void *data; DLDeviceC device; int32_t ndim; DLDataTypeC dtype
 struct DLManagedTensorC { DLTensorC dl_tensor; void *manager_ctx; void (*deleter)(DLManagedTensorC *); };
 constexpr int32_t kDLCPU = 1, kDLCUDA = 2, kDLCUDAHost = 3, kDLROCM = 10, kDLROCMHost = 11;
 
-// haystack -> (pointer, length, on_device).  Returns the capsule to release afterwards (new reference).
+// haystack -> (pointer, length, on_device).  Returns the capsule to release afterwards (new reference).  want_device < 0: a
+// call without an automaton takes a tensor on any device.
 PyObject *dlpack_view(PyObject *hay, int want_device, const uint8_t **ptr, uint64_t *len, bool *on_device) {
     PyObject *cap = PyObject_CallMethod(hay, "__dlpack__", nullptr);
     if (!cap) return nullptr;
@@ -848,7 +849,7 @@ PyObject *dlpack_view(PyObject *hay, int want_device, const uint8_t **ptr, uint6
     const bool host = t.device.device_type == kDLCPU || t.device.device_type == kDLROCMHost ||
                       t.device.device_type == kDLCUDAHost;
     if (!err && !dev && !host) err = "unsupported DLPack device type";
-    if (!err && dev && t.device.device_id != want_device) {
+    if (!err && dev && want_device >= 0 && t.device.device_id != want_device) {
         PyErr_Format(PyExc_ValueError, "haystack lives on device %d, the automaton on device %d",
                      (int)t.device.device_id, want_device);
         Py_DECREF(cap);
@@ -1021,9 +1022,10 @@ PyTypeObject *PatternCountsType = nullptr;
 PyTypeObject *FilteredRowsType = nullptr;
 PyTypeObject *RowScoresType = nullptr;
 PyTypeObject *MaskedRowsType = nullptr;
+PyTypeObject *RowOffsetsType = nullptr;
 
 // What a Column's owner -- a MatchColumns, a PatternCounts, a FilteredRows (`which`: ACX_COL_*, ACX_TALLY_*, ACX_FILT_*), a
-// RowScores (its one part) or a MaskedRows (`which`: MR_*) -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
+// RowScores or a RowOffsets (their one part) or a MaskedRows (`which`: MR_*) -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
 struct OwnerOps {
     int (*on_device)(const void *h);
     const void *(*data)(const void *h, int which); // (waits for the device work)
@@ -1069,7 +1071,11 @@ const OwnerOps MR_OPS = {[](const void *h) { return acx_masked_on_device(static_
                                                     : acx_masked_data(static_cast<const acx_masked_t *>(h));
                          },
                          [](void *h) { acx_free_masked(static_cast<acx_masked_t *>(h)); }};
+const OwnerOps RO_OPS = {[](const void *h) { return acx_rows_on_device(static_cast<const acx_rows_t *>(h)); },
+                         [](const void *h, int) -> const void * { return acx_rows_offsets(static_cast<const acx_rows_t *>(h)); },
+                         [](void *h) { acx_free_rows(static_cast<acx_rows_t *>(h)); }};
 OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
+acx_rows_t *ro_handle(PyObject *s) { return static_cast<acx_rows_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
 acx_masked_t *mr_handle(PyObject *s) { return static_cast<acx_masked_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
 acx_columns_t *mc_handle(PyObject *s) { return static_cast<acx_columns_t *>(owner_of(s)->h); }
 acx_tally_t *pc_handle(PyObject *s) { return static_cast<acx_tally_t *>(owner_of(s)->h); }
@@ -1319,7 +1325,7 @@ PyType_Slot col_slots[] = {
     {Py_sq_length, reinterpret_cast<void *>(col_len)},
     {Py_bf_getbuffer, reinterpret_cast<void *>(col_getbuffer)},
     {Py_tp_doc, const_cast<char *>(
-        "One int64 column of a MatchColumns, a PatternCounts or a RowScores, or one part of a FilteredRows or a MaskedRows (int64; their data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
+        "One int64 column of a MatchColumns, a PatternCounts, a RowScores or a RowOffsets, or one part of a FilteredRows or a MaskedRows (int64; their data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
         "copy) and, in host memory, the buffer protocol (format 'q', or 'B' for uint8; read-only).")},
     {0, nullptr},
 };
@@ -1773,6 +1779,17 @@ PyObject *bac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
 // (acx_filter_scored / acx_filter_scored_device).  A RowScores owns the acx_scores_t; .score is a Column with the lifetime
 // chain of a MatchColumns' columns.
 // ---------------------------------------------------------------------------
+// the first n words of v as list[int] (RowScores.tolist, RowOffsets.tolist)
+PyObject *i64_list(const std::vector<int64_t> &v, uint64_t n) {
+    PyObject *list = PyList_New((Py_ssize_t)n);
+    for (uint64_t i = 0; list && i < n; i++) {
+        PyObject *it = PyLong_FromLongLong((long long)v[(size_t)i]);
+        if (!it) { Py_CLEAR(list); break; }
+        PyList_SET_ITEM(list, (Py_ssize_t)i, it);
+    }
+    return list;
+}
+
 PyObject *rs_get_score(PyObject *s, void *) { return new_column(s, 0, acx_scores_rows(rs_handle(s))); }
 Py_ssize_t rs_len(PyObject *s) { return (Py_ssize_t)acx_scores_rows(rs_handle(s)); }
 
@@ -1785,13 +1802,7 @@ PyObject *rs_tolist(PyObject *self_, PyObject *) {
     rc = acx_scores_copy(h, v.data());
     Py_END_ALLOW_THREADS
     if (rc != ACX_OK) return raise_acx(rc);
-    PyObject *list = PyList_New((Py_ssize_t)rows);
-    for (uint64_t i = 0; list && i < rows; i++) {
-        PyObject *it = PyLong_FromLongLong((long long)v[(size_t)i]);
-        if (!it) { Py_CLEAR(list); break; }
-        PyList_SET_ITEM(list, (Py_ssize_t)i, it);
-    }
-    return list;
+    return i64_list(v, rows);
 }
 
 PyGetSetDef rs_getset[] = {
@@ -1956,15 +1967,15 @@ PyObject *bac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *k
 // ---------------------------------------------------------------------------
 
 // fill: an int 0..255 or a one-byte buffer (the bytes class), a one-character ASCII str (the str class: the output stays
-// valid UTF-8); sets the exception
-bool parse_fill(PyObject *fill, bool utf8, uint8_t *out) {
+// valid UTF-8); sets the exception.  name: the argument as the messages call it (split_rows' delimiter takes the same check).
+bool parse_fill(PyObject *fill, bool utf8, uint8_t *out, const char *name = "fill") {
     if (utf8) {
         if (!PyUnicode_Check(fill)) {
-            PyErr_Format(PyExc_TypeError, "argument 'fill': '%.100s' object cannot be converted to 'PyString'", Py_TYPE(fill)->tp_name);
+            PyErr_Format(PyExc_TypeError, "argument '%s': '%.100s' object cannot be converted to 'PyString'", name, Py_TYPE(fill)->tp_name);
             return false;
         }
         if (PyUnicode_GET_LENGTH(fill) != 1 || PyUnicode_READ_CHAR(fill, 0) > 0x7F) {
-            PyErr_SetString(PyExc_ValueError, "fill must be one ASCII character");
+            PyErr_Format(PyExc_ValueError, "%s must be one ASCII character", name);
             return false;
         }
         *out = (uint8_t)PyUnicode_READ_CHAR(fill, 0);
@@ -1975,14 +1986,14 @@ bool parse_fill(PyObject *fill, bool utf8, uint8_t *out) {
         const long long v = PyLong_AsLongLongAndOverflow(fill, &overflow);
         if (v == -1 && !overflow && PyErr_Occurred()) return false;
         if (overflow || v < 0 || v > 255) {
-            PyErr_SetString(PyExc_ValueError, "fill must be in range(256)");
+            PyErr_Format(PyExc_ValueError, "%s must be in range(256)", name);
             return false;
         }
         *out = (uint8_t)v;
         return true;
     }
     if (PyUnicode_Check(fill) || PyBool_Check(fill) || !PyObject_CheckBuffer(fill)) {
-        PyErr_Format(PyExc_TypeError, "argument 'fill': an int in range(256) or a one-byte buffer is needed, not '%.100s'",
+        PyErr_Format(PyExc_TypeError, "argument '%s': an int in range(256) or a one-byte buffer is needed, not '%.100s'", name,
                      Py_TYPE(fill)->tp_name);
         return false;
     }
@@ -1991,7 +2002,7 @@ bool parse_fill(PyObject *fill, bool utf8, uint8_t *out) {
     const bool one = v.len == 1;
     if (one) *out = *static_cast<const uint8_t *>(v.buf);
     PyBuffer_Release(&v);
-    if (!one) PyErr_SetString(PyExc_ValueError, "fill must be one byte");
+    if (!one) PyErr_Format(PyExc_ValueError, "%s must be one byte", name);
     return one;
 }
 
@@ -2168,6 +2179,90 @@ template <bool TEXT, bool BATCH> PyObject *bac_mask(PyObject *self_, PyObject *a
     return mask_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false, TEXT, BATCH);
 }
 
+// ---------------------------------------------------------------------------
+// split_rows(data, delimiter=b"\n") -> RowOffsets (acx_split_rows / acx_split_rows_device): a delimited buffer cut into rows.
+// A module function -- no automaton is involved.  A RowOffsets owns the acx_rows_t; .offsets is a Column with the lifetime
+// chain of a MatchColumns' columns, and what the _batch methods take as offsets=.
+// ---------------------------------------------------------------------------
+PyObject *ro_get_offsets(PyObject *s, void *) { return new_column(s, 0, acx_rows_count(ro_handle(s)) + 1); }
+PyObject *ro_get_nbytes(PyObject *s, void *) { return PyLong_FromUnsignedLongLong(acx_rows_bytes(ro_handle(s))); }
+Py_ssize_t ro_len(PyObject *s) { return (Py_ssize_t)acx_rows_count(ro_handle(s)); }
+
+PyObject *ro_tolist(PyObject *self_, PyObject *) {
+    acx_rows_t *h = ro_handle(self_);
+    const uint64_t n = acx_rows_count(h) + 1;
+    std::vector<int64_t> v((size_t)n);
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = acx_rows_copy(h, v.data());
+    Py_END_ALLOW_THREADS
+    if (rc != ACX_OK) return raise_acx(rc);
+    return i64_list(v, n);
+}
+
+PyGetSetDef ro_getset[] = {
+    {"offsets", ro_get_offsets, nullptr, "Column of len(self) + 1 int64 entries from 0 to nbytes: row i is data[offsets[i]:offsets[i + 1]]", nullptr},
+    {"device", owner_get_device, nullptr, "None: the offsets are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {"nbytes", ro_get_nbytes, nullptr, "the length of the data that was cut", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+PyMethodDef ro_methods[] = {
+    {"tolist", ro_tolist, METH_NOARGS, "the offsets as list[int] (copies device offsets to the host)"},
+    {nullptr, nullptr, 0, nullptr},
+};
+PyType_Slot ro_slots[] = {
+    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
+    {Py_tp_methods, ro_methods},
+    {Py_tp_getset, ro_getset},
+    {Py_sq_length, reinterpret_cast<void *>(ro_len)},
+    {Py_tp_doc, const_cast<char *>(
+        "The result of split_rows: .offsets is an int64 Column of len(self) + 1 entries that rise strictly from 0 to .nbytes, "
+        "where the data lies (.device); len(self) is the number of rows.  Pass .offsets as offsets= to the _batch methods.")},
+    {0, nullptr},
+};
+
+PyObject *mod_split_rows(PyObject *, PyObject *args, PyObject *kwargs) {
+    static const char *kw[] = {"data", "delimiter", nullptr};
+    PyObject *data = nullptr, *delim = nullptr;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|O:split_rows", const_cast<char **>(kw), &data, &delim)) return nullptr;
+    uint8_t d = '\n';
+    if (delim && !parse_fill(delim, PyUnicode_Check(delim) != 0, &d, "delimiter")) return nullptr;
+    acx_rows_t *r = nullptr;
+    int rc;
+    if (!PyUnicode_Check(data) && !PyObject_CheckBuffer(data) && PyObject_HasAttrString(data, "__dlpack__")) {
+        const uint8_t *p = nullptr;
+        uint64_t len = 0;
+        bool on_device = false;
+        PyObject *cap = dlpack_view(data, -1, &p, &len, &on_device);
+        if (!cap) return nullptr;
+        const DLTensorC &t = static_cast<DLManagedTensorC *>(PyCapsule_GetPointer(cap, "dltensor"))->dl_tensor;
+        const int device = t.device.device_id;
+        if (t.ndim != 1) {
+            dlpack_release(cap);
+            PyErr_SetString(PyExc_TypeError, "Only one-dimensional sequences are supported");
+            return nullptr;
+        }
+        Py_BEGIN_ALLOW_THREADS
+        if (on_device) {
+            rc = acx_device_synchronize_on(device); // (the producer's kernels may still write the tensor)
+            if (rc == ACX_OK) rc = acx_split_rows_device(p, len, d, &r);
+        } else {
+            rc = acx_split_rows(p, len, d, &r);
+        }
+        Py_END_ALLOW_THREADS
+        dlpack_release(cap);
+    } else {
+        Py_buffer v;
+        if (!get_bytes_view(data, &v)) return nullptr;
+        Py_BEGIN_ALLOW_THREADS
+        rc = acx_split_rows(static_cast<const uint8_t *>(v.buf), (uint64_t)v.len, d, &r);
+        Py_END_ALLOW_THREADS
+        PyBuffer_Release(&v);
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    return reinterpret_cast<PyObject *>(new_owner(RowOffsetsType, &RO_OPS, r, acx_rows_device(r)));
+}
+
 // device-resident search -> list of tuples (the records come back with ONE D2H copy of the result)
 PyObject *find_on_device(acx_automaton_t *a, const uint8_t *d_hay, uint64_t len, int overlapping) {
     acx_result_t *r = nullptr;
@@ -2317,6 +2412,13 @@ PyType_Slot bac_slots[] = {
 };
 
 PyMethodDef module_methods[] = {
+    {"split_rows", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(mod_split_rows)), METH_VARARGS | METH_KEYWORDS,
+     "[extension] split_rows(data, delimiter=b'\\n') -> RowOffsets: the offsets that cut a delimited buffer into rows -- 0, "
+     "then p + 1 for every byte p that equals the delimiter, then len(data) if the last byte is not one.  The delimiter ends "
+     "its row (splitlines(keepends=True) for '\\n'), no row is empty.  data: one 1-D contiguous uint8 __dlpack__ tensor -- on a "
+     "ROCm device it is cut where it lies and the offsets stay there -- or any contiguous byte buffer; it is never written.  "
+     "delimiter: an int in range(256), a one-byte buffer or a one-character ASCII str.  Pass the result's .offsets as "
+     "offsets= to the _batch methods that take a tensor."},
     {"_mask_fill", mod_mask_fill, METH_VARARGS,
      "_mask_fill(fill, text) -> int: the fill byte mask_all takes from `fill` (text: the str class's rule), or its error"},
     {"_mask_per_character", mod_mask_per_character, METH_VARARGS,
@@ -2362,16 +2464,19 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, rs_slots};
     PyType_Spec mr_spec = {"ahocorasick_rs.MaskedRows", sizeof(MaskedRowsObject), 0,
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, mr_slots};
+    PyType_Spec ro_spec = {"ahocorasick_rs.RowOffsets", sizeof(OwnerObject), 0,
+                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, ro_slots};
     MaskedRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mr_spec));
+    RowOffsetsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&ro_spec));
     FilteredRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&fr_spec));
     RowScoresType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&rs_spec));
     MatchColumnsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mc_spec));
     ColumnType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&col_spec));
     PatternCountsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&pc_spec));
-    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType || !RowScoresType || !MaskedRowsType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
-    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType, RowScoresType, MaskedRowsType}) { // (the module holds one reference, the globals the other)
+    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType || !RowScoresType || !MaskedRowsType || !RowOffsetsType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
+    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType, RowScoresType, MaskedRowsType, RowOffsetsType}) { // (the module holds one reference, the globals the other)
         Py_INCREF(tp);
-        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : tp == RowScoresType ? "RowScores" : tp == MaskedRowsType ? "MaskedRows" : "MatchColumns",
+        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : tp == RowScoresType ? "RowScores" : tp == MaskedRowsType ? "MaskedRows" : tp == RowOffsetsType ? "RowOffsets" : "MatchColumns",
                                reinterpret_cast<PyObject *>(tp)) < 0) {
             Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);
             return nullptr;

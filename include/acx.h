@@ -41,6 +41,9 @@ extern "C" {
  *     sixth addendum (additive as well): acx_mask / acx_mask_device / acx_mask_host / acx_mask_rows_device, ACX_MASK_ZERO,
  *     the acx_masked_t accessors (acx_masked_bytes, _rows, _on_device, _data, _offsets, _copy, _copy_offsets,
  *     acx_free_masked);
+ *     seventh addendum (additive as well): acx_split_rows / acx_split_rows_device / acx_split_rows_host /
+ *     acx_split_rows_into_device and the acx_rows_t accessors (acx_rows_count, _bytes, _on_device, _device, _offsets, _copy,
+ *     acx_free_rows);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -674,6 +677,43 @@ int acx_mask_host(const uint8_t *hay, uint64_t len, const uint64_t *offsets, uin
 int acx_mask_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
                          const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint8_t fill, uint32_t flags,
                          void *d_out);
+
+/* ---- rows: a delimited buffer (newline-terminated records: web text, JSONL, logs) cut into the rows the batch entry points
+ * take -- the step before acx_filter_device, acx_score_device, acx_mask_device, acx_tally_device and the rest.  No automaton is
+ * involved.  For `len` bytes and a delimiter byte d the result is rows + 1 int64 words:
+ *   0; then p + 1 for every position p with hay[p] == d, ascending; then len if len > 0 and hay[len - 1] != d
+ * -- row i is hay[offsets[i] .. offsets[i + 1]).  Every row but possibly the last ends with its delimiter (the delimiter
+ * belongs to the row, as in Python's splitlines(keepends=True) for '\n'), no row is empty, and the words rise strictly from 0
+ * to len: exactly what `offsets` / `d_offsets` of the batch entry points must be.  No bytes: 0 rows and the one word 0.
+ * acx_split_rows: host bytes, a host result.
+ * acx_split_rows_device: bytes in HBM (any address), the result in HBM on the same device; the work is queued on that
+ * device's null stream: two passes over the bytes with a scan of per-tile counts between them, and 16 bytes back to the host
+ * (the number of rows).  It returns once the number of rows is known -- acx_rows_count is valid at return -- and the second
+ * pass may still run: acx_rows_offsets / _copy wait for it.  d_hay must stay valid and unchanged until then.  A result of 8
+ * bytes per input byte (every byte a delimiter) that cannot be allocated is ACX_ENOMEM.
+ * len = 0 launches nothing and allows a null pointer; a null pointer with len > 0 is ACX_EINVAL. */
+typedef struct acx_rows acx_rows_t;
+int acx_split_rows(const uint8_t *hay, uint64_t len, uint8_t delimiter, acx_rows_t **out);
+int acx_split_rows_device(const void *d_hay, uint64_t len, uint8_t delimiter, acx_rows_t **out);
+uint64_t acx_rows_count(const acx_rows_t *r);      /* the rows; valid when the call has returned           */
+uint64_t acx_rows_bytes(const acx_rows_t *r);      /* len                                                   */
+int acx_rows_on_device(const acx_rows_t *r);       /* 1: the offsets are in HBM, 0: host memory             */
+int acx_rows_device(const acx_rows_t *r);          /* the HIP ordinal they lie on (on_device)               */
+/* host or device pointer by acx_rows_on_device: rows + 1 int64 words; waits for the device stage.  NULL: the wait failed.
+ * Valid until acx_free_rows. */
+const int64_t *acx_rows_offsets(const acx_rows_t *r);
+int acx_rows_copy(const acx_rows_t *r, int64_t *host_dst);
+void acx_free_rows(acx_rows_t *r);
+/* the cut itself, into the caller's memory.  capacity: the int64 words `offsets` / `d_offsets` holds; *n_rows is set whenever
+ * the bytes were counted.  rows + 1 > capacity: nothing is written behind the buffer (nothing at all), *n_rows says what is
+ * needed and the call returns ACX_EINVAL with a message that names the number of words.
+ * acx_split_rows_host: host memory, no device needed -- the definition above inside the library; offsets = NULL counts only.
+ * acx_split_rows_into_device: the device stage alone; synchronous: d_offsets is complete when it returns.  d_offsets: 8-byte
+ * aligned (ACX_EINVAL otherwise), or NULL: count only; d_hay: any address. */
+int acx_split_rows_host(const uint8_t *hay, uint64_t len, uint8_t delimiter, int64_t *offsets /* NULL: count only */,
+                        uint64_t capacity, uint64_t *n_rows);
+int acx_split_rows_into_device(const void *d_hay, uint64_t len, uint8_t delimiter, int64_t *d_offsets, uint64_t capacity,
+                               uint64_t *n_rows);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
