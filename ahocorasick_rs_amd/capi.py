@@ -325,9 +325,41 @@ def pack(patterns: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
     return blob, off
 
 
-class HostAutomaton:
+class _Handle:
+    """The one owner of a handle of the C ABI: `_h`, given back exactly once through the C function that _FREE names -- by
+    free() (close() where a class spells it so), or when the object goes; afterwards `_h` is None."""
+    _FREE = ""
+    _h: Optional[int] = None  # (a constructor that raised leaves nothing to give back)
+
+    def __init__(self, handle: Optional[int]):
+        self._h = handle
+
+    def free(self) -> None:
+        if self._h:
+            getattr(lib(), self._FREE)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class _Result(_Handle):
+    """... of a result whose parts lie in HBM or in host memory: _ON_DEVICE names the C function that tells which"""
+    _ON_DEVICE = ""
+
+    @property
+    def on_device(self) -> bool:
+        return bool(getattr(lib(), self._ON_DEVICE)(self._h))
+
+
+class HostAutomaton(_Handle):
     """acx_host_automaton_t: the compiled tables on the host (no device needed).
     Arrays are numpy views valid while this object is alive."""
+    _FREE = "acx_free_host"
+    close = _Handle.free
 
     def __init__(self, patterns: Sequence[bytes], match_kind: int = MATCH_STANDARD, flags: int = 0):
         blob, off = pack(patterns)
@@ -380,17 +412,6 @@ class HostAutomaton:
         self.pattern_shift = view(t.pattern_shift, int(t.n_patterns), np.uint8)
         self.pattern_head = view(t.pattern_head, 4 * int(t.n_patterns) if t.pattern_head else 0, np.uint32).reshape(-1, 4)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            lib().acx_free_host(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def filter_hash(gram: bytes) -> int:
     """level-1 hash H of a (Q-1)-byte gram: entry = H >> 18, signature bits from H >> 9."""
@@ -425,11 +446,10 @@ def output_offsets(counts: Sequence[int]) -> List[int]:
     return [int(x) for x in out]
 
 
-class Comm:
+class Comm(_Handle):
     """acx_comm_t: the count exchange over RCCL, without torch (include/acx.h)."""
-
-    def __init__(self, handle: int):
-        self._h = handle
+    _FREE = "acx_comm_free"
+    close = _Handle.free
 
     @classmethod
     def init_all(cls, devices: Sequence[int]) -> "Comm":
@@ -461,26 +481,21 @@ class Comm:
         _check(lib().acx_comm_allgather_counts(self._h, loc.ctypes.data, out.ctypes.data))
         return [int(x) for x in out]
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            lib().acx_comm_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceBuffer:
+class DeviceBuffer(_Handle):
     """hipMalloc'ed bytes owned by this object (for hosts without torch)."""
+    _FREE = "acx_device_free"
 
     def __init__(self, nbytes: int):
         p = ctypes.c_void_p()
         _check(lib().acx_device_alloc(ctypes.byref(p), nbytes))
-        self.ptr = p.value
+        super().__init__(p.value)
         self.nbytes = nbytes
+
+    @property
+    def ptr(self) -> Optional[int]:
+        """the device address; None once freed"""
+        return self._h
 
     def upload(self, arr: np.ndarray) -> "DeviceBuffer":
         a = np.ascontiguousarray(arr)
@@ -494,23 +509,13 @@ class DeviceBuffer:
         _check(lib().acx_device_download(out.ctypes.data, self.ptr, n))
         return out
 
-    def free(self) -> None:
-        if self.ptr:
-            lib().acx_device_free(self.ptr)
-            self.ptr = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class DeviceResult:
+class DeviceResult(_Handle):
     """Matches resident in HBM (acx_result_t)."""
+    _FREE = "acx_free_result"
 
     def __init__(self, handle: int, n_hay: int):
-        self._h = handle
+        super().__init__(handle)
         self.n_hay = n_hay
 
     @property
@@ -533,23 +538,13 @@ class DeviceResult:
             _check(lib().acx_result_copy_counts(self._h, out.ctypes.data))
         return out
 
-    def free(self) -> None:
-        if self._h:
-            lib().acx_free_result(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class DeviceReplaced:
+class DeviceReplaced(_Handle):
     """The output of Automaton.replace_device, resident in HBM (acx_replaced_t)."""
+    _FREE = "acx_free_replaced"
 
     def __init__(self, handle: int, n_hay: int):
-        self._h = handle
+        super().__init__(handle)
         self.n_hay = n_hay
 
     @property
@@ -570,35 +565,21 @@ class DeviceReplaced:
     def download(self) -> bytes:
         return _replaced_bytes(self._h)
 
-    def free(self) -> None:
-        if self._h:
-            lib().acx_free_replaced(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class DeviceSummary:
+class DeviceSummary(_Result):
     """The summaries of Automaton.summarize / summarize_batch / summarize_device (acx_summary_t): reduced in HBM
     (on_device) or on the host; every part is copied out when it is asked for.  A part that `what` did not name raises
     ValueError (code EINVAL)."""
+    _ON_DEVICE, _FREE = "acx_summary_on_device", "acx_free_summary"
 
     def __init__(self, handle: int, n_hay: int, n_patterns: int):
-        self._h = handle
+        super().__init__(handle)
         self.n_hay = n_hay
         self.n_patterns = n_patterns
 
     @property
     def total(self) -> int:
         return int(lib().acx_summary_total(self._h))
-
-    @property
-    def on_device(self) -> bool:
-        return bool(lib().acx_summary_on_device(self._h))
 
     def _part(self, name: str, n: int, dtype) -> np.ndarray:
         out = np.zeros(n, dtype=dtype)
@@ -630,17 +611,6 @@ class DeviceSummary:
         """where the part ("counts", "any", "first", "by_pattern") lies in HBM (waits for the reduction); 0 on the host route"""
         return getattr(lib(), "acx_summary_device_" + name)(self._h) or 0
 
-    def free(self) -> None:
-        if self._h:
-            lib().acx_free_summary(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 def summarize_host(matches, counts: Optional[Sequence[int]], n_patterns: int, what: int = SUM_FIRST | SUM_BY_PATTERN):
     """acx_summarize_host: the reduction of a match list (rows of pattern, start, end; all haystacks behind one another,
@@ -662,18 +632,11 @@ def summarize_host(matches, counts: Optional[Sequence[int]], n_patterns: int, wh
             hist[:n_patterns] if what & SUM_BY_PATTERN else None)
 
 
-class _PartsResult:
+class _PartsResult(_Result):
     """What DeviceColumns, DeviceTally and DeviceFiltered share: a handle of the C ABI whose parts lie in HBM (on_device) or
     in host memory.  A subclass names its three C functions (_ON_DEVICE, _DATA, _COPY, _FREE) and, in _part_shape(which), a
     part's length and element type."""
-    _ON_DEVICE = _DATA = _COPY = _FREE = ""
-
-    def __init__(self, handle: int):
-        self._h = handle
-
-    @property
-    def on_device(self) -> bool:
-        return bool(getattr(lib(), self._ON_DEVICE)(self._h))
+    _DATA = _COPY = ""
 
     def data_ptr(self, which: int) -> int:
         """host or device address of the part (by on_device), behind the device work; 0: the result has no such part"""
@@ -684,17 +647,6 @@ class _PartsResult:
         out = np.zeros(n, dtype=dtype)
         _check(getattr(lib(), self._COPY)(self._h, which, out.ctypes.data if out.size else None))
         return out
-
-    def free(self) -> None:
-        if self._h:
-            getattr(lib(), self._FREE)(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 class DeviceColumns(_PartsResult):
@@ -871,16 +823,10 @@ def filter_rows_device(d_hay: int, nbytes: int, d_offsets: int, n_hay: int, unif
     return int(k.value), int(nb.value)
 
 
-class DeviceScores:
+class DeviceScores(_Result):
     """The result of Automaton.score / score_device (acx_scores_t): one int64 score per row of the batch, in HBM (on_device)
     or in host memory.  scores() copies them out; data_ptr() is where they lie (both wait for the device stage)."""
-
-    def __init__(self, handle: int):
-        self._h = handle
-
-    @property
-    def on_device(self) -> bool:
-        return bool(lib().acx_scores_on_device(self._h))
+    _ON_DEVICE, _FREE = "acx_scores_on_device", "acx_free_scores"
 
     @property
     def rows(self) -> int:
@@ -893,17 +839,6 @@ class DeviceScores:
         out = np.zeros(self.rows, dtype=np.int64)
         _check(lib().acx_scores_copy(self._h, out.ctypes.data if out.size else None))
         return out
-
-    def free(self) -> None:
-        if self._h:
-            lib().acx_free_scores(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def _weights(weights) -> np.ndarray:
@@ -937,18 +872,12 @@ def score_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, d_weigh
                                        d_scores or None))
 
 
-class DeviceMasked:
+class DeviceMasked(_Result):
     """The result of Automaton.mask / mask_device (acx_masked_t): the batch's bytes with every covered byte filled (or the
     0 / 1 mask), nbytes of them in the input's own layout, and the rows' offsets (rows + 1 int64 words from 0) -- in HBM
     (on_device) or in host memory.  data() / offsets() copy them out; data_ptr() / offsets_ptr() are where they lie (all
     wait for the device stage)."""
-
-    def __init__(self, handle: int):
-        self._h = handle
-
-    @property
-    def on_device(self) -> bool:
-        return bool(lib().acx_masked_on_device(self._h))
+    _ON_DEVICE, _FREE = "acx_masked_on_device", "acx_free_masked"
 
     @property
     def rows(self) -> int:
@@ -973,17 +902,6 @@ class DeviceMasked:
         out = np.zeros(self.rows + 1, dtype=np.int64)
         _check(lib().acx_masked_copy_offsets(self._h, out.ctypes.data))
         return out
-
-    def free(self) -> None:
-        if self._h:
-            lib().acx_free_masked(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def mask_host(hay, offsets: Optional[Sequence[int]], matches, counts: Optional[Sequence[int]], fill: int,
@@ -1018,17 +936,11 @@ def mask_rows_device(d_hay: int, nbytes: int, d_offsets: int, n_hay: int, unifor
                                       d_counts or None, fill, flags, d_out or None))
 
 
-class DeviceRows:
+class DeviceRows(_Result):
     """The result of split_rows / split_rows_device (acx_rows_t): the offsets that cut nbytes of delimited data into rows --
     rows + 1 int64 words from 0 to nbytes, in HBM (on_device, on `device`) or in host memory.  `rows` is valid at once;
     offsets() copies the words out and offsets_ptr() is where they lie (both wait for the device stage)."""
-
-    def __init__(self, handle: int):
-        self._h = handle
-
-    @property
-    def on_device(self) -> bool:
-        return bool(lib().acx_rows_on_device(self._h))
+    _ON_DEVICE, _FREE = "acx_rows_on_device", "acx_free_rows"
 
     @property
     def device(self) -> int:
@@ -1049,17 +961,6 @@ class DeviceRows:
         out = np.zeros(self.rows + 1, dtype=np.int64)
         _check(lib().acx_rows_copy(self._h, out.ctypes.data))
         return out
-
-    def free(self) -> None:
-        if self._h:
-            lib().acx_free_rows(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def split_rows(hay, delimiter: int = 10) -> DeviceRows:
@@ -1134,8 +1035,10 @@ def _take_matches(ptr: Optional[int], n: int) -> np.ndarray:
     return np.frombuffer(buf, dtype=MATCH_DTYPE)
 
 
-class Automaton:
+class Automaton(_Handle):
     """acx_automaton_t: compiled patterns + device tables."""
+    _FREE = "acx_free_automaton"
+    close = _Handle.free
 
     def __init__(self, patterns: Sequence[bytes], match_kind: int = MATCH_STANDARD,
                  implementation: int = IMPL_AUTO, kernel: Optional[int] = None, ascii_case_insensitive: bool = False):
@@ -1147,17 +1050,6 @@ class Automaton:
         self._h = h.value
         if kernel is not None:
             self.set_kernel(kernel)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            lib().acx_free_automaton(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def info(self) -> Info:

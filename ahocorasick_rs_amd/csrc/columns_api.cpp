@@ -30,17 +30,15 @@ namespace {
 int run_columns(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping,
                 int codepoints, acx_columns **out) {
     *out = nullptr;
-    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
+    const bool segmented = rows_of(G).segmented;
     acx_result *r = nullptr;
     if (!(segmented && G.n_hay == 0)) { // (an empty batch: nothing to search, one row offset)
         int rc = run_find(a, x, d_hay, len, G, overlapping, codepoints, &r);
         if (rc != ACX_OK) return rc;
     }
-    acx_columns *R = new (std::nothrow) acx_columns();
-    if (!R) { acx_free_result(r); return fail(ACX_ENOMEM, "out of memory"); }
+    acx_columns *R = new_result<acx_columns>(a->device, true);
+    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
     hipStream_t st = x->stream;
-    R->device = a->device;
-    R->on_device = 1;
     R->batch = segmented;
     R->rows = segmented ? G.n_hay : 0;
     R->n = r ? r->n : 0;
@@ -85,12 +83,10 @@ int acx_split_device(const acx_match_t *d_m, uint64_t n, int64_t *d_pattern, int
     if (!d_m || !d_pattern || !d_start || !d_end) return fail(ACX_EINVAL, "null argument");
     if (((uintptr_t)d_m | (uintptr_t)d_pattern | (uintptr_t)d_start | (uintptr_t)d_end) & 7)
         return fail(ACX_EINVAL, "records and columns must be 8-byte aligned");
-    hipPointerAttribute_t at;
-    HIPCHK(hipPointerGetAttributes(&at, d_m));
-    DeviceScope ds(at.device);
-    HIPCHK(acx::col_split(d_m, n, d_pattern, d_start, d_end, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    return ACX_OK;
+    return rows_call(d_m, [&](int, void **, void **) -> int {
+        HIPCHK(acx::col_split(d_m, n, d_pattern, d_start, d_end, nullptr));
+        return ACX_OK;
+    });
 }
 
 int acx_find_columns(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
@@ -101,17 +97,10 @@ int acx_find_columns(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const
     acx_match_t *m = nullptr;
     uint64_t nm = 0;
     std::vector<uint64_t> counts;
-    int rc;
-    if (offsets) {
-        try { counts.assign(n_hay, 0); } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
-        rc = acx_find_batch(a, hay, offsets, n_hay, overlapping, codepoints, &m, &nm, counts.data());
-    } else {
-        rc = acx_find(a, hay, len, overlapping, codepoints, &m, &nm);
-    }
+    int rc = host_find(a, hay, len, offsets, n_hay, overlapping, codepoints, &m, &nm, &counts);
     if (rc != ACX_OK) return rc;
-    acx_columns *R = new (std::nothrow) acx_columns();
-    if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
-    R->device = a->device;
+    acx_columns *R = new_result<acx_columns>(a->device, false);
+    if (!R) { acx_free_matches(m); return ACX_ENOMEM; }
     R->batch = offsets != nullptr;
     R->rows = R->batch ? n_hay : 0;
     R->n = nm;
@@ -155,10 +144,6 @@ int acx_columns_copy(const acx_columns_t *c, int which, int64_t *host_dst) {
     return c->copy_out(host_dst, c->col[which], words * 8);
 }
 
-void acx_free_columns(acx_columns_t *c) {
-    if (!c) return;
-    c->release();
-    delete c;
-}
+void acx_free_columns(acx_columns_t *c) { free_result(c); }
 
 } // extern "C"

@@ -113,18 +113,15 @@ int check_args(uint64_t min_matches, uint32_t flags) {
 int run_filter(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_search, uint64_t len, const Segments &G,
                int overlapping, uint64_t min_matches, uint32_t flags, acx_filtered_t **out, const ScoreBy *by = nullptr) {
     *out = nullptr;
-    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
-    const uint64_t n = segmented ? G.n_hay : 1;
+    const uint64_t n = rows_of(G).n;
     acx_result *r = nullptr;
     if (n) { // (an empty batch: nothing to search, one offset)
         int rc = run_find(a, x, d_search, len, G, overlapping, 0, &r);
         if (rc != ACX_OK) return rc;
     }
-    acx_filtered_t *R = new (std::nothrow) acx_filtered_t();
-    if (!R) { acx_free_result(r); return fail(ACX_ENOMEM, "out of memory"); }
+    acx_filtered_t *R = new_result<acx_filtered_t>(a->device, true);
+    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
     hipStream_t st = x->stream;
-    R->device = a->device;
-    R->on_device = 1;
     R->n_src = n;
     Stage S;
     ScoreTemps T;
@@ -163,9 +160,8 @@ int host_filtered(const acx_automaton *a, const HostBatch &B, uint64_t len, uint
     uint64_t k = 0, total = 0;
     int rc = acx_filter_host(B.hay, len, B.rel.data(), n_hay, counts, min_matches, flags, nullptr, nullptr, nullptr, &k, &total);
     if (rc != ACX_OK) return rc;
-    acx_filtered_t *R = new (std::nothrow) acx_filtered_t();
-    if (!R) return fail(ACX_ENOMEM, "out of memory");
-    R->device = a->device;
+    acx_filtered_t *R = new_result<acx_filtered_t>(a->device, false);
+    if (!R) return ACX_ENOMEM;
     R->n_src = n_hay;
     R->rows = k;
     R->bytes = total;
@@ -187,13 +183,8 @@ int acx_filter_host(const uint8_t *hay, uint64_t len, const uint64_t *offsets, u
     int rc = check_args(min_matches, flags);
     if (rc != ACX_OK) return rc;
     if (!n_rows || !n_bytes || (n_hay && !counts) || (len && dst && !hay)) return fail(ACX_EINVAL, "null argument");
-    if (!offsets) {
-        if (n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
-    } else {
-        if (offsets[0] != 0 || offsets[n_hay] != len) return fail(ACX_EINVAL, "offsets must rise from 0 to the batch's length");
-        for (uint64_t h = 0; h < n_hay; h++)
-            if (offsets[h + 1] < offsets[h]) return fail(ACX_EINVAL, "offsets must rise from 0 to the batch's length");
-    }
+    if (!offsets && n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
+    if (offsets && (rc = offsets_span(offsets, n_hay, len)) != ACX_OK) return rc;
     const bool keep_matched = (flags & ACX_FILTER_KEEP_MATCHED) != 0;
     uint64_t k = 0, at = 0;
     for (uint64_t h = 0; h < n_hay; h++) {
@@ -292,35 +283,25 @@ int acx_filter_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_of
     if (rc != ACX_OK) return rc;
     if (!d_out_offsets || !n_rows || !n_bytes) return fail(ACX_EINVAL, "null argument");
     *n_rows = *n_bytes = 0;
-    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
-    if (!d_offsets && !uniform_len) n_hay = 1;
-    if (uniform_len && n_hay * uniform_len != len) return fail(ACX_EINVAL, "n_hay * uniform_len is not the batch's length");
+    if ((rc = device_rows_args(d_offsets, &n_hay, uniform_len, len)) != ACX_OK) return rc;
     if ((n_hay && (!d_counts || !d_rows)) || (len && (!d_hay || !d_data))) return fail(ACX_EINVAL, "null argument");
     if (((uintptr_t)d_offsets | (uintptr_t)d_counts | (uintptr_t)d_rows | (uintptr_t)d_out_offsets) & 7)
         return fail(ACX_EINVAL, "offsets, counts and the word outputs must be 8-byte aligned");
     if ((uintptr_t)d_data & 15) return fail(ACX_EINVAL, "the data output must be 16-byte aligned");
-    hipPointerAttribute_t at;
-    HIPCHK(hipPointerGetAttributes(&at, d_out_offsets));
-    DeviceScope ds(at.device);
-    if (!n_hay) {
-        HIPCHK(hipMemsetAsync(d_out_offsets, 0, 8, nullptr));
-        HIPCHK(hipStreamSynchronize(nullptr));
-        return ACX_OK;
-    }
-    if (d_offsets) { // where the offsets begin and end; between the two they are the caller's word
-        uint64_t ends[2] = {1, 0};
-        HIPCHK(hipMemcpy(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(&ends[1], d_offsets + n_hay, 8, hipMemcpyDeviceToHost));
-        if (ends[0] != 0 || ends[1] != len) return fail(ACX_EINVAL, "offsets must rise from 0 to the batch's length");
-    }
-    Stage S;
     uint64_t k = 0, total = 0;
-    const acx::FilterRows rows{d_offsets, uniform_len, n_hay, len};
-    rc = stage_sizes(at.device, nullptr, rows, d_counts, min_matches, (flags & ACX_FILTER_KEEP_MATCHED) != 0, &S, &k, &total);
-    if (rc == ACX_OK) rc = stage_finish(&S, (const uint8_t *)d_hay, k, total, d_rows, d_out_offsets, d_data, nullptr);
-    const hipError_t e = hipStreamSynchronize(nullptr);
-    g_bufs.put(S.block, at.device);
-    if (rc == ACX_OK && e != hipSuccess) rc = hipfail(e, "hipStreamSynchronize");
+    rc = rows_call(d_out_offsets, [&](int device, void **block, void **) -> int {
+        if (!n_hay) { // (no row: the one offset)
+            HIPCHK(hipMemsetAsync(d_out_offsets, 0, 8, nullptr));
+            return ACX_OK;
+        }
+        int rs = device_offsets_span(d_offsets, n_hay, len);
+        if (rs != ACX_OK) return rs;
+        Stage S;
+        const acx::FilterRows rows{d_offsets, uniform_len, n_hay, len};
+        rs = stage_sizes(device, nullptr, rows, d_counts, min_matches, (flags & ACX_FILTER_KEEP_MATCHED) != 0, &S, &k, &total);
+        *block = S.block;
+        return rs == ACX_OK ? stage_finish(&S, (const uint8_t *)d_hay, k, total, d_rows, d_out_offsets, d_data, nullptr) : rs;
+    });
     if (rc == ACX_OK) { *n_rows = k; *n_bytes = total; }
     return rc;
 }
@@ -341,10 +322,6 @@ int acx_filtered_copy(const acx_filtered_t *f, int which, void *host_dst) {
     return f->copy_out(host_dst, f->part[which], bytes);
 }
 
-void acx_free_filtered(acx_filtered_t *f) {
-    if (!f) return;
-    f->release();
-    delete f;
-}
+void acx_free_filtered(acx_filtered_t *f) { free_result(f); }
 
 } // extern "C"

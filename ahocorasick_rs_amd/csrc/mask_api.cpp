@@ -32,10 +32,9 @@ int check_flags(uint32_t flags) {
 }
 
 // The device stage on stream st: d_out becomes a copy of d_hay (or zeros: ACX_MASK_ZERO; or stays as it is: d_out == d_hay),
-// then the records' bytes are painted.  d_m: n records; d_counts: R.rows words that sum to n (check_sum: they are a caller's
-// -- read back and compared before a kernel reads a record by them).  No record, no row or no byte: nothing beyond the copy
-// or the clear.  *block: the stage's temporaries, one block of the buffer cache -- the caller's to return, behind the
-// stage's kernels.
+// then the records' bytes are painted.  d_m: n records; d_counts: R.rows words that sum to n (check_sum: record_offsets,
+// behind the copy or the clear).  No record, no row or no byte: nothing beyond the copy or the clear.  *block: the stage's
+// temporaries, one block of the buffer cache -- the caller's to return, behind the stage's kernels.
 int mask_stage(int device, hipStream_t st, const uint8_t *d_hay, const acx::MaskRows &R, const acx_match_t *d_m, uint64_t n,
                const uint64_t *d_counts, bool check_sum, uint8_t fill, uint32_t flags, uint8_t *d_out, void **block) {
     if (R.len && d_out != d_hay) {
@@ -49,13 +48,7 @@ int mask_stage(int device, hipStream_t st, const uint8_t *d_hay, const acx::Mask
     HIPCHK(g_bufs.get(block, C.bytes(), device));
     uint64_t *b = (uint64_t *)*block;
     int64_t *rec_off = (int64_t *)(b + o_rec);
-    HIPCHK(acx::replace_scan(nullptr, nullptr, d_counts, R.rows, rec_off, b + o_scan, st));
-    if (check_sum) {
-        uint64_t sum = 0;
-        HIPCHK(hipMemcpyAsync(&sum, rec_off + R.rows, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (sum != n) return fail(ACX_EINVAL, "the counts do not sum to the number of records");
-    }
+    if (int rc = record_offsets(d_counts, R.rows, n, check_sum, rec_off, b + o_scan, st)) return rc;
     HIPCHK(acx::mask_paint(d_m, n, rec_off, R, fill, b + o_tiles, d_out, st));
     return ACX_OK;
 }
@@ -66,18 +59,16 @@ int mask_stage(int device, hipStream_t st, const uint8_t *d_hay, const acx::Mask
 int run_mask(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_search, uint64_t len, const Segments &G,
              int overlapping, uint8_t fill, uint32_t flags, acx_masked_t **out) {
     *out = nullptr;
-    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
-    const uint64_t rows = segmented ? G.n_hay : 1;
-    acx_masked_t *R = new (std::nothrow) acx_masked_t();
-    if (!R) return fail(ACX_ENOMEM, "out of memory");
+    const bool segmented = rows_of(G).segmented;
+    const uint64_t rows = rows_of(G).n;
+    acx_masked_t *R = new_result<acx_masked_t>(a->device, true);
+    if (!R) return ACX_ENOMEM;
     acx_result *r = nullptr;
     if (rows && len) { // (an empty batch, or empty rows only: nothing to search)
         int rc = run_find(a, x, d_search, len, G, overlapping, 0, &r);
         if (rc != ACX_OK) { delete R; return rc; }
     }
     hipStream_t st = x->stream;
-    R->device = a->device;
-    R->on_device = 1;
     R->rows = rows;
     R->bytes = len;
     void *block = nullptr;
@@ -116,19 +107,11 @@ int acx_mask_host(const uint8_t *hay, uint64_t len, const uint64_t *offsets, uin
     if (!offsets) {
         if (n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
         n_hay = 1;
-    } else {
-        if (offsets[0] != 0 || offsets[n_hay] != len) return fail(ACX_EINVAL, "offsets must rise from 0 to the batch's length");
-        for (uint64_t h = 0; h < n_hay; h++)
-            if (offsets[h + 1] < offsets[h]) return fail(ACX_EINVAL, "offsets must rise from 0 to the batch's length");
+    } else if ((rc = offsets_span(offsets, n_hay, len)) != ACX_OK) {
+        return rc;
     }
     if (!counts && n_hay > 1) return fail(ACX_EINVAL, "several haystacks need counts");
-    if (!counts && !n_hay && n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
-    uint64_t sum = 0;
-    for (uint64_t h = 0; counts && h < n_hay; h++) {
-        if (counts[h] > n_m - sum) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
-        sum += counts[h];
-    }
-    if (counts && sum != n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+    if ((rc = counts_sum_to(counts, n_hay, n_m)) != ACX_OK) return rc;
     if (len) {
         if (zero) std::memset(dst, 0, len);
         else if (dst != hay) std::memmove(dst, hay, len);
@@ -158,23 +141,16 @@ int acx_mask(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_
     acx_match_t *m = nullptr;
     uint64_t nm = 0;
     std::vector<uint64_t> counts;
-    try {
-        counts.assign(n_hay + 1, 0);
-    } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
-    if (n_hay && len) {
-        rc = offsets ? acx_find_batch(a, B.hay, B.rel.data(), n_hay, overlapping, 0, &m, &nm, counts.data())
-                     : acx_find(a, B.hay, len, overlapping, 0, &m, &nm);
-        if (rc != ACX_OK) return rc;
-        if (!offsets) counts[0] = nm;
-    }
-    acx_masked_t *R = new (std::nothrow) acx_masked_t();
-    if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
-    R->device = a->device;
+    const bool search = n_hay && len; // (an empty batch, or empty rows only: nothing to search, nothing to paint)
+    if (search) rc = host_find(a, B.hay, len, offsets ? B.rel.data() : nullptr, n_hay, overlapping, 0, &m, &nm, &counts);
+    if (rc != ACX_OK) return rc;
+    acx_masked_t *R = new_result<acx_masked_t>(a->device, false);
+    if (!R) { acx_free_matches(m); return ACX_ENOMEM; }
     R->rows = n_hay;
     R->bytes = len;
     if ((rc = R->alloc()) == ACX_OK) {
         for (uint64_t h = 0; h <= n_hay; h++) R->offsets[h] = (int64_t)B.rel[h];
-        rc = acx_mask_host(B.hay, len, B.rel.data(), n_hay, m, nm, counts.data(), fill, flags, R->data);
+        if (search) rc = acx_mask_host(B.hay, len, B.rel.data(), n_hay, m, nm, counts.data(), fill, flags, R->data);
     }
     acx_free_matches(m);
     if (rc != ACX_OK) { acx_free_masked(R); return rc; }
@@ -200,31 +176,19 @@ int acx_mask_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_offs
     int rc = check_flags(flags);
     if (rc != ACX_OK) return rc;
     const bool zero = (flags & ACX_MASK_ZERO) != 0;
-    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
-    if (!d_offsets && !uniform_len) n_hay = 1;
-    if (uniform_len && n_hay * uniform_len != len) return fail(ACX_EINVAL, "n_hay * uniform_len is not the batch's length");
+    if ((rc = device_rows_args(d_offsets, &n_hay, uniform_len, len)) != ACX_OK) return rc;
     if ((len && (!d_out || (!d_hay && !zero))) || (n && (!d_records || !d_counts))) return fail(ACX_EINVAL, "null argument");
     if (zero && len && d_out == d_hay) return fail(ACX_EINVAL, "ACX_MASK_ZERO cannot be made in place");
     if (!n_hay && n) return fail(ACX_EINVAL, "the counts do not sum to the number of records");
     if (((uintptr_t)d_offsets | (uintptr_t)d_records | (uintptr_t)d_counts) & 7)
         return fail(ACX_EINVAL, "offsets, records and counts must be 8-byte aligned");
     if (!len) return ACX_OK; // (no byte to write)
-    hipPointerAttribute_t at;
-    HIPCHK(hipPointerGetAttributes(&at, d_out));
-    DeviceScope ds(at.device);
-    if (d_offsets) { // where the offsets begin and end; between the two they are the caller's word
-        uint64_t ends[2] = {1, 0};
-        HIPCHK(hipMemcpy(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(&ends[1], d_offsets + n_hay, 8, hipMemcpyDeviceToHost));
-        if (ends[0] != 0 || ends[1] != len) return fail(ACX_EINVAL, "offsets must rise from 0 to the batch's length");
-    }
-    void *block = nullptr;
-    const acx::MaskRows R{d_offsets, uniform_len, n_hay, len};
-    rc = mask_stage(at.device, nullptr, (const uint8_t *)d_hay, R, d_records, n, d_counts, true, fill, flags, (uint8_t *)d_out, &block);
-    const hipError_t e = hipStreamSynchronize(nullptr);
-    g_bufs.put(block, at.device);
-    if (rc == ACX_OK && e != hipSuccess) rc = hipfail(e, "hipStreamSynchronize");
-    return rc;
+    return rows_call(d_out, [&](int device, void **block, void **) {
+        const int span = device_offsets_span(d_offsets, n_hay, len);
+        if (span != ACX_OK) return span;
+        const acx::MaskRows R{d_offsets, uniform_len, n_hay, len};
+        return mask_stage(device, nullptr, (const uint8_t *)d_hay, R, d_records, n, d_counts, true, fill, flags, (uint8_t *)d_out, block);
+    });
 }
 
 uint64_t acx_masked_rows(const acx_masked_t *m) { return m ? m->rows : 0; }
@@ -244,10 +208,6 @@ int acx_masked_copy_offsets(const acx_masked_t *m, int64_t *host_dst) {
     return m->copy_out(host_dst, m->offsets, (m->rows + 1) * 8);
 }
 
-void acx_free_masked(acx_masked_t *m) {
-    if (!m) return;
-    m->release();
-    delete m;
-}
+void acx_free_masked(acx_masked_t *m) { free_result(m); }
 
 } // extern "C"

@@ -29,14 +29,12 @@ int run_replace(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d
     acx_result *r = nullptr;
     int rc = run_find(a, x, d_hay, len, G, 0, 0, &r);
     if (rc != ACX_OK) return rc;
-    acx_replaced *R = new (std::nothrow) acx_replaced();
-    if (!R) { acx_free_result(r); return fail(ACX_ENOMEM, "out of memory"); }
-    R->device = a->device;
-    R->on_device = 1;
+    acx_replaced *R = new_result<acx_replaced>(a->device, true);
+    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
     R->find = r;
     hipStream_t st = x->stream;
-    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
-    const uint64_t n_hay = segmented ? G.n_hay : 1, n = r->n;
+    const bool segmented = rows_of(G).segmented;
+    const uint64_t n_hay = rows_of(G).n, n = r->n;
     const uint64_t r0 = n_repl ? repl_offsets[0] : 0, blob_len = n_repl ? repl_offsets[n_repl] - r0 : 0;
     std::vector<uint64_t> roff(n_repl + 1);
     for (uint64_t i = 0; i <= n_repl; i++) roff[i] = n_repl ? repl_offsets[i] - r0 : 0;
@@ -153,17 +151,11 @@ int acx_replace(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint
         // host route: the find entry points as they are (K0, the resident K0, the in-place read), then the splice here
         acx_match_t *m = nullptr;
         uint64_t nm = 0;
-        std::vector<uint64_t> counts(n_hay, 0);
-        if (!offsets) {
-            rc = acx_find(a, h, len, 0, 0, &m, &nm);
-            counts[0] = nm;
-        } else if (n_hay) {
-            rc = acx_find_batch(a, h, rel.data(), n_hay, 0, 0, &m, &nm, counts.data());
-        }
+        std::vector<uint64_t> counts;
+        rc = host_find(a, h, len, offsets ? rel.data() : nullptr, n_hay, 0, 0, &m, &nm, &counts);
         if (rc != ACX_OK) return rc;
-        acx_replaced *R = new (std::nothrow) acx_replaced();
-        if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
-        R->device = a->device;
+        acx_replaced *R = new_result<acx_replaced>(a->device, false);
+        if (!R) { acx_free_matches(m); return ACX_ENOMEM; }
         R->offsets.assign(n_hay + 1, 0);
         uint64_t at = 0;
         for (uint64_t i = 0; i < n_hay && rc == ACX_OK; i++) { // (sizes first: one allocation)
@@ -190,15 +182,9 @@ int acx_replace(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint
         return ACX_OK;
     }
     // device route: staged, searched and spliced under one lease
-    Lease lease(a);
-    Ctx *c = lease.c;
-    if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    rc = stage_host(a, c, h, len, offsets ? rel.data() : nullptr, offsets ? n_hay + 1 : 0, false);
-    if (rc != ACX_OK) return rc;
-    const uint8_t *d_search = nullptr;
-    if ((rc = fold_copy(a, c, c->ws.hay, len, &d_search)) != ACX_OK) return rc;
-    const Segments G = offsets ? Segments{c->ws.offsets, n_hay, 0} : Segments{nullptr, 1, 0};
-    return run_replace(a, c, d_search, c->ws.hay, len, G, repl_blob, repl_offsets, n_repl, out);
+    return staged_call(a, B, len, n_hay, offsets != nullptr, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_replace(a, c, d_search, c->ws.hay, len, G, repl_blob, repl_offsets, n_repl, out);
+    });
 }
 
 int acx_replace_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
@@ -235,10 +221,9 @@ int acx_replaced_copy(const acx_replaced_t *r, void *host_dst) {
 const void *acx_replaced_device_bytes(const acx_replaced_t *r) { return r && r->on_device ? r->ptr_after_wait(r->d_block) : nullptr; }
 
 void acx_free_replaced(acx_replaced_t *r) {
-    if (!r) return;
-    r->release(); // (the gather reads the find result as well: it goes after the wait)
-    acx_free_result(r->find);
-    delete r;
+    acx_result *find = r ? r->find : nullptr;
+    free_result(r); // (the gather reads the find result as well: it goes after the wait)
+    acx_free_result(find);
 }
 
 } // extern "C"

@@ -1,5 +1,8 @@
-// result_block.cpp -- the owner of a post-find result's memory and the end of a post-find stage (result_block.hpp).
+// result_block.cpp -- the owner of a post-find result's memory, the end of a post-find stage and the checks and the find
+// that the stages' entry points share (result_block.hpp).
 #include "result_block.hpp"
+
+#include "replace.hpp"
 
 namespace acxh ACX_HIDDEN {
 
@@ -127,6 +130,65 @@ int counts_of(const acx_result *r, hipStream_t st, uint64_t **one, const uint64_
     HIPCHK(hipMemcpyAsync(*one, &r->n, 8, hipMemcpyHostToDevice, st));
     *d_counts = *one;
     return ACX_OK;
+}
+
+int record_offsets(const uint64_t *d_counts, uint64_t rows, uint64_t n, bool check_sum, int64_t *rec_off, uint64_t *scan_tmp,
+                   hipStream_t st) {
+    HIPCHK(acx::replace_scan(nullptr, nullptr, d_counts, rows, rec_off, scan_tmp, st));
+    if (!check_sum) return ACX_OK;
+    uint64_t sum = 0;
+    HIPCHK(hipMemcpyAsync(&sum, rec_off + rows, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return sum == n ? ACX_OK : fail(ACX_EINVAL, "the counts do not sum to the number of records");
+}
+
+int counts_sum_to(const uint64_t *counts, uint64_t n_hay, uint64_t n_m) {
+    bool ok = counts || n_hay || !n_m;
+    uint64_t sum = 0;
+    for (uint64_t h = 0; ok && counts && h < n_hay; h++) {
+        ok = counts[h] <= n_m - sum;
+        sum += ok ? counts[h] : 0;
+    }
+    if (counts && sum != n_m) ok = false;
+    return ok ? ACX_OK : fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+}
+
+namespace {
+int span_error() { return fail(ACX_EINVAL, "offsets must rise from 0 to the batch's length"); }
+} // namespace
+
+int offsets_span(const uint64_t *offsets, uint64_t n_hay, uint64_t len) {
+    bool ok = offsets[0] == 0 && offsets[n_hay] == len;
+    for (uint64_t h = 0; ok && h < n_hay; h++) ok = offsets[h + 1] >= offsets[h];
+    return ok ? ACX_OK : span_error();
+}
+
+int device_rows_args(const uint64_t *d_offsets, uint64_t *n_hay, uint64_t uniform_len, uint64_t len) {
+    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
+    if (!d_offsets && !uniform_len) *n_hay = 1;
+    if (uniform_len && *n_hay * uniform_len != len) return fail(ACX_EINVAL, "n_hay * uniform_len is not the batch's length");
+    return ACX_OK;
+}
+
+int device_offsets_span(const uint64_t *d_offsets, uint64_t n_hay, uint64_t len) {
+    if (!d_offsets) return ACX_OK;
+    uint64_t ends[2] = {1, 0};
+    HIPCHK(hipMemcpy(&ends[0], d_offsets, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&ends[1], d_offsets + n_hay, 8, hipMemcpyDeviceToHost));
+    return ends[0] == 0 && ends[1] == len ? ACX_OK : span_error();
+}
+
+int host_find(acx_automaton *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
+              int codepoints, acx_match_t **m, uint64_t *nm, std::vector<uint64_t> *counts) {
+    *m = nullptr;
+    *nm = 0;
+    try {
+        counts->assign((offsets ? n_hay : 1) + 1, 0);
+    } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
+    if (offsets) return acx_find_batch(a, hay, offsets, n_hay, overlapping, codepoints, m, nm, counts->data());
+    const int rc = acx_find(a, hay, len, overlapping, codepoints, m, nm);
+    (*counts)[0] = *nm;
+    return rc;
 }
 
 int host_batch(const uint8_t *hay, uint64_t *len, const uint64_t *offsets, uint64_t *n_hay, HostBatch *B) {

@@ -1,5 +1,6 @@
 // result_block.hpp -- what the stages behind the find pipeline (summaries, splice, columns, tally, row filter, scores) share: the
-// owner of a result's memory, the layout of its block, the end of a stage (retire_find) and the frame of its entry points.
+// owner of a result's memory, the layout of its block, the end of a stage (retire_find), the checks of its arguments and the
+// frames of its entry points.
 // The stages' middles are their own (summary_api.cpp .. filter_api.cpp); no kernel includes this.
 #pragma once
 #include <initializer_list>
@@ -31,6 +32,23 @@ struct ResultBlock {
     // and read the scratch: nothing goes back to a pool before they are done)
     void release();
 };
+
+// A stage's result (a ResultBlock with the stage's own fields), empty; null: out of memory, the error is set.
+template <class T>
+T *new_result(int device, bool on_device) {
+    T *R = new (std::nothrow) T();
+    if (!R) { (void)fail(ACX_ENOMEM, "out of memory"); return nullptr; }
+    R->device = device;
+    R->on_device = on_device;
+    return R;
+}
+// ... and its end (acx_free_*): behind the kernels that write it; null: nothing
+template <class T>
+void free_result(T *r) {
+    if (!r) return;
+    r->release();
+    delete r;
+}
 
 // Where the parts of a block begin, in bytes, and the block's size: every part at least one word long (an empty part still
 // has an address that DLPack consumers accept) and a multiple of 256 bytes behind the previous one.  The last part is
@@ -74,6 +92,52 @@ int retire_find(int rc, hipStream_t st, acx_result *r, ResultBlock *R, void *t1 
 // none), its total uploaded to *one -- a temporary for retire_find.
 int counts_of(const acx_result *r, hipStream_t st, uint64_t **one, const uint64_t **d_counts);
 
+// The rows a stage makes of a find's segments: G.n_hay of them, or -- neither offsets nor a row length: no batch -- one.
+struct Rows {
+    bool segmented;
+    uint64_t n;
+};
+inline Rows rows_of(const Segments &G) {
+    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
+    return Rows{segmented, segmented ? G.n_hay : 1};
+}
+
+// Where every row's records begin: the scan of d_counts (rows words, rows > 0) into rec_off (rows + 1 words) on st;
+// scan_tmp: replace_scan_words(rows) words.  check_sum: the counts are a caller's -- their sum is read back (st is waited
+// for) and must be n before a kernel reads a record by them.
+int record_offsets(const uint64_t *d_counts, uint64_t rows, uint64_t n, bool check_sum, int64_t *rec_off, uint64_t *scan_tmp,
+                   hipStream_t st);
+
+// The *_host forms' check that n_hay counts sum to n_m, whatever the counts are (no sum wraps).  Null counts: one haystack
+// holds every match -- there must be one, or no match.
+int counts_sum_to(const uint64_t *counts, uint64_t n_hay, uint64_t n_m);
+// ... and that n_hay + 1 offsets rise from 0 to len
+int offsets_span(const uint64_t *offsets, uint64_t n_hay, uint64_t len);
+
+// How a *_rows_device entry's bytes are cut, in front of its other checks: offsets and a row length exclude one another,
+// neither is one row (*n_hay becomes 1), and rows of one length fill the batch.
+int device_rows_args(const uint64_t *d_offsets, uint64_t *n_hay, uint64_t uniform_len, uint64_t len);
+// ... and, on the data's device: device offsets (null: nothing) begin at 0 and end at len -- two words are read back; between
+// the two they are the caller's word
+int device_offsets_span(const uint64_t *d_offsets, uint64_t n_hay, uint64_t len);
+
+// The frame of a *_rows_device entry behind its argument checks: on the device that holds `where`, body(device, &t1, &t2)
+// queues the stage on the null stream and names its temporaries (blocks of the buffer cache, or null); the stream is waited
+// for whatever the body returned, then the temporaries go back to the cache.  The body's error comes first.
+template <typename Body>
+int rows_call(const void *where, Body &&body) {
+    hipPointerAttribute_t at;
+    HIPCHK(hipPointerGetAttributes(&at, where));
+    DeviceScope ds(at.device);
+    void *t1 = nullptr, *t2 = nullptr;
+    int rc = body(at.device, &t1, &t2);
+    const hipError_t e = hipStreamSynchronize(nullptr);
+    g_bufs.put(t1, at.device);
+    g_bufs.put(t2, at.device);
+    if (rc == ACX_OK && e != hipSuccess) rc = hipfail(e, "hipStreamSynchronize");
+    return rc;
+}
+
 // The score stage (score.hpp; score_api.cpp) behind a find's records and counts, for acx_score_device, acx_score_rows_device
 // and the hook of acx_filter_scored_device.  Its temporaries are one block of the buffer cache -- the caller's to return,
 // behind the stage's kernels.
@@ -82,9 +146,9 @@ struct ScoreTemps {
     int64_t *score = nullptr;  // the scores: d_score, or a part of the block
     uint64_t *flags = nullptr; // score >= *min_score as 0 / 1 words (min_score != null): the row filter's counts
 };
-// d_m: n records; d_counts: rows words (rows > 0) that sum to n (check_sum: they are a caller's -- read back and compared
-// before a kernel reads a record by them).  The weights, n_patterns of them: h_weights (host memory that stays valid until
-// the stream has passed the copy) or d_weights (device memory).  d_score: rows words, or null: in the block.
+// d_m: n records; d_counts: rows words (rows > 0) that sum to n (check_sum: record_offsets below).  The weights, n_patterns
+// of them: h_weights (host memory that stays valid until the stream has passed the copy) or d_weights (device memory).
+// d_score: rows words, or null: in the block.
 int score_stage(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, const uint64_t *d_counts, uint64_t rows,
                 const int32_t *h_weights, const int32_t *d_weights, uint64_t n_patterns, bool check_sum, int64_t *d_score,
                 const int64_t *min_score, ScoreTemps *T);
@@ -115,6 +179,46 @@ int device_call(acx_automaton *a, const void *d_hay, uint64_t len, const uint64_
     rc = fold_copy(a, lease.c, (const uint8_t *)d_hay, len, &d_search);
     if (rc != ACX_OK) return rc;
     return run(lease.c, d_search, G);
+}
+
+// The host route's find: acx_find (offsets == null: one haystack of len bytes, (*counts)[0] becomes its matches) or
+// acx_find_batch as they are -- the small-call kernel, its resident form, the in-place read, the staged pipeline, each
+// under its own lease.  *m: the matches, the caller's to free (acx_free_matches) whatever happens later; *counts: a word
+// per haystack and one more (an empty batch still has a pointer to give).
+int host_find(acx_automaton *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
+              int codepoints, acx_match_t **m, uint64_t *nm, std::vector<uint64_t> *counts);
+
+// The staged device route of a host entry point, the mirror of device_call: the lease, the haystacks (and, for a batch,
+// B's offsets) staged, the folded copy of a case-insensitive handle; then run(ctx, d_search, segments) under the lease --
+// the staged bytes are ctx->ws.hay.  A run whose result goes home (copy_down) waits for it there: the staging buffers are
+// the context's.  No batch: ONE haystack, no offsets.
+template <typename Run>
+int staged_call(acx_automaton *a, const HostBatch &B, uint64_t len, uint64_t n_hay, bool batch, Run &&run) {
+    Lease lease(a);
+    Ctx *c = lease.c;
+    if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
+    int rc = stage_host(a, c, B.hay, len, batch ? B.rel.data() : nullptr, batch ? n_hay + 1 : 0, false);
+    if (rc != ACX_OK) return rc;
+    const uint8_t *d_search = nullptr;
+    if ((rc = fold_copy(a, c, c->ws.hay, len, &d_search)) != ACX_OK) return rc;
+    return run(c, d_search, batch ? Segments{c->ws.offsets, n_hay, 0} : Segments{nullptr, 1, 0});
+}
+
+// The end of a staged call whose result goes home: `bytes` of D's block (the device result, waited for under the lease;
+// null when rc says the call failed) come down into R's (its host twin; null: out of memory) in one copy.  D is freed
+// either way; *out becomes R, which is freed on failure.
+template <class T>
+int copy_down(int rc, T *D, T *R, uint64_t bytes, const char *what, T **out) {
+    if (rc == ACX_OK && !R) rc = fail(ACX_ENOMEM, "out of memory");
+    if (rc == ACX_OK) {
+        DeviceScope ds(D->device);
+        const hipError_t e = hipMemcpy(R->h_block, D->d_block, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = hipfail(e, what);
+    }
+    free_result(D);
+    if (rc != ACX_OK) { free_result(R); return rc; }
+    *out = R;
+    return ACX_OK;
 }
 
 } // namespace acxh

@@ -96,8 +96,8 @@ int acx_split_rows(const uint8_t *hay, uint64_t len, uint8_t delimiter, acx_rows
     if (!out) return fail(ACX_EINVAL, "null argument");
     *out = nullptr;
     if (len && !hay) return fail(ACX_EINVAL, "null argument");
-    acx_rows_t *R = new (std::nothrow) acx_rows_t();
-    if (!R) return fail(ACX_ENOMEM, "out of memory");
+    acx_rows_t *R = new_result<acx_rows_t>(0, false);
+    if (!R) return ACX_ENOMEM;
     R->rows = host_cut(hay, len, delimiter, nullptr);
     R->bytes = len;
     int rc = R->alloc();
@@ -120,10 +120,8 @@ int acx_split_rows_device(const void *d_hay, uint64_t len, uint8_t delimiter, ac
         HIPCHK(hipGetDevice(&device)); // (no byte, no pointer to ask: the calling thread's device)
     }
     DeviceScope ds(device);
-    acx_rows_t *R = new (std::nothrow) acx_rows_t();
-    if (!R) return fail(ACX_ENOMEM, "out of memory");
-    R->device = device;
-    R->on_device = 1;
+    acx_rows_t *R = new_result<acx_rows_t>(device, true);
+    if (!R) return ACX_ENOMEM;
     R->bytes = len;
     Stage S;
     auto body = [&]() -> int {
@@ -153,25 +151,18 @@ int acx_split_rows_into_device(const void *d_hay, uint64_t len, uint8_t delimite
         DeviceScope ds(at.device);
         return zero_word(d_offsets);
     }
-    hipPointerAttribute_t at;
-    HIPCHK(hipPointerGetAttributes(&at, d_hay));
-    DeviceScope ds(at.device);
-    Stage S;
-    uint64_t rows = 0;
-    int rc = stage_sizes(at.device, nullptr, (const uint8_t *)d_hay, len, delimiter, &S, &rows);
-    if (rc == ACX_OK) {
+    return rows_call(d_hay, [&](int device, void **block, void **) -> int {
+        Stage S;
+        uint64_t rows = 0;
+        const int rc = stage_sizes(device, nullptr, (const uint8_t *)d_hay, len, delimiter, &S, &rows);
+        *block = S.block;
+        if (rc != ACX_OK) return rc;
         *n_rows = rows;
-        if (d_offsets && rows + 1 > capacity) {
-            rc = too_small(rows, capacity);
-        } else if (d_offsets) {
-            const hipError_t e = acx::rows_write((const uint8_t *)d_hay, len, delimiter, S.base, S.total, S.open, d_offsets, nullptr);
-            if (e != hipSuccess) rc = hipfail(e, "rows_write");
-        }
-    }
-    const hipError_t e = hipStreamSynchronize(nullptr);
-    g_bufs.put(S.block, at.device);
-    if (rc == ACX_OK && e != hipSuccess) rc = hipfail(e, "hipStreamSynchronize");
-    return rc;
+        if (!d_offsets) return ACX_OK;
+        if (rows + 1 > capacity) return too_small(rows, capacity);
+        const hipError_t e = acx::rows_write((const uint8_t *)d_hay, len, delimiter, S.base, S.total, S.open, d_offsets, nullptr);
+        return e == hipSuccess ? ACX_OK : hipfail(e, "rows_write");
+    });
 }
 
 uint64_t acx_rows_count(const acx_rows_t *r) { return r ? r->rows : 0; }
@@ -186,10 +177,6 @@ int acx_rows_copy(const acx_rows_t *r, int64_t *host_dst) {
     return r->copy_out(host_dst, r->offsets, (r->rows + 1) * 8);
 }
 
-void acx_free_rows(acx_rows_t *r) {
-    if (!r) return;
-    r->release();
-    delete r;
-}
+void acx_free_rows(acx_rows_t *r) { free_result(r); }
 
 } // extern "C"

@@ -41,13 +41,8 @@ int score_stage(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, 
         if (n_patterns) HIPCHK(hipMemcpyAsync(b + o_w, h_weights, n_patterns * 4, hipMemcpyHostToDevice, st));
         d_weights = (const int32_t *)(b + o_w);
     }
-    HIPCHK(acx::replace_scan(nullptr, nullptr, d_counts, rows, rec_off, b + o_scan, st));
-    if (check_sum) {
-        uint64_t sum = 0;
-        HIPCHK(hipMemcpyAsync(&sum, rec_off + rows, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (sum != n) return fail(ACX_EINVAL, "the counts do not sum to the number of records");
-    }
+    int rc = record_offsets(d_counts, rows, n, check_sum, rec_off, b + o_scan, st);
+    if (rc != ACX_OK) return rc;
     HIPCHK(acx::score_rows(d_m, n, rec_off, rows, d_weights, n_patterns, b + o_tiles, T->score, st));
     if (min_score) {
         T->flags = b + o_flags;
@@ -79,10 +74,9 @@ int check_weights(const acx_automaton *a, const int32_t *weights, uint64_t n_wei
 int run_score(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping,
               const int32_t *weights, uint64_t n_weights, acx_scores_t **out) {
     *out = nullptr;
-    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
-    const uint64_t rows = segmented ? G.n_hay : 1;
-    acx_scores_t *R = new (std::nothrow) acx_scores_t();
-    if (!R) return fail(ACX_ENOMEM, "out of memory");
+    const uint64_t rows = rows_of(G).n;
+    acx_scores_t *R = new_result<acx_scores_t>(a->device, true);
+    if (!R) return ACX_ENOMEM;
     try {
         R->weights.assign(weights, weights + n_weights);
     } catch (...) { delete R; return fail(ACX_ENOMEM, "out of memory"); }
@@ -92,8 +86,6 @@ int run_score(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, cons
         if (rc != ACX_OK) { delete R; return rc; }
     }
     hipStream_t st = x->stream;
-    R->device = a->device;
-    R->on_device = 1;
     R->rows = rows;
     ScoreTemps T;
     uint64_t *one_count = nullptr;
@@ -112,9 +104,8 @@ int run_score(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, cons
 }
 
 acx_scores_t *host_scores(int device, uint64_t rows) {
-    acx_scores_t *R = new (std::nothrow) acx_scores_t();
+    acx_scores_t *R = new_result<acx_scores_t>(device, false);
     if (!R) return nullptr;
-    R->device = device;
     R->rows = rows;
     if (R->alloc() != ACX_OK) { delete R; return nullptr; }
     R->score[0] = 0;
@@ -129,13 +120,7 @@ int acx_score_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts, u
                    uint64_t n_weights, int64_t *scores) {
     if ((n_m && !m) || (n_weights && !weights) || (n_hay && !scores)) return fail(ACX_EINVAL, "null argument");
     if (!counts && n_hay > 1) return fail(ACX_EINVAL, "several haystacks need counts");
-    if (!counts && !n_hay && n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
-    uint64_t sum = 0;
-    for (uint64_t h = 0; counts && h < n_hay; h++) {
-        if (counts[h] > n_m - sum) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
-        sum += counts[h];
-    }
-    if (counts && sum != n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+    if (int rc = counts_sum_to(counts, n_hay, n_m)) return rc;
     uint64_t at = 0;
     for (uint64_t h = 0; h < n_hay; h++) {
         const uint64_t end = counts ? at + counts[h] : n_m;
@@ -160,8 +145,8 @@ int acx_score(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64
         // host route: acx_find_batch as it is (the small-call kernel, the in-place read, the staged pipeline), then the sums here
         acx_match_t *m = nullptr;
         uint64_t nm = 0;
-        std::vector<uint64_t> counts(n_hay, 0);
-        if (n_hay) rc = acx_find_batch(a, B.hay, B.rel.data(), n_hay, overlapping, 0, &m, &nm, counts.data());
+        std::vector<uint64_t> counts;
+        if (n_hay) rc = host_find(a, B.hay, len, B.rel.data(), n_hay, overlapping, 0, &m, &nm, &counts);
         if (rc != ACX_OK) return rc;
         acx_scores_t *R = host_scores(a->device, n_hay);
         if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
@@ -173,29 +158,12 @@ int acx_score(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64
     }
     // device route: staged, searched and scored under one lease; 8 bytes per row come back
     acx_scores_t *D = nullptr;
-    {
-        Lease lease(a);
-        Ctx *c = lease.c;
-        if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-        rc = stage_host(a, c, B.hay, len, B.rel.data(), n_hay + 1, false);
-        if (rc != ACX_OK) return rc;
-        const uint8_t *d_search = nullptr;
-        if ((rc = fold_copy(a, c, c->ws.hay, len, &d_search)) != ACX_OK) return rc;
-        rc = run_score(a, c, d_search, len, Segments{c->ws.offsets, n_hay, 0}, overlapping, weights, n_weights, &D);
-        if (rc != ACX_OK) return rc;
-        rc = D->wait(); // (the staging buffers are the context's: the lease ends behind the kernels)
-    }
-    acx_scores_t *R = rc == ACX_OK ? host_scores(a->device, D->rows) : nullptr;
-    if (rc == ACX_OK && !R) rc = fail(ACX_ENOMEM, "out of memory");
-    if (rc == ACX_OK) {
-        DeviceScope ds(a->device);
-        const hipError_t e = hipMemcpy(R->h_block, D->d_block, D->rows * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hipfail(e, "copying the scores to the host");
-    }
-    acx_free_scores(D);
-    if (rc != ACX_OK) { acx_free_scores(R); return rc; }
-    *out = R;
-    return ACX_OK;
+    rc = staged_call(a, B, len, n_hay, true, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        const int run = run_score(a, c, d_search, len, G, overlapping, weights, n_weights, &D);
+        return run == ACX_OK ? D->wait() : run; // (the staging buffers are the context's: the lease ends behind the kernels)
+    });
+    return copy_down(rc, D, rc == ACX_OK ? host_scores(a->device, D->rows) : nullptr, D ? D->rows * 8 : 0,
+                     "copying the scores to the host", out);
 }
 
 int acx_score_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
@@ -216,15 +184,12 @@ int acx_score_rows_device(const acx_match_t *d_records, uint64_t n, const uint64
     if (((uintptr_t)d_records | (uintptr_t)d_counts | (uintptr_t)d_scores) & 7)
         return fail(ACX_EINVAL, "records, counts and scores must be 8-byte aligned");
     if ((uintptr_t)d_weights & 3) return fail(ACX_EINVAL, "the weights must be 4-byte aligned");
-    hipPointerAttribute_t at;
-    HIPCHK(hipPointerGetAttributes(&at, d_scores));
-    DeviceScope ds(at.device);
-    ScoreTemps T;
-    int rc = score_stage(at.device, nullptr, d_records, n, d_counts, n_hay, nullptr, d_weights, n_weights, true, d_scores, nullptr, &T);
-    const hipError_t e = hipStreamSynchronize(nullptr);
-    g_bufs.put(T.block, at.device);
-    if (rc == ACX_OK && e != hipSuccess) rc = hipfail(e, "hipStreamSynchronize");
-    return rc;
+    return rows_call(d_scores, [&](int device, void **t1, void **) {
+        ScoreTemps T;
+        const int rc = score_stage(device, nullptr, d_records, n, d_counts, n_hay, nullptr, d_weights, n_weights, true, d_scores, nullptr, &T);
+        *t1 = T.block;
+        return rc;
+    });
 }
 
 uint64_t acx_scores_rows(const acx_scores_t *s) { return s ? s->rows : 0; }
@@ -241,10 +206,6 @@ int acx_scores_copy(const acx_scores_t *s, int64_t *host_dst) {
     return s->copy_out(host_dst, s->score, s->rows * 8);
 }
 
-void acx_free_scores(acx_scores_t *s) {
-    if (!s) return;
-    s->release();
-    delete s;
-}
+void acx_free_scores(acx_scores_t *s) { free_result(s); }
 
 } // extern "C"

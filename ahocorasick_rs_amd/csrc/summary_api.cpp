@@ -31,14 +31,12 @@ int run_summary(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, co
     acx_result *r = nullptr;
     int rc = run_find(a, x, d_hay, len, G, overlapping, codepoints, &r);
     if (rc != ACX_OK) return rc;
-    acx_summary *R = new (std::nothrow) acx_summary();
-    if (!R) { acx_free_result(r); return fail(ACX_ENOMEM, "out of memory"); }
+    acx_summary *R = new_result<acx_summary>(a->device, true);
+    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
     hipStream_t st = x->stream;
-    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
-    R->device = a->device;
-    R->on_device = 1;
+    const bool segmented = rows_of(G).segmented;
     R->what = what;
-    R->n_hay = segmented ? G.n_hay : 1;
+    R->n_hay = rows_of(G).n;
     R->n_patterns = a->host.n_patterns;
     R->total = r->n;
     const uint64_t n_hay = R->n_hay, n = r->n;
@@ -99,12 +97,7 @@ int acx_summarize_host(const acx_match_t *m, uint64_t n_m, const uint64_t *count
     if (!counts) n_hay = 1;
     if ((what & ACX_SUM_FIRST) && n_hay && (!any_bits || !first)) return fail(ACX_EINVAL, "null argument");
     if ((what & ACX_SUM_BY_PATTERN) && n_patterns && !by_pattern) return fail(ACX_EINVAL, "null argument");
-    uint64_t sum = 0;
-    for (uint64_t h = 0; counts && h < n_hay; h++) {
-        if (counts[h] > n_m - sum) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
-        sum += counts[h];
-    }
-    if (counts && sum != n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+    if (int rc = counts_sum_to(counts, n_hay, n_m)) return rc;
     for (uint64_t i = 0; i < n_m; i++)
         if (m[i].pattern >= n_patterns)
             return fail(ACX_EINVAL, "match " + std::to_string(i) + " names pattern " + std::to_string(m[i].pattern) + " of " +
@@ -139,17 +132,11 @@ int acx_summarize(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const ui
         // host route: the find entry points as they are (K0, the resident K0, the in-place read), then the reduction here
         acx_match_t *m = nullptr;
         uint64_t nm = 0;
-        std::vector<uint64_t> counts(n_hay, 0);
-        if (!offsets) {
-            rc = acx_find(a, B.hay, len, overlapping, codepoints, &m, &nm);
-            counts[0] = nm;
-        } else if (n_hay) {
-            rc = acx_find_batch(a, B.hay, B.rel.data(), n_hay, overlapping, codepoints, &m, &nm, counts.data());
-        }
+        std::vector<uint64_t> counts;
+        rc = host_find(a, B.hay, len, offsets ? B.rel.data() : nullptr, n_hay, overlapping, codepoints, &m, &nm, &counts);
         if (rc != ACX_OK) return rc;
-        acx_summary *R = new (std::nothrow) acx_summary();
-        if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
-        R->device = a->device;
+        acx_summary *R = new_result<acx_summary>(a->device, false);
+        if (!R) { acx_free_matches(m); return ACX_ENOMEM; }
         R->what = what;
         R->n_hay = n_hay;
         R->n_patterns = a->host.n_patterns;
@@ -158,10 +145,8 @@ int acx_summarize(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const ui
             if (what & ACX_SUM_FIRST) { R->any.assign((n_hay + 63) / 64, 0); R->first.resize(n_hay); }
             if (what & ACX_SUM_BY_PATTERN) R->hist.assign(R->n_patterns, 0);
         } catch (...) { rc = fail(ACX_ENOMEM, "out of memory"); }
-        const uint64_t none = 0; // (an empty batch: the counts' vector has no storage to point at)
         if (rc == ACX_OK)
-            rc = acx_summarize_host(m, nm, n_hay ? counts.data() : &none, n_hay, R->n_patterns, what, R->any.data(), R->first.data(),
-                                    R->hist.data());
+            rc = acx_summarize_host(m, nm, counts.data(), n_hay, R->n_patterns, what, R->any.data(), R->first.data(), R->hist.data());
         R->counts = std::move(counts);
         acx_free_matches(m);
         if (rc != ACX_OK) { acx_free_summary(R); return rc; }
@@ -169,15 +154,9 @@ int acx_summarize(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const ui
         return ACX_OK;
     }
     // device route: staged, searched and reduced under one lease
-    Lease lease(a);
-    Ctx *c = lease.c;
-    if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    rc = stage_host(a, c, B.hay, len, offsets ? B.rel.data() : nullptr, offsets ? n_hay + 1 : 0, false);
-    if (rc != ACX_OK) return rc;
-    const uint8_t *d_search = nullptr;
-    if ((rc = fold_copy(a, c, c->ws.hay, len, &d_search)) != ACX_OK) return rc;
-    const Segments G = offsets ? Segments{c->ws.offsets, n_hay, 0} : Segments{nullptr, 1, 0};
-    return run_summary(a, c, d_search, len, G, overlapping, codepoints, what, out);
+    return staged_call(a, B, len, n_hay, offsets != nullptr, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_summary(a, c, d_search, len, G, overlapping, codepoints, what, out);
+    });
 }
 
 int acx_summarize_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
@@ -227,10 +206,6 @@ const uint64_t *acx_summary_device_by_pattern(const acx_summary_t *r) {
     return (const uint64_t *)device_part(r, r ? r->d_hist : nullptr);
 }
 
-void acx_free_summary(acx_summary_t *r) {
-    if (!r) return;
-    r->release();
-    delete r;
-}
+void acx_free_summary(acx_summary_t *r) { free_result(r); }
 
 } // extern "C"

@@ -52,8 +52,8 @@ struct Stage {
 };
 
 // The stage up to the point where nnz is known: the scans, the tile kernel, the long rows' form when there are any.
-// S->roff then holds the row offsets (rows + 1 words); d_m: n records, d_counts: rows words (rows > 0).  check_sum: the
-// counts are a caller's (acx_tally_rows_device) -- they must sum to n before a kernel reads a record by them.
+// S->roff then holds the row offsets (rows + 1 words); d_m: n records, d_counts: rows words (rows > 0; check_sum:
+// record_offsets).
 int stage_count(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, const uint64_t *d_counts, uint64_t rows,
                 uint64_t n_patterns, bool check_sum, Stage *S, uint64_t *nnz) {
     S->device = device;
@@ -74,13 +74,7 @@ int stage_count(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, 
     S->tmp_pattern = (int64_t *)(b + o_tp);
     S->tmp_count = (int64_t *)(b + o_tc);
     uint64_t *n_long = (uint64_t *)S->roff + rows + 1; // (behind the scan's last entry: one readback brings both)
-    HIPCHK(acx::replace_scan(nullptr, nullptr, d_counts, rows, S->rec_off, S->scan_tmp, st));
-    if (check_sum) {
-        uint64_t sum = 0;
-        HIPCHK(hipMemcpyAsync(&sum, S->rec_off + rows, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (sum != n) return fail(ACX_EINVAL, "the counts do not sum to the number of records");
-    }
+    if (int rc = record_offsets(d_counts, rows, n, check_sum, S->rec_off, S->scan_tmp, st)) return rc;
     if (!n) { // every row is empty
         HIPCHK(hipMemsetAsync(S->roff, 0, (rows + 1) * 8, st));
         return ACX_OK;
@@ -118,18 +112,15 @@ int stage_finish(const Stage *S, uint64_t nnz, int64_t *row_offsets, int64_t *pa
 // run (out->done).  d_hay, and G.offsets, must stay valid until then.
 int run_tally(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping, acx_tally_t **out) {
     *out = nullptr;
-    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
-    const uint64_t rows = segmented ? G.n_hay : 1;
+    const uint64_t rows = rows_of(G).n;
     acx_result *r = nullptr;
     if (rows) { // (an empty batch: nothing to search, one row offset)
         int rc = run_find(a, x, d_hay, len, G, overlapping, 0, &r);
         if (rc != ACX_OK) return rc;
     }
-    acx_tally_t *R = new (std::nothrow) acx_tally_t();
-    if (!R) { acx_free_result(r); return fail(ACX_ENOMEM, "out of memory"); }
+    acx_tally_t *R = new_result<acx_tally_t>(a->device, true);
+    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
     hipStream_t st = x->stream;
-    R->device = a->device;
-    R->on_device = 1;
     R->rows = rows;
     Stage S;
     uint64_t *one_count = nullptr;
@@ -155,9 +146,8 @@ int run_tally(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, cons
 }
 
 acx_tally_t *host_tally(int device, uint64_t rows, uint64_t nnz_room) {
-    acx_tally_t *R = new (std::nothrow) acx_tally_t();
+    acx_tally_t *R = new_result<acx_tally_t>(device, false);
     if (!R) return nullptr;
-    R->device = device;
     R->rows = rows;
     if (R->alloc(nnz_room) != ACX_OK) { delete R; return nullptr; }
     for (int k = 0; k < 3; k++) R->part[k][0] = 0;
@@ -171,12 +161,7 @@ extern "C" {
 int acx_tally_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts, uint64_t n_hay, int64_t *row_offsets,
                    int64_t *pattern, int64_t *count, uint64_t *nnz) {
     if (!row_offsets || !nnz || (n_m && (!m || !pattern || !count)) || (n_hay && !counts)) return fail(ACX_EINVAL, "null argument");
-    uint64_t sum = 0;
-    for (uint64_t h = 0; h < n_hay; h++) {
-        if (counts[h] > n_m - sum) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
-        sum += counts[h];
-    }
-    if (sum != n_m) return fail(ACX_EINVAL, "the counts do not sum to the number of matches");
+    if (int rc = counts_sum_to(counts, n_hay, n_m)) return rc;
     std::vector<uint64_t> row;
     uint64_t at = 0, w = 0;
     try {
@@ -214,8 +199,8 @@ int acx_tally(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64
         // reduction here
         acx_match_t *m = nullptr;
         uint64_t nm = 0;
-        std::vector<uint64_t> counts(n_hay, 0);
-        if (n_hay) rc = acx_find_batch(a, B.hay, B.rel.data(), n_hay, overlapping, 0, &m, &nm, counts.data());
+        std::vector<uint64_t> counts;
+        if (n_hay) rc = host_find(a, B.hay, len, B.rel.data(), n_hay, overlapping, 0, &m, &nm, &counts);
         if (rc != ACX_OK) return rc;
         acx_tally_t *R = host_tally(a->device, n_hay, nm);
         if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
@@ -227,30 +212,13 @@ int acx_tally(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64
     }
     // device route: staged, searched and reduced under one lease; the compact block comes back in one copy
     acx_tally_t *D = nullptr;
-    {
-        Lease lease(a);
-        Ctx *c = lease.c;
-        if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-        rc = stage_host(a, c, B.hay, len, B.rel.data(), n_hay + 1, false);
-        if (rc != ACX_OK) return rc;
-        const uint8_t *d_search = nullptr;
-        if ((rc = fold_copy(a, c, c->ws.hay, len, &d_search)) != ACX_OK) return rc;
-        rc = run_tally(a, c, d_search, len, Segments{c->ws.offsets, n_hay, 0}, overlapping, &D);
-        if (rc != ACX_OK) return rc;
-        rc = D->wait(); // (the staging buffers are the context's: the lease ends behind the kernels)
-    }
+    rc = staged_call(a, B, len, n_hay, true, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        const int run = run_tally(a, c, d_search, len, G, overlapping, &D);
+        return run == ACX_OK ? D->wait() : run; // (the staging buffers are the context's: the lease ends behind the kernels)
+    });
     acx_tally_t *R = rc == ACX_OK ? host_tally(a->device, D->rows, D->nnz) : nullptr;
-    if (rc == ACX_OK && !R) rc = fail(ACX_ENOMEM, "out of memory");
-    if (rc == ACX_OK) {
-        R->nnz = D->nnz;
-        DeviceScope ds(a->device);
-        const hipError_t e = hipMemcpy(R->h_block, D->d_block, acx_tally::layout(D->rows, D->nnz).bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hipfail(e, "copying the tally to the host");
-    }
-    acx_free_tally(D);
-    if (rc != ACX_OK) { acx_free_tally(R); return rc; }
-    *out = R;
-    return ACX_OK;
+    if (R) R->nnz = D->nnz;
+    return copy_down(rc, D, R, D ? acx_tally::layout(D->rows, D->nnz).bytes : 0, "copying the tally to the host", out);
 }
 
 int acx_tally_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
@@ -271,22 +239,18 @@ int acx_tally_rows_device(const acx_match_t *d_records, uint64_t n, const uint64
         return fail(ACX_EINVAL, "records, counts and outputs must be 8-byte aligned");
     if (n_patterns > (1ull << acx::TALLY_PATTERN_BITS)) return fail(ACX_EINVAL, "more than 2^24 patterns");
     if (n && !n_hay) return fail(ACX_EINVAL, "the counts do not sum to the number of records");
-    hipPointerAttribute_t at;
-    HIPCHK(hipPointerGetAttributes(&at, d_row_offsets));
-    DeviceScope ds(at.device);
-    if (!n_hay) {
-        HIPCHK(hipMemsetAsync(d_row_offsets, 0, 8, nullptr));
-        HIPCHK(hipStreamSynchronize(nullptr));
-        return ACX_OK;
-    }
-    Stage S;
-    int rc = stage_count(at.device, nullptr, d_records, n, d_counts, n_hay, n_patterns, true, &S, nnz);
-    if (rc == ACX_OK) rc = stage_finish(&S, *nnz, d_row_offsets, d_pattern, d_count, nullptr);
-    const hipError_t e = hipStreamSynchronize(nullptr);
-    g_bufs.put(S.block, at.device);
-    g_bufs.put(S.long_block, at.device);
-    if (rc == ACX_OK && e != hipSuccess) rc = hipfail(e, "hipStreamSynchronize");
-    return rc;
+    return rows_call(d_row_offsets, [&](int device, void **t1, void **t2) -> int {
+        if (!n_hay) { // (no row: the one offset)
+            HIPCHK(hipMemsetAsync(d_row_offsets, 0, 8, nullptr));
+            return ACX_OK;
+        }
+        Stage S;
+        int rc = stage_count(device, nullptr, d_records, n, d_counts, n_hay, n_patterns, true, &S, nnz);
+        if (rc == ACX_OK) rc = stage_finish(&S, *nnz, d_row_offsets, d_pattern, d_count, nullptr);
+        *t1 = S.block;
+        *t2 = S.long_block;
+        return rc;
+    });
 }
 
 uint64_t acx_tally_nnz(const acx_tally_t *t) { return t ? t->nnz : 0; }
@@ -305,10 +269,6 @@ int acx_tally_copy(const acx_tally_t *t, int which, int64_t *host_dst) {
     return t->copy_out(host_dst, t->part[which], words * 8);
 }
 
-void acx_free_tally(acx_tally_t *t) {
-    if (!t) return;
-    t->release();
-    delete t;
-}
+void acx_free_tally(acx_tally_t *t) { free_result(t); }
 
 } // extern "C"
