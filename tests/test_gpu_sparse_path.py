@@ -280,7 +280,10 @@ def test_dense_output_concentrated_in_one_place(kernel):
     # first pass counted (capacity = grid x the fullest region would be two orders of magnitude more)
     import random
     rng = random.Random(5)
-    pats = list({bytes(rng.choice(b"abc") for _ in range(rng.randint(1, 8))) for _ in range(3000)})
+    # (one fixed order: a set's order changes with the process's hash seed, and under LeftmostFirst the number of matches with it
+    # -- 96 000 .. 160 000 over the seeds, on either side of the bound below)
+    pats = sorted({bytes(rng.choice(b"abc") for _ in range(rng.randint(1, 8))) for _ in range(3000)})
+    random.Random(6).shuffle(pats)  # (a generator of its own: the haystack below is drawn as before)
     dense = bytes(rng.choice(b"abc") for _ in range(400_000))
     hay = dense + b"z" * 1_600_000
     for mk in (1, 0):
