@@ -87,8 +87,11 @@ def test_hot_regions_at_the_seams(where):
 
 
 def test_bucket_and_group_overflow_stay_local():
-    # not the slots but the stage of k_tile_main overflows: more than 24 occurrences in ONE 4 KiB bucket of an otherwise
-    # sparse stream, and more than 1024 reported matches in one group without a full bucket -- both used to redo the call
+    # not the tiles' HIT_SLOTS but the stage of k_tile_main overflows: more occurrences in ONE 4 KiB bucket of an otherwise
+    # sparse stream than a bucket stages (STAGE_SLOTS_W32 with this set's narrow words; 40 plants here, both patterns'
+    # occurrences are staged whatever the call reports), and more than GROUP_MAX reported matches in one group (1 542 in
+    # group 1; at 24 or 25 plants to a bucket its buckets overfill as well) -- both used to redo the call.  The limits
+    # themselves -- one below, at, one above, a group above GROUP_MAX with no full bucket -- are tests/test_gpu_post_seams.py's.
     pats = [b"abcde", b"cde"]
     a = capi.Automaton(pats, 0)
     o = Oracle(pats, 0, KIND_DFA)

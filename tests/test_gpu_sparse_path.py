@@ -36,7 +36,7 @@ def test_chains_across_bucket_and_tile_boundaries(mk, kernel):
     # nearest certified sync point)
     pats = [b"ababab", b"babab", b"abab", b"bab", b"abababababab"]
     hay = bytearray(b"x" * (3 * TILE + 5000))
-    run = b"ab" * 14  # 28 bytes, < 32 occurrences per bucket
+    run = b"ab" * 14  # 28 bytes: the runs of a bucket stay below the STAGE_SLOTS occurrences it stages
     for centre in (4096, 8192 + 1, TILE, 2 * TILE - 3, 2 * TILE + 4096, 3 * TILE + 2):
         for shift in (-27, -14, -1, 0):
             s = centre + shift
@@ -57,18 +57,27 @@ def test_bucket_and_tile_overflow_fall_back_to_dense_path(kernel):
     pats = [b"abcde", b"cde"]
     a = capi.Automaton(pats, 0, kernel=kernel)
     o = Oracle(pats, 0, KIND_DFA)
-    # (1) one 4 KiB bucket with more than 32 occurrences in an otherwise empty stream
+    # (1) one 4 KiB bucket with more occurrences (40 plants, both patterns' occurrences staged) than a bucket of k_tile_main
+    # stages (STAGE_SLOTS_W32 for this set's narrow words) in an otherwise empty stream.  K1b's hits: the group goes to the hot pipeline and the
+    # call stays off the dense path; the DFA walk's hits have no hot pipeline: the call is redone on the dense path
     hay = bytearray(b"." * (1 << 20))
     hay[50000:50000 + 5 * 40] = b"abcde" * 40
+    a.path_stats(reset=True)
     check(a, o, bytes(hay), 0)
-    # the calls right after run in region mode (hold-off), then the sparse path returns
+    st = a.path_stats()
+    if kernel == capi.KERNEL_PREFILTER:
+        assert st["hot_calls"] == 2 and st["sparse"] == 0 and st["dense_tiles"] + st["dense_radix"] == 0, st
+    else:
+        assert st["dense_tiles"] + st["dense_radix"] >= 1 and st["hot_calls"] == 0, st
+    # the calls right after: (DFA walk) on the dense path while the handle is held there (dense_hold), then the sparse path returns
     sparse = bytearray(b"." * (1 << 20))
     for p in range(1000, len(sparse) - 10, 3001):
         sparse[p:p + 5] = b"abcde"
     sparse = bytes(sparse)
     for _ in range(12):
         check(a, o, sparse, 0)
-    # (2) no bucket above 32, but a tile above 1024: 24 occurrences in every bucket (48 with overlapping)
+    # (2) 24 or 25 plants to every bucket (two staged occurrences each: above STAGE_SLOTS_W32), 1 542 reported matches in a
+    # group: above GROUP_MAX
     hay = bytearray(b"." * (2 * TILE))
     for p in range(0, len(hay) - 8, 170):
         hay[p:p + 5] = b"abcde"
@@ -104,14 +113,25 @@ def test_textlike_10k_patterns_matches_oracle_on_both_paths():
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("mk", [0, 1, 2])
 def test_chain_longer_than_the_context_takes_the_dense_path(mk, kernel):
-    # a 256-byte pattern of period 128 on a periodic haystack: an occurrence every 128 bytes (32 per
-    # tile: the slots hold them), each overlapping the next, no sync point anywhere -- no group can
-    # certify where the greedy chain stands, the call is redone on the dense path
+    # a 256-byte pattern of period 128 on a periodic haystack: an occurrence every 128 bytes (64 prefix hits per
+    # tile: HIT_SLOTS hold them), each overlapping the next.  The two leftmost kinds (keyed on the START) have no sync
+    # point behind the first occurrence -- no group but the first can certify where the greedy chain stands, nor can a
+    # dense group of the hot pipeline or of the tile-ordered dense form (the same rule, L.first_sync > out0): the call ends
+    # on the radix form.  Standard is keyed on the END: the 55-byte pattern's occurrences end first, none overlaps the
+    # next, each is a certified sync point -- the chains are short, only the buckets are too full (64 occurrences each):
+    # K1b's calls are finished by the hot pipeline, the DFA walk's (no hot pipeline) by the radix form
     unit = bytes((i * 7 + 3) % 251 for i in range(128))
     pats = [unit * 2, unit[5:60]]
     hay = b"q" * 1000 + unit * 4200 + b"q" * 777
     a = capi.Automaton(pats, mk, kernel=kernel)
     o = Oracle(pats, mk, KIND_DFA)
+    a.path_stats(reset=True)
+    assert np.array_equal(cols(a.find(hay)), o.find_raw(hay)), mk
+    st = a.path_stats()
+    if mk == 0 and kernel == capi.KERNEL_PREFILTER:
+        assert st["hot_calls"] == 1 and st["sparse"] + st["dense_radix"] + st["dense_tiles"] == 0, sorted(st.items())
+    else:
+        assert st["dense_radix"] == 1 and st["sparse"] + st["hot_calls"] + st["dense_tiles"] == 0, sorted(st.items())
     check(a, o, hay, mk)
     check(a, o, hay[3:], mk)
     a.close()
@@ -142,9 +162,10 @@ def test_slot_bucket_and_group_overflow(kernel):
     o_pats = [b"abcdefg", b"efg", b"g"]
     a = capi.Automaton(o_pats, 0, kernel=kernel)
     o = Oracle(o_pats, 0, KIND_DFA)
-    # (1) more than 32 prefix hits in one tile; (2) 32 hits or fewer per tile, but more than 32
-    # occurrences in one bucket of the END position (overlapping: three per hit); (3) no bucket
-    # above 32, but more than 1024 reported matches in one group
+    # (1) 40 plants in 280 bytes of one tile: more prefix hits (two keyed prefixes a plant) than HIT_SLOTS; (2) 13 or 14
+    # plants per tile: the hits fit their slots, the three occurrences a plant overfill the bucket of the END position
+    # (STAGE_SLOTS_W32); (3) 25 or 26 plants per tile over a whole group: full buckets again, and more than GROUP_MAX
+    # reported matches in the group.  (Each limit by itself, one below, at and one above: tests/test_gpu_post_seams.py.)
     for step, span in ((7, 7 * 40), (300, 20 * 300), (160, TILE)):
         hay = bytearray(b"." * (2 * TILE))
         for p in range(TILE // 2, TILE // 2 + span, step):
