@@ -27,7 +27,10 @@ def sets():
     return {
         "direct comparison": FEW,                                          # MODE 2
         "table in LDS": FEW + [b"seventeen-bytes-xy"],                     # MODE 1
-        "tables in global memory": FEW + gen.gen_patterns(3000, 4, 12, gen.AZ, 3),  # MODE 0, MODE 3 beyond 1 KiB
+        # MODE 0 at every length: b"b" is a 1-byte pattern (short_min_len != 0), so small_prefilter_ok() refuses the set
+        "tables in global memory": FEW + gen.gen_patterns(3000, 4, 12, gen.AZ, 3),
+        # MODE 0 up to 1 KiB, MODE 3 beyond: no pattern under 3 bytes (tests/test_k0_seams_cpu.py holds both claims)
+        "prefilter beyond 1 KiB": [p for p in FEW if len(p) >= 3] + gen.gen_patterns(3000, 4, 12, gen.AZ, 3),
     }
 
 
@@ -48,7 +51,7 @@ def haystacks(pats, n, seed, lo=1, hi=400):
     return out
 
 
-@pytest.mark.parametrize("which", ["direct comparison", "table in LDS", "tables in global memory"])
+@pytest.mark.parametrize("which", ["direct comparison", "table in LDS", "tables in global memory", "prefilter beyond 1 KiB"])
 def test_resident_loop_every_mode_every_kind_bytes_and_code_points(which):
     pats = sets()[which]
     hays = haystacks(pats, 300, 5) + haystacks(pats, 40, 6, 1025, 5000) + [b"b", b"x", b"b" * 7, b"hello fish abc b host7 host76"]
@@ -215,7 +218,9 @@ print("OK")
 @pytest.mark.parametrize("env,which", [({"ACX_RESIDENT_LIFE_US": "30"}, "table in LDS"),
                                         ({"ACX_RESIDENT_LIFE_US": "30"}, "tables in global memory"),
                                         ({"ACX_RESIDENT_IDLE_US": "3"}, "direct comparison"),
-                                        ({"ACX_NO_RESIDENT": "1"}, "table in LDS")])
+                                        ({"ACX_NO_RESIDENT": "1"}, "table in LDS"),
+                                        # (the new case last: the ids of the four above stay env0 .. env3)
+                                        ({"ACX_RESIDENT_LIFE_US": "30"}, "prefilter beyond 1 KiB")])
 def test_resident_short_lives_and_switched_off(env, which):
     """A life of 30 us / an idle limit of 3 us: the kernel leaves between (and under) the calls all the time -- every call
     still gets its answer, from the kernel that took it or from the next launch.  ACX_NO_RESIDENT=1: plain launches only."""
