@@ -22,6 +22,7 @@ from .ahocorasick_rs import (
     FilteredRows,
     RowScores,
     MaskedRows,
+    MatchSpans,
     RowOffsets,
     split_rows,
 )
@@ -48,6 +49,8 @@ __all__ = [
     "RowScores",
     # Extension: the result of mask_all_batch / match_mask_batch
     "MaskedRows",
+    # Extension: the result of cover_spans / cover_spans_batch
+    "MatchSpans",
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",

@@ -27,6 +27,7 @@ try:
         FilteredRows,
     RowScores,
         MaskedRows,
+        MatchSpans,
         RowOffsets,
         split_rows,
     )
@@ -56,6 +57,8 @@ __all__ = [
     "RowScores",
     # Extension: the result of mask_all_batch / match_mask_batch
     "MaskedRows",
+    # Extension: the result of cover_spans / cover_spans_batch
+    "MatchSpans",
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",

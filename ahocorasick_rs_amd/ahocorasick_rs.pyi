@@ -98,6 +98,20 @@ class MaskedRows:
     # entries of continuation bytes are dropped on the host); a tensor gives the bytes as they are (decoded for list[str])
     def tolist(self) -> Any: ...
 
+# extension: the result of cover_spans / cover_spans_batch -- the union of a search's matches as two int64 columns, where the
+# search ran.  Within a row the spans are ascending and disjoint, and next.start - prev.end > gap
+class MatchSpans:
+    @property
+    def start(self) -> Column: ...  # len(self) int64 entries
+    @property
+    def end(self) -> Column: ...  # len(self) int64 entries
+    @property
+    def row_offsets(self) -> Optional[Column]: ...  # None for one haystack; len(haystacks) + 1 entries from 0 for a batch
+    @property
+    def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
+    def __len__(self) -> int: ...  # the number of spans
+    def tolist(self) -> Any: ...  # list[tuple[int, int]] of (start, end), or one such list per row of a batch
+
 # extension: the result of split_rows -- the offsets that cut a delimited buffer into rows, where the data lies
 class RowOffsets:
     @property
@@ -190,6 +204,16 @@ class AhoCorasick:
     def match_mask_batch(
         self, haystacks: Any, overlapping: bool = False, *, offsets: Any = None, row_length: Optional[int] = None
     ) -> MaskedRows: ...
+    # extension: the merged spans of a search's matches -- what find_matches_as_indexes(haystack, overlapping) reports, with
+    # matches that overlap, touch or lie at most gap characters apart joined into one (start, end).  Character indexes (a
+    # tensor of the _batch form: byte offsets local to the row).  gap: an int 0 .. 2**63 - 1 (ValueError outside; TypeError
+    # for a bool or anything that is no int).  With gap=0 the spans are the runs of ones of match_mask.  The _batch form
+    # takes haystacks as count_by_pattern_sparse_batch does; spans never join across rows
+    def cover_spans(self, haystack: str, overlapping: bool = False, *, gap: int = 0) -> MatchSpans: ...
+    def cover_spans_batch(
+        self, haystacks: Any, overlapping: bool = False, *, gap: int = 0, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> MatchSpans: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -260,4 +284,14 @@ class BytesAhoCorasick:
     def match_mask_batch(
         self, haystacks: Any, overlapping: bool = False, *, offsets: Any = None, row_length: Optional[int] = None
     ) -> MaskedRows: ...
+    # extension: the merged spans of a search's matches -- what find_matches_as_indexes(haystack, overlapping) reports, with
+    # matches that overlap, touch or lie at most gap bytes apart joined into one (start, end); byte offsets local to the
+    # row.  A __dlpack__ tensor on the automaton's device is searched and merged where it lies: the columns stay in HBM.
+    # gap: an int 0 .. 2**63 - 1 (ValueError outside; TypeError for a bool or anything that is no int).  With gap=0 the
+    # spans are the runs of ones of match_mask.  The _batch form takes haystacks as count_by_pattern_sparse_batch does
+    def cover_spans(self, haystack: Any, overlapping: bool = False, *, gap: int = 0) -> MatchSpans: ...
+    def cover_spans_batch(
+        self, haystacks: Any, overlapping: bool = False, *, gap: int = 0, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> MatchSpans: ...
     def _info(self) -> dict[str, Any]: ...

@@ -33,6 +33,7 @@ COL_PATTERN, COL_START, COL_END, COL_ROW_OFFSETS = 0, 1, 2, 3  # acx_columns_dat
 TALLY_ROW_OFFSETS, TALLY_PATTERN, TALLY_COUNT = 0, 1, 2  # acx_tally_data / acx_tally_copy (ACX_TALLY_*)
 FILT_ROWS, FILT_OFFSETS, FILT_DATA = 0, 1, 2  # acx_filtered_data / acx_filtered_copy (ACX_FILT_*)
 FILTER_KEEP_MATCHED = 1  # acx_filter* flags (ACX_FILTER_KEEP_MATCHED); 0 keeps the unmatched rows
+SPAN_START, SPAN_END, SPAN_ROW_OFFSETS = 0, 1, 2  # acx_spans_data / acx_spans_copy (ACX_SPAN_*)
 MASK_ZERO = 1  # acx_mask* flags (ACX_MASK_ZERO): uncovered bytes become 0 instead of the haystack's own
 ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
@@ -278,6 +279,19 @@ def lib() -> ctypes.CDLL:
     L.acx_free_rows.restype = None
     L.acx_split_rows_host.argtypes = [vp, u64, u8, vp, u64, ctypes.POINTER(u64)]
     L.acx_split_rows_into_device.argtypes = [vp, u64, u8, vp, u64, ctypes.POINTER(u64)]
+    L.acx_spans.argtypes = [vp, vp, u64, vp, u64, i32, i32, u64, ctypes.POINTER(vp)]
+    L.acx_spans_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, i32, u64, ctypes.POINTER(vp)]
+    for name in ("count", "rows"):
+        getattr(L, "acx_spans_" + name).argtypes = [vp]
+        getattr(L, "acx_spans_" + name).restype = u64
+    L.acx_spans_on_device.argtypes = [vp]
+    L.acx_spans_data.argtypes = [vp, i32]
+    L.acx_spans_data.restype = vp
+    L.acx_spans_copy.argtypes = [vp, i32, vp]
+    L.acx_free_spans.argtypes = [vp]
+    L.acx_free_spans.restype = None
+    L.acx_spans_host.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, ctypes.POINTER(u64)]
+    L.acx_spans_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, ctypes.POINTER(u64)]
     _lib = L
     return L
 
@@ -1002,6 +1016,70 @@ def split_rows_into_device(d_hay: int, nbytes: int, delimiter: int, d_offsets: i
     return int(n.value)
 
 
+class DeviceSpans(_PartsResult):
+    """The result of Automaton.spans / spans_device (acx_spans_t): the merged spans of a search's matches as two int64
+    columns of `count` words and, for a batch, n_hay + 1 row offsets -- in HBM (on_device) or in host memory.  column()
+    copies one out; data_ptr() is where it lies (both wait for the stage's last kernel)."""
+    _ON_DEVICE, _DATA, _COPY, _FREE = "acx_spans_on_device", "acx_spans_data", "acx_spans_copy", "acx_free_spans"
+
+    def __init__(self, handle: int, batch: bool):
+        super().__init__(handle)
+        self.batch = batch
+
+    @property
+    def count(self) -> int:
+        return int(lib().acx_spans_count(self._h))
+
+    @property
+    def rows(self) -> int:
+        return int(lib().acx_spans_rows(self._h))
+
+    def _part_shape(self, which: int):
+        return (self.rows + 1 if which == SPAN_ROW_OFFSETS else self.count), np.int64
+
+    def column(self, which: int) -> np.ndarray:
+        return self._copy_part(which)
+
+    def start(self) -> np.ndarray:
+        return self.column(SPAN_START)
+
+    def end(self) -> np.ndarray:
+        return self.column(SPAN_END)
+
+    def row_offsets(self) -> Optional[np.ndarray]:
+        return self.column(SPAN_ROW_OFFSETS) if self.batch else None
+
+
+def spans_host(matches, counts: Optional[Sequence[int]], gap: int = 0):
+    """acx_spans_host: the merge of a match list (rows of pattern, start, end whose ends do not decrease within a row; all
+    rows behind one another, counts[h] of them row h's -- None: one row) on the host, no device involved ->
+    (row_offsets, start, end): len(counts) + 1 (one row: 2) int64 offsets and the spans' int64 columns.  ValueError (code
+    EINVAL) when the counts do not sum to the records or gap is 2**63 or more."""
+    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    n_hay = 1 if c is None else len(c)
+    ro = np.zeros(n_hay + 1, dtype=np.int64)
+    start = np.zeros(len(m) + 1, dtype=np.int64)
+    end = np.zeros(len(m) + 1, dtype=np.int64)
+    pad = np.zeros(1, dtype=np.uint64)  # (an empty batch is still a batch: a non-null counts pointer)
+    n = ctypes.c_uint64()
+    _check(lib().acx_spans_host(m.ctypes.data if len(m) else None, len(m),
+                                None if c is None else (c.ctypes.data if len(c) else pad.ctypes.data), n_hay, gap,
+                                ro.ctypes.data, start.ctypes.data, end.ctypes.data, ctypes.byref(n)))
+    return ro, start[:n.value], end[:n.value]
+
+
+def spans_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, gap: int, d_row_offsets: int, d_start: int,
+                      d_end: int) -> int:
+    """acx_spans_rows_device: the device stage alone -- n records of 24 bytes at d_records, n_hay counts at d_counts ->
+    n_hay + 1 int64 row offsets at d_row_offsets and the spans' columns at d_start / d_end (room for n words each; only the
+    first S are written); complete when it returns.  Returns S, the number of spans."""
+    s = ctypes.c_uint64()
+    _check(lib().acx_spans_rows_device(d_records or None, n, d_counts or None, n_hay, gap, d_row_offsets or None,
+                                       d_start or None, d_end or None, ctypes.byref(s)))
+    return int(s.value)
+
+
 def _replaced_bytes(h: int) -> bytes:
     buf = bytearray(int(lib().acx_replaced_len(h)))
     if buf:
@@ -1325,6 +1403,30 @@ class Automaton(_Handle):
         _check(lib().acx_mask_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
                                      fill, flags, ctypes.byref(out)))
         return DeviceMasked(out.value)
+
+    # ---- merged spans: the union of the matches as start / end columns (acx_spans*)
+    def spans(self, haystacks: Optional[Sequence[bytes]], overlapping: bool = False, codepoints: bool = False, gap: int = 0, *,
+              single: Optional[bytes] = None) -> DeviceSpans:
+        """host haystacks' merged spans, a host result; single=...: one haystack that is no batch (offsets = NULL, no row
+        offsets)"""
+        out = ctypes.c_void_p()
+        if single is not None:
+            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
+            _check(lib().acx_spans(self._h, hb.ctypes.data, len(single), None, 0, int(overlapping), int(codepoints), gap,
+                                   ctypes.byref(out)))
+            return DeviceSpans(out.value, False)
+        hb, hoff = pack(haystacks)
+        _check(lib().acx_spans(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
+                               int(codepoints), gap, ctypes.byref(out)))
+        return DeviceSpans(out.value, True)
+
+    def spans_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
+                     overlapping: bool = False, codepoints: bool = False, gap: int = 0) -> DeviceSpans:
+        """the haystacks in HBM searched and their matches merged there; nothing but the number of spans crosses the bus"""
+        out = ctypes.c_void_p()
+        _check(lib().acx_spans_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
+                                      int(codepoints), gap, ctypes.byref(out)))
+        return DeviceSpans(out.value, bool(uniform_len or d_offsets))
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

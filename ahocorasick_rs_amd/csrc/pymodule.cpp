@@ -699,6 +699,23 @@ template <bool TEXT, bool BATCH> PyObject *bac_mask(PyObject *self_, PyObject *a
      METH_VARARGS | METH_KEYWORDS,                                                                                             \
      "[extension] match_mask_batch(haystacks, overlapping=False, *, offsets=None, row_length=None) -> MaskedRows: "            \
      "match_mask of every row in one call: .data is 1 where a match covers the byte, else 0."}
+// the merged spans of a search's matches (defined behind the MaskedRows below); BATCH: the *_batch form
+template <bool BATCH> PyObject *ac_spans(PyObject *self_, PyObject *args, PyObject *kwargs);
+template <bool BATCH> PyObject *bac_spans(PyObject *self_, PyObject *args, PyObject *kwargs);
+#define ACX_SPANS_METHODS(fn)                                                                                                  \
+    {"cover_spans", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)), METH_VARARGS | METH_KEYWORDS,      \
+     "cover_spans(haystack, overlapping=False, *, gap=0) -> MatchSpans\n\n[extension] the union of the matches that "           \
+     "find_matches_as_indexes(haystack, overlapping) reports, as two int64 columns .start / .end: matches that overlap, "      \
+     "touch or lie at most gap positions apart are ONE span -- the ranges to highlight, cut or redact.  The spans are "        \
+     "ascending and disjoint and next.start - prev.end > gap; with gap=0 they are the runs of ones of match_mask.  "           \
+     "AhoCorasick: character indexes; BytesAhoCorasick: byte offsets, and a __dlpack__ tensor on the automaton's device is "   \
+     "searched and merged there -- nothing but the number of spans crosses the bus.  gap: an int 0 .. 2**63 - 1."},           \
+    {"cover_spans_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<true>)), METH_VARARGS | METH_KEYWORDS, \
+     "cover_spans_batch(haystacks, overlapping=False, *, gap=0, offsets=None, row_length=None) -> MatchSpans\n\n"              \
+     "[extension] cover_spans of every row in one call, with .row_offsets: spans row_offsets[h] .. row_offsets[h + 1] - 1 "    \
+     "are row h's, their offsets local to it; spans never join across rows.  haystacks: a sequence, or ONE 1-D contiguous "    \
+     "uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for count_by_pattern_sparse_batch (byte "       \
+     "offsets for a tensor).  A tensor on the automaton's device is searched and merged there and the columns stay there."}
 #define ACX_COLUMNS_METHODS(fn)                                                                                                 \
     {"find_matches_as_columns", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)),                        \
      METH_VARARGS | METH_KEYWORDS,                                                                                              \
@@ -739,6 +756,7 @@ PyMethodDef ac_methods[] = {
     ACX_FILTER_METHOD(ac_filter_batch),
     ACX_SCORE_METHODS(ac_score_batch, ac_filter_by_score_batch),
     ACX_MASK_METHODS(ac_mask),
+    ACX_SPANS_METHODS(ac_spans),
     {"_info", ac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -1023,9 +1041,10 @@ PyTypeObject *FilteredRowsType = nullptr;
 PyTypeObject *RowScoresType = nullptr;
 PyTypeObject *MaskedRowsType = nullptr;
 PyTypeObject *RowOffsetsType = nullptr;
+PyTypeObject *MatchSpansType = nullptr;
 
 // What a Column's owner -- a MatchColumns, a PatternCounts, a FilteredRows (`which`: ACX_COL_*, ACX_TALLY_*, ACX_FILT_*), a
-// RowScores or a RowOffsets (their one part) or a MaskedRows (`which`: MR_*) -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
+// RowScores or a RowOffsets (their one part), a MaskedRows (`which`: MR_*) or a MatchSpans (`which`: ACX_SPAN_*) -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
 struct OwnerOps {
     int (*on_device)(const void *h);
     const void *(*data)(const void *h, int which); // (waits for the device work)
@@ -1046,6 +1065,9 @@ struct PatternCountsObject : OwnerObject {
 struct FilteredRowsObject : OwnerObject {
     uint64_t n_src;  // the rows of the batch that was filtered
     bool utf8;       // made by the str class: tolist() decodes
+};
+struct MatchSpansObject : OwnerObject {
+    bool batch;
 };
 enum { MR_OFFSETS = 0, MR_DATA = 1 };
 struct MaskedRowsObject : OwnerObject {
@@ -1074,7 +1096,11 @@ const OwnerOps MR_OPS = {[](const void *h) { return acx_masked_on_device(static_
 const OwnerOps RO_OPS = {[](const void *h) { return acx_rows_on_device(static_cast<const acx_rows_t *>(h)); },
                          [](const void *h, int) -> const void * { return acx_rows_offsets(static_cast<const acx_rows_t *>(h)); },
                          [](void *h) { acx_free_rows(static_cast<acx_rows_t *>(h)); }};
+const OwnerOps MS_OPS = {[](const void *h) { return acx_spans_on_device(static_cast<const acx_spans_t *>(h)); },
+                         [](const void *h, int w) -> const void * { return acx_spans_data(static_cast<const acx_spans_t *>(h), w); },
+                         [](void *h) { acx_free_spans(static_cast<acx_spans_t *>(h)); }};
 OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
+acx_spans_t *ms_handle(PyObject *s) { return static_cast<acx_spans_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
 acx_rows_t *ro_handle(PyObject *s) { return static_cast<acx_rows_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
 acx_masked_t *mr_handle(PyObject *s) { return static_cast<acx_masked_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
 acx_columns_t *mc_handle(PyObject *s) { return static_cast<acx_columns_t *>(owner_of(s)->h); }
@@ -1325,7 +1351,7 @@ PyType_Slot col_slots[] = {
     {Py_sq_length, reinterpret_cast<void *>(col_len)},
     {Py_bf_getbuffer, reinterpret_cast<void *>(col_getbuffer)},
     {Py_tp_doc, const_cast<char *>(
-        "One int64 column of a MatchColumns, a PatternCounts, a RowScores or a RowOffsets, or one part of a FilteredRows or a MaskedRows (int64; their data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
+        "One int64 column of a MatchColumns, a MatchSpans, a PatternCounts, a RowScores or a RowOffsets, or one part of a FilteredRows or a MaskedRows (int64; their data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
         "copy) and, in host memory, the buffer protocol (format 'q', or 'B' for uint8; read-only).")},
     {0, nullptr},
 };
@@ -2180,6 +2206,177 @@ template <bool TEXT, bool BATCH> PyObject *bac_mask(PyObject *self_, PyObject *a
 }
 
 // ---------------------------------------------------------------------------
+// the merged spans of a search's matches: cover_spans / cover_spans_batch -> MatchSpans (acx_spans / acx_spans_device).  A
+// MatchSpans owns the acx_spans_t; .start, .end and .row_offsets are Columns with the lifetime chain of a MatchColumns'
+// columns.
+// ---------------------------------------------------------------------------
+PyObject *ms_column(PyObject *self, int which) {
+    if (which == ACX_SPAN_ROW_OFFSETS && !static_cast<MatchSpansObject *>(owner_of(self))->batch) Py_RETURN_NONE;
+    return new_column(self, which, which == ACX_SPAN_ROW_OFFSETS ? acx_spans_rows(ms_handle(self)) + 1 : acx_spans_count(ms_handle(self)));
+}
+PyObject *ms_get_start(PyObject *s, void *) { return ms_column(s, ACX_SPAN_START); }
+PyObject *ms_get_end(PyObject *s, void *) { return ms_column(s, ACX_SPAN_END); }
+PyObject *ms_get_row_offsets(PyObject *s, void *) { return ms_column(s, ACX_SPAN_ROW_OFFSETS); }
+Py_ssize_t ms_len(PyObject *s) { return (Py_ssize_t)acx_spans_count(ms_handle(s)); }
+
+// list[tuple[int, int]], or one such list per row
+PyObject *ms_tolist(PyObject *self_, PyObject *) {
+    acx_spans_t *c = ms_handle(self_);
+    const bool batch = static_cast<MatchSpansObject *>(owner_of(self_))->batch;
+    const uint64_t n = acx_spans_count(c), rows = acx_spans_rows(c);
+    std::vector<int64_t> col[2], ro;
+    int rc = ACX_OK;
+    Py_BEGIN_ALLOW_THREADS
+    for (int k = 0; k < 2 && rc == ACX_OK; k++) {
+        col[k].resize((size_t)n);
+        rc = acx_spans_copy(c, k, col[k].data());
+    }
+    if (rc == ACX_OK && batch) {
+        ro.resize((size_t)rows + 1);
+        rc = acx_spans_copy(c, ACX_SPAN_ROW_OFFSETS, ro.data());
+    }
+    Py_END_ALLOW_THREADS
+    if (rc != ACX_OK) return raise_acx(rc);
+    auto rows_list = [&](uint64_t b, uint64_t e) -> PyObject * {
+        PyObject *list = PyList_New((Py_ssize_t)(e - b));
+        for (uint64_t i = b; list && i < e; i++) {
+            PyObject *t = Py_BuildValue("(KK)", (unsigned long long)col[0][i], (unsigned long long)col[1][i]);
+            if (!t) { Py_CLEAR(list); break; }
+            PyList_SET_ITEM(list, (Py_ssize_t)(i - b), t);
+        }
+        return list;
+    };
+    if (!batch) return rows_list(0, n);
+    PyObject *outer = PyList_New((Py_ssize_t)rows);
+    for (uint64_t h = 0; outer && h < rows; h++) {
+        PyObject *inner = rows_list((uint64_t)ro[h], (uint64_t)ro[h + 1]);
+        if (!inner) { Py_CLEAR(outer); break; }
+        PyList_SET_ITEM(outer, (Py_ssize_t)h, inner);
+    }
+    return outer;
+}
+
+PyGetSetDef ms_getset[] = {
+    {"start", ms_get_start, nullptr, "Column: where every span starts", nullptr},
+    {"end", ms_get_end, nullptr, "Column: where every span ends", nullptr},
+    {"row_offsets", ms_get_row_offsets, nullptr,
+     "None for one haystack; for a batch a Column of len(haystacks) + 1 entries: spans row_offsets[h] .. row_offsets[h + 1] "
+     "are haystack h's", nullptr},
+    {"device", owner_get_device, nullptr, "None: the columns are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+PyMethodDef ms_methods[] = {
+    {"tolist", ms_tolist, METH_NOARGS,
+     "the spans as list[tuple[int, int]] of (start, end), or one such list per row of a batch (copies device columns to the "
+     "host)"},
+    {nullptr, nullptr, 0, nullptr},
+};
+PyType_Slot ms_slots[] = {
+    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
+    {Py_tp_methods, ms_methods},
+    {Py_tp_getset, ms_getset},
+    {Py_sq_length, reinterpret_cast<void *>(ms_len)},
+    {Py_tp_doc, const_cast<char *>(
+        "The merged spans of cover_spans / cover_spans_batch: .start and .end (and .row_offsets for a batch) are Column "
+        "objects of len(self) int64 entries, where the search ran (.device).  Every accessor of a column waits for the "
+        "stage's last kernel first.")},
+    {0, nullptr},
+};
+
+// gap: an int 0 .. 2^63 - 1; sets the exception
+bool parse_gap(PyObject *gap, uint64_t *out) {
+    if (!PyLong_Check(gap) || PyBool_Check(gap)) {
+        PyErr_Format(PyExc_TypeError, "argument 'gap': '%.100s' object cannot be converted to 'PyInt'", Py_TYPE(gap)->tp_name);
+        return false;
+    }
+    int overflow = 0;
+    const long long v = PyLong_AsLongLongAndOverflow(gap, &overflow);
+    if (v == -1 && !overflow && PyErr_Occurred()) return false;
+    if (overflow || v < 0) {
+        PyErr_SetString(PyExc_ValueError, "gap must be in range(2**63)");
+        return false;
+    }
+    *out = (uint64_t)v;
+    return true;
+}
+// the check without an automaton (the CPU tests; a module function)
+PyObject *mod_spans_gap(PyObject *, PyObject *arg) {
+    uint64_t g = 0;
+    if (!parse_gap(arg, &g)) return nullptr;
+    return PyLong_FromUnsignedLongLong(g);
+}
+
+// cover_spans / cover_spans_batch of both classes: utf8 = the str class (code-point offsets when the text is not ASCII)
+PyObject *spans_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool batch, bool utf8) {
+    static const char *kw_s[] = {"haystack", "overlapping", "gap", nullptr};
+    static const char *kw_b[] = {"haystacks", "overlapping", "gap", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *ov = nullptr, *gap_o = nullptr, *offsets = nullptr, *row_length = nullptr;
+    int overlapping = 0;
+    if (batch ? !PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$OOO:cover_spans_batch", const_cast<char **>(kw_b), &hay, &ov, &gap_o,
+                                             &offsets, &row_length)
+              : !PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$O:cover_spans", const_cast<char **>(kw_s), &hay, &ov, &gap_o))
+        return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    uint64_t gap = 0;
+    if (gap_o && !parse_gap(gap_o, &gap)) return nullptr;
+    const int device = acx_automaton_device(a);
+    acx_spans_t *c = nullptr;
+    int rc;
+    auto host = [&](const uint8_t *p, uint64_t len, int codepoints) {
+        Py_BEGIN_ALLOW_THREADS
+        rc = acx_spans(a, p, len, nullptr, 0, overlapping, codepoints, gap, &c);
+        Py_END_ALLOW_THREADS
+    };
+    if (batch) {
+        BatchInput in;
+        if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
+        const int codepoints = (utf8 && !in.tensor && !in.seq.all_ascii) ? 1 : 0;
+        rc = batch_dispatch(
+            device, in,
+            [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+                return acx_spans(a, p, len, off, rows, overlapping, codepoints, gap, &c);
+            },
+            [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_len) {
+                return acx_spans_device(a, p, len, d_off, rows, row_len, overlapping, 0, gap, &c);
+            });
+        if (rc == BAD_OFFSETS) return nullptr;
+    } else if (utf8) {
+        const char *p; Py_ssize_t len;
+        if (!str_view(hay, &p, &len)) return nullptr;
+        host(reinterpret_cast<const uint8_t *>(p), (uint64_t)len, PyUnicode_IS_ASCII(hay) ? 0 : 1);
+    } else if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
+        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
+        PyObject *cap = dlpack_view(hay, device, &p, &len, &on_device);
+        if (!cap) return nullptr;
+        if (on_device) { // searched and merged where it lies
+            Py_BEGIN_ALLOW_THREADS
+            rc = acx_device_synchronize_on(device); // (the producer's kernels may still write it)
+            if (rc == ACX_OK) rc = acx_spans_device(a, p, len, nullptr, 0, 0, overlapping, 0, gap, &c);
+            Py_END_ALLOW_THREADS
+        } else {
+            host(p, len, 0);
+        }
+        dlpack_release(cap);
+    } else {
+        Py_buffer v;
+        if (!get_bytes_view(hay, &v)) return nullptr;
+        host((const uint8_t *)v.buf, (uint64_t)v.len, 0);
+        PyBuffer_Release(&v);
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    OwnerObject *o = new_owner(MatchSpansType, &MS_OPS, c, device);
+    if (o) static_cast<MatchSpansObject *>(o)->batch = batch;
+    return reinterpret_cast<PyObject *>(o);
+}
+
+template <bool BATCH> PyObject *ac_spans(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return spans_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, BATCH, true);
+}
+template <bool BATCH> PyObject *bac_spans(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return spans_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, BATCH, false);
+}
+
+// ---------------------------------------------------------------------------
 // split_rows(data, delimiter=b"\n") -> RowOffsets (acx_split_rows / acx_split_rows_device): a delimited buffer cut into rows.
 // A module function -- no automaton is involved.  A RowOffsets owns the acx_rows_t; .offsets is a Column with the lifetime
 // chain of a MatchColumns' columns, and what the _batch methods take as offsets=.
@@ -2397,6 +2594,7 @@ PyMethodDef bac_methods[] = {
     ACX_FILTER_METHOD(bac_filter_batch),
     ACX_SCORE_METHODS(bac_score_batch, bac_filter_by_score_batch),
     ACX_MASK_METHODS(bac_mask),
+    ACX_SPANS_METHODS(bac_spans),
     {"_info", bac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -2421,6 +2619,8 @@ PyMethodDef module_methods[] = {
      "offsets= to the _batch methods that take a tensor."},
     {"_mask_fill", mod_mask_fill, METH_VARARGS,
      "_mask_fill(fill, text) -> int: the fill byte mask_all takes from `fill` (text: the str class's rule), or its error"},
+    {"_spans_gap", mod_spans_gap, METH_O,
+     "_spans_gap(gap) -> int: the gap cover_spans takes from its `gap` argument, or its error"},
     {"_mask_per_character", mod_mask_per_character, METH_VARARGS,
      "_mask_per_character(haystack, row, text) -> str | bytes: a str haystack's masked row (one entry per UTF-8 byte) as "
      "mask_all (text) / match_mask return it: one entry per character"},
@@ -2466,6 +2666,9 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, mr_slots};
     PyType_Spec ro_spec = {"ahocorasick_rs.RowOffsets", sizeof(OwnerObject), 0,
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, ro_slots};
+    PyType_Spec ms_spec = {"ahocorasick_rs.MatchSpans", sizeof(MatchSpansObject), 0,
+                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, ms_slots};
+    MatchSpansType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&ms_spec));
     MaskedRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mr_spec));
     RowOffsetsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&ro_spec));
     FilteredRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&fr_spec));
@@ -2473,10 +2676,10 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
     MatchColumnsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mc_spec));
     ColumnType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&col_spec));
     PatternCountsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&pc_spec));
-    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType || !RowScoresType || !MaskedRowsType || !RowOffsetsType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
-    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType, RowScoresType, MaskedRowsType, RowOffsetsType}) { // (the module holds one reference, the globals the other)
+    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType || !RowScoresType || !MaskedRowsType || !RowOffsetsType || !MatchSpansType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
+    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType, RowScoresType, MaskedRowsType, RowOffsetsType, MatchSpansType}) { // (the module holds one reference, the globals the other)
         Py_INCREF(tp);
-        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : tp == RowScoresType ? "RowScores" : tp == MaskedRowsType ? "MaskedRows" : tp == RowOffsetsType ? "RowOffsets" : "MatchColumns",
+        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : tp == RowScoresType ? "RowScores" : tp == MaskedRowsType ? "MaskedRows" : tp == RowOffsetsType ? "RowOffsets" : tp == MatchSpansType ? "MatchSpans" : "MatchColumns",
                                reinterpret_cast<PyObject *>(tp)) < 0) {
             Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);
             return nullptr;

@@ -44,6 +44,8 @@ extern "C" {
  *     seventh addendum (additive as well): acx_split_rows / acx_split_rows_device / acx_split_rows_host /
  *     acx_split_rows_into_device and the acx_rows_t accessors (acx_rows_count, _bytes, _on_device, _device, _offsets, _copy,
  *     acx_free_rows);
+ *     eighth addendum (additive as well): acx_spans / acx_spans_device / acx_spans_host / acx_spans_rows_device, ACX_SPAN_*,
+ *     the acx_spans_t accessors (acx_spans_count, _rows, _on_device, _data, _copy, acx_free_spans);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -714,6 +716,60 @@ int acx_split_rows_host(const uint8_t *hay, uint64_t len, uint8_t delimiter, int
                         uint64_t capacity, uint64_t *n_rows);
 int acx_split_rows_into_device(const void *d_hay, uint64_t len, uint8_t delimiter, int64_t *d_offsets, uint64_t capacity,
                                uint64_t *n_rows);
+
+/* ---- merged spans: the union of a search's matches as `start` / `end` columns -- what a highlight, a snippet cut, a
+ * redaction range or a map from matches to tokens needs -- 16 bytes per run of covered positions instead of the mask's byte
+ * per haystack byte.  For a batch of rows, row h's matches M_h (what acx_find_batch / acx_find_device reports for the same
+ * match kind, overlapping and codepoints, offsets local to the row; a match with start >= end covers nothing and is ignored)
+ * and gap >= 0: the spans of row h are the coarsest partition of M_h into groups such that two matches are in one group when
+ * the later one starts at most `gap` positions behind the end of the earlier one (start <= end of the other + gap, through
+ * chains); a span is (min start, max end) of a group.  Within a row the spans are ascending and disjoint, and two consecutive
+ * ones satisfy next.start - prev.end > gap; with gap = 0 they are exactly the maximal runs of ones in the 0 / 1 mask
+ * (ACX_MASK_ZERO, fill 1) of the same search: touching matches are one span.  Spans never join across rows.
+ * The result: two int64 columns of acx_spans_count words and -- for a batch -- rows + 1 row offsets from 0 to the count (the
+ * CSR form: spans row_offsets[h] .. row_offsets[h + 1] - 1 are row h's).  gap >= 2^63 is ACX_EINVAL.
+ * acx_spans: host haystacks (offsets: n_hay + 1, or NULL: one haystack of len bytes, no row offsets), a host result.
+ * acx_find / acx_find_batch runs as it is and chooses its own route; the records cross the bus and acx_spans_host merges them.
+ * acx_spans_device: acx_find_device's pipeline (d_offsets / uniform_len as there; neither: one haystack, acx_spans_rows is 0
+ * and there are no row offsets), then the span stage on the same stream: the result lies in HBM on the automaton's device.
+ * The call returns when the number of spans is known (8 bytes cross the bus); the last kernel may still run: acx_spans_data /
+ * _copy wait for it.  d_hay and d_offsets must stay valid and unchanged until then.  An overlapping search on a handle that
+ * is not Standard is ACX_EOVERLAP before any device state; a result block that cannot be allocated is ACX_ENOMEM. */
+#define ACX_SPAN_START 0
+#define ACX_SPAN_END 1
+#define ACX_SPAN_ROW_OFFSETS 2
+typedef struct acx_spans acx_spans_t;
+int acx_spans(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one haystack */,
+              uint64_t n_hay, int overlapping, int codepoints, uint64_t gap, acx_spans_t **out);
+int acx_spans_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                     uint64_t uniform_len, int overlapping, int codepoints, uint64_t gap, acx_spans_t **out);
+uint64_t acx_spans_count(const acx_spans_t *s);    /* S: the spans; valid when the call has returned        */
+uint64_t acx_spans_rows(const acx_spans_t *s);     /* the rows of the batch; 0: one haystack                */
+int acx_spans_on_device(const acx_spans_t *s);     /* 1: the columns are in HBM, 0: host memory             */
+/* host or device pointer by acx_spans_on_device: column `which` (ACX_SPAN_*: S words; the row offsets: rows + 1); waits for
+ * the device stage.  NULL: no such column (the single form has no row offsets), or the wait failed.  Valid until
+ * acx_free_spans. */
+const int64_t *acx_spans_data(const acx_spans_t *s, int which);
+int acx_spans_copy(const acx_spans_t *s, int which, int64_t *host_dst);
+void acx_free_spans(acx_spans_t *s);
+/* the merge itself, over a caller's records.  PRECONDITION: within a row the records' ends do not decrease -- the order of
+ * every find of this library (overlapping: by end, then longer first; else by start).  With sufmin(i) = the smallest start of
+ * a live record at index >= i of record i's row, a live record i closes a span iff no live record follows it in its row or
+ * sufmin(i + 1) - end_i > gap, and an index opens one iff it is its row's first or follows a closer, and a live record lies
+ * at or behind it; the k-th opener's sufmin and the k-th closer's end are span k.  For records in another order these same
+ * formulas are evaluated: memory-safe, at most n spans, not the union.
+ * acx_spans_host: host memory, no device needed -- the definition inside the library; m: n_m records, all rows behind one
+ * another, counts[h] of them row h's (ACX_EINVAL when they do not sum to n_m), or counts = NULL: one row holds them all;
+ * row_offsets: n_hay + 1 words (one row: 2), or NULL: not wanted; start, end: n_m words each, the first *n_spans are written.
+ * acx_spans_rows_device: the device stage alone on a caller's records and counts (they must sum to n: checked before a kernel
+ * reads a record by them, and before anything is written) in HBM on one device; needs no automaton; synchronous: the outputs
+ * are complete when it returns.  d_start, d_end: n words each, the first *n_spans are written and nothing behind them;
+ * d_row_offsets: n_hay + 1 words, all written.  Every pointer 8-byte aligned.  n = 0 writes the zero row offsets and launches
+ * nothing else (the counts are not read). */
+int acx_spans_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts /* NULL: one row */, uint64_t n_hay, uint64_t gap,
+                   int64_t *row_offsets, int64_t *start, int64_t *end, uint64_t *n_spans);
+int acx_spans_rows_device(const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint64_t n_hay, uint64_t gap,
+                          int64_t *d_row_offsets, int64_t *d_start, int64_t *d_end, uint64_t *n_spans);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
