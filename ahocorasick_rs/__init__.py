@@ -23,6 +23,7 @@ from .ahocorasick_rs import (
     RowScores,
     MaskedRows,
     MatchSpans,
+    MatchSnippets,
     RowOffsets,
     split_rows,
 )
@@ -51,6 +52,8 @@ __all__ = [
     "MaskedRows",
     # Extension: the result of cover_spans / cover_spans_batch
     "MatchSpans",
+    # Extension: the result of find_matches_as_snippets / find_matches_as_snippets_batch
+    "MatchSnippets",
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",

@@ -28,6 +28,7 @@ try:
     RowScores,
         MaskedRows,
         MatchSpans,
+        MatchSnippets,
         RowOffsets,
         split_rows,
     )
@@ -59,6 +60,8 @@ __all__ = [
     "MaskedRows",
     # Extension: the result of cover_spans / cover_spans_batch
     "MatchSpans",
+    # Extension: the result of find_matches_as_snippets / find_matches_as_snippets_batch
+    "MatchSnippets",
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",

@@ -112,6 +112,27 @@ class MatchSpans:
     def __len__(self) -> int: ...  # the number of spans
     def tolist(self) -> Any: ...  # list[tuple[int, int]] of (start, end), or one such list per row of a batch
 
+# extension: the result of find_matches_as_snippets / find_matches_as_snippets_batch -- one snippet per match: the matched
+# text and its context as the caller's own bytes, where the search ran.  Snippet i is data[offsets[i]:offsets[i + 1]] and its
+# match begins at data[offsets[i] + lead[i]]
+class MatchSnippets:
+    @property
+    def data(self) -> Column: ...  # nbytes uint8 entries: the snippets back to back
+    @property
+    def offsets(self) -> Column: ...  # len(self) + 1 int64 entries from 0
+    @property
+    def pattern(self) -> Column: ...  # len(self) int64 entries: the pattern column of find_matches_as_columns
+    @property
+    def lead(self) -> Column: ...  # len(self) int64 entries: the bytes of snippet i in front of its match
+    @property
+    def row_offsets(self) -> Optional[Column]: ...  # None for one haystack; len(haystacks) + 1 entries from 0 for a batch
+    @property
+    def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
+    @property
+    def nbytes(self) -> int: ...  # the size of data
+    def __len__(self) -> int: ...  # the number of snippets
+    def tolist(self) -> Any: ...  # list[str] (AhoCorasick) or list[bytes]; one such list per row of a batch
+
 # extension: the result of split_rows -- the offsets that cut a delimited buffer into rows, where the data lies
 class RowOffsets:
     @property
@@ -214,6 +235,18 @@ class AhoCorasick:
         self, haystacks: Any, overlapping: bool = False, *, gap: int = 0, offsets: Any = None,
         row_length: Optional[int] = None
     ) -> MatchSpans: ...
+    # extension: the matched text and the text around it -- one snippet per match of find_matches_as_columns(haystack,
+    # overlapping), in its order: the match and up to context BYTES on each side, clipped to the haystack (a row of the
+    # _batch form).  Everything is in UTF-8 bytes, as for MaskedRows; a snippet never splits a character -- its ends move
+    # inward to a character boundary, never into the match -- so tolist() is a list[str], and with context=0 it equals
+    # find_matches_as_strings(haystack).  The bytes are the caller's own, also under ascii_case_insensitive.  context: an int
+    # 0 .. 2**63 - 1 (ValueError outside; TypeError for a bool or anything that is no int).  The _batch form takes haystacks
+    # as cover_spans_batch does
+    def find_matches_as_snippets(self, haystack: str, overlapping: bool = False, *, context: int = 0) -> MatchSnippets: ...
+    def find_matches_as_snippets_batch(
+        self, haystacks: Any, overlapping: bool = False, *, context: int = 0, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> MatchSnippets: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -294,4 +327,14 @@ class BytesAhoCorasick:
         self, haystacks: Any, overlapping: bool = False, *, gap: int = 0, offsets: Any = None,
         row_length: Optional[int] = None
     ) -> MatchSpans: ...
+    # extension: the matched text and the text around it -- one snippet per match of find_matches_as_columns(haystack,
+    # overlapping), in its order: the match and up to context bytes on each side, clipped to the haystack (a row of the
+    # _batch form); the bytes are the caller's own, also under ascii_case_insensitive.  A __dlpack__ tensor on the automaton's
+    # device is searched and cut where it lies: every part stays in HBM.  context: an int 0 .. 2**63 - 1 (ValueError outside;
+    # TypeError for a bool or anything that is no int).  The _batch form takes haystacks as cover_spans_batch does
+    def find_matches_as_snippets(self, haystack: Any, overlapping: bool = False, *, context: int = 0) -> MatchSnippets: ...
+    def find_matches_as_snippets_batch(
+        self, haystacks: Any, overlapping: bool = False, *, context: int = 0, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> MatchSnippets: ...
     def _info(self) -> dict[str, Any]: ...

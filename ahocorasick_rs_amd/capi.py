@@ -34,6 +34,8 @@ TALLY_ROW_OFFSETS, TALLY_PATTERN, TALLY_COUNT = 0, 1, 2  # acx_tally_data / acx_
 FILT_ROWS, FILT_OFFSETS, FILT_DATA = 0, 1, 2  # acx_filtered_data / acx_filtered_copy (ACX_FILT_*)
 FILTER_KEEP_MATCHED = 1  # acx_filter* flags (ACX_FILTER_KEEP_MATCHED); 0 keeps the unmatched rows
 SPAN_START, SPAN_END, SPAN_ROW_OFFSETS = 0, 1, 2  # acx_spans_data / acx_spans_copy (ACX_SPAN_*)
+SNIP_DATA, SNIP_OFFSETS, SNIP_PATTERN, SNIP_LEAD, SNIP_ROW_OFFSETS = 0, 1, 2, 3, 4  # acx_snippets_data / _copy (ACX_SNIP_*)
+SNIPPET_UTF8 = 1  # acx_snippets* flags (ACX_SNIPPET_UTF8): the ends move inward to a character boundary
 MASK_ZERO = 1  # acx_mask* flags (ACX_MASK_ZERO): uncovered bytes become 0 instead of the haystack's own
 ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
@@ -292,6 +294,20 @@ def lib() -> ctypes.CDLL:
     L.acx_free_spans.restype = None
     L.acx_spans_host.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, ctypes.POINTER(u64)]
     L.acx_spans_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, ctypes.POINTER(u64)]
+    L.acx_snippets.argtypes = [vp, vp, u64, vp, u64, i32, u64, u32, ctypes.POINTER(vp)]
+    L.acx_snippets_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, u64, u32, ctypes.POINTER(vp)]
+    for name in ("count", "rows", "nbytes"):
+        getattr(L, "acx_snippets_" + name).argtypes = [vp]
+        getattr(L, "acx_snippets_" + name).restype = u64
+    L.acx_snippets_on_device.argtypes = [vp]
+    L.acx_snippets_data.argtypes = [vp, i32]
+    L.acx_snippets_data.restype = vp
+    L.acx_snippets_copy.argtypes = [vp, i32, vp]
+    L.acx_free_snippets.argtypes = [vp]
+    L.acx_free_snippets.restype = None
+    L.acx_snippets_host.argtypes = [vp, u64, vp, u64, vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, ctypes.POINTER(u64)]
+    L.acx_snippets_rows_device.argtypes = [vp, u64, vp, u64, vp, u64, vp, u64, u64, u32, vp, vp, vp, vp, vp, u64,
+                                           ctypes.POINTER(u64)]
     _lib = L
     return L
 
@@ -1080,6 +1096,104 @@ def spans_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, gap: in
     return int(s.value)
 
 
+class DeviceSnippets(_PartsResult):
+    """The result of Automaton.snippets / snippets_device (acx_snippets_t): one snippet per match -- the bytes back to back
+    (uint8), count + 1 offsets, the pattern and lead columns (int64) and, for a batch, n_hay + 1 row offsets -- in HBM
+    (on_device) or in host memory.  part() copies one out; data_ptr() is where it lies (both wait for the gather)."""
+    _ON_DEVICE, _DATA, _COPY, _FREE = "acx_snippets_on_device", "acx_snippets_data", "acx_snippets_copy", "acx_free_snippets"
+
+    def __init__(self, handle: int, batch: bool):
+        super().__init__(handle)
+        self.batch = batch
+
+    @property
+    def count(self) -> int:
+        return int(lib().acx_snippets_count(self._h))
+
+    @property
+    def rows(self) -> int:
+        return int(lib().acx_snippets_rows(self._h))
+
+    @property
+    def nbytes(self) -> int:
+        return int(lib().acx_snippets_nbytes(self._h))
+
+    def _part_shape(self, which: int):
+        if which == SNIP_DATA:
+            return self.nbytes, np.uint8
+        return (self.rows + 1 if which == SNIP_ROW_OFFSETS else self.count + (which == SNIP_OFFSETS)), np.int64
+
+    def part(self, which: int) -> np.ndarray:
+        return self._copy_part(which)
+
+    def data(self) -> np.ndarray:
+        return self.part(SNIP_DATA)
+
+    def offsets(self) -> np.ndarray:
+        return self.part(SNIP_OFFSETS)
+
+    def pattern(self) -> np.ndarray:
+        return self.part(SNIP_PATTERN)
+
+    def lead(self) -> np.ndarray:
+        return self.part(SNIP_LEAD)
+
+    def row_offsets(self) -> Optional[np.ndarray]:
+        return self.part(SNIP_ROW_OFFSETS) if self.batch else None
+
+    def tolist(self) -> list:
+        """the snippets as bytes objects, in order"""
+        d, o = self.data().tobytes(), self.offsets()
+        return [d[o[i]:o[i + 1]] for i in range(self.count)]
+
+
+def snippets_host(matches, counts: Optional[Sequence[int]], hay, offsets: Optional[Sequence[int]], context: int = 0,
+                  flags: int = 0, *, sizes_only: bool = False):
+    """acx_snippets_host: the definition of the cut on the host, no device involved.  matches: rows of (pattern, start, end),
+    all rows behind one another, counts[h] of them row h's (None: one row); hay: bytes-like; offsets: n_hay + 1 from 0 to
+    len(hay), or None (one row).  Returns (data, offsets, pattern, lead, row_offsets) as uint8 / int64 arrays -- the two-call
+    form: sizes with null outputs, then the fill -- or the data's size alone with sizes_only.  ValueError (code EINVAL) for a
+    bad flag, a context of 2**63 or more, counts that do not sum to the records or offsets that do not rise from 0 to
+    len(hay)."""
+    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    h = np.frombuffer(bytes(hay), dtype=np.uint8)
+    off = None if offsets is None else np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+    n_hay = (1 if c is None else len(c)) if off is None else len(off) - 1
+    pad = np.zeros(1, dtype=np.uint64)  # (an empty batch is still a batch: non-null pointers)
+    args = (m.ctypes.data if len(m) else None, len(m), None if c is None else (c.ctypes.data if len(c) else pad.ctypes.data),
+            n_hay, h.ctypes.data if len(h) else None, len(h), None if off is None else off.ctypes.data, context, flags)
+    total = ctypes.c_uint64()
+    _check(lib().acx_snippets_host(*args, None, None, None, None, None, ctypes.byref(total)))
+    if sizes_only:
+        return int(total.value)
+    data = np.zeros(total.value, dtype=np.uint8)
+    o = np.zeros(len(m) + 1, dtype=np.int64)
+    pat = np.zeros(len(m), dtype=np.int64)
+    lead = np.zeros(len(m), dtype=np.int64)
+    ro = np.zeros(n_hay + 1, dtype=np.int64)
+    _check(lib().acx_snippets_host(*args, o.ctypes.data, pat.ctypes.data if len(m) else None, lead.ctypes.data if len(m) else None,
+                                   ro.ctypes.data, data.ctypes.data if data.size else None, ctypes.byref(total)))
+    return data, o, pat, lead, ro
+
+
+def snippets_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, d_hay: int, nbytes: int, d_offsets: int,
+                         uniform_len: int, context: int, flags: int, d_out_offsets: int, d_pattern: int, d_lead: int,
+                         d_row_offsets: int, d_data: int, data_capacity: int):
+    """acx_snippets_rows_device: the device stage alone -- n records of 24 bytes at d_records, n_hay counts at d_counts, nbytes
+    at d_hay (any address) cut by n_hay + 1 offsets at d_offsets, by uniform_len or not at all (one row) -> n + 1 offsets, n
+    patterns, n leads, n_hay + 1 row offsets and the snippets' bytes at d_data (16-byte aligned, data_capacity bytes);
+    complete when it returns.  Returns (code, total): code is 0 or ETOOBIG (total > data_capacity: d_data is untouched);
+    every other failure raises."""
+    t = ctypes.c_uint64()
+    rc = lib().acx_snippets_rows_device(d_records or None, n, d_counts or None, n_hay, d_hay or None, nbytes, d_offsets or None,
+                                        uniform_len, context, flags, d_out_offsets or None, d_pattern or None, d_lead or None,
+                                        d_row_offsets or None, d_data or None, data_capacity, ctypes.byref(t))
+    if rc != ETOOBIG:
+        _check(rc)
+    return rc, int(t.value)
+
+
 def _replaced_bytes(h: int) -> bytes:
     buf = bytearray(int(lib().acx_replaced_len(h)))
     if buf:
@@ -1427,6 +1541,30 @@ class Automaton(_Handle):
         _check(lib().acx_spans_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
                                       int(codepoints), gap, ctypes.byref(out)))
         return DeviceSpans(out.value, bool(uniform_len or d_offsets))
+
+    # ---- snippets: the matched text and its context as the caller's own bytes (acx_snippets*)
+    def snippets(self, haystacks: Optional[Sequence[bytes]], overlapping: bool = False, context: int = 0, flags: int = 0, *,
+                 single: Optional[bytes] = None) -> DeviceSnippets:
+        """host haystacks' snippets, a host result; single=...: one haystack that is no batch (offsets = NULL, no row
+        offsets)"""
+        out = ctypes.c_void_p()
+        if single is not None:
+            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
+            _check(lib().acx_snippets(self._h, hb.ctypes.data, len(single), None, 0, int(overlapping), context, flags,
+                                      ctypes.byref(out)))
+            return DeviceSnippets(out.value, False)
+        hb, hoff = pack(haystacks)
+        _check(lib().acx_snippets(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
+                                  context, flags, ctypes.byref(out)))
+        return DeviceSnippets(out.value, True)
+
+    def snippets_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
+                        overlapping: bool = False, context: int = 0, flags: int = 0) -> DeviceSnippets:
+        """the haystacks in HBM searched and their matches cut there; nothing but the data's size crosses the bus"""
+        out = ctypes.c_void_p()
+        _check(lib().acx_snippets_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
+                                         context, flags, ctypes.byref(out)))
+        return DeviceSnippets(out.value, bool(uniform_len or d_offsets))
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

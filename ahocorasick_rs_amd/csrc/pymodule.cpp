@@ -716,6 +716,26 @@ template <bool BATCH> PyObject *bac_spans(PyObject *self_, PyObject *args, PyObj
      "are row h's, their offsets local to it; spans never join across rows.  haystacks: a sequence, or ONE 1-D contiguous "    \
      "uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for count_by_pattern_sparse_batch (byte "       \
      "offsets for a tensor).  A tensor on the automaton's device is searched and merged there and the columns stay there."}
+// the matched text and its context (defined behind the MatchSpans below); BATCH: the *_batch form
+template <bool BATCH> PyObject *ac_snippets(PyObject *self_, PyObject *args, PyObject *kwargs);
+template <bool BATCH> PyObject *bac_snippets(PyObject *self_, PyObject *args, PyObject *kwargs);
+#define ACX_SNIPPETS_METHODS(fn)                                                                                               \
+    {"find_matches_as_snippets", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)),                       \
+     METH_VARARGS | METH_KEYWORDS,                                                                                             \
+     "find_matches_as_snippets(haystack, overlapping=False, *, context=0) -> MatchSnippets\n\n[extension] one snippet per "    \
+     "match that find_matches_as_columns(haystack, overlapping) reports, in its order: the matched text and up to context "    \
+     "BYTES on each side of it, clipped to the haystack, as the caller's own bytes (.data, cut by .offsets; the match begins "  \
+     ".lead bytes into its snippet; .pattern is the columns' pattern).  AhoCorasick: UTF-8 bytes, the ends moved inward to a " \
+     "character boundary, so tolist() is a list[str] and with context=0 it equals find_matches_as_strings.  "                  \
+     "BytesAhoCorasick: a __dlpack__ tensor on the automaton's device is searched and cut there -- nothing but the size of "   \
+     "the data crosses the bus.  context: an int 0 .. 2**63 - 1."},                                                            \
+    {"find_matches_as_snippets_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<true>)),                  \
+     METH_VARARGS | METH_KEYWORDS,                                                                                             \
+     "find_matches_as_snippets_batch(haystacks, overlapping=False, *, context=0, offsets=None, row_length=None) -> "           \
+     "MatchSnippets\n\n[extension] find_matches_as_snippets of every row in one call, with .row_offsets: snippets "            \
+     "row_offsets[h] .. row_offsets[h + 1] - 1 are row h's; a snippet never crosses a row.  haystacks: a sequence, or ONE 1-D " \
+     "contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for cover_spans_batch.  A tensor on " \
+     "the automaton's device is searched and cut there and every part stays there."}
 #define ACX_COLUMNS_METHODS(fn)                                                                                                 \
     {"find_matches_as_columns", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)),                        \
      METH_VARARGS | METH_KEYWORDS,                                                                                              \
@@ -757,6 +777,7 @@ PyMethodDef ac_methods[] = {
     ACX_SCORE_METHODS(ac_score_batch, ac_filter_by_score_batch),
     ACX_MASK_METHODS(ac_mask),
     ACX_SPANS_METHODS(ac_spans),
+    ACX_SNIPPETS_METHODS(ac_snippets),
     {"_info", ac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -1042,6 +1063,7 @@ PyTypeObject *RowScoresType = nullptr;
 PyTypeObject *MaskedRowsType = nullptr;
 PyTypeObject *RowOffsetsType = nullptr;
 PyTypeObject *MatchSpansType = nullptr;
+PyTypeObject *MatchSnippetsType = nullptr;
 
 // What a Column's owner -- a MatchColumns, a PatternCounts, a FilteredRows (`which`: ACX_COL_*, ACX_TALLY_*, ACX_FILT_*), a
 // RowScores or a RowOffsets (their one part), a MaskedRows (`which`: MR_*) or a MatchSpans (`which`: ACX_SPAN_*) -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
@@ -1068,6 +1090,10 @@ struct FilteredRowsObject : OwnerObject {
 };
 struct MatchSpansObject : OwnerObject {
     bool batch;
+};
+struct MatchSnippetsObject : OwnerObject {
+    bool batch;
+    bool utf8; // made by the str class: tolist() decodes
 };
 enum { MR_OFFSETS = 0, MR_DATA = 1 };
 struct MaskedRowsObject : OwnerObject {
@@ -1099,7 +1125,11 @@ const OwnerOps RO_OPS = {[](const void *h) { return acx_rows_on_device(static_ca
 const OwnerOps MS_OPS = {[](const void *h) { return acx_spans_on_device(static_cast<const acx_spans_t *>(h)); },
                          [](const void *h, int w) -> const void * { return acx_spans_data(static_cast<const acx_spans_t *>(h), w); },
                          [](void *h) { acx_free_spans(static_cast<acx_spans_t *>(h)); }};
+const OwnerOps SN_OPS = {[](const void *h) { return acx_snippets_on_device(static_cast<const acx_snippets_t *>(h)); },
+                         [](const void *h, int w) -> const void * { return acx_snippets_data(static_cast<const acx_snippets_t *>(h), w); },
+                         [](void *h) { acx_free_snippets(static_cast<acx_snippets_t *>(h)); }};
 OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
+acx_snippets_t *sn_handle(PyObject *s) { return static_cast<acx_snippets_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
 acx_spans_t *ms_handle(PyObject *s) { return static_cast<acx_spans_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
 acx_rows_t *ro_handle(PyObject *s) { return static_cast<acx_rows_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
 acx_masked_t *mr_handle(PyObject *s) { return static_cast<acx_masked_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
@@ -1351,7 +1381,7 @@ PyType_Slot col_slots[] = {
     {Py_sq_length, reinterpret_cast<void *>(col_len)},
     {Py_bf_getbuffer, reinterpret_cast<void *>(col_getbuffer)},
     {Py_tp_doc, const_cast<char *>(
-        "One int64 column of a MatchColumns, a MatchSpans, a PatternCounts, a RowScores or a RowOffsets, or one part of a FilteredRows or a MaskedRows (int64; their data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
+        "One int64 column of a MatchColumns, a MatchSpans, a PatternCounts, a RowScores or a RowOffsets, or one part of a FilteredRows, a MaskedRows or a MatchSnippets (int64; their data: uint8): len(), __dlpack__ / __dlpack_device__ (torch.from_dlpack, numpy.from_dlpack: no "
         "copy) and, in host memory, the buffer protocol (format 'q', or 'B' for uint8; read-only).")},
     {0, nullptr},
 };
@@ -2377,6 +2407,195 @@ template <bool BATCH> PyObject *bac_spans(PyObject *self_, PyObject *args, PyObj
 }
 
 // ---------------------------------------------------------------------------
+// the matched text and its context: find_matches_as_snippets / find_matches_as_snippets_batch -> MatchSnippets (acx_snippets /
+// acx_snippets_device).  A MatchSnippets owns the acx_snippets_t; its parts are Columns (.data uint8, the others int64) with
+// the lifetime chain of a MatchColumns' columns.
+// ---------------------------------------------------------------------------
+PyObject *sn_column(PyObject *self, int which) {
+    acx_snippets_t *c = sn_handle(self);
+    if (which == ACX_SNIP_ROW_OFFSETS && !static_cast<MatchSnippetsObject *>(owner_of(self))->batch) Py_RETURN_NONE;
+    if (which == ACX_SNIP_DATA) return new_column(self, which, acx_snippets_nbytes(c), 1);
+    return new_column(self, which, which == ACX_SNIP_ROW_OFFSETS ? acx_snippets_rows(c) + 1 : acx_snippets_count(c) + (which == ACX_SNIP_OFFSETS ? 1 : 0));
+}
+PyObject *sn_get_data(PyObject *s, void *) { return sn_column(s, ACX_SNIP_DATA); }
+PyObject *sn_get_offsets(PyObject *s, void *) { return sn_column(s, ACX_SNIP_OFFSETS); }
+PyObject *sn_get_pattern(PyObject *s, void *) { return sn_column(s, ACX_SNIP_PATTERN); }
+PyObject *sn_get_lead(PyObject *s, void *) { return sn_column(s, ACX_SNIP_LEAD); }
+PyObject *sn_get_row_offsets(PyObject *s, void *) { return sn_column(s, ACX_SNIP_ROW_OFFSETS); }
+PyObject *sn_get_nbytes(PyObject *s, void *) { return PyLong_FromUnsignedLongLong(acx_snippets_nbytes(sn_handle(s))); }
+Py_ssize_t sn_len(PyObject *s) { return (Py_ssize_t)acx_snippets_count(sn_handle(s)); }
+
+// list[str] of the str class (UTF-8 decoded), list[bytes] of the bytes class; a batch: one such list per row
+PyObject *sn_tolist(PyObject *self_, PyObject *) {
+    acx_snippets_t *c = sn_handle(self_);
+    const MatchSnippetsObject *o = static_cast<MatchSnippetsObject *>(owner_of(self_));
+    const bool batch = o->batch, utf8 = o->utf8;
+    const uint64_t n = acx_snippets_count(c), rows = acx_snippets_rows(c), nb = acx_snippets_nbytes(c);
+    std::vector<int64_t> off((size_t)n + 1), ro;
+    std::vector<uint8_t> data((size_t)nb + 1);
+    int rc;
+    Py_BEGIN_ALLOW_THREADS
+    rc = acx_snippets_copy(c, ACX_SNIP_OFFSETS, off.data());
+    if (rc == ACX_OK) rc = acx_snippets_copy(c, ACX_SNIP_DATA, data.data());
+    if (rc == ACX_OK && batch) {
+        ro.resize((size_t)rows + 1);
+        rc = acx_snippets_copy(c, ACX_SNIP_ROW_OFFSETS, ro.data());
+    }
+    Py_END_ALLOW_THREADS
+    if (rc != ACX_OK) return raise_acx(rc);
+    auto rows_list = [&](uint64_t b, uint64_t e) -> PyObject * {
+        PyObject *list = PyList_New((Py_ssize_t)(e - b));
+        for (uint64_t i = b; list && i < e; i++) {
+            const char *p = reinterpret_cast<const char *>(data.data()) + off[(size_t)i];
+            const Py_ssize_t k = (Py_ssize_t)(off[(size_t)i + 1] - off[(size_t)i]);
+            PyObject *it = utf8 ? PyUnicode_DecodeUTF8(p, k, nullptr) : PyBytes_FromStringAndSize(p, k);
+            if (!it) { Py_CLEAR(list); break; }
+            PyList_SET_ITEM(list, (Py_ssize_t)(i - b), it);
+        }
+        return list;
+    };
+    if (!batch) return rows_list(0, n);
+    PyObject *outer = PyList_New((Py_ssize_t)rows);
+    for (uint64_t h = 0; outer && h < rows; h++) {
+        PyObject *inner = rows_list((uint64_t)ro[h], (uint64_t)ro[h + 1]);
+        if (!inner) { Py_CLEAR(outer); break; }
+        PyList_SET_ITEM(outer, (Py_ssize_t)h, inner);
+    }
+    return outer;
+}
+
+PyGetSetDef sn_getset[] = {
+    {"data", sn_get_data, nullptr, "Column of nbytes uint8 entries: the snippets back to back", nullptr},
+    {"offsets", sn_get_offsets, nullptr, "Column of len(self) + 1 int64 entries from 0: snippet i is data[offsets[i]:offsets[i + 1]]",
+     nullptr},
+    {"pattern", sn_get_pattern, nullptr, "Column of len(self) int64 entries: the pattern of every match", nullptr},
+    {"lead", sn_get_lead, nullptr,
+     "Column of len(self) int64 entries: the bytes of snippet i that stand before the match, which begins at "
+     "data[offsets[i] + lead[i]]", nullptr},
+    {"row_offsets", sn_get_row_offsets, nullptr,
+     "None for one haystack; for a batch a Column of len(haystacks) + 1 entries: snippets row_offsets[h] .. row_offsets[h + 1] "
+     "are haystack h's", nullptr},
+    {"device", owner_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
+    {"nbytes", sn_get_nbytes, nullptr, "the size of data", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+PyMethodDef sn_methods[] = {
+    {"tolist", sn_tolist, METH_NOARGS,
+     "the snippets as list[str] (the str class: UTF-8 decoded) or list[bytes], or one such list per row of a batch (copies "
+     "device parts to the host)"},
+    {nullptr, nullptr, 0, nullptr},
+};
+PyType_Slot sn_slots[] = {
+    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
+    {Py_tp_methods, sn_methods},
+    {Py_tp_getset, sn_getset},
+    {Py_sq_length, reinterpret_cast<void *>(sn_len)},
+    {Py_tp_doc, const_cast<char *>(
+        "The result of find_matches_as_snippets / find_matches_as_snippets_batch: one snippet per match.  .data is a uint8 "
+        "Column of nbytes entries, .offsets, .pattern and .lead (and .row_offsets for a batch) are int64 Column objects, where "
+        "the search ran (.device); len(self) is the number of snippets.  Every accessor of a part waits for the stage's last "
+        "kernel first.")},
+    {0, nullptr},
+};
+
+// context: an int 0 .. 2^63 - 1; sets the exception
+bool parse_context(PyObject *context, uint64_t *out) {
+    if (!PyLong_Check(context) || PyBool_Check(context)) {
+        PyErr_Format(PyExc_TypeError, "argument 'context': '%.100s' object cannot be converted to 'PyInt'", Py_TYPE(context)->tp_name);
+        return false;
+    }
+    int overflow = 0;
+    const long long v = PyLong_AsLongLongAndOverflow(context, &overflow);
+    if (v == -1 && !overflow && PyErr_Occurred()) return false;
+    if (overflow || v < 0) {
+        PyErr_SetString(PyExc_ValueError, "context must be in range(2**63)");
+        return false;
+    }
+    *out = (uint64_t)v;
+    return true;
+}
+// the check without an automaton (the CPU tests; a module function)
+PyObject *mod_snippets_context(PyObject *, PyObject *arg) {
+    uint64_t g = 0;
+    if (!parse_context(arg, &g)) return nullptr;
+    return PyLong_FromUnsignedLongLong(g);
+}
+
+// find_matches_as_snippets / _batch of both classes: utf8 = the str class (UTF-8 bytes, the ends trimmed to characters).  The
+// search runs on bytes: every offset of the result is a byte offset into .data
+PyObject *snippets_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool batch, bool utf8) {
+    static const char *kw_s[] = {"haystack", "overlapping", "context", nullptr};
+    static const char *kw_b[] = {"haystacks", "overlapping", "context", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *ov = nullptr, *ctx_o = nullptr, *offsets = nullptr, *row_length = nullptr;
+    int overlapping = 0;
+    if (batch ? !PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$OOO:find_matches_as_snippets_batch", const_cast<char **>(kw_b), &hay,
+                                             &ov, &ctx_o, &offsets, &row_length)
+              : !PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$O:find_matches_as_snippets", const_cast<char **>(kw_s), &hay, &ov, &ctx_o))
+        return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    uint64_t context = 0;
+    if (ctx_o && !parse_context(ctx_o, &context)) return nullptr;
+    const uint32_t flags = utf8 ? ACX_SNIPPET_UTF8 : 0;
+    const int device = acx_automaton_device(a);
+    acx_snippets_t *c = nullptr;
+    int rc;
+    auto host = [&](const uint8_t *p, uint64_t len) {
+        Py_BEGIN_ALLOW_THREADS
+        rc = acx_snippets(a, p, len, nullptr, 0, overlapping, context, flags, &c);
+        Py_END_ALLOW_THREADS
+    };
+    if (batch) {
+        BatchInput in;
+        if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
+        rc = batch_dispatch(
+            device, in,
+            [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+                return acx_snippets(a, p, len, off, rows, overlapping, context, flags, &c);
+            },
+            [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_len) {
+                return acx_snippets_device(a, p, len, d_off, rows, row_len, overlapping, context, flags, &c);
+            });
+        if (rc == BAD_OFFSETS) return nullptr;
+    } else if (utf8) {
+        const char *p; Py_ssize_t len;
+        if (!str_view(hay, &p, &len)) return nullptr;
+        host(reinterpret_cast<const uint8_t *>(p), (uint64_t)len);
+    } else if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
+        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
+        PyObject *cap = dlpack_view(hay, device, &p, &len, &on_device);
+        if (!cap) return nullptr;
+        if (on_device) { // searched and cut where it lies
+            Py_BEGIN_ALLOW_THREADS
+            rc = acx_device_synchronize_on(device); // (the producer's kernels may still write it)
+            if (rc == ACX_OK) rc = acx_snippets_device(a, p, len, nullptr, 0, 0, overlapping, context, flags, &c);
+            Py_END_ALLOW_THREADS
+        } else {
+            host(p, len);
+        }
+        dlpack_release(cap);
+    } else {
+        Py_buffer v;
+        if (!get_bytes_view(hay, &v)) return nullptr;
+        host((const uint8_t *)v.buf, (uint64_t)v.len);
+        PyBuffer_Release(&v);
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    OwnerObject *o = new_owner(MatchSnippetsType, &SN_OPS, c, device);
+    if (o) {
+        static_cast<MatchSnippetsObject *>(o)->batch = batch;
+        static_cast<MatchSnippetsObject *>(o)->utf8 = utf8;
+    }
+    return reinterpret_cast<PyObject *>(o);
+}
+
+template <bool BATCH> PyObject *ac_snippets(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return snippets_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, BATCH, true);
+}
+template <bool BATCH> PyObject *bac_snippets(PyObject *self_, PyObject *args, PyObject *kwargs) {
+    return snippets_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, BATCH, false);
+}
+
+// ---------------------------------------------------------------------------
 // split_rows(data, delimiter=b"\n") -> RowOffsets (acx_split_rows / acx_split_rows_device): a delimited buffer cut into rows.
 // A module function -- no automaton is involved.  A RowOffsets owns the acx_rows_t; .offsets is a Column with the lifetime
 // chain of a MatchColumns' columns, and what the _batch methods take as offsets=.
@@ -2595,6 +2814,7 @@ PyMethodDef bac_methods[] = {
     ACX_SCORE_METHODS(bac_score_batch, bac_filter_by_score_batch),
     ACX_MASK_METHODS(bac_mask),
     ACX_SPANS_METHODS(bac_spans),
+    ACX_SNIPPETS_METHODS(bac_snippets),
     {"_info", bac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
     {nullptr, nullptr, 0, nullptr},
 };
@@ -2621,6 +2841,8 @@ PyMethodDef module_methods[] = {
      "_mask_fill(fill, text) -> int: the fill byte mask_all takes from `fill` (text: the str class's rule), or its error"},
     {"_spans_gap", mod_spans_gap, METH_O,
      "_spans_gap(gap) -> int: the gap cover_spans takes from its `gap` argument, or its error"},
+    {"_snippets_context", mod_snippets_context, METH_O,
+     "_snippets_context(context) -> int: the budget find_matches_as_snippets takes from its `context` argument, or its error"},
     {"_mask_per_character", mod_mask_per_character, METH_VARARGS,
      "_mask_per_character(haystack, row, text) -> str | bytes: a str haystack's masked row (one entry per UTF-8 byte) as "
      "mask_all (text) / match_mask return it: one entry per character"},
@@ -2669,6 +2891,9 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
     PyType_Spec ms_spec = {"ahocorasick_rs.MatchSpans", sizeof(MatchSpansObject), 0,
                            Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, ms_slots};
     MatchSpansType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&ms_spec));
+    PyType_Spec sn_spec = {"ahocorasick_rs.MatchSnippets", sizeof(MatchSnippetsObject), 0,
+                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, sn_slots};
+    MatchSnippetsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&sn_spec));
     MaskedRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mr_spec));
     RowOffsetsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&ro_spec));
     FilteredRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&fr_spec));
@@ -2676,10 +2901,10 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
     MatchColumnsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mc_spec));
     ColumnType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&col_spec));
     PatternCountsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&pc_spec));
-    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType || !RowScoresType || !MaskedRowsType || !RowOffsetsType || !MatchSpansType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
-    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType, RowScoresType, MaskedRowsType, RowOffsetsType, MatchSpansType}) { // (the module holds one reference, the globals the other)
+    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType || !RowScoresType || !MaskedRowsType || !RowOffsetsType || !MatchSpansType || !MatchSnippetsType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
+    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType, RowScoresType, MaskedRowsType, RowOffsetsType, MatchSpansType, MatchSnippetsType}) { // (the module holds one reference, the globals the other)
         Py_INCREF(tp);
-        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : tp == RowScoresType ? "RowScores" : tp == MaskedRowsType ? "MaskedRows" : tp == RowOffsetsType ? "RowOffsets" : tp == MatchSpansType ? "MatchSpans" : "MatchColumns",
+        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : tp == RowScoresType ? "RowScores" : tp == MaskedRowsType ? "MaskedRows" : tp == RowOffsetsType ? "RowOffsets" : tp == MatchSpansType ? "MatchSpans" : tp == MatchSnippetsType ? "MatchSnippets" : "MatchColumns",
                                reinterpret_cast<PyObject *>(tp)) < 0) {
             Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);
             return nullptr;

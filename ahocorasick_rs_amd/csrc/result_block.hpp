@@ -54,7 +54,7 @@ void free_result(T *r) {
 // has an address that DLPack consumers accept) and a multiple of 256 bytes behind the previous one.  The last part is
 // rounded up to `tail` bytes.
 struct Layout {
-    uint64_t at[4] = {0, 0, 0, 0}, bytes = 0;
+    uint64_t at[5] = {0, 0, 0, 0, 0}, bytes = 0;
 };
 constexpr Layout block_layout(std::initializer_list<uint64_t> part_bytes, uint64_t tail = 256) {
     Layout L;

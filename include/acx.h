@@ -46,6 +46,9 @@ extern "C" {
  *     acx_free_rows);
  *     eighth addendum (additive as well): acx_spans / acx_spans_device / acx_spans_host / acx_spans_rows_device, ACX_SPAN_*,
  *     the acx_spans_t accessors (acx_spans_count, _rows, _on_device, _data, _copy, acx_free_spans);
+ *     ninth addendum (additive as well): acx_snippets / acx_snippets_device / acx_snippets_host / acx_snippets_rows_device,
+ *     ACX_SNIP_*, the acx_snippets_t accessors (acx_snippets_count, _rows, _nbytes, _on_device, _data, _copy,
+ *     acx_free_snippets);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -770,6 +773,76 @@ int acx_spans_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts /*
                    int64_t *row_offsets, int64_t *start, int64_t *end, uint64_t *n_spans);
 int acx_spans_rows_device(const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint64_t n_hay, uint64_t gap,
                           int64_t *d_row_offsets, int64_t *d_start, int64_t *d_end, uint64_t *n_spans);
+
+/* ---- snippets: the matched text and the text around it -- the audit line, the KWIC snippet, grep -o and grep -C in bytes --
+ * as the caller's own bytes, where the search ran.  One snippet per match of acx_find_batch / acx_find_device for the same match
+ * kind and overlapping, with byte offsets (codepoints = 0), in the find's order.  THE DEFINITION, for a record (p, s, e) in a row
+ * of L bytes B (row-local byte offsets) and a budget of `context` bytes on each side:
+ *   s' = min(s, L);  e' = min(max(e, s'), L)                        (any record is memory-safe)
+ *   lo = s' - min(s', context);  hi = e' + min(context, L - e')     (no sum can wrap)
+ *   ACX_SNIPPET_UTF8 only:  up to 3 times: if lo < s' and B[lo] in 0x80..0xBF: lo += 1
+ *                        up to 3 times: if e' < hi < L and B[hi] in 0x80..0xBF: hi -= 1
+ *   snippet = B[lo:hi];  lead = s' - lo
+ * The context is clipped to the row: snippets never cross a row.  With ACX_SNIPPET_UTF8 the ends move INWARD to a character
+ * boundary and never into the match, so a snippet of valid UTF-8 around a match on character boundaries decodes; the three
+ * steps bound the trim for invalid UTF-8 too.  Snippets of an overlapping search, or with context > 0, may overlap one another:
+ * they are independent copies.  The bytes are the caller's own (a case-insensitive handle matches on a folded copy and cuts
+ * the unfolded bytes).  context >= 2^63 and any other flag bit: ACX_EINVAL.
+ * The result, n = the number of matches:
+ *   ACX_SNIP_DATA         offsets[n] bytes: the snippets back to back
+ *   ACX_SNIP_OFFSETS      n + 1 int64 words from 0: snippet i = data[offsets[i] .. offsets[i + 1])
+ *   ACX_SNIP_PATTERN      n int64 words: the pattern of match i (the column of acx_find_columns*)
+ *   ACX_SNIP_LEAD         n int64 words: the bytes of snippet i in front of the match, which begins at data[offsets[i] + lead[i]]
+ *   ACX_SNIP_ROW_OFFSETS  a batch only: rows + 1 int64 words from 0 to n, the CSR form over snippets
+ * acx_snippets: host haystacks (offsets: n_hay + 1, or NULL: one haystack of len bytes, no row offsets), a host result.
+ * acx_find / acx_find_batch runs as it is and chooses its own route; the records cross the bus and acx_snippets_host cuts.
+ * acx_snippets_device: acx_find_device's pipeline (d_offsets / uniform_len as there; neither: one haystack, acx_snippets_rows is
+ * 0 and there are no row offsets), then the stage on the same stream: the result lies in HBM on the automaton's device.  The
+ * call returns when the size of the data is known (8 bytes cross the bus); the gather may still run: acx_snippets_data / _copy
+ * wait for it.  d_hay and d_offsets must stay valid and unchanged until then.  An overlapping search on a handle that is not
+ * Standard is ACX_EOVERLAP before any device state; a result block that cannot be allocated is ACX_ENOMEM. */
+#define ACX_SNIP_DATA 0
+#define ACX_SNIP_OFFSETS 1
+#define ACX_SNIP_PATTERN 2
+#define ACX_SNIP_LEAD 3
+#define ACX_SNIP_ROW_OFFSETS 4
+#define ACX_SNIPPET_UTF8 1 /* acx_snippets* flags: the ends move inward to a character boundary */
+typedef struct acx_snippets acx_snippets_t;
+int acx_snippets(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one haystack */,
+                 uint64_t n_hay, int overlapping, uint64_t context, uint32_t flags, acx_snippets_t **out);
+int acx_snippets_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                        uint64_t uniform_len, int overlapping, uint64_t context, uint32_t flags, acx_snippets_t **out);
+uint64_t acx_snippets_count(const acx_snippets_t *s);  /* n: the snippets; valid when the call has returned     */
+uint64_t acx_snippets_rows(const acx_snippets_t *s);   /* the rows of the batch; 0: one haystack                */
+uint64_t acx_snippets_nbytes(const acx_snippets_t *s); /* the size of the data; valid when the call has returned */
+int acx_snippets_on_device(const acx_snippets_t *s);   /* 1: the parts are in HBM, 0: host memory               */
+/* host or device pointer by acx_snippets_on_device: part `which` (ACX_SNIP_*); waits for the device stage.  NULL: no such part
+ * (the single form has no row offsets), or the wait failed.  Valid until acx_free_snippets. */
+const void *acx_snippets_data(const acx_snippets_t *s, int which);
+int acx_snippets_copy(const acx_snippets_t *s, int which, void *host_dst);
+void acx_free_snippets(acx_snippets_t *s);
+/* the cut itself, over a caller's records: the definition above, whatever the records say.
+ * acx_snippets_host: host memory, no device needed -- the definition inside the library; m: n_m records, all rows behind one
+ * another, counts[h] of them row h's (ACX_EINVAL when they do not sum to n_m), or counts = NULL: one row holds them all;
+ * offsets: n_hay + 1 from 0 to len (ACX_EINVAL when they do not rise from 0 to len), or NULL: one row of len bytes.  A
+ * two-call form: every output may be NULL (not wanted) and *total is always set -- sizes first, then the fill.  out_offsets:
+ * n_m + 1 words; pattern, lead: n_m words; row_offsets: n_hay + 1 words (one row: 2); data: *total bytes.
+ * acx_snippets_rows_device: the device stage alone on a caller's records and counts (they must sum to n: checked before a
+ * kernel reads a record by them, and before anything is written) and bytes, cut by d_offsets, by uniform_len, or one row, in
+ * HBM on one device; needs no automaton; synchronous: the outputs are complete when it returns.  d_out_offsets: n + 1 words;
+ * d_pattern, d_lead: n words; d_row_offsets: n_hay + 1 words -- all written, every pointer 8-byte aligned; d_data: 16-byte
+ * aligned, data_capacity bytes.  *total is reported whenever the sizes were made; total > data_capacity: nothing is stored to
+ * d_data and the call returns ACX_ETOOBIG (the other outputs are complete).  Exactly *total bytes are written at d_data and
+ * nothing behind them -- there is no round-up.  n = 0 writes the zero offsets and launches nothing else (the counts are not
+ * read). */
+int acx_snippets_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts /* NULL: one row */, uint64_t n_hay,
+                      const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one row */, uint64_t context,
+                      uint32_t flags, int64_t *out_offsets, int64_t *pattern, int64_t *lead, int64_t *row_offsets,
+                      uint8_t *data /* NULL: sizes only */, uint64_t *total);
+int acx_snippets_rows_device(const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, uint64_t n_hay, const void *d_hay,
+                             uint64_t len, const uint64_t *d_offsets, uint64_t uniform_len, uint64_t context, uint32_t flags,
+                             int64_t *d_out_offsets, int64_t *d_pattern, int64_t *d_lead, int64_t *d_row_offsets, uint8_t *d_data,
+                             uint64_t data_capacity, uint64_t *total);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
