@@ -15,8 +15,10 @@
 
 #include <cstdint>
 #include <cstring>
+#include <iterator>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "acx.h"
@@ -176,19 +178,66 @@ PyObject *matches_to_list(const acx_match_t *m, uint64_t n) {
     return list;
 }
 
-// run acx_find with the GIL released (py.detach, src/lib.rs:238, 261, 433)
-int find_nogil(acx_automaton_t *a, const uint8_t *hay, uint64_t len, int overlapping,
-               int codepoints, acx_match_t **out, uint64_t *n) {
+// f() with the GIL released (py.detach, src/lib.rs:238, 261, 433)
+template <typename F> int nogil(F &&f) {
     int rc;
     Py_BEGIN_ALLOW_THREADS
-    rc = acx_find(a, hay, len, overlapping, codepoints, out, n);
+    rc = f();
     Py_END_ALLOW_THREADS
     return rc;
 }
 
-bool utf8_is_ascii(const char *s, Py_ssize_t n, PyObject *str) {
-    (void)s; (void)n;
-    return PyUnicode_IS_ASCII(str);
+// An int argument: a real int, no bool (TypeError, naming the argument).  overflow: -1 / 0 / +1 as the value lies below, in or
+// above int64 (*out is then -1); the range and its message are the caller's.  A caller without a rule for that passes none and
+// gets CPython's own OverflowError.
+bool parse_int(PyObject *o, const char *name, long long *out, int *overflow = nullptr) {
+    if (!PyLong_Check(o) || PyBool_Check(o)) {
+        PyErr_Format(PyExc_TypeError, "argument '%s': '%.100s' object cannot be converted to 'PyInt'", name, Py_TYPE(o)->tp_name);
+        return false;
+    }
+    int of = 0;
+    *out = PyLong_AsLongLongAndOverflow(o, &of);
+    if (*out == -1 && !of && PyErr_Occurred()) return false;
+    if (overflow) *overflow = of;
+    else if (of) { PyLong_AsLongLong(o); return false; } // (raises it)
+    return true;
+}
+
+// gap / context: an int 0 .. 2^63 - 1; sets the exception
+bool parse_u63(PyObject *o, const char *name, uint64_t *out) {
+    long long v;
+    int overflow;
+    if (!parse_int(o, name, &v, &overflow)) return false;
+    if (overflow || v < 0) {
+        PyErr_Format(PyExc_ValueError, "%s must be in range(2**63)", name);
+        return false;
+    }
+    *out = (uint64_t)v;
+    return true;
+}
+
+// the items item(b) .. item(e - 1) as a list; nullptr (and the list dropped) when an item cannot be made
+template <typename Item> PyObject *list_of(uint64_t b, uint64_t e, Item &&item) {
+    PyObject *list = PyList_New((Py_ssize_t)(e - b));
+    for (uint64_t i = b; list && i < e; i++) {
+        PyObject *x = item(i);
+        if (!x) { Py_CLEAR(list); break; }
+        PyList_SET_ITEM(list, (Py_ssize_t)(i - b), x);
+    }
+    return list;
+}
+
+// ... cut into one list per row by the rows' offsets (ro: rows + 1 entries), or, ro = null, the n items as one list
+template <typename Item> PyObject *rows_of(const std::vector<int64_t> *ro, uint64_t n, Item &&item) {
+    if (!ro) return list_of(0, n, item);
+    return list_of(0, ro->size() - 1, [&](uint64_t h) { return list_of((uint64_t)(*ro)[h], (uint64_t)(*ro)[h + 1], item); });
+}
+
+// item i of a blob cut by offsets: bytes, or (utf8) the decoded str
+PyObject *cut_item(const std::vector<uint8_t> &data, const std::vector<int64_t> &off, uint64_t i, bool utf8) {
+    const char *p = reinterpret_cast<const char *>(data.data()) + off[(size_t)i];
+    const Py_ssize_t n = (Py_ssize_t)(off[(size_t)i + 1] - off[(size_t)i]);
+    return utf8 ? PyUnicode_DecodeUTF8(p, n, nullptr) : PyBytes_FromStringAndSize(p, n);
 }
 
 PyObject *info_dict(acx_automaton_t *a) {
@@ -284,55 +333,60 @@ bool pack_sequence(PyObject *haystacks, bool utf8, bool named, Packed *out) {
     return true;
 }
 
-// Batched search shared by both classes: `items` are str (utf8 = true) or
-// buffers.  Returns list[list[tuple]].  devices: None = the object's own device; a sequence of
-// ordinals = the batch is cut into that many contiguous ranges of haystacks, one host thread per
-// device (acx_find_batch_multi).
-PyObject *find_batch_impl(acx_automaton_t *a, PyObject *haystacks, int overlapping, bool utf8,
-                          PyObject *devices, Replicas **replicas) {
-    std::vector<acx_automaton_t *> handles;
-    if (!batch_handles(a, devices, replicas, &handles)) return nullptr;
-    Packed in;
-    if (!pack_sequence(haystacks, utf8, false, &in)) return nullptr;
-    const Py_ssize_t n = in.n;
-    std::vector<uint64_t> counts((size_t)n, 0);
-    acx_match_t *m = nullptr; uint64_t total = 0;
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = acx_find_batch_multi(handles.data(), (int)handles.size(), in.blob.data(), in.off.data(), (uint64_t)n, overlapping,
-                              (utf8 && !in.all_ascii) ? 1 : 0, &m, &total, counts.data());
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    PyObject *outer = PyList_New(n);
-    uint64_t pos = 0;
-    for (Py_ssize_t i = 0; outer && i < n; i++) {
-        PyObject *inner = matches_to_list(m + pos, counts[(size_t)i]);
-        if (!inner) { Py_CLEAR(outer); break; }
-        PyList_SET_ITEM(outer, i, inner);
-        pos += counts[(size_t)i];
+// One entry per CHARACTER of a str haystack.  row: what the library made of hay's UTF-8 bytes, one entry per byte.  text: the
+// entries of a covered character's continuation bytes are dropped (fill is ASCII, so a continuation byte that differs from
+// the haystack's is a covered one) and the rest is decoded; else (the 0 / 1 mask) the entry of every continuation byte is.
+PyObject *per_character(const uint8_t *hay, const uint8_t *row, size_t len, bool text) {
+    std::string s;
+    s.reserve(len);
+    for (size_t i = 0; i < len; i++) {
+        const bool cont = (hay[i] & 0xC0) == 0x80;
+        if (cont && (!text || row[i] != hay[i])) continue;
+        s.push_back((char)row[i]);
     }
-    acx_free_matches(m);
-    return outer;
+    return text ? PyUnicode_DecodeUTF8(s.data(), (Py_ssize_t)s.size(), nullptr) : PyBytes_FromStringAndSize(s.data(), (Py_ssize_t)s.size());
 }
 
 // ---------------------------------------------------------------------------
-// AhoCorasick (str)
+// The two automaton classes.  Both begin alike, so a method that both have is ONE function: it takes the automaton from the
+// base and asks the object whether it is the str class.
 // ---------------------------------------------------------------------------
-struct AcObject {
+struct AutomatonObject {
     PyObject_HEAD
     acx_automaton_t *ac;
-    PyObject *patterns; // list[str] or NULL   (src/lib.rs:30-33 `patterns: Option<Vec<Py<PyString>>>`)
     Replicas *replicas; // automata on other devices (batch calls with devices=[...]), or NULL
 };
+struct AcObject : AutomatonObject { // AhoCorasick (str)
+    PyObject *patterns; // list[str] or NULL   (src/lib.rs:30-33 `patterns: Option<Vec<Py<PyString>>>`)
+};
+typedef AutomatonObject BacObject;  // BytesAhoCorasick
 
-void ac_dealloc(PyObject *self) {
-    AcObject *o = reinterpret_cast<AcObject *>(self);
+PyTypeObject *AhoCorasickType = nullptr;
+acx_automaton_t *ac_of(PyObject *self) { return reinterpret_cast<AutomatonObject *>(self)->ac; }
+bool utf8_of(PyObject *self) { return Py_TYPE(self) == AhoCorasickType; } // the str class: haystacks are str, searched as UTF-8
+
+void automaton_dealloc(PyObject *self) {
+    AutomatonObject *o = reinterpret_cast<AutomatonObject *>(self);
     if (o->ac) acx_free_automaton(o->ac);
     free_replicas(o->replicas);
-    Py_XDECREF(o->patterns);
+    if (utf8_of(self)) Py_XDECREF(static_cast<AcObject *>(o)->patterns);
     PyTypeObject *tp = Py_TYPE(self);
     tp->tp_free(self);
     Py_DECREF(tp);
+}
+
+// the packed patterns -> a new object of `type`, or the build's error (the reference yields the GIL while building,
+// src/lib.rs:198)
+AutomatonObject *new_automaton(PyTypeObject *type, std::vector<uint8_t> &blob, const std::vector<uint64_t> &off, int mk, int impl, int ci) {
+    acx_automaton_t *ac = nullptr;
+    blob.push_back(0);
+    const int rc = nogil([&] { return acx_build_ex(blob.data(), off.data(), off.size() - 1, mk, impl, ci ? ACX_BUILD_ASCII_CASE_INSENSITIVE : 0, &ac); });
+    if (rc != ACX_OK) { raise_acx(rc); return nullptr; }
+    AutomatonObject *self = reinterpret_cast<AutomatonObject *>(type->tp_alloc(type, 0));
+    if (!self) { acx_free_automaton(ac); return nullptr; }
+    self->ac = ac;
+    self->replicas = nullptr;
+    return self;
 }
 
 // src/lib.rs:134-224
@@ -391,19 +445,9 @@ PyObject *ac_new(PyTypeObject *type, PyObject *args, PyObject *kwargs) {
     Py_DECREF(iter);
     if (failed || PyErr_Occurred()) { Py_DECREF(kept); return nullptr; } // iterator errors propagate
     bool do_store = store == 1 || (store == -1 && heuristic_store);
-    acx_automaton_t *ac = nullptr;
-    int rc;
-    blob.push_back(0);
-    Py_BEGIN_ALLOW_THREADS // the reference yields the GIL while building, src/lib.rs:198
-    rc = acx_build_ex(blob.data(), off.data(), off.size() - 1, mk, impl, ci ? ACX_BUILD_ASCII_CASE_INSENSITIVE : 0, &ac);
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) { Py_DECREF(kept); return raise_acx(rc); }
-    AcObject *self = reinterpret_cast<AcObject *>(type->tp_alloc(type, 0));
-    if (!self) { acx_free_automaton(ac); Py_DECREF(kept); return nullptr; }
-    self->ac = ac;
-    self->replicas = nullptr;
-    if (do_store) self->patterns = kept;
-    else { self->patterns = nullptr; Py_DECREF(kept); }
+    AcObject *self = static_cast<AcObject *>(new_automaton(type, blob, off, mk, impl, ci));
+    if (self && do_store) self->patterns = kept;
+    else Py_DECREF(kept);
     return reinterpret_cast<PyObject *>(self);
 }
 
@@ -480,18 +524,13 @@ PyObject *replaced_result(acx_replaced_t *r, bool utf8, std::vector<uint64_t> *b
     return s;
 }
 
-// one host haystack (or a batch: offsets != null) -> acx_replace with the GIL released
-int replace_nogil(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
-                  const std::vector<uint8_t> &blob, const std::vector<uint64_t> &off, acx_replaced_t **out) {
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = acx_replace(a, hay, len, offsets, n_hay, blob.data(), off.data(), off.size() - 1, out);
-    Py_END_ALLOW_THREADS
-    return rc;
-}
-
-// replace_all_batch of both classes: list[str] / list[bytes], [replace_all(h, replace_with) for h in haystacks]
-PyObject *replace_batch_impl(acx_automaton_t *a, PyObject *haystacks, PyObject *replace_with, bool utf8) {
+// replace_all_batch: list[str] / list[bytes], [replace_all(h, replace_with) for h in haystacks]
+PyObject *replace_all_batch(PyObject *self, PyObject *args, PyObject *kwargs) {
+    static const char *kw[] = {"haystacks", "replace_with", nullptr};
+    PyObject *haystacks, *replace_with;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "OO:replace_all_batch", const_cast<char **>(kw), &haystacks, &replace_with)) return nullptr;
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
     Packed in;
     if (!pack_sequence(haystacks, utf8, true, &in)) return nullptr;
     const Py_ssize_t n = in.n;
@@ -499,317 +538,56 @@ PyObject *replace_batch_impl(acx_automaton_t *a, PyObject *haystacks, PyObject *
     std::vector<uint64_t> off;
     if (!replacements(replace_with, utf8, &blob, &off)) return nullptr;
     acx_replaced_t *r = nullptr;
-    const int rc = replace_nogil(a, in.blob.data(), in.off[(size_t)n], in.off.data(), (uint64_t)n, blob, off, &r);
+    const int rc = nogil([&] {
+        return acx_replace(a, in.blob.data(), in.off[(size_t)n], in.off.data(), (uint64_t)n, blob.data(), off.data(), off.size() - 1, &r);
+    });
     if (rc != ACX_OK) return raise_acx(rc);
     std::vector<uint64_t> bounds((size_t)n + 1, 0);
     PyObject *whole = replaced_result(r, false, &bounds);
     if (!whole) return nullptr;
     const char *w = PyBytes_AS_STRING(whole);
-    PyObject *list = PyList_New(n);
-    for (Py_ssize_t i = 0; list && i < n; i++) {
+    PyObject *list = list_of(0, (uint64_t)n, [&](uint64_t i) {
         const char *p = w + bounds[(size_t)i];
         const Py_ssize_t len = (Py_ssize_t)(bounds[(size_t)i + 1] - bounds[(size_t)i]);
-        PyObject *item = utf8 ? PyUnicode_DecodeUTF8(p, len, "strict") : PyBytes_FromStringAndSize(p, len);
-        if (!item) { Py_CLEAR(list); break; }
-        PyList_SET_ITEM(list, i, item);
-    }
+        return utf8 ? PyUnicode_DecodeUTF8(p, len, "strict") : PyBytes_FromStringAndSize(p, len);
+    });
     Py_DECREF(whole);
     return list;
 }
 
-// src/lib.rs:229-249: code-point offsets
-PyObject *ac_find_indexes(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    AcObject *self = reinterpret_cast<AcObject *>(self_);
-    PyObject *hay; int overlapping;
-    if (!parse_find_args(args, kwargs, "O|O:find_matches_as_indexes", &hay, &overlapping)) return nullptr;
-    const char *s; Py_ssize_t len;
-    if (!str_view(hay, &s, &len)) return nullptr;
-    // ASCII haystack: byte offset == code-point index, skip the device fix-up
-    int codepoints = utf8_is_ascii(s, len, hay) ? 0 : 1;
-    acx_match_t *m = nullptr; uint64_t n = 0;
-    int rc = find_nogil(self->ac, reinterpret_cast<const uint8_t *>(s), (uint64_t)len, overlapping,
-                        codepoints, &m, &n);
-    if (rc != ACX_OK) return raise_acx(rc);
-    PyObject *list = matches_to_list(m, n);
-    acx_free_matches(m);
-    return list;
-}
-
-// src/lib.rs:253-272
-PyObject *ac_find_strings(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    AcObject *self = reinterpret_cast<AcObject *>(self_);
-    PyObject *hay; int overlapping;
-    if (!parse_find_args(args, kwargs, "O|O:find_matches_as_strings", &hay, &overlapping)) return nullptr;
-    const char *s; Py_ssize_t len;
-    if (!str_view(hay, &s, &len)) return nullptr;
-    acx_match_t *m = nullptr; uint64_t n = 0;
-    int rc = find_nogil(self->ac, reinterpret_cast<const uint8_t *>(s), (uint64_t)len, overlapping,
-                        0 /* byte offsets */, &m, &n);
-    if (rc != ACX_OK) return raise_acx(rc);
-    PyObject *list = PyList_New((Py_ssize_t)n);
-    for (uint64_t i = 0; list && i < n; i++) {
-        PyObject *item;
-        if (self->patterns) { // clone_ref of the stored pattern, src/lib.rs:263-266
-            item = PyList_GET_ITEM(self->patterns, (Py_ssize_t)m[i].pattern);
-            Py_INCREF(item);
-        } else {              // slice of the haystack by byte offsets, src/lib.rs:267-270
-            item = PyUnicode_DecodeUTF8(s + m[i].start, (Py_ssize_t)(m[i].end - m[i].start), "strict");
-            if (!item) { Py_CLEAR(list); break; }
-        }
-        PyList_SET_ITEM(list, (Py_ssize_t)i, item);
-    }
-    acx_free_matches(m);
-    return list;
-}
-
-PyObject *ac_find_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
+// find_matches_as_indexes_batch: list[list[tuple]].  devices: None = the object's own device; a sequence of ordinals = the
+// batch is cut into that many contiguous ranges of haystacks, one host thread per device (acx_find_batch_multi).
+PyObject *find_batch(PyObject *self, PyObject *args, PyObject *kwargs) {
     static const char *kw[] = {"haystacks", "overlapping", "devices", nullptr};
     PyObject *hs, *ov = nullptr, *devs = nullptr; int overlapping = 0;
     if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|OO:find_matches_as_indexes_batch",
                                      const_cast<char **>(kw), &hs, &ov, &devs))
         return nullptr;
     if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
-    AcObject *self = reinterpret_cast<AcObject *>(self_);
-    return find_batch_impl(self->ac, hs, overlapping, true, devs, &self->replicas);
-}
-
-PyObject *ac_replace_all(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    static const char *kw[] = {"haystack", "replace_with", nullptr};
-    PyObject *hay, *rw;
-    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "OO:replace_all", const_cast<char **>(kw), &hay, &rw)) return nullptr;
-    const char *s; Py_ssize_t len;
-    if (!str_view(hay, &s, &len)) return nullptr;
-    std::vector<uint8_t> blob;
-    std::vector<uint64_t> off;
-    if (!replacements(rw, true, &blob, &off)) return nullptr;
-    acx_replaced_t *r = nullptr;
-    const int rc = replace_nogil(reinterpret_cast<AcObject *>(self_)->ac, reinterpret_cast<const uint8_t *>(s),
-                                 (uint64_t)len, nullptr, 0, blob, off, &r);
+    std::vector<acx_automaton_t *> handles;
+    if (!batch_handles(ac_of(self), devs, &reinterpret_cast<AutomatonObject *>(self)->replicas, &handles)) return nullptr;
+    Packed in;
+    if (!pack_sequence(hs, utf8_of(self), false, &in)) return nullptr;
+    std::vector<uint64_t> counts((size_t)in.n, 0);
+    acx_match_t *m = nullptr; uint64_t total = 0;
+    const int rc = nogil([&] {
+        return acx_find_batch_multi(handles.data(), (int)handles.size(), in.blob.data(), in.off.data(), (uint64_t)in.n, overlapping,
+                                    (utf8_of(self) && !in.all_ascii) ? 1 : 0, &m, &total, counts.data());
+    });
     if (rc != ACX_OK) return raise_acx(rc);
-    return replaced_result(r, true);
+    uint64_t pos = 0;
+    PyObject *outer = list_of(0, (uint64_t)in.n, [&](uint64_t i) {
+        PyObject *inner = matches_to_list(m + pos, counts[(size_t)i]);
+        pos += counts[(size_t)i];
+        return inner;
+    });
+    acx_free_matches(m);
+    return outer;
 }
 
-PyObject *ac_replace_all_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    static const char *kw[] = {"haystacks", "replace_with", nullptr};
-    PyObject *hs, *rw;
-    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "OO:replace_all_batch", const_cast<char **>(kw), &hs, &rw)) return nullptr;
-    return replace_batch_impl(reinterpret_cast<AcObject *>(self_)->ac, hs, rw, true);
-}
+PyObject *automaton_info(PyObject *self, PyObject *) { return info_dict(ac_of(self)); }
 
-PyObject *ac_info(PyObject *self_, PyObject *) {
-    return info_dict(reinterpret_cast<AcObject *>(self_)->ac);
-}
-
-// summaries (defined behind the DLPack adapter below): K = SUM_IS_MATCH .. SUM_BY_PATTERN, BATCH: the *_batch form
 enum { SUM_IS_MATCH = 0, SUM_FIND_FIRST = 1, SUM_COUNT = 2, SUM_BY_PATTERN = 3 };
-template <int K, bool BATCH> PyObject *ac_summary(PyObject *self_, PyObject *args, PyObject *kwargs);
-template <int K, bool BATCH> PyObject *bac_summary(PyObject *self_, PyObject *args, PyObject *kwargs);
-#define ACX_SUMMARY_METHODS(fn)                                                                                                 \
-    {"is_match", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_IS_MATCH, false>)),                         \
-     METH_VARARGS | METH_KEYWORDS,                                                                                              \
-     "[extension] bool(find_matches_as_indexes(haystack)) without the match list (the crate's is_match).  No early exit: "     \
-     "one search over the whole haystack."},                                                                                    \
-    {"find_first", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_FIND_FIRST, false>)),                     \
-     METH_VARARGS | METH_KEYWORDS,                                                                                              \
-     "[extension] find_matches_as_indexes(haystack)[0], or None (the crate's find for the object's match kind)."},            \
-    {"count_matches", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_COUNT, false>)),                       \
-     METH_VARARGS | METH_KEYWORDS, "[extension] len(find_matches_as_indexes(haystack, overlapping))."},                        \
-    {"count_by_pattern", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_BY_PATTERN, false>)),               \
-     METH_VARARGS | METH_KEYWORDS,                                                                                              \
-     "[extension] one int per pattern: how many of find_matches_as_indexes(haystack, overlapping) name it."},                  \
-    {"is_match_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_IS_MATCH, true>)),                    \
-     METH_VARARGS | METH_KEYWORDS, "[extension] [self.is_match(h) for h in haystacks] in one call."},                          \
-    {"find_first_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_FIND_FIRST, true>)),                \
-     METH_VARARGS | METH_KEYWORDS, "[extension] [self.find_first(h) for h in haystacks] in one call."},                        \
-    {"count_matches_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_COUNT, true>)),                  \
-     METH_VARARGS | METH_KEYWORDS, "[extension] [self.count_matches(h, overlapping) for h in haystacks] in one call."},        \
-    {"count_by_pattern_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<SUM_BY_PATTERN, true>)),          \
-     METH_VARARGS | METH_KEYWORDS,                                                                                              \
-     "[extension] the per-pattern totals over all haystacks: the sum of self.count_by_pattern(h, overlapping)."}
-
-// matches as columns (defined behind the DLPack adapter below)
-template <bool BATCH> PyObject *ac_columns(PyObject *self_, PyObject *args, PyObject *kwargs);
-template <bool BATCH> PyObject *bac_columns(PyObject *self_, PyObject *args, PyObject *kwargs);
-// per-haystack pattern counts as a CSR matrix (defined behind MatchColumns below)
-PyObject *ac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs);
-PyObject *bac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs);
-#define ACX_SPARSE_COUNTS_METHOD(fn)                                                                                           \
-    {"count_by_pattern_sparse_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn)),                         \
-     METH_VARARGS | METH_KEYWORDS,                                                                                             \
-     "[extension] count_by_pattern_sparse_batch(haystacks, overlapping=False, *, offsets=None, row_length=None) -> "           \
-     "PatternCounts: which patterns occur in which haystack and how often, as a CSR matrix of len(haystacks) x patterns "      \
-     "(row_offsets, pattern ascending within a row, count: int64 Columns that torch.sparse_csr_tensor takes as they are).  "   \
-     "haystacks: a sequence, as in every other _batch method, or ONE 1-D contiguous uint8 __dlpack__ tensor that holds the "   \
-     "rows back to back, cut by exactly one of offsets (a 1-D int64 __dlpack__ tensor of rows + 1 entries on the haystack's "  \
-     "device) and row_length (an int that divides the tensor's length).  A tensor on the automaton's device is searched and "  \
-     "reduced there and the result stays there; nothing but its size crosses the bus."}
-// the rows of a batch kept or dropped by match (defined behind the PatternCounts below)
-PyObject *ac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
-PyObject *bac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
-#define ACX_FILTER_METHOD(fn)                                                                                                  \
-    {"filter_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn)), METH_VARARGS | METH_KEYWORDS,            \
-     "[extension] filter_batch(haystacks, overlapping=False, *, keep='unmatched', min_matches=1, offsets=None, "               \
-     "row_length=None) -> FilteredRows: the rows of the batch with fewer than min_matches matches (keep='unmatched': drop "    \
-     "every row that contains a pattern) or with at least that many (keep='matched'), compacted where the search ran: "        \
-     ".rows (the kept source row indexes), .offsets and .data (the kept rows' own bytes back to back).  haystacks: a "          \
-     "sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "           \
-     "count_by_pattern_sparse_batch.  A tensor on the automaton's device is searched and compacted there and the result "      \
-     "stays there; nothing but its two sizes crosses the bus."}
-// per-pattern weights: a score per row, and the rows kept or dropped by score (defined behind the FilteredRows below)
-PyObject *ac_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
-PyObject *bac_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
-PyObject *ac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
-PyObject *bac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs);
-#define ACX_SCORE_METHODS(score_fn, filter_fn)                                                                                 \
-    {"score_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(score_fn)), METH_VARARGS | METH_KEYWORDS,       \
-     "[extension] score_batch(haystacks, weights, overlapping=False, *, offsets=None, row_length=None) -> RowScores: for "     \
-     "every row the sum of weights[pattern] over the matches find_matches_as_indexes_batch reports for it (int64; it wraps "   \
-     "modulo 2^64).  weights: one int per pattern, |w| < 2^31 -- a sequence of ints or an int64 / int32 buffer.  haystacks: "  \
-     "a sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "         \
-     "count_by_pattern_sparse_batch.  A tensor on the automaton's device is searched and scored there and the result stays "   \
-     "there."},                                                                                                                \
-    {"filter_by_score_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(filter_fn)),                          \
-     METH_VARARGS | METH_KEYWORDS,                                                                                             \
-     "[extension] filter_by_score_batch(haystacks, weights, overlapping=False, *, keep='unmatched', min_score=1, "             \
-     "offsets=None, row_length=None) -> FilteredRows: filter_batch with the verdict on a row taken from its score -- a row "   \
-     "is matched when score_batch's value for it is at least min_score (any int64)."}
-// the cover of a search's matches (defined behind the RowScores below): TEXT = mask_all (the haystack with its matches
-// filled), else match_mask (the 0 / 1 mask); BATCH: the *_batch form
-template <bool TEXT, bool BATCH> PyObject *ac_mask(PyObject *self_, PyObject *args, PyObject *kwargs);
-template <bool TEXT, bool BATCH> PyObject *bac_mask(PyObject *self_, PyObject *args, PyObject *kwargs);
-#define ACX_MASK_METHODS(fn)                                                                                                   \
-    {"mask_all", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<true, false>)), METH_VARARGS | METH_KEYWORDS,   \
-     "[extension] mask_all(haystack, fill, overlapping=False) -> the haystack with every byte that a match covers replaced "   \
-     "by fill and every other byte where it was: fixed-fill redaction.  fill: an int 0..255 or a one-byte buffer "             \
-     "(BytesAhoCorasick), a one-character ASCII str (AhoCorasick: a covered character becomes ONE fill, so the result has "    \
-     "len(haystack) characters).  overlapping=True on a Standard object covers the union of all occurrences."},               \
-    {"match_mask", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false, false>)),                              \
-     METH_VARARGS | METH_KEYWORDS,                                                                                             \
-     "[extension] match_mask(haystack, overlapping=False) -> bytes: 1 where a match covers the haystack's byte "               \
-     "(AhoCorasick: its character), else 0; len(haystack) entries."},                                                         \
-    {"mask_all_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<true, true>)),                            \
-     METH_VARARGS | METH_KEYWORDS,                                                                                             \
-     "[extension] mask_all_batch(haystacks, fill, overlapping=False, *, offsets=None, row_length=None) -> MaskedRows: "        \
-     "mask_all of every row in one call, as one uint8 .data in the input's own layout with its .offsets.  haystacks: a "       \
-     "sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "           \
-     "count_by_pattern_sparse_batch.  A tensor on the automaton's device is searched and painted there and the result "        \
-     "stays there.  AhoCorasick: .data is in UTF-8 bytes (a covered k-byte character is k fills); tolist() gives one fill "    \
-     "per character for a sequence of str and the bytes as they are, decoded, for a tensor."},                                \
-    {"match_mask_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false, true>)),                         \
-     METH_VARARGS | METH_KEYWORDS,                                                                                             \
-     "[extension] match_mask_batch(haystacks, overlapping=False, *, offsets=None, row_length=None) -> MaskedRows: "            \
-     "match_mask of every row in one call: .data is 1 where a match covers the byte, else 0."}
-// the merged spans of a search's matches (defined behind the MaskedRows below); BATCH: the *_batch form
-template <bool BATCH> PyObject *ac_spans(PyObject *self_, PyObject *args, PyObject *kwargs);
-template <bool BATCH> PyObject *bac_spans(PyObject *self_, PyObject *args, PyObject *kwargs);
-#define ACX_SPANS_METHODS(fn)                                                                                                  \
-    {"cover_spans", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)), METH_VARARGS | METH_KEYWORDS,      \
-     "cover_spans(haystack, overlapping=False, *, gap=0) -> MatchSpans\n\n[extension] the union of the matches that "           \
-     "find_matches_as_indexes(haystack, overlapping) reports, as two int64 columns .start / .end: matches that overlap, "      \
-     "touch or lie at most gap positions apart are ONE span -- the ranges to highlight, cut or redact.  The spans are "        \
-     "ascending and disjoint and next.start - prev.end > gap; with gap=0 they are the runs of ones of match_mask.  "           \
-     "AhoCorasick: character indexes; BytesAhoCorasick: byte offsets, and a __dlpack__ tensor on the automaton's device is "   \
-     "searched and merged there -- nothing but the number of spans crosses the bus.  gap: an int 0 .. 2**63 - 1."},           \
-    {"cover_spans_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<true>)), METH_VARARGS | METH_KEYWORDS, \
-     "cover_spans_batch(haystacks, overlapping=False, *, gap=0, offsets=None, row_length=None) -> MatchSpans\n\n"              \
-     "[extension] cover_spans of every row in one call, with .row_offsets: spans row_offsets[h] .. row_offsets[h + 1] - 1 "    \
-     "are row h's, their offsets local to it; spans never join across rows.  haystacks: a sequence, or ONE 1-D contiguous "    \
-     "uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for count_by_pattern_sparse_batch (byte "       \
-     "offsets for a tensor).  A tensor on the automaton's device is searched and merged there and the columns stay there."}
-// the matched text and its context (defined behind the MatchSpans below); BATCH: the *_batch form
-template <bool BATCH> PyObject *ac_snippets(PyObject *self_, PyObject *args, PyObject *kwargs);
-template <bool BATCH> PyObject *bac_snippets(PyObject *self_, PyObject *args, PyObject *kwargs);
-#define ACX_SNIPPETS_METHODS(fn)                                                                                               \
-    {"find_matches_as_snippets", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)),                       \
-     METH_VARARGS | METH_KEYWORDS,                                                                                             \
-     "find_matches_as_snippets(haystack, overlapping=False, *, context=0) -> MatchSnippets\n\n[extension] one snippet per "    \
-     "match that find_matches_as_columns(haystack, overlapping) reports, in its order: the matched text and up to context "    \
-     "BYTES on each side of it, clipped to the haystack, as the caller's own bytes (.data, cut by .offsets; the match begins "  \
-     ".lead bytes into its snippet; .pattern is the columns' pattern).  AhoCorasick: UTF-8 bytes, the ends moved inward to a " \
-     "character boundary, so tolist() is a list[str] and with context=0 it equals find_matches_as_strings.  "                  \
-     "BytesAhoCorasick: a __dlpack__ tensor on the automaton's device is searched and cut there -- nothing but the size of "   \
-     "the data crosses the bus.  context: an int 0 .. 2**63 - 1."},                                                            \
-    {"find_matches_as_snippets_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<true>)),                  \
-     METH_VARARGS | METH_KEYWORDS,                                                                                             \
-     "find_matches_as_snippets_batch(haystacks, overlapping=False, *, context=0, offsets=None, row_length=None) -> "           \
-     "MatchSnippets\n\n[extension] find_matches_as_snippets of every row in one call, with .row_offsets: snippets "            \
-     "row_offsets[h] .. row_offsets[h + 1] - 1 are row h's; a snippet never crosses a row.  haystacks: a sequence, or ONE 1-D " \
-     "contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for cover_spans_batch.  A tensor on " \
-     "the automaton's device is searched and cut there and every part stays there."}
-#define ACX_COLUMNS_METHODS(fn)                                                                                                 \
-    {"find_matches_as_columns", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<false>)),                        \
-     METH_VARARGS | METH_KEYWORDS,                                                                                              \
-     "[extension] find_matches_as_indexes(haystack, overlapping) as a MatchColumns: three int64 columns (pattern, start, "     \
-     "end) exported through DLPack, in host memory for a host haystack and in HBM on the automaton's device for a "            \
-     "__dlpack__ tensor there -- no tuple list, and for a tensor nothing but the number of matches crosses the bus.  The "     \
-     "call returns once that number is known; every accessor of a column, __dlpack__ included, waits for the split kernel "    \
-     "first, so a consumer on any stream sees finished data."},                                                                \
-    {"find_matches_as_columns_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fn<true>)),                   \
-     METH_VARARGS | METH_KEYWORDS,                                                                                              \
-     "[extension] find_matches_as_indexes_batch(haystacks, overlapping) as a MatchColumns with row_offsets: rows "             \
-     "row_offsets[h] .. row_offsets[h + 1] are haystack h's matches, their offsets local to it."}
-
-PyMethodDef ac_methods[] = {
-    {"find_matches_as_indexes", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_find_indexes)),
-     METH_VARARGS | METH_KEYWORDS,
-     "Return matches as tuple of (index_into_patterns, start_index_in_haystack, "
-     "end_index_in_haystack). If ``overlapping`` is ``False`` (the default), don't include "
-     "overlapping results."},
-    {"find_matches_as_strings", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_find_strings)),
-     METH_VARARGS | METH_KEYWORDS,
-     "Return matches as list of patterns (i.e. strings). If ``overlapping`` is ``False`` (the "
-     "default), don't include overlapping results."},
-    {"find_matches_as_indexes_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_find_batch)),
-     METH_VARARGS | METH_KEYWORDS,
-     "[extension] one device pass over many haystacks; equals "
-     "[self.find_matches_as_indexes(h, overlapping) for h in haystacks].  devices=[ordinals]: the batch "
-     "is cut into contiguous ranges of haystacks, one per device (replicas of the automaton are built on "
-     "first use), scanned side by side from one host thread each."},
-    {"replace_all", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_replace_all)), METH_VARARGS | METH_KEYWORDS,
-     "[extension] the haystack with every non-overlapping match (as find_matches_as_indexes reports them) replaced by "
-     "replace_with[pattern index]; replace_with has one str per pattern (ValueError otherwise)."},
-    {"replace_all_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(ac_replace_all_batch)),
-     METH_VARARGS | METH_KEYWORDS, "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
-    ACX_SUMMARY_METHODS(ac_summary),
-    ACX_COLUMNS_METHODS(ac_columns),
-    ACX_SPARSE_COUNTS_METHOD(ac_sparse_counts),
-    ACX_FILTER_METHOD(ac_filter_batch),
-    ACX_SCORE_METHODS(ac_score_batch, ac_filter_by_score_batch),
-    ACX_MASK_METHODS(ac_mask),
-    ACX_SPANS_METHODS(ac_spans),
-    ACX_SNIPPETS_METHODS(ac_snippets),
-    {"_info", ac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
-    {nullptr, nullptr, 0, nullptr},
-};
-
-PyType_Slot ac_slots[] = {
-    {Py_tp_new, reinterpret_cast<void *>(ac_new)},
-    {Py_tp_dealloc, reinterpret_cast<void *>(ac_dealloc)},
-    {Py_tp_methods, ac_methods},
-    {Py_tp_doc, const_cast<char *>(
-        "Search for multiple pattern strings against a single haystack string.\n\n"
-        "AhoCorasick(patterns, matchkind=MatchKind.Standard, store_patterns=None, implementation=None, "
-        "ascii_case_insensitive=False)")},
-    {0, nullptr},
-};
-
-// ---------------------------------------------------------------------------
-// BytesAhoCorasick
-// ---------------------------------------------------------------------------
-struct BacObject {
-    PyObject_HEAD
-    acx_automaton_t *ac;
-    Replicas *replicas;
-};
-
-void bac_dealloc(PyObject *self) {
-    BacObject *o = reinterpret_cast<BacObject *>(self);
-    if (o->ac) acx_free_automaton(o->ac);
-    free_replicas(o->replicas);
-    PyTypeObject *tp = Py_TYPE(self);
-    tp->tp_free(self);
-    Py_DECREF(tp);
-}
 
 // src/lib.rs:369-413
 PyObject *bac_new(PyTypeObject *type, PyObject *args, PyObject *kwargs) {
@@ -842,18 +620,7 @@ PyObject *bac_new(PyTypeObject *type, PyObject *args, PyObject *kwargs) {
     }
     Py_DECREF(iter);
     if (failed || PyErr_Occurred()) return nullptr;
-    acx_automaton_t *ac = nullptr;
-    int rc;
-    blob.push_back(0);
-    Py_BEGIN_ALLOW_THREADS
-    rc = acx_build_ex(blob.data(), off.data(), off.size() - 1, mk, impl, ci ? ACX_BUILD_ASCII_CASE_INSENSITIVE : 0, &ac);
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    BacObject *self = reinterpret_cast<BacObject *>(type->tp_alloc(type, 0));
-    if (!self) { acx_free_automaton(ac); return nullptr; }
-    self->ac = ac;
-    self->replicas = nullptr;
-    return reinterpret_cast<PyObject *>(self);
+    return reinterpret_cast<PyObject *>(new_automaton(type, blob, off, mk, impl, ci));
 }
 
 // ---- device-resident haystacks (extends the buffer adapter of src/lib.rs:276-340): an object that
@@ -915,6 +682,60 @@ void dlpack_release(PyObject *cap) { // we consumed the capsule: rename it and r
     Py_DECREF(cap);
 }
 
+// the tensor behind a capsule that dlpack_view returned
+const DLTensorC &capsule_tensor(PyObject *cap) { return static_cast<DLManagedTensorC *>(PyCapsule_GetPointer(cap, "dltensor"))->dl_tensor; }
+
+// The haystack of a single-haystack method: `len` bytes at `p`, in HBM (on_device) or in host memory.  It owns the Py_buffer
+// or the capsule that keeps the bytes where they are, until it goes out of scope.
+struct HaystackView {
+    const uint8_t *p = nullptr;
+    uint64_t len = 0;
+    bool on_device = false;
+    bool is_ascii = false; // a str without a character beyond ASCII: byte offsets are its character indexes
+    Py_buffer buf;
+    bool has_buf = false;
+    PyObject *cap = nullptr;
+    HaystackView() = default;
+    HaystackView(const HaystackView &) = delete;
+    HaystackView &operator=(const HaystackView &) = delete;
+    ~HaystackView() { if (has_buf) PyBuffer_Release(&buf); dlpack_release(cap); }
+};
+
+// utf8 (the str class): a str, as its UTF-8 bytes.  Else a contiguous byte buffer or, tensors (the methods that take one): an
+// object that is no buffer but exports __dlpack__ -- on want_device if it is in HBM (want_device < 0: on any).  Sets the
+// exception.
+bool haystack_view(PyObject *hay, bool utf8, bool tensors, int want_device, HaystackView *v) {
+    if (utf8) {
+        const char *s; Py_ssize_t len;
+        if (!str_view(hay, &s, &len)) return false;
+        v->p = reinterpret_cast<const uint8_t *>(s);
+        v->len = (uint64_t)len;
+        v->is_ascii = PyUnicode_IS_ASCII(hay);
+        return true;
+    }
+    if (tensors && !PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
+        v->cap = dlpack_view(hay, want_device, &v->p, &v->len, &v->on_device);
+        return v->cap != nullptr;
+    }
+    if (!get_bytes_view(hay, &v->buf)) return false;
+    v->has_buf = true;
+    v->p = static_cast<const uint8_t *>(v->buf.buf);
+    v->len = (uint64_t)v->buf.len;
+    return true;
+}
+
+// One call on a HaystackView with the GIL released: host(p, len), or device(p, len) on a tensor in HBM -- behind everything
+// queued on its device: the producer's kernels may still be writing the tensor on their own stream, and the library's
+// streams are non-blocking ones.  device_ordinal: the tensor's (the automaton's: dlpack_view checked that).
+template <typename Host, typename Device>
+int single_dispatch(int device_ordinal, const HaystackView &v, Host &&host, Device &&device) {
+    return nogil([&] {
+        if (!v.on_device) return host(v.p, v.len);
+        const int rc = acx_device_synchronize_on(device_ordinal);
+        return rc == ACX_OK ? device(v.p, v.len) : rc;
+    });
+}
+
 // ---------------------------------------------------------------------------
 // summaries: is_match / find_first / count_matches / count_by_pattern and their batch forms (acx_summarize: the crate's
 // AhoCorasick::is_match and ::find, and the counts of its iterators; the reference binding stops at the match list)
@@ -926,20 +747,14 @@ struct Summary {
 };
 
 // one acx_summarize call (on_device: acx_summarize_device on a tensor in HBM) and the copies of the parts the method
-// returns, with the GIL released
-int summarize_nogil(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
-                    bool on_device, int overlapping, int codepoints, int kind, bool batch, Summary *out) {
+// returns; the caller has released the GIL
+int summarize(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
+              bool on_device, int overlapping, int codepoints, int kind, bool batch, Summary *out) {
     const uint32_t what = kind == SUM_FIND_FIRST || (kind == SUM_IS_MATCH && batch) ? ACX_SUM_FIRST
                           : kind == SUM_BY_PATTERN ? ACX_SUM_BY_PATTERN : 0;
-    int rc = ACX_OK;
-    Py_BEGIN_ALLOW_THREADS
     acx_summary_t *r = nullptr;
-    if (on_device) { // (the producer's kernels may still be writing the tensor on its own stream: find_on_device)
-        rc = acx_device_synchronize_on(acx_automaton_device(a));
-        if (rc == ACX_OK) rc = acx_summarize_device(a, hay, len, nullptr, 0, 0, overlapping, codepoints, what, &r);
-    } else {
-        rc = acx_summarize(a, hay, len, offsets, n_hay, overlapping, codepoints, what, &r);
-    }
+    int rc = on_device ? acx_summarize_device(a, hay, len, nullptr, 0, 0, overlapping, codepoints, what, &r)
+                       : acx_summarize(a, hay, len, offsets, n_hay, overlapping, codepoints, what, &r);
     if (rc == ACX_OK) {
         const uint64_t n = offsets ? n_hay : 1;
         out->total = acx_summary_total(r);
@@ -962,7 +777,6 @@ int summarize_nogil(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const 
         }
     }
     acx_free_summary(r);
-    Py_END_ALLOW_THREADS
     return rc;
 }
 
@@ -972,13 +786,7 @@ PyObject *first_to_object(const acx_match_t &m) {
 }
 
 PyObject *u64_list(const std::vector<uint64_t> &v) {
-    PyObject *list = PyList_New((Py_ssize_t)v.size());
-    for (size_t i = 0; list && i < v.size(); i++) {
-        PyObject *x = PyLong_FromUnsignedLongLong(v[i]);
-        if (!x) { Py_CLEAR(list); break; }
-        PyList_SET_ITEM(list, (Py_ssize_t)i, x);
-    }
-    return list;
+    return list_of(0, v.size(), [&](uint64_t i) { return PyLong_FromUnsignedLongLong(v[(size_t)i]); });
 }
 
 PyObject *summary_to_object(const Summary &s, int kind, bool batch, Py_ssize_t n) {
@@ -989,23 +797,20 @@ PyObject *summary_to_object(const Summary &s, int kind, bool batch, Py_ssize_t n
         return first_to_object(s.first[0]);
     }
     if (kind == SUM_COUNT) return u64_list(s.counts);
-    PyObject *list = PyList_New(n);
-    for (Py_ssize_t i = 0; list && i < n; i++) {
-        PyObject *x = kind == SUM_IS_MATCH ? PyBool_FromLong((long)((s.any[(size_t)i >> 6] >> (i & 63)) & 1))
-                                           : first_to_object(s.first[(size_t)i]);
-        if (!x) { Py_CLEAR(list); break; }
-        PyList_SET_ITEM(list, i, x);
-    }
-    return list;
+    return list_of(0, (uint64_t)n, [&](uint64_t i) {
+        return kind == SUM_IS_MATCH ? PyBool_FromLong((long)((s.any[(size_t)i >> 6] >> (i & 63)) & 1)) : first_to_object(s.first[(size_t)i]);
+    });
 }
 
 const char *const SUMMARY_FMT[2][4] = {{"O:is_match", "O:find_first", "O|O:count_matches", "O|O:count_by_pattern"},
                                        {"O:is_match_batch", "O:find_first_batch", "O|O:count_matches_batch",
                                         "O|O:count_by_pattern_batch"}};
 
-// every summary method of both classes: utf8 = the str class.  Code points are asked for only where offsets are returned
-// (find_first) and the text is not ASCII; find_first is always a non-overlapping search.
-PyObject *summary_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, int kind, bool batch, bool utf8) {
+// Every summary method: kind = SUM_IS_MATCH .. SUM_BY_PATTERN, batch: the *_batch form.  Code points are asked for only where
+// offsets are returned (find_first) and the text is not ASCII; find_first is always a non-overlapping search.
+template <int kind, bool batch> PyObject *summary(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
     // (is_match and find_first take no `overlapping`: the one does not depend on it, the other is the crate's find)
     const bool has_ov = kind == SUM_COUNT || kind == SUM_BY_PATTERN;
     const char *kw[] = {batch ? "haystacks" : "haystack", has_ov ? "overlapping" : nullptr, nullptr};
@@ -1020,34 +825,21 @@ PyObject *summary_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, int
         Packed in;
         if (!pack_sequence(hay, utf8, true, &in)) return nullptr;
         n = in.n;
-        rc = summarize_nogil(a, in.blob.data(), in.off[(size_t)n], in.off.data(), (uint64_t)n, false, overlapping,
+        rc = nogil([&] {
+            return summarize(a, in.blob.data(), in.off[(size_t)n], in.off.data(), (uint64_t)n, false, overlapping,
                              utf8 && !in.all_ascii && kind == SUM_FIND_FIRST, kind, true, &s);
-    } else if (utf8) {
-        const char *p; Py_ssize_t len;
-        if (!str_view(hay, &p, &len)) return nullptr;
-        rc = summarize_nogil(a, reinterpret_cast<const uint8_t *>(p), (uint64_t)len, nullptr, 0, false, overlapping,
-                             kind == SUM_FIND_FIRST && !PyUnicode_IS_ASCII(hay), kind, false, &s);
-    } else if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
-        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
-        PyObject *cap = dlpack_view(hay, acx_automaton_device(a), &p, &len, &on_device);
-        if (!cap) return nullptr;
-        rc = summarize_nogil(a, p, len, nullptr, 0, on_device, overlapping, 0, kind, false, &s); // (in HBM: reduced where it lies)
-        dlpack_release(cap);
+        });
     } else {
-        Py_buffer v;
-        if (!get_bytes_view(hay, &v)) return nullptr;
-        rc = summarize_nogil(a, (const uint8_t *)v.buf, (uint64_t)v.len, nullptr, 0, false, overlapping, 0, kind, false, &s);
-        PyBuffer_Release(&v);
+        HaystackView v;
+        if (!haystack_view(hay, utf8, true, acx_automaton_device(a), &v)) return nullptr;
+        const int codepoints = utf8 && !v.is_ascii && kind == SUM_FIND_FIRST;
+        rc = single_dispatch(
+            acx_automaton_device(a), v,
+            [&](const uint8_t *p, uint64_t len) { return summarize(a, p, len, nullptr, 0, false, overlapping, codepoints, kind, false, &s); },
+            [&](const uint8_t *p, uint64_t len) { return summarize(a, p, len, nullptr, 0, true, overlapping, 0, kind, false, &s); }); // (reduced where it lies)
     }
     if (rc != ACX_OK) return raise_acx(rc);
     return summary_to_object(s, kind, batch, n);
-}
-
-template <int K, bool BATCH> PyObject *ac_summary(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return summary_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, K, BATCH, true);
-}
-template <int K, bool BATCH> PyObject *bac_summary(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return summary_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, K, BATCH, false);
 }
 
 // ---------------------------------------------------------------------------
@@ -1055,27 +847,14 @@ template <int K, bool BATCH> PyObject *bac_summary(PyObject *self_, PyObject *ar
 // A MatchColumns owns the acx_columns_t; a Column is a view of one of its parts and keeps the MatchColumns alive; a DLPack
 // capsule -- and whatever tensor a consumer makes of it -- keeps the Column alive until the consumer calls its deleter.
 // ---------------------------------------------------------------------------
-PyTypeObject *MatchColumnsType = nullptr;
 PyTypeObject *ColumnType = nullptr;
-PyTypeObject *PatternCountsType = nullptr;
-PyTypeObject *FilteredRowsType = nullptr;
-PyTypeObject *RowScoresType = nullptr;
-PyTypeObject *MaskedRowsType = nullptr;
-PyTypeObject *RowOffsetsType = nullptr;
-PyTypeObject *MatchSpansType = nullptr;
-PyTypeObject *MatchSnippetsType = nullptr;
 
-// What a Column's owner -- a MatchColumns, a PatternCounts, a FilteredRows (`which`: ACX_COL_*, ACX_TALLY_*, ACX_FILT_*), a
-// RowScores or a RowOffsets (their one part), a MaskedRows (`which`: MR_*) or a MatchSpans (`which`: ACX_SPAN_*) -- begins with: the handle of the C ABI's result and the three calls a Column makes on it.
-struct OwnerOps {
-    int (*on_device)(const void *h);
-    const void *(*data)(const void *h, int which); // (waits for the device work)
-    void (*free)(void *h);
-};
+// What every result object -- the owner of a C ABI result and of the Columns made of its parts -- begins with.
+struct ResultType;
 struct OwnerObject {
     PyObject_HEAD
-    const OwnerOps *ops;
-    void *h;
+    const ResultType *rt;
+    void *h;    // the C ABI's result
     int device; // the automaton's ordinal (where device parts lie)
 };
 struct MatchColumnsObject : OwnerObject {
@@ -1101,48 +880,53 @@ struct MaskedRowsObject : OwnerObject {
     bool text;                 // mask_all_batch: the rows are the input's text; false: match_mask_batch, 0 / 1 bytes
     std::vector<uint8_t> *src; // a sequence of str with a non-ASCII one: its UTF-8 bytes, for tolist()'s entry per character
 };
-const OwnerOps MC_OPS = {[](const void *h) { return acx_columns_on_device(static_cast<const acx_columns_t *>(h)); },
-                         [](const void *h, int w) -> const void * { return acx_columns_data(static_cast<const acx_columns_t *>(h), w); },
-                         [](void *h) { acx_free_columns(static_cast<acx_columns_t *>(h)); }};
-const OwnerOps PC_OPS = {[](const void *h) { return acx_tally_on_device(static_cast<const acx_tally_t *>(h)); },
-                         [](const void *h, int w) -> const void * { return acx_tally_data(static_cast<const acx_tally_t *>(h), w); },
-                         [](void *h) { acx_free_tally(static_cast<acx_tally_t *>(h)); }};
-const OwnerOps FR_OPS = {[](const void *h) { return acx_filtered_on_device(static_cast<const acx_filtered_t *>(h)); },
-                         [](const void *h, int w) { return acx_filtered_data(static_cast<const acx_filtered_t *>(h), w); },
-                         [](void *h) { acx_free_filtered(static_cast<acx_filtered_t *>(h)); }};
-const OwnerOps RS_OPS = {[](const void *h) { return acx_scores_on_device(static_cast<const acx_scores_t *>(h)); },
-                         [](const void *h, int) -> const void * { return acx_scores_data(static_cast<const acx_scores_t *>(h)); },
-                         [](void *h) { acx_free_scores(static_cast<acx_scores_t *>(h)); }};
-const OwnerOps MR_OPS = {[](const void *h) { return acx_masked_on_device(static_cast<const acx_masked_t *>(h)); },
-                         [](const void *h, int w) -> const void * {
-                             return w == MR_OFFSETS ? static_cast<const void *>(acx_masked_offsets(static_cast<const acx_masked_t *>(h)))
-                                                    : acx_masked_data(static_cast<const acx_masked_t *>(h));
-                         },
-                         [](void *h) { acx_free_masked(static_cast<acx_masked_t *>(h)); }};
-const OwnerOps RO_OPS = {[](const void *h) { return acx_rows_on_device(static_cast<const acx_rows_t *>(h)); },
-                         [](const void *h, int) -> const void * { return acx_rows_offsets(static_cast<const acx_rows_t *>(h)); },
-                         [](void *h) { acx_free_rows(static_cast<acx_rows_t *>(h)); }};
-const OwnerOps MS_OPS = {[](const void *h) { return acx_spans_on_device(static_cast<const acx_spans_t *>(h)); },
-                         [](const void *h, int w) -> const void * { return acx_spans_data(static_cast<const acx_spans_t *>(h), w); },
-                         [](void *h) { acx_free_spans(static_cast<acx_spans_t *>(h)); }};
-const OwnerOps SN_OPS = {[](const void *h) { return acx_snippets_on_device(static_cast<const acx_snippets_t *>(h)); },
-                         [](const void *h, int w) -> const void * { return acx_snippets_data(static_cast<const acx_snippets_t *>(h), w); },
-                         [](void *h) { acx_free_snippets(static_cast<acx_snippets_t *>(h)); }};
-OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
-acx_snippets_t *sn_handle(PyObject *s) { return static_cast<acx_snippets_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
-acx_spans_t *ms_handle(PyObject *s) { return static_cast<acx_spans_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
-acx_rows_t *ro_handle(PyObject *s) { return static_cast<acx_rows_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
-acx_masked_t *mr_handle(PyObject *s) { return static_cast<acx_masked_t *>(reinterpret_cast<OwnerObject *>(s)->h); }
-acx_columns_t *mc_handle(PyObject *s) { return static_cast<acx_columns_t *>(owner_of(s)->h); }
-acx_tally_t *pc_handle(PyObject *s) { return static_cast<acx_tally_t *>(owner_of(s)->h); }
-acx_filtered_t *fr_handle(PyObject *s) { return static_cast<acx_filtered_t *>(owner_of(s)->h); }
-acx_scores_t *rs_handle(PyObject *s) { return static_cast<acx_scores_t *>(owner_of(s)->h); }
 
-// a new owner of `type` around the result h; frees h when the object cannot be made
-OwnerObject *new_owner(PyTypeObject *type, const OwnerOps *ops, void *h, int device) {
-    OwnerObject *o = reinterpret_cast<OwnerObject *>(type->tp_alloc(type, 0));
-    if (!o) { ops->free(h); return nullptr; }
-    o->ops = ops;
+// The three calls a Column makes on its owner's result, cast from the C ABI's typed ones (data: with or without `which`)
+struct OwnerOps {
+    int (*on_device)(const void *h);
+    const void *(*data)(const void *h, int which); // (waits for the device work)
+    void (*free)(void *h);
+};
+template <typename T, int (*OnDevice)(const T *), auto Data, void (*Free)(T *)> OwnerOps owner_ops() {
+    return {[](const void *h) { return OnDevice(static_cast<const T *>(h)); },
+            [](const void *h, int which) -> const void * {
+                (void)which;
+                if constexpr (std::is_invocable_v<decltype(Data), const T *, int>) return Data(static_cast<const T *>(h), which);
+                else return Data(static_cast<const T *>(h));
+            },
+            [](void *h) { Free(static_cast<T *>(h)); }};
+}
+
+// One row of RESULT_TYPES (behind the tolist methods below): all that tells one result type from another.
+constexpr uint64_t NO_PART = ~0ull;
+struct ResultType {
+    const char *name; // "ahocorasick_rs.<Name>"
+    int size;         // of the object
+    OwnerOps ops;
+    // the entries of part `which` (*elem = 1: uint8 bytes, else int64 words), or NO_PART: the attribute is None
+    uint64_t (*part_len)(const OwnerObject *o, int which, int *elem);
+    Py_ssize_t (*len)(PyObject *self);
+    PyObject *(*tolist)(PyObject *self, PyObject *);
+    const char *tolist_doc, *doc;
+    // the attributes; {name, nullptr, nullptr, doc, which}: a part, served as a Column by owner_get_part
+    std::vector<PyGetSetDef> getset;
+    void (*dealloc)(PyObject *self);
+    PyTypeObject *type; // made by PyInit
+    PyMethodDef methods[2];
+};
+enum { RT_MATCH_COLUMNS, RT_PATTERN_COUNTS, RT_FILTERED_ROWS, RT_ROW_SCORES, RT_MASKED_ROWS, RT_ROW_OFFSETS, RT_MATCH_SPANS, RT_MATCH_SNIPPETS, RT_COUNT };
+extern ResultType RESULT_TYPES[RT_COUNT];
+
+OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
+template <typename T> T *handle(PyObject *s) { return static_cast<T *>(owner_of(s)->h); }
+template <typename T> const T *handle(const OwnerObject *o) { return static_cast<const T *>(o->h); }
+
+// a new owner of type RESULT_TYPES[rt] around the result h; frees h when the object cannot be made
+OwnerObject *new_owner(int rt, void *h, int device) {
+    const ResultType &t = RESULT_TYPES[rt];
+    OwnerObject *o = reinterpret_cast<OwnerObject *>(t.type->tp_alloc(t.type, 0));
+    if (!o) { t.ops.free(h); return nullptr; }
+    o->rt = &t;
     o->h = h;
     o->device = device;
     return o;
@@ -1150,16 +934,17 @@ OwnerObject *new_owner(PyTypeObject *type, const OwnerOps *ops, void *h, int dev
 
 void owner_dealloc(PyObject *self) {
     OwnerObject *o = owner_of(self);
-    if (o->h) o->ops->free(o->h); // (waits for the device work if nobody has: microseconds to a millisecond)
+    if (o->h) o->rt->ops.free(o->h); // (waits for the device work if nobody has: microseconds to a millisecond)
     PyTypeObject *tp = Py_TYPE(self);
     tp->tp_free(self);
     Py_DECREF(tp);
 }
 
 PyObject *owner_get_device(PyObject *s, void *) {
-    if (!owner_of(s)->ops->on_device(owner_of(s)->h)) Py_RETURN_NONE;
+    if (!owner_of(s)->rt->ops.on_device(owner_of(s)->h)) Py_RETURN_NONE;
     return PyLong_FromLong(owner_of(s)->device);
 }
+
 
 struct ColumnObject {
     PyObject_HEAD
@@ -1188,93 +973,17 @@ void col_dealloc(PyObject *self) {
 }
 
 int col_device(ColumnObject *o) { return owner_of(o->owner)->device; }
-bool col_on_device(ColumnObject *o) { return owner_of(o->owner)->ops->on_device(owner_of(o->owner)->h) != 0; }
+bool col_on_device(ColumnObject *o) { return owner_of(o->owner)->rt->ops.on_device(owner_of(o->owner)->h) != 0; }
 
 // the part's address once the device work is done (GIL released around the wait); sets the exception
 const void *col_data(ColumnObject *o) {
     const void *p;
     Py_BEGIN_ALLOW_THREADS
-    p = owner_of(o->owner)->ops->data(owner_of(o->owner)->h, o->which);
+    p = owner_of(o->owner)->rt->ops.data(owner_of(o->owner)->h, o->which);
     Py_END_ALLOW_THREADS
     if (!p) PyErr_SetString(PyExc_RuntimeError, "the column's device work failed");
     return p;
 }
-
-PyObject *mc_column(PyObject *self, int which) {
-    if (which == ACX_COL_ROW_OFFSETS && !static_cast<MatchColumnsObject *>(owner_of(self))->batch) Py_RETURN_NONE;
-    return new_column(self, which, which == ACX_COL_ROW_OFFSETS ? acx_columns_rows(mc_handle(self)) + 1 : acx_columns_count(mc_handle(self)));
-}
-PyObject *mc_get_pattern(PyObject *s, void *) { return mc_column(s, ACX_COL_PATTERN); }
-PyObject *mc_get_start(PyObject *s, void *) { return mc_column(s, ACX_COL_START); }
-PyObject *mc_get_end(PyObject *s, void *) { return mc_column(s, ACX_COL_END); }
-PyObject *mc_get_row_offsets(PyObject *s, void *) { return mc_column(s, ACX_COL_ROW_OFFSETS); }
-Py_ssize_t mc_len(PyObject *s) { return (Py_ssize_t)acx_columns_count(mc_handle(s)); }
-
-// exactly what find_matches_as_indexes / _batch returns for the same arguments
-PyObject *mc_tolist(PyObject *self_, PyObject *) {
-    acx_columns_t *c = mc_handle(self_);
-    const bool batch = static_cast<MatchColumnsObject *>(owner_of(self_))->batch;
-    const uint64_t n = acx_columns_count(c), rows = acx_columns_rows(c);
-    std::vector<int64_t> col[3], ro;
-    int rc = ACX_OK;
-    Py_BEGIN_ALLOW_THREADS
-    for (int k = 0; k < 3 && rc == ACX_OK; k++) {
-        col[k].resize((size_t)n);
-        rc = acx_columns_copy(c, k, col[k].data());
-    }
-    if (rc == ACX_OK && batch) {
-        ro.resize((size_t)rows + 1);
-        rc = acx_columns_copy(c, ACX_COL_ROW_OFFSETS, ro.data());
-    }
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    auto rows_list = [&](uint64_t b, uint64_t e) -> PyObject * {
-        PyObject *list = PyList_New((Py_ssize_t)(e - b));
-        for (uint64_t i = b; list && i < e; i++) {
-            PyObject *t = Py_BuildValue("(KKK)", (unsigned long long)col[0][i], (unsigned long long)col[1][i],
-                                        (unsigned long long)col[2][i]);
-            if (!t) { Py_CLEAR(list); break; }
-            PyList_SET_ITEM(list, (Py_ssize_t)(i - b), t);
-        }
-        return list;
-    };
-    if (!batch) return rows_list(0, n);
-    PyObject *outer = PyList_New((Py_ssize_t)rows);
-    for (uint64_t h = 0; outer && h < rows; h++) {
-        PyObject *inner = rows_list((uint64_t)ro[h], (uint64_t)ro[h + 1]);
-        if (!inner) { Py_CLEAR(outer); break; }
-        PyList_SET_ITEM(outer, (Py_ssize_t)h, inner);
-    }
-    return outer;
-}
-
-PyGetSetDef mc_getset[] = {
-    {"pattern", mc_get_pattern, nullptr, "Column: the pattern index of every match", nullptr},
-    {"start", mc_get_start, nullptr, "Column: where every match starts", nullptr},
-    {"end", mc_get_end, nullptr, "Column: where every match ends", nullptr},
-    {"row_offsets", mc_get_row_offsets, nullptr,
-     "None for one haystack; for a batch a Column of len(haystacks) + 1 entries: rows row_offsets[h] .. row_offsets[h + 1] "
-     "are haystack h's matches", nullptr},
-    {"device", owner_get_device, nullptr, "None: the columns are in host memory; otherwise the HIP ordinal they lie on", nullptr},
-    {nullptr, nullptr, nullptr, nullptr, nullptr},
-};
-PyMethodDef mc_methods[] = {
-    {"tolist", mc_tolist, METH_NOARGS,
-     "what find_matches_as_indexes / find_matches_as_indexes_batch returns for the same arguments (copies device columns "
-     "to the host)"},
-    {nullptr, nullptr, 0, nullptr},
-};
-PyType_Slot mc_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
-    {Py_tp_methods, mc_methods},
-    {Py_tp_getset, mc_getset},
-    {Py_sq_length, reinterpret_cast<void *>(mc_len)},
-    {Py_tp_doc, const_cast<char *>(
-        "The matches of find_matches_as_columns / _batch: .pattern, .start, .end (and .row_offsets for a batch) are Column "
-        "objects of len(self) int64 entries, where the search ran (.device).  Every accessor of a column waits for the "
-        "split kernel first.")},
-    {0, nullptr},
-};
 
 Py_ssize_t col_len(PyObject *s) { return (Py_ssize_t)reinterpret_cast<ColumnObject *>(s)->len; }
 
@@ -1386,15 +1095,301 @@ PyType_Slot col_slots[] = {
     {0, nullptr},
 };
 
-PyObject *columns_object(acx_columns_t *c, bool batch, int device) {
-    OwnerObject *o = new_owner(MatchColumnsType, &MC_OPS, c, device);
-    if (o) static_cast<MatchColumnsObject *>(o)->batch = batch;
-    return reinterpret_cast<PyObject *>(o);
+// ---------------------------------------------------------------------------
+// The result types: MatchColumns, PatternCounts, FilteredRows, RowScores, MaskedRows, RowOffsets, MatchSpans, MatchSnippets.
+// What tells one from another -- how long a part is, what tolist() gives, the attributes that are no parts -- and
+// RESULT_TYPES, the one list of it.  The methods that make them follow.
+// ---------------------------------------------------------------------------
+// every part of every result type: `which` is the PyGetSetDef's closure
+void *part(int which) { return reinterpret_cast<void *>(static_cast<intptr_t>(which)); }
+PyObject *owner_get_part(PyObject *s, void *which) {
+    int elem = 0;
+    const uint64_t len = owner_of(s)->rt->part_len(owner_of(s), (int)reinterpret_cast<intptr_t>(which), &elem);
+    if (len == NO_PART) Py_RETURN_NONE;
+    return new_column(s, (int)reinterpret_cast<intptr_t>(which), len, elem);
+}
+// a size of the result as len(self) / as an attribute
+template <typename T, uint64_t (*Size)(const T *)> Py_ssize_t size_len(PyObject *s) { return (Py_ssize_t)Size(handle<T>(s)); }
+template <typename T, uint64_t (*Size)(const T *)> PyObject *size_get(PyObject *s, void *) { return PyLong_FromUnsignedLongLong(Size(handle<T>(s))); }
+
+// tolist() of a result whose parts are int64 columns of n entries: the tuples (parts[0][i], parts[1][i], ..) as one list or,
+// ro_part >= 0, as one list per row (rows + 1 row offsets).  The copies run with the GIL released.
+template <typename T, int (*Copy)(const T *, int, int64_t *)>
+PyObject *tuples_tolist(PyObject *self, const std::vector<int> &parts, uint64_t n, int ro_part, uint64_t rows) {
+    const T *h = handle<T>(self);
+    std::vector<std::vector<int64_t>> col(parts.size(), std::vector<int64_t>((size_t)n));
+    std::vector<int64_t> ro(ro_part >= 0 ? (size_t)rows + 1 : 0);
+    const int rc = nogil([&] {
+        int rc = ACX_OK;
+        for (size_t k = 0; k < parts.size() && rc == ACX_OK; k++) rc = Copy(h, parts[k], col[k].data());
+        if (rc == ACX_OK && ro_part >= 0) rc = Copy(h, ro_part, ro.data());
+        return rc;
+    });
+    if (rc != ACX_OK) return raise_acx(rc);
+    return rows_of(ro_part >= 0 ? &ro : nullptr, n, [&](uint64_t i) {
+        PyObject *t = PyTuple_New((Py_ssize_t)col.size());
+        for (size_t k = 0; t && k < col.size(); k++) {
+            PyObject *x = PyLong_FromUnsignedLongLong((unsigned long long)col[k][(size_t)i]);
+            if (!x) { Py_CLEAR(t); break; }
+            PyTuple_SET_ITEM(t, (Py_ssize_t)k, x);
+        }
+        return t;
+    });
 }
 
-// find_matches_as_columns / _batch of both classes: utf8 = the str class (code-point offsets when the text is not ASCII).
-// The haystack arguments and their errors are find_matches_as_indexes' / _batch's.
-PyObject *columns_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool batch, bool utf8) {
+// MatchColumns: exactly what find_matches_as_indexes / _batch returns for the same arguments
+uint64_t mc_part_len(const OwnerObject *o, int which, int *) {
+    if (which != ACX_COL_ROW_OFFSETS) return acx_columns_count(handle<acx_columns_t>(o));
+    return static_cast<const MatchColumnsObject *>(o)->batch ? acx_columns_rows(handle<acx_columns_t>(o)) + 1 : NO_PART;
+}
+PyObject *mc_tolist(PyObject *self, PyObject *) {
+    const acx_columns_t *c = handle<acx_columns_t>(self);
+    return tuples_tolist<acx_columns_t, acx_columns_copy>(self, {ACX_COL_PATTERN, ACX_COL_START, ACX_COL_END}, acx_columns_count(c),
+                                                          static_cast<MatchColumnsObject *>(owner_of(self))->batch ? ACX_COL_ROW_OFFSETS : -1, acx_columns_rows(c));
+}
+
+// MatchSpans: list[tuple[int, int]], or one such list per row
+uint64_t ms_part_len(const OwnerObject *o, int which, int *) {
+    if (which != ACX_SPAN_ROW_OFFSETS) return acx_spans_count(handle<acx_spans_t>(o));
+    return static_cast<const MatchSpansObject *>(o)->batch ? acx_spans_rows(handle<acx_spans_t>(o)) + 1 : NO_PART;
+}
+PyObject *ms_tolist(PyObject *self, PyObject *) {
+    const acx_spans_t *c = handle<acx_spans_t>(self);
+    return tuples_tolist<acx_spans_t, acx_spans_copy>(self, {ACX_SPAN_START, ACX_SPAN_END}, acx_spans_count(c),
+                                                      static_cast<MatchSpansObject *>(owner_of(self))->batch ? ACX_SPAN_ROW_OFFSETS : -1, acx_spans_rows(c));
+}
+
+// PatternCounts: one list per haystack of (pattern, count), patterns ascending
+uint64_t pc_part_len(const OwnerObject *o, int which, int *) {
+    return which == ACX_TALLY_ROW_OFFSETS ? acx_tally_rows(handle<acx_tally_t>(o)) + 1 : acx_tally_nnz(handle<acx_tally_t>(o));
+}
+PyObject *pc_tolist(PyObject *self, PyObject *) {
+    const acx_tally_t *t = handle<acx_tally_t>(self);
+    return tuples_tolist<acx_tally_t, acx_tally_copy>(self, {ACX_TALLY_PATTERN, ACX_TALLY_COUNT}, acx_tally_nnz(t), ACX_TALLY_ROW_OFFSETS, acx_tally_rows(t));
+}
+PyObject *pc_get_shape(PyObject *s, void *) {
+    return Py_BuildValue("(KK)", (unsigned long long)acx_tally_rows(handle<acx_tally_t>(s)),
+                         (unsigned long long)static_cast<PatternCountsObject *>(owner_of(s))->n_patterns);
+}
+
+// FilteredRows: the kept rows, list[str] of the str class (UTF-8 decoded), list[bytes] of the bytes class
+uint64_t fr_part_len(const OwnerObject *o, int which, int *elem) {
+    *elem = which == ACX_FILT_DATA;
+    return which == ACX_FILT_DATA ? acx_filtered_bytes(handle<acx_filtered_t>(o)) : acx_filtered_rows(handle<acx_filtered_t>(o)) + (which == ACX_FILT_OFFSETS);
+}
+PyObject *fr_tolist(PyObject *self, PyObject *) {
+    const acx_filtered_t *f = handle<acx_filtered_t>(self);
+    const uint64_t k = acx_filtered_rows(f);
+    std::vector<int64_t> off((size_t)k + 1);
+    std::vector<uint8_t> data((size_t)acx_filtered_bytes(f) + 1);
+    const int rc = nogil([&] {
+        const int rc = acx_filtered_copy(f, ACX_FILT_OFFSETS, off.data());
+        return rc == ACX_OK ? acx_filtered_copy(f, ACX_FILT_DATA, data.data()) : rc;
+    });
+    if (rc != ACX_OK) return raise_acx(rc);
+    const bool utf8 = static_cast<FilteredRowsObject *>(owner_of(self))->utf8;
+    return list_of(0, k, [&](uint64_t i) { return cut_item(data, off, i, utf8); });
+}
+PyObject *fr_get_source_rows(PyObject *s, void *) {
+    return PyLong_FromUnsignedLongLong(static_cast<FilteredRowsObject *>(owner_of(s))->n_src);
+}
+
+// MatchSnippets: list[str] of the str class (UTF-8 decoded), list[bytes] of the bytes class; a batch: one such list per row
+uint64_t sn_part_len(const OwnerObject *o, int which, int *elem) {
+    const acx_snippets_t *c = handle<acx_snippets_t>(o);
+    *elem = which == ACX_SNIP_DATA;
+    if (which == ACX_SNIP_DATA) return acx_snippets_nbytes(c);
+    if (which != ACX_SNIP_ROW_OFFSETS) return acx_snippets_count(c) + (which == ACX_SNIP_OFFSETS);
+    return static_cast<const MatchSnippetsObject *>(o)->batch ? acx_snippets_rows(c) + 1 : NO_PART;
+}
+PyObject *sn_tolist(PyObject *self, PyObject *) {
+    const acx_snippets_t *c = handle<acx_snippets_t>(self);
+    const MatchSnippetsObject *o = static_cast<MatchSnippetsObject *>(owner_of(self));
+    const uint64_t n = acx_snippets_count(c);
+    std::vector<int64_t> off((size_t)n + 1), ro(o->batch ? (size_t)acx_snippets_rows(c) + 1 : 0);
+    std::vector<uint8_t> data((size_t)acx_snippets_nbytes(c) + 1);
+    const int rc = nogil([&] {
+        int rc = acx_snippets_copy(c, ACX_SNIP_OFFSETS, off.data());
+        if (rc == ACX_OK) rc = acx_snippets_copy(c, ACX_SNIP_DATA, data.data());
+        if (rc == ACX_OK && o->batch) rc = acx_snippets_copy(c, ACX_SNIP_ROW_OFFSETS, ro.data());
+        return rc;
+    });
+    if (rc != ACX_OK) return raise_acx(rc);
+    return rows_of(o->batch ? &ro : nullptr, n, [&](uint64_t i) { return cut_item(data, off, i, o->utf8); });
+}
+
+// MaskedRows: list[str] for mask_all_batch of the str class (a sequence of str: one entry per character), else list[bytes]
+const void *masked_part(const acx_masked_t *m, int which) {
+    return which == MR_OFFSETS ? static_cast<const void *>(acx_masked_offsets(m)) : acx_masked_data(m);
+}
+uint64_t mr_part_len(const OwnerObject *o, int which, int *elem) {
+    *elem = which == MR_DATA;
+    return which == MR_DATA ? acx_masked_bytes(handle<acx_masked_t>(o)) : acx_masked_rows(handle<acx_masked_t>(o)) + 1;
+}
+PyObject *mr_tolist(PyObject *self, PyObject *) {
+    const acx_masked_t *m = handle<acx_masked_t>(self);
+    const MaskedRowsObject *o = static_cast<MaskedRowsObject *>(owner_of(self));
+    const uint64_t k = acx_masked_rows(m);
+    std::vector<int64_t> off((size_t)k + 1);
+    std::vector<uint8_t> data((size_t)acx_masked_bytes(m) + 1);
+    const int rc = nogil([&] {
+        const int rc = acx_masked_copy_offsets(m, off.data());
+        return rc == ACX_OK ? acx_masked_copy(m, data.data()) : rc;
+    });
+    if (rc != ACX_OK) return raise_acx(rc);
+    return list_of(0, k, [&](uint64_t i) {
+        if (!o->src) return cut_item(data, off, i, o->utf8 && o->text);
+        return per_character(o->src->data() + off[(size_t)i], data.data() + off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i]), o->text);
+    });
+}
+void mr_dealloc(PyObject *self) {
+    delete static_cast<MaskedRowsObject *>(owner_of(self))->src;
+    owner_dealloc(self);
+}
+
+// RowScores and RowOffsets: their one part as list[int]
+uint64_t rs_part_len(const OwnerObject *o, int, int *) { return acx_scores_rows(handle<acx_scores_t>(o)); }
+uint64_t ro_part_len(const OwnerObject *o, int, int *) { return acx_rows_count(handle<acx_rows_t>(o)) + 1; }
+template <typename T, int (*Copy)(const T *, int64_t *)> PyObject *words_tolist(PyObject *self, PyObject *) {
+    int elem = 0;
+    const uint64_t n = owner_of(self)->rt->part_len(owner_of(self), 0, &elem);
+    std::vector<int64_t> v((size_t)n + 1);
+    const int rc = nogil([&] { return Copy(handle<T>(self), v.data()); });
+    if (rc != ACX_OK) return raise_acx(rc);
+    return list_of(0, n, [&](uint64_t i) { return PyLong_FromLongLong((long long)v[(size_t)i]); });
+}
+
+#define DEVICE_ATTR(what) {"device", owner_get_device, nullptr, "None: the " what " in host memory; otherwise the HIP ordinal they lie on", nullptr}
+ResultType RESULT_TYPES[RT_COUNT] = {
+    {"ahocorasick_rs.MatchColumns", sizeof(MatchColumnsObject), owner_ops<acx_columns_t, acx_columns_on_device, acx_columns_data, acx_free_columns>(),
+     mc_part_len, size_len<acx_columns_t, acx_columns_count>, mc_tolist,
+     "what find_matches_as_indexes / find_matches_as_indexes_batch returns for the same arguments (copies device columns "
+     "to the host)",
+     "The matches of find_matches_as_columns / _batch: .pattern, .start, .end (and .row_offsets for a batch) are Column "
+     "objects of len(self) int64 entries, where the search ran (.device).  Every accessor of a column waits for the "
+     "split kernel first.",
+     {{"pattern", owner_get_part, nullptr, "Column: the pattern index of every match", part(ACX_COL_PATTERN)},
+      {"start", owner_get_part, nullptr, "Column: where every match starts", part(ACX_COL_START)},
+      {"end", owner_get_part, nullptr, "Column: where every match ends", part(ACX_COL_END)},
+      {"row_offsets", owner_get_part, nullptr,
+       "None for one haystack; for a batch a Column of len(haystacks) + 1 entries: rows row_offsets[h] .. row_offsets[h + 1] "
+       "are haystack h's matches", part(ACX_COL_ROW_OFFSETS)},
+      DEVICE_ATTR("columns are")}},
+    {"ahocorasick_rs.PatternCounts", sizeof(PatternCountsObject), owner_ops<acx_tally_t, acx_tally_on_device, acx_tally_data, acx_free_tally>(),
+     pc_part_len, size_len<acx_tally_t, acx_tally_nnz>, pc_tolist,
+     "one list per haystack of (pattern, count) tuples, patterns ascending (copies device parts to the host)",
+     "The result of count_by_pattern_sparse_batch: the CSR form of the haystacks x patterns matrix of match counts.  "
+     ".row_offsets, .pattern and .count are Column objects (int64) where the search ran (.device); len(self) is the "
+     "number of non-zero entries.  torch.sparse_csr_tensor(*map(torch.from_dlpack, (pc.row_offsets, pc.pattern, pc.count)), "
+     "size=pc.shape) is the matrix, without a copy.",
+     {{"row_offsets", owner_get_part, nullptr,
+       "Column of shape[0] + 1 entries from 0: entries row_offsets[h] .. row_offsets[h + 1] of pattern and count are haystack h's",
+       part(ACX_TALLY_ROW_OFFSETS)},
+      {"pattern", owner_get_part, nullptr, "Column of len(self) pattern indexes, strictly ascending within a row", part(ACX_TALLY_PATTERN)},
+      {"count", owner_get_part, nullptr, "Column of len(self) counts, all >= 1", part(ACX_TALLY_COUNT)},
+      {"shape", pc_get_shape, nullptr, "(haystacks, patterns): the size of the matrix", nullptr},
+      DEVICE_ATTR("parts are")}},
+    {"ahocorasick_rs.FilteredRows", sizeof(FilteredRowsObject), owner_ops<acx_filtered_t, acx_filtered_on_device, acx_filtered_data, acx_free_filtered>(),
+     fr_part_len, size_len<acx_filtered_t, acx_filtered_rows>, fr_tolist,
+     "the kept rows as list[str] (the str class: UTF-8 decoded) or list[bytes] (copies device parts to the host)",
+     "The result of filter_batch: the kept rows of a batch as a compacted batch.  .rows and .offsets are int64 Column "
+     "objects, .data a uint8 one, where the search ran (.device); len(self) is the number of kept rows, .nbytes the size "
+     "of .data, .source_rows the rows of the batch.  Kept row i is source row rows[i] = data[offsets[i]:offsets[i + 1]].",
+     {{"rows", owner_get_part, nullptr, "Column of len(self) int64 entries: the kept source row indexes, strictly ascending", part(ACX_FILT_ROWS)},
+      {"offsets", owner_get_part, nullptr, "Column of len(self) + 1 int64 entries from 0: kept row i is data[offsets[i]:offsets[i + 1]]",
+       part(ACX_FILT_OFFSETS)},
+      {"data", owner_get_part, nullptr, "Column of nbytes uint8 entries: the kept rows' own bytes back to back", part(ACX_FILT_DATA)},
+      DEVICE_ATTR("parts are"),
+      {"nbytes", size_get<acx_filtered_t, acx_filtered_bytes>, nullptr, "the size of data", nullptr},
+      {"source_rows", fr_get_source_rows, nullptr, "the rows of the batch that was filtered", nullptr}}},
+    {"ahocorasick_rs.RowScores", sizeof(OwnerObject), owner_ops<acx_scores_t, acx_scores_on_device, acx_scores_data, acx_free_scores>(),
+     rs_part_len, size_len<acx_scores_t, acx_scores_rows>, words_tolist<acx_scores_t, acx_scores_copy>,
+     "the scores as list[int] (copies device scores to the host)",
+     "The result of score_batch: .score is an int64 Column of len(self) entries, one per row of the batch, where the "
+     "search ran (.device).",
+     {{"score", owner_get_part, nullptr, "Column of len(self) int64 entries: every row's score", nullptr},
+      DEVICE_ATTR("scores are")}},
+    {"ahocorasick_rs.MaskedRows", sizeof(MaskedRowsObject), owner_ops<acx_masked_t, acx_masked_on_device, masked_part, acx_free_masked>(),
+     mr_part_len, size_len<acx_masked_t, acx_masked_rows>, mr_tolist,
+     "the rows as list[str] (mask_all_batch of the str class) or list[bytes] (copies device parts to the host); for a sequence "
+     "of str one entry per character",
+     "The result of mask_all_batch / match_mask_batch: .data is a uint8 Column of nbytes entries in the input's own layout "
+     "-- fill (or 1) where a match covers a byte -- and .offsets an int64 Column of len(self) + 1 entries from 0, where the "
+     "search ran (.device); len(self) is the number of rows.  For a tensor input the caller's own offsets cut .data as well.",
+     {{"data", owner_get_part, nullptr, "Column of nbytes uint8 entries: the rows back to back, in the input's own layout", part(MR_DATA)},
+      {"offsets", owner_get_part, nullptr, "Column of len(self) + 1 int64 entries from 0: row i is data[offsets[i]:offsets[i + 1]]", part(MR_OFFSETS)},
+      DEVICE_ATTR("parts are"),
+      {"nbytes", size_get<acx_masked_t, acx_masked_bytes>, nullptr, "the size of data: the input's", nullptr}},
+     mr_dealloc},
+    {"ahocorasick_rs.RowOffsets", sizeof(OwnerObject), owner_ops<acx_rows_t, acx_rows_on_device, acx_rows_offsets, acx_free_rows>(),
+     ro_part_len, size_len<acx_rows_t, acx_rows_count>, words_tolist<acx_rows_t, acx_rows_copy>,
+     "the offsets as list[int] (copies device offsets to the host)",
+     "The result of split_rows: .offsets is an int64 Column of len(self) + 1 entries that rise strictly from 0 to .nbytes, "
+     "where the data lies (.device); len(self) is the number of rows.  Pass .offsets as offsets= to the _batch methods.",
+     {{"offsets", owner_get_part, nullptr, "Column of len(self) + 1 int64 entries from 0 to nbytes: row i is data[offsets[i]:offsets[i + 1]]", nullptr},
+      DEVICE_ATTR("offsets are"),
+      {"nbytes", size_get<acx_rows_t, acx_rows_bytes>, nullptr, "the length of the data that was cut", nullptr}}},
+    {"ahocorasick_rs.MatchSpans", sizeof(MatchSpansObject), owner_ops<acx_spans_t, acx_spans_on_device, acx_spans_data, acx_free_spans>(),
+     ms_part_len, size_len<acx_spans_t, acx_spans_count>, ms_tolist,
+     "the spans as list[tuple[int, int]] of (start, end), or one such list per row of a batch (copies device columns to the "
+     "host)",
+     "The merged spans of cover_spans / cover_spans_batch: .start and .end (and .row_offsets for a batch) are Column "
+     "objects of len(self) int64 entries, where the search ran (.device).  Every accessor of a column waits for the "
+     "stage's last kernel first.",
+     {{"start", owner_get_part, nullptr, "Column: where every span starts", part(ACX_SPAN_START)},
+      {"end", owner_get_part, nullptr, "Column: where every span ends", part(ACX_SPAN_END)},
+      {"row_offsets", owner_get_part, nullptr,
+       "None for one haystack; for a batch a Column of len(haystacks) + 1 entries: spans row_offsets[h] .. row_offsets[h + 1] "
+       "are haystack h's", part(ACX_SPAN_ROW_OFFSETS)},
+      DEVICE_ATTR("columns are")}},
+    {"ahocorasick_rs.MatchSnippets", sizeof(MatchSnippetsObject), owner_ops<acx_snippets_t, acx_snippets_on_device, acx_snippets_data, acx_free_snippets>(),
+     sn_part_len, size_len<acx_snippets_t, acx_snippets_count>, sn_tolist,
+     "the snippets as list[str] (the str class: UTF-8 decoded) or list[bytes], or one such list per row of a batch (copies "
+     "device parts to the host)",
+     "The result of find_matches_as_snippets / find_matches_as_snippets_batch: one snippet per match.  .data is a uint8 "
+     "Column of nbytes entries, .offsets, .pattern and .lead (and .row_offsets for a batch) are int64 Column objects, where "
+     "the search ran (.device); len(self) is the number of snippets.  Every accessor of a part waits for the stage's last "
+     "kernel first.",
+     {{"data", owner_get_part, nullptr, "Column of nbytes uint8 entries: the snippets back to back", part(ACX_SNIP_DATA)},
+      {"offsets", owner_get_part, nullptr, "Column of len(self) + 1 int64 entries from 0: snippet i is data[offsets[i]:offsets[i + 1]]",
+       part(ACX_SNIP_OFFSETS)},
+      {"pattern", owner_get_part, nullptr, "Column of len(self) int64 entries: the pattern of every match", part(ACX_SNIP_PATTERN)},
+      {"lead", owner_get_part, nullptr,
+       "Column of len(self) int64 entries: the bytes of snippet i that stand before the match, which begins at "
+       "data[offsets[i] + lead[i]]", part(ACX_SNIP_LEAD)},
+      {"row_offsets", owner_get_part, nullptr,
+       "None for one haystack; for a batch a Column of len(haystacks) + 1 entries: snippets row_offsets[h] .. row_offsets[h + 1] "
+       "are haystack h's", part(ACX_SNIP_ROW_OFFSETS)},
+      DEVICE_ATTR("parts are"),
+      {"nbytes", size_get<acx_snippets_t, acx_snippets_nbytes>, nullptr, "the size of data", nullptr}}},
+};
+#undef DEVICE_ATTR
+
+// one result type of the table as a Python type in the module; false with the exception set
+bool register_result_type(PyObject *module, ResultType *t) {
+    t->getset.push_back({nullptr, nullptr, nullptr, nullptr, nullptr});
+    t->methods[0] = {"tolist", t->tolist, METH_NOARGS, t->tolist_doc};
+    t->methods[1] = {nullptr, nullptr, 0, nullptr};
+    PyType_Slot slots[] = {
+        {Py_tp_dealloc, reinterpret_cast<void *>(t->dealloc ? t->dealloc : owner_dealloc)},
+        {Py_tp_methods, t->methods},
+        {Py_tp_getset, t->getset.data()},
+        {Py_sq_length, reinterpret_cast<void *>(t->len)},
+        {Py_tp_doc, const_cast<char *>(t->doc)},
+        {0, nullptr},
+    };
+    PyType_Spec spec = {t->name, t->size, 0, Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, slots};
+    t->type = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&spec));
+    if (!t->type) return false;
+    Py_INCREF(t->type); // (the module holds one reference, the table the other)
+    return PyModule_AddObject(module, strchr(t->name, '.') + 1, reinterpret_cast<PyObject *>(t->type)) == 0;
+}
+
+// find_matches_as_columns / _batch (code-point offsets when the str class's text is not ASCII).  The haystack arguments and
+// their errors are find_matches_as_indexes' / _batch's.
+template <bool batch> PyObject *columns(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
     const char *kw[] = {batch ? "haystacks" : "haystack", "overlapping", nullptr};
     PyObject *hay = nullptr, *ov = nullptr;
     int overlapping = 0;
@@ -1402,122 +1397,33 @@ PyObject *columns_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, boo
                                      const_cast<char **>(kw), &hay, &ov))
         return nullptr;
     if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    const int device = acx_automaton_device(a);
     acx_columns_t *c = nullptr;
     int rc;
-    auto host = [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t n, int codepoints) {
-        Py_BEGIN_ALLOW_THREADS
-        rc = acx_find_columns(a, p, len, off, n, overlapping, codepoints, &c);
-        Py_END_ALLOW_THREADS
-    };
     if (batch) {
         Packed in;
         if (!pack_sequence(hay, utf8, false, &in)) return nullptr;
-        host(in.blob.data(), in.off[(size_t)in.n], in.off.data(), (uint64_t)in.n, (utf8 && !in.all_ascii) ? 1 : 0);
-    } else if (utf8) {
-        const char *p; Py_ssize_t len;
-        if (!str_view(hay, &p, &len)) return nullptr;
-        host(reinterpret_cast<const uint8_t *>(p), (uint64_t)len, nullptr, 0, PyUnicode_IS_ASCII(hay) ? 0 : 1);
-    } else if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
-        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
-        PyObject *cap = dlpack_view(hay, acx_automaton_device(a), &p, &len, &on_device);
-        if (!cap) return nullptr;
-        if (on_device) { // searched and split where it lies
-            Py_BEGIN_ALLOW_THREADS
-            rc = acx_device_synchronize_on(acx_automaton_device(a)); // (the producer's kernels may still write it)
-            if (rc == ACX_OK) rc = acx_find_columns_device(a, p, len, nullptr, 0, 0, overlapping, 0, &c);
-            Py_END_ALLOW_THREADS
-        } else {
-            host(p, len, nullptr, 0, 0);
-        }
-        dlpack_release(cap);
+        rc = nogil([&] {
+            return acx_find_columns(a, in.blob.data(), in.off[(size_t)in.n], in.off.data(), (uint64_t)in.n, overlapping, utf8 && !in.all_ascii, &c);
+        });
     } else {
-        Py_buffer v;
-        if (!get_bytes_view(hay, &v)) return nullptr;
-        host((const uint8_t *)v.buf, (uint64_t)v.len, nullptr, 0, 0);
-        PyBuffer_Release(&v);
+        HaystackView v;
+        if (!haystack_view(hay, utf8, true, device, &v)) return nullptr;
+        rc = single_dispatch(
+            device, v,
+            [&](const uint8_t *p, uint64_t len) { return acx_find_columns(a, p, len, nullptr, 0, overlapping, utf8 && !v.is_ascii, &c); },
+            [&](const uint8_t *p, uint64_t len) { return acx_find_columns_device(a, p, len, nullptr, 0, 0, overlapping, 0, &c); }); // (split where it lies)
     }
     if (rc != ACX_OK) return raise_acx(rc);
-    return columns_object(c, batch, acx_automaton_device(a));
-}
-
-template <bool BATCH> PyObject *ac_columns(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return columns_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, BATCH, true);
-}
-template <bool BATCH> PyObject *bac_columns(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return columns_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, BATCH, false);
+    OwnerObject *o = new_owner(RT_MATCH_COLUMNS, c, device);
+    if (o) static_cast<MatchColumnsObject *>(o)->batch = batch;
+    return reinterpret_cast<PyObject *>(o);
 }
 
 // ---------------------------------------------------------------------------
 // per-haystack pattern counts: count_by_pattern_sparse_batch -> PatternCounts (acx_tally / acx_tally_device).  A
 // PatternCounts owns the acx_tally_t; its three parts are Columns with the lifetime chain of a MatchColumns' columns.
 // ---------------------------------------------------------------------------
-PyObject *pc_column(PyObject *self, int which) {
-    return new_column(self, which, which == ACX_TALLY_ROW_OFFSETS ? acx_tally_rows(pc_handle(self)) + 1 : acx_tally_nnz(pc_handle(self)));
-}
-PyObject *pc_get_row_offsets(PyObject *s, void *) { return pc_column(s, ACX_TALLY_ROW_OFFSETS); }
-PyObject *pc_get_pattern(PyObject *s, void *) { return pc_column(s, ACX_TALLY_PATTERN); }
-PyObject *pc_get_count(PyObject *s, void *) { return pc_column(s, ACX_TALLY_COUNT); }
-PyObject *pc_get_shape(PyObject *s, void *) {
-    return Py_BuildValue("(KK)", (unsigned long long)acx_tally_rows(pc_handle(s)),
-                         (unsigned long long)static_cast<PatternCountsObject *>(owner_of(s))->n_patterns);
-}
-Py_ssize_t pc_len(PyObject *s) { return (Py_ssize_t)acx_tally_nnz(pc_handle(s)); }
-
-// one list per haystack of (pattern, count), patterns ascending
-PyObject *pc_tolist(PyObject *self_, PyObject *) {
-    acx_tally_t *t = pc_handle(self_);
-    const uint64_t nnz = acx_tally_nnz(t), rows = acx_tally_rows(t);
-    std::vector<int64_t> ro((size_t)rows + 1), pat((size_t)nnz), cnt((size_t)nnz);
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = acx_tally_copy(t, ACX_TALLY_ROW_OFFSETS, ro.data());
-    if (rc == ACX_OK) rc = acx_tally_copy(t, ACX_TALLY_PATTERN, pat.data());
-    if (rc == ACX_OK) rc = acx_tally_copy(t, ACX_TALLY_COUNT, cnt.data());
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    PyObject *outer = PyList_New((Py_ssize_t)rows);
-    for (uint64_t h = 0; outer && h < rows; h++) {
-        const uint64_t b = (uint64_t)ro[h], e = (uint64_t)ro[h + 1];
-        PyObject *inner = PyList_New((Py_ssize_t)(e - b));
-        for (uint64_t i = b; inner && i < e; i++) {
-            PyObject *t = Py_BuildValue("(KK)", (unsigned long long)pat[i], (unsigned long long)cnt[i]);
-            if (!t) { Py_CLEAR(inner); break; }
-            PyList_SET_ITEM(inner, (Py_ssize_t)(i - b), t);
-        }
-        if (!inner) { Py_CLEAR(outer); break; }
-        PyList_SET_ITEM(outer, (Py_ssize_t)h, inner);
-    }
-    return outer;
-}
-
-PyGetSetDef pc_getset[] = {
-    {"row_offsets", pc_get_row_offsets, nullptr,
-     "Column of shape[0] + 1 entries from 0: entries row_offsets[h] .. row_offsets[h + 1] of pattern and count are haystack h's",
-     nullptr},
-    {"pattern", pc_get_pattern, nullptr, "Column of len(self) pattern indexes, strictly ascending within a row", nullptr},
-    {"count", pc_get_count, nullptr, "Column of len(self) counts, all >= 1", nullptr},
-    {"shape", pc_get_shape, nullptr, "(haystacks, patterns): the size of the matrix", nullptr},
-    {"device", owner_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
-    {nullptr, nullptr, nullptr, nullptr, nullptr},
-};
-PyMethodDef pc_methods[] = {
-    {"tolist", pc_tolist, METH_NOARGS,
-     "one list per haystack of (pattern, count) tuples, patterns ascending (copies device parts to the host)"},
-    {nullptr, nullptr, 0, nullptr},
-};
-PyType_Slot pc_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
-    {Py_tp_methods, pc_methods},
-    {Py_tp_getset, pc_getset},
-    {Py_sq_length, reinterpret_cast<void *>(pc_len)},
-    {Py_tp_doc, const_cast<char *>(
-        "The result of count_by_pattern_sparse_batch: the CSR form of the haystacks x patterns matrix of match counts.  "
-        ".row_offsets, .pattern and .count are Column objects (int64) where the search ran (.device); len(self) is the "
-        "number of non-zero entries.  torch.sparse_csr_tensor(*map(torch.from_dlpack, (pc.row_offsets, pc.pattern, pc.count)), "
-        "size=pc.shape) is the matrix, without a copy.")},
-    {0, nullptr},
-};
-
 // The haystacks of a _batch method: a sequence of str (utf8) / buffers packed into one blob with its offsets, or one 1-D
 // uint8 __dlpack__ tensor that holds the rows back to back, cut by `offsets` (a 1-D int64 __dlpack__ tensor on the same
 // device) or by `row_length`.  Kept in one place so that the other _batch methods can take it.
@@ -1555,21 +1461,13 @@ bool batch_input(PyObject *hay, PyObject *offsets, PyObject *row_length, bool ut
     }
     in->cap = dlpack_view(hay, want_device, &in->p, &in->len, &in->on_device);
     if (!in->cap) return false;
-    {
-        const DLTensorC &t = static_cast<DLManagedTensorC *>(PyCapsule_GetPointer(in->cap, "dltensor"))->dl_tensor;
-        if (t.ndim != 1) {
-            PyErr_SetString(PyExc_TypeError, "Only one-dimensional sequences are supported");
-            return false;
-        }
+    if (capsule_tensor(in->cap).ndim != 1) {
+        PyErr_SetString(PyExc_TypeError, "Only one-dimensional sequences are supported");
+        return false;
     }
     if (row_length) {
-        if (!PyLong_Check(row_length) || PyBool_Check(row_length)) {
-            PyErr_Format(PyExc_TypeError, "argument 'row_length': '%.100s' object cannot be converted to 'PyInt'",
-                         Py_TYPE(row_length)->tp_name);
-            return false;
-        }
-        const long long rl = PyLong_AsLongLong(row_length);
-        if (rl == -1 && PyErr_Occurred()) return false;
+        long long rl;
+        if (!parse_int(row_length, "row_length", &rl)) return false;
         if (rl <= 0 || in->len % (uint64_t)rl) {
             PyErr_SetString(PyExc_ValueError, "row_length must be positive and divide the tensor's length");
             return false;
@@ -1655,8 +1553,10 @@ int batch_dispatch(int device_ordinal, const BatchInput &in, Host &&host, Device
     return BAD_OFFSETS;
 }
 
-// count_by_pattern_sparse_batch of both classes: utf8 = the str class (no offset is reported: the search is on bytes)
-PyObject *sparse_counts_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool utf8) {
+// count_by_pattern_sparse_batch (no offset is reported: the str class's search is on bytes too)
+PyObject *sparse_counts(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
     static const char *kw[] = {"haystacks", "overlapping", "offsets", "row_length", nullptr};
     PyObject *hay = nullptr, *ov = nullptr, *offsets = nullptr, *row_length = nullptr;
     int overlapping = 0;
@@ -1678,16 +1578,9 @@ PyObject *sparse_counts_impl(acx_automaton_t *a, PyObject *args, PyObject *kwarg
         });
     if (rc == BAD_OFFSETS) return nullptr;
     if (rc != ACX_OK) return raise_acx(rc);
-    OwnerObject *o = new_owner(PatternCountsType, &PC_OPS, t, device);
+    OwnerObject *o = new_owner(RT_PATTERN_COUNTS, t, device);
     if (o) static_cast<PatternCountsObject *>(o)->n_patterns = info.n_patterns;
     return reinterpret_cast<PyObject *>(o);
-}
-
-PyObject *ac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return sparse_counts_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, true);
-}
-PyObject *bac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return sparse_counts_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false);
 }
 
 // ---------------------------------------------------------------------------
@@ -1695,71 +1588,6 @@ PyObject *bac_sparse_counts(PyObject *self_, PyObject *args, PyObject *kwargs) {
 // acx_filtered_t; its three parts are Columns (rows and offsets int64, data uint8) with the lifetime chain of a
 // MatchColumns' columns.
 // ---------------------------------------------------------------------------
-PyObject *fr_column(PyObject *self, int which) {
-    acx_filtered_t *f = fr_handle(self);
-    return new_column(self, which, which == ACX_FILT_DATA ? acx_filtered_bytes(f) : acx_filtered_rows(f) + (which == ACX_FILT_OFFSETS ? 1 : 0),
-                      which == ACX_FILT_DATA ? 1 : 0);
-}
-PyObject *fr_get_rows(PyObject *s, void *) { return fr_column(s, ACX_FILT_ROWS); }
-PyObject *fr_get_offsets(PyObject *s, void *) { return fr_column(s, ACX_FILT_OFFSETS); }
-PyObject *fr_get_data(PyObject *s, void *) { return fr_column(s, ACX_FILT_DATA); }
-PyObject *fr_get_nbytes(PyObject *s, void *) { return PyLong_FromUnsignedLongLong(acx_filtered_bytes(fr_handle(s))); }
-PyObject *fr_get_source_rows(PyObject *s, void *) {
-    return PyLong_FromUnsignedLongLong(static_cast<FilteredRowsObject *>(owner_of(s))->n_src);
-}
-Py_ssize_t fr_len(PyObject *s) { return (Py_ssize_t)acx_filtered_rows(fr_handle(s)); }
-
-// the kept rows: list[str] of the str class (UTF-8 decoded), list[bytes] of the bytes class
-PyObject *fr_tolist(PyObject *self_, PyObject *) {
-    acx_filtered_t *f = fr_handle(self_);
-    const bool utf8 = static_cast<FilteredRowsObject *>(owner_of(self_))->utf8;
-    const uint64_t k = acx_filtered_rows(f), nb = acx_filtered_bytes(f);
-    std::vector<int64_t> off((size_t)k + 1);
-    std::vector<uint8_t> data((size_t)nb + 1);
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = acx_filtered_copy(f, ACX_FILT_OFFSETS, off.data());
-    if (rc == ACX_OK) rc = acx_filtered_copy(f, ACX_FILT_DATA, data.data());
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    PyObject *list = PyList_New((Py_ssize_t)k);
-    for (uint64_t i = 0; list && i < k; i++) {
-        const char *b = reinterpret_cast<const char *>(data.data()) + off[(size_t)i];
-        const Py_ssize_t n = (Py_ssize_t)(off[(size_t)i + 1] - off[(size_t)i]);
-        PyObject *it = utf8 ? PyUnicode_DecodeUTF8(b, n, nullptr) : PyBytes_FromStringAndSize(b, n);
-        if (!it) { Py_CLEAR(list); break; }
-        PyList_SET_ITEM(list, (Py_ssize_t)i, it);
-    }
-    return list;
-}
-
-PyGetSetDef fr_getset[] = {
-    {"rows", fr_get_rows, nullptr, "Column of len(self) int64 entries: the kept source row indexes, strictly ascending", nullptr},
-    {"offsets", fr_get_offsets, nullptr, "Column of len(self) + 1 int64 entries from 0: kept row i is data[offsets[i]:offsets[i + 1]]",
-     nullptr},
-    {"data", fr_get_data, nullptr, "Column of nbytes uint8 entries: the kept rows' own bytes back to back", nullptr},
-    {"device", owner_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
-    {"nbytes", fr_get_nbytes, nullptr, "the size of data", nullptr},
-    {"source_rows", fr_get_source_rows, nullptr, "the rows of the batch that was filtered", nullptr},
-    {nullptr, nullptr, nullptr, nullptr, nullptr},
-};
-PyMethodDef fr_methods[] = {
-    {"tolist", fr_tolist, METH_NOARGS,
-     "the kept rows as list[str] (the str class: UTF-8 decoded) or list[bytes] (copies device parts to the host)"},
-    {nullptr, nullptr, 0, nullptr},
-};
-PyType_Slot fr_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
-    {Py_tp_methods, fr_methods},
-    {Py_tp_getset, fr_getset},
-    {Py_sq_length, reinterpret_cast<void *>(fr_len)},
-    {Py_tp_doc, const_cast<char *>(
-        "The result of filter_batch: the kept rows of a batch as a compacted batch.  .rows and .offsets are int64 Column "
-        "objects, .data a uint8 one, where the search ran (.device); len(self) is the number of kept rows, .nbytes the size "
-        "of .data, .source_rows the rows of the batch.  Kept row i is source row rows[i] = data[offsets[i]:offsets[i + 1]].")},
-    {0, nullptr},
-};
-
 // keep = 'unmatched' | 'matched' -> the acx_filter* flags; sets the exception
 bool parse_keep(PyObject *keep, uint32_t *flags) {
     if (!PyUnicode_Check(keep)) {
@@ -1774,8 +1602,20 @@ bool parse_keep(PyObject *keep, uint32_t *flags) {
     return true;
 }
 
-// filter_batch of both classes: utf8 = the str class (no offset into a row is reported: the search is on bytes)
-PyObject *filter_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool utf8) {
+// a new FilteredRows around f (filter_batch, filter_by_score_batch)
+PyObject *filtered_object(acx_filtered_t *f, int device, uint64_t n_src, bool utf8) {
+    OwnerObject *o = new_owner(RT_FILTERED_ROWS, f, device);
+    if (o) {
+        static_cast<FilteredRowsObject *>(o)->n_src = n_src;
+        static_cast<FilteredRowsObject *>(o)->utf8 = utf8;
+    }
+    return reinterpret_cast<PyObject *>(o);
+}
+
+// filter_batch (no offset into a row is reported: the str class's search is on bytes too)
+PyObject *filter_batch(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
     static const char *kw[] = {"haystacks", "overlapping", "keep", "min_matches", "offsets", "row_length", nullptr};
     PyObject *hay = nullptr, *ov = nullptr, *keep = nullptr, *mm = nullptr, *offsets = nullptr, *row_length = nullptr;
     int overlapping = 0;
@@ -1787,14 +1627,9 @@ PyObject *filter_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool
     if (keep && !parse_keep(keep, &flags)) return nullptr;
     unsigned long long min_matches = 1;
     if (mm) {
-        if (!PyLong_Check(mm) || PyBool_Check(mm)) {
-            PyErr_Format(PyExc_TypeError, "argument 'min_matches': '%.100s' object cannot be converted to 'PyInt'",
-                         Py_TYPE(mm)->tp_name);
-            return nullptr;
-        }
-        int overflow = 0;
-        const long long v = PyLong_AsLongLongAndOverflow(mm, &overflow);
-        if (v == -1 && !overflow && PyErr_Occurred()) return nullptr;
+        long long v;
+        int overflow;
+        if (!parse_int(mm, "min_matches", &v, &overflow)) return nullptr;
         if (overflow < 0 || (!overflow && v < 1)) {
             PyErr_SetString(PyExc_ValueError, "min_matches must be at least 1");
             return nullptr;
@@ -1815,19 +1650,7 @@ PyObject *filter_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool
         });
     if (rc == BAD_OFFSETS) return nullptr;
     if (rc != ACX_OK) return raise_acx(rc);
-    OwnerObject *o = new_owner(FilteredRowsType, &FR_OPS, f, device);
-    if (o) {
-        static_cast<FilteredRowsObject *>(o)->n_src = in.rows;
-        static_cast<FilteredRowsObject *>(o)->utf8 = utf8;
-    }
-    return reinterpret_cast<PyObject *>(o);
-}
-
-PyObject *ac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return filter_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, true);
-}
-PyObject *bac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return filter_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false);
+    return filtered_object(f, device, in.rows, utf8);
 }
 
 // ---------------------------------------------------------------------------
@@ -1835,52 +1658,6 @@ PyObject *bac_filter_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
 // (acx_filter_scored / acx_filter_scored_device).  A RowScores owns the acx_scores_t; .score is a Column with the lifetime
 // chain of a MatchColumns' columns.
 // ---------------------------------------------------------------------------
-// the first n words of v as list[int] (RowScores.tolist, RowOffsets.tolist)
-PyObject *i64_list(const std::vector<int64_t> &v, uint64_t n) {
-    PyObject *list = PyList_New((Py_ssize_t)n);
-    for (uint64_t i = 0; list && i < n; i++) {
-        PyObject *it = PyLong_FromLongLong((long long)v[(size_t)i]);
-        if (!it) { Py_CLEAR(list); break; }
-        PyList_SET_ITEM(list, (Py_ssize_t)i, it);
-    }
-    return list;
-}
-
-PyObject *rs_get_score(PyObject *s, void *) { return new_column(s, 0, acx_scores_rows(rs_handle(s))); }
-Py_ssize_t rs_len(PyObject *s) { return (Py_ssize_t)acx_scores_rows(rs_handle(s)); }
-
-PyObject *rs_tolist(PyObject *self_, PyObject *) {
-    acx_scores_t *h = rs_handle(self_);
-    const uint64_t rows = acx_scores_rows(h);
-    std::vector<int64_t> v((size_t)rows + 1);
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = acx_scores_copy(h, v.data());
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    return i64_list(v, rows);
-}
-
-PyGetSetDef rs_getset[] = {
-    {"score", rs_get_score, nullptr, "Column of len(self) int64 entries: every row's score", nullptr},
-    {"device", owner_get_device, nullptr, "None: the scores are in host memory; otherwise the HIP ordinal they lie on", nullptr},
-    {nullptr, nullptr, nullptr, nullptr, nullptr},
-};
-PyMethodDef rs_methods[] = {
-    {"tolist", rs_tolist, METH_NOARGS, "the scores as list[int] (copies device scores to the host)"},
-    {nullptr, nullptr, 0, nullptr},
-};
-PyType_Slot rs_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
-    {Py_tp_methods, rs_methods},
-    {Py_tp_getset, rs_getset},
-    {Py_sq_length, reinterpret_cast<void *>(rs_len)},
-    {Py_tp_doc, const_cast<char *>(
-        "The result of score_batch: .score is an int64 Column of len(self) entries, one per row of the batch, where the "
-        "search ran (.device).")},
-    {0, nullptr},
-};
-
 // weights: one int per pattern, |w| < 2^31 -- an int64 / int32 buffer or a sequence of ints; sets the exception
 bool parse_weights(PyObject *w, uint64_t n_patterns, std::vector<int32_t> *out) {
     std::vector<long long> wide;
@@ -1943,9 +1720,11 @@ bool parse_weights(PyObject *w, uint64_t n_patterns, std::vector<int32_t> *out) 
     return true;
 }
 
-// score_batch (filter = false) and filter_by_score_batch of both classes: utf8 = the str class (no offset into a row is
-// reported: the search is on bytes)
-PyObject *scored_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool utf8, bool filter) {
+// score_batch (filter = false) and filter_by_score_batch (no offset into a row is reported: the str class's search is on
+// bytes too)
+template <bool filter> PyObject *scored(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
     static const char *kw_s[] = {"haystacks", "weights", "overlapping", "offsets", "row_length", nullptr};
     static const char *kw_f[] = {"haystacks", "weights", "overlapping", "keep", "min_score", "offsets", "row_length", nullptr};
     PyObject *hay = nullptr, *wts = nullptr, *ov = nullptr, *keep = nullptr, *ms = nullptr, *offsets = nullptr, *row_length = nullptr;
@@ -1960,13 +1739,8 @@ PyObject *scored_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool
     if (keep && !parse_keep(keep, &flags)) return nullptr;
     long long min_score = 1;
     if (ms) {
-        if (!PyLong_Check(ms) || PyBool_Check(ms)) {
-            PyErr_Format(PyExc_TypeError, "argument 'min_score': '%.100s' object cannot be converted to 'PyInt'", Py_TYPE(ms)->tp_name);
-            return nullptr;
-        }
-        int overflow = 0;
-        min_score = PyLong_AsLongLongAndOverflow(ms, &overflow);
-        if (min_score == -1 && !overflow && PyErr_Occurred()) return nullptr;
+        int overflow;
+        if (!parse_int(ms, "min_score", &min_score, &overflow)) return nullptr;
         if (overflow) {
             PyErr_SetString(PyExc_ValueError, "min_score must fit an int64");
             return nullptr;
@@ -1994,26 +1768,8 @@ PyObject *scored_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool
         });
     if (rc == BAD_OFFSETS) return nullptr;
     if (rc != ACX_OK) return raise_acx(rc);
-    if (!filter) return reinterpret_cast<PyObject *>(new_owner(RowScoresType, &RS_OPS, s, device));
-    OwnerObject *o = new_owner(FilteredRowsType, &FR_OPS, f, device);
-    if (o) {
-        static_cast<FilteredRowsObject *>(o)->n_src = in.rows;
-        static_cast<FilteredRowsObject *>(o)->utf8 = utf8;
-    }
-    return reinterpret_cast<PyObject *>(o);
-}
-
-PyObject *ac_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return scored_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, true, false);
-}
-PyObject *bac_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return scored_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false, false);
-}
-PyObject *ac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return scored_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, true, true);
-}
-PyObject *bac_filter_by_score_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return scored_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false, true);
+    if (!filter) return reinterpret_cast<PyObject *>(new_owner(RT_ROW_SCORES, s, device));
+    return filtered_object(f, device, in.rows, utf8);
 }
 
 // ---------------------------------------------------------------------------
@@ -2038,9 +1794,9 @@ bool parse_fill(PyObject *fill, bool utf8, uint8_t *out, const char *name = "fil
         return true;
     }
     if (PyLong_Check(fill) && !PyBool_Check(fill)) {
-        int overflow = 0;
-        const long long v = PyLong_AsLongLongAndOverflow(fill, &overflow);
-        if (v == -1 && !overflow && PyErr_Occurred()) return false;
+        long long v;
+        int overflow;
+        if (!parse_int(fill, name, &v, &overflow)) return false;
         if (overflow || v < 0 || v > 255) {
             PyErr_Format(PyExc_ValueError, "%s must be in range(256)", name);
             return false;
@@ -2060,20 +1816,6 @@ bool parse_fill(PyObject *fill, bool utf8, uint8_t *out, const char *name = "fil
     PyBuffer_Release(&v);
     if (!one) PyErr_Format(PyExc_ValueError, "%s must be one byte", name);
     return one;
-}
-
-// One entry per CHARACTER of a str haystack.  row: what the library made of hay's UTF-8 bytes, one entry per byte.  text: the
-// entries of a covered character's continuation bytes are dropped (fill is ASCII, so a continuation byte that differs from
-// the haystack's is a covered one) and the rest is decoded; else (the 0 / 1 mask) the entry of every continuation byte is.
-PyObject *per_character(const uint8_t *hay, const uint8_t *row, size_t len, bool text) {
-    std::string s;
-    s.reserve(len);
-    for (size_t i = 0; i < len; i++) {
-        const bool cont = (hay[i] & 0xC0) == 0x80;
-        if (cont && (!text || row[i] != hay[i])) continue;
-        s.push_back((char)row[i]);
-    }
-    return text ? PyUnicode_DecodeUTF8(s.data(), (Py_ssize_t)s.size(), nullptr) : PyBytes_FromStringAndSize(s.data(), (Py_ssize_t)s.size());
 }
 
 // the two argument checks and the per-character rule without an automaton (the CPU tests; module functions)
@@ -2099,69 +1841,11 @@ PyObject *mod_mask_per_character(PyObject *, PyObject *args) {
     return out;
 }
 
-void mr_dealloc(PyObject *self) {
-    delete static_cast<MaskedRowsObject *>(owner_of(self))->src;
-    owner_dealloc(self);
-}
-PyObject *mr_get_data(PyObject *s, void *) { return new_column(s, MR_DATA, acx_masked_bytes(mr_handle(s)), 1); }
-PyObject *mr_get_offsets(PyObject *s, void *) { return new_column(s, MR_OFFSETS, acx_masked_rows(mr_handle(s)) + 1); }
-PyObject *mr_get_nbytes(PyObject *s, void *) { return PyLong_FromUnsignedLongLong(acx_masked_bytes(mr_handle(s))); }
-Py_ssize_t mr_len(PyObject *s) { return (Py_ssize_t)acx_masked_rows(mr_handle(s)); }
-
-// the rows: list[str] for mask_all_batch of the str class (a sequence of str: one entry per character), else list[bytes]
-PyObject *mr_tolist(PyObject *self_, PyObject *) {
-    acx_masked_t *m = mr_handle(self_);
-    const MaskedRowsObject *o = static_cast<MaskedRowsObject *>(owner_of(self_));
-    const uint64_t k = acx_masked_rows(m), nb = acx_masked_bytes(m);
-    std::vector<int64_t> off((size_t)k + 1);
-    std::vector<uint8_t> data((size_t)nb + 1);
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = acx_masked_copy_offsets(m, off.data());
-    if (rc == ACX_OK) rc = acx_masked_copy(m, data.data());
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    PyObject *list = PyList_New((Py_ssize_t)k);
-    for (uint64_t i = 0; list && i < k; i++) {
-        const uint8_t *b = data.data() + off[(size_t)i];
-        const Py_ssize_t n = (Py_ssize_t)(off[(size_t)i + 1] - off[(size_t)i]);
-        PyObject *it = o->src ? per_character(o->src->data() + off[(size_t)i], b, (size_t)n, o->text)
-                              : o->utf8 && o->text ? PyUnicode_DecodeUTF8(reinterpret_cast<const char *>(b), n, nullptr)
-                                                   : PyBytes_FromStringAndSize(reinterpret_cast<const char *>(b), n);
-        if (!it) { Py_CLEAR(list); break; }
-        PyList_SET_ITEM(list, (Py_ssize_t)i, it);
-    }
-    return list;
-}
-
-PyGetSetDef mr_getset[] = {
-    {"data", mr_get_data, nullptr, "Column of nbytes uint8 entries: the rows back to back, in the input's own layout", nullptr},
-    {"offsets", mr_get_offsets, nullptr, "Column of len(self) + 1 int64 entries from 0: row i is data[offsets[i]:offsets[i + 1]]", nullptr},
-    {"device", owner_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
-    {"nbytes", mr_get_nbytes, nullptr, "the size of data: the input's", nullptr},
-    {nullptr, nullptr, nullptr, nullptr, nullptr},
-};
-PyMethodDef mr_methods[] = {
-    {"tolist", mr_tolist, METH_NOARGS,
-     "the rows as list[str] (mask_all_batch of the str class) or list[bytes] (copies device parts to the host); for a sequence "
-     "of str one entry per character"},
-    {nullptr, nullptr, 0, nullptr},
-};
-PyType_Slot mr_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(mr_dealloc)},
-    {Py_tp_methods, mr_methods},
-    {Py_tp_getset, mr_getset},
-    {Py_sq_length, reinterpret_cast<void *>(mr_len)},
-    {Py_tp_doc, const_cast<char *>(
-        "The result of mask_all_batch / match_mask_batch: .data is a uint8 Column of nbytes entries in the input's own layout "
-        "-- fill (or 1) where a match covers a byte -- and .offsets an int64 Column of len(self) + 1 entries from 0, where the "
-        "search ran (.device); len(self) is the number of rows.  For a tensor input the caller's own offsets cut .data as well.")},
-    {0, nullptr},
-};
-
-// mask_all / match_mask / mask_all_batch / match_mask_batch of both classes: utf8 = the str class (no offset is reported:
-// the search is on bytes), text = the mask_all forms
-PyObject *mask_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool utf8, bool text, bool batch) {
+// mask_all / match_mask / mask_all_batch / match_mask_batch: text = the mask_all forms (the haystack with its matches
+// filled), else the 0 / 1 mask; batch: the *_batch form.  No offset is reported: the str class's search is on bytes too.
+template <bool text, bool batch> PyObject *mask(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
     static const char *kw_t[] = {"haystack", "fill", "overlapping", nullptr};
     static const char *kw_m[] = {"haystack", "overlapping", nullptr};
     static const char *kw_tb[] = {"haystacks", "fill", "overlapping", "offsets", "row_length", nullptr};
@@ -2182,24 +1866,18 @@ PyObject *mask_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool u
     acx_masked_t *m = nullptr;
     int rc;
     if (!batch) {
-        const char *p = nullptr;
-        Py_ssize_t len = 0;
-        Py_buffer v;
-        if (utf8 ? !str_view(hay, &p, &len) : !get_bytes_view(hay, &v)) return nullptr;
-        if (!utf8) { p = static_cast<const char *>(v.buf); len = v.len; }
-        Py_BEGIN_ALLOW_THREADS
-        rc = acx_mask(a, reinterpret_cast<const uint8_t *>(p), (uint64_t)len, nullptr, 1, overlapping, fill, flags, &m);
-        Py_END_ALLOW_THREADS
+        HaystackView v; // (a str or a buffer: these two take no tensor)
+        if (!haystack_view(hay, utf8, false, -1, &v)) return nullptr;
+        rc = nogil([&] { return acx_mask(a, v.p, v.len, nullptr, 1, overlapping, fill, flags, &m); });
         PyObject *out = nullptr;
         if (rc != ACX_OK) raise_acx(rc);
         else {
             const uint8_t *row = static_cast<const uint8_t *>(acx_masked_data(m)); // (a host result)
             out = !row ? raise_acx(ACX_EDEVICE)
-                  : utf8 ? per_character(reinterpret_cast<const uint8_t *>(p), row, (size_t)len, text)
-                         : PyBytes_FromStringAndSize(reinterpret_cast<const char *>(row), len);
+                  : utf8 ? per_character(v.p, row, (size_t)v.len, text)
+                         : PyBytes_FromStringAndSize(reinterpret_cast<const char *>(row), (Py_ssize_t)v.len);
         }
         acx_free_masked(m);
-        if (!utf8) PyBuffer_Release(&v);
         return out;
     }
     const int device = acx_automaton_device(a);
@@ -2220,7 +1898,7 @@ PyObject *mask_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool u
         src = new (std::nothrow) std::vector<uint8_t>(std::move(in.seq.blob));
         if (!src) { acx_free_masked(m); return PyErr_NoMemory(); }
     }
-    OwnerObject *o = new_owner(MaskedRowsType, &MR_OPS, m, device);
+    OwnerObject *o = new_owner(RT_MASKED_ROWS, m, device);
     if (!o) { delete src; return nullptr; }
     static_cast<MaskedRowsObject *>(o)->utf8 = utf8;
     static_cast<MaskedRowsObject *>(o)->text = text;
@@ -2228,116 +1906,18 @@ PyObject *mask_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool u
     return reinterpret_cast<PyObject *>(o);
 }
 
-template <bool TEXT, bool BATCH> PyObject *ac_mask(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return mask_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, true, TEXT, BATCH);
-}
-template <bool TEXT, bool BATCH> PyObject *bac_mask(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return mask_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, false, TEXT, BATCH);
-}
-
 // ---------------------------------------------------------------------------
 // the merged spans of a search's matches: cover_spans / cover_spans_batch -> MatchSpans (acx_spans / acx_spans_device).  A
 // MatchSpans owns the acx_spans_t; .start, .end and .row_offsets are Columns with the lifetime chain of a MatchColumns'
 // columns.
 // ---------------------------------------------------------------------------
-PyObject *ms_column(PyObject *self, int which) {
-    if (which == ACX_SPAN_ROW_OFFSETS && !static_cast<MatchSpansObject *>(owner_of(self))->batch) Py_RETURN_NONE;
-    return new_column(self, which, which == ACX_SPAN_ROW_OFFSETS ? acx_spans_rows(ms_handle(self)) + 1 : acx_spans_count(ms_handle(self)));
-}
-PyObject *ms_get_start(PyObject *s, void *) { return ms_column(s, ACX_SPAN_START); }
-PyObject *ms_get_end(PyObject *s, void *) { return ms_column(s, ACX_SPAN_END); }
-PyObject *ms_get_row_offsets(PyObject *s, void *) { return ms_column(s, ACX_SPAN_ROW_OFFSETS); }
-Py_ssize_t ms_len(PyObject *s) { return (Py_ssize_t)acx_spans_count(ms_handle(s)); }
+// the check of `gap` without an automaton (the CPU tests; a module function)
+PyObject *mod_spans_gap(PyObject *, PyObject *arg) { uint64_t g; return parse_u63(arg, "gap", &g) ? PyLong_FromUnsignedLongLong(g) : nullptr; }
 
-// list[tuple[int, int]], or one such list per row
-PyObject *ms_tolist(PyObject *self_, PyObject *) {
-    acx_spans_t *c = ms_handle(self_);
-    const bool batch = static_cast<MatchSpansObject *>(owner_of(self_))->batch;
-    const uint64_t n = acx_spans_count(c), rows = acx_spans_rows(c);
-    std::vector<int64_t> col[2], ro;
-    int rc = ACX_OK;
-    Py_BEGIN_ALLOW_THREADS
-    for (int k = 0; k < 2 && rc == ACX_OK; k++) {
-        col[k].resize((size_t)n);
-        rc = acx_spans_copy(c, k, col[k].data());
-    }
-    if (rc == ACX_OK && batch) {
-        ro.resize((size_t)rows + 1);
-        rc = acx_spans_copy(c, ACX_SPAN_ROW_OFFSETS, ro.data());
-    }
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    auto rows_list = [&](uint64_t b, uint64_t e) -> PyObject * {
-        PyObject *list = PyList_New((Py_ssize_t)(e - b));
-        for (uint64_t i = b; list && i < e; i++) {
-            PyObject *t = Py_BuildValue("(KK)", (unsigned long long)col[0][i], (unsigned long long)col[1][i]);
-            if (!t) { Py_CLEAR(list); break; }
-            PyList_SET_ITEM(list, (Py_ssize_t)(i - b), t);
-        }
-        return list;
-    };
-    if (!batch) return rows_list(0, n);
-    PyObject *outer = PyList_New((Py_ssize_t)rows);
-    for (uint64_t h = 0; outer && h < rows; h++) {
-        PyObject *inner = rows_list((uint64_t)ro[h], (uint64_t)ro[h + 1]);
-        if (!inner) { Py_CLEAR(outer); break; }
-        PyList_SET_ITEM(outer, (Py_ssize_t)h, inner);
-    }
-    return outer;
-}
-
-PyGetSetDef ms_getset[] = {
-    {"start", ms_get_start, nullptr, "Column: where every span starts", nullptr},
-    {"end", ms_get_end, nullptr, "Column: where every span ends", nullptr},
-    {"row_offsets", ms_get_row_offsets, nullptr,
-     "None for one haystack; for a batch a Column of len(haystacks) + 1 entries: spans row_offsets[h] .. row_offsets[h + 1] "
-     "are haystack h's", nullptr},
-    {"device", owner_get_device, nullptr, "None: the columns are in host memory; otherwise the HIP ordinal they lie on", nullptr},
-    {nullptr, nullptr, nullptr, nullptr, nullptr},
-};
-PyMethodDef ms_methods[] = {
-    {"tolist", ms_tolist, METH_NOARGS,
-     "the spans as list[tuple[int, int]] of (start, end), or one such list per row of a batch (copies device columns to the "
-     "host)"},
-    {nullptr, nullptr, 0, nullptr},
-};
-PyType_Slot ms_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
-    {Py_tp_methods, ms_methods},
-    {Py_tp_getset, ms_getset},
-    {Py_sq_length, reinterpret_cast<void *>(ms_len)},
-    {Py_tp_doc, const_cast<char *>(
-        "The merged spans of cover_spans / cover_spans_batch: .start and .end (and .row_offsets for a batch) are Column "
-        "objects of len(self) int64 entries, where the search ran (.device).  Every accessor of a column waits for the "
-        "stage's last kernel first.")},
-    {0, nullptr},
-};
-
-// gap: an int 0 .. 2^63 - 1; sets the exception
-bool parse_gap(PyObject *gap, uint64_t *out) {
-    if (!PyLong_Check(gap) || PyBool_Check(gap)) {
-        PyErr_Format(PyExc_TypeError, "argument 'gap': '%.100s' object cannot be converted to 'PyInt'", Py_TYPE(gap)->tp_name);
-        return false;
-    }
-    int overflow = 0;
-    const long long v = PyLong_AsLongLongAndOverflow(gap, &overflow);
-    if (v == -1 && !overflow && PyErr_Occurred()) return false;
-    if (overflow || v < 0) {
-        PyErr_SetString(PyExc_ValueError, "gap must be in range(2**63)");
-        return false;
-    }
-    *out = (uint64_t)v;
-    return true;
-}
-// the check without an automaton (the CPU tests; a module function)
-PyObject *mod_spans_gap(PyObject *, PyObject *arg) {
-    uint64_t g = 0;
-    if (!parse_gap(arg, &g)) return nullptr;
-    return PyLong_FromUnsignedLongLong(g);
-}
-
-// cover_spans / cover_spans_batch of both classes: utf8 = the str class (code-point offsets when the text is not ASCII)
-PyObject *spans_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool batch, bool utf8) {
+// cover_spans / cover_spans_batch (code-point offsets when the str class's text is not ASCII)
+template <bool batch> PyObject *spans(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
     static const char *kw_s[] = {"haystack", "overlapping", "gap", nullptr};
     static const char *kw_b[] = {"haystacks", "overlapping", "gap", "offsets", "row_length", nullptr};
     PyObject *hay = nullptr, *ov = nullptr, *gap_o = nullptr, *offsets = nullptr, *row_length = nullptr;
@@ -2348,15 +1928,10 @@ PyObject *spans_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool 
         return nullptr;
     if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
     uint64_t gap = 0;
-    if (gap_o && !parse_gap(gap_o, &gap)) return nullptr;
+    if (gap_o && !parse_u63(gap_o, "gap", &gap)) return nullptr;
     const int device = acx_automaton_device(a);
     acx_spans_t *c = nullptr;
     int rc;
-    auto host = [&](const uint8_t *p, uint64_t len, int codepoints) {
-        Py_BEGIN_ALLOW_THREADS
-        rc = acx_spans(a, p, len, nullptr, 0, overlapping, codepoints, gap, &c);
-        Py_END_ALLOW_THREADS
-    };
     if (batch) {
         BatchInput in;
         if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
@@ -2370,40 +1945,18 @@ PyObject *spans_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool 
                 return acx_spans_device(a, p, len, d_off, rows, row_len, overlapping, 0, gap, &c);
             });
         if (rc == BAD_OFFSETS) return nullptr;
-    } else if (utf8) {
-        const char *p; Py_ssize_t len;
-        if (!str_view(hay, &p, &len)) return nullptr;
-        host(reinterpret_cast<const uint8_t *>(p), (uint64_t)len, PyUnicode_IS_ASCII(hay) ? 0 : 1);
-    } else if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
-        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
-        PyObject *cap = dlpack_view(hay, device, &p, &len, &on_device);
-        if (!cap) return nullptr;
-        if (on_device) { // searched and merged where it lies
-            Py_BEGIN_ALLOW_THREADS
-            rc = acx_device_synchronize_on(device); // (the producer's kernels may still write it)
-            if (rc == ACX_OK) rc = acx_spans_device(a, p, len, nullptr, 0, 0, overlapping, 0, gap, &c);
-            Py_END_ALLOW_THREADS
-        } else {
-            host(p, len, 0);
-        }
-        dlpack_release(cap);
     } else {
-        Py_buffer v;
-        if (!get_bytes_view(hay, &v)) return nullptr;
-        host((const uint8_t *)v.buf, (uint64_t)v.len, 0);
-        PyBuffer_Release(&v);
+        HaystackView v;
+        if (!haystack_view(hay, utf8, true, device, &v)) return nullptr;
+        rc = single_dispatch(
+            device, v,
+            [&](const uint8_t *p, uint64_t len) { return acx_spans(a, p, len, nullptr, 0, overlapping, utf8 && !v.is_ascii, gap, &c); },
+            [&](const uint8_t *p, uint64_t len) { return acx_spans_device(a, p, len, nullptr, 0, 0, overlapping, 0, gap, &c); }); // (merged where it lies)
     }
     if (rc != ACX_OK) return raise_acx(rc);
-    OwnerObject *o = new_owner(MatchSpansType, &MS_OPS, c, device);
+    OwnerObject *o = new_owner(RT_MATCH_SPANS, c, device);
     if (o) static_cast<MatchSpansObject *>(o)->batch = batch;
     return reinterpret_cast<PyObject *>(o);
-}
-
-template <bool BATCH> PyObject *ac_spans(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return spans_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, BATCH, true);
-}
-template <bool BATCH> PyObject *bac_spans(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return spans_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, BATCH, false);
 }
 
 // ---------------------------------------------------------------------------
@@ -2411,119 +1964,14 @@ template <bool BATCH> PyObject *bac_spans(PyObject *self_, PyObject *args, PyObj
 // acx_snippets_device).  A MatchSnippets owns the acx_snippets_t; its parts are Columns (.data uint8, the others int64) with
 // the lifetime chain of a MatchColumns' columns.
 // ---------------------------------------------------------------------------
-PyObject *sn_column(PyObject *self, int which) {
-    acx_snippets_t *c = sn_handle(self);
-    if (which == ACX_SNIP_ROW_OFFSETS && !static_cast<MatchSnippetsObject *>(owner_of(self))->batch) Py_RETURN_NONE;
-    if (which == ACX_SNIP_DATA) return new_column(self, which, acx_snippets_nbytes(c), 1);
-    return new_column(self, which, which == ACX_SNIP_ROW_OFFSETS ? acx_snippets_rows(c) + 1 : acx_snippets_count(c) + (which == ACX_SNIP_OFFSETS ? 1 : 0));
-}
-PyObject *sn_get_data(PyObject *s, void *) { return sn_column(s, ACX_SNIP_DATA); }
-PyObject *sn_get_offsets(PyObject *s, void *) { return sn_column(s, ACX_SNIP_OFFSETS); }
-PyObject *sn_get_pattern(PyObject *s, void *) { return sn_column(s, ACX_SNIP_PATTERN); }
-PyObject *sn_get_lead(PyObject *s, void *) { return sn_column(s, ACX_SNIP_LEAD); }
-PyObject *sn_get_row_offsets(PyObject *s, void *) { return sn_column(s, ACX_SNIP_ROW_OFFSETS); }
-PyObject *sn_get_nbytes(PyObject *s, void *) { return PyLong_FromUnsignedLongLong(acx_snippets_nbytes(sn_handle(s))); }
-Py_ssize_t sn_len(PyObject *s) { return (Py_ssize_t)acx_snippets_count(sn_handle(s)); }
+// the check of `context` without an automaton (the CPU tests; a module function)
+PyObject *mod_snippets_context(PyObject *, PyObject *arg) { uint64_t c; return parse_u63(arg, "context", &c) ? PyLong_FromUnsignedLongLong(c) : nullptr; }
 
-// list[str] of the str class (UTF-8 decoded), list[bytes] of the bytes class; a batch: one such list per row
-PyObject *sn_tolist(PyObject *self_, PyObject *) {
-    acx_snippets_t *c = sn_handle(self_);
-    const MatchSnippetsObject *o = static_cast<MatchSnippetsObject *>(owner_of(self_));
-    const bool batch = o->batch, utf8 = o->utf8;
-    const uint64_t n = acx_snippets_count(c), rows = acx_snippets_rows(c), nb = acx_snippets_nbytes(c);
-    std::vector<int64_t> off((size_t)n + 1), ro;
-    std::vector<uint8_t> data((size_t)nb + 1);
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = acx_snippets_copy(c, ACX_SNIP_OFFSETS, off.data());
-    if (rc == ACX_OK) rc = acx_snippets_copy(c, ACX_SNIP_DATA, data.data());
-    if (rc == ACX_OK && batch) {
-        ro.resize((size_t)rows + 1);
-        rc = acx_snippets_copy(c, ACX_SNIP_ROW_OFFSETS, ro.data());
-    }
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    auto rows_list = [&](uint64_t b, uint64_t e) -> PyObject * {
-        PyObject *list = PyList_New((Py_ssize_t)(e - b));
-        for (uint64_t i = b; list && i < e; i++) {
-            const char *p = reinterpret_cast<const char *>(data.data()) + off[(size_t)i];
-            const Py_ssize_t k = (Py_ssize_t)(off[(size_t)i + 1] - off[(size_t)i]);
-            PyObject *it = utf8 ? PyUnicode_DecodeUTF8(p, k, nullptr) : PyBytes_FromStringAndSize(p, k);
-            if (!it) { Py_CLEAR(list); break; }
-            PyList_SET_ITEM(list, (Py_ssize_t)(i - b), it);
-        }
-        return list;
-    };
-    if (!batch) return rows_list(0, n);
-    PyObject *outer = PyList_New((Py_ssize_t)rows);
-    for (uint64_t h = 0; outer && h < rows; h++) {
-        PyObject *inner = rows_list((uint64_t)ro[h], (uint64_t)ro[h + 1]);
-        if (!inner) { Py_CLEAR(outer); break; }
-        PyList_SET_ITEM(outer, (Py_ssize_t)h, inner);
-    }
-    return outer;
-}
-
-PyGetSetDef sn_getset[] = {
-    {"data", sn_get_data, nullptr, "Column of nbytes uint8 entries: the snippets back to back", nullptr},
-    {"offsets", sn_get_offsets, nullptr, "Column of len(self) + 1 int64 entries from 0: snippet i is data[offsets[i]:offsets[i + 1]]",
-     nullptr},
-    {"pattern", sn_get_pattern, nullptr, "Column of len(self) int64 entries: the pattern of every match", nullptr},
-    {"lead", sn_get_lead, nullptr,
-     "Column of len(self) int64 entries: the bytes of snippet i that stand before the match, which begins at "
-     "data[offsets[i] + lead[i]]", nullptr},
-    {"row_offsets", sn_get_row_offsets, nullptr,
-     "None for one haystack; for a batch a Column of len(haystacks) + 1 entries: snippets row_offsets[h] .. row_offsets[h + 1] "
-     "are haystack h's", nullptr},
-    {"device", owner_get_device, nullptr, "None: the parts are in host memory; otherwise the HIP ordinal they lie on", nullptr},
-    {"nbytes", sn_get_nbytes, nullptr, "the size of data", nullptr},
-    {nullptr, nullptr, nullptr, nullptr, nullptr},
-};
-PyMethodDef sn_methods[] = {
-    {"tolist", sn_tolist, METH_NOARGS,
-     "the snippets as list[str] (the str class: UTF-8 decoded) or list[bytes], or one such list per row of a batch (copies "
-     "device parts to the host)"},
-    {nullptr, nullptr, 0, nullptr},
-};
-PyType_Slot sn_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
-    {Py_tp_methods, sn_methods},
-    {Py_tp_getset, sn_getset},
-    {Py_sq_length, reinterpret_cast<void *>(sn_len)},
-    {Py_tp_doc, const_cast<char *>(
-        "The result of find_matches_as_snippets / find_matches_as_snippets_batch: one snippet per match.  .data is a uint8 "
-        "Column of nbytes entries, .offsets, .pattern and .lead (and .row_offsets for a batch) are int64 Column objects, where "
-        "the search ran (.device); len(self) is the number of snippets.  Every accessor of a part waits for the stage's last "
-        "kernel first.")},
-    {0, nullptr},
-};
-
-// context: an int 0 .. 2^63 - 1; sets the exception
-bool parse_context(PyObject *context, uint64_t *out) {
-    if (!PyLong_Check(context) || PyBool_Check(context)) {
-        PyErr_Format(PyExc_TypeError, "argument 'context': '%.100s' object cannot be converted to 'PyInt'", Py_TYPE(context)->tp_name);
-        return false;
-    }
-    int overflow = 0;
-    const long long v = PyLong_AsLongLongAndOverflow(context, &overflow);
-    if (v == -1 && !overflow && PyErr_Occurred()) return false;
-    if (overflow || v < 0) {
-        PyErr_SetString(PyExc_ValueError, "context must be in range(2**63)");
-        return false;
-    }
-    *out = (uint64_t)v;
-    return true;
-}
-// the check without an automaton (the CPU tests; a module function)
-PyObject *mod_snippets_context(PyObject *, PyObject *arg) {
-    uint64_t g = 0;
-    if (!parse_context(arg, &g)) return nullptr;
-    return PyLong_FromUnsignedLongLong(g);
-}
-
-// find_matches_as_snippets / _batch of both classes: utf8 = the str class (UTF-8 bytes, the ends trimmed to characters).  The
-// search runs on bytes: every offset of the result is a byte offset into .data
-PyObject *snippets_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bool batch, bool utf8) {
+// find_matches_as_snippets / _batch (the str class: UTF-8 bytes, the ends trimmed to characters).  The search runs on bytes:
+// every offset of the result is a byte offset into .data
+template <bool batch> PyObject *snippets(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
     static const char *kw_s[] = {"haystack", "overlapping", "context", nullptr};
     static const char *kw_b[] = {"haystacks", "overlapping", "context", "offsets", "row_length", nullptr};
     PyObject *hay = nullptr, *ov = nullptr, *ctx_o = nullptr, *offsets = nullptr, *row_length = nullptr;
@@ -2534,16 +1982,11 @@ PyObject *snippets_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bo
         return nullptr;
     if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
     uint64_t context = 0;
-    if (ctx_o && !parse_context(ctx_o, &context)) return nullptr;
+    if (ctx_o && !parse_u63(ctx_o, "context", &context)) return nullptr;
     const uint32_t flags = utf8 ? ACX_SNIPPET_UTF8 : 0;
     const int device = acx_automaton_device(a);
     acx_snippets_t *c = nullptr;
     int rc;
-    auto host = [&](const uint8_t *p, uint64_t len) {
-        Py_BEGIN_ALLOW_THREADS
-        rc = acx_snippets(a, p, len, nullptr, 0, overlapping, context, flags, &c);
-        Py_END_ALLOW_THREADS
-    };
     if (batch) {
         BatchInput in;
         if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
@@ -2556,31 +1999,16 @@ PyObject *snippets_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bo
                 return acx_snippets_device(a, p, len, d_off, rows, row_len, overlapping, context, flags, &c);
             });
         if (rc == BAD_OFFSETS) return nullptr;
-    } else if (utf8) {
-        const char *p; Py_ssize_t len;
-        if (!str_view(hay, &p, &len)) return nullptr;
-        host(reinterpret_cast<const uint8_t *>(p), (uint64_t)len);
-    } else if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
-        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
-        PyObject *cap = dlpack_view(hay, device, &p, &len, &on_device);
-        if (!cap) return nullptr;
-        if (on_device) { // searched and cut where it lies
-            Py_BEGIN_ALLOW_THREADS
-            rc = acx_device_synchronize_on(device); // (the producer's kernels may still write it)
-            if (rc == ACX_OK) rc = acx_snippets_device(a, p, len, nullptr, 0, 0, overlapping, context, flags, &c);
-            Py_END_ALLOW_THREADS
-        } else {
-            host(p, len);
-        }
-        dlpack_release(cap);
     } else {
-        Py_buffer v;
-        if (!get_bytes_view(hay, &v)) return nullptr;
-        host((const uint8_t *)v.buf, (uint64_t)v.len);
-        PyBuffer_Release(&v);
+        HaystackView v;
+        if (!haystack_view(hay, utf8, true, device, &v)) return nullptr;
+        rc = single_dispatch(
+            device, v,
+            [&](const uint8_t *p, uint64_t len) { return acx_snippets(a, p, len, nullptr, 0, overlapping, context, flags, &c); },
+            [&](const uint8_t *p, uint64_t len) { return acx_snippets_device(a, p, len, nullptr, 0, 0, overlapping, context, flags, &c); }); // (cut where it lies)
     }
     if (rc != ACX_OK) return raise_acx(rc);
-    OwnerObject *o = new_owner(MatchSnippetsType, &SN_OPS, c, device);
+    OwnerObject *o = new_owner(RT_MATCH_SNIPPETS, c, device);
     if (o) {
         static_cast<MatchSnippetsObject *>(o)->batch = batch;
         static_cast<MatchSnippetsObject *>(o)->utf8 = utf8;
@@ -2588,246 +2016,253 @@ PyObject *snippets_impl(acx_automaton_t *a, PyObject *args, PyObject *kwargs, bo
     return reinterpret_cast<PyObject *>(o);
 }
 
-template <bool BATCH> PyObject *ac_snippets(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return snippets_impl(reinterpret_cast<AcObject *>(self_)->ac, args, kwargs, BATCH, true);
-}
-template <bool BATCH> PyObject *bac_snippets(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    return snippets_impl(reinterpret_cast<BacObject *>(self_)->ac, args, kwargs, BATCH, false);
-}
-
 // ---------------------------------------------------------------------------
 // split_rows(data, delimiter=b"\n") -> RowOffsets (acx_split_rows / acx_split_rows_device): a delimited buffer cut into rows.
 // A module function -- no automaton is involved.  A RowOffsets owns the acx_rows_t; .offsets is a Column with the lifetime
 // chain of a MatchColumns' columns, and what the _batch methods take as offsets=.
 // ---------------------------------------------------------------------------
-PyObject *ro_get_offsets(PyObject *s, void *) { return new_column(s, 0, acx_rows_count(ro_handle(s)) + 1); }
-PyObject *ro_get_nbytes(PyObject *s, void *) { return PyLong_FromUnsignedLongLong(acx_rows_bytes(ro_handle(s))); }
-Py_ssize_t ro_len(PyObject *s) { return (Py_ssize_t)acx_rows_count(ro_handle(s)); }
-
-PyObject *ro_tolist(PyObject *self_, PyObject *) {
-    acx_rows_t *h = ro_handle(self_);
-    const uint64_t n = acx_rows_count(h) + 1;
-    std::vector<int64_t> v((size_t)n);
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    rc = acx_rows_copy(h, v.data());
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    return i64_list(v, n);
-}
-
-PyGetSetDef ro_getset[] = {
-    {"offsets", ro_get_offsets, nullptr, "Column of len(self) + 1 int64 entries from 0 to nbytes: row i is data[offsets[i]:offsets[i + 1]]", nullptr},
-    {"device", owner_get_device, nullptr, "None: the offsets are in host memory; otherwise the HIP ordinal they lie on", nullptr},
-    {"nbytes", ro_get_nbytes, nullptr, "the length of the data that was cut", nullptr},
-    {nullptr, nullptr, nullptr, nullptr, nullptr},
-};
-PyMethodDef ro_methods[] = {
-    {"tolist", ro_tolist, METH_NOARGS, "the offsets as list[int] (copies device offsets to the host)"},
-    {nullptr, nullptr, 0, nullptr},
-};
-PyType_Slot ro_slots[] = {
-    {Py_tp_dealloc, reinterpret_cast<void *>(owner_dealloc)},
-    {Py_tp_methods, ro_methods},
-    {Py_tp_getset, ro_getset},
-    {Py_sq_length, reinterpret_cast<void *>(ro_len)},
-    {Py_tp_doc, const_cast<char *>(
-        "The result of split_rows: .offsets is an int64 Column of len(self) + 1 entries that rise strictly from 0 to .nbytes, "
-        "where the data lies (.device); len(self) is the number of rows.  Pass .offsets as offsets= to the _batch methods.")},
-    {0, nullptr},
-};
-
 PyObject *mod_split_rows(PyObject *, PyObject *args, PyObject *kwargs) {
     static const char *kw[] = {"data", "delimiter", nullptr};
     PyObject *data = nullptr, *delim = nullptr;
     if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|O:split_rows", const_cast<char **>(kw), &data, &delim)) return nullptr;
     uint8_t d = '\n';
     if (delim && !parse_fill(delim, PyUnicode_Check(delim) != 0, &d, "delimiter")) return nullptr;
+    HaystackView v; // (a tensor on any device)
+    if (!haystack_view(data, false, true, -1, &v)) return nullptr;
+    if (v.cap && capsule_tensor(v.cap).ndim != 1) {
+        PyErr_SetString(PyExc_TypeError, "Only one-dimensional sequences are supported");
+        return nullptr;
+    }
     acx_rows_t *r = nullptr;
-    int rc;
-    if (!PyUnicode_Check(data) && !PyObject_CheckBuffer(data) && PyObject_HasAttrString(data, "__dlpack__")) {
-        const uint8_t *p = nullptr;
-        uint64_t len = 0;
-        bool on_device = false;
-        PyObject *cap = dlpack_view(data, -1, &p, &len, &on_device);
-        if (!cap) return nullptr;
-        const DLTensorC &t = static_cast<DLManagedTensorC *>(PyCapsule_GetPointer(cap, "dltensor"))->dl_tensor;
-        const int device = t.device.device_id;
-        if (t.ndim != 1) {
-            dlpack_release(cap);
-            PyErr_SetString(PyExc_TypeError, "Only one-dimensional sequences are supported");
-            return nullptr;
-        }
-        Py_BEGIN_ALLOW_THREADS
-        if (on_device) {
-            rc = acx_device_synchronize_on(device); // (the producer's kernels may still write the tensor)
-            if (rc == ACX_OK) rc = acx_split_rows_device(p, len, d, &r);
-        } else {
-            rc = acx_split_rows(p, len, d, &r);
-        }
-        Py_END_ALLOW_THREADS
-        dlpack_release(cap);
-    } else {
-        Py_buffer v;
-        if (!get_bytes_view(data, &v)) return nullptr;
-        Py_BEGIN_ALLOW_THREADS
-        rc = acx_split_rows(static_cast<const uint8_t *>(v.buf), (uint64_t)v.len, d, &r);
-        Py_END_ALLOW_THREADS
-        PyBuffer_Release(&v);
-    }
+    const int rc = single_dispatch(
+        v.cap ? capsule_tensor(v.cap).device.device_id : 0, v,
+        [&](const uint8_t *p, uint64_t len) { return acx_split_rows(p, len, d, &r); },
+        [&](const uint8_t *p, uint64_t len) { return acx_split_rows_device(p, len, d, &r); });
     if (rc != ACX_OK) return raise_acx(rc);
-    return reinterpret_cast<PyObject *>(new_owner(RowOffsetsType, &RO_OPS, r, acx_rows_device(r)));
+    return reinterpret_cast<PyObject *>(new_owner(RT_ROW_OFFSETS, r, acx_rows_device(r)));
 }
 
-// device-resident search -> list of tuples (the records come back with ONE D2H copy of the result)
-PyObject *find_on_device(acx_automaton_t *a, const uint8_t *d_hay, uint64_t len, int overlapping) {
-    acx_result_t *r = nullptr;
-    std::vector<acx_match_t> m;
-    int rc;
-    Py_BEGIN_ALLOW_THREADS
-    // the producer's kernels may still be writing the tensor on its own stream: the library's
-    // streams are non-blocking ones, so order the search behind everything queued on the device
-    // (on the AUTOMATON's device -- the tensor's: dlpack_view checked that -- not the thread's current one)
-    rc = acx_device_synchronize_on(acx_automaton_device(a));
-    if (rc == ACX_OK) rc = acx_find_device(a, d_hay, len, nullptr, 0, 0, overlapping, 0, &r);
-    if (rc == ACX_OK) {
-        m.resize((size_t)acx_result_count(r));
-        if (!m.empty()) rc = acx_result_copy(r, m.data());
-    }
-    if (r) acx_free_result(r);
-    Py_END_ALLOW_THREADS
-    if (rc != ACX_OK) return raise_acx(rc);
-    return matches_to_list(m.data(), (uint64_t)m.size());
-}
-
-// src/lib.rs:422-434: byte offsets, no fix-up
-PyObject *bac_find_indexes(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    BacObject *self = reinterpret_cast<BacObject *>(self_);
+// ---------------------------------------------------------------------------
+// the matches themselves: find_matches_as_indexes, find_matches_as_strings, replace_all
+// ---------------------------------------------------------------------------
+// src/lib.rs:229-249 (the str class: code-point offsets) and 422-434 (the bytes class: byte offsets, no fix-up).  A tensor in
+// HBM is searched where it lies; the records come back with ONE D2H copy of the result.
+PyObject *find_indexes(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
     PyObject *hay; int overlapping;
     if (!parse_find_args(args, kwargs, "O|O:find_matches_as_indexes", &hay, &overlapping)) return nullptr;
-    if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
-        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
-        PyObject *cap = dlpack_view(hay, acx_automaton_device(self->ac), &p, &len, &on_device);
-        if (!cap) return nullptr;
-        PyObject *res;
-        if (on_device) {
-            res = find_on_device(self->ac, p, len, overlapping);
-        } else { // (host memory behind DLPack: the ordinary entry point)
-            acx_match_t *m = nullptr; uint64_t n = 0;
-            const int rc = find_nogil(self->ac, p, len, overlapping, 0, &m, &n);
-            res = rc != ACX_OK ? raise_acx(rc) : matches_to_list(m, n);
-            if (rc == ACX_OK) acx_free_matches(m);
-        }
-        dlpack_release(cap);
-        return res;
-    }
-    Py_buffer v;
-    if (!get_bytes_view(hay, &v)) return nullptr;
-    acx_match_t *m = nullptr; uint64_t n = 0;
-    int rc = find_nogil(self->ac, (const uint8_t *)v.buf, (uint64_t)v.len, overlapping, 0, &m, &n);
-    PyBuffer_Release(&v);
+    HaystackView v;
+    if (!haystack_view(hay, utf8_of(self), true, acx_automaton_device(a), &v)) return nullptr;
+    acx_match_t *m = nullptr; uint64_t n = 0; // a host haystack's matches; a tensor's: dm
+    std::vector<acx_match_t> dm;
+    const int rc = single_dispatch(
+        acx_automaton_device(a), v,
+        // (an ASCII str: byte offset == code-point index, the device fix-up is skipped)
+        [&](const uint8_t *p, uint64_t len) { return acx_find(a, p, len, overlapping, utf8_of(self) && !v.is_ascii, &m, &n); },
+        [&](const uint8_t *p, uint64_t len) {
+            acx_result_t *r = nullptr;
+            int rc = acx_find_device(a, p, len, nullptr, 0, 0, overlapping, 0, &r);
+            if (rc == ACX_OK) {
+                dm.resize((size_t)acx_result_count(r));
+                if (!dm.empty()) rc = acx_result_copy(r, dm.data());
+            }
+            if (r) acx_free_result(r);
+            return rc;
+        });
     if (rc != ACX_OK) return raise_acx(rc);
-    PyObject *list = matches_to_list(m, n);
+    PyObject *list = v.on_device ? matches_to_list(dm.data(), (uint64_t)dm.size()) : matches_to_list(m, n);
     acx_free_matches(m);
     return list;
 }
 
-PyObject *bac_find_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    static const char *kw[] = {"haystacks", "overlapping", "devices", nullptr};
-    PyObject *hs, *ov = nullptr, *devs = nullptr; int overlapping = 0;
-    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|OO:find_matches_as_indexes_batch",
-                                     const_cast<char **>(kw), &hs, &ov, &devs))
-        return nullptr;
-    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
-    BacObject *self = reinterpret_cast<BacObject *>(self_);
-    return find_batch_impl(self->ac, hs, overlapping, false, devs, &self->replicas);
+// src/lib.rs:253-272 (the str class alone)
+PyObject *ac_find_strings(PyObject *self, PyObject *args, PyObject *kwargs) {
+    PyObject *hay; int overlapping;
+    if (!parse_find_args(args, kwargs, "O|O:find_matches_as_strings", &hay, &overlapping)) return nullptr;
+    HaystackView v;
+    if (!haystack_view(hay, true, false, -1, &v)) return nullptr;
+    acx_match_t *m = nullptr; uint64_t n = 0;
+    const int rc = nogil([&] { return acx_find(ac_of(self), v.p, v.len, overlapping, 0 /* byte offsets */, &m, &n); });
+    if (rc != ACX_OK) return raise_acx(rc);
+    PyObject *patterns = reinterpret_cast<AcObject *>(self)->patterns;
+    PyObject *list = list_of(0, n, [&](uint64_t i) -> PyObject * {
+        if (!patterns) // slice of the haystack by byte offsets, src/lib.rs:267-270
+            return PyUnicode_DecodeUTF8(reinterpret_cast<const char *>(v.p) + m[i].start, (Py_ssize_t)(m[i].end - m[i].start), "strict");
+        PyObject *item = PyList_GET_ITEM(patterns, (Py_ssize_t)m[i].pattern); // clone_ref of the stored pattern, src/lib.rs:263-266
+        Py_INCREF(item);
+        return item;
+    });
+    acx_free_matches(m);
+    return list;
 }
 
-PyObject *bac_replace_all(PyObject *self_, PyObject *args, PyObject *kwargs) {
+// replace_all: the str class's str, or the bytes class's buffer or tensor (searched and spliced where it lies; only the
+// output crosses to the host).  The haystack is looked at before replace_with.
+PyObject *replace_all(PyObject *self, PyObject *args, PyObject *kwargs) {
     static const char *kw[] = {"haystack", "replace_with", nullptr};
     PyObject *hay, *rw;
     if (!PyArg_ParseTupleAndKeywords(args, kwargs, "OO:replace_all", const_cast<char **>(kw), &hay, &rw)) return nullptr;
-    acx_automaton_t *a = reinterpret_cast<BacObject *>(self_)->ac;
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
+    HaystackView v;
+    if (!haystack_view(hay, utf8, true, acx_automaton_device(a), &v)) return nullptr;
     std::vector<uint8_t> blob;
     std::vector<uint64_t> off;
-    if (!PyObject_CheckBuffer(hay) && PyObject_HasAttrString(hay, "__dlpack__")) {
-        const uint8_t *p = nullptr; uint64_t len = 0; bool on_device = false;
-        PyObject *cap = dlpack_view(hay, acx_automaton_device(a), &p, &len, &on_device);
-        if (!cap) return nullptr;
-        if (!replacements(rw, false, &blob, &off)) { dlpack_release(cap); return nullptr; }
-        acx_replaced_t *r = nullptr;
-        int rc;
-        if (on_device) { // searched and spliced where it lies; only the output crosses to the host
-            Py_BEGIN_ALLOW_THREADS
-            rc = acx_device_synchronize_on(acx_automaton_device(a)); // (the producer's kernels may still write it)
-            if (rc == ACX_OK) rc = acx_replace_device(a, p, len, nullptr, 0, 0, blob.data(), off.data(), off.size() - 1, &r);
-            Py_END_ALLOW_THREADS
-        } else {
-            rc = replace_nogil(a, p, len, nullptr, 0, blob, off, &r);
-        }
-        PyObject *res = rc != ACX_OK ? raise_acx(rc) : replaced_result(r, false);
-        dlpack_release(cap);
-        return res;
-    }
-    Py_buffer v;
-    if (!get_bytes_view(hay, &v)) return nullptr;
-    if (!replacements(rw, false, &blob, &off)) { PyBuffer_Release(&v); return nullptr; }
+    if (!replacements(rw, utf8, &blob, &off)) return nullptr;
     acx_replaced_t *r = nullptr;
-    const int rc = replace_nogil(a, (const uint8_t *)v.buf, (uint64_t)v.len, nullptr, 0, blob, off, &r);
-    PyBuffer_Release(&v);
+    const int rc = single_dispatch(
+        acx_automaton_device(a), v,
+        [&](const uint8_t *p, uint64_t len) { return acx_replace(a, p, len, nullptr, 0, blob.data(), off.data(), off.size() - 1, &r); },
+        [&](const uint8_t *p, uint64_t len) { return acx_replace_device(a, p, len, nullptr, 0, 0, blob.data(), off.data(), off.size() - 1, &r); });
     if (rc != ACX_OK) return raise_acx(rc);
-    return replaced_result(r, false);
+    return replaced_result(r, utf8);
 }
 
-PyObject *bac_replace_all_batch(PyObject *self_, PyObject *args, PyObject *kwargs) {
-    static const char *kw[] = {"haystacks", "replace_with", nullptr};
-    PyObject *hs, *rw;
-    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "OO:replace_all_batch", const_cast<char **>(kw), &hs, &rw)) return nullptr;
-    return replace_batch_impl(reinterpret_cast<BacObject *>(self_)->ac, hs, rw, false);
-}
-
-PyObject *bac_info(PyObject *self_, PyObject *) {
-    return info_dict(reinterpret_cast<BacObject *>(self_)->ac);
-}
-
-PyMethodDef bac_methods[] = {
-    {"find_matches_as_indexes", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(bac_find_indexes)),
-     METH_VARARGS | METH_KEYWORDS,
+// ---------------------------------------------------------------------------
+// the method tables: the methods both classes have, once; what only one has, or has with words of its own, in front
+// ---------------------------------------------------------------------------
+#define KW(...) reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(__VA_ARGS__)), METH_VARARGS | METH_KEYWORDS
+const PyMethodDef SHARED_METHODS[] = {
+    {"find_matches_as_indexes", KW(find_indexes),
      "Return matches as tuple of (index_into_patterns, start_index_in_haystack, "
      "end_index_in_haystack). If ``overlapping`` is ``False`` (the default), don't include "
      "overlapping results."},
-    {"find_matches_as_indexes_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(bac_find_batch)),
-     METH_VARARGS | METH_KEYWORDS,
+    {"find_matches_as_indexes_batch", KW(find_batch),
      "[extension] one device pass over many haystacks; equals "
      "[self.find_matches_as_indexes(h, overlapping) for h in haystacks].  devices=[ordinals]: the batch "
      "is cut into contiguous ranges of haystacks, one per device (replicas of the automaton are built on "
      "first use), scanned side by side from one host thread each."},
-    {"replace_all", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(bac_replace_all)), METH_VARARGS | METH_KEYWORDS,
-     "[extension] the haystack (a buffer, or a __dlpack__ tensor on the automaton's device) as bytes with every "
-     "non-overlapping match replaced by replace_with[pattern index]; replace_with has one buffer per pattern."},
-    {"replace_all_batch", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(bac_replace_all_batch)),
-     METH_VARARGS | METH_KEYWORDS, "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
-    ACX_SUMMARY_METHODS(bac_summary),
-    ACX_COLUMNS_METHODS(bac_columns),
-    ACX_SPARSE_COUNTS_METHOD(bac_sparse_counts),
-    ACX_FILTER_METHOD(bac_filter_batch),
-    ACX_SCORE_METHODS(bac_score_batch, bac_filter_by_score_batch),
-    ACX_MASK_METHODS(bac_mask),
-    ACX_SPANS_METHODS(bac_spans),
-    ACX_SNIPPETS_METHODS(bac_snippets),
-    {"_info", bac_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
-    {nullptr, nullptr, 0, nullptr},
+    {"replace_all_batch", KW(replace_all_batch), "[extension] [self.replace_all(h, replace_with) for h in haystacks] in one call."},
+    {"_info", automaton_info, METH_NOARGS, "[extension] automaton / device facts as a dict."},
+    {"is_match", KW(summary<SUM_IS_MATCH, false>),
+     "[extension] bool(find_matches_as_indexes(haystack)) without the match list (the crate's is_match).  No early exit: "
+     "one search over the whole haystack."},
+    {"find_first", KW(summary<SUM_FIND_FIRST, false>),
+     "[extension] find_matches_as_indexes(haystack)[0], or None (the crate's find for the object's match kind)."},
+    {"count_matches", KW(summary<SUM_COUNT, false>), "[extension] len(find_matches_as_indexes(haystack, overlapping))."},
+    {"count_by_pattern", KW(summary<SUM_BY_PATTERN, false>),
+     "[extension] one int per pattern: how many of find_matches_as_indexes(haystack, overlapping) name it."},
+    {"is_match_batch", KW(summary<SUM_IS_MATCH, true>), "[extension] [self.is_match(h) for h in haystacks] in one call."},
+    {"find_first_batch", KW(summary<SUM_FIND_FIRST, true>), "[extension] [self.find_first(h) for h in haystacks] in one call."},
+    {"count_matches_batch", KW(summary<SUM_COUNT, true>), "[extension] [self.count_matches(h, overlapping) for h in haystacks] in one call."},
+    {"count_by_pattern_batch", KW(summary<SUM_BY_PATTERN, true>),
+     "[extension] the per-pattern totals over all haystacks: the sum of self.count_by_pattern(h, overlapping)."},
+    {"count_by_pattern_sparse_batch", KW(sparse_counts),
+     "[extension] count_by_pattern_sparse_batch(haystacks, overlapping=False, *, offsets=None, row_length=None) -> "
+     "PatternCounts: which patterns occur in which haystack and how often, as a CSR matrix of len(haystacks) x patterns "
+     "(row_offsets, pattern ascending within a row, count: int64 Columns that torch.sparse_csr_tensor takes as they are).  "
+     "haystacks: a sequence, as in every other _batch method, or ONE 1-D contiguous uint8 __dlpack__ tensor that holds the "
+     "rows back to back, cut by exactly one of offsets (a 1-D int64 __dlpack__ tensor of rows + 1 entries on the haystack's "
+     "device) and row_length (an int that divides the tensor's length).  A tensor on the automaton's device is searched and "
+     "reduced there and the result stays there; nothing but its size crosses the bus."},
+    {"filter_batch", KW(filter_batch),
+     "[extension] filter_batch(haystacks, overlapping=False, *, keep='unmatched', min_matches=1, offsets=None, "
+     "row_length=None) -> FilteredRows: the rows of the batch with fewer than min_matches matches (keep='unmatched': drop "
+     "every row that contains a pattern) or with at least that many (keep='matched'), compacted where the search ran: "
+     ".rows (the kept source row indexes), .offsets and .data (the kept rows' own bytes back to back).  haystacks: a "
+     "sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "
+     "count_by_pattern_sparse_batch.  A tensor on the automaton's device is searched and compacted there and the result "
+     "stays there; nothing but its two sizes crosses the bus."},
+    {"score_batch", KW(scored<false>),
+     "[extension] score_batch(haystacks, weights, overlapping=False, *, offsets=None, row_length=None) -> RowScores: for "
+     "every row the sum of weights[pattern] over the matches find_matches_as_indexes_batch reports for it (int64; it wraps "
+     "modulo 2^64).  weights: one int per pattern, |w| < 2^31 -- a sequence of ints or an int64 / int32 buffer.  haystacks: "
+     "a sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "
+     "count_by_pattern_sparse_batch.  A tensor on the automaton's device is searched and scored there and the result stays "
+     "there."},
+    {"filter_by_score_batch", KW(scored<true>),
+     "[extension] filter_by_score_batch(haystacks, weights, overlapping=False, *, keep='unmatched', min_score=1, "
+     "offsets=None, row_length=None) -> FilteredRows: filter_batch with the verdict on a row taken from its score -- a row "
+     "is matched when score_batch's value for it is at least min_score (any int64)."},
+    {"mask_all", KW(mask<true, false>),
+     "[extension] mask_all(haystack, fill, overlapping=False) -> the haystack with every byte that a match covers replaced "
+     "by fill and every other byte where it was: fixed-fill redaction.  fill: an int 0..255 or a one-byte buffer "
+     "(BytesAhoCorasick), a one-character ASCII str (AhoCorasick: a covered character becomes ONE fill, so the result has "
+     "len(haystack) characters).  overlapping=True on a Standard object covers the union of all occurrences."},
+    {"match_mask", KW(mask<false, false>),
+     "[extension] match_mask(haystack, overlapping=False) -> bytes: 1 where a match covers the haystack's byte "
+     "(AhoCorasick: its character), else 0; len(haystack) entries."},
+    {"mask_all_batch", KW(mask<true, true>),
+     "[extension] mask_all_batch(haystacks, fill, overlapping=False, *, offsets=None, row_length=None) -> MaskedRows: "
+     "mask_all of every row in one call, as one uint8 .data in the input's own layout with its .offsets.  haystacks: a "
+     "sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "
+     "count_by_pattern_sparse_batch.  A tensor on the automaton's device is searched and painted there and the result "
+     "stays there.  AhoCorasick: .data is in UTF-8 bytes (a covered k-byte character is k fills); tolist() gives one fill "
+     "per character for a sequence of str and the bytes as they are, decoded, for a tensor."},
+    {"match_mask_batch", KW(mask<false, true>),
+     "[extension] match_mask_batch(haystacks, overlapping=False, *, offsets=None, row_length=None) -> MaskedRows: "
+     "match_mask of every row in one call: .data is 1 where a match covers the byte, else 0."},
+    {"cover_spans", KW(spans<false>),
+     "cover_spans(haystack, overlapping=False, *, gap=0) -> MatchSpans\n\n[extension] the union of the matches that "
+     "find_matches_as_indexes(haystack, overlapping) reports, as two int64 columns .start / .end: matches that overlap, "
+     "touch or lie at most gap positions apart are ONE span -- the ranges to highlight, cut or redact.  The spans are "
+     "ascending and disjoint and next.start - prev.end > gap; with gap=0 they are the runs of ones of match_mask.  "
+     "AhoCorasick: character indexes; BytesAhoCorasick: byte offsets, and a __dlpack__ tensor on the automaton's device is "
+     "searched and merged there -- nothing but the number of spans crosses the bus.  gap: an int 0 .. 2**63 - 1."},
+    {"cover_spans_batch", KW(spans<true>),
+     "cover_spans_batch(haystacks, overlapping=False, *, gap=0, offsets=None, row_length=None) -> MatchSpans\n\n"
+     "[extension] cover_spans of every row in one call, with .row_offsets: spans row_offsets[h] .. row_offsets[h + 1] - 1 "
+     "are row h's, their offsets local to it; spans never join across rows.  haystacks: a sequence, or ONE 1-D contiguous "
+     "uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for count_by_pattern_sparse_batch (byte "
+     "offsets for a tensor).  A tensor on the automaton's device is searched and merged there and the columns stay there."},
+    {"find_matches_as_snippets", KW(snippets<false>),
+     "find_matches_as_snippets(haystack, overlapping=False, *, context=0) -> MatchSnippets\n\n[extension] one snippet per "
+     "match that find_matches_as_columns(haystack, overlapping) reports, in its order: the matched text and up to context "
+     "BYTES on each side of it, clipped to the haystack, as the caller's own bytes (.data, cut by .offsets; the match begins "
+     ".lead bytes into its snippet; .pattern is the columns' pattern).  AhoCorasick: UTF-8 bytes, the ends moved inward to a "
+     "character boundary, so tolist() is a list[str] and with context=0 it equals find_matches_as_strings.  "
+     "BytesAhoCorasick: a __dlpack__ tensor on the automaton's device is searched and cut there -- nothing but the size of "
+     "the data crosses the bus.  context: an int 0 .. 2**63 - 1."},
+    {"find_matches_as_snippets_batch", KW(snippets<true>),
+     "find_matches_as_snippets_batch(haystacks, overlapping=False, *, context=0, offsets=None, row_length=None) -> "
+     "MatchSnippets\n\n[extension] find_matches_as_snippets of every row in one call, with .row_offsets: snippets "
+     "row_offsets[h] .. row_offsets[h + 1] - 1 are row h's; a snippet never crosses a row.  haystacks: a sequence, or ONE 1-D "
+     "contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for cover_spans_batch.  A tensor on "
+     "the automaton's device is searched and cut there and every part stays there."},
+    {"find_matches_as_columns", KW(columns<false>),
+     "[extension] find_matches_as_indexes(haystack, overlapping) as a MatchColumns: three int64 columns (pattern, start, "
+     "end) exported through DLPack, in host memory for a host haystack and in HBM on the automaton's device for a "
+     "__dlpack__ tensor there -- no tuple list, and for a tensor nothing but the number of matches crosses the bus.  The "
+     "call returns once that number is known; every accessor of a column, __dlpack__ included, waits for the split kernel "
+     "first, so a consumer on any stream sees finished data."},
+    {"find_matches_as_columns_batch", KW(columns<true>),
+     "[extension] find_matches_as_indexes_batch(haystacks, overlapping) as a MatchColumns with row_offsets: rows "
+     "row_offsets[h] .. row_offsets[h + 1] are haystack h's matches, their offsets local to it."},
 };
 
-PyType_Slot bac_slots[] = {
-    {Py_tp_new, reinterpret_cast<void *>(bac_new)},
-    {Py_tp_dealloc, reinterpret_cast<void *>(bac_dealloc)},
-    {Py_tp_methods, bac_methods},
-    {Py_tp_doc, const_cast<char *>(
-        "Search for multiple pattern bytes against a single bytes haystack.\n\n"
-        "BytesAhoCorasick(patterns, matchkind=MatchKind.Standard, implementation=None, ascii_case_insensitive=False)")},
-    {0, nullptr},
+const PyMethodDef AC_METHODS[] = {
+    {"find_matches_as_strings", KW(ac_find_strings),
+     "Return matches as list of patterns (i.e. strings). If ``overlapping`` is ``False`` (the "
+     "default), don't include overlapping results."},
+    {"replace_all", KW(replace_all),
+     "[extension] the haystack with every non-overlapping match (as find_matches_as_indexes reports them) replaced by "
+     "replace_with[pattern index]; replace_with has one str per pattern (ValueError otherwise)."},
 };
+const PyMethodDef BAC_METHODS[] = {
+    {"replace_all", KW(replace_all),
+     "[extension] the haystack (a buffer, or a __dlpack__ tensor on the automaton's device) as bytes with every "
+     "non-overlapping match replaced by replace_with[pattern index]; replace_with has one buffer per pattern."},
+};
+#undef KW
+
+// One automaton class in the module: its own methods, then the shared ones.  The table lives as long as the type.
+template <size_t N>
+PyTypeObject *register_automaton_type(PyObject *module, const char *name, int size, newfunc tp_new, const char *doc, const PyMethodDef (&own)[N]) {
+    std::vector<PyMethodDef> *methods = new std::vector<PyMethodDef>(own, own + N);
+    methods->insert(methods->end(), std::begin(SHARED_METHODS), std::end(SHARED_METHODS));
+    methods->push_back({nullptr, nullptr, 0, nullptr});
+    PyType_Slot slots[] = {
+        {Py_tp_new, reinterpret_cast<void *>(tp_new)},
+        {Py_tp_dealloc, reinterpret_cast<void *>(automaton_dealloc)},
+        {Py_tp_methods, methods->data()},
+        {Py_tp_doc, const_cast<char *>(doc)},
+        {0, nullptr},
+    };
+    PyType_Spec spec = {name, size, 0, Py_TPFLAGS_DEFAULT, slots};
+    PyObject *tp = PyType_FromSpec(&spec);
+    if (!tp || PyModule_AddObject(module, strchr(name, '.') + 1, tp) < 0) { Py_XDECREF(tp); return nullptr; }
+    return reinterpret_cast<PyTypeObject *>(tp);
+}
 
 PyMethodDef module_methods[] = {
     {"split_rows", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(mod_split_rows)), METH_VARARGS | METH_KEYWORDS,
@@ -2869,51 +2304,22 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
     MatchKindType = make_enum(m, "MatchKind", "ahocorasick_rs.MatchKind", mk_v, mk_q, 3);
     ImplementationType = make_enum(m, "Implementation", "ahocorasick_rs.Implementation", im_v, im_q, 3);
     if (!MatchKindType || !ImplementationType) { Py_DECREF(m); return nullptr; }
-    PyType_Spec ac_spec = {"ahocorasick_rs.AhoCorasick", sizeof(AcObject), 0, Py_TPFLAGS_DEFAULT, ac_slots};
-    PyType_Spec bac_spec = {"ahocorasick_rs.BytesAhoCorasick", sizeof(BacObject), 0, Py_TPFLAGS_DEFAULT,
-                            bac_slots};
-    PyObject *ac_t = PyType_FromSpec(&ac_spec);
-    PyObject *bac_t = PyType_FromSpec(&bac_spec);
-    PyType_Spec mc_spec = {"ahocorasick_rs.MatchColumns", sizeof(MatchColumnsObject), 0,
-                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, mc_slots};
     PyType_Spec col_spec = {"ahocorasick_rs.Column", sizeof(ColumnObject), 0,
                             Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, col_slots};
-    PyType_Spec pc_spec = {"ahocorasick_rs.PatternCounts", sizeof(PatternCountsObject), 0,
-                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, pc_slots};
-    PyType_Spec fr_spec = {"ahocorasick_rs.FilteredRows", sizeof(FilteredRowsObject), 0,
-                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, fr_slots};
-    PyType_Spec rs_spec = {"ahocorasick_rs.RowScores", sizeof(OwnerObject), 0,
-                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, rs_slots};
-    PyType_Spec mr_spec = {"ahocorasick_rs.MaskedRows", sizeof(MaskedRowsObject), 0,
-                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, mr_slots};
-    PyType_Spec ro_spec = {"ahocorasick_rs.RowOffsets", sizeof(OwnerObject), 0,
-                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, ro_slots};
-    PyType_Spec ms_spec = {"ahocorasick_rs.MatchSpans", sizeof(MatchSpansObject), 0,
-                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, ms_slots};
-    MatchSpansType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&ms_spec));
-    PyType_Spec sn_spec = {"ahocorasick_rs.MatchSnippets", sizeof(MatchSnippetsObject), 0,
-                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, sn_slots};
-    MatchSnippetsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&sn_spec));
-    MaskedRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mr_spec));
-    RowOffsetsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&ro_spec));
-    FilteredRowsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&fr_spec));
-    RowScoresType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&rs_spec));
-    MatchColumnsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&mc_spec));
     ColumnType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&col_spec));
-    PatternCountsType = reinterpret_cast<PyTypeObject *>(PyType_FromSpec(&pc_spec));
-    if (!MatchColumnsType || !ColumnType || !PatternCountsType || !FilteredRowsType || !RowScoresType || !MaskedRowsType || !RowOffsetsType || !MatchSpansType || !MatchSnippetsType) { Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m); return nullptr; }
-    for (PyTypeObject *tp : {MatchColumnsType, ColumnType, PatternCountsType, FilteredRowsType, RowScoresType, MaskedRowsType, RowOffsetsType, MatchSpansType, MatchSnippetsType}) { // (the module holds one reference, the globals the other)
-        Py_INCREF(tp);
-        if (PyModule_AddObject(m, tp == ColumnType ? "Column" : tp == PatternCountsType ? "PatternCounts" : tp == FilteredRowsType ? "FilteredRows" : tp == RowScoresType ? "RowScores" : tp == MaskedRowsType ? "MaskedRows" : tp == RowOffsetsType ? "RowOffsets" : tp == MatchSpansType ? "MatchSpans" : tp == MatchSnippetsType ? "MatchSnippets" : "MatchColumns",
-                               reinterpret_cast<PyObject *>(tp)) < 0) {
-            Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);
-            return nullptr;
-        }
-    }
-    if (!ac_t || !bac_t || PyModule_AddObject(m, "AhoCorasick", ac_t) < 0 ||
-        PyModule_AddObject(m, "BytesAhoCorasick", bac_t) < 0) {
-        Py_XDECREF(ac_t); Py_XDECREF(bac_t); Py_DECREF(m);
-        return nullptr;
-    }
+    bool ok = ColumnType != nullptr;
+    if (ok) Py_INCREF(ColumnType); // (the module holds one reference, the global the other)
+    ok = ok && PyModule_AddObject(m, "Column", reinterpret_cast<PyObject *>(ColumnType)) == 0;
+    for (ResultType &t : RESULT_TYPES) ok = ok && register_result_type(m, &t);
+    AhoCorasickType = !ok ? nullptr : register_automaton_type(
+        m, "ahocorasick_rs.AhoCorasick", sizeof(AcObject), ac_new,
+        "Search for multiple pattern strings against a single haystack string.\n\n"
+        "AhoCorasick(patterns, matchkind=MatchKind.Standard, store_patterns=None, implementation=None, "
+        "ascii_case_insensitive=False)", AC_METHODS);
+    ok = AhoCorasickType && register_automaton_type(
+        m, "ahocorasick_rs.BytesAhoCorasick", sizeof(BacObject), bac_new,
+        "Search for multiple pattern bytes against a single bytes haystack.\n\n"
+        "BytesAhoCorasick(patterns, matchkind=MatchKind.Standard, implementation=None, ascii_case_insensitive=False)", BAC_METHODS);
+    if (!ok) { Py_DECREF(m); return nullptr; }
     return m;
 }
