@@ -11,13 +11,7 @@ namespace acx {
 // ---------------------------------------------------------------------------
 // 1. + 3. one thread per source row
 // ---------------------------------------------------------------------------
-__device__ inline uint64_t row_begin(const FilterRows &R, uint64_t h) {
-    if (R.in_off) return R.in_off[h];
-    if (R.uniform_len) return h * R.uniform_len;
-    return h ? R.len : 0;
-}
-
-__global__ void k_filter_flags(FilterRows R, const uint64_t *__restrict__ counts, uint64_t min_matches, uint32_t keep_matched,
+__global__ void k_filter_flags(RowCut R, const uint64_t *__restrict__ counts, uint64_t min_matches, uint32_t keep_matched,
                                uint64_t *__restrict__ klen, uint64_t *__restrict__ kflag) {
     const uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (h >= R.n) return;
@@ -27,7 +21,7 @@ __global__ void k_filter_flags(FilterRows R, const uint64_t *__restrict__ counts
     kflag[h] = kept ? 1 : 0;
 }
 
-__global__ void k_filter_index(FilterRows R, const int64_t *__restrict__ A, const int64_t *__restrict__ B,
+__global__ void k_filter_index(RowCut R, const int64_t *__restrict__ A, const int64_t *__restrict__ B,
                                int64_t *__restrict__ rows, int64_t *__restrict__ offsets, uint64_t *__restrict__ src) {
     const uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (h >= R.n) return;
@@ -40,7 +34,7 @@ __global__ void k_filter_index(FilterRows R, const int64_t *__restrict__ A, cons
     if (h == R.n - 1) offsets[B[R.n]] = A[R.n];
 }
 
-hipError_t filter_flags(const FilterRows &R, const uint64_t *counts, uint64_t min_matches, bool keep_matched, uint64_t *klen,
+hipError_t filter_flags(const RowCut &R, const uint64_t *counts, uint64_t min_matches, bool keep_matched, uint64_t *klen,
                         uint64_t *kflag, hipStream_t st) {
     if (!R.n) return hipSuccess;
     hipLaunchKernelGGL(k_filter_flags, dim3((uint32_t)((R.n + 255) / 256)), dim3(256), 0, st, R, counts, min_matches,
@@ -48,7 +42,7 @@ hipError_t filter_flags(const FilterRows &R, const uint64_t *counts, uint64_t mi
     return hipGetLastError();
 }
 
-hipError_t filter_index(const FilterRows &R, const int64_t *A, const int64_t *B, int64_t *rows, int64_t *offsets, uint64_t *src,
+hipError_t filter_index(const RowCut &R, const int64_t *A, const int64_t *B, int64_t *rows, int64_t *offsets, uint64_t *src,
                         hipStream_t st) {
     if (!R.n) return hipSuccess;
     hipLaunchKernelGGL(k_filter_index, dim3((uint32_t)((R.n + 255) / 256)), dim3(256), 0, st, R, A, B, rows, offsets, src);
@@ -69,33 +63,10 @@ hipError_t filter_index(const FilterRows &R, const int64_t *A, const int64_t *B,
 constexpr uint32_t FG_CHUNKS = FILTER_TILE / 16 / FILTER_THREADS;
 static_assert(FG_CHUNKS * 16 * FILTER_THREADS == FILTER_TILE, "a tile is a whole number of chunks per thread");
 
-__device__ inline uint64_t count_le(const int64_t *o, uint64_t n, uint64_t x) { // entries <= x (o ascending)
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if ((uint64_t)o[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// per tile boundary t = 0 .. ntiles: U[t] = the rows that begin at or before t * FILTER_TILE, L[t] = those that begin
-// before it (clamped to the output's end) -- tile t stages rows U[t] - 1 .. L[t + 1] - 1
+// the kept rows that begin at or before, and before, every boundary of the output's tiles (stage_device.hpp)
 __global__ void k_filter_tiles(const int64_t *__restrict__ offsets, uint64_t k, uint64_t total, uint64_t ntiles, uint64_t *U,
                                uint64_t *L) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t > ntiles) return;
-    const uint64_t x = std::min<uint64_t>(t * FILTER_TILE, total);
-    U[t] = count_le(offsets, k, x);
-    L[t] = x ? count_le(offsets, k, x - 1) : 0;
-}
-
-__device__ inline uint4 funnel16(uint4 lo, uint4 hi, uint32_t s) { // bytes s .. s + 15 of lo:hi
-    uint32_t v0 = lo.x, v1 = lo.y, v2 = lo.z, v3 = lo.w, v4 = hi.x, v5 = hi.y, v6 = hi.z, v7 = hi.w;
-    if (s & 8) { v0 = v2; v1 = v3; v2 = v4; v3 = v5; v4 = v6; v5 = v7; }
-    if (s & 4) { v0 = v1; v1 = v2; v2 = v3; v3 = v4; v4 = v5; }
-    const uint32_t sh = s & 3;
-    return make_uint4(__builtin_amdgcn_alignbyte(v1, v0, sh), __builtin_amdgcn_alignbyte(v2, v1, sh),
-                      __builtin_amdgcn_alignbyte(v3, v2, sh), __builtin_amdgcn_alignbyte(v4, v3, sh));
+    out_tile_bounds<FILTER_TILE>(offsets, k, total, ntiles, U, L);
 }
 
 __global__ __launch_bounds__(FILTER_THREADS) void k_filter_gather(const uint8_t *__restrict__ hay, uint64_t len,
@@ -197,12 +168,12 @@ __global__ __launch_bounds__(FILTER_THREADS) void k_filter_gather(const uint8_t 
     }
 }
 
-uint64_t filter_tile_words(uint64_t total) { return 2 * ((total + FILTER_TILE - 1) / FILTER_TILE + 1); }
+uint64_t filter_tile_words(uint64_t total) { return out_tile_words(total, FILTER_TILE); }
 
 hipError_t filter_gather(const uint8_t *hay, uint64_t len, const int64_t *offsets, const uint64_t *src, uint64_t k,
                          uint64_t *tiles, uint8_t *out, uint64_t total, hipStream_t st) {
     if (!total || !k) return hipSuccess;
-    const uint64_t ntiles = (total + FILTER_TILE - 1) / FILTER_TILE;
+    const uint64_t ntiles = tiles_of(total, FILTER_TILE);
     if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
     uint64_t *U = tiles, *L = tiles + ntiles + 1;
     hipLaunchKernelGGL(k_filter_tiles, dim3((uint32_t)((ntiles + 1 + 255) / 256)), dim3(256), 0, st, offsets, k, total, ntiles, U,

@@ -1,6 +1,6 @@
 // filter.hpp -- launch wrappers of the row-filter kernels in filter.hip (acx_filter_device / acx_filter_rows_device).
 //
-// A batch of n rows in HBM -- `len` bytes at hay, cut by in_off (n + 1 offsets from 0), by uniform_len, or one row -- and
+// A batch of n rows in HBM -- `len` bytes at hay, cut by offsets (n + 1 of them from 0), by uniform_len, or one row -- and
 // counts[h] matches per row become the COMPACTED batch of the kept rows: row h is kept iff (counts[h] >= min_matches) ==
 // keep_matched.  rows (k source row indexes, ascending), offsets (k + 1 words from 0) and data (the kept rows' bytes back
 // to back).  All on the caller's stream, every offset and size 64-bit (32-bit indexes within a tile only), vector stores:
@@ -18,6 +18,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "stage_device.hpp"
+
 namespace acx {
 
 // STARTING SIZES, NOT MEASURED ONES.  A workgroup of FILTER_THREADS threads writes one tile of
@@ -29,20 +31,11 @@ constexpr uint32_t FILTER_THREADS = 256;
 constexpr uint32_t FILTER_TILE = 16384;
 constexpr uint32_t FILTER_WIN = 1024;
 
-// The input's rows: in_off != null (n + 1 device offsets from 0 to len), uniform_len > 0 (row h starts at h * uniform_len),
-// or neither (one row of `len` bytes: n = 1).
-struct FilterRows {
-    const uint64_t *in_off;
-    uint64_t uniform_len;
-    uint64_t n;
-    uint64_t len;
-};
-
-// klen, kflag: n words each.  n == 0: nothing is launched.
-hipError_t filter_flags(const FilterRows &R, const uint64_t *counts, uint64_t min_matches, bool keep_matched, uint64_t *klen,
+// R: the input's rows (stage_device.hpp).  klen, kflag: n words each.  n == 0: nothing is launched.
+hipError_t filter_flags(const RowCut &R, const uint64_t *counts, uint64_t min_matches, bool keep_matched, uint64_t *klen,
                         uint64_t *kflag, hipStream_t st);
 // A, B: the scans' n + 1 entries; rows: k words, offsets: k + 1 words, src: k words (k = B[n]).  n == 0: nothing is launched.
-hipError_t filter_index(const FilterRows &R, const int64_t *A, const int64_t *B, int64_t *rows, int64_t *offsets, uint64_t *src,
+hipError_t filter_index(const RowCut &R, const int64_t *A, const int64_t *B, int64_t *rows, int64_t *offsets, uint64_t *src,
                         hipStream_t st);
 // u64 words of scratch filter_gather needs for an output of `total` bytes (the rows of every output tile)
 uint64_t filter_tile_words(uint64_t total);

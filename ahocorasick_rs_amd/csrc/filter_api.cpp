@@ -33,11 +33,11 @@ struct Stage {
     void *block = nullptr;
     uint64_t *klen = nullptr, *kflag = nullptr, *scan_tmp = nullptr, *src = nullptr, *tiles = nullptr;
     int64_t *A = nullptr, *B = nullptr;
-    acx::FilterRows R{nullptr, 0, 0, 0};
+    acx::RowCut R{nullptr, 0, 0, 0};
 };
 
 // The stage up to the point where the result's size is known: the flags and the two scans (n > 0).  d_counts: n words.
-int stage_sizes(int device, hipStream_t st, const acx::FilterRows &R, const uint64_t *d_counts, uint64_t min_matches,
+int stage_sizes(int device, hipStream_t st, const acx::RowCut &R, const uint64_t *d_counts, uint64_t min_matches,
                 bool keep_matched, Stage *S, uint64_t *k, uint64_t *total) {
     S->R = R;
     const uint64_t n = R.n;
@@ -138,7 +138,7 @@ int run_filter(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_
                 d_counts = T.flags;
                 min_matches = 1;
             }
-            const acx::FilterRows rows{G.offsets, G.uniform_len, n, len};
+            const acx::RowCut rows = row_cut(G, len);
             rc = stage_sizes(a->device, st, rows, d_counts, min_matches, (flags & ACX_FILTER_KEEP_MATCHED) != 0, &S, &R->rows, &R->bytes);
             if (rc != ACX_OK) return rc;
         }
@@ -297,7 +297,7 @@ int acx_filter_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_of
         int rs = device_offsets_span(d_offsets, n_hay, len);
         if (rs != ACX_OK) return rs;
         Stage S;
-        const acx::FilterRows rows{d_offsets, uniform_len, n_hay, len};
+        const acx::RowCut rows{d_offsets, uniform_len, n_hay, len};
         rs = stage_sizes(device, nullptr, rows, d_counts, min_matches, (flags & ACX_FILTER_KEEP_MATCHED) != 0, &S, &k, &total);
         *block = S.block;
         return rs == ACX_OK ? stage_finish(&S, (const uint8_t *)d_hay, k, total, d_rows, d_out_offsets, d_data, nullptr) : rs;

@@ -18,25 +18,10 @@ static_assert(MK_IPT * MASK_THREADS == MASK_TILE && MK_IPT == 4, "a thread reads
 static_assert(MASK_THREADS % 64 == 0 && MASK_THREADS >= 48, "whole waves; threads 0 .. 15 and 32 .. 47 store a sweep's edge bytes");
 static_assert(MASK_LONG >= 32, "a swept record holds a 16-byte boundary before its last one");
 
-__device__ inline uint64_t mask_count_le(const int64_t *o, uint64_t n, uint64_t x) { // entries <= x (o ascending)
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if ((uint64_t)o[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// per tile t: U[t] = the row that holds record t * MASK_TILE, L[t] = the row that holds the tile's last record -- the LAST
-// row that begins at or before the record (of several rows with one start all but the last are empty).  rec_off[0] = 0 and
-// rec_off[rows] = n bound both; the clamp keeps a caller's wrong offsets inside the rows.
+// per tile of MASK_TILE records the rows that hold its first and its last record (stage_device.hpp)
 __global__ void k_mask_tiles(const int64_t *__restrict__ rec_off, uint64_t rows, uint64_t n, uint64_t ntiles,
                              uint64_t *__restrict__ U, uint64_t *__restrict__ L) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ntiles) return;
-    const uint64_t base = t * MASK_TILE, last = std::min<uint64_t>(base + MASK_TILE, n) - 1;
-    U[t] = std::min<uint64_t>(std::max<uint64_t>(mask_count_le(rec_off, rows + 1, base), 1) - 1, rows - 1);
-    L[t] = std::min<uint64_t>(std::max<uint64_t>(mask_count_le(rec_off, rows + 1, last), 1) - 1, rows - 1);
+    rec_tile_bounds<MASK_TILE>(rec_off, rows, n, ntiles, U, L);
 }
 
 // n bytes of the value f4 repeats, at p (global memory, any alignment): every store naturally aligned and inside [p, p + n).
@@ -72,7 +57,7 @@ __device__ inline void mask_fill(uint8_t *p, uint64_t n, uint32_t f4) {
 //           by threads 0 .. 15 and 32 .. 47, the 16-byte words between 16 bytes per lane.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(MASK_THREADS) void k_mask_paint(const uint64_t *__restrict__ w, uint64_t n,
-                                                             const int64_t *__restrict__ rec_off, MaskRows R,
+                                                             const int64_t *__restrict__ rec_off, RowCut R,
                                                              const uint64_t *__restrict__ U, const uint64_t *__restrict__ L,
                                                              uint32_t f4, uint8_t *out) {
     __shared__ uint64_t s_row[MASK_TILE];
@@ -176,21 +161,21 @@ __global__ __launch_bounds__(MASK_THREADS) void k_mask_paint(const uint64_t *__r
     }
 }
 
-__global__ void k_mask_offsets(MaskRows R, int64_t *__restrict__ o) {
+__global__ void k_mask_offsets(RowCut R, int64_t *__restrict__ o) {
     const uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (h > R.rows) return;
-    o[h] = (int64_t)(R.off ? R.off[h] : R.uniform_len ? h * R.uniform_len : h ? R.len : 0);
+    if (h > R.n) return;
+    o[h] = (int64_t)row_begin(R, h);
 }
 
-uint64_t mask_tile_words(uint64_t n) { return 2 * ((n + MASK_TILE - 1) / MASK_TILE); }
+uint64_t mask_tile_words(uint64_t n) { return rec_tile_words(n, MASK_TILE); }
 
-hipError_t mask_paint(const acx_match_t *m, uint64_t n, const int64_t *rec_off, const MaskRows &R, uint8_t fill, uint64_t *tiles,
+hipError_t mask_paint(const acx_match_t *m, uint64_t n, const int64_t *rec_off, const RowCut &R, uint8_t fill, uint64_t *tiles,
                       uint8_t *out, hipStream_t st) {
-    if (!n || !R.rows || !R.len) return hipSuccess;
-    const uint64_t ntiles = (n + MASK_TILE - 1) / MASK_TILE;
+    if (!n || !R.n || !R.len) return hipSuccess;
+    const uint64_t ntiles = tiles_of(n, MASK_TILE);
     if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
     uint64_t *U = tiles, *L = tiles + ntiles;
-    hipLaunchKernelGGL(k_mask_tiles, dim3((uint32_t)((ntiles + 255) / 256)), dim3(256), 0, st, rec_off, R.rows, n, ntiles, U, L);
+    hipLaunchKernelGGL(k_mask_tiles, dim3((uint32_t)((ntiles + 255) / 256)), dim3(256), 0, st, rec_off, R.n, n, ntiles, U, L);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_mask_paint, dim3((uint32_t)ntiles), dim3(MASK_THREADS), 0, st, (const uint64_t *)m, n, rec_off, R,
@@ -198,9 +183,9 @@ hipError_t mask_paint(const acx_match_t *m, uint64_t n, const int64_t *rec_off, 
     return hipGetLastError();
 }
 
-hipError_t mask_offsets(const MaskRows &R, int64_t *o, hipStream_t st) {
-    if ((R.rows + 256) / 256 >= (1ull << 31)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mask_offsets, dim3((uint32_t)((R.rows + 256) / 256)), dim3(256), 0, st, R, o);
+hipError_t mask_offsets(const RowCut &R, int64_t *o, hipStream_t st) {
+    if ((R.n + 256) / 256 >= (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mask_offsets, dim3((uint32_t)((R.n + 256) / 256)), dim3(256), 0, st, R, o);
     return hipGetLastError();
 }
 

@@ -29,6 +29,7 @@
 #include <cstdint>
 
 #include "../../include/acx.h"
+#include "stage_device.hpp"
 
 namespace acx {
 
@@ -42,24 +43,15 @@ constexpr uint32_t MASK_THREADS = 256;
 constexpr uint32_t MASK_TILE = 1024;
 constexpr uint32_t MASK_LONG = 512;
 
-// The rows' places in `len` bytes: off != null (rows + 1 device offsets from 0 to len), uniform_len > 0 (row h begins at
-// h * uniform_len), or neither (one row of `len` bytes: rows = 1).
-struct MaskRows {
-    const uint64_t *off;
-    uint64_t uniform_len;
-    uint64_t rows;
-    uint64_t len;
-};
-
 // u64 words of scratch mask_paint needs for n records (two rows per tile)
 uint64_t mask_tile_words(uint64_t n);
-// out: `len` writable bytes of any alignment; m: n records; rec_off: R.rows + 1 entries from 0 to n (the caller's word: a
+// out: `len` writable bytes of any alignment; m: n records; rec_off: R.n + 1 entries from 0 to n (the caller's word: a
 // kernel reads records by them); tiles: mask_tile_words(n) words.  Offsets that do not rise, or pass len, paint less: every
-// store lies inside [0, len).  n == 0, R.rows == 0 or len == 0: nothing is launched.
-hipError_t mask_paint(const acx_match_t *m, uint64_t n, const int64_t *rec_off, const MaskRows &R, uint8_t fill, uint64_t *tiles,
+// store lies inside [0, len).  n == 0, R.n == 0 or len == 0: nothing is launched.
+hipError_t mask_paint(const acx_match_t *m, uint64_t n, const int64_t *rec_off, const RowCut &R, uint8_t fill, uint64_t *tiles,
                       uint8_t *out, hipStream_t st);
-// o[h] = where row h begins for h = 0 .. R.rows (R.rows + 1 int64 words, the last one len): the offsets a result carries
+// o[h] = where row h begins for h = 0 .. R.n (R.n + 1 int64 words, the last one len): the offsets a result carries
 // beside its bytes
-hipError_t mask_offsets(const MaskRows &R, int64_t *o, hipStream_t st);
+hipError_t mask_offsets(const RowCut &R, int64_t *o, hipStream_t st);
 
 } // namespace acx

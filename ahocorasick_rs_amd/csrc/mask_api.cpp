@@ -32,23 +32,23 @@ int check_flags(uint32_t flags) {
 }
 
 // The device stage on stream st: d_out becomes a copy of d_hay (or zeros: ACX_MASK_ZERO; or stays as it is: d_out == d_hay),
-// then the records' bytes are painted.  d_m: n records; d_counts: R.rows words that sum to n (check_sum: record_offsets,
+// then the records' bytes are painted.  d_m: n records; d_counts: R.n words that sum to n (check_sum: record_offsets,
 // behind the copy or the clear).  No record, no row or no byte: nothing beyond the copy or the clear.  *block: the stage's
 // temporaries, one block of the buffer cache -- the caller's to return, behind the stage's kernels.
-int mask_stage(int device, hipStream_t st, const uint8_t *d_hay, const acx::MaskRows &R, const acx_match_t *d_m, uint64_t n,
+int mask_stage(int device, hipStream_t st, const uint8_t *d_hay, const acx::RowCut &R, const acx_match_t *d_m, uint64_t n,
                const uint64_t *d_counts, bool check_sum, uint8_t fill, uint32_t flags, uint8_t *d_out, void **block) {
     if (R.len && d_out != d_hay) {
         if (flags & ACX_MASK_ZERO) HIPCHK(hipMemsetAsync(d_out, 0, R.len, st));
         else HIPCHK(hipMemcpyAsync(d_out, d_hay, R.len, hipMemcpyDeviceToDevice, st));
     }
-    if (!n || !R.rows || !R.len) return ACX_OK;
+    if (!n || !R.n || !R.len) return ACX_OK;
     // [rec_off: rows + 1][scan][tiles], every part 256-byte aligned
     Carver C;
-    const uint64_t o_rec = C.part(R.rows + 1), o_scan = C.part(replace_scan_words(R.rows)), o_tiles = C.part(acx::mask_tile_words(n));
+    const uint64_t o_rec = C.part(R.n + 1), o_scan = C.part(replace_scan_words(R.n)), o_tiles = C.part(acx::mask_tile_words(n));
     HIPCHK(g_bufs.get(block, C.bytes(), device));
     uint64_t *b = (uint64_t *)*block;
     int64_t *rec_off = (int64_t *)(b + o_rec);
-    if (int rc = record_offsets(d_counts, R.rows, n, check_sum, rec_off, b + o_scan, st)) return rc;
+    if (int rc = record_offsets(d_counts, R.n, n, check_sum, rec_off, b + o_scan, st)) return rc;
     HIPCHK(acx::mask_paint(d_m, n, rec_off, R, fill, b + o_tiles, d_out, st));
     return ACX_OK;
 }
@@ -59,7 +59,6 @@ int mask_stage(int device, hipStream_t st, const uint8_t *d_hay, const acx::Mask
 int run_mask(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_search, uint64_t len, const Segments &G,
              int overlapping, uint8_t fill, uint32_t flags, acx_masked_t **out) {
     *out = nullptr;
-    const bool segmented = rows_of(G).segmented;
     const uint64_t rows = rows_of(G).n;
     acx_masked_t *R = new_result<acx_masked_t>(a->device, true);
     if (!R) return ACX_ENOMEM;
@@ -76,7 +75,7 @@ int run_mask(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_se
     auto body = [&]() -> int {
         int rc;
         if ((rc = R->alloc()) != ACX_OK) return rc;
-        const acx::MaskRows MR{segmented ? G.offsets : nullptr, segmented ? G.uniform_len : 0, rows, len};
+        const acx::RowCut MR = row_cut(G, len);
         if (!rows) {
             HIPCHK(hipMemsetAsync(R->offsets, 0, 8, st));
         } else {
@@ -186,7 +185,7 @@ int acx_mask_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_offs
     return rows_call(d_out, [&](int device, void **block, void **) {
         const int span = device_offsets_span(d_offsets, n_hay, len);
         if (span != ACX_OK) return span;
-        const acx::MaskRows R{d_offsets, uniform_len, n_hay, len};
+        const acx::RowCut R{d_offsets, uniform_len, n_hay, len};
         return mask_stage(device, nullptr, (const uint8_t *)d_hay, R, d_records, n, d_counts, true, fill, flags, (uint8_t *)d_out, block);
     });
 }

@@ -111,36 +111,30 @@ hipError_t replace_scan(const acx_match_t *m, const uint64_t *roff, const uint64
 // ---------------------------------------------------------------------------
 // 2. where every replacement starts in the output, and every haystack's output bounds
 // ---------------------------------------------------------------------------
-__device__ inline uint64_t in_base(const RepSegs &S, uint64_t h) {
-    if (S.in_off) return S.in_off[h];
-    if (S.uniform_len) return h * S.uniform_len;
-    return h ? S.len : 0;
-}
-
 __global__ void k_rep_positions(const acx_match_t *__restrict__ m, uint64_t n, const int64_t *__restrict__ P, RepSegs S,
                                 uint64_t *o, uint64_t *out_off) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         uint64_t h = 0;
         if (S.first) { // the last haystack whose first match is at or before i (empty ones share their successor's)
-            uint64_t lo = 0, hi = S.n_hay + 1;
+            uint64_t lo = 0, hi = S.cut.n + 1;
             while (lo < hi) {
                 const uint64_t mid = (lo + hi) >> 1;
                 if (S.first[mid] <= i) lo = mid + 1; else hi = mid;
             }
             h = lo - 1;
         }
-        o[i] = in_base(S, h) + m[i].start + (uint64_t)P[i];
+        o[i] = row_begin(S.cut, h) + m[i].start + (uint64_t)P[i];
     }
-    if (i <= S.n_hay) {
+    if (i <= S.cut.n) {
         const uint64_t f = S.first ? S.first[i] : (i ? n : 0);
-        out_off[i] = in_base(S, i) + (uint64_t)P[f];
+        out_off[i] = row_begin(S.cut, i) + (uint64_t)P[f];
     }
 }
 
 hipError_t replace_positions(const acx_match_t *m, uint64_t n, const int64_t *P, const RepSegs &S, uint64_t *o,
                              uint64_t *out_off, hipStream_t st) {
-    const uint64_t threads = std::max(n, S.n_hay + 1);
+    const uint64_t threads = std::max(n, S.cut.n + 1);
     hipLaunchKernelGGL(k_rep_positions, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st, m, n, P, S, o, out_off);
     return hipGetLastError();
 }
@@ -157,33 +151,10 @@ hipError_t replace_positions(const acx_match_t *m, uint64_t n, const int64_t *P,
 // ---------------------------------------------------------------------------
 constexpr uint32_t RG_THREADS = 256, RG_TILE = 16384, RG_CHUNKS = RG_TILE / 16 / RG_THREADS, RG_WIN = 1024;
 
-__device__ inline uint64_t count_le(const uint64_t *o, uint64_t n, uint64_t x) { // entries <= x (o ascending)
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (o[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// per tile boundary t = 0 .. ntiles: U[t] = the replacements that begin at or before t * RG_TILE, L[t] = those that
-// begin before it (clamped to the output's end) -- tile t stages segments U[t] - 1 .. L[t + 1] - 1
+// the replacements that begin at or before, and before, every boundary of the output's tiles (stage_device.hpp)
 __global__ void k_rep_tiles(const uint64_t *__restrict__ o, uint64_t n, uint64_t total, uint64_t ntiles, uint64_t *U,
                             uint64_t *L) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t > ntiles) return;
-    const uint64_t x = std::min<uint64_t>(t * RG_TILE, total);
-    U[t] = count_le(o, n, x);
-    L[t] = x ? count_le(o, n, x - 1) : 0;
-}
-
-__device__ inline uint4 funnel16(uint4 lo, uint4 hi, uint32_t s) { // bytes s .. s + 15 of lo:hi
-    uint32_t v0 = lo.x, v1 = lo.y, v2 = lo.z, v3 = lo.w, v4 = hi.x, v5 = hi.y, v6 = hi.z, v7 = hi.w;
-    if (s & 8) { v0 = v2; v1 = v3; v2 = v4; v3 = v5; v4 = v6; v5 = v7; }
-    if (s & 4) { v0 = v1; v1 = v2; v2 = v3; v3 = v4; v4 = v5; }
-    const uint32_t sh = s & 3;
-    return make_uint4(__builtin_amdgcn_alignbyte(v1, v0, sh), __builtin_amdgcn_alignbyte(v2, v1, sh),
-                      __builtin_amdgcn_alignbyte(v3, v2, sh), __builtin_amdgcn_alignbyte(v4, v3, sh));
+    out_tile_bounds<RG_TILE>(o, n, total, ntiles, U, L);
 }
 
 // 16 bytes at base + pos (pos + 16 <= size); the two aligned loads only where both lie inside [base, base + size)
@@ -272,7 +243,7 @@ hipError_t replace_gather(const uint8_t *hay, uint64_t len, const acx_match_t *m
                           const int64_t *P, const uint8_t *blob, uint64_t blob_len, const uint64_t *roff, uint64_t *tiles,
                           uint8_t *out, uint64_t total, hipStream_t st) {
     if (!total) return hipSuccess;
-    const uint64_t ntiles = (total + RG_TILE - 1) / RG_TILE;
+    const uint64_t ntiles = tiles_of(total, RG_TILE);
     uint64_t *U = tiles, *L = tiles + ntiles + 1;
     hipLaunchKernelGGL(k_rep_tiles, dim3((uint32_t)((ntiles + 1 + 255) / 256)), dim3(256), 0, st, o, n, total, ntiles, U, L);
     hipError_t e = hipGetLastError();
@@ -282,6 +253,6 @@ hipError_t replace_gather(const uint8_t *hay, uint64_t len, const acx_match_t *m
     return hipGetLastError();
 }
 
-uint64_t replace_tile_words(uint64_t total) { return 2 * ((total + RG_TILE - 1) / RG_TILE + 1); }
+uint64_t replace_tile_words(uint64_t total) { return out_tile_words(total, RG_TILE); }
 
 } // namespace acx

@@ -6,7 +6,7 @@
 //   1. replace_scan     P[i] = sum_{j<i} d_j, d_j = |r[p_j]| - (e_j - s_j), P[n] = the total; the same two-launch scan
 //                       gives the first match of every haystack of a batch from the result's per-haystack counts
 //   2. replace_positions o[i] = (global start of match i) + P[i]: where replacement i begins in the output; out_off[h] =
-//                       in_off[h] + P[first match of h] for h = 0 .. n_hay (out_off[n_hay] = the output's length)
+//                       (where h begins) + P[first match of h] for h = 0 .. n_hay (out_off[n_hay] = the output's length)
 //   3. replace_gather   output side: a workgroup per 16 KiB output tile, 16-byte stores; every chunk is taken from the
 //                       replacement blob or from the haystack at its segment's shift (input = output - P[j + 1])
 #pragma once
@@ -16,17 +16,14 @@
 #include <cstdint>
 
 #include "../../include/acx.h"
+#include "stage_device.hpp"
 
 namespace acx {
 
-// The input's haystacks: in_off != null (n_hay + 1 device offsets from 0), uniform_len > 0 (haystack h starts at
-// h * uniform_len), or neither (one haystack of `len` bytes: n_hay = 1).  first != null: the first match of every
-// haystack (n_hay + 1 entries, first[n_hay] = n); null: one haystack.
+// The input's haystacks (cut: stage_device.hpp).  first != null: the first match of every haystack (cut.n + 1 entries,
+// first[cut.n] = n); null: one haystack.
 struct RepSegs {
-    const uint64_t *in_off;
-    uint64_t uniform_len;
-    uint64_t n_hay;
-    uint64_t len;
+    RowCut cut;
     const uint64_t *first;
 };
 

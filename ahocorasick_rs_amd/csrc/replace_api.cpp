@@ -61,7 +61,7 @@ int run_replace(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d
             HIPCHK(replace_scan(nullptr, nullptr, r->d_counts, n_hay, (int64_t *)first, temp, st));
         }
         HIPCHK(replace_scan(r->d_matches, d_roff, nullptr, n, P, temp, st));
-        const RepSegs S{segmented ? G.offsets : nullptr, G.uniform_len, n_hay, len, first};
+        const RepSegs S{row_cut(G, len), first};
         HIPCHK(replace_positions(r->d_matches, n, P, S, o, out_off, st));
         R->offsets.resize(n_hay + 1);
         HIPCHK(hipMemcpyAsync(R->offsets.data(), out_off, (n_hay + 1) * 8, hipMemcpyDeviceToHost, st));

@@ -6,6 +6,7 @@
 #include <initializer_list>
 
 #include "find_pipeline.hpp"
+#include "stage_device.hpp"
 
 namespace acxh ACX_HIDDEN {
 
@@ -100,6 +101,11 @@ struct Rows {
 inline Rows rows_of(const Segments &G) {
     const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
     return Rows{segmented, segmented ? G.n_hay : 1};
+}
+// ... and how they cut the `len` bytes of the find (stage_device.hpp)
+inline acx::RowCut row_cut(const Segments &G, uint64_t len) {
+    const Rows r = rows_of(G);
+    return acx::RowCut{r.segmented ? G.offsets : nullptr, r.segmented ? G.uniform_len : 0, r.n, len};
 }
 
 // Where every row's records begin: the scan of d_counts (rows words, rows > 0) into rec_off (rows + 1 words) on st;

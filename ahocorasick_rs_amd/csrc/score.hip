@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "score.hpp"
+#include "stage_device.hpp"
 
 namespace acx {
 
@@ -15,25 +16,10 @@ constexpr uint32_t SC_WORDS = SCORE_TILE / 32;          // words of the bitmap w
 static_assert(SC_IPT * SCORE_THREADS == SCORE_TILE && SC_IPT == 8, "a thread reads its 8 weights as two 16-byte LDS loads");
 static_assert(SCORE_THREADS % 64 == 0 && SC_WORDS + 1 <= SCORE_THREADS, "whole waves; one thread clears one bitmap word");
 
-__device__ inline uint64_t score_count_le(const int64_t *o, uint64_t n, uint64_t x) { // entries <= x (o ascending)
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if ((uint64_t)o[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// per tile t: U[t] = the row that holds record t * SCORE_TILE, L[t] = the row that holds the tile's last record -- the LAST
-// row that begins at or before the record (of several rows with one start all but the last are empty).  rec_off[0] = 0 and
-// rec_off[rows] = n bound both; the clamp keeps a caller's wrong offsets inside the score.
+// per tile of SCORE_TILE records the rows that hold its first and its last record (stage_device.hpp)
 __global__ void k_score_tiles(const int64_t *__restrict__ rec_off, uint64_t rows, uint64_t n, uint64_t ntiles,
                               uint64_t *__restrict__ U, uint64_t *__restrict__ L) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ntiles) return;
-    const uint64_t base = t * SCORE_TILE, last = std::min<uint64_t>(base + SCORE_TILE, n) - 1;
-    U[t] = std::min<uint64_t>(std::max<uint64_t>(score_count_le(rec_off, rows + 1, base), 1) - 1, rows - 1);
-    L[t] = std::min<uint64_t>(std::max<uint64_t>(score_count_le(rec_off, rows + 1, last), 1) - 1, rows - 1);
+    rec_tile_bounds<SCORE_TILE>(rec_off, rows, n, ntiles, U, L);
 }
 
 // ---------------------------------------------------------------------------
@@ -149,14 +135,14 @@ __global__ void k_score_flags(const int64_t *__restrict__ score, uint64_t rows, 
     if (h < rows) flag[h] = score[h] >= min_score ? 1 : 0;
 }
 
-uint64_t score_tile_words(uint64_t n) { return 2 * ((n + SCORE_TILE - 1) / SCORE_TILE); }
+uint64_t score_tile_words(uint64_t n) { return rec_tile_words(n, SCORE_TILE); }
 
 hipError_t score_rows(const acx_match_t *m, uint64_t n, const int64_t *rec_off, uint64_t rows, const int32_t *weights,
                       uint64_t n_patterns, uint64_t *tiles, int64_t *score, hipStream_t st) {
     if (!rows) return hipSuccess;
     hipError_t e = hipMemsetAsync(score, 0, rows * 8, st);
     if (e != hipSuccess || !n) return e;
-    const uint64_t ntiles = (n + SCORE_TILE - 1) / SCORE_TILE;
+    const uint64_t ntiles = tiles_of(n, SCORE_TILE);
     if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
     uint64_t *U = tiles, *L = tiles + ntiles;
     hipLaunchKernelGGL(k_score_tiles, dim3((uint32_t)((ntiles + 255) / 256)), dim3(256), 0, st, rec_off, rows, n, ntiles, U, L);

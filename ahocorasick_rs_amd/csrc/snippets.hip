@@ -9,31 +9,13 @@
 
 namespace acx {
 
-// entries <= x of o[0 .. n) (o ascending)
-__device__ inline uint64_t snip_count_le(const int64_t *o, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if ((uint64_t)o[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ inline uint64_t snip_row_begin(const SnipRows &R, uint64_t h) {
-    uint64_t b;
-    if (R.in_off) b = R.in_off[h];
-    else if (R.uniform_len) b = h * R.uniform_len;
-    else b = h ? R.len : 0;
-    return std::min(b, R.len); // (offsets between the first and the last are the caller's word: no byte is read beyond len)
-}
-
 __device__ inline bool snip_continuation(uint8_t b) { return (b & 0xC0) == 0x80; }
 
 // ---------------------------------------------------------------------------
 // 1. one thread per record: the definition
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_snip_sizes(const acx_match_t *__restrict__ m, uint64_t n,
-                                                    const int64_t *__restrict__ rec_off, SnipRows R,
+                                                    const int64_t *__restrict__ rec_off, RowCut R,
                                                     const uint8_t *__restrict__ hay, uint64_t context, uint32_t flags,
                                                     uint64_t *__restrict__ seg_len, uint64_t *__restrict__ src,
                                                     int64_t *__restrict__ lead, int64_t *__restrict__ pattern) {
@@ -44,16 +26,17 @@ __global__ __launch_bounds__(256) void k_snip_sizes(const acx_match_t *__restric
     __shared__ uint64_t s_h[2];
     const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x, i = i0 + threadIdx.x;
     if (threadIdx.x == 0) {
-        const uint64_t a = snip_count_le(rec_off, R.n + 1, i0), h_first = std::min(a ? a - 1 : 0, R.n - 1);
-        const uint64_t b = h_first + snip_count_le(rec_off + h_first, R.n + 1 - h_first, std::min(i0 + blockDim.x - 1, n - 1));
+        const uint64_t a = count_le(rec_off, R.n + 1, i0), h_first = std::min(a ? a - 1 : 0, R.n - 1);
+        const uint64_t b = h_first + count_le(rec_off + h_first, R.n + 1 - h_first, std::min(i0 + blockDim.x - 1, n - 1));
         s_h[0] = h_first;
         s_h[1] = std::min(b > h_first ? b - 1 : h_first, R.n - 1);
     }
     __syncthreads();
     if (i >= n) return;
-    const uint64_t h0 = s_h[0], in_tile = snip_count_le(rec_off + h0, s_h[1] - h0 + 1, i);
+    const uint64_t h0 = s_h[0], in_tile = count_le(rec_off + h0, s_h[1] - h0 + 1, i);
     const uint64_t h = h0 + (in_tile ? in_tile - 1 : 0);
-    const uint64_t rb = snip_row_begin(R, h), re = std::max(snip_row_begin(R, h + 1), rb), L = re - rb;
+    // (offsets between the first and the last are the caller's word: no byte is read beyond len)
+    const uint64_t rb = std::min(row_begin(R, h), R.len), re = std::max(std::min(row_begin(R, h + 1), R.len), rb), L = re - rb;
     const uint64_t s = std::min<uint64_t>(m[i].start, L), e = std::min(std::max<uint64_t>(m[i].end, s), L);
     uint64_t lo = s - std::min(s, context), hi = e + std::min(context, L - e);
     if (flags & SNIP_UTF8) {
@@ -71,7 +54,7 @@ __global__ __launch_bounds__(256) void k_snip_sizes(const acx_match_t *__restric
     pattern[i] = (int64_t)m[i].pattern;
 }
 
-hipError_t snip_sizes(const acx_match_t *m, uint64_t n, const int64_t *rec_off, const SnipRows &R, const uint8_t *hay,
+hipError_t snip_sizes(const acx_match_t *m, uint64_t n, const int64_t *rec_off, const RowCut &R, const uint8_t *hay,
                       uint64_t context, uint32_t flags, uint64_t *seg_len, uint64_t *src, int64_t *lead, int64_t *pattern,
                       hipStream_t st) {
     if (!n || !R.n) return hipSuccess;
@@ -82,18 +65,11 @@ hipError_t snip_sizes(const acx_match_t *m, uint64_t n, const int64_t *rec_off, 
 }
 
 // ---------------------------------------------------------------------------
-// 2. per tile boundary t = 0 .. ntiles: U[t] = the segments that begin at or before t * SNIP_TILE, L[t] = those that begin
-//    before it (clamped to the output's end) -- tile t stages segments U[t] - 1 .. L[t + 1] - 1: from the last one that
-//    begins at or before the tile (it covers the tile's first byte: of several segments with one start, all but the last are
-//    empty) to the last one that begins inside it.
+// 2. the segments that begin at or before, and before, every boundary of the output's tiles (stage_device.hpp)
 // ---------------------------------------------------------------------------
 __global__ void k_snip_tiles(const int64_t *__restrict__ offsets, uint64_t n, uint64_t total, uint64_t ntiles, uint64_t *U,
                              uint64_t *L) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t > ntiles) return;
-    const uint64_t x = std::min<uint64_t>(t * SNIP_TILE, total);
-    U[t] = snip_count_le(offsets, n, x);
-    L[t] = x ? snip_count_le(offsets, n, x - 1) : 0;
+    out_tile_bounds<SNIP_TILE>(offsets, n, total, ntiles, U, L);
 }
 
 // ---------------------------------------------------------------------------
@@ -211,12 +187,12 @@ __global__ __launch_bounds__(SNIP_THREADS) void k_snip_gather(const uint8_t *__r
     }
 }
 
-uint64_t snip_tile_words(uint64_t total) { return 2 * ((total + SNIP_TILE - 1) / SNIP_TILE + 1); }
+uint64_t snip_tile_words(uint64_t total) { return out_tile_words(total, SNIP_TILE); }
 
 hipError_t snip_gather(const uint8_t *hay, uint64_t len, const int64_t *offsets, const uint64_t *src, uint64_t n, uint64_t *tiles,
                        uint8_t *out, uint64_t total, hipStream_t st) {
     if (!total || !n) return hipSuccess;
-    const uint64_t ntiles = (total + SNIP_TILE - 1) / SNIP_TILE;
+    const uint64_t ntiles = tiles_of(total, SNIP_TILE);
     if (ntiles >= (1ull << 31)) return hipErrorInvalidValue;
     uint64_t *U = tiles, *L = tiles + ntiles + 1;
     hipLaunchKernelGGL(k_snip_tiles, dim3((uint32_t)((ntiles + 1 + 255) / 256)), dim3(256), 0, st, offsets, n, total, ntiles, U, L);

@@ -31,6 +31,7 @@
 #include <cstdint>
 
 #include "../../include/acx.h"
+#include "stage_device.hpp"
 
 namespace acx {
 
@@ -45,18 +46,10 @@ constexpr uint32_t SNIP_WIN = 512;
 
 constexpr uint32_t SNIP_UTF8 = 1; // ACX_SNIPPET_UTF8: the ends move inward to a character boundary
 
-// The input's rows: in_off != null (n + 1 device offsets from 0 to len), uniform_len > 0 (row h starts at h * uniform_len),
-// or neither (one row of `len` bytes: n = 1).  A row's begin and end are clamped to len before a byte is read by them.
-struct SnipRows {
-    const uint64_t *in_off;
-    uint64_t uniform_len;
-    uint64_t n;
-    uint64_t len;
-};
-
+// R: the input's rows (stage_device.hpp); a row's begin and end are clamped to len before a byte is read by them.
 // m: n records (0 < n < 2^39); rec_off: R.n + 1 entries from 0 to n (R.n > 0); seg_len, src: n words each; lead, pattern: n
 // words each.
-hipError_t snip_sizes(const acx_match_t *m, uint64_t n, const int64_t *rec_off, const SnipRows &R, const uint8_t *hay,
+hipError_t snip_sizes(const acx_match_t *m, uint64_t n, const int64_t *rec_off, const RowCut &R, const uint8_t *hay,
                       uint64_t context, uint32_t flags, uint64_t *seg_len, uint64_t *src, int64_t *lead, int64_t *pattern,
                       hipStream_t st);
 // u64 words of scratch snip_gather needs for an output of `total` bytes (the segments of every output tile)

@@ -63,7 +63,7 @@ struct Stage {
 // The stage up to the point where the output's size is known (n > 0, R.n > 0): where the rows' records begin, every
 // record's cut, the scan of the lengths, and the 8 bytes that cross the bus.  d_counts: R.n words that sum to n (check_sum:
 // record_offsets).  offsets (n + 1), pattern, lead (n each): where they are wanted, or null: parts of the block.
-int stage_sizes(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, const uint64_t *d_counts, const acx::SnipRows &R,
+int stage_sizes(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, const uint64_t *d_counts, const acx::RowCut &R,
                 bool check_sum, const uint8_t *d_hay, uint64_t context, uint32_t flags, int64_t *offsets, int64_t *pattern,
                 int64_t *lead, Stage *G) {
     if (n >= (1ull << 39)) return fail(ACX_ETOOBIG, "too many records to be cut in one call");
@@ -130,7 +130,7 @@ int run_snippets(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *
         const uint64_t *d_counts = nullptr;
         if ((rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
         const uint64_t rows = rows_of(G).n;
-        const acx::SnipRows SR{segmented ? G.offsets : nullptr, segmented ? G.uniform_len : 0, rows, len};
+        const acx::RowCut SR = row_cut(G, len);
         if ((rc = stage_sizes(a->device, st, r->d_matches, n, d_counts, SR, false, d_hay, context, flags, nullptr, nullptr, nullptr,
                               &S)) != ACX_OK)
             return rc;
@@ -269,7 +269,7 @@ int acx_snippets_rows_device(const acx_match_t *d_records, uint64_t n, const uin
         }
         const int span = device_offsets_span(d_offsets, n_hay, len);
         if (span != ACX_OK) return span;
-        const acx::SnipRows SR{d_offsets, uniform_len, n_hay, len};
+        const acx::RowCut SR{d_offsets, uniform_len, n_hay, len};
         Stage S;
         const int sized = stage_sizes(device, nullptr, d_records, n, d_counts, SR, true, (const uint8_t *)d_hay, context, flags,
                                       d_out_offsets, d_pattern, d_lead, &S);

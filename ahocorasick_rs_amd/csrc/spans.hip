@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "spans.hpp"
+#include "stage_device.hpp"
 
 namespace acx {
 
@@ -22,23 +23,6 @@ constexpr uint64_t SP_PIECE = (uint64_t)SPANS_CARRY_THREADS * SPANS_CARRY_PER; /
 static_assert(SP_IPT * SPANS_THREADS == SPANS_TILE && SP_IPT == 4, "a thread reads its 4 marks as one 16-byte LDS load");
 static_assert(SPANS_THREADS % 64 == 0 && SPANS_CARRY_THREADS % 64 == 0, "whole waves");
 static_assert((SPANS_CARRY_THREADS & (SPANS_CARRY_THREADS - 1)) == 0, "the carry's doubling steps");
-
-__device__ inline uint64_t span_count_le(const int64_t *o, uint64_t n, uint64_t x) { // entries <= x (o ascending)
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if ((uint64_t)o[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-__device__ inline uint64_t span_count_lt(const int64_t *o, uint64_t n, uint64_t x) { // entries < x
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if ((uint64_t)o[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 __device__ inline uint64_t span_after(uint64_t a, uint32_t pass, uint64_t x) { return std::min(a, pass ? x : SP_INF); }
 // does a live record that ends at `end` close its span, `next` being the smallest live start behind it in its row
@@ -61,9 +45,9 @@ __global__ __launch_bounds__(SPANS_THREADS) void k_span_tiles(const uint64_t *__
     const uint64_t t = blockIdx.x, base = t * SPANS_TILE;
     const uint32_t cnt = (uint32_t)std::min<uint64_t>(SPANS_TILE, n - base);
     if (tid == 0) {
-        const uint64_t lo = std::min(span_count_lt(rec_off, rows + 1, base), rows);
-        const uint64_t up = std::min(span_count_le(rec_off, rows + 1, base), rows); // the first entry beyond `base`
-        const uint64_t hi = std::min(span_count_le(rec_off, rows + 1, base + cnt - 1), rows);
+        const uint64_t lo = std::min(count_lt(rec_off, rows + 1, base), rows);
+        const uint64_t up = std::min(count_le(rec_off, rows + 1, base), rows); // the first entry beyond `base`
+        const uint64_t hi = std::min(count_le(rec_off, rows + 1, base + cnt - 1), rows);
         const uint64_t row_end = (uint64_t)rec_off[up];
         const uint32_t stop = row_end > base ? (uint32_t)std::min<uint64_t>(row_end - base, cnt) : cnt;
         LO[t] = lo;

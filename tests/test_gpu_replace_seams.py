@@ -8,7 +8,7 @@ tests with it.  The expected output is always built without the code under test:
 bytes for a case-insensitive handle) spliced by plain Python / numpy, per haystack.
 
 What enters which branch (the constants as they stand: RS_ITEMS = 2 048, RG_TILE = 16 384, RG_WIN = 1 024):
-  in_base(): uniform_len / in_off      test_device_batch_uniform / test_device_batch_ragged (n_hay = 200 / 13)
+  row_begin(): uniform_len / off       test_device_batch_uniform / test_device_batch_ragged (n_hay = 200 / 13)
   k_rep_positions' search over S.first the same two, and test_counts_scan_beyond_one_level (n_hay > RS_ITEMS: the counts
                                        scan takes two levels)
   scan_level, three levels             test_three_scan_levels (the oracle's row count is asserted: RS_ITEMS^2 + 1 and beyond)
