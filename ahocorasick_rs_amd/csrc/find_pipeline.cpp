@@ -84,10 +84,10 @@ int expand_copies(acx_automaton *a, Ctx *x, acx_result *r, bool segmented) {
     if (hipError_t e = g_bufs.get((void **)&k, (n + 1) * 8, a->device); e != hipSuccess) return done(hipfail(e, "expand_copies"));
     if (hipError_t e = g_bufs.get((void **)&offs, (n + 1) * 8, a->device); e != hipSuccess) return done(hipfail(e, "expand_copies"));
     hipError_t e = copy_runs(r->d_matches, n, a->d_xcnt, temp, tb, k, offs, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(w.h_pinned + 8, offs + n, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(w.h_pinned + PIN_EXPANDED, offs + n, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return done(hipfail(e, "expand_copies"));
-    const uint64_t total = w.h_pinned[8];
+    const uint64_t total = w.h_pinned[PIN_EXPANDED];
     if (total == n) return done(ACX_OK); // (no occurrence of a string with copies)
     if ((e = g_bufs.get((void **)&out, total * sizeof(acx_match_t), a->device)) != hipSuccess) return done(hipfail(e, "expand_copies"));
     e = expand_copies_write(r->d_matches, n, offs, a->d_xoff, a->d_xids, out, total, st);
@@ -123,7 +123,7 @@ int expand_copies_host(const acx_automaton *a, acx_match_t **m, uint64_t *n) {
 
 namespace {
 int run_chunked(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, int overlapping, int codepoints,
-                acx_result **out, bool wait, uint64_t piece, int depth);
+                acx_result **out, uint64_t piece, int depth);
 int run_batch_split(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping,
                     int codepoints, acx_result **out, int depth);
 } // namespace
@@ -140,10 +140,9 @@ int run_find(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const
     if (!x) return fail(ACX_EDEVICE, "could not create a stream for the call");
     settle_post_profile(a, x);
     hipStream_t st = x->stream;
-    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
-    acx_result *r = new (std::nothrow) acx_result();
+    const bool segmented = is_segmented(G);
+    acx_result *r = new (std::nothrow) acx_result(a->device);
     if (!r) return fail(ACX_ENOMEM, "out of memory");
-    r->device = a->device;
     r->n_hay = segmented ? G.n_hay : 0;
     FindCall c{a, x, d_hay, len, G, overlapping != 0, codepoints != 0, segmented, r,
                overlapping ? 0 : a->host.match_kind};
@@ -204,7 +203,7 @@ int run_find(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const
         if (segmented && depth < 40) return run_batch_split(a, x, d_hay, len, G, overlapping, codepoints, out, depth + 1);
         if (segmented || depth >= 40 || piece <= 2 * m + 16)
             return fail(ACX_ETOOBIG, "more than 2^32 occurrences");
-        return run_chunked(a, x, d_hay, len, overlapping, codepoints, out, wait, piece, depth + 1);
+        return run_chunked(a, x, d_hay, len, overlapping, codepoints, out, piece, depth + 1);
     }
     *out = r;
     return ACX_OK;
@@ -243,9 +242,9 @@ int run_batch_split(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len
     if (G.uniform_len) {
         cut = half * G.uniform_len;
     } else {
-        HIPCHK(hipMemcpyAsync(w.h_pinned + 8, G.offsets + half, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(w.h_pinned + PIN_SPLIT_CUT, G.offsets + half, 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        cut = w.h_pinned[8];
+        cut = w.h_pinned[PIN_SPLIT_CUT];
         HIPCHK(g_bufs.get((void **)&reb, (n - half + 1) * 8, a->device));
         hipError_t e = rebase_offsets(reb, G.offsets + half, n - half + 1, cut, st);
         if (e != hipSuccess) { g_bufs.put(reb, a->device); return hipfail(e, "rebase_offsets"); }
@@ -258,10 +257,9 @@ int run_batch_split(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len
     };
     int rc = part(d_hay, cut, G.offsets, half, &ra);
     if (rc == ACX_OK) rc = part(d_hay + cut, len - cut, reb, n - half, &rb);
-    acx_result *r = rc == ACX_OK ? new (std::nothrow) acx_result() : nullptr;
+    acx_result *r = rc == ACX_OK ? new (std::nothrow) acx_result(a->device) : nullptr;
     if (rc == ACX_OK && !r) rc = fail(ACX_ENOMEM, "out of memory");
     if (rc == ACX_OK) {
-        r->device = a->device;
         r->n_hay = n;
         r->n = ra->n + rb->n;
         hipError_t e = g_bufs.get((void **)&r->d_counts, n * 8, a->device);
@@ -292,7 +290,7 @@ int run_batch_split(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len
 //                    it, so the scan stops there, and nothing the truncated window hides beats what it shows.
 // Code points (str API): the pieces run on byte offsets, the conversion runs once over the whole result.
 int run_chunked(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, int overlapping, int codepoints,
-                acx_result **out, bool wait, uint64_t piece, int depth) {
+                acx_result **out, uint64_t piece, int depth) {
     *out = nullptr;
     hipStream_t st = x->stream;
     Workspace &w = x->ws;
@@ -305,7 +303,7 @@ int run_chunked(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, in
     FindOpts piece_opts; // (a piece waits for its device work: its matches are cut and copied here)
     piece_opts.wait = true;
     piece_opts.depth = depth;
-    uint64_t *cut = w.summary + 12; // (two device words of the context's scratch)
+    uint64_t *cut = w.summary + SCR_RANGE_CUT; // (two device words of the context's scratch)
     for (uint64_t lo = 0; lo < len;) {
         const uint64_t hi = std::min(len, lo + piece);
         const bool last = hi == len;
@@ -323,11 +321,11 @@ int run_chunked(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, in
             // end); non-overlapping: the matches that start at or behind hi to the next one (a suffix: ordered by start)
             hipError_t e = overlapping ? cut_point(r->d_matches, n, true, a0, lo + 1, cut, st)
                                        : cut_point(r->d_matches, n, false, a0, hi, cut, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(w.h_pinned + 8, cut, 16, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(w.h_pinned + PIN_RANGE_CUT, cut, 16, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) { acx_free_result(r); drop(); return hipfail(e, "cut of a byte range"); }
-            if (overlapping) first = w.h_pinned[8];
-            else { n = w.h_pinned[8]; last_end = w.h_pinned[9]; }
+            if (overlapping) first = w.h_pinned[PIN_RANGE_CUT];
+            else { n = w.h_pinned[PIN_RANGE_CUT]; last_end = w.h_pinned[PIN_RANGE_CUT + 1]; }
         } else if (n && !overlapping) {
             last_end = len; // (the last range: nothing follows)
         }
@@ -340,9 +338,8 @@ int run_chunked(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, in
         if (!overlapping) carry = std::max(std::max(carry, hi), last_end);
         lo = hi;
     }
-    acx_result *r = new (std::nothrow) acx_result();
+    acx_result *r = new (std::nothrow) acx_result(a->device);
     if (!r) { drop(); return fail(ACX_ENOMEM, "out of memory"); }
-    r->device = a->device;
     r->n = total;
     auto body = [&]() -> int {
         if (!total) return ACX_OK;
@@ -367,7 +364,6 @@ int run_chunked(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, in
     drop();
     if (rc == ACX_OK && e != hipSuccess) rc = hipfail(e, "a call in byte ranges");
     if (rc != ACX_OK) { acx_free_result(r); return rc; }
-    (void)wait; // (synchronised either way)
     *out = r;
     return ACX_OK;
 }

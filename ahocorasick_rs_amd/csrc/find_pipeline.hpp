@@ -3,7 +3,8 @@
 #include "workspace.hpp"
 
 struct ACX_HIDDEN acx_result {
-    int device = 0;
+    explicit acx_result(int device_) : device(device_) {} // an empty result on that device
+    int device;
     acx_match_t *d_matches = nullptr;
     uint64_t n = 0;
     uint64_t *d_counts = nullptr;
@@ -19,6 +20,8 @@ namespace acxh ACX_HIDDEN {
 int check_overlapping(const acx_automaton *a);
 // how a device entry point's byte stream is cut into haystacks: uniform_len, or n_hay + 1 device offsets, or one haystack
 int make_segments(const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len, uint64_t len, Segments *G);
+// ... a batch (offsets or a row length), not one haystack
+inline bool is_segmented(const Segments &G) { return G.uniform_len != 0 || G.offsets != nullptr; }
 
 struct FindOpts {
     bool allow_small = true;  // K0 may take the call (a small haystack)

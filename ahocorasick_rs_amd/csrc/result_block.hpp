@@ -99,7 +99,7 @@ struct Rows {
     uint64_t n;
 };
 inline Rows rows_of(const Segments &G) {
-    const bool segmented = G.uniform_len != 0 || G.offsets != nullptr;
+    const bool segmented = is_segmented(G);
     return Rows{segmented, segmented ? G.n_hay : 1};
 }
 // ... and how they cut the `len` bytes of the find (stage_device.hpp)

@@ -44,24 +44,29 @@ bool small_ok(const acx_automaton *a, uint64_t len) {
            (len <= SMALL_MAX_LEN || (len <= SMALL_PF_MAX_LEN && small_prefilter_ok(a->dev)));
 }
 
-// Wait until a kernel has published the line that carries `seq` at pinned word `at` (kernels.hpp, k0_line_check: one
-// 64-byte line, one store instruction, [0] seq, [1 .. 6] payload, [7] seq ^ check(payload)) and take a COPY of it: the line
-// is complete when its first word carries the number and its last word agrees with the six in between AS READ HERE --
-// nothing is read twice, and nothing beside the line is read at all (separate device writes to host memory arrive in no
-// particular order).  The wake-up of a blocking stream synchronisation costs 10-20 us; polling costs one PCIe round trip.
+namespace {
+// One reading of the polled line at p (kernels.hpp, k0_line_check: one 64-byte line, one store instruction, [0] seq, [1 .. 6]
+// payload, [7] seq ^ check(payload)) into a COPY: the line is complete when its first word carries the number and its last
+// word agrees with the six in between AS READ HERE -- nothing is read twice, and nothing beside the line is read at all
+// (separate device writes to host memory arrive in no particular order).
+inline bool read_line(volatile const uint64_t *p, uint64_t seq, uint64_t line[8]) {
+    if (p[0] != seq) return false;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (uint32_t i = 1; i < 8; i++) line[i] = p[i];
+    return line[7] == (seq ^ k0_line_check(line + 1));
+}
+} // namespace
+
+// Wait until a kernel has published the line that carries `seq` at pinned word `at` and take a verified copy of it
+// (read_line).  The wake-up of a blocking stream synchronisation costs 10-20 us; polling costs one PCIe round trip.
 // Falls back to the stream after a few milliseconds.
 int wait_line(Ctx *c, uint32_t at, uint64_t seq, uint64_t line[8], const char *what) {
     volatile uint64_t *p = c->ws.h_pinned + at;
-    auto complete = [&]() -> bool {
-        if (p[0] != seq) return false;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        for (uint32_t i = 1; i < 8; i++) line[i] = p[i];
-        return line[7] == (seq ^ k0_line_check(line + 1));
-    };
     // (the fallback synchronises the context's own stream whoever writes the line -- the resident K0 writes it from its own
     // stream, Resident::stream: which stream to wait for is decided here, and here only)
     hipError_t e = hipSuccess;
-    const bool arrived = poll_until(complete, 1023, std::chrono::milliseconds(8), [&] { e = hipStreamSynchronize(c->stream); });
+    const bool arrived = poll_until([&] { return read_line(p, seq, line); }, 1023, std::chrono::milliseconds(8),
+                                    [&] { e = hipStreamSynchronize(c->stream); });
     if (e != hipSuccess) return hipfail(e, "hipStreamSynchronize(c->stream)");
     if (!arrived) return fail(ACX_EDEVICE, what);
     line[0] = seq;
@@ -80,6 +85,28 @@ int take_more_lines(Ctx *c, uint64_t seq, uint64_t n) {
     return ACX_OK;
 }
 
+namespace {
+// a small call was answered by K0, with n matches
+void small_call_answered(acx_automaton *a, uint64_t n, uint64_t *n_out, bool *done) {
+    *n_out = n;
+    *done = true;
+    std::lock_guard<std::mutex> lk(a->prof_mu);
+    a->profile.small_calls++;
+    a->path[7]++;
+}
+// The first result line of a polled K0 call has been taken (a verified copy): kept for take_small_matches, and -- unless
+// the call was too dense for K0 (*done stays false) -- the lines behind it are taken too.
+int first_line_taken(acx_automaton *a, Ctx *c, uint64_t seq, const uint64_t line[K0_LINE_WORDS], uint64_t *n_out, bool *done) {
+    for (uint32_t i = 1; i < K0_LINE_WORDS - 1; i++) c->ws.h_lines[0][i] = line[i]; // (what the caller unpacks the matches from)
+    const uint64_t w1 = line[1]; // matches | too dense << 32 | hash of pin_out << 33
+    if (((w1 >> 32) & 1u) != 0) return ACX_OK;
+    int rc = take_more_lines(c, seq, w1 & 0xFFFFFFFFull);
+    if (rc) return rc;
+    small_call_answered(a, w1 & 0xFFFFFFFFull, n_out, done);
+    return ACX_OK;
+}
+} // namespace
+
 // One K0 launch + one sync.  hay / out: anything the device can address (HBM or pinned host);
 // out holds SMALL_MAX_OCC records.  *done = false: too many occurrences, use the general path.
 // poll: hay and out are host memory the kernel reads / writes in place: wait for the number the kernel publishes
@@ -93,33 +120,17 @@ int run_small(acx_automaton *a, Ctx *c, const uint8_t *hay, uint64_t len, int ov
     const int key_mode = overlapping ? 0 : a->host.match_kind;
     const uint64_t seq = poll ? ++c->small_seq : 0;
     HIPCHK(launch_small(view(a, overlapping != 0), hay, (uint32_t)len, key_mode, overlapping != 0, codepoints != 0, out,
-                        seq ? w.h_pinned + PIN_K0 : w.h_pinned + 8, seq, c->stream, !(overlapping && a->expand_ov)));
+                        seq ? w.h_pinned + PIN_K0 : w.h_pinned + PIN_K0_COUNT, seq, c->stream, !(overlapping && a->expand_ov)));
     if (seq) {
         // the result line (kernels.hpp): complete when its first word carries this call's number and its last word
         // agrees with the six in between as read (wait_line: a copy is checked and used)
         uint64_t line[K0_LINE_WORDS];
         int rc = wait_line(c, PIN_K0, seq, line, "K0 did not publish its result");
         if (rc) return rc;
-        for (uint32_t i = 1; i < K0_LINE_WORDS - 1; i++) w.h_lines[0][i] = line[i]; // (what the caller unpacks the matches from)
-        const uint64_t w1 = line[1]; // matches | too dense << 32 | hash of pin_out << 33
-        if (((w1 >> 32) & 1u) == 0) {
-            if ((rc = take_more_lines(c, seq, w1 & 0xFFFFFFFFull)) != ACX_OK) return rc;
-            *n_out = w1 & 0xFFFFFFFFull;
-            *done = true;
-            std::lock_guard<std::mutex> lk(a->prof_mu);
-            a->profile.small_calls++;
-            a->path[7]++;
-        }
-        return ACX_OK;
+        return first_line_taken(a, c, seq, line, n_out, done);
     }
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (w.h_pinned[9] == 0) {
-        *n_out = w.h_pinned[8];
-        *done = true;
-        std::lock_guard<std::mutex> lk(a->prof_mu);
-        a->profile.small_calls++;
-        a->path[7]++;
-    }
+    if (w.h_pinned[PIN_K0_DENSE] == 0) small_call_answered(a, w.h_pinned[PIN_K0_COUNT], n_out, done);
     return ACX_OK;
 }
 
@@ -200,12 +211,7 @@ int run_resident(acx_automaton *a, Ctx *c, const uint8_t *hay, uint64_t len, int
     // more, and a call the kernel did not take is the first call of the next launch
     volatile uint64_t *p = w.h_pinned + PIN_K0;
     uint64_t line[K0_LINE_WORDS];
-    auto complete = [&]() -> bool {
-        if (p[0] != seq) return false;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        for (uint32_t i = 1; i < 8; i++) line[i] = p[i];
-        return line[7] == (seq ^ k0_line_check(line + 1));
-    };
+    auto complete = [&]() -> bool { return read_line(p, seq, line); };
     // every 16 polls: has the kernel left?  Then the line is read once more, and the call is the first of the next launch
     // (a launch that fails ends the wait).  Not after the deadline below: the kernel has been told to leave by then.
     uint32_t polls = 0;
@@ -237,17 +243,7 @@ int run_resident(acx_automaton *a, Ctx *c, const uint8_t *hay, uint64_t len, int
     if (sync_e != hipSuccess) return hipfail(sync_e, "hipStreamSynchronize(R.stream)");
     if (!got) { R.off = 64; return ACX_OK; }
     *taken = true;
-    for (uint32_t i = 1; i < K0_LINE_WORDS - 1; i++) w.h_lines[0][i] = line[i];
-    const uint64_t w1 = line[1]; // matches | too dense << 32 | hash of pin_out << 33
-    if (((w1 >> 32) & 1u) == 0) {
-        if ((rc = take_more_lines(c, seq, w1 & 0xFFFFFFFFull)) != ACX_OK) return rc;
-        *n_out = w1 & 0xFFFFFFFFull;
-        *done = true;
-        std::lock_guard<std::mutex> lk(a->prof_mu);
-        a->profile.small_calls++;
-        a->path[7]++;
-    }
-    return ACX_OK;
+    return first_line_taken(a, c, seq, line, n_out, done);
 }
 
 namespace {

@@ -121,8 +121,39 @@ struct PinBuf {
     }
 };
 
-// pinned host scratch of a context, in 64-bit words (Workspace::h_pinned)
+// pinned host scratch of a context, in 64-bit words (Workspace::h_pinned): the POLLED lines, each written by one store and
+// accepted on its check word (kernels.hpp) ...
 constexpr uint32_t PIN_TOTALS = 24, PIN_HOT_TOTALS = 32, PIN_SPEC_TOTALS = 40, PIN_RESIDENT = 48, PIN_K0 = 64, PINNED_WORDS = 96;
+// ... and words [0 .. 15]: what a copy or a kernel on the context's stream leaves and the host reads BEHIND a synchronisation
+// of that stream.  Host-side names (the kernels keep their literals).  Users that share a word cannot meet: one call holds the
+// context at a time, and each of them queues its write, synchronises and reads before it lets anything else onto the stream.
+enum PinWord : uint32_t {
+    PIN_OCC = 0, PIN_OCC_MAX = 1,   // radix form: occurrences kept / the fullest region (copies of SCR_OCC ..)
+    PIN_HITS = 2, PIN_HITS_MAX = 3, // both dense forms: prefix hits kept / the fullest hit region
+    PIN_ITEMS_OVERFLOW = 4,         // radix form, K1a: the failureless walk ran out of item room (u32)
+    PIN_RADIX_FINAL = 6,            // radix form: the matches the greedy resolution kept (u32)
+    PIN_DENSE_MATCHES = 8, PIN_DENSE_OCC = 9, PIN_DENSE_ABORT = 10, // tile-ordered form: its totals and abort flag (u32)
+    PIN_EXACT_TOTAL = 10,           // radix form: the exact total of the regions' counts (an attempt of that form never reads
+                                    // the tile-ordered form's flag: each reads right behind its own synchronisation)
+    // words 8, 9 between pipeline runs -- none of these has an attempt in flight:
+    PIN_K0_COUNT = 8, PIN_K0_DENSE = 9, // an unpolled K0: matches / too dense (the pipeline starts after they are read)
+    PIN_EXPANDED = 8,                   // expand_copies: the records behind the expansion (the pipeline is over)
+    PIN_SPLIT_CUT = 8,                  // run_batch_split: the first byte of the second part (before the parts run)
+    PIN_RANGE_CUT = 8,                  // run_chunked: the two words of SCR_RANGE_CUT (between two pieces)
+};
+// device scratch of a context, in 64-bit words (Workspace::summary, 16 of them)
+enum ScratchWord : uint32_t {
+    SCR_OCC = 0, SCR_OCC_MAX = 1, SCR_HITS = 2, SCR_HITS_MAX = 3, // sink_summary: the fill of the occurrence / hit regions
+                                    // (k_tile_write leaves its occurrences and hits in [0], [2] as well; nobody reads them)
+    SCR_ITEMS_OVERFLOW = 4,         // radix form, K1a: the walk's item-overflow flag (u32), cleared in front of the walk -- and
+                                    // where k_tile_write leaves its matches, which no host code reads
+    SCR_DENSE_MATCHES = 8, SCR_DENSE_OCC = 9, // tile-ordered form: its totals; the radix form's second summary (exact
+                                    // regions) scribbles here, in an attempt of its own
+    SCR_ABORT = 10, SCR_ZERO = 11,  // (u32 each) the abort flag of the hot pipeline and of the tile-ordered form, and a flag
+                                    // that stays zero for its write kernel: the dense form clears both in front of its kernels,
+                                    // the sparse write kernel when it announces hot groups -- one stream, one after the other
+    SCR_RANGE_CUT = 12,             // run_chunked: the two words cut_point leaves (13 as well)
+};
 // The structs the kernels take by value (DenseTiles, TileSpace: device_types.hpp) stay plain views; the memory behind a view's
 // pointers is owned by the group of buffers next to it, and the view is filled from the group once all of it is allocated.
 struct Workspace {
@@ -139,13 +170,13 @@ struct Workspace {
     DevBuf<uint4> hrecs;              // dense path, K1b prefix-hit sink: hit_total() records of 32 B (two elements each)
     uint64_t hit_total() const { return hrecs.cap / 2; }
     DevBuf<uint64_t> hit_counts;      // device: one per K1b wave
-    DevBuf<uint64_t> summary;         // device: [0] occurrences kept, [1] max per region, [2..3] same for
-                                      // hits, [4] matches written, [5..6] abort flags of the sparse path
+    DevBuf<uint64_t> summary;         // device: 16 words of scratch for totals and flags (ScratchWord above: sink fill, the walk's
+                                      // overflow flag, the dense totals, the abort and zero flags, the cut of a byte range)
     DevBuf<uint64_t> block_counts;    // device: one per scan workgroup
     DevBuf<uint64_t> region_off;      // device: exclusive prefix of the kept counts
-    PinBuf<uint64_t> h_pinned;        // pinned host scratch (PINNED_WORDS x u64, 64-byte lines): [0 .. 15] the dense paths' totals
-                                      // (copied behind a stream synchronisation; [8], [9] = result of an unpolled K0), then the
-                                      // POLLED lines, each written by one store and accepted on its check word (kernels.hpp):
+    PinBuf<uint64_t> h_pinned;        // pinned host scratch (PINNED_WORDS x u64, 64-byte lines): [0 .. 15] words read behind a stream
+                                      // synchronisation (PinWord above: the dense paths' totals, an unpolled K0's result, the
+                                      // borrowers between pipeline runs), then the POLLED lines (PIN_TOTALS ..):
                                       // [64 .. 95] K0's result (up to four lines), [24 .. 31] the sparse path's totals, [32 .. 39] the hot pipeline's
                                       // early total (hot_totals), [40 .. 47] the speculative hot pipeline's, [48] the epoch of
                                       // the last resident K0 that has left (Resident)
