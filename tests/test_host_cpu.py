@@ -576,10 +576,13 @@ def test_no_cpu_fallback_without_a_device():
         capi.Automaton([b"hello"])
 
 
-def failureless_walk_occurrences(h, hay: bytes):
+def failureless_walk_occurrences(h, hay: bytes, trace=None):
     """Test-side twin of k1a_scan + k1a_walk over the host compiler's walk tables (NOT a product
     path): level 1 on symbols, the depth-3 record by class triple, the depth-4 record (a tail is
-    compared, not walked), everything else walked from its node or from the root."""
+    compared, not walked), everything else walked from its node or from the root.
+    trace: a dict of three lists that take the positions that survive level 1 ("survivors"), that the
+    scan hands to the walk -- from the root, or from a depth-4 node where a pattern ends or the fifth
+    byte has a child -- ("items"), and that stage G settles itself, a tail that matches ("hits")."""
     OWN, TAIL, SHORT, MANY = 1 << 31, 1 << 30, 1 << 31, 0xFFFFFFFE
     nc, n, out = h.n_classes, len(hay), []
     cls = [int(c) for c in h.classes]
@@ -616,15 +619,27 @@ def failureless_walk_occurrences(h, hay: bytes):
             s = [b & 31 for b in hay[pos:pos + 4]]
             if not (int(h.walk_t3b[((s[0] << 5) | s[1]) * 33 + s[2]]) >> s[3]) & 1:
                 continue
+        if trace is not None:
+            trace["survivors"].append(pos)
         c = [cls[b] for b in hay[pos:pos + 5]] + [0] * 5
         x, y = (int(v) for v in h.walk_t3r[(c[0] * nc + c[1]) * nc + c[2]]) if pos + 3 <= n else (0, SHORT)
         if (y & SHORT) or pos + 5 > n:
+            if trace is not None:
+                trace["items"].append(pos)
             walk(pos, 0, 0)
             continue
         if not (x >> c[3]) & 1:
             continue
         node = (y & ID_MASK) + bin(x & ((1 << c[3]) - 1)).count("1")
+        before = len(out)
         walk(pos, node, 4)
+        if trace is not None:
+            r = [int(v) for v in h.walk_grec[node]]
+            if r[1] & TAIL:
+                if len(out) > before:
+                    trace["hits"].append(pos)
+            elif (r[1] & OWN) or (r[0] >> c[4]) & 1:
+                trace["items"].append(pos)
     return out
 
 
