@@ -12,57 +12,42 @@ using namespace acxh;
 struct ACX_HIDDEN acx_columns : ResultBlock {
     bool batch = false;
     uint64_t n = 0, rows = 0;
-    int64_t *col[4] = {nullptr, nullptr, nullptr, nullptr}; // ACX_COL_*; [3]: null in the single form
 
-    int alloc() { // the block (by on_device) and the columns' places in it
-        const Layout L = batch ? block_layout({n * 8, n * 8, n * 8, (rows + 1) * 8}) : block_layout({n * 8, n * 8, n * 8});
-        int rc = ResultBlock::alloc(L.bytes);
-        for (int k = 0; rc == ACX_OK && k < 3 + (batch ? 1 : 0); k++) col[k] = (int64_t *)(base() + L.at[k]);
-        return rc;
-    }
+    // the block (by on_device) and its parts, ACX_COL_*; the single form has no row offsets
+    int alloc() { return batch ? alloc_parts({n * 8, n * 8, n * 8, (rows + 1) * 8}) : alloc_parts({n * 8, n * 8, n * 8}); }
+    int64_t *col(int which) const { return at<int64_t>(which); }
 };
 
 namespace {
+
+constexpr int N_PARTS = ACX_COL_ROW_OFFSETS + 1;
 
 // The device route: the find pipeline as acx_find_device runs it (byte ranges, batch splits and the expansion of copies
 // included), then the split -- and, for a batch, the scan of the counts -- on the same stream.  Returns when the number of
 // matches is known; the kernels may still run (out->done).  d_hay, and G.offsets, must stay valid until then.
 int run_columns(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping,
                 int codepoints, acx_columns **out) {
-    *out = nullptr;
     const bool segmented = rows_of(G).segmented;
-    acx_result *r = nullptr;
-    if (!(segmented && G.n_hay == 0)) { // (an empty batch: nothing to search, one row offset)
-        int rc = run_find(a, x, d_hay, len, G, overlapping, codepoints, &r);
-        if (rc != ACX_OK) return rc;
-    }
-    acx_columns *R = new_result<acx_columns>(a->device, true);
-    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
-    hipStream_t st = x->stream;
-    R->batch = segmented;
-    R->rows = segmented ? G.n_hay : 0;
-    R->n = r ? r->n : 0;
-    auto body = [&]() -> int {
+    // (an empty batch: nothing to search, one row offset)
+    return find_stage(a, x, d_hay, len, G, overlapping, codepoints, !(segmented && G.n_hay == 0), out, [&](FindStage<acx_columns> &F) -> int {
+        acx_columns *R = F.R;
+        R->batch = segmented;
+        R->rows = segmented ? G.n_hay : 0;
+        R->n = F.r ? F.r->n : 0;
         int rc = R->alloc();
         if (rc != ACX_OK) return rc;
-        if (r) HIPCHK(acx::col_split(r->d_matches, R->n, R->col[0], R->col[1], R->col[2], st));
+        if (F.r) HIPCHK(acx::col_split(F.r->d_matches, R->n, R->col(0), R->col(1), R->col(2), F.st));
         if (R->batch && R->rows) { // where every haystack's records begin, from the counts
             uint64_t *temp = nullptr;
             HIPCHK(g_bufs.get((void **)&temp, std::max<uint64_t>(replace_scan_words(R->rows) * 8, 16), a->device));
-            R->scratch.push_back(temp);
-            HIPCHK(acx::replace_scan(nullptr, nullptr, r->d_counts, R->rows, R->col[3], temp, st));
+            F.keep(temp);
+            HIPCHK(acx::replace_scan(nullptr, nullptr, F.r->d_counts, R->rows, R->col(3), temp, F.st));
         } else if (R->batch) {
-            HIPCHK(hipMemsetAsync(R->col[3], 0, 8, st));
+            HIPCHK(hipMemsetAsync(R->col(3), 0, 8, F.st));
         }
         return ACX_OK;
-    };
-    int rc = retire_find(body(), st, r, R);
-    if (rc != ACX_OK) { acx_free_columns(R); return rc; }
-    *out = R;
-    return ACX_OK;
+    });
 }
-
-uint64_t part_words(const acx_columns *c, int which) { return which == ACX_COL_ROW_OFFSETS ? c->rows + 1 : c->n; }
 
 } // namespace
 
@@ -94,26 +79,23 @@ int acx_find_columns(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const
     if (!a || !out) return fail(ACX_EINVAL, "null argument");
     *out = nullptr;
     // the find entry points as they are (K0, the resident K0, the in-place read, the staged pipeline), each under its lease
-    acx_match_t *m = nullptr;
-    uint64_t nm = 0;
-    std::vector<uint64_t> counts;
-    int rc = host_find(a, hay, len, offsets, n_hay, overlapping, codepoints, &m, &nm, &counts);
+    HostFind f;
+    int rc = f.find(a, hay, len, offsets, n_hay, overlapping, codepoints);
     if (rc != ACX_OK) return rc;
     acx_columns *R = new_result<acx_columns>(a->device, false);
-    if (!R) { acx_free_matches(m); return ACX_ENOMEM; }
+    if (!R) return ACX_ENOMEM;
     R->batch = offsets != nullptr;
     R->rows = R->batch ? n_hay : 0;
-    R->n = nm;
-    if ((rc = R->alloc()) != ACX_OK) { acx_free_matches(m); delete R; return rc; }
-    for (int k = 0; k < 3; k++) R->col[k][0] = 0; // (the one word of an empty column)
-    rc = acx_split_host(m, nm, R->col[0], R->col[1], R->col[2]);
-    acx_free_matches(m);
+    R->n = f.nm;
+    if ((rc = R->alloc()) != ACX_OK) { free_result(R); return rc; }
+    for (int k = 0; k < 3; k++) R->col(k)[0] = 0; // (the one word of an empty column)
+    rc = acx_split_host(f.m, f.nm, R->col(0), R->col(1), R->col(2));
     if (R->batch) {
         int64_t at = 0;
-        for (uint64_t h = 0; h < n_hay; h++) { R->col[3][h] = at; at += (int64_t)counts[h]; }
-        R->col[3][n_hay] = at;
+        for (uint64_t h = 0; h < n_hay; h++) { R->col(3)[h] = at; at += (int64_t)f.counts[h]; }
+        R->col(3)[n_hay] = at;
     }
-    if (rc != ACX_OK) { acx_free_columns(R); return rc; }
+    if (rc != ACX_OK) { free_result(R); return rc; }
     *out = R;
     return ACX_OK;
 }
@@ -131,17 +113,9 @@ uint64_t acx_columns_count(const acx_columns_t *c) { return c ? c->n : 0; }
 uint64_t acx_columns_rows(const acx_columns_t *c) { return c ? c->rows : 0; }
 int acx_columns_on_device(const acx_columns_t *c) { return c ? c->on_device : 0; }
 
-const int64_t *acx_columns_data(const acx_columns_t *c, int which) {
-    if (!c || which < 0 || which > ACX_COL_ROW_OFFSETS) return nullptr;
-    return (const int64_t *)c->ptr_after_wait(c->col[which]);
-}
-
+const int64_t *acx_columns_data(const acx_columns_t *c, int which) { return (const int64_t *)part_ptr(c, which, N_PARTS); }
 int acx_columns_copy(const acx_columns_t *c, int which, int64_t *host_dst) {
-    if (!c || which < 0 || which > ACX_COL_ROW_OFFSETS) return fail(ACX_EINVAL, "no such column");
-    if (!c->col[which]) return fail(ACX_EINVAL, "the single form has no row offsets");
-    const uint64_t words = part_words(c, which);
-    if (words && !host_dst) return fail(ACX_EINVAL, "null argument");
-    return c->copy_out(host_dst, c->col[which], words * 8);
+    return part_copy(c, which, N_PARTS, host_dst, "no such column", "the single form has no row offsets");
 }
 
 void acx_free_columns(acx_columns_t *c) { free_result(c); }

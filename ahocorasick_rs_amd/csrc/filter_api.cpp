@@ -12,21 +12,14 @@ using namespace acxh;
 // and counts and the stage's temporaries have gone back to the cache behind the stage's kernels.
 struct ACX_HIDDEN acx_filtered : ResultBlock {
     uint64_t n_src = 0, rows = 0, bytes = 0;
-    uint8_t *part[3] = {nullptr, nullptr, nullptr}; // ACX_FILT_*
 
-    int alloc() { // the block (by on_device) and the parts' places in it
-        const Layout L = block_layout({rows * 8, (rows + 1) * 8, std::max<uint64_t>((bytes + 15) / 16 * 16, 16)}, 16);
-        int rc = ResultBlock::alloc(L.bytes);
-        for (int p = 0; rc == ACX_OK && p < 3; p++) part[p] = base() + L.at[p];
-        return rc;
-    }
+    // the block (by on_device) and its parts, ACX_FILT_*; the tail of 16 gives the data round_up(bytes, 16), at least 16
+    int alloc() { return alloc_parts({rows * 8, (rows + 1) * 8, bytes}, 16); }
 };
 
 namespace {
 
-uint64_t part_bytes(const acx_filtered_t *f, int which) {
-    return which == ACX_FILT_ROWS ? f->rows * 8 : which == ACX_FILT_OFFSETS ? (f->rows + 1) * 8 : f->bytes;
-}
+constexpr int N_PARTS = ACX_FILT_DATA + 1;
 
 // The temporaries of one run of the device stage: one block of the buffer cache.
 struct Stage {
@@ -112,45 +105,34 @@ int check_args(uint64_t min_matches, uint32_t flags) {
 // same stream, and the stage runs on the verdicts as its counts with min_matches = 1.
 int run_filter(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_search, uint64_t len, const Segments &G,
                int overlapping, uint64_t min_matches, uint32_t flags, acx_filtered_t **out, const ScoreBy *by = nullptr) {
-    *out = nullptr;
     const uint64_t n = rows_of(G).n;
-    acx_result *r = nullptr;
-    if (n) { // (an empty batch: nothing to search, one offset)
-        int rc = run_find(a, x, d_search, len, G, overlapping, 0, &r);
-        if (rc != ACX_OK) return rc;
-    }
-    acx_filtered_t *R = new_result<acx_filtered_t>(a->device, true);
-    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
-    hipStream_t st = x->stream;
-    R->n_src = n;
-    Stage S;
-    ScoreTemps T;
-    uint64_t *one_count = nullptr;
-    auto body = [&]() -> int {
+    // (an empty batch: nothing to search, one offset)
+    return find_stage(a, x, d_search, len, G, overlapping, 0, n != 0, out, [&](FindStage<acx_filtered> &F) -> int {
+        acx_filtered *R = F.R;
+        hipStream_t st = F.st;
+        R->n_src = n;
         int rc;
+        Stage S;
         if (n) {
             const uint64_t *d_counts = nullptr;
-            if ((rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
+            if ((rc = F.counts(&d_counts)) != ACX_OK) return rc;
             if (by) { // (stage_sizes waits for the stream: the caller's weights are uploaded when it returns)
-                rc = score_stage(a->device, st, r->d_matches, r->n, d_counts, n, by->weights, nullptr, by->n_weights, false, nullptr,
+                ScoreTemps T;
+                rc = score_stage(a->device, st, F.r->d_matches, F.r->n, d_counts, n, by->weights, nullptr, by->n_weights, false, nullptr,
                                  &by->min_score, &T);
+                F.keep(T.block); // (the scored form: kept until acx_free_filtered)
                 if (rc != ACX_OK) return rc;
                 d_counts = T.flags;
                 min_matches = 1;
             }
             const acx::RowCut rows = row_cut(G, len);
             rc = stage_sizes(a->device, st, rows, d_counts, min_matches, (flags & ACX_FILTER_KEEP_MATCHED) != 0, &S, &R->rows, &R->bytes);
+            F.temp = S.block;
             if (rc != ACX_OK) return rc;
         }
         if ((rc = R->alloc()) != ACX_OK) return rc;
-        return stage_finish(&S, d_hay, R->rows, R->bytes, (int64_t *)R->part[0], (int64_t *)R->part[1], R->part[2], st);
-    };
-    int rc = body();
-    if (T.block) R->scratch.push_back(T.block); // (the scored form: kept until acx_free_filtered)
-    rc = retire_find(rc, st, r, R, S.block, one_count);
-    if (rc != ACX_OK) { acx_free_filtered(R); return rc; }
-    *out = R;
-    return ACX_OK;
+        return stage_finish(&S, d_hay, R->rows, R->bytes, R->at<int64_t>(0), R->at<int64_t>(1), R->at<uint8_t>(2), st);
+    });
 }
 
 // The host route's end: the rows kept by counts[h] >= min_matches, copied from the caller's memory (the output never crosses
@@ -165,10 +147,10 @@ int host_filtered(const acx_automaton *a, const HostBatch &B, uint64_t len, uint
     R->n_src = n_hay;
     R->rows = k;
     R->bytes = total;
-    if ((rc = R->alloc()) != ACX_OK) { delete R; return rc; }
-    rc = acx_filter_host(B.hay, len, B.rel.data(), n_hay, counts, min_matches, flags, (int64_t *)R->part[0], (int64_t *)R->part[1],
-                         R->part[2], &R->rows, &R->bytes);
-    if (rc != ACX_OK) { acx_free_filtered(R); return rc; }
+    if ((rc = R->alloc()) != ACX_OK) { free_result(R); return rc; }
+    rc = acx_filter_host(B.hay, len, B.rel.data(), n_hay, counts, min_matches, flags, R->at<int64_t>(0), R->at<int64_t>(1),
+                         R->at<uint8_t>(2), &R->rows, &R->bytes);
+    if (rc != ACX_OK) { free_result(R); return rc; }
     *out = R;
     return ACX_OK;
 }
@@ -310,17 +292,8 @@ uint64_t acx_filtered_rows(const acx_filtered_t *f) { return f ? f->rows : 0; }
 uint64_t acx_filtered_bytes(const acx_filtered_t *f) { return f ? f->bytes : 0; }
 int acx_filtered_on_device(const acx_filtered_t *f) { return f ? f->on_device : 0; }
 
-const void *acx_filtered_data(const acx_filtered_t *f, int which) {
-    if (!f || which < 0 || which > ACX_FILT_DATA) return nullptr;
-    return f->ptr_after_wait(f->part[which]);
-}
-
-int acx_filtered_copy(const acx_filtered_t *f, int which, void *host_dst) {
-    if (!f || which < 0 || which > ACX_FILT_DATA) return fail(ACX_EINVAL, "no such part");
-    const uint64_t bytes = part_bytes(f, which);
-    if (bytes && !host_dst) return fail(ACX_EINVAL, "null argument");
-    return f->copy_out(host_dst, f->part[which], bytes);
-}
+const void *acx_filtered_data(const acx_filtered_t *f, int which) { return part_ptr(f, which, N_PARTS); }
+int acx_filtered_copy(const acx_filtered_t *f, int which, void *host_dst) { return part_copy(f, which, N_PARTS, host_dst, "no such part"); }
 
 void acx_free_filtered(acx_filtered_t *f) { free_result(f); }
 

@@ -10,19 +10,12 @@ using namespace acxh;
 // (result_block.hpp).  Device route: the find's records and the stage's temporaries have gone back to the cache behind the
 // stage's kernels.
 struct ACX_HIDDEN acx_masked : ResultBlock {
+    enum { OFFSETS, DATA, N_PARTS };
     uint64_t rows = 0, bytes = 0;
-    int64_t *offsets = nullptr;
-    uint8_t *data = nullptr;
 
-    int alloc() { // the block (by on_device) and the parts' places in it
-        const Layout L = block_layout({(rows + 1) * 8, bytes});
-        int rc = ResultBlock::alloc(L.bytes);
-        if (rc == ACX_OK) {
-            offsets = (int64_t *)(base() + L.at[0]);
-            data = base() + L.at[1];
-        }
-        return rc;
-    }
+    int alloc() { return alloc_parts({(rows + 1) * 8, bytes}); } // the block (by on_device) and its two parts
+    int64_t *offsets() const { return at<int64_t>(OFFSETS); }
+    uint8_t *data() const { return at<uint8_t>(DATA); }
 };
 
 namespace {
@@ -58,38 +51,27 @@ int mask_stage(int device, hipStream_t st, const uint8_t *d_hay, const acx::RowC
 // Returns with the stage in flight (out->done).  d_hay, d_search and G.offsets must stay valid until then.
 int run_mask(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_search, uint64_t len, const Segments &G,
              int overlapping, uint8_t fill, uint32_t flags, acx_masked_t **out) {
-    *out = nullptr;
     const uint64_t rows = rows_of(G).n;
-    acx_masked_t *R = new_result<acx_masked_t>(a->device, true);
-    if (!R) return ACX_ENOMEM;
-    acx_result *r = nullptr;
-    if (rows && len) { // (an empty batch, or empty rows only: nothing to search)
-        int rc = run_find(a, x, d_search, len, G, overlapping, 0, &r);
-        if (rc != ACX_OK) { delete R; return rc; }
-    }
-    hipStream_t st = x->stream;
-    R->rows = rows;
-    R->bytes = len;
-    void *block = nullptr;
-    uint64_t *one_count = nullptr;
-    auto body = [&]() -> int {
+    // (an empty batch, or empty rows only: nothing to search)
+    return find_stage(a, x, d_search, len, G, overlapping, 0, rows && len, out, [&](FindStage<acx_masked> &F) -> int {
+        acx_masked *R = F.R;
+        acx_result *r = F.r;
+        hipStream_t st = F.st;
+        R->rows = rows;
+        R->bytes = len;
         int rc;
         if ((rc = R->alloc()) != ACX_OK) return rc;
         const acx::RowCut MR = row_cut(G, len);
         if (!rows) {
-            HIPCHK(hipMemsetAsync(R->offsets, 0, 8, st));
+            HIPCHK(hipMemsetAsync(R->offsets(), 0, 8, st));
         } else {
-            HIPCHK(acx::mask_offsets(MR, R->offsets, st));
+            HIPCHK(acx::mask_offsets(MR, R->offsets(), st));
         }
         const uint64_t *d_counts = nullptr;
-        if (r && (rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
-        return mask_stage(a->device, st, d_hay, MR, r ? r->d_matches : nullptr, r ? r->n : 0, d_counts, false, fill, flags, R->data,
-                          &block);
-    };
-    int rc = retire_find(body(), st, r, R, block, one_count);
-    if (rc != ACX_OK) { acx_free_masked(R); return rc; }
-    *out = R;
-    return ACX_OK;
+        if (r && (rc = F.counts(&d_counts)) != ACX_OK) return rc;
+        return mask_stage(a->device, st, d_hay, MR, r ? r->d_matches : nullptr, r ? r->n : 0, d_counts, false, fill, flags, R->data(),
+                          &F.temp);
+    });
 }
 
 } // namespace
@@ -137,22 +119,18 @@ int acx_mask(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_
     if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
     // the find as it is (the small-call kernel, its resident form, the in-place read, the staged pipeline all still apply):
     // the records cross the bus, the output never does
-    acx_match_t *m = nullptr;
-    uint64_t nm = 0;
-    std::vector<uint64_t> counts;
+    HostFind f;
     const bool search = n_hay && len; // (an empty batch, or empty rows only: nothing to search, nothing to paint)
-    if (search) rc = host_find(a, B.hay, len, offsets ? B.rel.data() : nullptr, n_hay, overlapping, 0, &m, &nm, &counts);
-    if (rc != ACX_OK) return rc;
+    if ((rc = f.find(a, B.hay, len, offsets ? B.rel.data() : nullptr, n_hay, overlapping, 0, search)) != ACX_OK) return rc;
     acx_masked_t *R = new_result<acx_masked_t>(a->device, false);
-    if (!R) { acx_free_matches(m); return ACX_ENOMEM; }
+    if (!R) return ACX_ENOMEM;
     R->rows = n_hay;
     R->bytes = len;
     if ((rc = R->alloc()) == ACX_OK) {
-        for (uint64_t h = 0; h <= n_hay; h++) R->offsets[h] = (int64_t)B.rel[h];
-        if (search) rc = acx_mask_host(B.hay, len, B.rel.data(), n_hay, m, nm, counts.data(), fill, flags, R->data);
+        for (uint64_t h = 0; h <= n_hay; h++) R->offsets()[h] = (int64_t)B.rel[h];
+        if (search) rc = acx_mask_host(B.hay, len, B.rel.data(), n_hay, f.m, f.nm, f.counts.data(), fill, flags, R->data());
     }
-    acx_free_matches(m);
-    if (rc != ACX_OK) { acx_free_masked(R); return rc; }
+    if (rc != ACX_OK) { free_result(R); return rc; }
     *out = R;
     return ACX_OK;
 }
@@ -194,17 +172,16 @@ uint64_t acx_masked_rows(const acx_masked_t *m) { return m ? m->rows : 0; }
 uint64_t acx_masked_bytes(const acx_masked_t *m) { return m ? m->bytes : 0; }
 int acx_masked_on_device(const acx_masked_t *m) { return m ? m->on_device : 0; }
 
-const void *acx_masked_data(const acx_masked_t *m) { return m ? m->ptr_after_wait(m->data) : nullptr; }
-const int64_t *acx_masked_offsets(const acx_masked_t *m) { return m ? (const int64_t *)m->ptr_after_wait(m->offsets) : nullptr; }
-
-int acx_masked_copy(const acx_masked_t *m, void *host_dst) {
-    if (!m || (m->bytes && !host_dst)) return fail(ACX_EINVAL, "null argument");
-    return m->copy_out(host_dst, m->data, m->bytes);
+const void *acx_masked_data(const acx_masked_t *m) { return part_ptr(m, acx_masked::DATA, acx_masked::N_PARTS); }
+const int64_t *acx_masked_offsets(const acx_masked_t *m) {
+    return (const int64_t *)part_ptr(m, acx_masked::OFFSETS, acx_masked::N_PARTS);
 }
-
+// (no result and nowhere to copy to are one refusal here; the offsets are never empty)
+int acx_masked_copy(const acx_masked_t *m, void *host_dst) {
+    return part_copy(m, acx_masked::DATA, acx_masked::N_PARTS, host_dst, "null argument");
+}
 int acx_masked_copy_offsets(const acx_masked_t *m, int64_t *host_dst) {
-    if (!m || !host_dst) return fail(ACX_EINVAL, "null argument");
-    return m->copy_out(host_dst, m->offsets, (m->rows + 1) * 8);
+    return part_copy(m, acx_masked::OFFSETS, acx_masked::N_PARTS, host_dst, "null argument");
 }
 
 void acx_free_masked(acx_masked_t *m) { free_result(m); }

@@ -149,13 +149,12 @@ int acx_replace(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint
     const std::vector<uint64_t> &rel = B.rel;
     if (len <= replace_host_max()) {
         // host route: the find entry points as they are (K0, the resident K0, the in-place read), then the splice here
-        acx_match_t *m = nullptr;
-        uint64_t nm = 0;
-        std::vector<uint64_t> counts;
-        rc = host_find(a, h, len, offsets ? rel.data() : nullptr, n_hay, 0, 0, &m, &nm, &counts);
-        if (rc != ACX_OK) return rc;
+        HostFind f;
+        if ((rc = f.find(a, h, len, offsets ? rel.data() : nullptr, n_hay, 0, 0)) != ACX_OK) return rc;
+        const acx_match_t *m = f.m;
+        const std::vector<uint64_t> &counts = f.counts;
         acx_replaced *R = new_result<acx_replaced>(a->device, false);
-        if (!R) { acx_free_matches(m); return ACX_ENOMEM; }
+        if (!R) return ACX_ENOMEM;
         R->offsets.assign(n_hay + 1, 0);
         uint64_t at = 0;
         for (uint64_t i = 0; i < n_hay && rc == ACX_OK; i++) { // (sizes first: one allocation)
@@ -176,7 +175,6 @@ int acx_replace(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint
                                  n_repl, R->h_out.data() + R->offsets[i], &sz);
             at += counts[i];
         }
-        acx_free_matches(m);
         if (rc != ACX_OK) { acx_free_replaced(R); return rc; }
         *out = R;
         return ACX_OK;

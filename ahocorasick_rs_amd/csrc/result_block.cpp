@@ -1,18 +1,19 @@
-// result_block.cpp -- the owner of a post-find result's memory, the end of a post-find stage and the checks and the find
-// that the stages' entry points share (result_block.hpp).
+// result_block.cpp -- the owner of a post-find result's memory and the accessors of its parts, the end of a post-find stage
+// and the checks and the find that the stages' entry points share (result_block.hpp).
 #include "result_block.hpp"
 
 #include "replace.hpp"
 
 namespace acxh ACX_HIDDEN {
 
-// The layout rule against the formulas the three block results were written with, at the sizes where (x + 31) / 32 * 32
-// and max(x, 1) change.
+// The layout rule against the formulas the block results were written with, at the sizes where (x + 31) / 32 * 32,
+// max(x, 1) and the 256-byte rounding of a part of bytes change.
 namespace {
 constexpr uint64_t r32(uint64_t words) { return (words + 31) / 32 * 32; }
 constexpr uint64_t least1(uint64_t x) { return x > 1 ? x : 1; }
-constexpr bool same(const Layout &L, uint64_t a0, uint64_t a1, uint64_t a2, uint64_t a3, uint64_t bytes) {
-    return L.at[0] == a0 && L.at[1] == a1 && L.at[2] == a2 && L.at[3] == a3 && L.bytes == bytes;
+constexpr uint64_t r256(uint64_t bytes) { return ((bytes > 8 ? bytes : 8) + 255) / 256 * 256; }
+constexpr bool same(const Layout &L, uint64_t a0, uint64_t a1, uint64_t a2, uint64_t a3, uint64_t bytes, uint64_t a4 = 0) {
+    return L.at[0] == a0 && L.at[1] == a1 && L.at[2] == a2 && L.at[3] == a3 && L.at[4] == a4 && L.bytes == bytes;
 }
 // columns: three columns of n words and, for a batch, rows + 1 row offsets
 constexpr bool columns_ok(uint64_t n, uint64_t rows) {
@@ -29,12 +30,32 @@ constexpr bool tally_ok(uint64_t rows, uint64_t nnz) {
 constexpr bool filter_ok(uint64_t k, uint64_t total) {
     const uint64_t r = (least1(k) * 8 + 255) / 256 * 256, o = ((k + 1) * 8 + 255) / 256 * 256;
     const uint64_t data = (total + 15) / 16 * 16 > 16 ? (total + 15) / 16 * 16 : 16;
-    return same(block_layout({k * 8, (k + 1) * 8, data}, 16), 0, r, r + o, 0, r + o + data);
+    return same(block_layout({k * 8, (k + 1) * 8, data}, 16), 0, r, r + o, 0, r + o + data) &&
+           same(block_layout({k * 8, (k + 1) * 8, total}, 16), 0, r, r + o, 0, r + o + data); // (the tail of 16 rounds it itself)
+}
+// spans: two columns of n words and, for a batch, rows + 1 row offsets
+constexpr bool spans_ok(uint64_t n, uint64_t rows) {
+    const uint64_t c = r32(least1(n)) * 8;
+    return same(block_layout({n * 8, n * 8}), 0, c, 0, 0, 2 * c) &&
+           same(block_layout({n * 8, n * 8, (rows + 1) * 8}), 0, c, 2 * c, 0, 2 * c + r32(rows + 1) * 8);
+}
+// snippets: the bytes, n + 1 offsets, two columns of n words and, for a batch, rows + 1 row offsets
+constexpr bool snippets_ok(uint64_t n, uint64_t rows, uint64_t bytes) {
+    const uint64_t d = r256(bytes), o = r32(n + 1) * 8, c = r32(least1(n)) * 8;
+    return same(block_layout({bytes, (n + 1) * 8, n * 8, n * 8}), 0, d, d + o, d + o + c, d + o + 2 * c) &&
+           same(block_layout({bytes, (n + 1) * 8, n * 8, n * 8, (rows + 1) * 8}), 0, d, d + o, d + o + c,
+                d + o + 2 * c + r32(rows + 1) * 8, d + o + 2 * c);
+}
+// mask: rows + 1 offsets, then the bytes
+constexpr bool mask_ok(uint64_t rows, uint64_t bytes) {
+    return same(block_layout({(rows + 1) * 8, bytes}), 0, r32(rows + 1) * 8, 0, 0, r32(rows + 1) * 8 + r256(bytes));
 }
 constexpr bool all_ok() {
     for (const uint64_t x : {0, 1, 32, 33})
         for (const uint64_t y : {0, 1, 32, 33})
-            if (!columns_ok(x, y) || !tally_ok(x, y) || !filter_ok(x, y)) return false;
+            if (!columns_ok(x, y) || !tally_ok(x, y) || !filter_ok(x, y) || !spans_ok(x, y) || !mask_ok(x, y * 8) ||
+                !mask_ok(x, y * 8 + 1) || !snippets_ok(x, y, 0) || !snippets_ok(x, y, 8 * x + 1))
+                return false;
     return true;
 }
 static_assert(all_ok(), "block_layout no longer places the parts where the results' blocks had them");
@@ -42,12 +63,37 @@ static_assert(filter_ok(33, 15) && filter_ok(33, 16) && filter_ok(33, 17) && fil
 } // namespace
 
 int ResultBlock::alloc(uint64_t bytes) {
+    block_bytes = bytes;
     if (on_device) {
         HIPCHK(g_bufs.get(&d_block, bytes, device));
         return ACX_OK;
     }
     h_block = new (std::nothrow) uint8_t[bytes];
     return h_block ? ACX_OK : fail(ACX_ENOMEM, "out of memory");
+}
+
+int ResultBlock::alloc_parts(std::initializer_list<uint64_t> part_bytes, uint64_t tail) {
+    const Layout L = block_layout(part_bytes, tail);
+    const int rc = alloc(L.bytes);
+    if (rc != ACX_OK) return rc;
+    int k = 0;
+    for (const uint64_t b : part_bytes) {
+        part[k] = Part{base() + L.at[k], b};
+        k++;
+    }
+    return ACX_OK;
+}
+
+const void *part_ptr(const ResultBlock *R, int which, int n) {
+    return R && which >= 0 && which < n ? R->ptr_after_wait(R->part[which].at) : nullptr;
+}
+
+int part_copy(const ResultBlock *R, int which, int n, void *host_dst, const char *no_such, const char *missing) {
+    if (!R || which < 0 || which >= n) return fail(ACX_EINVAL, no_such);
+    const ResultBlock::Part &p = R->part[which];
+    if (missing && !p.at) return fail(ACX_EINVAL, missing);
+    if (p.bytes && !host_dst) return fail(ACX_EINVAL, "null argument");
+    return R->copy_out(host_dst, p.at, p.bytes);
 }
 
 int ResultBlock::wait() const {
@@ -178,16 +224,15 @@ int device_offsets_span(const uint64_t *d_offsets, uint64_t n_hay, uint64_t len)
     return ends[0] == 0 && ends[1] == len ? ACX_OK : span_error();
 }
 
-int host_find(acx_automaton *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
-              int codepoints, acx_match_t **m, uint64_t *nm, std::vector<uint64_t> *counts) {
-    *m = nullptr;
-    *nm = 0;
+int HostFind::find(acx_automaton *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
+                   int codepoints, bool search) {
     try {
-        counts->assign((offsets ? n_hay : 1) + 1, 0);
+        counts.assign((offsets ? n_hay : 1) + 1, 0);
     } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
-    if (offsets) return acx_find_batch(a, hay, offsets, n_hay, overlapping, codepoints, m, nm, counts->data());
-    const int rc = acx_find(a, hay, len, overlapping, codepoints, m, nm);
-    (*counts)[0] = *nm;
+    if (!search) return ACX_OK;
+    if (offsets) return acx_find_batch(a, hay, offsets, n_hay, overlapping, codepoints, &m, &nm, counts.data());
+    const int rc = acx_find(a, hay, len, overlapping, codepoints, &m, &nm);
+    counts[0] = nm;
     return rc;
 }
 

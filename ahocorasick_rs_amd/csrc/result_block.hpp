@@ -1,6 +1,7 @@
 // result_block.hpp -- what the stages behind the find pipeline (summaries, splice, columns, tally, row filter, scores) share: the
-// owner of a result's memory, the layout of its block, the end of a stage (retire_find), the checks of its arguments and the
-// frames of its entry points.
+// owner of a result's memory and the table of its parts, the layout of its block, the frame from a find to a stage's result
+// (find_stage) and its end (retire_find), the owner of the host route's records (HostFind), the checks of a stage's
+// arguments and the frames of its entry points.
 // The stages' middles are their own (summary_api.cpp .. filter_api.cpp); no kernel includes this.
 #pragma once
 #include <initializer_list>
@@ -10,10 +11,35 @@
 
 namespace acxh ACX_HIDDEN {
 
+// Where the parts of a block begin, in bytes, and the block's size: every part at least one word long (an empty part still
+// has an address that DLPack consumers accept) and a multiple of 256 bytes behind the previous one.  The last part is
+// rounded up to `tail` bytes.
+struct Layout {
+    uint64_t at[5] = {0, 0, 0, 0, 0}, bytes = 0;
+};
+constexpr Layout block_layout(std::initializer_list<uint64_t> part_bytes, uint64_t tail = 256) {
+    Layout L;
+    int k = 0;
+    for (const uint64_t b : part_bytes) {
+        const uint64_t step = k + 1 < (int)part_bytes.size() ? 256 : tail;
+        L.at[k++] = L.bytes;
+        L.bytes += ((b > 8 ? b : 8) + step - 1) / step * step;
+    }
+    return L;
+}
+
 // The owner of a result's memory.  Device route: blocks of the buffer cache (g_bufs, workspace.cpp), written by kernels that
 // may still run when the call returns -- `done` fires behind the last of them; `scratch` is what those kernels still read.
 // Host route: a block of host memory, nothing to wait for.
+// `part`: where every part of the block lies and how many bytes of it count -- written once, by alloc_parts, and read by the
+// stages (at<T>) and by the accessors (part_ptr, part_copy).  A part the form at hand lacks has no address.
 struct ResultBlock {
+    struct Part {
+        uint8_t *at = nullptr;
+        uint64_t bytes = 0;
+    };
+    Part part[5];
+    uint64_t block_bytes = 0;
     int device = 0;
     int on_device = 0;
     uint8_t *h_block = nullptr;
@@ -23,6 +49,12 @@ struct ResultBlock {
 
     int alloc(uint64_t bytes); // the block: of the cache (on_device) or of host memory
     uint8_t *base() const { return on_device ? (uint8_t *)d_block : h_block; }
+    // the block as block_layout cuts it for parts of these sizes, and the table of them
+    int alloc_parts(std::initializer_list<uint64_t> part_bytes, uint64_t tail = 256);
+    // a part that was given room before its size was known (the host tally: room for a run per record): what of it counts
+    void resize_part(int k, uint64_t bytes) { part[k].bytes = bytes; }
+    template <class T>
+    T *at(int k) const { return (T *)part[k].at; }
     // every accessor's wait for the stage's last kernel
     int wait() const;
     // `bytes` at `src` (a part of this result) to host memory, behind the kernels; zero bytes: nothing
@@ -51,22 +83,12 @@ void free_result(T *r) {
     delete r;
 }
 
-// Where the parts of a block begin, in bytes, and the block's size: every part at least one word long (an empty part still
-// has an address that DLPack consumers accept) and a multiple of 256 bytes behind the previous one.  The last part is
-// rounded up to `tail` bytes.
-struct Layout {
-    uint64_t at[5] = {0, 0, 0, 0, 0}, bytes = 0;
-};
-constexpr Layout block_layout(std::initializer_list<uint64_t> part_bytes, uint64_t tail = 256) {
-    Layout L;
-    int k = 0;
-    for (const uint64_t b : part_bytes) {
-        const uint64_t step = k + 1 < (int)part_bytes.size() ? 256 : tail;
-        L.at[k++] = L.bytes;
-        L.bytes += ((b > 8 ? b : 8) + step - 1) / step * step;
-    }
-    return L;
-}
+// The bodies of the accessors by part (acx_*_data, acx_*_copy and the named ones; which: 0 .. n - 1, R may be null).
+// The part's address once the kernels are done; null: no result, no such part, a part this form lacks, a failed wait.
+const void *part_ptr(const ResultBlock *R, int which, int n);
+// ... and the part in host memory.  The refusals, all ACX_EINVAL, in this order: no result or no such part (no_such), a part
+// this form lacks (missing), bytes to copy and nowhere to ("null argument").  The texts are the result type's own.
+int part_copy(const ResultBlock *R, int which, int n, void *host_dst, const char *no_such, const char *missing = nullptr);
 
 // Carves one block of the cache into a stage's temporaries, in words: every part 256 bytes behind the previous one.
 struct Carver {
@@ -92,6 +114,49 @@ int retire_find(int rc, hipStream_t st, acx_result *r, ResultBlock *R, void *t1 
 // The per-haystack counts of a find, on the device: the result's own or, for one haystack that is no batch (the find kept
 // none), its total uploaded to *one -- a temporary for retire_find.
 int counts_of(const acx_result *r, hipStream_t st, uint64_t **one, const uint64_t **d_counts);
+
+// What find_stage hands a stage's body.
+template <class T>
+struct FindStage {
+    T *R;                    // the stage's result, empty
+    hipStream_t st;          // the stream the find ran on, and the stage's
+    acx_result *r;           // the find's result; null: there was nothing to search
+    void *temp = nullptr;    // the body's: its temporaries, one block of the cache (or null), named as soon as it exists
+    uint64_t *one = nullptr; // the frame's: the single count that counts() uploaded
+
+    // the find's per-haystack counts on the device (r != null)
+    int counts(const uint64_t **d_counts) { return counts_of(r, st, &one, d_counts); }
+    // a buffer of the cache that the result's kernels read after the call: the result's from here on (null: nothing).  The
+    // body hands it over straight behind the call that made it, BEFORE it looks at that call's outcome.
+    void keep(void *p) {
+        if (p) R->scratch.push_back(p);
+    }
+};
+
+// The frame from a find to a stage's result, for the run_* functions of the stages whose find is spent by them (columns,
+// spans, snippets, tally, filter, mask, score, summary).  `search`: the stage's own word on whether there is anything to
+// search -- false: no find, the body gets r == null.
+// The find first, then the result (a result that cannot be made frees the find's), then body(F) queues the stage on F.st
+// and returns its outcome; whatever that is, retire_find ends the stage with F.temp and F.one as its temporaries, and what
+// the body kept is R's: free_result gives it back when the body failed halfway.  *out: the result, or null on failure.
+template <class T, class Body>
+int find_stage(acx_automaton *a, Ctx *x, const uint8_t *d_search, uint64_t len, const Segments &G, int overlapping, int codepoints,
+               bool search, T **out, Body &&body) {
+    *out = nullptr;
+    acx_result *r = nullptr;
+    if (search) {
+        const int found = run_find(a, x, d_search, len, G, overlapping, codepoints, &r);
+        if (found != ACX_OK) return found;
+    }
+    T *R = new_result<T>(a->device, true);
+    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
+    FindStage<T> F{R, x->stream, r};
+    const int queued = body(F); // (in a statement of its own: F.temp and F.one are read behind it)
+    const int rc = retire_find(queued, F.st, r, R, F.temp, F.one);
+    if (rc != ACX_OK) { free_result(R); return rc; }
+    *out = R;
+    return ACX_OK;
+}
 
 // The rows a stage makes of a find's segments: G.n_hay of them, or -- neither offsets nor a row length: no batch -- one.
 struct Rows {
@@ -187,12 +252,22 @@ int device_call(acx_automaton *a, const void *d_hay, uint64_t len, const uint64_
     return run(lease.c, d_search, G);
 }
 
-// The host route's find: acx_find (offsets == null: one haystack of len bytes, (*counts)[0] becomes its matches) or
-// acx_find_batch as they are -- the small-call kernel, its resident form, the in-place read, the staged pipeline, each
-// under its own lease.  *m: the matches, the caller's to free (acx_free_matches) whatever happens later; *counts: a word
-// per haystack and one more (an empty batch still has a pointer to give).
-int host_find(acx_automaton *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
-              int codepoints, acx_match_t **m, uint64_t *nm, std::vector<uint64_t> *counts);
+// The host route's find and the owner of its records: m goes back (acx_free_matches) when this goes, on every exit.
+struct HostFind {
+    acx_match_t *m = nullptr;
+    uint64_t nm = 0;
+    std::vector<uint64_t> counts; // a word per haystack and one more (an empty batch still has a pointer to give)
+
+    HostFind() = default;
+    HostFind(const HostFind &) = delete;
+    HostFind &operator=(const HostFind &) = delete;
+    ~HostFind() { acx_free_matches(m); }
+    // acx_find (offsets == null: one haystack of len bytes, counts[0] becomes its matches) or acx_find_batch as they are --
+    // the small-call kernel, its resident form, the in-place read, the staged pipeline, each under its own lease.
+    // search == false: the entry's word that there is nothing to search (no row, or no byte) -- no record, zero counts.
+    int find(acx_automaton *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
+             int codepoints, bool search = true);
+};
 
 // The staged device route of a host entry point, the mirror of device_call: the lease, the haystacks (and, for a batch,
 // B's offsets) staged, the folded copy of a case-insensitive handle; then run(ctx, d_search, segments) under the lease --

@@ -10,13 +10,9 @@ using namespace acxh;
 // temporaries have gone back to the cache behind the stage's kernels.
 struct ACX_HIDDEN acx_rows : ResultBlock {
     uint64_t rows = 0, bytes = 0;
-    int64_t *offsets = nullptr;
 
-    int alloc() { // the block (by on_device)
-        int rc = ResultBlock::alloc(block_layout({(rows + 1) * 8}).bytes);
-        if (rc == ACX_OK) offsets = (int64_t *)base();
-        return rc;
-    }
+    int alloc() { return alloc_parts({(rows + 1) * 8}); } // the block (by on_device): its one part
+    int64_t *offsets() const { return at<int64_t>(0); }
 };
 
 namespace {
@@ -101,8 +97,8 @@ int acx_split_rows(const uint8_t *hay, uint64_t len, uint8_t delimiter, acx_rows
     R->rows = host_cut(hay, len, delimiter, nullptr);
     R->bytes = len;
     int rc = R->alloc();
-    if (rc != ACX_OK) { delete R; return rc; }
-    (void)host_cut(hay, len, delimiter, R->offsets);
+    if (rc != ACX_OK) { free_result(R); return rc; }
+    (void)host_cut(hay, len, delimiter, R->offsets());
     *out = R;
     return ACX_OK;
 }
@@ -126,10 +122,10 @@ int acx_split_rows_device(const void *d_hay, uint64_t len, uint8_t delimiter, ac
     Stage S;
     auto body = [&]() -> int {
         int rc;
-        if (!len) return (rc = R->alloc()) != ACX_OK ? rc : zero_word(R->offsets);
+        if (!len) return (rc = R->alloc()) != ACX_OK ? rc : zero_word(R->offsets());
         if ((rc = stage_sizes(device, nullptr, (const uint8_t *)d_hay, len, delimiter, &S, &R->rows)) != ACX_OK) return rc;
         if ((rc = R->alloc()) != ACX_OK) return rc; // (at worst 8 bytes per input byte: a failure is the call's, not the process's)
-        HIPCHK(acx::rows_write((const uint8_t *)d_hay, len, delimiter, S.base, S.total, S.open, R->offsets, nullptr));
+        HIPCHK(acx::rows_write((const uint8_t *)d_hay, len, delimiter, S.base, S.total, S.open, R->offsets(), nullptr));
         return ACX_OK;
     };
     const int rc = retire_find(body(), nullptr, nullptr, R, S.block);
@@ -170,12 +166,8 @@ uint64_t acx_rows_bytes(const acx_rows_t *r) { return r ? r->bytes : 0; }
 int acx_rows_on_device(const acx_rows_t *r) { return r ? r->on_device : 0; }
 int acx_rows_device(const acx_rows_t *r) { return r ? r->device : 0; }
 
-const int64_t *acx_rows_offsets(const acx_rows_t *r) { return r ? (const int64_t *)r->ptr_after_wait(r->offsets) : nullptr; }
-
-int acx_rows_copy(const acx_rows_t *r, int64_t *host_dst) {
-    if (!r || !host_dst) return fail(ACX_EINVAL, "null argument");
-    return r->copy_out(host_dst, r->offsets, (r->rows + 1) * 8);
-}
+const int64_t *acx_rows_offsets(const acx_rows_t *r) { return (const int64_t *)part_ptr(r, 0, 1); }
+int acx_rows_copy(const acx_rows_t *r, int64_t *host_dst) { return part_copy(r, 0, 1, host_dst, "null argument"); } // (never empty)
 
 void acx_free_rows(acx_rows_t *r) { free_result(r); }
 

@@ -12,15 +12,10 @@ using namespace acxh;
 // weights, which the upload reads until `done`.
 struct ACX_HIDDEN acx_scores : ResultBlock {
     uint64_t rows = 0;
-    int64_t *score = nullptr;
     std::vector<int32_t> weights;
 
-    static Layout layout(uint64_t rows) { return block_layout({rows * 8}); }
-    int alloc() { // the block (by on_device)
-        int rc = ResultBlock::alloc(layout(rows).bytes);
-        if (rc == ACX_OK) score = (int64_t *)base();
-        return rc;
-    }
+    int alloc() { return alloc_parts({rows * 8}); } // the block (by on_device): its one part
+    int64_t *score() const { return at<int64_t>(0); }
 };
 
 namespace acxh ACX_HIDDEN {
@@ -73,42 +68,32 @@ int check_weights(const acx_automaton *a, const int32_t *weights, uint64_t n_wei
 // d_hay, and G.offsets, must stay valid until then; the weights are copied here.
 int run_score(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping,
               const int32_t *weights, uint64_t n_weights, acx_scores_t **out) {
-    *out = nullptr;
     const uint64_t rows = rows_of(G).n;
-    acx_scores_t *R = new_result<acx_scores_t>(a->device, true);
-    if (!R) return ACX_ENOMEM;
-    try {
-        R->weights.assign(weights, weights + n_weights);
-    } catch (...) { delete R; return fail(ACX_ENOMEM, "out of memory"); }
-    acx_result *r = nullptr;
-    if (rows) { // (an empty batch: nothing to search, no score)
-        int rc = run_find(a, x, d_hay, len, G, overlapping, 0, &r);
-        if (rc != ACX_OK) { delete R; return rc; }
-    }
-    hipStream_t st = x->stream;
-    R->rows = rows;
-    ScoreTemps T;
-    uint64_t *one_count = nullptr;
-    auto body = [&]() -> int {
+    // (an empty batch: nothing to search, no score)
+    return find_stage(a, x, d_hay, len, G, overlapping, 0, rows != 0, out, [&](FindStage<acx_scores> &F) -> int {
+        acx_scores *R = F.R;
+        R->rows = rows;
+        try {
+            R->weights.assign(weights, weights + n_weights);
+        } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
         int rc;
         if ((rc = R->alloc()) != ACX_OK || !rows) return rc;
         const uint64_t *d_counts = nullptr;
-        if ((rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
-        return score_stage(a->device, st, r->d_matches, r->n, d_counts, rows, R->weights.data(), nullptr, n_weights, false, R->score,
-                           nullptr, &T);
-    };
-    int rc = retire_find(body(), st, r, R, T.block, one_count);
-    if (rc != ACX_OK) { acx_free_scores(R); return rc; }
-    *out = R;
-    return ACX_OK;
+        if ((rc = F.counts(&d_counts)) != ACX_OK) return rc;
+        ScoreTemps T;
+        rc = score_stage(a->device, F.st, F.r->d_matches, F.r->n, d_counts, rows, R->weights.data(), nullptr, n_weights, false,
+                         R->score(), nullptr, &T);
+        F.temp = T.block;
+        return rc;
+    });
 }
 
 acx_scores_t *host_scores(int device, uint64_t rows) {
     acx_scores_t *R = new_result<acx_scores_t>(device, false);
     if (!R) return nullptr;
     R->rows = rows;
-    if (R->alloc() != ACX_OK) { delete R; return nullptr; }
-    R->score[0] = 0;
+    if (R->alloc() != ACX_OK) { free_result(R); return nullptr; }
+    R->score()[0] = 0;
     return R;
 }
 
@@ -143,16 +128,12 @@ int acx_score(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64
     if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
     if (len <= score_host_max() || !n_hay) {
         // host route: acx_find_batch as it is (the small-call kernel, the in-place read, the staged pipeline), then the sums here
-        acx_match_t *m = nullptr;
-        uint64_t nm = 0;
-        std::vector<uint64_t> counts;
-        if (n_hay) rc = host_find(a, B.hay, len, B.rel.data(), n_hay, overlapping, 0, &m, &nm, &counts);
-        if (rc != ACX_OK) return rc;
+        HostFind f;
+        if ((rc = f.find(a, B.hay, len, B.rel.data(), n_hay, overlapping, 0, n_hay != 0)) != ACX_OK) return rc;
         acx_scores_t *R = host_scores(a->device, n_hay);
-        if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
-        if (n_hay) rc = acx_score_host(m, nm, counts.data(), n_hay, weights, n_weights, R->score);
-        acx_free_matches(m);
-        if (rc != ACX_OK) { acx_free_scores(R); return rc; }
+        if (!R) return fail(ACX_ENOMEM, "out of memory");
+        if (n_hay) rc = acx_score_host(f.m, f.nm, f.counts.data(), n_hay, weights, n_weights, R->score());
+        if (rc != ACX_OK) { free_result(R); return rc; }
         *out = R;
         return ACX_OK;
     }
@@ -195,16 +176,8 @@ int acx_score_rows_device(const acx_match_t *d_records, uint64_t n, const uint64
 uint64_t acx_scores_rows(const acx_scores_t *s) { return s ? s->rows : 0; }
 int acx_scores_on_device(const acx_scores_t *s) { return s ? s->on_device : 0; }
 
-const int64_t *acx_scores_data(const acx_scores_t *s) {
-    if (!s) return nullptr;
-    return (const int64_t *)s->ptr_after_wait(s->score);
-}
-
-int acx_scores_copy(const acx_scores_t *s, int64_t *host_dst) {
-    if (!s) return fail(ACX_EINVAL, "null argument");
-    if (s->rows && !host_dst) return fail(ACX_EINVAL, "null argument");
-    return s->copy_out(host_dst, s->score, s->rows * 8);
-}
+const int64_t *acx_scores_data(const acx_scores_t *s) { return (const int64_t *)part_ptr(s, 0, 1); }
+int acx_scores_copy(const acx_scores_t *s, int64_t *host_dst) { return part_copy(s, 0, 1, host_dst, "null argument"); }
 
 void acx_free_scores(acx_scores_t *s) { free_result(s); }
 

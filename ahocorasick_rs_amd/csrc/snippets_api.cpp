@@ -12,20 +12,18 @@ using namespace acxh;
 struct ACX_HIDDEN acx_snippets : ResultBlock {
     bool batch = false;
     uint64_t n = 0, rows = 0, bytes = 0;
-    void *part[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // ACX_SNIP_*; [4]: null in the single form
 
-    int alloc() { // the block (by on_device) and the parts' places in it
-        const Layout L = batch ? block_layout({bytes, (n + 1) * 8, n * 8, n * 8, (rows + 1) * 8})
-                               : block_layout({bytes, (n + 1) * 8, n * 8, n * 8});
-        int rc = ResultBlock::alloc(L.bytes);
-        for (int k = 0; rc == ACX_OK && k < 4 + (batch ? 1 : 0); k++) part[k] = base() + L.at[k];
-        return rc;
+    // the block (by on_device) and its parts, ACX_SNIP_*; the single form has no row offsets
+    int alloc() {
+        return batch ? alloc_parts({bytes, (n + 1) * 8, n * 8, n * 8, (rows + 1) * 8}) : alloc_parts({bytes, (n + 1) * 8, n * 8, n * 8});
     }
-    uint8_t *data() const { return (uint8_t *)part[ACX_SNIP_DATA]; }
-    int64_t *words(int which) const { return (int64_t *)part[which]; }
+    uint8_t *data() const { return at<uint8_t>(ACX_SNIP_DATA); }
+    int64_t *words(int which) const { return at<int64_t>(which); }
 };
 
 namespace {
+
+constexpr int N_PARTS = ACX_SNIP_ROW_OFFSETS + 1;
 
 constexpr uint64_t CONTEXT_LIMIT = 1ull << 63;
 
@@ -104,21 +102,14 @@ int stage_gather(int device, hipStream_t st, const uint8_t *d_hay, uint64_t len,
 // the output's size is known; the gather may still run (out->done).  d_hay, d_search and G.offsets must stay valid until then.
 int run_snippets(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_search, uint64_t len, const Segments &G,
                  int overlapping, uint64_t context, uint32_t flags, acx_snippets_t **out) {
-    *out = nullptr;
     const bool segmented = rows_of(G).segmented;
-    acx_result *r = nullptr;
-    if (!(segmented && G.n_hay == 0)) { // (an empty batch: nothing to search, one row offset)
-        int rc = run_find(a, x, d_search, len, G, overlapping, 0, &r);
-        if (rc != ACX_OK) return rc;
-    }
-    acx_snippets_t *R = new_result<acx_snippets_t>(a->device, true);
-    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
-    hipStream_t st = x->stream;
-    R->batch = segmented;
-    R->rows = segmented ? G.n_hay : 0;
-    Stage S;
-    uint64_t *one_count = nullptr;
-    auto body = [&]() -> int {
+    // (an empty batch: nothing to search, one row offset)
+    return find_stage(a, x, d_search, len, G, overlapping, 0, !(segmented && G.n_hay == 0), out, [&](FindStage<acx_snippets_t> &F) -> int {
+        acx_snippets_t *R = F.R;
+        acx_result *r = F.r;
+        hipStream_t st = F.st;
+        R->batch = segmented;
+        R->rows = segmented ? G.n_hay : 0;
         int rc;
         const uint64_t n = r ? r->n : 0;
         if (!n) { // no record: no snippet, and every offset is zero
@@ -128,12 +119,13 @@ int run_snippets(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *
             return ACX_OK;
         }
         const uint64_t *d_counts = nullptr;
-        if ((rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
+        if ((rc = F.counts(&d_counts)) != ACX_OK) return rc;
         const uint64_t rows = rows_of(G).n;
         const acx::RowCut SR = row_cut(G, len);
-        if ((rc = stage_sizes(a->device, st, r->d_matches, n, d_counts, SR, false, d_hay, context, flags, nullptr, nullptr, nullptr,
-                              &S)) != ACX_OK)
-            return rc;
+        Stage S;
+        rc = stage_sizes(a->device, st, r->d_matches, n, d_counts, SR, false, d_hay, context, flags, nullptr, nullptr, nullptr, &S);
+        F.temp = S.block;
+        if (rc != ACX_OK) return rc;
         R->n = n;
         R->bytes = S.total;
         if ((rc = R->alloc()) != ACX_OK) return rc;
@@ -142,17 +134,9 @@ int run_snippets(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *
         HIPCHK(hipMemcpyAsync(R->words(ACX_SNIP_LEAD), S.lead, n * 8, hipMemcpyDeviceToDevice, st));
         if (R->batch) HIPCHK(hipMemcpyAsync(R->words(ACX_SNIP_ROW_OFFSETS), S.rec_off, (rows + 1) * 8, hipMemcpyDeviceToDevice, st));
         rc = stage_gather(a->device, st, d_hay, len, n, R->data(), &S);
-        if (S.tiles) R->scratch.push_back(S.tiles); // (kept until acx_free_snippets)
+        F.keep(S.tiles); // (kept until acx_free_snippets)
         return rc;
-    };
-    int rc = retire_find(body(), st, r, R, S.block, one_count);
-    if (rc != ACX_OK) { acx_free_snippets(R); return rc; }
-    *out = R;
-    return ACX_OK;
-}
-
-uint64_t part_bytes(const acx_snippets_t *s, int which) {
-    return which == ACX_SNIP_DATA ? s->bytes : 8 * (which == ACX_SNIP_OFFSETS ? s->n + 1 : which == ACX_SNIP_ROW_OFFSETS ? s->rows + 1 : s->n);
+    });
 }
 
 } // namespace
@@ -206,28 +190,23 @@ int acx_snippets(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uin
     if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
     // the find entry points as they are (K0, the resident K0, the in-place read, the staged pipeline), each under its lease,
     // with byte offsets: the records cross the bus, the snippets are cut of the caller's own bytes here
-    acx_match_t *m = nullptr;
-    uint64_t nm = 0;
-    std::vector<uint64_t> counts(1, 0);
+    HostFind f;
     const bool search = n_hay && len; // (an empty batch, or empty rows only: nothing to search)
-    if (search) rc = host_find(a, B.hay, len, offsets ? B.rel.data() : nullptr, n_hay, overlapping, 0, &m, &nm, &counts);
-    else counts.assign((size_t)n_hay + 1, 0);
-    if (rc != ACX_OK) return rc;
+    if ((rc = f.find(a, B.hay, len, offsets ? B.rel.data() : nullptr, n_hay, overlapping, 0, search)) != ACX_OK) return rc;
     acx_snippets_t *R = new_result<acx_snippets_t>(a->device, false);
-    if (!R) { acx_free_matches(m); return ACX_ENOMEM; }
+    if (!R) return ACX_ENOMEM;
     R->batch = offsets != nullptr;
     R->rows = R->batch ? n_hay : 0;
-    R->n = nm;
+    R->n = f.nm;
     const uint64_t *rel = R->batch ? B.rel.data() : nullptr;
-    rc = acx_snippets_host(m, nm, counts.data(), n_hay, B.hay, len, rel, context, flags, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           &R->bytes);
+    rc = acx_snippets_host(f.m, f.nm, f.counts.data(), n_hay, B.hay, len, rel, context, flags, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, &R->bytes);
     if (rc == ACX_OK) rc = R->alloc();
     if (rc == ACX_OK)
-        rc = acx_snippets_host(m, nm, counts.data(), n_hay, B.hay, len, rel, context, flags, R->words(ACX_SNIP_OFFSETS),
+        rc = acx_snippets_host(f.m, f.nm, f.counts.data(), n_hay, B.hay, len, rel, context, flags, R->words(ACX_SNIP_OFFSETS),
                                R->words(ACX_SNIP_PATTERN), R->words(ACX_SNIP_LEAD), R->batch ? R->words(ACX_SNIP_ROW_OFFSETS) : nullptr,
                                R->data(), &R->bytes);
-    acx_free_matches(m);
-    if (rc != ACX_OK) { acx_free_snippets(R); return rc; }
+    if (rc != ACX_OK) { free_result(R); return rc; }
     *out = R;
     return ACX_OK;
 }
@@ -289,17 +268,9 @@ uint64_t acx_snippets_rows(const acx_snippets_t *s) { return s ? s->rows : 0; }
 uint64_t acx_snippets_nbytes(const acx_snippets_t *s) { return s ? s->bytes : 0; }
 int acx_snippets_on_device(const acx_snippets_t *s) { return s ? s->on_device : 0; }
 
-const void *acx_snippets_data(const acx_snippets_t *s, int which) {
-    if (!s || which < 0 || which > ACX_SNIP_ROW_OFFSETS) return nullptr;
-    return s->ptr_after_wait(s->part[which]);
-}
-
+const void *acx_snippets_data(const acx_snippets_t *s, int which) { return part_ptr(s, which, N_PARTS); }
 int acx_snippets_copy(const acx_snippets_t *s, int which, void *host_dst) {
-    if (!s || which < 0 || which > ACX_SNIP_ROW_OFFSETS) return fail(ACX_EINVAL, "no such part");
-    if (!s->part[which]) return fail(ACX_EINVAL, "the single form has no row offsets");
-    const uint64_t bytes = part_bytes(s, which);
-    if (bytes && !host_dst) return fail(ACX_EINVAL, "null argument");
-    return s->copy_out(host_dst, s->part[which], bytes);
+    return part_copy(s, which, N_PARTS, host_dst, "no such part", "the single form has no row offsets");
 }
 
 void acx_free_snippets(acx_snippets_t *s) { free_result(s); }

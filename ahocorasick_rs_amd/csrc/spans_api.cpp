@@ -12,17 +12,15 @@ using namespace acxh;
 struct ACX_HIDDEN acx_spans : ResultBlock {
     bool batch = false;
     uint64_t n = 0, rows = 0;
-    int64_t *col[3] = {nullptr, nullptr, nullptr}; // ACX_SPAN_*; [2]: null in the single form
 
-    int alloc() { // the block (by on_device) and the columns' places in it
-        const Layout L = batch ? block_layout({n * 8, n * 8, (rows + 1) * 8}) : block_layout({n * 8, n * 8});
-        int rc = ResultBlock::alloc(L.bytes);
-        for (int k = 0; rc == ACX_OK && k < 2 + (batch ? 1 : 0); k++) col[k] = (int64_t *)(base() + L.at[k]);
-        return rc;
-    }
+    // the block (by on_device) and its parts, ACX_SPAN_*; the single form has no row offsets
+    int alloc() { return batch ? alloc_parts({n * 8, n * 8, (rows + 1) * 8}) : alloc_parts({n * 8, n * 8}); }
+    int64_t *col(int which) const { return at<int64_t>(which); }
 };
 
 namespace {
+
+constexpr int N_PARTS = ACX_SPAN_ROW_OFFSETS + 1;
 
 constexpr uint64_t GAP_LIMIT = 1ull << 63;
 
@@ -94,45 +92,34 @@ int stage_sizes(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, 
 // (out->done).  d_hay, and G.offsets, must stay valid until then.
 int run_spans(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping, int codepoints,
               uint64_t gap, acx_spans_t **out) {
-    *out = nullptr;
     const bool segmented = rows_of(G).segmented;
-    acx_result *r = nullptr;
-    if (!(segmented && G.n_hay == 0)) { // (an empty batch: nothing to search, one row offset)
-        int rc = run_find(a, x, d_hay, len, G, overlapping, codepoints, &r);
-        if (rc != ACX_OK) return rc;
-    }
-    acx_spans_t *R = new_result<acx_spans_t>(a->device, true);
-    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
-    hipStream_t st = x->stream;
-    R->batch = segmented;
-    R->rows = segmented ? G.n_hay : 0;
-    Stage S;
-    uint64_t *one_count = nullptr;
-    auto body = [&]() -> int {
+    // (an empty batch: nothing to search, one row offset)
+    return find_stage(a, x, d_hay, len, G, overlapping, codepoints, !(segmented && G.n_hay == 0), out, [&](FindStage<acx_spans_t> &F) -> int {
+        acx_spans_t *R = F.R;
+        hipStream_t st = F.st;
+        R->batch = segmented;
+        R->rows = segmented ? G.n_hay : 0;
         int rc;
-        const uint64_t n = r ? r->n : 0;
+        const uint64_t n = F.r ? F.r->n : 0;
         if (!n) { // no record: no span, and the rows' offsets are zeros
             if ((rc = R->alloc()) != ACX_OK) return rc;
-            if (R->batch) HIPCHK(hipMemsetAsync(R->col[ACX_SPAN_ROW_OFFSETS], 0, (R->rows + 1) * 8, st));
+            if (R->batch) HIPCHK(hipMemsetAsync(R->col(ACX_SPAN_ROW_OFFSETS), 0, (R->rows + 1) * 8, st));
             return ACX_OK;
         }
         const uint64_t *d_counts = nullptr;
-        if ((rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
+        if ((rc = F.counts(&d_counts)) != ACX_OK) return rc;
         const uint64_t rows = rows_of(G).n;
-        if ((rc = stage_sizes(a->device, st, r->d_matches, n, d_counts, rows, false, gap, &S)) != ACX_OK) return rc;
+        Stage S;
+        rc = stage_sizes(a->device, st, F.r->d_matches, n, d_counts, rows, false, gap, &S);
+        F.temp = S.block;
+        if (rc != ACX_OK) return rc;
         R->n = S.S;
         if ((rc = R->alloc()) != ACX_OK) return rc; // (at most 16 bytes per record: a failure is the call's)
-        HIPCHK(acx::spans_emit(r->d_matches, n, S.rec_off, rows, gap, S.temp, S.base, S.S, R->col[ACX_SPAN_ROW_OFFSETS],
-                               R->col[ACX_SPAN_START], R->col[ACX_SPAN_END], st));
+        HIPCHK(acx::spans_emit(F.r->d_matches, n, S.rec_off, rows, gap, S.temp, S.base, S.S, R->col(ACX_SPAN_ROW_OFFSETS),
+                               R->col(ACX_SPAN_START), R->col(ACX_SPAN_END), st));
         return ACX_OK;
-    };
-    int rc = retire_find(body(), st, r, R, S.block, one_count);
-    if (rc != ACX_OK) { acx_free_spans(R); return rc; }
-    *out = R;
-    return ACX_OK;
+    });
 }
-
-uint64_t part_words(const acx_spans_t *s, int which) { return which == ACX_SPAN_ROW_OFFSETS ? s->rows + 1 : s->n; }
 
 } // namespace
 
@@ -176,30 +163,26 @@ int acx_spans(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64
     if (rc != ACX_OK) return rc;
     // the find entry points as they are (K0, the resident K0, the in-place read, the staged pipeline), each under its lease:
     // the records cross the bus, the spans are made of them here
-    acx_match_t *m = nullptr;
-    uint64_t nm = 0;
-    std::vector<uint64_t> counts;
-    if ((rc = host_find(a, hay, len, offsets, n_hay, overlapping, codepoints, &m, &nm, &counts)) != ACX_OK) return rc;
-    const uint64_t rows = offsets ? n_hay : 1;
+    HostFind f;
+    if ((rc = f.find(a, hay, len, offsets, n_hay, overlapping, codepoints)) != ACX_OK) return rc;
+    const uint64_t rows = offsets ? n_hay : 1, nm = f.nm;
     std::vector<int64_t> tmp;
     uint64_t S = 0;
     try {
         tmp.resize((size_t)(2 * nm + rows + 1));
-    } catch (...) { rc = fail(ACX_ENOMEM, "out of memory"); }
+    } catch (...) { return fail(ACX_ENOMEM, "out of memory"); }
     int64_t *ro = tmp.data() + 2 * nm;
-    if (rc == ACX_OK) rc = acx_spans_host(m, nm, counts.data(), rows, gap, ro, tmp.data(), tmp.data() + nm, &S);
-    acx_free_matches(m);
-    if (rc != ACX_OK) return rc;
+    if ((rc = acx_spans_host(f.m, nm, f.counts.data(), rows, gap, ro, tmp.data(), tmp.data() + nm, &S)) != ACX_OK) return rc;
     acx_spans_t *R = new_result<acx_spans_t>(a->device, false);
     if (!R) return ACX_ENOMEM;
     R->batch = offsets != nullptr;
     R->rows = R->batch ? n_hay : 0;
     R->n = S;
-    if ((rc = R->alloc()) != ACX_OK) { delete R; return rc; }
-    for (int k = 0; k < 2; k++) R->col[k][0] = 0; // (the one word of an empty column)
-    std::memcpy(R->col[ACX_SPAN_START], tmp.data(), (size_t)S * 8);
-    std::memcpy(R->col[ACX_SPAN_END], tmp.data() + nm, (size_t)S * 8);
-    if (R->batch) std::memcpy(R->col[ACX_SPAN_ROW_OFFSETS], ro, (size_t)(rows + 1) * 8);
+    if ((rc = R->alloc()) != ACX_OK) { free_result(R); return rc; }
+    for (int k = 0; k < 2; k++) R->col(k)[0] = 0; // (the one word of an empty column)
+    std::memcpy(R->col(ACX_SPAN_START), tmp.data(), (size_t)S * 8);
+    std::memcpy(R->col(ACX_SPAN_END), tmp.data() + nm, (size_t)S * 8);
+    if (R->batch) std::memcpy(R->col(ACX_SPAN_ROW_OFFSETS), ro, (size_t)(rows + 1) * 8);
     *out = R;
     return ACX_OK;
 }
@@ -243,17 +226,9 @@ uint64_t acx_spans_count(const acx_spans_t *s) { return s ? s->n : 0; }
 uint64_t acx_spans_rows(const acx_spans_t *s) { return s ? s->rows : 0; }
 int acx_spans_on_device(const acx_spans_t *s) { return s ? s->on_device : 0; }
 
-const int64_t *acx_spans_data(const acx_spans_t *s, int which) {
-    if (!s || which < 0 || which > ACX_SPAN_ROW_OFFSETS) return nullptr;
-    return (const int64_t *)s->ptr_after_wait(s->col[which]);
-}
-
+const int64_t *acx_spans_data(const acx_spans_t *s, int which) { return (const int64_t *)part_ptr(s, which, N_PARTS); }
 int acx_spans_copy(const acx_spans_t *s, int which, int64_t *host_dst) {
-    if (!s || which < 0 || which > ACX_SPAN_ROW_OFFSETS) return fail(ACX_EINVAL, "no such column");
-    if (!s->col[which]) return fail(ACX_EINVAL, "the single form has no row offsets");
-    const uint64_t words = part_words(s, which);
-    if (words && !host_dst) return fail(ACX_EINVAL, "null argument");
-    return s->copy_out(host_dst, s->col[which], words * 8);
+    return part_copy(s, which, N_PARTS, host_dst, "no such column", "the single form has no row offsets");
 }
 
 void acx_free_spans(acx_spans_t *s) { free_result(s); }

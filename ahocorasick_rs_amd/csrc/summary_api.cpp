@@ -27,27 +27,24 @@ constexpr uint32_t SUM_ALL = ACX_SUM_FIRST | ACX_SUM_BY_PATTERN;
 // of matches is known; the reductions may still run (out->done).  d_hay, and G.offsets, must stay valid until then.
 int run_summary(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping,
                 int codepoints, uint32_t what, acx_summary **out) {
-    *out = nullptr;
-    acx_result *r = nullptr;
-    int rc = run_find(a, x, d_hay, len, G, overlapping, codepoints, &r);
-    if (rc != ACX_OK) return rc;
-    acx_summary *R = new_result<acx_summary>(a->device, true);
-    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
-    hipStream_t st = x->stream;
-    const bool segmented = rows_of(G).segmented;
-    R->what = what;
-    R->n_hay = rows_of(G).n;
-    R->n_patterns = a->host.n_patterns;
-    R->total = r->n;
-    const uint64_t n_hay = R->n_hay, n = r->n;
-    auto get = [&](void **p, uint64_t bytes) -> hipError_t { // (kept until acx_free_summary)
-        const hipError_t e = g_bufs.get(p, std::max<uint64_t>(bytes, 16), a->device);
-        if (e == hipSuccess) R->scratch.push_back(*p);
-        return e;
-    };
-    auto body = [&]() -> int {
+    // (the summary always searches: an empty batch's find is its counts)
+    return find_stage(a, x, d_hay, len, G, overlapping, codepoints, true, out, [&](FindStage<acx_summary> &F) -> int {
+        acx_summary *R = F.R;
+        acx_result *r = F.r;
+        hipStream_t st = F.st;
+        const bool segmented = rows_of(G).segmented;
+        R->what = what;
+        R->n_hay = rows_of(G).n;
+        R->n_patterns = a->host.n_patterns;
+        R->total = r->n;
+        const uint64_t n_hay = R->n_hay, n = r->n;
+        auto get = [&](void **p, uint64_t bytes) -> hipError_t { // (kept until acx_free_summary)
+            const hipError_t e = g_bufs.get(p, std::max<uint64_t>(bytes, 16), a->device);
+            if (e == hipSuccess) F.keep(*p);
+            return e;
+        };
         if (segmented) { // the per-haystack counts are the summary's from here on
-            R->scratch.push_back(r->d_counts);
+            F.keep(r->d_counts);
             R->d_counts = r->d_counts;
             r->d_counts = nullptr;
         } else {
@@ -71,11 +68,7 @@ int run_summary(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, co
             HIPCHK(acx::summary_hist(r->d_matches, n, R->n_patterns, R->d_hist, st));
         }
         return ACX_OK;
-    };
-    rc = retire_find(body(), st, r, R);
-    if (rc != ACX_OK) { acx_free_summary(R); return rc; }
-    *out = R;
-    return ACX_OK;
+    });
 }
 
 // ACX_SUMMARY_HOST_MAX (bytes, read per call): calls up to this size reduce on the host, behind acx_find / acx_find_batch
@@ -130,26 +123,22 @@ int acx_summarize(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const ui
     if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
     if (len <= summary_host_max()) {
         // host route: the find entry points as they are (K0, the resident K0, the in-place read), then the reduction here
-        acx_match_t *m = nullptr;
-        uint64_t nm = 0;
-        std::vector<uint64_t> counts;
-        rc = host_find(a, B.hay, len, offsets ? B.rel.data() : nullptr, n_hay, overlapping, codepoints, &m, &nm, &counts);
-        if (rc != ACX_OK) return rc;
+        HostFind f;
+        if ((rc = f.find(a, B.hay, len, offsets ? B.rel.data() : nullptr, n_hay, overlapping, codepoints)) != ACX_OK) return rc;
         acx_summary *R = new_result<acx_summary>(a->device, false);
-        if (!R) { acx_free_matches(m); return ACX_ENOMEM; }
+        if (!R) return ACX_ENOMEM;
         R->what = what;
         R->n_hay = n_hay;
         R->n_patterns = a->host.n_patterns;
-        R->total = nm;
+        R->total = f.nm;
         try {
             if (what & ACX_SUM_FIRST) { R->any.assign((n_hay + 63) / 64, 0); R->first.resize(n_hay); }
             if (what & ACX_SUM_BY_PATTERN) R->hist.assign(R->n_patterns, 0);
         } catch (...) { rc = fail(ACX_ENOMEM, "out of memory"); }
         if (rc == ACX_OK)
-            rc = acx_summarize_host(m, nm, counts.data(), n_hay, R->n_patterns, what, R->any.data(), R->first.data(), R->hist.data());
-        R->counts = std::move(counts);
-        acx_free_matches(m);
-        if (rc != ACX_OK) { acx_free_summary(R); return rc; }
+            rc = acx_summarize_host(f.m, f.nm, f.counts.data(), n_hay, R->n_patterns, what, R->any.data(), R->first.data(), R->hist.data());
+        R->counts = std::move(f.counts);
+        if (rc != ACX_OK) { free_result(R); return rc; }
         *out = R;
         return ACX_OK;
     }

@@ -11,20 +11,21 @@ using namespace acxh;
 // stage's kernels.
 struct ACX_HIDDEN acx_tally : ResultBlock {
     uint64_t rows = 0, nnz = 0;
-    int64_t *part[3] = {nullptr, nullptr, nullptr}; // ACX_TALLY_*
 
-    static Layout layout(uint64_t rows, uint64_t nnz) { return block_layout({(rows + 1) * 8, nnz * 8, nnz * 8}); }
-    int alloc(uint64_t nnz_room) { // the block (by on_device) and the parts' places in it
-        const Layout L = layout(rows, nnz_room);
-        int rc = ResultBlock::alloc(L.bytes);
-        for (int k = 0; rc == ACX_OK && k < 3; k++) part[k] = (int64_t *)(base() + L.at[k]);
-        return rc;
+    // the block (by on_device) and its parts, ACX_TALLY_*, with room for nnz_room entries
+    int alloc(uint64_t nnz_room) { return alloc_parts({(rows + 1) * 8, nnz_room * 8, nnz_room * 8}); }
+    // ... of which nnz count, known only now (the host route gives every record room)
+    void set_nnz(uint64_t k) {
+        nnz = k;
+        resize_part(ACX_TALLY_PATTERN, k * 8);
+        resize_part(ACX_TALLY_COUNT, k * 8);
     }
+    int64_t *words(int which) const { return at<int64_t>(which); }
 };
 
 namespace {
 
-uint64_t part_words(const acx_tally_t *t, int which) { return which == ACX_TALLY_ROW_OFFSETS ? t->rows + 1 : t->nnz; }
+constexpr int N_PARTS = ACX_TALLY_COUNT + 1;
 
 // ACX_TALLY_HOST_MAX (bytes, read per call): batches up to this size reduce on the host, behind acx_find_batch.  The
 // default is ACX_SUMMARY_HOST_MAX's, which is itself not a measured crossover.
@@ -111,46 +112,34 @@ int stage_finish(const Stage *S, uint64_t nnz, int64_t *row_offsets, int64_t *pa
 // offsets: no offset is reported), then the stage on the same stream.  Returns when nnz is known; tally_compact may still
 // run (out->done).  d_hay, and G.offsets, must stay valid until then.
 int run_tally(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, const Segments &G, int overlapping, acx_tally_t **out) {
-    *out = nullptr;
     const uint64_t rows = rows_of(G).n;
-    acx_result *r = nullptr;
-    if (rows) { // (an empty batch: nothing to search, one row offset)
-        int rc = run_find(a, x, d_hay, len, G, overlapping, 0, &r);
-        if (rc != ACX_OK) return rc;
-    }
-    acx_tally_t *R = new_result<acx_tally_t>(a->device, true);
-    if (!R) { acx_free_result(r); return ACX_ENOMEM; }
-    hipStream_t st = x->stream;
-    R->rows = rows;
-    Stage S;
-    uint64_t *one_count = nullptr;
-    auto body = [&]() -> int {
+    // (an empty batch: nothing to search, one row offset)
+    return find_stage(a, x, d_hay, len, G, overlapping, 0, rows != 0, out, [&](FindStage<acx_tally_t> &F) -> int {
+        acx_tally_t *R = F.R;
+        R->rows = rows;
         int rc;
+        Stage S;
         if (rows) {
             const uint64_t *d_counts = nullptr;
-            if ((rc = counts_of(r, st, &one_count, &d_counts)) != ACX_OK) return rc;
-            rc = stage_count(a->device, st, r->d_matches, r->n, d_counts, rows, a->host.n_patterns, false, &S, &R->nnz);
+            if ((rc = F.counts(&d_counts)) != ACX_OK) return rc;
+            rc = stage_count(a->device, F.st, F.r->d_matches, F.r->n, d_counts, rows, a->host.n_patterns, false, &S, &R->nnz);
+            F.temp = S.block;
+            F.keep(S.long_block); // (the rare form: kept until acx_free_tally)
             if (rc != ACX_OK) return rc;
         }
         if ((rc = R->alloc(R->nnz)) != ACX_OK) return rc;
-        if (rows) return stage_finish(&S, R->nnz, R->part[0], R->part[1], R->part[2], st);
-        HIPCHK(hipMemsetAsync(R->part[0], 0, 8, st));
+        if (rows) return stage_finish(&S, R->nnz, R->words(0), R->words(1), R->words(2), F.st);
+        HIPCHK(hipMemsetAsync(R->words(0), 0, 8, F.st));
         return ACX_OK;
-    };
-    int rc = body();
-    if (S.long_block) R->scratch.push_back(S.long_block); // (the rare form: kept until acx_free_tally)
-    rc = retire_find(rc, st, r, R, S.block, one_count);
-    if (rc != ACX_OK) { acx_free_tally(R); return rc; }
-    *out = R;
-    return ACX_OK;
+    });
 }
 
 acx_tally_t *host_tally(int device, uint64_t rows, uint64_t nnz_room) {
     acx_tally_t *R = new_result<acx_tally_t>(device, false);
     if (!R) return nullptr;
     R->rows = rows;
-    if (R->alloc(nnz_room) != ACX_OK) { delete R; return nullptr; }
-    for (int k = 0; k < 3; k++) R->part[k][0] = 0;
+    if (R->alloc(nnz_room) != ACX_OK) { free_result(R); return nullptr; }
+    for (int k = 0; k < 3; k++) R->words(k)[0] = 0;
     return R;
 }
 
@@ -197,16 +186,14 @@ int acx_tally(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64
     if (len <= tally_host_max() || !n_hay) {
         // host route: acx_find_batch as it is (the small-call kernel, the in-place read, the staged pipeline), then the
         // reduction here
-        acx_match_t *m = nullptr;
-        uint64_t nm = 0;
-        std::vector<uint64_t> counts;
-        if (n_hay) rc = host_find(a, B.hay, len, B.rel.data(), n_hay, overlapping, 0, &m, &nm, &counts);
-        if (rc != ACX_OK) return rc;
-        acx_tally_t *R = host_tally(a->device, n_hay, nm);
-        if (!R) { acx_free_matches(m); return fail(ACX_ENOMEM, "out of memory"); }
-        rc = acx_tally_host(m, nm, counts.data(), n_hay, R->part[0], R->part[1], R->part[2], &R->nnz);
-        acx_free_matches(m);
-        if (rc != ACX_OK) { acx_free_tally(R); return rc; }
+        HostFind f;
+        if ((rc = f.find(a, B.hay, len, B.rel.data(), n_hay, overlapping, 0, n_hay != 0)) != ACX_OK) return rc;
+        acx_tally_t *R = host_tally(a->device, n_hay, f.nm);
+        if (!R) return fail(ACX_ENOMEM, "out of memory");
+        uint64_t nnz = 0;
+        rc = acx_tally_host(f.m, f.nm, f.counts.data(), n_hay, R->words(0), R->words(1), R->words(2), &nnz);
+        if (rc != ACX_OK) { free_result(R); return rc; }
+        R->set_nnz(nnz);
         *out = R;
         return ACX_OK;
     }
@@ -218,7 +205,7 @@ int acx_tally(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64
     });
     acx_tally_t *R = rc == ACX_OK ? host_tally(a->device, D->rows, D->nnz) : nullptr;
     if (R) R->nnz = D->nnz;
-    return copy_down(rc, D, R, D ? acx_tally::layout(D->rows, D->nnz).bytes : 0, "copying the tally to the host", out);
+    return copy_down(rc, D, R, D ? D->block_bytes : 0, "copying the tally to the host", out); // (the twins' blocks are one size)
 }
 
 int acx_tally_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
@@ -257,17 +244,8 @@ uint64_t acx_tally_nnz(const acx_tally_t *t) { return t ? t->nnz : 0; }
 uint64_t acx_tally_rows(const acx_tally_t *t) { return t ? t->rows : 0; }
 int acx_tally_on_device(const acx_tally_t *t) { return t ? t->on_device : 0; }
 
-const int64_t *acx_tally_data(const acx_tally_t *t, int which) {
-    if (!t || which < 0 || which > ACX_TALLY_COUNT) return nullptr;
-    return (const int64_t *)t->ptr_after_wait(t->part[which]);
-}
-
-int acx_tally_copy(const acx_tally_t *t, int which, int64_t *host_dst) {
-    if (!t || which < 0 || which > ACX_TALLY_COUNT) return fail(ACX_EINVAL, "no such part");
-    const uint64_t words = part_words(t, which);
-    if (words && !host_dst) return fail(ACX_EINVAL, "null argument");
-    return t->copy_out(host_dst, t->part[which], words * 8);
-}
+const int64_t *acx_tally_data(const acx_tally_t *t, int which) { return (const int64_t *)part_ptr(t, which, N_PARTS); }
+int acx_tally_copy(const acx_tally_t *t, int which, int64_t *host_dst) { return part_copy(t, which, N_PARTS, host_dst, "no such part"); }
 
 void acx_free_tally(acx_tally_t *t) { free_result(t); }
 
