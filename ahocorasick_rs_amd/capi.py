@@ -94,6 +94,129 @@ def _preload_hip_runtime() -> None:
         pass
 
 
+vp, u64, i64, u32, i32, u8 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint8
+_out, _u64p = ctypes.POINTER(vp), ctypes.POINTER(u64)  # where a call leaves a handle / a count
+
+# ---- the declarations of include/acx.h, as data (tests/test_capi_abi_cpu.py holds them against the header)
+# A stage with a host and a device form: name -> the arguments between the haystack and `out`.  _declare_pair makes
+#   acx_<name>(a, hay, len, offsets, n_hay, *tail, out)
+#   acx_<name>_device(a, d_hay, len, d_offsets, n_hay, uniform_len, *tail, out)
+_PAIRS = {
+    "replace": [vp, vp, u64], "summarize": [i32, i32, u32], "find_columns": [i32, i32], "tally": [i32],
+    "filter": [i32, u64, u32], "score": [i32, vp, u64], "filter_scored": [i32, vp, u64, i64, u32], "mask": [i32, u8, u32],
+    "spans": [i32, i32, u64], "snippets": [i32, u64, u32],
+}
+# A result type: prefix -> (its size getters, whether _data / _copy take a `which`; None: it has no such pair).  _declare_result
+# adds acx_<prefix>_on_device and acx_free_<prefix>.
+_RESULTS = {
+    "summary": (("total",), None), "columns": (("count", "rows"), True), "tally": (("nnz", "rows"), True),
+    "filtered": (("rows", "bytes"), True), "scores": (("rows",), False), "masked": (("bytes", "rows"), False),
+    "rows": (("count", "bytes"), None), "spans": (("count", "rows"), True), "snippets": (("count", "rows", "nbytes"), True),
+}
+# Everything else, one row each: name -> arguments, or (arguments, what it returns) where that is no status.  (acx_version is
+# declared by lib() itself, ahead of the version check.)
+_SINGLES = {
+    "acx_last_error": ([], ctypes.c_char_p),
+    "acx_device_count": [ctypes.POINTER(i32)],
+    "acx_set_device": [i32],
+    "acx_build": [vp, vp, u64, i32, i32, _out],
+    "acx_build_ex": [vp, vp, u64, i32, i32, u32, _out],
+    "acx_free_automaton": ([vp], None),
+    "acx_automaton_info": [vp, ctypes.POINTER(Info)],
+    "acx_set_kernel": [vp, i32],
+    "acx_compile_host": [vp, vp, u64, i32, _out],
+    "acx_compile_host_ex": [vp, vp, u64, i32, u32, _out],
+    "acx_host_tables": [vp, ctypes.POINTER(HostTables)],
+    "acx_free_host": ([vp], None),
+    "acx_filter_hash": ([u32], u32),
+    "acx_prefix_slot": ([u64, u32, u32], u32),
+    "acx_find": [vp, vp, u64, i32, i32, _out, _u64p],
+    "acx_free_matches": ([vp], None),
+    "acx_find_batch": [vp, vp, vp, u64, i32, i32, _out, _u64p, vp],
+    "acx_find_device": [vp, vp, u64, vp, u64, u64, i32, i32, _out],
+    "acx_replicate": [vp, i32, _out],
+    "acx_automaton_device": [vp],
+    "acx_shard_range": ([u64, i32, i32, _u64p, _u64p], None),
+    "acx_find_batch_multi": [vp, i32, vp, vp, u64, i32, i32, _out, _u64p, vp],
+    "acx_result_count": ([vp], u64),
+    "acx_result_device_matches": ([vp], vp),
+    "acx_result_device_counts": ([vp], vp),
+    "acx_result_copy": [vp, vp],
+    "acx_result_copy_counts": [vp, vp],
+    "acx_free_result": ([vp], None),
+    "acx_profile_enable": [vp, i32],
+    "acx_profile_read": [vp, ctypes.POINTER(Profile), i32],
+    "acx_path_stats": [vp, _u64p, i32],
+    "acx_device_alloc": [_out, u64],
+    "acx_device_free": [vp],
+    "acx_device_upload": [vp, vp, u64],
+    "acx_device_download": [vp, vp, u64],
+    "acx_device_synchronize": [],
+    "acx_device_synchronize_on": [i32],
+    "acx_comm_init_all": [ctypes.POINTER(i32), i32, _out],
+    "acx_comm_unique_id": [vp],
+    "acx_comm_init_rank": [vp, i32, i32, i32, _out],
+    "acx_comm_world": [vp],
+    "acx_comm_local_ranks": [vp],
+    "acx_comm_allgather_counts": [vp, vp, vp],
+    "acx_comm_free": ([vp], None),
+    "acx_output_offsets": ([vp, i32, vp], None),
+    "acx_generate_haystack": [vp, vp, u64, i32, u64, u64],
+    "acx_replaced_len": ([vp], u64),
+    "acx_replaced_offsets": [vp, vp],
+    "acx_replaced_copy": [vp, vp],
+    "acx_replaced_device_bytes": ([vp], vp),
+    "acx_free_replaced": ([vp], None),
+    "acx_splice_host": [vp, u64, vp, u64, vp, vp, u64, vp, _u64p],
+    **{"acx_summary_" + part: [vp, vp] for part in ("counts", "any", "first", "by_pattern")},
+    **{"acx_summary_device_" + part: ([vp], vp) for part in ("counts", "any", "first", "by_pattern")},
+    "acx_summarize_host": [vp, u64, vp, u64, u64, u32, vp, vp, vp],
+    "acx_split_host": [vp, u64, vp, vp, vp],
+    "acx_split_device": [vp, u64, vp, vp, vp],
+    "acx_tally_host": [vp, u64, vp, u64, vp, vp, vp, _u64p],
+    "acx_tally_rows_device": [vp, u64, vp, u64, u64, vp, vp, vp, _u64p],
+    "acx_filter_host": [vp, u64, vp, u64, vp, u64, u32, vp, vp, vp, _u64p, _u64p],
+    "acx_filter_rows_device": [vp, u64, vp, u64, u64, vp, u64, u32, vp, vp, vp, _u64p, _u64p],
+    "acx_score_host": [vp, u64, vp, u64, vp, u64, vp],
+    "acx_score_rows_device": [vp, u64, vp, u64, vp, u64, vp],
+    "acx_masked_offsets": ([vp], vp),
+    "acx_masked_copy_offsets": [vp, vp],
+    "acx_mask_host": [vp, u64, vp, u64, vp, u64, vp, u8, u32, vp],
+    "acx_mask_rows_device": [vp, u64, vp, u64, u64, vp, u64, vp, u8, u32, vp],
+    "acx_split_rows": [vp, u64, u8, _out],
+    "acx_split_rows_device": [vp, u64, u8, _out],
+    "acx_rows_device": [vp],
+    "acx_rows_offsets": ([vp], vp),
+    "acx_rows_copy": [vp, vp],
+    "acx_split_rows_host": [vp, u64, u8, vp, u64, _u64p],
+    "acx_split_rows_into_device": [vp, u64, u8, vp, u64, _u64p],
+    "acx_spans_host": [vp, u64, vp, u64, u64, vp, vp, vp, _u64p],
+    "acx_spans_rows_device": [vp, u64, vp, u64, u64, vp, vp, vp, _u64p],
+    "acx_snippets_host": [vp, u64, vp, u64, vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, _u64p],
+    "acx_snippets_rows_device": [vp, u64, vp, u64, vp, u64, vp, u64, u64, u32, vp, vp, vp, vp, vp, u64, _u64p],
+}
+
+
+def _declare(L, name: str, argtypes, restype=i32) -> None:
+    fn = getattr(L, name)
+    fn.argtypes, fn.restype = list(argtypes), restype
+
+
+def _declare_pair(L, name: str, tail) -> None:
+    _declare(L, "acx_" + name, [vp, vp, u64, vp, u64, *tail, _out])
+    _declare(L, f"acx_{name}_device", [vp, vp, u64, vp, u64, u64, *tail, _out])
+
+
+def _declare_result(L, prefix: str, sizes, which: Optional[bool]) -> None:
+    for size in sizes:
+        _declare(L, f"acx_{prefix}_{size}", [vp], u64)
+    _declare(L, f"acx_{prefix}_on_device", [vp])
+    _declare(L, "acx_free_" + prefix, [vp], None)
+    if which is not None:
+        _declare(L, f"acx_{prefix}_data", [vp, i32] if which else [vp], vp)
+        _declare(L, f"acx_{prefix}_copy", [vp, i32, vp] if which else [vp, vp])
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -107,207 +230,17 @@ def lib() -> ctypes.CDLL:
             " (hipcc --offload-arch=gfx950).  There is no CPU fallback.")
     _preload_hip_runtime()
     L = ctypes.CDLL(os.environ.get("ACX_LIB", _SO), mode=ctypes.RTLD_GLOBAL)  # ACX_LIB: experiments with variant builds
-    vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
-    L.acx_version.restype = i32
+    _declare(L, "acx_version", [])
     # (ACX_LIB_ANY_ABI=1 with ACX_LIB: same-box measurements against an older build of the library)
     if L.acx_version() != ABI_VERSION and not (os.environ.get("ACX_LIB") and os.environ.get("ACX_LIB_ANY_ABI")):
         raise ImportError(f"libacx_hip.so speaks C ABI version {L.acx_version()}, this binding version {ABI_VERSION}: "
                           "rebuild (python -c 'import __graft_entry__ as g; g.build()')")
-    L.acx_last_error.restype = ctypes.c_char_p
-    L.acx_device_count.argtypes = [ctypes.POINTER(i32)]
-    L.acx_set_device.argtypes = [i32]
-    L.acx_build.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(vp)]
-    L.acx_build_ex.argtypes = [vp, vp, u64, i32, i32, ctypes.c_uint32, ctypes.POINTER(vp)]
-    L.acx_free_automaton.argtypes = [vp]
-    L.acx_free_automaton.restype = None
-    L.acx_automaton_info.argtypes = [vp, ctypes.POINTER(Info)]
-    L.acx_set_kernel.argtypes = [vp, i32]
-    L.acx_compile_host.argtypes = [vp, vp, u64, i32, ctypes.POINTER(vp)]
-    L.acx_compile_host_ex.argtypes = [vp, vp, u64, i32, ctypes.c_uint32, ctypes.POINTER(vp)]
-    L.acx_host_tables.argtypes = [vp, ctypes.POINTER(HostTables)]
-    L.acx_filter_hash.argtypes = [ctypes.c_uint32]
-    L.acx_filter_hash.restype = ctypes.c_uint32
-    L.acx_prefix_slot.argtypes = [u64, ctypes.c_uint32, ctypes.c_uint32]
-    L.acx_prefix_slot.restype = ctypes.c_uint32
-    L.acx_free_host.argtypes = [vp]
-    L.acx_free_host.restype = None
-    L.acx_find.argtypes = [vp, vp, u64, i32, i32, ctypes.POINTER(vp), ctypes.POINTER(u64)]
-    L.acx_free_matches.argtypes = [vp]
-    L.acx_free_matches.restype = None
-    L.acx_find_batch.argtypes = [vp, vp, vp, u64, i32, i32, ctypes.POINTER(vp),
-                                 ctypes.POINTER(u64), vp]
-    L.acx_find_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, i32, ctypes.POINTER(vp)]
-    L.acx_replicate.argtypes = [vp, i32, ctypes.POINTER(vp)]
-    L.acx_automaton_device.argtypes = [vp]
-    L.acx_shard_range.argtypes = [u64, i32, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
-    L.acx_shard_range.restype = None
-    L.acx_find_batch_multi.argtypes = [vp, i32, vp, vp, u64, i32, i32, ctypes.POINTER(vp), ctypes.POINTER(u64), vp]
-    L.acx_result_count.argtypes = [vp]
-    L.acx_result_count.restype = u64
-    L.acx_result_device_matches.argtypes = [vp]
-    L.acx_result_device_matches.restype = vp
-    L.acx_result_device_counts.argtypes = [vp]
-    L.acx_result_device_counts.restype = vp
-    L.acx_result_copy.argtypes = [vp, vp]
-    L.acx_result_copy_counts.argtypes = [vp, vp]
-    L.acx_free_result.argtypes = [vp]
-    L.acx_free_result.restype = None
-    L.acx_profile_enable.argtypes = [vp, i32]
-    L.acx_profile_read.argtypes = [vp, ctypes.POINTER(Profile), i32]
-    L.acx_path_stats.argtypes = [vp, ctypes.POINTER(u64), i32]
-    L.acx_device_alloc.argtypes = [ctypes.POINTER(vp), u64]
-    L.acx_device_free.argtypes = [vp]
-    L.acx_device_upload.argtypes = [vp, vp, u64]
-    L.acx_device_download.argtypes = [vp, vp, u64]
-    L.acx_device_synchronize.argtypes = []
-    L.acx_device_synchronize_on.argtypes = [i32]
-    L.acx_comm_init_all.argtypes = [ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
-    L.acx_comm_unique_id.argtypes = [vp]
-    L.acx_comm_init_rank.argtypes = [vp, i32, i32, i32, ctypes.POINTER(vp)]
-    L.acx_comm_world.argtypes = [vp]
-    L.acx_comm_local_ranks.argtypes = [vp]
-    L.acx_comm_allgather_counts.argtypes = [vp, vp, vp]
-    L.acx_comm_free.argtypes = [vp]
-    L.acx_comm_free.restype = None
-    L.acx_output_offsets.argtypes = [vp, i32, vp]
-    L.acx_output_offsets.restype = None
-    L.acx_generate_haystack.argtypes = [vp, vp, u64, i32, u64, u64]
-    L.acx_replace.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, ctypes.POINTER(vp)]
-    L.acx_replace_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, vp, u64, ctypes.POINTER(vp)]
-    L.acx_replaced_len.argtypes = [vp]
-    L.acx_replaced_len.restype = u64
-    L.acx_replaced_offsets.argtypes = [vp, vp]
-    L.acx_replaced_copy.argtypes = [vp, vp]
-    L.acx_replaced_device_bytes.argtypes = [vp]
-    L.acx_replaced_device_bytes.restype = vp
-    L.acx_free_replaced.argtypes = [vp]
-    L.acx_free_replaced.restype = None
-    L.acx_splice_host.argtypes = [vp, u64, vp, u64, vp, vp, u64, vp, ctypes.POINTER(u64)]
-    L.acx_summarize.argtypes = [vp, vp, u64, vp, u64, i32, i32, ctypes.c_uint32, ctypes.POINTER(vp)]
-    L.acx_summarize_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, i32, ctypes.c_uint32, ctypes.POINTER(vp)]
-    L.acx_summary_total.argtypes = [vp]
-    L.acx_summary_total.restype = u64
-    L.acx_summary_on_device.argtypes = [vp]
-    for name in ("counts", "any", "first", "by_pattern"):
-        getattr(L, "acx_summary_" + name).argtypes = [vp, vp]
-        getattr(L, "acx_summary_device_" + name).argtypes = [vp]
-        getattr(L, "acx_summary_device_" + name).restype = vp
-    L.acx_free_summary.argtypes = [vp]
-    L.acx_free_summary.restype = None
-    L.acx_summarize_host.argtypes = [vp, u64, vp, u64, u64, ctypes.c_uint32, vp, vp, vp]
-    L.acx_find_columns.argtypes = [vp, vp, u64, vp, u64, i32, i32, ctypes.POINTER(vp)]
-    L.acx_find_columns_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, i32, ctypes.POINTER(vp)]
-    for name in ("count", "rows"):
-        getattr(L, "acx_columns_" + name).argtypes = [vp]
-        getattr(L, "acx_columns_" + name).restype = u64
-    L.acx_columns_on_device.argtypes = [vp]
-    L.acx_columns_data.argtypes = [vp, i32]
-    L.acx_columns_data.restype = vp
-    L.acx_columns_copy.argtypes = [vp, i32, vp]
-    L.acx_free_columns.argtypes = [vp]
-    L.acx_free_columns.restype = None
-    L.acx_split_host.argtypes = [vp, u64, vp, vp, vp]
-    L.acx_split_device.argtypes = [vp, u64, vp, vp, vp]
-    L.acx_tally.argtypes = [vp, vp, u64, vp, u64, i32, ctypes.POINTER(vp)]
-    L.acx_tally_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, ctypes.POINTER(vp)]
-    for name in ("nnz", "rows"):
-        getattr(L, "acx_tally_" + name).argtypes = [vp]
-        getattr(L, "acx_tally_" + name).restype = u64
-    L.acx_tally_on_device.argtypes = [vp]
-    L.acx_tally_data.argtypes = [vp, i32]
-    L.acx_tally_data.restype = vp
-    L.acx_tally_copy.argtypes = [vp, i32, vp]
-    L.acx_free_tally.argtypes = [vp]
-    L.acx_free_tally.restype = None
-    L.acx_tally_host.argtypes = [vp, u64, vp, u64, vp, vp, vp, ctypes.POINTER(u64)]
-    L.acx_tally_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, ctypes.POINTER(u64)]
-    u32 = ctypes.c_uint32
-    L.acx_filter.argtypes = [vp, vp, u64, vp, u64, i32, u64, u32, ctypes.POINTER(vp)]
-    L.acx_filter_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, u64, u32, ctypes.POINTER(vp)]
-    for name in ("rows", "bytes"):
-        getattr(L, "acx_filtered_" + name).argtypes = [vp]
-        getattr(L, "acx_filtered_" + name).restype = u64
-    L.acx_filtered_on_device.argtypes = [vp]
-    L.acx_filtered_data.argtypes = [vp, i32]
-    L.acx_filtered_data.restype = vp
-    L.acx_filtered_copy.argtypes = [vp, i32, vp]
-    L.acx_free_filtered.argtypes = [vp]
-    L.acx_free_filtered.restype = None
-    L.acx_filter_host.argtypes = [vp, u64, vp, u64, vp, u64, u32, vp, vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
-    L.acx_filter_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, u64, u32, vp, vp, vp, ctypes.POINTER(u64),
-                                         ctypes.POINTER(u64)]
-    i64 = ctypes.c_int64
-    L.acx_score.argtypes = [vp, vp, u64, vp, u64, i32, vp, u64, ctypes.POINTER(vp)]
-    L.acx_score_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, vp, u64, ctypes.POINTER(vp)]
-    L.acx_scores_rows.argtypes = [vp]
-    L.acx_scores_rows.restype = u64
-    L.acx_scores_on_device.argtypes = [vp]
-    L.acx_scores_data.argtypes = [vp]
-    L.acx_scores_data.restype = vp
-    L.acx_scores_copy.argtypes = [vp, vp]
-    L.acx_free_scores.argtypes = [vp]
-    L.acx_free_scores.restype = None
-    L.acx_score_host.argtypes = [vp, u64, vp, u64, vp, u64, vp]
-    L.acx_score_rows_device.argtypes = [vp, u64, vp, u64, vp, u64, vp]
-    L.acx_filter_scored.argtypes = [vp, vp, u64, vp, u64, i32, vp, u64, i64, u32, ctypes.POINTER(vp)]
-    L.acx_filter_scored_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, vp, u64, i64, u32, ctypes.POINTER(vp)]
-    u8 = ctypes.c_uint8
-    L.acx_mask.argtypes = [vp, vp, u64, vp, u64, i32, u8, u32, ctypes.POINTER(vp)]
-    L.acx_mask_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, u8, u32, ctypes.POINTER(vp)]
-    for name in ("bytes", "rows"):
-        getattr(L, "acx_masked_" + name).argtypes = [vp]
-        getattr(L, "acx_masked_" + name).restype = u64
-    L.acx_masked_on_device.argtypes = [vp]
-    for name in ("data", "offsets"):
-        getattr(L, "acx_masked_" + name).argtypes = [vp]
-        getattr(L, "acx_masked_" + name).restype = vp
-    L.acx_masked_copy.argtypes = [vp, vp]
-    L.acx_masked_copy_offsets.argtypes = [vp, vp]
-    L.acx_free_masked.argtypes = [vp]
-    L.acx_free_masked.restype = None
-    L.acx_mask_host.argtypes = [vp, u64, vp, u64, vp, u64, vp, u8, u32, vp]
-    L.acx_mask_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, u64, vp, u8, u32, vp]
-    L.acx_split_rows.argtypes = [vp, u64, u8, ctypes.POINTER(vp)]
-    L.acx_split_rows_device.argtypes = [vp, u64, u8, ctypes.POINTER(vp)]
-    for name in ("count", "bytes"):
-        getattr(L, "acx_rows_" + name).argtypes = [vp]
-        getattr(L, "acx_rows_" + name).restype = u64
-    L.acx_rows_on_device.argtypes = [vp]
-    L.acx_rows_device.argtypes = [vp]
-    L.acx_rows_offsets.argtypes = [vp]
-    L.acx_rows_offsets.restype = vp
-    L.acx_rows_copy.argtypes = [vp, vp]
-    L.acx_free_rows.argtypes = [vp]
-    L.acx_free_rows.restype = None
-    L.acx_split_rows_host.argtypes = [vp, u64, u8, vp, u64, ctypes.POINTER(u64)]
-    L.acx_split_rows_into_device.argtypes = [vp, u64, u8, vp, u64, ctypes.POINTER(u64)]
-    L.acx_spans.argtypes = [vp, vp, u64, vp, u64, i32, i32, u64, ctypes.POINTER(vp)]
-    L.acx_spans_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, i32, u64, ctypes.POINTER(vp)]
-    for name in ("count", "rows"):
-        getattr(L, "acx_spans_" + name).argtypes = [vp]
-        getattr(L, "acx_spans_" + name).restype = u64
-    L.acx_spans_on_device.argtypes = [vp]
-    L.acx_spans_data.argtypes = [vp, i32]
-    L.acx_spans_data.restype = vp
-    L.acx_spans_copy.argtypes = [vp, i32, vp]
-    L.acx_free_spans.argtypes = [vp]
-    L.acx_free_spans.restype = None
-    L.acx_spans_host.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, ctypes.POINTER(u64)]
-    L.acx_spans_rows_device.argtypes = [vp, u64, vp, u64, u64, vp, vp, vp, ctypes.POINTER(u64)]
-    L.acx_snippets.argtypes = [vp, vp, u64, vp, u64, i32, u64, u32, ctypes.POINTER(vp)]
-    L.acx_snippets_device.argtypes = [vp, vp, u64, vp, u64, u64, i32, u64, u32, ctypes.POINTER(vp)]
-    for name in ("count", "rows", "nbytes"):
-        getattr(L, "acx_snippets_" + name).argtypes = [vp]
-        getattr(L, "acx_snippets_" + name).restype = u64
-    L.acx_snippets_on_device.argtypes = [vp]
-    L.acx_snippets_data.argtypes = [vp, i32]
-    L.acx_snippets_data.restype = vp
-    L.acx_snippets_copy.argtypes = [vp, i32, vp]
-    L.acx_free_snippets.argtypes = [vp]
-    L.acx_free_snippets.restype = None
-    L.acx_snippets_host.argtypes = [vp, u64, vp, u64, vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, ctypes.POINTER(u64)]
-    L.acx_snippets_rows_device.argtypes = [vp, u64, vp, u64, vp, u64, vp, u64, u64, u32, vp, vp, vp, vp, vp, u64,
-                                           ctypes.POINTER(u64)]
+    for name, tail in _PAIRS.items():
+        _declare_pair(L, name, tail)
+    for prefix, (sizes, which) in _RESULTS.items():
+        _declare_result(L, prefix, sizes, which)
+    for name, row in _SINGLES.items():
+        _declare(L, name, *(row if isinstance(row, tuple) else (row,)))
     _lib = L
     return L
 
@@ -376,13 +309,41 @@ class _Handle:
             pass
 
 
+class _Size:
+    """a size of a result as an attribute: asked of the C getter acx_<prefix>_<getter> whenever it is read"""
+
+    def __init__(self, getter: str):
+        self.getter = getter
+
+    def __get__(self, obj, cls=None):
+        return self if obj is None else int(obj._fn(self.getter)(obj._h))
+
+
 class _Result(_Handle):
-    """... of a result whose parts lie in HBM or in host memory: _ON_DEVICE names the C function that tells which"""
-    _ON_DEVICE = ""
+    """... of a result whose parts lie in HBM or in host memory (on_device tells which).  A subclass names its C prefix
+    (_PREFIX: its functions are acx_<prefix>_<name>, its free is acx_free_<prefix>) and its sizes (_Size); _address and
+    _copy_out are the two ways to a part."""
+    _PREFIX = ""
+
+    def __init_subclass__(cls):
+        cls._FREE = "acx_free_" + cls._PREFIX
+
+    def _fn(self, name: str):
+        return getattr(lib(), f"acx_{self._PREFIX}_{name}")
 
     @property
     def on_device(self) -> bool:
-        return bool(getattr(lib(), self._ON_DEVICE)(self._h))
+        return bool(self._fn("on_device")(self._h))
+
+    def _address(self, name: str, *which: int) -> int:
+        """host or device address of a part (by on_device), behind the device work; 0: the result has no such part"""
+        return self._fn(name)(self._h, *which) or 0
+
+    def _copy_out(self, name: str, n: int, dtype, *which: int) -> np.ndarray:
+        """n elements copied out by acx_<prefix>_<name>; nothing to copy: a null destination"""
+        out = np.zeros(n, dtype=dtype)
+        _check(self._fn(name)(self._h, *which, out.ctypes.data if out.size else None))
+        return out
 
 
 class HostAutomaton(_Handle):
@@ -593,36 +554,31 @@ class DeviceReplaced(_Handle):
         return out
 
     def download(self) -> bytes:
-        return _replaced_bytes(self._h)
+        buf = bytearray(self.nbytes)
+        if buf:
+            _check(lib().acx_replaced_copy(self._h, (ctypes.c_uint8 * len(buf)).from_buffer(buf)))
+        return bytes(buf)
 
 
 class DeviceSummary(_Result):
     """The summaries of Automaton.summarize / summarize_batch / summarize_device (acx_summary_t): reduced in HBM
     (on_device) or on the host; every part is copied out when it is asked for.  A part that `what` did not name raises
     ValueError (code EINVAL)."""
-    _ON_DEVICE, _FREE = "acx_summary_on_device", "acx_free_summary"
+    _PREFIX = "summary"
+    total = _Size("total")
 
     def __init__(self, handle: int, n_hay: int, n_patterns: int):
         super().__init__(handle)
         self.n_hay = n_hay
         self.n_patterns = n_patterns
 
-    @property
-    def total(self) -> int:
-        return int(lib().acx_summary_total(self._h))
-
-    def _part(self, name: str, n: int, dtype) -> np.ndarray:
-        out = np.zeros(n, dtype=dtype)
-        _check(getattr(lib(), "acx_summary_" + name)(self._h, out.ctypes.data if n else None))
-        return out
-
     def counts(self) -> np.ndarray:
         """matches per haystack"""
-        return self._part("counts", self.n_hay, np.uint64)
+        return self._copy_out("counts", self.n_hay, np.uint64)
 
     def any_bits(self) -> np.ndarray:
         """the bitmap as the library keeps it: (n_hay + 63) // 64 words, LSB first"""
-        return self._part("any", (self.n_hay + 63) // 64, np.uint64)
+        return self._copy_out("any", (self.n_hay + 63) // 64, np.uint64)
 
     def any(self) -> np.ndarray:
         """one bool per haystack: it has a match"""
@@ -631,15 +587,34 @@ class DeviceSummary(_Result):
 
     def first(self) -> np.ndarray:
         """every haystack's first match (MATCH_DTYPE; pattern == NO_MATCH: none)"""
-        return self._part("first", self.n_hay, MATCH_DTYPE)
+        return self._copy_out("first", self.n_hay, MATCH_DTYPE)
 
     def by_pattern(self) -> np.ndarray:
         """matches of the whole call per pattern"""
-        return self._part("by_pattern", self.n_patterns, np.uint64)
+        return self._copy_out("by_pattern", self.n_patterns, np.uint64)
 
     def device_ptr(self, name: str) -> int:
         """where the part ("counts", "any", "first", "by_pattern") lies in HBM (waits for the reduction); 0 on the host route"""
-        return getattr(lib(), "acx_summary_device_" + name)(self._h) or 0
+        return self._address("device_" + name)
+
+
+def _records(matches) -> np.ndarray:
+    """rows of (pattern, start, end) as a C-contiguous (n, 3) uint64 array"""
+    return np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+
+
+def _u64(seq) -> Optional[np.ndarray]:
+    """a C-contiguous flat uint64 array (None stays None: counts or offsets that were not given)"""
+    return None if seq is None else np.ascontiguousarray(np.asarray(seq, dtype=np.uint64).reshape(-1))
+
+
+def _ptr(arr: Optional[np.ndarray], empty: Optional[int] = None) -> Optional[int]:
+    """the array's address; `empty` (NULL) when it has no element, NULL when there is no array.  An empty batch is still a
+    batch: the *_host definitions take its counts from a non-null pointer, `empty` = the address of a spare word."""
+    return None if arr is None else (arr.ctypes.data if len(arr) else empty)
+
+
+_SPARE = np.zeros(1, dtype=np.uint64)
 
 
 def summarize_host(matches, counts: Optional[Sequence[int]], n_patterns: int, what: int = SUM_FIRST | SUM_BY_PATTERN):
@@ -647,61 +622,50 @@ def summarize_host(matches, counts: Optional[Sequence[int]], n_patterns: int, wh
     counts[h] rows each -- None: one haystack) on the host, no device involved -> (any, first, by_pattern): one bool per
     haystack, MATCH_DTYPE rows, one count per pattern; a part `what` does not name is None.  ValueError (code EINVAL) when
     the counts do not sum to the rows or a row names a pattern >= n_patterns."""
-    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
-    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    m, c = _records(matches), _u64(counts)
     n_hay = 1 if c is None else len(c)
     bits = np.zeros((n_hay + 63) // 64 + 1, dtype=np.uint64)
     first = np.zeros(n_hay + 1, dtype=MATCH_DTYPE)
     hist = np.zeros(n_patterns + 1, dtype=np.uint64)
-    pad = np.zeros(1, dtype=np.uint64)  # (an empty batch is still a batch: a non-null counts pointer)
-    _check(lib().acx_summarize_host(m.ctypes.data if len(m) else None, len(m),
-                                    None if c is None else (c.ctypes.data if len(c) else pad.ctypes.data), n_hay, n_patterns,
-                                    what, bits.ctypes.data, first.ctypes.data, hist.ctypes.data))
+    _check(lib().acx_summarize_host(_ptr(m), len(m), _ptr(c, _SPARE.ctypes.data), n_hay, n_patterns, what, bits.ctypes.data,
+                                    first.ctypes.data, hist.ctypes.data))
     any_ = np.unpackbits(bits.view(np.uint8), bitorder="little")[:n_hay].astype(bool)
     return (any_ if what & SUM_FIRST else None, first[:n_hay] if what & SUM_FIRST else None,
             hist[:n_patterns] if what & SUM_BY_PATTERN else None)
 
 
 class _PartsResult(_Result):
-    """What DeviceColumns, DeviceTally and DeviceFiltered share: a handle of the C ABI whose parts lie in HBM (on_device) or
-    in host memory.  A subclass names its three C functions (_ON_DEVICE, _DATA, _COPY, _FREE) and, in _part_shape(which), a
-    part's length and element type."""
-    _DATA = _COPY = ""
+    """A result whose parts acx_<prefix>_data / acx_<prefix>_copy address by a `which`.  A subclass states them in _PARTS:
+    which -> (the size the part goes by, its words beyond that size, its element type)."""
+    _PARTS: dict = {}
 
     def data_ptr(self, which: int) -> int:
         """host or device address of the part (by on_device), behind the device work; 0: the result has no such part"""
-        return getattr(lib(), self._DATA)(self._h, which) or 0
+        return self._address("data", which)
 
     def _copy_part(self, which: int) -> np.ndarray:
-        n, dtype = self._part_shape(which)
-        out = np.zeros(n, dtype=dtype)
-        _check(getattr(lib(), self._COPY)(self._h, which, out.ctypes.data if out.size else None))
-        return out
+        # (a `which` the class does not state has no size here: the C side refuses it before it looks at the destination)
+        size, beyond, dtype = self._PARTS.get(which, (None, 0, np.int64))
+        return self._copy_out("copy", getattr(self, size) + beyond if size else 0, dtype, which)
 
 
-class DeviceColumns(_PartsResult):
-    """The columns of Automaton.find_columns / find_columns_batch / find_columns_device (acx_columns_t): three int64
-    columns of `count` words and, for a batch, n_hay + 1 row offsets -- in HBM (on_device) or in host memory.  column()
-    copies one out; data_ptr() is where it lies (both wait for the split kernel)."""
-    _ON_DEVICE, _DATA, _COPY, _FREE = "acx_columns_on_device", "acx_columns_data", "acx_columns_copy", "acx_free_columns"
+class _BatchPartsResult(_PartsResult):
+    """... and whose row offsets exist for a batch only (`batch`: the call was one)"""
 
     def __init__(self, handle: int, batch: bool):
         super().__init__(handle)
         self.batch = batch
 
-    @property
-    def count(self) -> int:
-        return int(lib().acx_columns_count(self._h))
 
-    @property
-    def rows(self) -> int:
-        return int(lib().acx_columns_rows(self._h))
-
-    def _part_shape(self, which: int):
-        return (self.rows + 1 if which == COL_ROW_OFFSETS else self.count), np.int64
-
-    def column(self, which: int) -> np.ndarray:
-        return self._copy_part(which)
+class DeviceColumns(_BatchPartsResult):
+    """The columns of Automaton.find_columns / find_columns_batch / find_columns_device (acx_columns_t): three int64
+    columns of `count` words and, for a batch, n_hay + 1 row offsets -- in HBM (on_device) or in host memory.  column()
+    copies one out; data_ptr() is where it lies (both wait for the split kernel)."""
+    _PREFIX = "columns"
+    count, rows = _Size("count"), _Size("rows")
+    _PARTS = {COL_PATTERN: ("count", 0, np.int64), COL_START: ("count", 0, np.int64), COL_END: ("count", 0, np.int64),
+              COL_ROW_OFFSETS: ("rows", 1, np.int64)}
+    column = _PartsResult._copy_part
 
     def pattern(self) -> np.ndarray:
         return self.column(COL_PATTERN)
@@ -718,9 +682,9 @@ class DeviceColumns(_PartsResult):
 
 def split_host(matches) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """acx_split_host: rows of (pattern, start, end) -> the three int64 columns, on the host, no device involved"""
-    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+    m = _records(matches)
     cols = [np.zeros(len(m), dtype=np.int64) for _ in range(3)]
-    _check(lib().acx_split_host(m.ctypes.data if len(m) else None, len(m), *[c.ctypes.data if len(m) else None for c in cols]))
+    _check(lib().acx_split_host(_ptr(m), len(m), *[_ptr(c) for c in cols]))
     return cols[0], cols[1], cols[2]
 
 
@@ -734,21 +698,10 @@ class DeviceTally(_PartsResult):
     """The result of Automaton.tally / tally_device (acx_tally_t): per-haystack pattern counts in CSR form -- rows + 1 row
     offsets, nnz patterns (ascending within a row) and nnz counts, int64 -- in HBM (on_device) or in host memory.  part()
     copies one out; data_ptr() is where it lies (both wait for the device stage)."""
-    _ON_DEVICE, _DATA, _COPY, _FREE = "acx_tally_on_device", "acx_tally_data", "acx_tally_copy", "acx_free_tally"
-
-    @property
-    def nnz(self) -> int:
-        return int(lib().acx_tally_nnz(self._h))
-
-    @property
-    def rows(self) -> int:
-        return int(lib().acx_tally_rows(self._h))
-
-    def _part_shape(self, which: int):
-        return (self.rows + 1 if which == TALLY_ROW_OFFSETS else self.nnz), np.int64
-
-    def part(self, which: int) -> np.ndarray:
-        return self._copy_part(which)
+    _PREFIX = "tally"
+    nnz, rows = _Size("nnz"), _Size("rows")
+    _PARTS = {TALLY_ROW_OFFSETS: ("rows", 1, np.int64), TALLY_PATTERN: ("nnz", 0, np.int64), TALLY_COUNT: ("nnz", 0, np.int64)}
+    part = _PartsResult._copy_part
 
     def row_offsets(self) -> np.ndarray:
         return self.part(TALLY_ROW_OFFSETS)
@@ -764,14 +717,11 @@ def tally_host(matches, counts: Sequence[int]) -> Tuple[np.ndarray, np.ndarray, 
     """acx_tally_host: rows of (pattern, start, end), counts[h] of them haystack h's -> (row_offsets, pattern, count) of the
     CSR matrix of per-haystack pattern counts, on the host, no device involved.  ValueError (code EINVAL) when the counts do
     not sum to the rows."""
-    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
-    c = np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    m, c = _records(matches), _u64(counts)
     ro = np.zeros(len(c) + 1, dtype=np.int64)
     pat, cnt = np.zeros(len(m), dtype=np.int64), np.zeros(len(m), dtype=np.int64)
     nnz = ctypes.c_uint64()
-    _check(lib().acx_tally_host(m.ctypes.data if len(m) else None, len(m), c.ctypes.data if len(c) else None, len(c),
-                                ro.ctypes.data, pat.ctypes.data if len(m) else None, cnt.ctypes.data if len(m) else None,
-                                ctypes.byref(nnz)))
+    _check(lib().acx_tally_host(_ptr(m), len(m), _ptr(c), len(c), ro.ctypes.data, _ptr(pat), _ptr(cnt), ctypes.byref(nnz)))
     return ro, pat[:nnz.value], cnt[:nnz.value]
 
 
@@ -790,21 +740,10 @@ class DeviceFiltered(_PartsResult):
     """The result of Automaton.filter / filter_device (acx_filtered_t): the kept rows of a batch -- k source row indexes
     and k + 1 offsets (int64) and the rows' bytes back to back (uint8) -- in HBM (on_device) or in host memory.  part()
     copies one out; data_ptr() is where it lies (both wait for the device stage)."""
-    _ON_DEVICE, _DATA, _COPY, _FREE = "acx_filtered_on_device", "acx_filtered_data", "acx_filtered_copy", "acx_free_filtered"
-
-    @property
-    def n_rows(self) -> int:
-        return int(lib().acx_filtered_rows(self._h))
-
-    @property
-    def nbytes(self) -> int:
-        return int(lib().acx_filtered_bytes(self._h))
-
-    def _part_shape(self, which: int):
-        return (self.nbytes, np.uint8) if which == FILT_DATA else (self.n_rows + (which == FILT_OFFSETS), np.int64)
-
-    def part(self, which: int) -> np.ndarray:
-        return self._copy_part(which)
+    _PREFIX = "filtered"
+    n_rows, nbytes = _Size("rows"), _Size("bytes")
+    _PARTS = {FILT_ROWS: ("n_rows", 0, np.int64), FILT_OFFSETS: ("n_rows", 1, np.int64), FILT_DATA: ("nbytes", 0, np.uint8)}
+    part = _PartsResult._copy_part
 
     def rows(self) -> np.ndarray:
         return self.part(FILT_ROWS)
@@ -823,14 +762,12 @@ def filter_host(hay, offsets: Optional[Sequence[int]], counts: Sequence[int], mi
     uint8 arrays, or (n_rows, n_bytes) with sizes_only.  ValueError (code EINVAL) for a bad flag, min_matches = 0 or
     offsets that do not rise from 0 to len(hay)."""
     h = np.frombuffer(bytes(hay), dtype=np.uint8)
-    c = np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
-    off = None if offsets is None else np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+    c, off = _u64(counts), _u64(offsets)
     n = len(c)
     if off is not None and len(off) != n + 1:
         raise ValueError("offsets needs len(counts) + 1 entries")
     k, nb = ctypes.c_uint64(), ctypes.c_uint64()
-    args = (h.ctypes.data if len(h) else None, len(h), None if off is None else off.ctypes.data, n,
-            c.ctypes.data if n else None, min_matches, flags)
+    args = (_ptr(h), len(h), None if off is None else off.ctypes.data, n, _ptr(c), min_matches, flags)
     _check(lib().acx_filter_host(*args, None, None, None, ctypes.byref(k), ctypes.byref(nb)))
     if sizes_only:
         return int(k.value), int(nb.value)
@@ -856,19 +793,14 @@ def filter_rows_device(d_hay: int, nbytes: int, d_offsets: int, n_hay: int, unif
 class DeviceScores(_Result):
     """The result of Automaton.score / score_device (acx_scores_t): one int64 score per row of the batch, in HBM (on_device)
     or in host memory.  scores() copies them out; data_ptr() is where they lie (both wait for the device stage)."""
-    _ON_DEVICE, _FREE = "acx_scores_on_device", "acx_free_scores"
-
-    @property
-    def rows(self) -> int:
-        return int(lib().acx_scores_rows(self._h))
+    _PREFIX = "scores"
+    rows = _Size("rows")
 
     def data_ptr(self) -> int:
-        return lib().acx_scores_data(self._h) or 0
+        return self._address("data")
 
     def scores(self) -> np.ndarray:
-        out = np.zeros(self.rows, dtype=np.int64)
-        _check(lib().acx_scores_copy(self._h, out.ctypes.data if out.size else None))
-        return out
+        return self._copy_out("copy", self.rows, np.int64)
 
 
 def _weights(weights) -> np.ndarray:
@@ -883,15 +815,10 @@ def score_host(matches, counts: Optional[Sequence[int]], weights) -> np.ndarray:
     """acx_score_host: rows of (pattern, start, end), counts[h] of them haystack h's (None: one row holds them all) -> the
     int64 score of every row, on the host, no device involved.  ValueError (code EINVAL) when the counts do not sum to the
     rows."""
-    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
-    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
-    w = _weights(weights)
+    m, c, w = _records(matches), _u64(counts), _weights(weights)
     n_hay = 1 if c is None else len(c)
     out = np.zeros(n_hay, dtype=np.int64)
-    pad = np.zeros(1, dtype=np.uint64)  # (an empty batch is still a batch: a non-null counts pointer)
-    _check(lib().acx_score_host(m.ctypes.data if len(m) else None, len(m),
-                                None if c is None else (c.ctypes.data if len(c) else pad.ctypes.data), n_hay,
-                                w.ctypes.data if len(w) else None, len(w), out.ctypes.data if n_hay else None))
+    _check(lib().acx_score_host(_ptr(m), len(m), _ptr(c, _SPARE.ctypes.data), n_hay, _ptr(w), len(w), _ptr(out)))
     return out
 
 
@@ -907,31 +834,20 @@ class DeviceMasked(_Result):
     0 / 1 mask), nbytes of them in the input's own layout, and the rows' offsets (rows + 1 int64 words from 0) -- in HBM
     (on_device) or in host memory.  data() / offsets() copy them out; data_ptr() / offsets_ptr() are where they lie (all
     wait for the device stage)."""
-    _ON_DEVICE, _FREE = "acx_masked_on_device", "acx_free_masked"
-
-    @property
-    def rows(self) -> int:
-        return int(lib().acx_masked_rows(self._h))
-
-    @property
-    def nbytes(self) -> int:
-        return int(lib().acx_masked_bytes(self._h))
+    _PREFIX = "masked"
+    rows, nbytes = _Size("rows"), _Size("bytes")
 
     def data_ptr(self) -> int:
-        return lib().acx_masked_data(self._h) or 0
+        return self._address("data")
 
     def offsets_ptr(self) -> int:
-        return lib().acx_masked_offsets(self._h) or 0
+        return self._address("offsets")
 
     def data(self) -> np.ndarray:
-        out = np.zeros(self.nbytes, dtype=np.uint8)
-        _check(lib().acx_masked_copy(self._h, out.ctypes.data if out.size else None))
-        return out
+        return self._copy_out("copy", self.nbytes, np.uint8)
 
     def offsets(self) -> np.ndarray:
-        out = np.zeros(self.rows + 1, dtype=np.int64)
-        _check(lib().acx_masked_copy_offsets(self._h, out.ctypes.data))
-        return out
+        return self._copy_out("copy_offsets", self.rows + 1, np.int64)
 
 
 def mask_host(hay, offsets: Optional[Sequence[int]], matches, counts: Optional[Sequence[int]], fill: int,
@@ -942,18 +858,13 @@ def mask_host(hay, offsets: Optional[Sequence[int]], matches, counts: Optional[S
     own byte (flags = 0) or 0 (MASK_ZERO).  ValueError (code EINVAL) for a bad flag, offsets that do not rise from 0 to
     len(hay) or counts that do not sum to the rows."""
     h = np.frombuffer(bytes(hay), dtype=np.uint8)
-    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
-    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
-    off = None if offsets is None else np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+    m, c, off = _records(matches), _u64(counts), _u64(offsets)
     n_hay = (1 if c is None else len(c)) if off is None else len(off) - 1
     if c is not None and off is not None and len(c) != n_hay:
         raise ValueError("offsets needs len(counts) + 1 entries")
     out = np.zeros(max(len(h), 1), dtype=np.uint8)
-    pad = np.zeros(1, dtype=np.uint64)  # (an empty batch is still a batch: a non-null counts pointer)
-    _check(lib().acx_mask_host(h.ctypes.data if len(h) else None, len(h), None if off is None else off.ctypes.data, n_hay,
-                               m.ctypes.data if len(m) else None, len(m),
-                               None if c is None else (c.ctypes.data if len(c) else pad.ctypes.data), fill, flags,
-                               out.ctypes.data))
+    _check(lib().acx_mask_host(_ptr(h), len(h), None if off is None else off.ctypes.data, n_hay, _ptr(m), len(m),
+                               _ptr(c, _SPARE.ctypes.data), fill, flags, out.ctypes.data))
     return out[:len(h)]
 
 
@@ -970,34 +881,21 @@ class DeviceRows(_Result):
     """The result of split_rows / split_rows_device (acx_rows_t): the offsets that cut nbytes of delimited data into rows --
     rows + 1 int64 words from 0 to nbytes, in HBM (on_device, on `device`) or in host memory.  `rows` is valid at once;
     offsets() copies the words out and offsets_ptr() is where they lie (both wait for the device stage)."""
-    _ON_DEVICE, _FREE = "acx_rows_on_device", "acx_free_rows"
-
-    @property
-    def device(self) -> int:
-        return int(lib().acx_rows_device(self._h))
-
-    @property
-    def rows(self) -> int:
-        return int(lib().acx_rows_count(self._h))
-
-    @property
-    def nbytes(self) -> int:
-        return int(lib().acx_rows_bytes(self._h))
+    _PREFIX = "rows"
+    device, rows, nbytes = _Size("device"), _Size("count"), _Size("bytes")
 
     def offsets_ptr(self) -> int:
-        return lib().acx_rows_offsets(self._h) or 0
+        return self._address("offsets")
 
     def offsets(self) -> np.ndarray:
-        out = np.zeros(self.rows + 1, dtype=np.int64)
-        _check(lib().acx_rows_copy(self._h, out.ctypes.data))
-        return out
+        return self._copy_out("copy", self.rows + 1, np.int64)
 
 
 def split_rows(hay, delimiter: int = 10) -> DeviceRows:
     """acx_split_rows: host bytes cut at every `delimiter` byte (the delimiter ends its row), a host result"""
     h = np.frombuffer(bytes(hay), dtype=np.uint8)
     out = ctypes.c_void_p()
-    _check(lib().acx_split_rows(h.ctypes.data if len(h) else None, len(h), delimiter, ctypes.byref(out)))
+    _check(lib().acx_split_rows(_ptr(h), len(h), delimiter, ctypes.byref(out)))
     return DeviceRows(out.value)
 
 
@@ -1013,7 +911,7 @@ def split_rows_host(hay, delimiter: int = 10, *, count_only: bool = False):
     """acx_split_rows_host: the definition on the host, no device involved -> rows + 1 int64 offsets (count_only: the number
     of rows)"""
     h = np.frombuffer(bytes(hay), dtype=np.uint8)
-    p = h.ctypes.data if len(h) else None
+    p = _ptr(h)
     n = ctypes.c_uint64()
     _check(lib().acx_split_rows_host(p, len(h), delimiter, None, 0, ctypes.byref(n)))
     if count_only:
@@ -1032,29 +930,14 @@ def split_rows_into_device(d_hay: int, nbytes: int, delimiter: int, d_offsets: i
     return int(n.value)
 
 
-class DeviceSpans(_PartsResult):
+class DeviceSpans(_BatchPartsResult):
     """The result of Automaton.spans / spans_device (acx_spans_t): the merged spans of a search's matches as two int64
     columns of `count` words and, for a batch, n_hay + 1 row offsets -- in HBM (on_device) or in host memory.  column()
     copies one out; data_ptr() is where it lies (both wait for the stage's last kernel)."""
-    _ON_DEVICE, _DATA, _COPY, _FREE = "acx_spans_on_device", "acx_spans_data", "acx_spans_copy", "acx_free_spans"
-
-    def __init__(self, handle: int, batch: bool):
-        super().__init__(handle)
-        self.batch = batch
-
-    @property
-    def count(self) -> int:
-        return int(lib().acx_spans_count(self._h))
-
-    @property
-    def rows(self) -> int:
-        return int(lib().acx_spans_rows(self._h))
-
-    def _part_shape(self, which: int):
-        return (self.rows + 1 if which == SPAN_ROW_OFFSETS else self.count), np.int64
-
-    def column(self, which: int) -> np.ndarray:
-        return self._copy_part(which)
+    _PREFIX = "spans"
+    count, rows = _Size("count"), _Size("rows")
+    _PARTS = {SPAN_START: ("count", 0, np.int64), SPAN_END: ("count", 0, np.int64), SPAN_ROW_OFFSETS: ("rows", 1, np.int64)}
+    column = _PartsResult._copy_part
 
     def start(self) -> np.ndarray:
         return self.column(SPAN_START)
@@ -1071,17 +954,14 @@ def spans_host(matches, counts: Optional[Sequence[int]], gap: int = 0):
     rows behind one another, counts[h] of them row h's -- None: one row) on the host, no device involved ->
     (row_offsets, start, end): len(counts) + 1 (one row: 2) int64 offsets and the spans' int64 columns.  ValueError (code
     EINVAL) when the counts do not sum to the records or gap is 2**63 or more."""
-    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
-    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    m, c = _records(matches), _u64(counts)
     n_hay = 1 if c is None else len(c)
     ro = np.zeros(n_hay + 1, dtype=np.int64)
     start = np.zeros(len(m) + 1, dtype=np.int64)
     end = np.zeros(len(m) + 1, dtype=np.int64)
-    pad = np.zeros(1, dtype=np.uint64)  # (an empty batch is still a batch: a non-null counts pointer)
     n = ctypes.c_uint64()
-    _check(lib().acx_spans_host(m.ctypes.data if len(m) else None, len(m),
-                                None if c is None else (c.ctypes.data if len(c) else pad.ctypes.data), n_hay, gap,
-                                ro.ctypes.data, start.ctypes.data, end.ctypes.data, ctypes.byref(n)))
+    _check(lib().acx_spans_host(_ptr(m), len(m), _ptr(c, _SPARE.ctypes.data), n_hay, gap, ro.ctypes.data, start.ctypes.data,
+                                end.ctypes.data, ctypes.byref(n)))
     return ro, start[:n.value], end[:n.value]
 
 
@@ -1096,35 +976,15 @@ def spans_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, gap: in
     return int(s.value)
 
 
-class DeviceSnippets(_PartsResult):
+class DeviceSnippets(_BatchPartsResult):
     """The result of Automaton.snippets / snippets_device (acx_snippets_t): one snippet per match -- the bytes back to back
     (uint8), count + 1 offsets, the pattern and lead columns (int64) and, for a batch, n_hay + 1 row offsets -- in HBM
     (on_device) or in host memory.  part() copies one out; data_ptr() is where it lies (both wait for the gather)."""
-    _ON_DEVICE, _DATA, _COPY, _FREE = "acx_snippets_on_device", "acx_snippets_data", "acx_snippets_copy", "acx_free_snippets"
-
-    def __init__(self, handle: int, batch: bool):
-        super().__init__(handle)
-        self.batch = batch
-
-    @property
-    def count(self) -> int:
-        return int(lib().acx_snippets_count(self._h))
-
-    @property
-    def rows(self) -> int:
-        return int(lib().acx_snippets_rows(self._h))
-
-    @property
-    def nbytes(self) -> int:
-        return int(lib().acx_snippets_nbytes(self._h))
-
-    def _part_shape(self, which: int):
-        if which == SNIP_DATA:
-            return self.nbytes, np.uint8
-        return (self.rows + 1 if which == SNIP_ROW_OFFSETS else self.count + (which == SNIP_OFFSETS)), np.int64
-
-    def part(self, which: int) -> np.ndarray:
-        return self._copy_part(which)
+    _PREFIX = "snippets"
+    count, rows, nbytes = _Size("count"), _Size("rows"), _Size("nbytes")
+    _PARTS = {SNIP_DATA: ("nbytes", 0, np.uint8), SNIP_OFFSETS: ("count", 1, np.int64), SNIP_PATTERN: ("count", 0, np.int64),
+              SNIP_LEAD: ("count", 0, np.int64), SNIP_ROW_OFFSETS: ("rows", 1, np.int64)}
+    part = _PartsResult._copy_part
 
     def data(self) -> np.ndarray:
         return self.part(SNIP_DATA)
@@ -1155,14 +1015,11 @@ def snippets_host(matches, counts: Optional[Sequence[int]], hay, offsets: Option
     form: sizes with null outputs, then the fill -- or the data's size alone with sizes_only.  ValueError (code EINVAL) for a
     bad flag, a context of 2**63 or more, counts that do not sum to the records or offsets that do not rise from 0 to
     len(hay)."""
-    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
-    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+    m, c, off = _records(matches), _u64(counts), _u64(offsets)
     h = np.frombuffer(bytes(hay), dtype=np.uint8)
-    off = None if offsets is None else np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
     n_hay = (1 if c is None else len(c)) if off is None else len(off) - 1
-    pad = np.zeros(1, dtype=np.uint64)  # (an empty batch is still a batch: non-null pointers)
-    args = (m.ctypes.data if len(m) else None, len(m), None if c is None else (c.ctypes.data if len(c) else pad.ctypes.data),
-            n_hay, h.ctypes.data if len(h) else None, len(h), None if off is None else off.ctypes.data, context, flags)
+    args = (_ptr(m), len(m), _ptr(c, _SPARE.ctypes.data), n_hay, _ptr(h), len(h), None if off is None else off.ctypes.data,
+            context, flags)
     total = ctypes.c_uint64()
     _check(lib().acx_snippets_host(*args, None, None, None, None, None, ctypes.byref(total)))
     if sizes_only:
@@ -1172,8 +1029,7 @@ def snippets_host(matches, counts: Optional[Sequence[int]], hay, offsets: Option
     pat = np.zeros(len(m), dtype=np.int64)
     lead = np.zeros(len(m), dtype=np.int64)
     ro = np.zeros(n_hay + 1, dtype=np.int64)
-    _check(lib().acx_snippets_host(*args, o.ctypes.data, pat.ctypes.data if len(m) else None, lead.ctypes.data if len(m) else None,
-                                   ro.ctypes.data, data.ctypes.data if data.size else None, ctypes.byref(total)))
+    _check(lib().acx_snippets_host(*args, o.ctypes.data, _ptr(pat), _ptr(lead), ro.ctypes.data, _ptr(data), ctypes.byref(total)))
     return data, o, pat, lead, ro
 
 
@@ -1194,22 +1050,14 @@ def snippets_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, d_ha
     return rc, int(t.value)
 
 
-def _replaced_bytes(h: int) -> bytes:
-    buf = bytearray(int(lib().acx_replaced_len(h)))
-    if buf:
-        _check(lib().acx_replaced_copy(h, (ctypes.c_uint8 * len(buf)).from_buffer(buf)))
-    return bytes(buf)
-
-
 def splice_host(hay, matches, replace_with: Sequence[bytes]) -> bytes:
     """acx_splice_host: `hay` with every match (pattern, start, end) replaced by replace_with[pattern] -- on the host,
     no device involved.  ValueError (code EINVAL) for unsorted, overlapping or out-of-range matches."""
     h = np.frombuffer(bytes(hay), dtype=np.uint8)
-    m = np.ascontiguousarray(np.asarray(matches, dtype=np.uint64).reshape(-1, 3))
+    m = _records(matches)
     blob, off = pack(replace_with)
     n = ctypes.c_uint64()
-    args = (h.ctypes.data if h.size else None, h.size, m.ctypes.data if len(m) else None, len(m),
-            blob.ctypes.data, off.ctypes.data, len(replace_with))
+    args = (_ptr(h), h.size, _ptr(m), len(m), blob.ctypes.data, off.ctypes.data, len(replace_with))
     _check(lib().acx_splice_host(*args, None, ctypes.byref(n)))
     out = np.empty(int(n.value) + 1, dtype=np.uint8)
     _check(lib().acx_splice_host(*args, out.ctypes.data, ctypes.byref(n)))
@@ -1225,6 +1073,38 @@ def _take_matches(ptr: Optional[int], n: int) -> np.ndarray:
     buf = (ctypes.c_uint8 * (n * 24)).from_address(ptr)
     weakref.finalize(buf, lib().acx_free_matches, ptr)
     return np.frombuffer(buf, dtype=MATCH_DTYPE)
+
+
+# How a stage's host form takes ONE haystack that is no batch (offsets = NULL): (a padded copy?, n_hay).  The C stages differ
+# here, so the binding states it per stage and unifies nothing.
+_SINGLE_ROW = (True, 1)     # filter, score, filter_scored, mask: a copy with one \0 behind it, a batch of one row -- the stage
+#                             reads n_hay with offsets == NULL
+_SINGLE_PADDED = (True, 0)  # spans, snippets: the same copy, n_hay = 0 -- the stage derives rows = offsets ? n_hay : 1
+_SINGLE_OWN = (False, 0)    # replace, summarize, find_columns: the caller's own bytes (NULL for none), n_hay = 0 -- as find()
+
+
+def _host_arg(haystacks, single=None, convention=None) -> tuple:
+    """the host haystack argument (hay, len, offsets, n_hay) of a batch -- a sequence, packed -- or of one buffer by its
+    stage's _SINGLE_* convention, with what must stay alive until the call is over behind it"""
+    if single is None:
+        blob, off = pack(haystacks)
+        return blob.ctypes.data, int(off[-1]), off.ctypes.data, len(haystacks), blob, off
+    padded, n_hay = convention
+    if padded:
+        a = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
+        return a.ctypes.data, len(single), None, n_hay, a
+    a = np.ascontiguousarray(np.frombuffer(single, dtype=np.uint8) if not isinstance(single, np.ndarray) else single)
+    return a.ctypes.data if a.size else None, a.size, None, n_hay, a
+
+
+def _batched(d_offsets: int, uniform_len: int) -> bool:
+    """a device call is a batch when its rows are cut by offsets or by a uniform length"""
+    return bool(uniform_len or d_offsets)
+
+
+def _rows(d_offsets: int, n_hay: int, uniform_len: int) -> int:
+    """the rows of a device call: one haystack that is no batch is one row"""
+    return n_hay if _batched(d_offsets, uniform_len) else 1
 
 
 class Automaton(_Handle):
@@ -1256,7 +1136,8 @@ class Automaton(_Handle):
     def set_kernel(self, kernel: int) -> None:
         _check(lib().acx_set_kernel(self._h, kernel))
 
-    # ---- host-memory entry points
+    # ---- host-memory entry points.  find, find_batch and find_device are what bench.py times, a few microseconds a call:
+    # they call the library directly and go through none of the frames below
     def find(self, hay, overlapping: bool = False, codepoints: bool = False) -> np.ndarray:
         a = np.frombuffer(hay, dtype=np.uint8) if not isinstance(hay, np.ndarray) else hay
         a = np.ascontiguousarray(a)
@@ -1312,136 +1193,112 @@ class Automaton(_Handle):
                                      ctypes.byref(out)))
         return DeviceResult(out.value, n_hay if (uniform_len or d_offsets) else 0)
 
+    # ---- the stages behind a find.  Every one has a host form, acx_<stage>(a, hay, len, offsets, n_hay, *tail, out), and a
+    # device form, acx_<stage>_device(a, d_hay, len, d_offsets, n_hay, uniform_len, *tail, out): a method below states the
+    # stage, its tail and its result class, and for the host form how the stage takes ONE haystack (_SINGLE_*)
+    def _host(self, stage: str, hay: tuple, tail: tuple, result, *more):
+        """the host forms' frame: hay = _host_arg(...) (it keeps the haystack's memory alive until the call is over)"""
+        out = ctypes.c_void_p()
+        _check(getattr(lib(), "acx_" + stage)(self._h, *hay[:4], *tail, ctypes.byref(out)))
+        return result(out.value, *more)
+
+    def _device(self, stage: str, dev: tuple, tail: tuple, result, *more):
+        """the device forms' frame: dev = (d_ptr, nbytes, d_offsets, n_hay, uniform_len); an address of 0 is NULL"""
+        d_ptr, nbytes, d_offsets, n_hay, uniform_len = dev
+        out = ctypes.c_void_p()
+        _check(getattr(lib(), f"acx_{stage}_device")(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, *tail,
+                                                     ctypes.byref(out)))
+        return result(out.value, *more)
+
     # ---- replacement (acx_replace / acx_replace_device)
     def replace(self, hay, replace_with: Sequence[bytes]) -> bytes:
         """every non-overlapping match of `hay` replaced by replace_with[pattern]"""
-        a = np.ascontiguousarray(np.frombuffer(hay, dtype=np.uint8) if not isinstance(hay, np.ndarray) else hay)
         blob, off = pack(replace_with)
-        out = ctypes.c_void_p()
-        _check(lib().acx_replace(self._h, a.ctypes.data if a.size else None, a.size, None, 0, blob.ctypes.data,
-                                 off.ctypes.data, len(replace_with), ctypes.byref(out)))
+        r = self._host("replace", _host_arg(None, hay, _SINGLE_OWN), (blob.ctypes.data, off.ctypes.data, len(replace_with)),
+                       DeviceReplaced, 1)
         try:
-            return _replaced_bytes(out.value)
+            return r.download()
         finally:
-            lib().acx_free_replaced(out.value)
+            r.free()
 
     def replace_batch(self, haystacks: Sequence[bytes], replace_with: Sequence[bytes]) -> List[bytes]:
         """[self.replace(h, replace_with) for h in haystacks] in one call"""
-        hb, hoff = pack(haystacks)
         blob, off = pack(replace_with)
-        out = ctypes.c_void_p()
-        _check(lib().acx_replace(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks),
-                                 blob.ctypes.data, off.ctypes.data, len(replace_with), ctypes.byref(out)))
+        r = self._host("replace", _host_arg(haystacks), (blob.ctypes.data, off.ctypes.data, len(replace_with)), DeviceReplaced,
+                       len(haystacks))
         try:
-            whole = _replaced_bytes(out.value)
-            bounds = np.zeros(len(haystacks) + 1, dtype=np.uint64)
-            _check(lib().acx_replaced_offsets(out.value, bounds.ctypes.data))
+            whole, bounds = r.download(), r.offsets()
         finally:
-            lib().acx_free_replaced(out.value)
+            r.free()
         return [whole[int(bounds[i]):int(bounds[i + 1])] for i in range(len(haystacks))]
 
     def replace_device(self, d_ptr: int, nbytes: int, replace_with: Sequence[bytes], *, d_offsets: int = 0,
                        n_hay: int = 0, uniform_len: int = 0) -> DeviceReplaced:
         """the haystack in HBM searched and spliced there; the output stays in HBM"""
         blob, off = pack(replace_with)
-        out = ctypes.c_void_p()
-        _check(lib().acx_replace_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, blob.ctypes.data,
-                                        off.ctypes.data, len(replace_with), ctypes.byref(out)))
-        return DeviceReplaced(out.value, n_hay if (uniform_len or d_offsets) else 1)
+        return self._device("replace", (d_ptr, nbytes, d_offsets, n_hay, uniform_len),
+                            (blob.ctypes.data, off.ctypes.data, len(replace_with)), DeviceReplaced,
+                            _rows(d_offsets, n_hay, uniform_len))
 
     # ---- summaries (acx_summarize / acx_summarize_device)
     def summarize(self, hay, what: int = SUM_FIRST | SUM_BY_PATTERN, overlapping: bool = False,
                   codepoints: bool = False) -> DeviceSummary:
         """is there a match, the first one, how many, how many per pattern -- without the match list"""
-        a = np.ascontiguousarray(np.frombuffer(hay, dtype=np.uint8) if not isinstance(hay, np.ndarray) else hay)
-        out = ctypes.c_void_p()
-        _check(lib().acx_summarize(self._h, a.ctypes.data if a.size else None, a.size, None, 0, int(overlapping),
-                                   int(codepoints), what, ctypes.byref(out)))
-        return DeviceSummary(out.value, 1, int(self.info.n_patterns))
+        return self._host("summarize", _host_arg(None, hay, _SINGLE_OWN), (int(overlapping), int(codepoints), what),
+                          DeviceSummary, 1, int(self.info.n_patterns))
 
     def summarize_batch(self, haystacks: Sequence[bytes], what: int = SUM_FIRST | SUM_BY_PATTERN, overlapping: bool = False,
                         codepoints: bool = False) -> DeviceSummary:
         """the same per haystack (by_pattern: over the whole batch); entry i equals summarize(haystacks[i])"""
-        hb, hoff = pack(haystacks)
-        out = ctypes.c_void_p()
-        _check(lib().acx_summarize(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
-                                   int(codepoints), what, ctypes.byref(out)))
-        return DeviceSummary(out.value, len(haystacks), int(self.info.n_patterns))
+        return self._host("summarize", _host_arg(haystacks), (int(overlapping), int(codepoints), what), DeviceSummary,
+                          len(haystacks), int(self.info.n_patterns))
 
     def summarize_device(self, d_ptr: int, nbytes: int, what: int = SUM_FIRST | SUM_BY_PATTERN, *, d_offsets: int = 0,
                          n_hay: int = 0, uniform_len: int = 0, overlapping: bool = False,
                          codepoints: bool = False) -> DeviceSummary:
         """the haystack in HBM searched and its result reduced there; the summaries stay in HBM until they are asked for"""
-        out = ctypes.c_void_p()
-        _check(lib().acx_summarize_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
-                                          int(codepoints), what, ctypes.byref(out)))
-        return DeviceSummary(out.value, n_hay if (uniform_len or d_offsets) else 1, int(self.info.n_patterns))
+        return self._device("summarize", (d_ptr, nbytes, d_offsets, n_hay, uniform_len), (int(overlapping), int(codepoints), what),
+                            DeviceSummary, _rows(d_offsets, n_hay, uniform_len), int(self.info.n_patterns))
 
     # ---- matches as columns (acx_find_columns / acx_find_columns_device)
     def find_columns(self, hay, overlapping: bool = False, codepoints: bool = False) -> DeviceColumns:
         """find()'s matches as three int64 columns in host memory"""
-        a = np.ascontiguousarray(np.frombuffer(hay, dtype=np.uint8) if not isinstance(hay, np.ndarray) else hay)
-        out = ctypes.c_void_p()
-        _check(lib().acx_find_columns(self._h, a.ctypes.data if a.size else None, a.size, None, 0, int(overlapping),
-                                      int(codepoints), ctypes.byref(out)))
-        return DeviceColumns(out.value, False)
+        return self._host("find_columns", _host_arg(None, hay, _SINGLE_OWN), (int(overlapping), int(codepoints)), DeviceColumns,
+                          False)
 
     def find_columns_batch(self, haystacks: Sequence[bytes], overlapping: bool = False,
                            codepoints: bool = False) -> DeviceColumns:
         """find_batch()'s matches as columns in host memory, with the row offsets of the haystacks"""
-        hb, hoff = pack(haystacks)
-        out = ctypes.c_void_p()
-        _check(lib().acx_find_columns(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks),
-                                      int(overlapping), int(codepoints), ctypes.byref(out)))
-        return DeviceColumns(out.value, True)
+        return self._host("find_columns", _host_arg(haystacks), (int(overlapping), int(codepoints)), DeviceColumns, True)
 
     def find_columns_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
                             overlapping: bool = False, codepoints: bool = False) -> DeviceColumns:
         """the haystack in HBM searched and its matches split into columns there; nothing but the total crosses the bus"""
-        out = ctypes.c_void_p()
-        _check(lib().acx_find_columns_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len,
-                                             int(overlapping), int(codepoints), ctypes.byref(out)))
-        return DeviceColumns(out.value, bool(uniform_len or d_offsets))
+        return self._device("find_columns", (d_ptr, nbytes, d_offsets, n_hay, uniform_len), (int(overlapping), int(codepoints)),
+                            DeviceColumns, _batched(d_offsets, uniform_len))
 
     # ---- per-haystack pattern counts as a CSR matrix (acx_tally / acx_tally_device)
     def tally(self, haystacks: Sequence[bytes], overlapping: bool = False) -> DeviceTally:
         """which patterns occur in which haystack, and how often: host haystacks, a host result"""
-        hb, hoff = pack(haystacks)
-        out = ctypes.c_void_p()
-        _check(lib().acx_tally(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
-                               ctypes.byref(out)))
-        return DeviceTally(out.value)
+        return self._host("tally", _host_arg(haystacks), (int(overlapping),), DeviceTally)
 
     def tally_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
                      overlapping: bool = False) -> DeviceTally:
         """the batch in HBM searched and reduced there; nothing but nnz crosses the bus"""
-        out = ctypes.c_void_p()
-        _check(lib().acx_tally_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
-                                      ctypes.byref(out)))
-        return DeviceTally(out.value)
+        return self._device("tally", (d_ptr, nbytes, d_offsets, n_hay, uniform_len), (int(overlapping),), DeviceTally)
 
     # ---- keep or drop the rows of a batch by match (acx_filter / acx_filter_device)
     def filter(self, haystacks: Optional[Sequence[bytes]], overlapping: bool = False, min_matches: int = 1, flags: int = 0, *,
                single: Optional[bytes] = None) -> DeviceFiltered:
         """the kept rows of host haystacks, a host result; single=...: one haystack that is no batch (offsets = NULL)"""
-        out = ctypes.c_void_p()
-        if single is not None:
-            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
-            _check(lib().acx_filter(self._h, hb.ctypes.data, len(single), None, 1, int(overlapping), min_matches, flags,
-                                    ctypes.byref(out)))
-            return DeviceFiltered(out.value)
-        hb, hoff = pack(haystacks)
-        _check(lib().acx_filter(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
-                                min_matches, flags, ctypes.byref(out)))
-        return DeviceFiltered(out.value)
+        return self._host("filter", _host_arg(haystacks, single, _SINGLE_ROW), (int(overlapping), min_matches, flags),
+                          DeviceFiltered)
 
     def filter_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
                       overlapping: bool = False, min_matches: int = 1, flags: int = 0) -> DeviceFiltered:
         """the batch in HBM searched and compacted there; nothing but the result's two sizes crosses the bus"""
-        out = ctypes.c_void_p()
-        _check(lib().acx_filter_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
-                                       min_matches, flags, ctypes.byref(out)))
-        return DeviceFiltered(out.value)
+        return self._device("filter", (d_ptr, nbytes, d_offsets, n_hay, uniform_len), (int(overlapping), min_matches, flags),
+                            DeviceFiltered)
 
     # ---- per-pattern weights: a score per row, and the row filter by score (acx_score* / acx_filter_scored*)
     def score(self, haystacks: Optional[Sequence[bytes]], weights, overlapping: bool = False, *,
@@ -1449,122 +1306,70 @@ class Automaton(_Handle):
         """every row's sum of weights[pattern] over its matches: host haystacks, a host result; single=...: one haystack
         that is no batch (offsets = NULL)"""
         w = _weights(weights)
-        out = ctypes.c_void_p()
-        if single is not None:
-            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
-            _check(lib().acx_score(self._h, hb.ctypes.data, len(single), None, 1, int(overlapping), w.ctypes.data, len(w),
-                                   ctypes.byref(out)))
-            return DeviceScores(out.value)
-        hb, hoff = pack(haystacks)
-        _check(lib().acx_score(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
-                               w.ctypes.data, len(w), ctypes.byref(out)))
-        return DeviceScores(out.value)
+        return self._host("score", _host_arg(haystacks, single, _SINGLE_ROW), (int(overlapping), w.ctypes.data, len(w)),
+                          DeviceScores)
 
     def score_device(self, d_ptr: int, nbytes: int, weights, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
                      overlapping: bool = False) -> DeviceScores:
         """the batch in HBM searched and scored there; the scores stay there"""
         w = _weights(weights)
-        out = ctypes.c_void_p()
-        _check(lib().acx_score_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
-                                      w.ctypes.data, len(w), ctypes.byref(out)))
-        return DeviceScores(out.value)
+        return self._device("score", (d_ptr, nbytes, d_offsets, n_hay, uniform_len), (int(overlapping), w.ctypes.data, len(w)),
+                            DeviceScores)
 
     def filter_scored(self, haystacks: Optional[Sequence[bytes]], weights, overlapping: bool = False, min_score: int = 1,
                       flags: int = 0, *, single: Optional[bytes] = None) -> DeviceFiltered:
         """filter() with a row matched when its score is at least min_score"""
         w = _weights(weights)
-        out = ctypes.c_void_p()
-        if single is not None:
-            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
-            _check(lib().acx_filter_scored(self._h, hb.ctypes.data, len(single), None, 1, int(overlapping), w.ctypes.data,
-                                           len(w), min_score, flags, ctypes.byref(out)))
-            return DeviceFiltered(out.value)
-        hb, hoff = pack(haystacks)
-        _check(lib().acx_filter_scored(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks),
-                                       int(overlapping), w.ctypes.data, len(w), min_score, flags, ctypes.byref(out)))
-        return DeviceFiltered(out.value)
+        return self._host("filter_scored", _host_arg(haystacks, single, _SINGLE_ROW),
+                          (int(overlapping), w.ctypes.data, len(w), min_score, flags), DeviceFiltered)
 
     def filter_scored_device(self, d_ptr: int, nbytes: int, weights, *, d_offsets: int = 0, n_hay: int = 0,
                              uniform_len: int = 0, overlapping: bool = False, min_score: int = 1,
                              flags: int = 0) -> DeviceFiltered:
         """filter_device() with a row matched when its score is at least min_score"""
         w = _weights(weights)
-        out = ctypes.c_void_p()
-        _check(lib().acx_filter_scored_device(self._h, d_ptr, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
-                                              w.ctypes.data, len(w), min_score, flags, ctypes.byref(out)))
-        return DeviceFiltered(out.value)
+        return self._device("filter_scored", (d_ptr, nbytes, d_offsets, n_hay, uniform_len),
+                            (int(overlapping), w.ctypes.data, len(w), min_score, flags), DeviceFiltered)
 
     # ---- cover / mask: every byte a match covers becomes `fill` (acx_mask*)
     def mask(self, haystacks: Optional[Sequence[bytes]], fill: int, overlapping: bool = False, flags: int = 0, *,
              single: Optional[bytes] = None) -> DeviceMasked:
         """host haystacks with their matches' bytes filled, a host result; single=...: one haystack that is no batch
         (offsets = NULL)"""
-        out = ctypes.c_void_p()
-        if single is not None:
-            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
-            _check(lib().acx_mask(self._h, hb.ctypes.data, len(single), None, 1, int(overlapping), fill, flags,
-                                  ctypes.byref(out)))
-            return DeviceMasked(out.value)
-        hb, hoff = pack(haystacks)
-        _check(lib().acx_mask(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
-                              fill, flags, ctypes.byref(out)))
-        return DeviceMasked(out.value)
+        return self._host("mask", _host_arg(haystacks, single, _SINGLE_ROW), (int(overlapping), fill, flags), DeviceMasked)
 
     def mask_device(self, d_ptr: int, nbytes: int, fill: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
                     overlapping: bool = False, flags: int = 0) -> DeviceMasked:
         """the batch in HBM searched and painted there; the output stays there"""
-        out = ctypes.c_void_p()
-        _check(lib().acx_mask_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
-                                     fill, flags, ctypes.byref(out)))
-        return DeviceMasked(out.value)
+        return self._device("mask", (d_ptr, nbytes, d_offsets, n_hay, uniform_len), (int(overlapping), fill, flags), DeviceMasked)
 
     # ---- merged spans: the union of the matches as start / end columns (acx_spans*)
     def spans(self, haystacks: Optional[Sequence[bytes]], overlapping: bool = False, codepoints: bool = False, gap: int = 0, *,
               single: Optional[bytes] = None) -> DeviceSpans:
         """host haystacks' merged spans, a host result; single=...: one haystack that is no batch (offsets = NULL, no row
         offsets)"""
-        out = ctypes.c_void_p()
-        if single is not None:
-            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
-            _check(lib().acx_spans(self._h, hb.ctypes.data, len(single), None, 0, int(overlapping), int(codepoints), gap,
-                                   ctypes.byref(out)))
-            return DeviceSpans(out.value, False)
-        hb, hoff = pack(haystacks)
-        _check(lib().acx_spans(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
-                               int(codepoints), gap, ctypes.byref(out)))
-        return DeviceSpans(out.value, True)
+        return self._host("spans", _host_arg(haystacks, single, _SINGLE_PADDED), (int(overlapping), int(codepoints), gap),
+                          DeviceSpans, single is None)
 
     def spans_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
                      overlapping: bool = False, codepoints: bool = False, gap: int = 0) -> DeviceSpans:
         """the haystacks in HBM searched and their matches merged there; nothing but the number of spans crosses the bus"""
-        out = ctypes.c_void_p()
-        _check(lib().acx_spans_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
-                                      int(codepoints), gap, ctypes.byref(out)))
-        return DeviceSpans(out.value, bool(uniform_len or d_offsets))
+        return self._device("spans", (d_ptr, nbytes, d_offsets, n_hay, uniform_len), (int(overlapping), int(codepoints), gap),
+                            DeviceSpans, _batched(d_offsets, uniform_len))
 
     # ---- snippets: the matched text and its context as the caller's own bytes (acx_snippets*)
     def snippets(self, haystacks: Optional[Sequence[bytes]], overlapping: bool = False, context: int = 0, flags: int = 0, *,
                  single: Optional[bytes] = None) -> DeviceSnippets:
         """host haystacks' snippets, a host result; single=...: one haystack that is no batch (offsets = NULL, no row
         offsets)"""
-        out = ctypes.c_void_p()
-        if single is not None:
-            hb = np.frombuffer(bytes(single) + b"\0", dtype=np.uint8)
-            _check(lib().acx_snippets(self._h, hb.ctypes.data, len(single), None, 0, int(overlapping), context, flags,
-                                      ctypes.byref(out)))
-            return DeviceSnippets(out.value, False)
-        hb, hoff = pack(haystacks)
-        _check(lib().acx_snippets(self._h, hb.ctypes.data, int(hoff[-1]), hoff.ctypes.data, len(haystacks), int(overlapping),
-                                  context, flags, ctypes.byref(out)))
-        return DeviceSnippets(out.value, True)
+        return self._host("snippets", _host_arg(haystacks, single, _SINGLE_PADDED), (int(overlapping), context, flags),
+                          DeviceSnippets, single is None)
 
     def snippets_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
                         overlapping: bool = False, context: int = 0, flags: int = 0) -> DeviceSnippets:
         """the haystacks in HBM searched and their matches cut there; nothing but the data's size crosses the bus"""
-        out = ctypes.c_void_p()
-        _check(lib().acx_snippets_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, int(overlapping),
-                                         context, flags, ctypes.byref(out)))
-        return DeviceSnippets(out.value, bool(uniform_len or d_offsets))
+        return self._device("snippets", (d_ptr, nbytes, d_offsets, n_hay, uniform_len), (int(overlapping), context, flags),
+                            DeviceSnippets, _batched(d_offsets, uniform_len))
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:
