@@ -26,6 +26,7 @@ from .ahocorasick_rs import (
     MatchSnippets,
     RowOffsets,
     split_rows,
+    ASCII_WORD_BYTES,
 )
 
 __acx_amd__ = True
@@ -57,6 +58,8 @@ __all__ = [
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",
+    # Extension: the default word set of find_whole_words_as_columns / _batch and filter_whole_words_batch
+    "ASCII_WORD_BYTES",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

@@ -31,6 +31,7 @@ try:
         MatchSnippets,
         RowOffsets,
         split_rows,
+        ASCII_WORD_BYTES,
     )
 except ImportError as e:  # pragma: no cover - build problem, fail loudly
     raise ImportError(
@@ -65,6 +66,8 @@ __all__ = [
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",
+    # Extension: the default word set of find_whole_words_as_columns / _batch and filter_whole_words_batch
+    "ASCII_WORD_BYTES",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

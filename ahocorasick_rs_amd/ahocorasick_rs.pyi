@@ -151,6 +151,9 @@ class RowOffsets:
 # anything else).  The result's .offsets is what the _batch methods take as offsets= beside the same tensor.
 def split_rows(data: Any, delimiter: Any = b"\n") -> RowOffsets: ...
 
+# extension: the default word set of the find_whole_words_* methods, ASCII [0-9A-Za-z_]
+ASCII_WORD_BYTES: bytes
+
 class AhoCorasick:
     def __init__(
         self,
@@ -247,6 +250,25 @@ class AhoCorasick:
         self, haystacks: Any, overlapping: bool = False, *, context: int = 0, offsets: Any = None,
         row_length: Optional[int] = None
     ) -> MatchSnippets: ...
+    # extension: whole-word matching (grep -w).  Of all occurrences of the patterns those whose neighbour bytes -- the byte in
+    # front of the match and the byte behind it; the ends of the haystack (of a row) are boundaries -- are no word bytes; of
+    # those the non-overlapping ones `matchkind` picks (overlapping=True: all of them).  The object must be a
+    # MatchKind.Standard one (ValueError otherwise); matchkind resolves the whole-word occurrences only.  word_bytes: None
+    # (ASCII_WORD_BYTES) or a bytes-like of the byte values that count (a str: TypeError).  The _batch forms take haystacks as
+    # count_by_pattern_sparse_batch does; filter_whole_words_batch is filter_batch on these matches
+    def find_whole_words_as_columns(
+        self, haystack: str, overlapping: bool = False, *, matchkind: MatchKind = MatchKind.LeftmostLongest,
+        word_bytes: Any = None
+    ) -> MatchColumns: ...
+    def find_whole_words_as_columns_batch(
+        self, haystacks: Any, overlapping: bool = False, *, matchkind: MatchKind = MatchKind.LeftmostLongest,
+        word_bytes: Any = None, offsets: Any = None, row_length: Optional[int] = None
+    ) -> MatchColumns: ...
+    def filter_whole_words_batch(
+        self, haystacks: Any, overlapping: bool = False, *, matchkind: MatchKind = MatchKind.LeftmostLongest,
+        word_bytes: Any = None, keep: str = "unmatched", min_matches: int = 1, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> FilteredRows: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -337,4 +359,23 @@ class BytesAhoCorasick:
         self, haystacks: Any, overlapping: bool = False, *, context: int = 0, offsets: Any = None,
         row_length: Optional[int] = None
     ) -> MatchSnippets: ...
+    # extension: whole-word matching (grep -w).  Of all occurrences of the patterns those whose neighbour bytes -- the byte in
+    # front of the match and the byte behind it; the ends of the haystack (of a row) are boundaries -- are no word bytes; of
+    # those the non-overlapping ones `matchkind` picks (overlapping=True: all of them).  The object must be a
+    # MatchKind.Standard one (ValueError otherwise); matchkind resolves the whole-word occurrences only.  word_bytes: None
+    # (ASCII_WORD_BYTES) or a bytes-like of the byte values that count (a str: TypeError).  The _batch forms take haystacks as
+    # count_by_pattern_sparse_batch does; filter_whole_words_batch is filter_batch on these matches
+    def find_whole_words_as_columns(
+        self, haystack: Any, overlapping: bool = False, *, matchkind: MatchKind = MatchKind.LeftmostLongest,
+        word_bytes: Any = None
+    ) -> MatchColumns: ...
+    def find_whole_words_as_columns_batch(
+        self, haystacks: Any, overlapping: bool = False, *, matchkind: MatchKind = MatchKind.LeftmostLongest,
+        word_bytes: Any = None, offsets: Any = None, row_length: Optional[int] = None
+    ) -> MatchColumns: ...
+    def filter_whole_words_batch(
+        self, haystacks: Any, overlapping: bool = False, *, matchkind: MatchKind = MatchKind.LeftmostLongest,
+        word_bytes: Any = None, keep: str = "unmatched", min_matches: int = 1, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> FilteredRows: ...
     def _info(self) -> dict[str, Any]: ...

@@ -105,6 +105,7 @@ _PAIRS = {
     "replace": [vp, vp, u64], "summarize": [i32, i32, u32], "find_columns": [i32, i32], "tally": [i32],
     "filter": [i32, u64, u32], "score": [i32, vp, u64], "filter_scored": [i32, vp, u64, i64, u32], "mask": [i32, u8, u32],
     "spans": [i32, i32, u64], "snippets": [i32, u64, u32],
+    "find_words": [i32, i32, vp], "filter_words": [i32, i32, vp, u64, u32],
 }
 # A result type: prefix -> (its size getters, whether _data / _copy take a `which`; None: it has no such pair).  _declare_result
 # adds acx_<prefix>_on_device and acx_free_<prefix>.
@@ -194,6 +195,8 @@ _SINGLES = {
     "acx_spans_rows_device": [vp, u64, vp, u64, u64, vp, vp, vp, _u64p],
     "acx_snippets_host": [vp, u64, vp, u64, vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, _u64p],
     "acx_snippets_rows_device": [vp, u64, vp, u64, vp, u64, vp, u64, u64, u32, vp, vp, vp, vp, vp, u64, _u64p],
+    "acx_words_host": [vp, u64, vp, u64, vp, u64, vp, i32, i32, vp, vp, vp, _u64p],
+    "acx_words_rows_device": [vp, u64, vp, u64, u64, vp, u64, vp, i32, i32, vp, vp, vp, _u64p],
 }
 
 
@@ -976,6 +979,57 @@ def spans_rows_device(d_records: int, n: int, d_counts: int, n_hay: int, gap: in
     return int(s.value)
 
 
+ASCII_WORD_BYTES = b"0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ_abcdefghijklmnopqrstuvwxyz"  # the default word set: [0-9A-Za-z_]
+
+
+def word_set(word_bytes) -> Optional[np.ndarray]:
+    """the 32 bytes acx_*words* take for a word set: None (the default, ASCII [0-9A-Za-z_]) stays None; else any bytes-like
+    of the byte values that count -- any length, duplicates allowed, empty allowed.  A str is a TypeError."""
+    if word_bytes is None:
+        return None
+    if isinstance(word_bytes, str):
+        raise TypeError("word_bytes must be bytes-like, not str")
+    out = np.zeros(32, dtype=np.uint8)
+    for v in bytes(word_bytes):
+        out[v >> 3] |= 1 << (v & 7)
+    return out
+
+
+def words_host(hay, offsets: Optional[Sequence[int]], matches, counts: Optional[Sequence[int]], overlapping: bool = False,
+               match_kind: int = MATCH_LEFTMOST_LONGEST, word_bytes=None):
+    """acx_words_host: the definition of whole-word matching on the host, no device involved.  hay: bytes-like; offsets: n + 1
+    from 0 to len(hay), or None (one row); matches: rows of (pattern, start, end) -- every occurrence, as an overlapping find
+    reports them -- counts[h] of them row h's (None: one row holds them all).  Returns (records, counts): the surviving
+    records as a MATCH_DTYPE array and the rows' new counts.  ValueError (code EINVAL) for a bad kind, offsets that do not
+    rise from 0 to len(hay) or counts that do not sum to the records."""
+    h = np.frombuffer(bytes(hay), dtype=np.uint8)
+    m, c, off, ws = _records(matches), _u64(counts), _u64(offsets), word_set(word_bytes)
+    n_hay = (1 if c is None else len(c)) if off is None else len(off) - 1
+    if c is not None and off is not None and len(c) != n_hay:
+        raise ValueError("offsets needs len(counts) + 1 entries")
+    out = np.zeros(len(m) + 1, dtype=MATCH_DTYPE)
+    oc = np.zeros(n_hay + 1, dtype=np.uint64)
+    n = ctypes.c_uint64()
+    _check(lib().acx_words_host(_ptr(h), len(h), None if off is None else off.ctypes.data, n_hay, _ptr(m), len(m),
+                                _ptr(c, _SPARE.ctypes.data), int(overlapping), match_kind, None if ws is None else ws.ctypes.data,
+                                out.ctypes.data, oc.ctypes.data, ctypes.byref(n)))
+    return out[:n.value], oc[:n_hay]
+
+
+def words_rows_device(d_hay: int, nbytes: int, d_offsets: int, n_hay: int, uniform_len: int, d_records: int, n: int,
+                      d_counts: int, overlapping: bool, match_kind: int, word_bytes, d_out_records: int, d_out_counts: int) -> int:
+    """acx_words_rows_device: the device stage alone -- nbytes at d_hay (any address) cut by n_hay + 1 offsets at d_offsets, by
+    uniform_len or not at all (one row), n records of 24 bytes at d_records in the overlapping find's order, n_hay counts at
+    d_counts -> the surviving records at d_out_records (room for n) and the rows' new counts at d_out_counts; complete when
+    it returns.  Returns the number of surviving records."""
+    ws = word_set(word_bytes)
+    k = ctypes.c_uint64()
+    _check(lib().acx_words_rows_device(d_hay or None, nbytes, d_offsets or None, n_hay, uniform_len, d_records or None, n,
+                                       d_counts or None, int(overlapping), match_kind, None if ws is None else ws.ctypes.data,
+                                       d_out_records or None, d_out_counts or None, ctypes.byref(k)))
+    return int(k.value)
+
+
 class DeviceSnippets(_BatchPartsResult):
     """The result of Automaton.snippets / snippets_device (acx_snippets_t): one snippet per match -- the bytes back to back
     (uint8), count + 1 offsets, the pattern and lead columns (int64) and, for a batch, n_hay + 1 row offsets -- in HBM
@@ -1370,6 +1424,40 @@ class Automaton(_Handle):
         """the haystacks in HBM searched and their matches cut there; nothing but the data's size crosses the bus"""
         return self._device("snippets", (d_ptr, nbytes, d_offsets, n_hay, uniform_len), (int(overlapping), context, flags),
                             DeviceSnippets, _batched(d_offsets, uniform_len))
+
+    # ---- whole words: the occurrences whose neighbour bytes are no word bytes, resolved by a match kind (acx_find_words* /
+    # acx_filter_words*; the handle must be a Standard one)
+    def find_words(self, haystacks: Optional[Sequence[bytes]], overlapping: bool = False,
+                   match_kind: int = MATCH_LEFTMOST_LONGEST, word_bytes=None, *, single: Optional[bytes] = None) -> DeviceColumns:
+        """host haystacks' whole-word matches as columns, a host result; single=...: one haystack that is no batch"""
+        ws = word_set(word_bytes)
+        return self._host("find_words", _host_arg(haystacks, single, _SINGLE_OWN),
+                          (int(overlapping), match_kind, None if ws is None else ws.ctypes.data), DeviceColumns, single is None)
+
+    def find_words_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
+                          overlapping: bool = False, match_kind: int = MATCH_LEFTMOST_LONGEST, word_bytes=None) -> DeviceColumns:
+        """the haystacks in HBM searched, tested and resolved there; nothing but two counts crosses the bus"""
+        ws = word_set(word_bytes)
+        return self._device("find_words", (d_ptr, nbytes, d_offsets, n_hay, uniform_len),
+                            (int(overlapping), match_kind, None if ws is None else ws.ctypes.data), DeviceColumns,
+                            _batched(d_offsets, uniform_len))
+
+    def filter_words(self, haystacks: Optional[Sequence[bytes]], overlapping: bool = False,
+                     match_kind: int = MATCH_LEFTMOST_LONGEST, word_bytes=None, min_matches: int = 1, flags: int = 0, *,
+                     single: Optional[bytes] = None) -> DeviceFiltered:
+        """filter() with a row's matches counted by whole word"""
+        ws = word_set(word_bytes)
+        return self._host("filter_words", _host_arg(haystacks, single, _SINGLE_ROW),
+                          (int(overlapping), match_kind, None if ws is None else ws.ctypes.data, min_matches, flags), DeviceFiltered)
+
+    def filter_words_device(self, d_ptr: int, nbytes: int, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0,
+                            overlapping: bool = False, match_kind: int = MATCH_LEFTMOST_LONGEST, word_bytes=None,
+                            min_matches: int = 1, flags: int = 0) -> DeviceFiltered:
+        """filter_device() with a row's matches counted by whole word"""
+        ws = word_set(word_bytes)
+        return self._device("filter_words", (d_ptr, nbytes, d_offsets, n_hay, uniform_len),
+                            (int(overlapping), match_kind, None if ws is None else ws.ctypes.data, min_matches, flags),
+                            DeviceFiltered)
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

@@ -1,5 +1,6 @@
 // columns_api.cpp -- a find's matches as columns (columns.hpp): the host split, the device route behind the find pipeline,
-// the acx_find_columns* entry points and the accessors of their result.
+// the acx_find_columns* entry points, acx_find_words* (the whole-word stage, words.hpp, in front of the columns) and the
+// accessors of their result.
 #include "columns.hpp"
 #include "replace.hpp"
 #include "result_block.hpp"
@@ -47,6 +48,49 @@ int run_columns(acx_automaton *a, Ctx *x, const uint8_t *d_hay, uint64_t len, co
         }
         return ACX_OK;
     });
+}
+
+// acx_find_words_device: an OVERLAPPING find on d_search (a case-insensitive handle: the folded copy), then the whole-word
+// stage (words.hpp) on the same stream over d_hay -- the caller's own bytes -- and its survivors straight into the columns.
+// Returns when the number of matches is known; the last kernel may still run (out->done).
+int run_words(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_search, uint64_t len, const Segments &G,
+              const WordsArgs &A, acx_columns **out) {
+    const bool segmented = rows_of(G).segmented;
+    // (an empty batch: nothing to search, one row offset)
+    return find_stage(a, x, d_search, len, G, 1, 0, !(segmented && G.n_hay == 0), out, [&](FindStage<acx_columns> &F) -> int {
+        acx_columns *R = F.R;
+        R->batch = segmented;
+        R->rows = segmented ? G.n_hay : 0;
+        const uint64_t n = F.r ? F.r->n : 0;
+        int rc;
+        if (!n) { // no occurrence: no whole word, and the rows' offsets are zeros
+            if ((rc = R->alloc()) != ACX_OK) return rc;
+            if (R->batch) HIPCHK(hipMemsetAsync(R->col(ACX_COL_ROW_OFFSETS), 0, (R->rows + 1) * 8, F.st));
+            return ACX_OK;
+        }
+        const uint64_t *d_counts = nullptr;
+        if ((rc = F.counts(&d_counts)) != ACX_OK) return rc;
+        WordsStage S;
+        rc = words_sizes(a->device, F.st, F.r->d_matches, n, d_counts, row_cut(G, len), false, d_hay, A, &S);
+        F.temp = S.block;
+        if (rc != ACX_OK) return rc;
+        R->n = S.total;
+        if ((rc = R->alloc()) != ACX_OK) return rc;
+        return words_finish(S, acx::WordsOut{nullptr, R->col(ACX_COL_PATTERN), R->col(ACX_COL_START), R->col(ACX_COL_END)},
+                            R->batch ? R->col(ACX_COL_ROW_OFFSETS) : nullptr, nullptr, F.st);
+    });
+}
+
+// a host result for n matches (rows: of a batch), its columns' first words zeroed; null: the error is set
+acx_columns *host_columns(int device, bool batch, uint64_t rows, uint64_t n) {
+    acx_columns *R = new_result<acx_columns>(device, false);
+    if (!R) return nullptr;
+    R->batch = batch;
+    R->rows = batch ? rows : 0;
+    R->n = n;
+    if (R->alloc() != ACX_OK) { free_result(R); return nullptr; }
+    for (int k = 0; k < 3; k++) R->col(k)[0] = 0; // (the one word of an empty column)
+    return R;
 }
 
 } // namespace
@@ -106,6 +150,55 @@ int acx_find_columns_device(acx_automaton_t *a, const void *d_hay, uint64_t len,
     *out = nullptr;
     return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, overlapping, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
         return run_columns(a, c, d_search, len, G, overlapping, codepoints, out);
+    });
+}
+
+int acx_find_words(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
+                   int match_kind, const uint8_t *word_set, acx_columns_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    WordsArgs A;
+    int rc = words_args(overlapping, match_kind, word_set, &A);
+    if (rc == ACX_OK) rc = check_overlapping(a); // (the stage's find is an overlapping one: the error, no device state)
+    if (rc != ACX_OK) return rc;
+    HostBatch B;
+    if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
+    const bool batch = offsets != nullptr;
+    if (len <= words_host_max() || !n_hay) {
+        std::vector<acx_match_t> m;
+        std::vector<uint64_t> counts;
+        if ((rc = words_host_find(a, B, len, n_hay, batch, A, word_set, &m, &counts)) != ACX_OK) return rc;
+        acx_columns *R = host_columns(a->device, batch, n_hay, m.size());
+        if (!R) return ACX_ENOMEM;
+        (void)acx_split_host(m.data(), m.size(), R->col(0), R->col(1), R->col(2));
+        if (batch) {
+            int64_t at = 0;
+            for (uint64_t h = 0; h < n_hay; h++) { R->col(3)[h] = at; at += (int64_t)counts[h]; }
+            R->col(3)[n_hay] = at;
+        }
+        *out = R;
+        return ACX_OK;
+    }
+    // device route: staged, searched and resolved under one lease; the columns come home in one copy
+    acx_columns *D = nullptr;
+    rc = staged_call(a, B, len, n_hay, batch, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        const int run = run_words(a, c, c->ws.hay, d_search, len, G, A, &D);
+        return run == ACX_OK ? D->wait() : run; // (the staging buffers are the context's: the lease ends behind the kernels)
+    });
+    return copy_down(rc, D, rc == ACX_OK ? host_columns(a->device, batch, n_hay, D->n) : nullptr, D ? D->block_bytes : 0,
+                     "copying the columns to the host", out);
+}
+
+int acx_find_words_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                          uint64_t uniform_len, int overlapping, int match_kind, const uint8_t *word_set, acx_columns_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    WordsArgs A;
+    const int rc = words_args(overlapping, match_kind, word_set, &A);
+    if (rc != ACX_OK) return rc;
+    // (a case-insensitive handle: the folded copy is searched, the caller's bytes are tested)
+    return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, 1, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_words(a, c, (const uint8_t *)d_hay, d_search, len, G, A, out);
     });
 }
 

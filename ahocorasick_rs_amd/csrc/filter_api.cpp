@@ -102,9 +102,12 @@ int check_args(uint64_t min_matches, uint32_t flags) {
 // offsets: no offset is reported) on d_search, then the stage on the same stream over d_hay -- the caller's own bytes.
 // Returns when the result's size is known; the gather may still run (out->done).  d_hay, d_search and G.offsets must stay
 // valid until then.  by != null: the rows' scores and their 0 / 1 verdicts are made between the find and the stage, on the
-// same stream, and the stage runs on the verdicts as its counts with min_matches = 1.
+// same stream, and the stage runs on the verdicts as its counts with min_matches = 1.  words != null (the find is an
+// overlapping one): the whole-word stage (words.hpp) runs between the find and the stage, on the same stream, and the stage
+// runs on the new counts -- no record is written.
 int run_filter(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_search, uint64_t len, const Segments &G,
-               int overlapping, uint64_t min_matches, uint32_t flags, acx_filtered_t **out, const ScoreBy *by = nullptr) {
+               int overlapping, uint64_t min_matches, uint32_t flags, acx_filtered_t **out, const ScoreBy *by = nullptr,
+               const WordsArgs *words = nullptr) {
     const uint64_t n = rows_of(G).n;
     // (an empty batch: nothing to search, one offset)
     return find_stage(a, x, d_search, len, G, overlapping, 0, n != 0, out, [&](FindStage<acx_filtered> &F) -> int {
@@ -125,9 +128,20 @@ int run_filter(acx_automaton *a, Ctx *x, const uint8_t *d_hay, const uint8_t *d_
                 d_counts = T.flags;
                 min_matches = 1;
             }
+            void *wblock = nullptr;
+            if (words && F.r->n) { // (no occurrence: the find's zeros are the counts)
+                WordsStage W;
+                rc = words_sizes(a->device, st, F.r->d_matches, F.r->n, d_counts, row_cut(G, len), false, d_hay, *words, &W);
+                wblock = W.block;
+                if (rc == ACX_OK) rc = words_finish(W, acx::WordsOut{nullptr, nullptr, nullptr, nullptr}, nullptr, W.new_counts, st);
+                if (rc != ACX_OK) { F.keep(wblock); return rc; } // (it goes back with the result, behind the stream)
+                d_counts = W.new_counts;
+            }
             const acx::RowCut rows = row_cut(G, len);
             rc = stage_sizes(a->device, st, rows, d_counts, min_matches, (flags & ACX_FILTER_KEEP_MATCHED) != 0, &S, &R->rows, &R->bytes);
             F.temp = S.block;
+            if (rc == ACX_OK) g_bufs.put(wblock, a->device); // (stage_sizes has waited for the stream: the new counts are spent)
+            else F.keep(wblock);
             if (rc != ACX_OK) return rc;
         }
         if ((rc = R->alloc()) != ACX_OK) return rc;
@@ -255,6 +269,53 @@ int acx_filter_scored_device(acx_automaton_t *a, const void *d_hay, uint64_t len
     if (rc != ACX_OK) return rc;
     return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, overlapping, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
         return run_filter(a, c, (const uint8_t *)d_hay, d_search, len, G, overlapping, 1, flags, out, &by);
+    });
+}
+
+int acx_filter_words(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, int overlapping,
+                     int match_kind, const uint8_t *word_set, uint64_t min_matches, uint32_t flags, acx_filtered_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    WordsArgs A;
+    int rc = check_args(min_matches, flags);
+    if (rc == ACX_OK) rc = words_args(overlapping, match_kind, word_set, &A);
+    if (rc == ACX_OK) rc = check_overlapping(a); // (the stage's find is an overlapping one: the error, no device state)
+    if (rc != ACX_OK) return rc;
+    HostBatch B;
+    const bool batch = offsets != nullptr;
+    if ((rc = host_batch(hay, &len, offsets, &n_hay, &B)) != ACX_OK) return rc;
+    if (len <= words_host_max() || !n_hay) {
+        std::vector<acx_match_t> m;
+        std::vector<uint64_t> counts;
+        if ((rc = words_host_find(a, B, len, n_hay, batch, A, word_set, &m, &counts)) != ACX_OK) return rc;
+        return host_filtered(a, B, len, n_hay, counts.data(), min_matches, flags, out);
+    }
+    // device route: staged, searched, resolved and compacted under one lease; the kept rows come home in one copy
+    acx_filtered_t *D = nullptr, *R = nullptr;
+    rc = staged_call(a, B, len, n_hay, batch, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        const int run = run_filter(a, c, c->ws.hay, d_search, len, G, 1, min_matches, flags, &D, nullptr, &A);
+        return run == ACX_OK ? D->wait() : run; // (the staging buffers are the context's: the lease ends behind the kernels)
+    });
+    if (rc == ACX_OK && (R = new_result<acx_filtered_t>(a->device, false))) {
+        R->n_src = D->n_src;
+        R->rows = D->rows;
+        R->bytes = D->bytes;
+        if (R->alloc() != ACX_OK) { free_result(R); R = nullptr; }
+    }
+    return copy_down(rc, D, R, D ? D->block_bytes : 0, "copying the kept rows to the host", out);
+}
+
+int acx_filter_words_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                            uint64_t uniform_len, int overlapping, int match_kind, const uint8_t *word_set, uint64_t min_matches,
+                            uint32_t flags, acx_filtered_t **out) {
+    if (!a || !out) return fail(ACX_EINVAL, "null argument");
+    *out = nullptr;
+    WordsArgs A;
+    int rc = check_args(min_matches, flags);
+    if (rc == ACX_OK) rc = words_args(overlapping, match_kind, word_set, &A);
+    if (rc != ACX_OK) return rc;
+    return device_call(a, d_hay, len, d_offsets, n_hay, uniform_len, 1, [&](Ctx *c, const uint8_t *d_search, const Segments &G) {
+        return run_filter(a, c, (const uint8_t *)d_hay, d_search, len, G, 1, min_matches, flags, out, nullptr, &A);
     });
 }
 

@@ -2017,6 +2017,143 @@ template <bool batch> PyObject *snippets(PyObject *self, PyObject *args, PyObjec
 }
 
 // ---------------------------------------------------------------------------
+// whole words: find_whole_words_as_columns / _batch -> MatchColumns (acx_find_words / acx_find_words_device) and
+// filter_whole_words_batch -> FilteredRows (acx_filter_words / acx_filter_words_device).  The search and the neighbour test
+// run on bytes; the str class's offsets become character indexes here, on the host.
+// ---------------------------------------------------------------------------
+constexpr char ASCII_WORD_BYTES[] = "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ_abcdefghijklmnopqrstuvwxyz";
+
+// word_bytes: None (the default set: *set stays null) or any bytes-like of the byte values that count; sets the exception
+bool parse_word_bytes(PyObject *o, uint8_t bits[32], const uint8_t **set) {
+    *set = nullptr;
+    if (!o || o == Py_None) return true;
+    if (PyUnicode_Check(o)) {
+        PyErr_SetString(PyExc_TypeError, "argument 'word_bytes': a bytes-like object of byte values is needed, not 'str'");
+        return false;
+    }
+    Py_buffer view;
+    if (!get_bytes_view(o, &view)) return false;
+    std::memset(bits, 0, 32);
+    const uint8_t *p = static_cast<const uint8_t *>(view.buf);
+    for (Py_ssize_t i = 0; i < view.len; i++) bits[p[i] >> 3] |= (uint8_t)(1u << (p[i] & 7));
+    PyBuffer_Release(&view);
+    *set = bits;
+    return true;
+}
+
+// the byte offsets of one row's matches [b, e) of a HOST result's columns to character indexes of the row's UTF-8 text: one
+// pass over the row numbers its bytes, then every offset is looked up
+bool to_characters(const uint8_t *row, uint64_t len, int64_t *start, int64_t *end, uint64_t b, uint64_t e) {
+    if (b == e) return true;
+    std::vector<int64_t> at;
+    try {
+        at.resize((size_t)len + 1);
+    } catch (...) { PyErr_NoMemory(); return false; }
+    int64_t chars = 0; // at[i] = the characters that begin before byte i (a match begins and ends between two characters)
+    for (uint64_t i = 0; i < len; i++) {
+        at[(size_t)i] = chars;
+        if ((row[i] & 0xC0) != 0x80) chars++;
+    }
+    at[(size_t)len] = chars;
+    for (uint64_t k = b; k < e; k++) {
+        start[k] = at[(size_t)std::min<uint64_t>((uint64_t)start[k], len)];
+        end[k] = at[(size_t)std::min<uint64_t>((uint64_t)end[k], len)];
+    }
+    return true;
+}
+
+// mode 0: find_whole_words_as_columns, 1: find_whole_words_as_columns_batch, 2: filter_whole_words_batch
+template <int mode> PyObject *whole_words(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
+    static const char *kw_s[] = {"haystack", "overlapping", "matchkind", "word_bytes", nullptr};
+    static const char *kw_b[] = {"haystacks", "overlapping", "matchkind", "word_bytes", "offsets", "row_length", nullptr};
+    static const char *kw_f[] = {"haystacks", "overlapping", "matchkind", "word_bytes", "keep", "min_matches", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *ov = nullptr, *mk_o = nullptr, *wb = nullptr, *keep = nullptr, *mm = nullptr, *offsets = nullptr,
+             *row_length = nullptr;
+    if (mode == 0 ? !PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$OO:find_whole_words_as_columns", const_cast<char **>(kw_s), &hay, &ov,
+                                                 &mk_o, &wb)
+        : mode == 1 ? !PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$OOOO:find_whole_words_as_columns_batch", const_cast<char **>(kw_b),
+                                                   &hay, &ov, &mk_o, &wb, &offsets, &row_length)
+                    : !PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$OOOOOO:filter_whole_words_batch", const_cast<char **>(kw_f), &hay,
+                                                   &ov, &mk_o, &wb, &keep, &mm, &offsets, &row_length))
+        return nullptr;
+    int overlapping = 0, kind = ACX_MATCH_LEFTMOST_LONGEST;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    if (mk_o && !parse_matchkind(mk_o, &kind)) return nullptr;
+    uint8_t bits[32];
+    const uint8_t *set = nullptr;
+    if (!parse_word_bytes(wb, bits, &set)) return nullptr;
+    uint32_t flags = 0;
+    if (keep && !parse_keep(keep, &flags)) return nullptr;
+    unsigned long long min_matches = 1;
+    if (mm) {
+        long long v;
+        int overflow;
+        if (!parse_int(mm, "min_matches", &v, &overflow)) return nullptr;
+        if (overflow < 0 || (!overflow && v < 1)) {
+            PyErr_SetString(PyExc_ValueError, "min_matches must be at least 1");
+            return nullptr;
+        }
+        min_matches = overflow ? ~0ull : (unsigned long long)v; // (more than any row can have)
+    }
+    const int device = acx_automaton_device(a);
+    if (mode == 2) {
+        BatchInput in;
+        if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
+        acx_filtered_t *f = nullptr;
+        const int rc = batch_dispatch(
+            device, in,
+            [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+                return acx_filter_words(a, p, len, off, rows, overlapping, kind, set, min_matches, flags, &f);
+            },
+            [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_len) {
+                return acx_filter_words_device(a, p, len, d_off, rows, row_len, overlapping, kind, set, min_matches, flags, &f);
+            });
+        if (rc == BAD_OFFSETS) return nullptr;
+        if (rc != ACX_OK) return raise_acx(rc);
+        return filtered_object(f, device, in.rows, utf8);
+    }
+    acx_columns_t *c = nullptr;
+    int rc;
+    bool converted = true;
+    if (mode == 1) {
+        BatchInput in;
+        if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
+        rc = batch_dispatch(
+            device, in,
+            [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+                return acx_find_words(a, p, len, off, rows, overlapping, kind, set, &c);
+            },
+            [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_len) {
+                return acx_find_words_device(a, p, len, d_off, rows, row_len, overlapping, kind, set, &c);
+            });
+        if (rc == BAD_OFFSETS) return nullptr;
+        if (rc == ACX_OK && utf8 && !in.tensor && !in.seq.all_ascii) { // a sequence of str: a host result, row by row
+            int64_t *start = const_cast<int64_t *>(acx_columns_data(c, ACX_COL_START)), *end = const_cast<int64_t *>(acx_columns_data(c, ACX_COL_END));
+            const int64_t *ro = acx_columns_data(c, ACX_COL_ROW_OFFSETS);
+            for (uint64_t h = 0; converted && ro && h < in.rows; h++)
+                converted = to_characters(in.seq.blob.data() + in.seq.off[(size_t)h], in.seq.off[(size_t)h + 1] - in.seq.off[(size_t)h], start, end,
+                                          (uint64_t)ro[h], (uint64_t)ro[h + 1]);
+        }
+    } else {
+        HaystackView v;
+        if (!haystack_view(hay, utf8, true, device, &v)) return nullptr;
+        rc = single_dispatch(
+            device, v, [&](const uint8_t *p, uint64_t len) { return acx_find_words(a, p, len, nullptr, 0, overlapping, kind, set, &c); },
+            [&](const uint8_t *p, uint64_t len) { return acx_find_words_device(a, p, len, nullptr, 0, 0, overlapping, kind, set, &c); });
+        if (rc == ACX_OK && utf8 && !v.is_ascii)
+            converted = to_characters(v.p, v.len, const_cast<int64_t *>(acx_columns_data(c, ACX_COL_START)),
+                                      const_cast<int64_t *>(acx_columns_data(c, ACX_COL_END)), 0, acx_columns_count(c));
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    if (!converted) { acx_free_columns(c); return nullptr; }
+    OwnerObject *o = new_owner(RT_MATCH_COLUMNS, c, device);
+    if (o) static_cast<MatchColumnsObject *>(o)->batch = mode == 1;
+    return reinterpret_cast<PyObject *>(o);
+}
+
+// ---------------------------------------------------------------------------
 // split_rows(data, delimiter=b"\n") -> RowOffsets (acx_split_rows / acx_split_rows_device): a delimited buffer cut into rows.
 // A module function -- no automaton is involved.  A RowOffsets owns the acx_rows_t; .offsets is a Column with the lifetime
 // chain of a MatchColumns' columns, and what the _batch methods take as offsets=.
@@ -2219,6 +2356,29 @@ const PyMethodDef SHARED_METHODS[] = {
      "row_offsets[h] .. row_offsets[h + 1] - 1 are row h's; a snippet never crosses a row.  haystacks: a sequence, or ONE 1-D "
      "contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for cover_spans_batch.  A tensor on "
      "the automaton's device is searched and cut there and every part stays there."},
+    {"find_whole_words_as_columns", KW(whole_words<0>),
+     "find_whole_words_as_columns(haystack, overlapping=False, *, matchkind=MatchKind.LeftmostLongest, word_bytes=None) -> "
+     "MatchColumns\n\n[extension] grep -w for the object's patterns: of all their occurrences those whose neighbour bytes "
+     "(the byte in front of the match and the byte behind it; a haystack's ends are boundaries) are no word bytes, and of "
+     "those the non-overlapping ones matchkind picks (overlapping=True: all of them, in the overlapping search's order).  "
+     "The object must be a MatchKind.Standard one (ValueError otherwise): the search behind it is an overlapping one, and "
+     "matchkind resolves the whole-word occurrences only -- with ['he cat', 'cat'] on 'the cat' the result is cat at 4, "
+     "which a filter over a leftmost search loses.  word_bytes: None (ASCII_WORD_BYTES: [0-9A-Za-z_]) or a bytes-like of the "
+     "byte values that count as word bytes.  AhoCorasick: character indexes (the test runs on UTF-8 bytes); "
+     "BytesAhoCorasick: byte offsets, and a __dlpack__ tensor on the automaton's device is searched, tested and resolved "
+     "there."},
+    {"find_whole_words_as_columns_batch", KW(whole_words<1>),
+     "find_whole_words_as_columns_batch(haystacks, overlapping=False, *, matchkind=MatchKind.LeftmostLongest, "
+     "word_bytes=None, offsets=None, row_length=None) -> MatchColumns\n\n[extension] find_whole_words_as_columns of every row "
+     "in one call, with .row_offsets; a row's first byte is never the neighbour of the row before it.  haystacks: a sequence, "
+     "or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "
+     "count_by_pattern_sparse_batch (byte offsets local to the row for a tensor).  A tensor on the automaton's device is "
+     "searched and resolved there and the columns stay there."},
+    {"filter_whole_words_batch", KW(whole_words<2>),
+     "filter_whole_words_batch(haystacks, overlapping=False, *, matchkind=MatchKind.LeftmostLongest, word_bytes=None, "
+     "keep='unmatched', min_matches=1, offsets=None, row_length=None) -> FilteredRows\n\n[extension] filter_batch with a row's "
+     "matches counted as find_whole_words_as_columns_batch reports them: a block list applied by whole word keeps 'class' "
+     "and 'Scunthorpe'.  .data is the caller's own bytes."},
     {"find_matches_as_columns", KW(columns<false>),
      "[extension] find_matches_as_indexes(haystack, overlapping) as a MatchColumns: three int64 columns (pattern, start, "
      "end) exported through DLPack, in host memory for a host haystack and in HBM on the automaton's device for a "
@@ -2320,6 +2480,7 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
         m, "ahocorasick_rs.BytesAhoCorasick", sizeof(BacObject), bac_new,
         "Search for multiple pattern bytes against a single bytes haystack.\n\n"
         "BytesAhoCorasick(patterns, matchkind=MatchKind.Standard, implementation=None, ascii_case_insensitive=False)", BAC_METHODS);
+    ok = ok && PyModule_AddObject(m, "ASCII_WORD_BYTES", PyBytes_FromString(ASCII_WORD_BYTES)) == 0;
     if (!ok) { Py_DECREF(m); return nullptr; }
     return m;
 }

@@ -8,6 +8,7 @@
 
 #include "find_pipeline.hpp"
 #include "stage_device.hpp"
+#include "words.hpp"
 
 namespace acxh ACX_HIDDEN {
 
@@ -223,6 +224,44 @@ struct ScoreTemps {
 int score_stage(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, const uint64_t *d_counts, uint64_t rows,
                 const int32_t *h_weights, const int32_t *d_weights, uint64_t n_patterns, bool check_sum, int64_t *d_score,
                 const int64_t *min_score, ScoreTemps *T);
+
+struct HostBatch;
+
+// The whole-word stage (words.hpp; words_api.cpp) behind an OVERLAPPING find's records and counts, for acx_words_rows_device,
+// acx_find_words_device (columns_api.cpp) and the hook of acx_filter_words_device (filter_api.cpp).
+struct WordsArgs {
+    int overlapping = 0; // 1: every whole-word occurrence; 0: those `kind` picks
+    int kind = ACX_MATCH_STANDARD;
+    acx::WordSet W{};
+};
+// match_kind is one of the three (ACX_EINVAL); word_set: 32 bytes, or null: ASCII [0-9A-Za-z_]
+int words_args(int overlapping, int match_kind, const uint8_t *word_set, WordsArgs *A);
+// What words_sizes leaves for words_finish: the items, their flags and ranks, the rows.  `block`: the stage's temporaries,
+// one block of the buffer cache -- the caller's to return, behind the stage's kernels.
+struct WordsStage {
+    void *block = nullptr;
+    const uint8_t *flag = nullptr;
+    const acx_match_t *items = nullptr;
+    const uint32_t *src = nullptr;
+    const int64_t *base = nullptr, *rows_off = nullptr;
+    int64_t *new_off = nullptr;    // rows + 1 words of the block, for a caller that wants the counts alone
+    uint64_t *new_counts = nullptr; // rows words of the block, for a caller that has nowhere else to put them
+    uint64_t n_items = 0, rows = 0, total = 0;
+};
+// The stage up to the point where the result's size is known (n > 0, R.n > 0).  d_m: n records; d_counts: R.n words that sum
+// to n (check_sum: record_offsets above); d_hay: the caller's own R.len bytes.  The stream is waited for: G->total is valid.
+int words_sizes(int device, hipStream_t st, const acx_match_t *d_m, uint64_t n, const uint64_t *d_counts, const acx::RowCut &R,
+                bool check_sum, const uint8_t *d_hay, const WordsArgs &A, WordsStage *G);
+// ... and from there: the G.total records to `out`, their rows' offsets (G.rows + 1 words, or null) and counts (G.rows words,
+// or null) -- device memory, 8-byte aligned
+int words_finish(const WordsStage &G, const acx::WordsOut &out, int64_t *row_offsets, uint64_t *counts, hipStream_t st);
+// ACX_WORDS_HOST_MAX (bytes, read per call): host haystacks up to this size take the host route of acx_find_words /
+// acx_filter_words.  The default is ACX_SUMMARY_HOST_MAX's, which is itself not a measured crossover.
+uint64_t words_host_max();
+// The host route's middle: an overlapping find of B's rows as it is (each route under its own lease), then acx_words_host.
+// out: the surviving records; counts: n_hay + 1 words, the rows' new counts.
+int words_host_find(acx_automaton *a, const HostBatch &B, uint64_t len, uint64_t n_hay, bool batch, const WordsArgs &A,
+                    const uint8_t *word_set, std::vector<acx_match_t> *out, std::vector<uint64_t> *counts);
 
 // A host entry point's haystacks as the stages take them: offsets (n_hay + 1 of them, monotone; null: ONE haystack of *len
 // bytes, *n_hay becomes 1) cut `hay`; afterwards *len bytes at B->hay (null when there are none) are the haystacks, cut by

@@ -49,6 +49,8 @@ extern "C" {
  *     ninth addendum (additive as well): acx_snippets / acx_snippets_device / acx_snippets_host / acx_snippets_rows_device,
  *     ACX_SNIP_*, the acx_snippets_t accessors (acx_snippets_count, _rows, _nbytes, _on_device, _data, _copy,
  *     acx_free_snippets);
+ *     tenth addendum (additive as well): whole-word matching -- acx_words_host / acx_words_rows_device, acx_find_words /
+ *     acx_find_words_device (an acx_columns_t), acx_filter_words / acx_filter_words_device (an acx_filtered_t);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -843,6 +845,58 @@ int acx_snippets_rows_device(const acx_match_t *d_records, uint64_t n, const uin
                              uint64_t len, const uint64_t *d_offsets, uint64_t uniform_len, uint64_t context, uint32_t flags,
                              int64_t *d_out_offsets, int64_t *d_pattern, int64_t *d_lead, int64_t *d_row_offsets, uint8_t *d_data,
                              uint64_t data_capacity, uint64_t *total);
+
+/* ---- whole-word matching: grep -w for a dictionary.  Per row B of L bytes, on the caller's own bytes (a case-insensitive
+ * handle matches on its folded copy, the neighbour test reads the unfolded bytes), with a word set W of byte values:
+ *   Occ  every (p, s, e) with B[s:e] equal to pattern p -- what the handle's overlapping find reports, copies of equal patterns
+ *        included
+ *   WW   the (p, s, e) of Occ with (s == 0 or B[s - 1] not in W) and (e == L or B[e] not in W).  A row's end is a boundary; the
+ *        pattern's own bytes are not looked at: the lookaround form (?<![W])(?:...)(?![W]), not \b.
+ * overlapping != 0: the result is WW in the overlapping find's order (end ascending, longer first, pattern index).
+ * overlapping == 0: pos = 0; among the records of WW with s >= pos the least by the kind's key is reported, pos = its e, and
+ * again -- the keys: ACX_MATCH_LEFTMOST_FIRST (s, p), ACX_MATCH_LEFTMOST_LONGEST (s, -e, p), ACX_MATCH_STANDARD (e, s, p).
+ * That is not a filter over the kind's own find: with "he cat" and "cat" on "the cat" a leftmost find reports "he cat" at 1,
+ * no whole word, which shadows the whole word "cat" at 4.
+ * word_set: 32 bytes, byte v is a word byte iff word_set[v >> 3] >> (v & 7) & 1 -- host memory in every form; NULL: ASCII
+ * [0-9A-Za-z_].  match_kind outside the three is ACX_EINVAL.
+ * acx_find_words / acx_find_words_device: the haystack arguments of acx_find_columns / _device, byte offsets, the result an
+ * acx_columns_t -- its accessors as they are.  The stage's find is an overlapping one: a handle that is not Standard is
+ * ACX_EOVERLAP before any device state is touched, and match_kind is the resolve's kind, not the handle's.  Host haystacks
+ * give a host result: up to ACX_WORDS_HOST_MAX bytes (the environment, read per call; 1 MiB) acx_find / acx_find_batch runs
+ * as it is and acx_words_host resolves, beyond that the bytes are staged and the device route runs.  The device form returns
+ * when the number of matches is known (overlapping == 0: the number of whole words crosses the bus before it); the last
+ * kernel may still run and the accessors wait for it.  ACX_ETOOBIG: 2^38 bytes or 2^32 occurrences in one call.
+ * acx_filter_words / acx_filter_words_device: acx_filter / acx_filter_device with a row's matches counted after the whole-word
+ * stage -- the find, the stage, then the row filter on the new counts. */
+int acx_find_words(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one haystack */,
+                   uint64_t n_hay, int overlapping, int match_kind, const uint8_t *word_set /* NULL: the default */,
+                   acx_columns_t **out);
+int acx_find_words_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                          uint64_t uniform_len, int overlapping, int match_kind, const uint8_t *word_set, acx_columns_t **out);
+int acx_filter_words(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one row */,
+                     uint64_t n_hay, int overlapping, int match_kind, const uint8_t *word_set, uint64_t min_matches,
+                     uint32_t flags, acx_filtered_t **out);
+int acx_filter_words_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                            uint64_t uniform_len, int overlapping, int match_kind, const uint8_t *word_set, uint64_t min_matches,
+                            uint32_t flags, acx_filtered_t **out);
+/* The stage alone.  m: n_m records, all rows behind one another, counts[h] of them row h's (ACX_EINVAL when they do not sum to
+ * n_m), or counts = NULL: one row holds them all; offsets: n_hay + 1 from 0 to len (ACX_EINVAL otherwise), or NULL: one row.
+ * out_m: room for n_m records, the first *n_out are written, row by row in the definition's order; out_counts: n_hay words
+ * (one row: 1), the rows' new counts.  A record with start >= end or end beyond its row is no occurrence and is dropped.
+ * acx_words_host: host memory, no device needed -- the definition inside the library, memory-safe for any records (a row's
+ * records are sorted by the kind's key, whatever their order).
+ * acx_words_rows_device: the device stage on a caller's records, counts and bytes (d_offsets / uniform_len as for
+ * acx_find_device, neither: one row; word_set stays host memory), synchronous: the outputs are complete when it returns.
+ * Records, counts, offsets and outputs 8-byte aligned, d_hay at any address.  It relies on a row's records being in the
+ * overlapping find's order (for other orders it is memory-safe, not the definition); d_out_m / d_out_counts feed every
+ * acx_*_rows_device stage.  ACX_ETOOBIG: len >= 2^38, n_m >= 2^32, or (leftmost kinds) a pattern of 2^24 or more. */
+int acx_words_host(const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one row */, uint64_t n_hay,
+                   const acx_match_t *m, uint64_t n_m, const uint64_t *counts /* NULL: one row */, int overlapping, int match_kind,
+                   const uint8_t *word_set /* NULL: the default */, acx_match_t *out_m, uint64_t *out_counts /* NULL: not wanted */,
+                   uint64_t *n_out);
+int acx_words_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
+                          const acx_match_t *d_m, uint64_t n_m, const uint64_t *d_counts, int overlapping, int match_kind,
+                          const uint8_t *word_set, acx_match_t *d_out_m, uint64_t *d_out_counts, uint64_t *n_out);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
