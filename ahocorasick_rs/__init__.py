@@ -24,6 +24,7 @@ from .ahocorasick_rs import (
     MaskedRows,
     MatchSpans,
     MatchSnippets,
+    TokenLabels,
     RowOffsets,
     split_rows,
     ASCII_WORD_BYTES,
@@ -55,6 +56,8 @@ __all__ = [
     "MatchSpans",
     # Extension: the result of find_matches_as_snippets / find_matches_as_snippets_batch
     "MatchSnippets",
+    # Extension: the result of label_tokens / label_tokens_batch
+    "TokenLabels",
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",

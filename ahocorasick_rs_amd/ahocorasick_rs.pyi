@@ -133,6 +133,21 @@ class MatchSnippets:
     def __len__(self) -> int: ...  # the number of snippets
     def tolist(self) -> Any: ...  # list[str] (AhoCorasick) or list[bytes]; one such list per row of a batch
 
+# extension: the result of label_tokens / label_tokens_batch -- a search's matches mapped onto token boundaries, one entry
+# per token, where the search ran.  A match touches token t iff token_start[t] < match.end and token_end[t] > match.start; the
+# token's owner is the first touching match in the search's order
+class TokenLabels:
+    @property
+    def pattern(self) -> Column: ...  # len(self) int64 entries: the owner's pattern, or -1; pattern >= 0 is the token mask
+    @property
+    def begin(self) -> Column: ...  # len(self) uint8 entries: 1 iff the token is the first of its owner's (the B of BIO)
+    @property
+    def row_offsets(self) -> Optional[list[int]]: ...  # a sequence of haystacks: len(haystacks) + 1 entries from 0; else None
+    @property
+    def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
+    def __len__(self) -> int: ...  # the number of tokens
+    def tolist(self) -> Any: ...  # list[tuple[int, int]] of (pattern, begin), or one such list per haystack of a sequence
+
 # extension: the result of split_rows -- the offsets that cut a delimited buffer into rows, where the data lies
 class RowOffsets:
     @property
@@ -269,6 +284,19 @@ class AhoCorasick:
         word_bytes: Any = None, keep: str = "unmatched", min_matches: int = 1, offsets: Any = None,
         row_length: Optional[int] = None
     ) -> FilteredRows: ...
+    # extension: the matches of find_matches_as_indexes(haystack, overlapping) mapped onto tokens.  token_offsets: the k + 1
+    # boundaries of k tokens, non-decreasing, within 0 .. len(haystack), in CHARACTERS -- the unit of find_matches_as_indexes
+    # and of a tokenizer's offset_mapping -- as a sequence of ints or an int64 buffer (ValueError otherwise).  The _batch form
+    # takes a sequence of haystacks with one such entry per haystack (a token never crosses a haystack; .row_offsets cuts the
+    # tokens by haystack), or ONE uint8 __dlpack__ tensor cut by offsets / row_length as mask_all_batch takes it, with ONE 1-D
+    # contiguous int64 __dlpack__ tensor of T + 1 GLOBAL BYTE boundaries on the same device (tokens may cross rows; on the
+    # automaton's device everything stays in HBM, the boundaries are the caller's word, as offsets are, and the TokenLabels
+    # keeps the input tensors alive until it goes: they must not be written before an accessor of a column has returned)
+    def label_tokens(self, haystack: str, token_offsets: Any, overlapping: bool = False) -> TokenLabels: ...
+    def label_tokens_batch(
+        self, haystacks: Any, token_offsets: Any, overlapping: bool = False, *, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> TokenLabels: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -378,4 +406,18 @@ class BytesAhoCorasick:
         word_bytes: Any = None, keep: str = "unmatched", min_matches: int = 1, offsets: Any = None,
         row_length: Optional[int] = None
     ) -> FilteredRows: ...
+    # extension: the matches of find_matches_as_indexes(haystack, overlapping) mapped onto tokens.  token_offsets: the k + 1
+    # boundaries of k tokens, non-decreasing, within 0 .. len(haystack), in BYTES, as a sequence of ints or an int64 buffer
+    # (ValueError otherwise); with a __dlpack__ tensor as haystack it is a 1-D contiguous int64 __dlpack__ tensor on the
+    # haystack's device.  The _batch form takes a sequence of haystacks with one such entry per haystack (a token never
+    # crosses a haystack; .row_offsets cuts the tokens by haystack), or ONE uint8 __dlpack__ tensor cut by offsets /
+    # row_length as mask_all_batch takes it, with ONE 1-D contiguous int64 __dlpack__ tensor of T + 1 GLOBAL byte boundaries
+    # on the same device (tokens may cross rows).  On the automaton's device everything stays in HBM, the boundaries are the
+    # caller's word, as offsets are, and the TokenLabels keeps the input tensors alive until it goes: they must not be
+    # written before an accessor of a column has returned
+    def label_tokens(self, haystack: Any, token_offsets: Any, overlapping: bool = False) -> TokenLabels: ...
+    def label_tokens_batch(
+        self, haystacks: Any, token_offsets: Any, overlapping: bool = False, *, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> TokenLabels: ...
     def _info(self) -> dict[str, Any]: ...

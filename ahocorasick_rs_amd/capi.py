@@ -113,6 +113,7 @@ _RESULTS = {
     "summary": (("total",), None), "columns": (("count", "rows"), True), "tally": (("nnz", "rows"), True),
     "filtered": (("rows", "bytes"), True), "scores": (("rows",), False), "masked": (("bytes", "rows"), False),
     "rows": (("count", "bytes"), None), "spans": (("count", "rows"), True), "snippets": (("count", "rows", "nbytes"), True),
+    "token_labels": (("count",), None),
 }
 # Everything else, one row each: name -> arguments, or (arguments, what it returns) where that is no status.  (acx_version is
 # declared by lib() itself, ahead of the version check.)
@@ -197,6 +198,15 @@ _SINGLES = {
     "acx_snippets_rows_device": [vp, u64, vp, u64, vp, u64, vp, u64, u64, u32, vp, vp, vp, vp, vp, u64, _u64p],
     "acx_words_host": [vp, u64, vp, u64, vp, u64, vp, i32, i32, vp, vp, vp, _u64p],
     "acx_words_rows_device": [vp, u64, vp, u64, u64, vp, u64, vp, i32, i32, vp, vp, vp, _u64p],
+    # (no _PAIRS row: the host form alone takes `codepoints`)
+    "acx_tokens": [vp, vp, u64, vp, u64, i32, i32, vp, vp, u64, _out],
+    "acx_tokens_device": [vp, vp, u64, vp, u64, u64, i32, vp, vp, u64, _out],
+    "acx_token_labels_pattern": ([vp], vp),
+    "acx_token_labels_begin": ([vp], vp),
+    "acx_token_labels_copy_pattern": [vp, vp],
+    "acx_token_labels_copy_begin": [vp, vp],
+    "acx_tokens_host": [vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, vp],
+    "acx_tokens_rows_device": [u64, vp, u64, u64, vp, u64, vp, vp, vp, u64, vp, vp],
 }
 
 
@@ -880,6 +890,60 @@ def mask_rows_device(d_hay: int, nbytes: int, d_offsets: int, n_hay: int, unifor
                                       d_counts or None, fill, flags, d_out or None))
 
 
+class DeviceTokenLabels(_Result):
+    """The result of Automaton.tokens / tokens_device (acx_token_labels_t): per token the owner's pattern (int64, -1: none) and
+    the begin flag (uint8) -- in HBM (on_device) or in host memory.  pattern() / begin() copy them out; pattern_ptr() /
+    begin_ptr() are where they lie (all wait for the device stage)."""
+    _PREFIX = "token_labels"
+    count = _Size("count")
+
+    def pattern_ptr(self) -> int:
+        return self._address("pattern")
+
+    def begin_ptr(self) -> int:
+        return self._address("begin")
+
+    def pattern(self) -> np.ndarray:
+        return self._copy_out("copy_pattern", self.count, np.int64)
+
+    def begin(self) -> np.ndarray:
+        return self._copy_out("copy_begin", self.count, np.uint8)
+
+
+def _i64(values) -> np.ndarray:
+    """int64 words, contiguous (an empty array still has an address to give)"""
+    a = np.ascontiguousarray(np.asarray(values, dtype=np.int64).reshape(-1))
+    return a if a.size else np.zeros(1, dtype=np.int64)[:0]
+
+
+def tokens_host(matches, counts: Optional[Sequence[int]], offsets: Optional[Sequence[int]], length: int, ts, te
+                ) -> Tuple[np.ndarray, np.ndarray]:
+    """acx_tokens_host: the definition of the token labels on the host, no device involved, any unit.  matches: rows of
+    (pattern, start, end), counts[h] of them row h's (None: one row holds them all); offsets: n + 1 from 0 to length, or None
+    (one row of `length` positions); ts, te: the tokens' global starts and ends.  Returns (pattern int64, begin uint8), an entry
+    per token.  ValueError (code EINVAL) for token arrays that do not rise or pass `length`, offsets that do not rise from 0 to
+    `length` or counts that do not sum to the rows."""
+    m, c, off, s, e = _records(matches), _u64(counts), _u64(offsets), _i64(ts), _i64(te)
+    if len(s) != len(e):
+        raise ValueError("ts and te need one entry per token each")
+    n_hay = (1 if c is None else len(c)) if off is None else len(off) - 1
+    if c is not None and off is not None and len(c) != n_hay:
+        raise ValueError("offsets needs len(counts) + 1 entries")
+    pattern, begin = np.zeros(max(len(s), 1), dtype=np.int64), np.zeros(max(len(s), 1), dtype=np.uint8)
+    _check(lib().acx_tokens_host(_ptr(m), len(m), _ptr(c, _SPARE.ctypes.data), n_hay, None if off is None else off.ctypes.data,
+                                 length, s.ctypes.data, e.ctypes.data, len(s), pattern.ctypes.data, begin.ctypes.data))
+    return pattern[:len(s)], begin[:len(s)]
+
+
+def tokens_rows_device(nbytes: int, d_offsets: int, n_hay: int, uniform_len: int, d_records: int, n: int, d_counts: int,
+                       d_ts: int, d_te: int, n_tokens: int, d_pattern: int, d_begin: int) -> None:
+    """acx_tokens_rows_device: the device stage alone -- nbytes cut by n_hay + 1 offsets at d_offsets, by uniform_len or not at
+    all (one row), n records of 24 bytes at d_records, n_hay counts at d_counts, n_tokens int64 words at d_ts and at d_te ->
+    n_tokens int64 words at d_pattern and n_tokens bytes at d_begin (any address); complete when it returns"""
+    _check(lib().acx_tokens_rows_device(nbytes, d_offsets or None, n_hay, uniform_len, d_records or None, n, d_counts or None,
+                                        d_ts or None, d_te or None, n_tokens, d_pattern or None, d_begin or None))
+
+
 class DeviceRows(_Result):
     """The result of split_rows / split_rows_device (acx_rows_t): the offsets that cut nbytes of delimited data into rows --
     rows + 1 int64 words from 0 to nbytes, in HBM (on_device, on `device`) or in host memory.  `rows` is valid at once;
@@ -1458,6 +1522,23 @@ class Automaton(_Handle):
         return self._device("filter_words", (d_ptr, nbytes, d_offsets, n_hay, uniform_len),
                             (int(overlapping), match_kind, None if ws is None else ws.ctypes.data, min_matches, flags),
                             DeviceFiltered)
+
+    # ---- token labels: the matches mapped onto token boundaries (acx_tokens*)
+    def tokens(self, haystacks: Optional[Sequence[bytes]], ts, te, overlapping: bool = False, codepoints: bool = False, *,
+               single: Optional[bytes] = None) -> DeviceTokenLabels:
+        """host haystacks' token labels, a host result; ts, te: the tokens' global starts and ends (bytes, or characters with
+        codepoints); single=...: one haystack that is no batch (offsets = NULL)"""
+        s, e = _i64(ts), _i64(te)
+        if len(s) != len(e):
+            raise ValueError("ts and te need one entry per token each")
+        return self._host("tokens", _host_arg(haystacks, single, _SINGLE_ROW),
+                          (int(overlapping), int(codepoints), s.ctypes.data, e.ctypes.data, len(s)), DeviceTokenLabels)
+
+    def tokens_device(self, d_ptr: int, nbytes: int, d_ts: int, d_te: int, n_tokens: int, *, d_offsets: int = 0, n_hay: int = 0,
+                      uniform_len: int = 0, overlapping: bool = False) -> DeviceTokenLabels:
+        """the batch in HBM searched and its matches mapped onto the tokens there; the columns stay there"""
+        return self._device("tokens", (d_ptr, nbytes, d_offsets, n_hay, uniform_len),
+                            (int(overlapping), d_ts or None, d_te or None, n_tokens), DeviceTokenLabels)
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

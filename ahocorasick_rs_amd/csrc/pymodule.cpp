@@ -17,6 +17,7 @@
 #include <cstring>
 #include <iterator>
 #include <map>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -874,6 +875,13 @@ struct MatchSnippetsObject : OwnerObject {
     bool batch;
     bool utf8; // made by the str class: tolist() decodes
 };
+enum { TL_PATTERN = 0, TL_BEGIN = 1 };
+struct TokenLabelsObject : OwnerObject {
+    std::vector<int64_t> *row_offsets; // the sequence form: where every row's tokens begin (rows + 1 entries); else null
+    // the device route: the capsules of the haystack, its offsets and the boundaries.  The call returns with the stage in
+    // flight and its kernels read all three on the library's stream: the tensors stay the producer's until the result goes
+    PyObject *inputs[3];
+};
 enum { MR_OFFSETS = 0, MR_DATA = 1 };
 struct MaskedRowsObject : OwnerObject {
     bool utf8;                 // made by the str class
@@ -914,7 +922,7 @@ struct ResultType {
     PyTypeObject *type; // made by PyInit
     PyMethodDef methods[2];
 };
-enum { RT_MATCH_COLUMNS, RT_PATTERN_COUNTS, RT_FILTERED_ROWS, RT_ROW_SCORES, RT_MASKED_ROWS, RT_ROW_OFFSETS, RT_MATCH_SPANS, RT_MATCH_SNIPPETS, RT_COUNT };
+enum { RT_MATCH_COLUMNS, RT_PATTERN_COUNTS, RT_FILTERED_ROWS, RT_ROW_SCORES, RT_MASKED_ROWS, RT_ROW_OFFSETS, RT_MATCH_SPANS, RT_MATCH_SNIPPETS, RT_TOKEN_LABELS, RT_COUNT };
 extern ResultType RESULT_TYPES[RT_COUNT];
 
 OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
@@ -1247,6 +1255,40 @@ void mr_dealloc(PyObject *self) {
     owner_dealloc(self);
 }
 
+// TokenLabels: list[tuple[int, int]] of (pattern, begin), or one such list per row for the sequence form
+const void *labels_part(const acx_token_labels_t *l, int which) {
+    return which == TL_PATTERN ? static_cast<const void *>(acx_token_labels_pattern(l)) : acx_token_labels_begin(l);
+}
+uint64_t tl_part_len(const OwnerObject *o, int which, int *elem) {
+    *elem = which == TL_BEGIN;
+    return acx_token_labels_count(handle<acx_token_labels_t>(o));
+}
+PyObject *tl_tolist(PyObject *self, PyObject *) {
+    const acx_token_labels_t *l = handle<acx_token_labels_t>(self);
+    const uint64_t n = acx_token_labels_count(l);
+    std::vector<int64_t> pattern((size_t)n + 1);
+    std::vector<uint8_t> begin((size_t)n + 1);
+    const int rc = nogil([&] {
+        const int rc = acx_token_labels_copy_pattern(l, pattern.data());
+        return rc == ACX_OK ? acx_token_labels_copy_begin(l, begin.data()) : rc;
+    });
+    if (rc != ACX_OK) return raise_acx(rc);
+    return rows_of(static_cast<TokenLabelsObject *>(owner_of(self))->row_offsets, n,
+                   [&](uint64_t i) { return Py_BuildValue("(Li)", (long long)pattern[(size_t)i], (int)begin[(size_t)i]); });
+}
+PyObject *tl_get_row_offsets(PyObject *s, void *) {
+    const std::vector<int64_t> *ro = static_cast<TokenLabelsObject *>(owner_of(s))->row_offsets;
+    if (!ro) Py_RETURN_NONE;
+    return list_of(0, ro->size(), [&](uint64_t i) { return PyLong_FromLongLong((long long)(*ro)[(size_t)i]); });
+}
+void tl_dealloc(PyObject *self) {
+    TokenLabelsObject *o = static_cast<TokenLabelsObject *>(owner_of(self));
+    delete o->row_offsets;
+    PyObject *inputs[3] = {o->inputs[0], o->inputs[1], o->inputs[2]};
+    owner_dealloc(self); // (waits for the stage: nothing reads the inputs after it)
+    for (PyObject *cap : inputs) dlpack_release(cap);
+}
+
 // RowScores and RowOffsets: their one part as list[int]
 uint64_t rs_part_len(const OwnerObject *o, int, int *) { return acx_scores_rows(handle<acx_scores_t>(o)); }
 uint64_t ro_part_len(const OwnerObject *o, int, int *) { return acx_rows_count(handle<acx_rows_t>(o)) + 1; }
@@ -1362,6 +1404,21 @@ ResultType RESULT_TYPES[RT_COUNT] = {
        "are haystack h's", part(ACX_SNIP_ROW_OFFSETS)},
       DEVICE_ATTR("parts are"),
       {"nbytes", size_get<acx_snippets_t, acx_snippets_nbytes>, nullptr, "the size of data", nullptr}}},
+    {"ahocorasick_rs.TokenLabels", sizeof(TokenLabelsObject), owner_ops<acx_token_labels_t, acx_token_labels_on_device, labels_part, acx_free_token_labels>(),
+     tl_part_len, size_len<acx_token_labels_t, acx_token_labels_count>, tl_tolist,
+     "the labels as list[tuple[int, int]] of (pattern, begin), or one such list per row for a sequence of haystacks (copies "
+     "device columns to the host)",
+     "The result of label_tokens / label_tokens_batch: one entry per token.  .pattern is an int64 Column -- the pattern of the "
+     "first match (in the search's order) that touches the token, or -1 -- and .begin a uint8 Column -- 1 where a match's "
+     "tokens begin, the B of BIO -- where the search ran (.device); len(self) is the number of tokens.  pattern >= 0 is the "
+     "token mask.  Every accessor of a column waits for the stage's last kernel first.",
+     {{"pattern", owner_get_part, nullptr, "Column of len(self) int64 entries: the owner's pattern, or -1", part(TL_PATTERN)},
+      {"begin", owner_get_part, nullptr, "Column of len(self) uint8 entries: 1 iff the token is the first of its owner's", part(TL_BEGIN)},
+      {"row_offsets", tl_get_row_offsets, nullptr,
+       "None for one haystack and for a tensor; for a sequence of haystacks a list of len(haystacks) + 1 ints: tokens "
+       "row_offsets[h] .. row_offsets[h + 1] - 1 are haystack h's", nullptr},
+      DEVICE_ATTR("columns are")},
+     tl_dealloc},
 };
 #undef DEVICE_ATTR
 
@@ -1441,6 +1498,39 @@ struct BatchInput {
     ~BatchInput() { dlpack_release(cap); dlpack_release(cap_off); }
 };
 
+// The tensor argument `name` that goes with a haystack tensor (offsets=, token_offsets): a 1-D contiguous int64 __dlpack__
+// tensor where the haystack tensor lies (on_device: in HBM on want_device, else in host memory).  *cap: its capsule, the
+// caller's to release (set as soon as it exists); *words / *entries: what it holds.  Sets the exception.
+bool int64_tensor(PyObject *o, const char *name, bool on_device, int want_device, PyObject **cap, const uint64_t **words, uint64_t *entries) {
+    if (!PyObject_HasAttrString(o, "__dlpack__")) {
+        PyErr_Format(PyExc_TypeError, "argument '%s': '%.100s' object has no __dlpack__", name, Py_TYPE(o)->tp_name);
+        return false;
+    }
+    *cap = PyObject_CallMethod(o, "__dlpack__", nullptr);
+    if (!*cap) return false;
+    DLManagedTensorC *mt = PyCapsule_IsValid(*cap, "dltensor")
+                               ? static_cast<DLManagedTensorC *>(PyCapsule_GetPointer(*cap, "dltensor")) : nullptr;
+    if (!mt) {
+        PyErr_SetString(PyExc_TypeError, "__dlpack__ did not return a 'dltensor' capsule");
+        return false;
+    }
+    const DLTensorC &t = mt->dl_tensor;
+    if (t.ndim != 1 || t.dtype.code != 0 || t.dtype.bits != 64 || t.dtype.lanes != 1 ||
+        (t.strides && t.shape[0] > 1 && t.strides[0] != 1)) {
+        PyErr_Format(PyExc_TypeError, "%s must be a 1-D contiguous int64 tensor", name);
+        return false;
+    }
+    const bool dev = t.device.device_type == kDLROCM || t.device.device_type == kDLCUDA;
+    const bool host = t.device.device_type == kDLCPU || t.device.device_type == kDLROCMHost || t.device.device_type == kDLCUDAHost;
+    if ((!dev && !host) || dev != on_device || (dev && t.device.device_id != want_device)) {
+        PyErr_Format(PyExc_ValueError, "the %s tensor lies on another device than the haystack tensor", name);
+        return false;
+    }
+    *words = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(t.data) + t.byte_offset);
+    *entries = (uint64_t)t.shape[0];
+    return true;
+}
+
 bool batch_input(PyObject *hay, PyObject *offsets, PyObject *row_length, bool utf8, int want_device, BatchInput *in) {
     if (offsets == Py_None) offsets = nullptr;
     if (row_length == Py_None) row_length = nullptr;
@@ -1476,36 +1566,13 @@ bool batch_input(PyObject *hay, PyObject *offsets, PyObject *row_length, bool ut
         in->rows = in->len / (uint64_t)rl;
         return true;
     }
-    if (!PyObject_HasAttrString(offsets, "__dlpack__")) {
-        PyErr_Format(PyExc_TypeError, "argument 'offsets': '%.100s' object has no __dlpack__", Py_TYPE(offsets)->tp_name);
-        return false;
-    }
-    in->cap_off = PyObject_CallMethod(offsets, "__dlpack__", nullptr);
-    if (!in->cap_off) return false;
-    DLManagedTensorC *mt = PyCapsule_IsValid(in->cap_off, "dltensor")
-                               ? static_cast<DLManagedTensorC *>(PyCapsule_GetPointer(in->cap_off, "dltensor")) : nullptr;
-    if (!mt) {
-        PyErr_SetString(PyExc_TypeError, "__dlpack__ did not return a 'dltensor' capsule");
-        return false;
-    }
-    const DLTensorC &t = mt->dl_tensor;
-    if (t.ndim != 1 || t.dtype.code != 0 || t.dtype.bits != 64 || t.dtype.lanes != 1 ||
-        (t.strides && t.shape[0] > 1 && t.strides[0] != 1)) {
-        PyErr_SetString(PyExc_TypeError, "offsets must be a 1-D contiguous int64 tensor");
-        return false;
-    }
-    const bool dev = t.device.device_type == kDLROCM || t.device.device_type == kDLCUDA;
-    const bool host = t.device.device_type == kDLCPU || t.device.device_type == kDLROCMHost || t.device.device_type == kDLCUDAHost;
-    if ((!dev && !host) || dev != in->on_device || (dev && t.device.device_id != want_device)) {
-        PyErr_SetString(PyExc_ValueError, "the offsets tensor lies on another device than the haystack tensor");
-        return false;
-    }
-    if (t.shape[0] < 1) {
+    uint64_t entries = 0;
+    if (!int64_tensor(offsets, "offsets", in->on_device, want_device, &in->cap_off, &in->t_off, &entries)) return false;
+    if (entries < 1) {
         PyErr_SetString(PyExc_ValueError, "offsets needs rows + 1 entries: at least one");
         return false;
     }
-    in->t_off = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(t.data) + t.byte_offset);
-    in->rows = (uint64_t)t.shape[0] - 1;
+    in->rows = entries - 1;
     if (!in->on_device) { // (device offsets: their ends are checked behind the producer's kernels, by the caller)
         const int64_t *o = reinterpret_cast<const int64_t *>(in->t_off);
         bool ok = o[0] == 0 && (uint64_t)o[in->rows] == in->len;
@@ -2154,6 +2221,181 @@ template <int mode> PyObject *whole_words(PyObject *self, PyObject *args, PyObje
 }
 
 // ---------------------------------------------------------------------------
+// a search's matches mapped onto token boundaries: label_tokens / label_tokens_batch -> TokenLabels (acx_tokens /
+// acx_tokens_device).  A TokenLabels owns the acx_token_labels_t; .pattern and .begin are Columns with the lifetime chain of a
+// MatchColumns' columns.  Tokens are a PARTITION here -- T + 1 boundaries, ts = tok, te = tok + 1; a (starts, ends) pair for
+// tokenizers whose tokens leave gaps is the same C ABI with two arrays and is not bound yet.
+// ---------------------------------------------------------------------------
+// the characters of UTF-8 bytes: a byte that continues none begins one
+uint64_t count_characters(const uint8_t *p, uint64_t n) {
+    uint64_t k = 0;
+    for (uint64_t i = 0; i < n; i++) k += (p[i] & 0xC0) != 0x80;
+    return k;
+}
+
+// One haystack's LOCAL token boundaries: a sequence of ints or a 1-D contiguous int64 buffer of k + 1 entries that do not
+// decrease and lie within 0 .. limit (the haystack's length in the unit at hand).  Sets the exception.
+bool parse_boundaries(PyObject *o, uint64_t limit, std::vector<int64_t> *out) {
+    out->clear();
+    if (PyObject_CheckBuffer(o)) {
+        Py_buffer view;
+        if (PyObject_GetBuffer(o, &view, PyBUF_FULL_RO) < 0) return false;
+        const char *fmt = view.format;
+        if (fmt && (*fmt == '@' || *fmt == '=' || *fmt == '<')) fmt++;
+        const bool ok = view.ndim == 1 && view.itemsize == 8 && fmt && (fmt[0] == 'q' || fmt[0] == 'l') && fmt[1] == 0 &&
+                        PyBuffer_IsContiguous(&view, 'C');
+        if (ok) out->assign(static_cast<const int64_t *>(view.buf), static_cast<const int64_t *>(view.buf) + view.len / 8);
+        PyBuffer_Release(&view);
+        if (!ok) {
+            PyErr_SetString(PyExc_TypeError, "token_offsets: a buffer must be 1-D contiguous int64");
+            return false;
+        }
+    } else {
+        PyObject *seq = PySequence_Fast(o, "token_offsets must be a sequence of ints or an int64 buffer");
+        if (!seq) return false;
+        const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
+        out->reserve((size_t)n);
+        for (Py_ssize_t i = 0; i < n; i++) {
+            long long v;
+            if (!parse_int(PySequence_Fast_GET_ITEM(seq, i), "token_offsets", &v)) { Py_DECREF(seq); return false; }
+            out->push_back((int64_t)v);
+        }
+        Py_DECREF(seq);
+    }
+    if (out->empty()) {
+        PyErr_SetString(PyExc_ValueError, "token_offsets needs tokens + 1 entries: at least one");
+        return false;
+    }
+    bool ok = (*out)[0] >= 0 && (uint64_t)out->back() <= limit;
+    for (size_t i = 0; ok && i + 1 < out->size(); i++) ok = (*out)[i] <= (*out)[i + 1];
+    if (!ok) PyErr_SetString(PyExc_ValueError, "token_offsets must not decrease and must lie within 0 .. len(haystack)");
+    return ok;
+}
+
+// local boundaries -> the tokens' global starts and ends, `base` positions into the data
+void append_tokens(const std::vector<int64_t> &local, uint64_t base, std::vector<int64_t> *ts, std::vector<int64_t> *te) {
+    for (size_t j = 0; j + 1 < local.size(); j++) {
+        ts->push_back((int64_t)base + local[j]);
+        te->push_back((int64_t)base + local[j + 1]);
+    }
+}
+
+// The token_offsets tensor that goes with a haystack tensor: T + 1 boundaries where the haystack lies.
+struct TokenTensor {
+    PyObject *cap = nullptr;
+    const int64_t *tok = nullptr;
+    uint64_t T = 0;
+    TokenTensor() = default;
+    TokenTensor(const TokenTensor &) = delete;
+    TokenTensor &operator=(const TokenTensor &) = delete;
+    ~TokenTensor() { dlpack_release(cap); }
+};
+bool token_tensor(PyObject *o, bool on_device, int want_device, TokenTensor *t) {
+    const uint64_t *words = nullptr;
+    uint64_t entries = 0;
+    if (!int64_tensor(o, "token_offsets", on_device, want_device, &t->cap, &words, &entries)) return false;
+    if (entries < 1) {
+        PyErr_SetString(PyExc_ValueError, "token_offsets needs tokens + 1 entries: at least one");
+        return false;
+    }
+    t->tok = reinterpret_cast<const int64_t *>(words);
+    t->T = entries - 1;
+    return true;
+}
+
+// label_tokens / label_tokens_batch.  A tensor: global byte boundaries, tokens may cross rows.  A str, a buffer or a sequence
+// of them: boundaries local to every haystack -- characters for the str class, the unit of find_matches_as_indexes and of a
+// tokenizer's offset_mapping (the search reports code points and the library measures the rows in characters), else bytes.
+template <bool batch> PyObject *label_tokens(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
+    static const char *kw_s[] = {"haystack", "token_offsets", "overlapping", nullptr};
+    static const char *kw_b[] = {"haystacks", "token_offsets", "overlapping", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *tok_o = nullptr, *ov = nullptr, *offsets = nullptr, *row_length = nullptr;
+    int overlapping = 0;
+    if (batch ? !PyArg_ParseTupleAndKeywords(args, kwargs, "OO|O$OO:label_tokens_batch", const_cast<char **>(kw_b), &hay, &tok_o, &ov,
+                                             &offsets, &row_length)
+              : !PyArg_ParseTupleAndKeywords(args, kwargs, "OO|O:label_tokens", const_cast<char **>(kw_s), &hay, &tok_o, &ov))
+        return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    const int device = acx_automaton_device(a);
+    acx_token_labels_t *l = nullptr;
+    std::vector<int64_t> ts, te, local;
+    std::unique_ptr<std::vector<int64_t>> ro;
+    PyObject *inputs[3] = {nullptr, nullptr, nullptr}; // what a stage in flight still reads (TokenLabelsObject)
+    auto keep = [&](PyObject **cap, int k) { inputs[k] = *cap; *cap = nullptr; };
+    int rc;
+    if (batch) {
+        BatchInput in;
+        if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
+        if (in.tensor) {
+            TokenTensor t;
+            if (!token_tensor(tok_o, in.on_device, device, &t)) return nullptr;
+            rc = batch_dispatch(
+                device, in,
+                [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+                    return acx_tokens(a, p, len, off, rows, overlapping, 0, t.tok, t.tok + 1, t.T, &l);
+                },
+                [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_len) {
+                    return acx_tokens_device(a, p, len, d_off, rows, row_len, overlapping, t.tok, t.tok + 1, t.T, &l);
+                });
+            if (rc == BAD_OFFSETS) return nullptr;
+            if (rc == ACX_OK && in.on_device) { keep(&in.cap, 0); keep(&in.cap_off, 1); keep(&t.cap, 2); }
+        } else {
+            PyObject *seq = PySequence_Fast(tok_o, "token_offsets must be a sequence with one entry per haystack");
+            if (!seq) return nullptr;
+            if ((uint64_t)PySequence_Fast_GET_SIZE(seq) != in.rows) {
+                Py_DECREF(seq);
+                PyErr_SetString(PyExc_ValueError, "token_offsets needs one entry per haystack");
+                return nullptr;
+            }
+            const int codepoints = (utf8 && !in.seq.all_ascii) ? 1 : 0;
+            ro.reset(new std::vector<int64_t>((size_t)in.rows + 1, 0));
+            uint64_t base = 0;
+            for (uint64_t h = 0; h < in.rows; h++) {
+                const uint64_t b = in.seq.off[(size_t)h], e = in.seq.off[(size_t)h + 1];
+                const uint64_t units = codepoints ? count_characters(in.seq.blob.data() + b, e - b) : e - b;
+                if (!parse_boundaries(PySequence_Fast_GET_ITEM(seq, (Py_ssize_t)h), units, &local)) { Py_DECREF(seq); return nullptr; }
+                append_tokens(local, base, &ts, &te);
+                (*ro)[(size_t)h + 1] = (int64_t)ts.size();
+                base += units;
+            }
+            Py_DECREF(seq);
+            rc = nogil([&] {
+                return acx_tokens(a, in.seq.blob.data(), in.seq.off[(size_t)in.rows], in.seq.off.data(), in.rows, overlapping, codepoints,
+                                  ts.data(), te.data(), (uint64_t)ts.size(), &l);
+            });
+        }
+    } else {
+        HaystackView v;
+        if (!haystack_view(hay, utf8, true, device, &v)) return nullptr;
+        if (v.cap) {
+            TokenTensor t;
+            if (!token_tensor(tok_o, v.on_device, device, &t)) return nullptr;
+            rc = single_dispatch(
+                device, v,
+                [&](const uint8_t *p, uint64_t len) { return acx_tokens(a, p, len, nullptr, 1, overlapping, 0, t.tok, t.tok + 1, t.T, &l); },
+                [&](const uint8_t *p, uint64_t len) { return acx_tokens_device(a, p, len, nullptr, 0, 0, overlapping, t.tok, t.tok + 1, t.T, &l); });
+            if (rc == ACX_OK && v.on_device) { keep(&v.cap, 0); keep(&t.cap, 2); }
+        } else {
+            const int codepoints = (utf8 && !v.is_ascii) ? 1 : 0;
+            if (!parse_boundaries(tok_o, codepoints ? count_characters(v.p, v.len) : v.len, &local)) return nullptr;
+            append_tokens(local, 0, &ts, &te);
+            rc = nogil([&] { return acx_tokens(a, v.p, v.len, nullptr, 1, overlapping, codepoints, ts.data(), te.data(), (uint64_t)ts.size(), &l); });
+        }
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    OwnerObject *o = new_owner(RT_TOKEN_LABELS, l, device); // (it frees l when the object cannot be made: the stage is waited for)
+    if (!o) {
+        for (PyObject *cap : inputs) dlpack_release(cap);
+        return nullptr;
+    }
+    static_cast<TokenLabelsObject *>(o)->row_offsets = ro.release();
+    for (int k = 0; k < 3; k++) static_cast<TokenLabelsObject *>(o)->inputs[k] = inputs[k];
+    return reinterpret_cast<PyObject *>(o);
+}
+
+// ---------------------------------------------------------------------------
 // split_rows(data, delimiter=b"\n") -> RowOffsets (acx_split_rows / acx_split_rows_device): a delimited buffer cut into rows.
 // A module function -- no automaton is involved.  A RowOffsets owns the acx_rows_t; .offsets is a Column with the lifetime
 // chain of a MatchColumns' columns, and what the _batch methods take as offsets=.
@@ -2356,6 +2598,27 @@ const PyMethodDef SHARED_METHODS[] = {
      "row_offsets[h] .. row_offsets[h + 1] - 1 are row h's; a snippet never crosses a row.  haystacks: a sequence, or ONE 1-D "
      "contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for cover_spans_batch.  A tensor on "
      "the automaton's device is searched and cut there and every part stays there."},
+    {"label_tokens", KW(label_tokens<false>),
+     "label_tokens(haystack, token_offsets, overlapping=False) -> TokenLabels\n\n[extension] the matches that "
+     "find_matches_as_indexes(haystack, overlapping) reports, mapped onto tokens: token t is haystack[token_offsets[t]:"
+     "token_offsets[t + 1]], and a match touches it iff token_offsets[t] < end and token_offsets[t + 1] > start (an empty "
+     "token strictly inside a match is touched, one on its edge is not).  .pattern[t] is the pattern of the FIRST touching "
+     "match in the search's order, or -1; .begin[t] is 1 where that match's tokens begin (the B of BIO).  token_offsets: "
+     "k + 1 boundaries that do not decrease, within 0 .. len(haystack) -- a sequence of ints or an int64 buffer; "
+     "AhoCorasick: CHARACTER indexes, the unit of find_matches_as_indexes and of a tokenizer's offset_mapping; "
+     "BytesAhoCorasick: byte offsets, and with a __dlpack__ tensor on the automaton's device as haystack, token_offsets is a "
+     "1-D int64 __dlpack__ tensor there and the search and the labels stay in HBM."},
+    {"label_tokens_batch", KW(label_tokens<true>),
+     "label_tokens_batch(haystacks, token_offsets, overlapping=False, *, offsets=None, row_length=None) -> TokenLabels\n\n"
+     "[extension] label_tokens over a batch in one call.  haystacks a sequence: token_offsets has one entry per haystack, "
+     "each that haystack's local boundaries (characters for AhoCorasick, else bytes); a token never crosses a haystack, "
+     ".row_offsets cuts the tokens by haystack and tolist() gives one list per haystack.  haystacks ONE 1-D contiguous uint8 "
+     "__dlpack__ tensor cut by exactly one of offsets and row_length, as for mask_all_batch: token_offsets is ONE 1-D "
+     "contiguous int64 __dlpack__ tensor of T + 1 GLOBAL byte boundaries on the same device, tokens may cross rows, and on "
+     "the automaton's device everything stays in HBM.  There the boundaries are the caller's word, as offsets are: arrays "
+     "that do not rise give wrong labels, never a write outside the T entries.  The call returns with the labels still being "
+     "made: the TokenLabels keeps the three input tensors alive until it goes, and they must not be written before an accessor "
+     "of a column has returned."},
     {"find_whole_words_as_columns", KW(whole_words<0>),
      "find_whole_words_as_columns(haystack, overlapping=False, *, matchkind=MatchKind.LeftmostLongest, word_bytes=None) -> "
      "MatchColumns\n\n[extension] grep -w for the object's patterns: of all their occurrences those whose neighbour bytes "

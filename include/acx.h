@@ -51,6 +51,9 @@ extern "C" {
  *     acx_free_snippets);
  *     tenth addendum (additive as well): whole-word matching -- acx_words_host / acx_words_rows_device, acx_find_words /
  *     acx_find_words_device (an acx_columns_t), acx_filter_words / acx_filter_words_device (an acx_filtered_t);
+ *     eleventh addendum (additive as well): acx_tokens / acx_tokens_device / acx_tokens_host / acx_tokens_rows_device and the
+ *     acx_token_labels_t accessors (acx_token_labels_count, _on_device, _pattern, _begin, _copy_pattern, _copy_begin,
+ *     acx_free_token_labels);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -897,6 +900,63 @@ int acx_words_host(const uint8_t *hay, uint64_t len, const uint64_t *offsets /* 
 int acx_words_rows_device(const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
                           const acx_match_t *d_m, uint64_t n_m, const uint64_t *d_counts, int overlapping, int match_kind,
                           const uint8_t *word_set, acx_match_t *d_out_m, uint64_t *d_out_counts, uint64_t *n_out);
+
+/* ---- token labels: a search's matches mapped onto token boundaries -- a loss mask over tokens, weak-NER (BIO) labels, "which
+ * tokens does the block list touch" -- the step behind acx_mask ("after a byte-to-token map") and acx_spans.  It extends the
+ * match list of src/lib.rs:229-249 (str: character indexes, 73-88) and 423-435 (bytes) by the map a tokenizer's offset_mapping
+ * needs; the matches are those acx_find_batch / acx_find_device reports for the same match kind and `overlapping`.
+ * THE DEFINITION.  Tokens t = 0 .. T - 1 are given by two ascending arrays ts[t], te[t] with ts[t] <= te[t] <= ts[t + 1]:
+ * GLOBAL positions in the unit of the row offsets, counted from where the first row begins (a partition by T + 1 boundaries
+ * `tok` is ts = tok, te = tok + 1; tokens may leave gaps, cross rows and be empty).  A record of row h is clipped to its row
+ * first (end' = min(end, row length), start' = min(start, end')); its global range is [g_s, g_e) = [off[h] + start',
+ * off[h] + end'), and an empty one touches nothing.  A record TOUCHES token t iff ts[t] < g_e and te[t] > g_s: a zero-length
+ * token strictly inside a match is touched, one on a match's edge is not.  The OWNER of t is the touching record with the
+ * smallest index in the find's order.  pattern[t] (int64) = the owner's pattern, or -1; begin[t] (uint8) = 1 iff t has an owner
+ * and (t == 0 or token t - 1 has another owner or none): the B of BIO; pattern >= 0 is the token mask.
+ * acx_tokens: host haystacks (offsets: n_hay + 1, or null: one haystack of len bytes) and host token arrays, a host result.
+ * acx_find / acx_find_batch runs as it is, then acx_tokens_host.  codepoints != 0: the search reports character indexes, the
+ * rows are measured in characters and so are the tokens (a tokenizer's offset_mapping over str rows).  Token arrays that do
+ * not rise or pass the data: ACX_EINVAL before any device work.
+ * acx_tokens_device: acx_find_device's pipeline (d_offsets / uniform_len as there; neither: one row; byte offsets), then the
+ * device stage on the same stream; d_ts / d_te: n_tokens int64 words each in HBM on the automaton's device, 8-byte aligned.
+ * The columns stay in HBM.  The call may return with the stage in flight: the accessors wait for it; d_hay, d_offsets, d_ts and
+ * d_te must stay valid until then.  The device form does NOT verify the token arrays -- they are the caller's word, as row
+ * offsets are: arrays that do not rise give wrong labels, never a store outside the n_tokens-entry columns.  A
+ * case-insensitive handle searches its folded copy; no byte is output.  An overlapping search on a non-Standard handle:
+ * ACX_EOVERLAP before any device state is touched.  ACX_ETOOBIG: 2^32 tokens or more, 2^41 records or more.
+ * An empty part still has a valid, non-null address. */
+typedef struct acx_token_labels acx_token_labels_t;
+int acx_tokens(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one haystack */,
+               uint64_t n_hay, int overlapping, int codepoints, const int64_t *ts, const int64_t *te, uint64_t n_tokens,
+               acx_token_labels_t **out);
+int acx_tokens_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                      uint64_t uniform_len, int overlapping, const int64_t *d_ts, const int64_t *d_te, uint64_t n_tokens,
+                      acx_token_labels_t **out);
+uint64_t acx_token_labels_count(const acx_token_labels_t *l); /* T: the tokens                                   */
+int acx_token_labels_on_device(const acx_token_labels_t *l);  /* 1: the columns are in HBM, 0: host memory       */
+/* host or device pointer by acx_token_labels_on_device (T int64 words; T bytes); waits for the device stage.  NULL: the wait
+ * failed.  Valid until acx_free_token_labels. */
+const int64_t *acx_token_labels_pattern(const acx_token_labels_t *l);
+const uint8_t *acx_token_labels_begin(const acx_token_labels_t *l);
+int acx_token_labels_copy_pattern(const acx_token_labels_t *l, int64_t *host_dst);
+int acx_token_labels_copy_begin(const acx_token_labels_t *l, uint8_t *host_dst);
+void acx_free_token_labels(acx_token_labels_t *l);
+/* the labels themselves, over a caller's records (both CLIP a record to its row, as acx_mask_host does).
+ * acx_tokens_host: host memory, no device needed, any unit -- the definition above inside the library; m: n_m matches, all rows
+ * behind one another, counts[h] of them row h's (ACX_EINVAL when they do not sum to n_m), or counts = NULL: one row holds them
+ * all; offsets: n_hay + 1 from 0 to len (ACX_EINVAL otherwise), or NULL: one row of len positions; ts, te: n_tokens words each
+ * -- ACX_EINVAL unless ts[t] <= te[t] <= ts[t + 1] and te[n_tokens - 1] <= len; pattern: n_tokens words, begin: n_tokens bytes.
+ * acx_tokens_rows_device: the device stage alone on a caller's offsets (or uniform_len, or neither: one row of len), records,
+ * counts (they must sum to n: checked before a kernel reads a record by them) and token arrays in HBM on one device; needs no
+ * automaton and reads no haystack; synchronous: both columns are complete when it returns.  It writes exactly n_tokens words
+ * at d_pattern and n_tokens bytes at d_begin.  The word arrays and d_pattern are 8-byte aligned, d_begin lies at any address.
+ * n = 0, n_hay = 0 or len = 0: the fills (pattern = -1, begin = 0) and nothing else; n_tokens = 0: nothing at all. */
+int acx_tokens_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts /* NULL: one row */, uint64_t n_hay,
+                    const uint64_t *offsets /* NULL: one row */, uint64_t len, const int64_t *ts, const int64_t *te,
+                    uint64_t n_tokens, int64_t *pattern, uint8_t *begin);
+int acx_tokens_rows_device(uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
+                           const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, const int64_t *d_ts,
+                           const int64_t *d_te, uint64_t n_tokens, int64_t *d_pattern, uint8_t *d_begin);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
