@@ -25,6 +25,7 @@ from .ahocorasick_rs import (
     MatchSpans,
     MatchSnippets,
     TokenLabels,
+    MatchesAt,
     RowOffsets,
     split_rows,
     ASCII_WORD_BYTES,
@@ -58,6 +59,8 @@ __all__ = [
     "MatchSnippets",
     # Extension: the result of label_tokens / label_tokens_batch
     "TokenLabels",
+    # Extension: the result of match_at / match_prefix_batch
+    "MatchesAt",
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",

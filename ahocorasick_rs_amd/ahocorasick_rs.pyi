@@ -148,6 +148,23 @@ class TokenLabels:
     def __len__(self) -> int: ...  # the number of tokens
     def tolist(self) -> Any: ...  # list[tuple[int, int]] of (pattern, begin), or one such list per haystack of a sequence
 
+# extension: the result of match_at / match_prefix_batch -- the crate's anchored search: which pattern begins exactly at
+# every anchor (a position, or the start of a row), where the walk ran.  The candidates of an anchor (p, L) are the patterns
+# P_i with haystack[p : p + len(P_i)] == P_i and p + len(P_i) <= L, L being the end of p's row; Standard reports the
+# shortest (then the lowest index), LeftmostFirst the lowest index, LeftmostLongest the longest; full=True keeps only
+# candidates that end at L
+class MatchesAt:
+    @property
+    def pattern(self) -> Column: ...  # int64: the pattern that begins at the anchor, or -1; overlapping: every such pattern
+    @property
+    def end(self) -> Column: ...  # int64: where it ends (match_prefix_batch: its length), or -1
+    @property
+    def row_offsets(self) -> Optional[Column]: ...  # overlapping=True: len(self) + 1 int64 entries that cut the entries by anchor; else None
+    @property
+    def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
+    def __len__(self) -> int: ...  # the number of anchors
+    def tolist(self) -> Any: ...  # list[tuple[int, int]] of (pattern, end), or -- overlapping -- one such list per anchor
+
 # extension: the result of split_rows -- the offsets that cut a delimited buffer into rows, where the data lies
 class RowOffsets:
     @property
@@ -297,6 +314,19 @@ class AhoCorasick:
         self, haystacks: Any, token_offsets: Any, overlapping: bool = False, *, offsets: Any = None,
         row_length: Optional[int] = None
     ) -> TokenLabels: ...
+    # extension: the anchored search -- for every position the pattern that begins exactly there, by the object's match kind,
+    # as (pattern, end) or (-1, -1); overlapping=True (Standard objects only, ValueError otherwise): every such pattern,
+    # ordered by end, then by index.  positions: a sequence of ints or an int64 buffer within 0 .. len(haystack), in
+    # CHARACTERS, any order, repeats allowed (ValueError outside); ends are character indexes too.  match_prefix_batch: the
+    # anchors are the starts of the rows -- a sequence of str -- and end is the length of the match; full=True: only a pattern
+    # that IS the row counts (a dictionary lookup: every kind then reports the lowest index).  No search runs
+    def match_at(
+        self, haystack: str, positions: Any, overlapping: bool = False, *, offsets: Any = None, row_length: Optional[int] = None
+    ) -> MatchesAt: ...
+    def match_prefix_batch(
+        self, haystacks: Any, overlapping: bool = False, *, full: bool = False, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> MatchesAt: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -420,4 +450,21 @@ class BytesAhoCorasick:
         self, haystacks: Any, token_offsets: Any, overlapping: bool = False, *, offsets: Any = None,
         row_length: Optional[int] = None
     ) -> TokenLabels: ...
+    # extension: the anchored search -- for every position the pattern that begins exactly there, by the object's match kind,
+    # as (pattern, end) or (-1, -1); overlapping=True (Standard objects only, ValueError otherwise): every such pattern,
+    # ordered by end, then by index.  haystack: one bytes-like with positions a sequence of ints or an int64 buffer within
+    # 0 .. len(haystack) (ValueError outside), or one uint8 __dlpack__ tensor with positions ONE 1-D contiguous int64
+    # __dlpack__ tensor on the same device; offsets / row_length (a tensor only) cut it into rows as mask_all_batch takes
+    # them, split_rows(t).offsets included: a match never crosses its position's row.  On the automaton's device everything
+    # stays in HBM, positions are the caller's word -- one outside the data gives (-1, -1) -- and the MatchesAt keeps the
+    # input tensors alive until it goes: they must not be written before an accessor of a column has returned.
+    # match_prefix_batch: the anchors are the starts of the rows (haystacks as filter_batch takes them), end is the length of
+    # the match; full=True: only a pattern that IS the row counts.  No search runs: a few bytes are read per anchor
+    def match_at(
+        self, haystack: Any, positions: Any, overlapping: bool = False, *, offsets: Any = None, row_length: Optional[int] = None
+    ) -> MatchesAt: ...
+    def match_prefix_batch(
+        self, haystacks: Any, overlapping: bool = False, *, full: bool = False, offsets: Any = None,
+        row_length: Optional[int] = None
+    ) -> MatchesAt: ...
     def _info(self) -> dict[str, Any]: ...

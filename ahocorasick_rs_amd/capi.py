@@ -36,6 +36,8 @@ FILTER_KEEP_MATCHED = 1  # acx_filter* flags (ACX_FILTER_KEEP_MATCHED); 0 keeps 
 SPAN_START, SPAN_END, SPAN_ROW_OFFSETS = 0, 1, 2  # acx_spans_data / acx_spans_copy (ACX_SPAN_*)
 SNIP_DATA, SNIP_OFFSETS, SNIP_PATTERN, SNIP_LEAD, SNIP_ROW_OFFSETS = 0, 1, 2, 3, 4  # acx_snippets_data / _copy (ACX_SNIP_*)
 SNIPPET_UTF8 = 1  # acx_snippets* flags (ACX_SNIPPET_UTF8): the ends move inward to a character boundary
+AT_OVERLAPPING, AT_FULL, AT_ROW_STARTS = 1, 2, 4  # acx_match_at* flags (ACX_AT_*)
+AT_PATTERN, AT_END, AT_ROW_OFFSETS = 0, 1, 2  # acx_at_copy (ACX_AT_PATTERN ..)
 MASK_ZERO = 1  # acx_mask* flags (ACX_MASK_ZERO): uncovered bytes become 0 instead of the haystack's own
 ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
@@ -113,7 +115,7 @@ _RESULTS = {
     "summary": (("total",), None), "columns": (("count", "rows"), True), "tally": (("nnz", "rows"), True),
     "filtered": (("rows", "bytes"), True), "scores": (("rows",), False), "masked": (("bytes", "rows"), False),
     "rows": (("count", "bytes"), None), "spans": (("count", "rows"), True), "snippets": (("count", "rows", "nbytes"), True),
-    "token_labels": (("count",), None),
+    "token_labels": (("count",), None), "at": (("count", "entries"), None),
 }
 # Everything else, one row each: name -> arguments, or (arguments, what it returns) where that is no status.  (acx_version is
 # declared by lib() itself, ahead of the version check.)
@@ -207,6 +209,15 @@ _SINGLES = {
     "acx_token_labels_copy_begin": [vp, vp],
     "acx_tokens_host": [vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, vp],
     "acx_tokens_rows_device": [u64, vp, u64, u64, vp, u64, vp, vp, vp, u64, vp, vp],
+    # (no _PAIRS row: positions and flags lie between the haystack and `out`, and the host form alone takes `codepoints`)
+    "acx_match_at": [vp, vp, u64, vp, u64, vp, u64, u32, i32, _out],
+    "acx_match_at_device": [vp, vp, u64, vp, u64, u64, vp, u64, u32, _out],
+    "acx_match_at_into_device": [vp, vp, u64, vp, u64, u64, vp, u64, u32, vp, vp],
+    "acx_match_at_host": [vp, vp, u64, vp, u64, vp, u64, u32, i32, vp, vp, vp],
+    "acx_at_pattern": ([vp], vp),
+    "acx_at_end": ([vp], vp),
+    "acx_at_row_offsets": ([vp], vp),
+    "acx_at_copy": [vp, i32, vp],
 }
 
 
@@ -944,6 +955,60 @@ def tokens_rows_device(nbytes: int, d_offsets: int, n_hay: int, uniform_len: int
                                         d_ts or None, d_te or None, n_tokens, d_pattern or None, d_begin or None))
 
 
+class DeviceMatchesAt(_Result):
+    """The result of Automaton.match_at / match_at_device (acx_at_t): per anchor the pattern that begins there and its end
+    (int64, -1: none) -- or, overlapping, every such pattern as a CSR over the anchors (row_offsets: anchors + 1 int64 words) --
+    in HBM (on_device) or in host memory.  pattern() / end() / row_offsets() copy them out; the _ptr() forms are where they lie
+    (all wait for the device stage; row_offsets: None / 0 unless the call was overlapping)."""
+    _PREFIX = "at"
+    count, entries = _Size("count"), _Size("entries")
+
+    def pattern_ptr(self) -> int:
+        return self._address("pattern")
+
+    def end_ptr(self) -> int:
+        return self._address("end")
+
+    def row_offsets_ptr(self) -> int:
+        return self._address("row_offsets")
+
+    def pattern(self) -> np.ndarray:
+        return self._copy_out("copy", self.entries, np.int64, AT_PATTERN)
+
+    def end(self) -> np.ndarray:
+        return self._copy_out("copy", self.entries, np.int64, AT_END)
+
+    def row_offsets(self) -> Optional[np.ndarray]:
+        return self._copy_out("copy", self.count + 1, np.int64, AT_ROW_OFFSETS) if self.row_offsets_ptr() else None
+
+
+def match_at_host(h: "HostAutomaton", hay, positions, *, offsets: Optional[Sequence[int]] = None, flags: int = 0,
+                  match_kind: int = MATCH_STANDARD):
+    """acx_match_at_host: the definition of the anchored search walked over a HostAutomaton's tables, no device involved.  hay:
+    bytes-like; positions: ints in 0 .. len(hay) (None with AT_ROW_STARTS); offsets: n + 1 from 0 to len(hay), or None (one
+    row).  Returns (pattern, end) with an entry per anchor, or -- AT_OVERLAPPING -- (pattern, end, row_offsets).  ValueError
+    (code EINVAL) for offsets that do not rise from 0 to len(hay), a position outside the data, AT_FULL without
+    AT_ROW_STARTS."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(hay), dtype=np.uint8))
+    off = _u64(offsets)
+    pos = None if positions is None else _i64(positions)
+    n_hay = 0 if off is None else len(off) - 1
+    n_pos = 0 if pos is None else len(pos)
+    anchors = (n_hay if off is not None else 1) if flags & AT_ROW_STARTS else n_pos
+    args = (h._h, a.ctypes.data if a.size else None, a.size, None if off is None else off.ctypes.data, n_hay,
+            None if pos is None else pos.ctypes.data, n_pos, flags, match_kind)
+    if not flags & AT_OVERLAPPING:
+        pattern, end = np.zeros(anchors + 1, dtype=np.int64), np.zeros(anchors + 1, dtype=np.int64)
+        _check(lib().acx_match_at_host(*args, pattern.ctypes.data, end.ctypes.data, None))
+        return pattern[:anchors], end[:anchors]
+    ro = np.zeros(anchors + 1, dtype=np.int64)
+    _check(lib().acx_match_at_host(*args, None, None, ro.ctypes.data))  # (count only)
+    n = int(ro[anchors])
+    pattern, end = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+    _check(lib().acx_match_at_host(*args, pattern.ctypes.data, end.ctypes.data, ro.ctypes.data))
+    return pattern[:n], end[:n], ro
+
+
 class DeviceRows(_Result):
     """The result of split_rows / split_rows_device (acx_rows_t): the offsets that cut nbytes of delimited data into rows --
     rows + 1 int64 words from 0 to nbytes, in HBM (on_device, on `device`) or in host memory.  `rows` is valid at once;
@@ -1539,6 +1604,32 @@ class Automaton(_Handle):
         """the batch in HBM searched and its matches mapped onto the tokens there; the columns stay there"""
         return self._device("tokens", (d_ptr, nbytes, d_offsets, n_hay, uniform_len),
                             (int(overlapping), d_ts or None, d_te or None, n_tokens), DeviceTokenLabels)
+
+    # ---- the anchored search: which pattern begins exactly here (acx_match_at*)
+    def match_at(self, haystacks: Optional[Sequence[bytes]], positions, flags: int = 0, codepoints: bool = False, *,
+                 single: Optional[bytes] = None) -> DeviceMatchesAt:
+        """host data -- a sequence of rows, or single=...: one haystack that is no batch (offsets = NULL) -- and host positions
+        (global, in bytes or, with codepoints, characters; None with AT_ROW_STARTS), a host result"""
+        pos = None if positions is None else _i64(positions)
+        hay = _host_arg(haystacks, single, _SINGLE_OWN)
+        out = ctypes.c_void_p()
+        _check(lib().acx_match_at(self._h, *hay[:4], None if pos is None else pos.ctypes.data, 0 if pos is None else len(pos),
+                                  flags, int(codepoints), ctypes.byref(out)))
+        return DeviceMatchesAt(out.value)
+
+    def match_at_device(self, d_ptr: int, nbytes: int, d_positions: int, n_pos: int, flags: int = 0, *, d_offsets: int = 0,
+                        n_hay: int = 0, uniform_len: int = 0) -> DeviceMatchesAt:
+        """everything in HBM; the columns stay there"""
+        out = ctypes.c_void_p()
+        _check(lib().acx_match_at_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len,
+                                         d_positions or None, n_pos, flags, ctypes.byref(out)))
+        return DeviceMatchesAt(out.value)
+
+    def match_at_into_device(self, d_ptr: int, nbytes: int, d_positions: int, n_pos: int, d_pattern: int, d_end: int,
+                             flags: int = 0, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0) -> None:
+        """the raw form: an int64 word per anchor at d_pattern and at d_end, complete when it returns"""
+        _check(lib().acx_match_at_into_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len,
+                                              d_positions or None, n_pos, flags, d_pattern or None, d_end or None))
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

@@ -4,10 +4,6 @@
 
 using namespace acxh;
 
-struct acx_host_automaton {
-    acx::Automaton host;
-};
-
 namespace {
 
 template <typename T>
@@ -356,6 +352,7 @@ int acx_compile_host_ex(const uint8_t *blob, const uint64_t *offsets, uint64_t n
     if (!h) return fail(ACX_ENOMEM, "out of memory");
     const int rc = compile_patterns(blob, offsets, n_patterns, match_kind, flags, 0, h->host);
     if (rc != ACX_OK) { delete h; return rc; }
+    h->flags = flags;
     *out = h;
     return ACX_OK;
 }

@@ -882,6 +882,11 @@ struct TokenLabelsObject : OwnerObject {
     // flight and its kernels read all three on the library's stream: the tensors stay the producer's until the result goes
     PyObject *inputs[3];
 };
+struct MatchesAtObject : OwnerObject {
+    // the device route: the capsules of the haystack, its offsets and the positions.  The call returns with the walk in
+    // flight and its kernels read all three on the library's stream: the tensors stay the producer's until the result goes
+    PyObject *inputs[3];
+};
 enum { MR_OFFSETS = 0, MR_DATA = 1 };
 struct MaskedRowsObject : OwnerObject {
     bool utf8;                 // made by the str class
@@ -922,7 +927,7 @@ struct ResultType {
     PyTypeObject *type; // made by PyInit
     PyMethodDef methods[2];
 };
-enum { RT_MATCH_COLUMNS, RT_PATTERN_COUNTS, RT_FILTERED_ROWS, RT_ROW_SCORES, RT_MASKED_ROWS, RT_ROW_OFFSETS, RT_MATCH_SPANS, RT_MATCH_SNIPPETS, RT_TOKEN_LABELS, RT_COUNT };
+enum { RT_MATCH_COLUMNS, RT_PATTERN_COUNTS, RT_FILTERED_ROWS, RT_ROW_SCORES, RT_MASKED_ROWS, RT_ROW_OFFSETS, RT_MATCH_SPANS, RT_MATCH_SNIPPETS, RT_TOKEN_LABELS, RT_MATCHES_AT, RT_COUNT };
 extern ResultType RESULT_TYPES[RT_COUNT];
 
 OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
@@ -1289,6 +1294,39 @@ void tl_dealloc(PyObject *self) {
     for (PyObject *cap : inputs) dlpack_release(cap);
 }
 
+// MatchesAt: list[tuple[int, int]] of (pattern, end) per anchor, or -- overlapping -- one such list per anchor
+const void *at_part(const acx_at_t *r, int which) {
+    return which == ACX_AT_PATTERN ? acx_at_pattern(r) : which == ACX_AT_END ? acx_at_end(r) : acx_at_row_offsets(r);
+}
+uint64_t at_part_len(const OwnerObject *o, int which, int *) {
+    const acx_at_t *r = handle<acx_at_t>(o);
+    if (which != ACX_AT_ROW_OFFSETS) return acx_at_entries(r);
+    return acx_at_row_offsets(r) ? acx_at_count(r) + 1 : NO_PART;
+}
+PyObject *at_tolist(PyObject *self, PyObject *) {
+    const acx_at_t *r = handle<acx_at_t>(self);
+    const uint64_t n = acx_at_entries(r), anchors = acx_at_count(r);
+    std::vector<int64_t> pattern((size_t)n + 1), end((size_t)n + 1), ro;
+    bool csr = false;
+    const int rc = nogil([&] {
+        csr = acx_at_row_offsets(r) != nullptr; // (waits for the walk)
+        if (csr) ro.assign((size_t)anchors + 1, 0);
+        int rc = acx_at_copy(r, ACX_AT_PATTERN, pattern.data());
+        if (rc == ACX_OK) rc = acx_at_copy(r, ACX_AT_END, end.data());
+        if (rc == ACX_OK && csr) rc = acx_at_copy(r, ACX_AT_ROW_OFFSETS, ro.data());
+        return rc;
+    });
+    if (rc != ACX_OK) return raise_acx(rc);
+    return rows_of(csr ? &ro : nullptr, n,
+                   [&](uint64_t i) { return Py_BuildValue("(LL)", (long long)pattern[(size_t)i], (long long)end[(size_t)i]); });
+}
+void at_dealloc(PyObject *self) {
+    MatchesAtObject *o = static_cast<MatchesAtObject *>(owner_of(self));
+    PyObject *inputs[3] = {o->inputs[0], o->inputs[1], o->inputs[2]};
+    owner_dealloc(self); // (waits for the walk: nothing reads the inputs after it)
+    for (PyObject *cap : inputs) dlpack_release(cap);
+}
+
 // RowScores and RowOffsets: their one part as list[int]
 uint64_t rs_part_len(const OwnerObject *o, int, int *) { return acx_scores_rows(handle<acx_scores_t>(o)); }
 uint64_t ro_part_len(const OwnerObject *o, int, int *) { return acx_rows_count(handle<acx_rows_t>(o)) + 1; }
@@ -1419,6 +1457,21 @@ ResultType RESULT_TYPES[RT_COUNT] = {
        "row_offsets[h] .. row_offsets[h + 1] - 1 are haystack h's", nullptr},
       DEVICE_ATTR("columns are")},
      tl_dealloc},
+    {"ahocorasick_rs.MatchesAt", sizeof(MatchesAtObject), owner_ops<acx_at_t, acx_at_on_device, at_part, acx_free_at>(),
+     at_part_len, size_len<acx_at_t, acx_at_count>, at_tolist,
+     "the result as list[tuple[int, int]] of (pattern, end), one per anchor, or -- overlapping -- one such list per anchor "
+     "(copies device columns to the host)",
+     "The result of match_at / match_prefix_batch: which pattern begins exactly at every anchor -- a position, or the start of "
+     "a row.  .pattern and .end are int64 Columns where the walk ran (.device): one entry per anchor, (-1, -1) where no pattern "
+     "begins; overlapping: every such pattern, ordered by end, then by pattern, and .row_offsets cuts the entries by anchor.  "
+     "len(self) is the number of anchors.  Every accessor of a column waits for the walk's last kernel first.",
+     {{"pattern", owner_get_part, nullptr, "Column of int64 entries: the pattern that begins at the anchor, or -1", part(ACX_AT_PATTERN)},
+      {"end", owner_get_part, nullptr, "Column of int64 entries: where that pattern ends (match_prefix_batch: its length), or -1", part(ACX_AT_END)},
+      {"row_offsets", owner_get_part, nullptr,
+       "None unless overlapping; else a Column of len(self) + 1 int64 entries: entries row_offsets[k] .. row_offsets[k + 1] - 1 "
+       "are anchor k's", part(ACX_AT_ROW_OFFSETS)},
+      DEVICE_ATTR("columns are")},
+     at_dealloc},
 };
 #undef DEVICE_ATTR
 
@@ -2396,6 +2449,157 @@ template <bool batch> PyObject *label_tokens(PyObject *self, PyObject *args, PyO
 }
 
 // ---------------------------------------------------------------------------
+// the anchored search: match_at / match_prefix_batch -> MatchesAt (acx_match_at / acx_match_at_device).  No find runs.  A
+// MatchesAt owns the acx_at_t; .pattern, .end and .row_offsets are Columns with the lifetime chain of a MatchColumns' columns.
+// ---------------------------------------------------------------------------
+// The positions of match_at on host data: a sequence of ints or a 1-D contiguous int64 buffer.  Their range is the C ABI's
+// to check (ValueError: it knows the unit).  Sets the exception.
+bool parse_positions(PyObject *o, std::vector<int64_t> *out) {
+    out->clear();
+    if (PyObject_CheckBuffer(o)) {
+        Py_buffer view;
+        if (PyObject_GetBuffer(o, &view, PyBUF_FULL_RO) < 0) return false;
+        const char *fmt = view.format;
+        if (fmt && (*fmt == '@' || *fmt == '=' || *fmt == '<')) fmt++;
+        const bool ok = view.ndim == 1 && view.itemsize == 8 && fmt && (fmt[0] == 'q' || fmt[0] == 'l') && fmt[1] == 0 &&
+                        PyBuffer_IsContiguous(&view, 'C');
+        if (ok) out->assign(static_cast<const int64_t *>(view.buf), static_cast<const int64_t *>(view.buf) + view.len / 8);
+        PyBuffer_Release(&view);
+        if (!ok) PyErr_SetString(PyExc_TypeError, "positions: a buffer must be 1-D contiguous int64");
+        return ok;
+    }
+    if (PyUnicode_Check(o)) {
+        PyErr_SetString(PyExc_TypeError, "positions must be a sequence of ints or an int64 buffer");
+        return false;
+    }
+    PyObject *seq = PySequence_Fast(o, "positions must be a sequence of ints or an int64 buffer");
+    if (!seq) return false;
+    const Py_ssize_t n = PySequence_Fast_GET_SIZE(seq);
+    out->reserve((size_t)n);
+    for (Py_ssize_t i = 0; i < n; i++) {
+        long long v;
+        int overflow = 0;
+        if (!parse_int(PySequence_Fast_GET_ITEM(seq, i), "positions", &v, &overflow)) { Py_DECREF(seq); return false; }
+        if (overflow) {
+            Py_DECREF(seq);
+            PyErr_SetString(PyExc_ValueError, "positions must lie within 0 .. len(haystack)");
+            return false;
+        }
+        out->push_back((int64_t)v);
+    }
+    Py_DECREF(seq);
+    return true;
+}
+
+// the MatchesAt around r; inputs: what a walk in flight still reads (released here when the object cannot be made)
+PyObject *new_matches_at(acx_at_t *r, int device, PyObject *(&inputs)[3]) {
+    OwnerObject *o = new_owner(RT_MATCHES_AT, r, device); // (it frees r when the object cannot be made: the walk is waited for)
+    if (!o) {
+        for (PyObject *cap : inputs) dlpack_release(cap);
+        return nullptr;
+    }
+    for (int k = 0; k < 3; k++) static_cast<MatchesAtObject *>(o)->inputs[k] = inputs[k];
+    return reinterpret_cast<PyObject *>(o);
+}
+
+// match_at(haystack, positions, overlapping=False, *, offsets=None, row_length=None).  A str or a buffer: positions on the
+// host, in characters for the str class (ends as well).  A tensor: ONE int64 tensor of byte positions where it lies, and
+// offsets / row_length cut it into rows as mask_all_batch takes them; in HBM everything stays there.
+PyObject *match_at(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
+    static const char *kw[] = {"haystack", "positions", "overlapping", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *pos_o = nullptr, *ov = nullptr, *offsets = nullptr, *row_length = nullptr;
+    int overlapping = 0;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "OO|O$OO:match_at", const_cast<char **>(kw), &hay, &pos_o, &ov, &offsets, &row_length))
+        return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    if (offsets == Py_None) offsets = nullptr;
+    if (row_length == Py_None) row_length = nullptr;
+    const uint32_t flags = overlapping ? ACX_AT_OVERLAPPING : 0u;
+    const int device = acx_automaton_device(a);
+    acx_at_t *r = nullptr;
+    PyObject *inputs[3] = {nullptr, nullptr, nullptr};
+    auto keep = [&](PyObject **cap, int k) { inputs[k] = *cap; *cap = nullptr; };
+    const uint64_t *words = nullptr;
+    uint64_t n_pos = 0;
+    PyObject *cap_pos = nullptr;
+    int rc;
+    if (offsets || row_length) { // ONE tensor cut into rows
+        BatchInput in;
+        if (utf8 || !batch_input(hay, offsets, row_length, utf8, device, &in)) {
+            if (utf8) PyErr_SetString(PyExc_TypeError, "offsets / row_length cut ONE __dlpack__ tensor into rows: a str takes neither");
+            return nullptr;
+        }
+        if (!int64_tensor(pos_o, "positions", in.on_device, device, &cap_pos, &words, &n_pos)) { dlpack_release(cap_pos); return nullptr; }
+        const int64_t *pos = reinterpret_cast<const int64_t *>(words);
+        rc = batch_dispatch(
+            device, in,
+            [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+                return acx_match_at(a, p, len, off, rows, pos, n_pos, flags, 0, &r);
+            },
+            [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_len) {
+                return acx_match_at_device(a, p, len, d_off, rows, row_len, pos, n_pos, flags, &r);
+            });
+        if (rc == ACX_OK && in.on_device) { keep(&in.cap, 0); keep(&in.cap_off, 1); keep(&cap_pos, 2); }
+        dlpack_release(cap_pos);
+        if (rc == BAD_OFFSETS) return nullptr;
+    } else {
+        HaystackView v;
+        if (!haystack_view(hay, utf8, true, device, &v)) return nullptr;
+        if (v.cap) {
+            if (!int64_tensor(pos_o, "positions", v.on_device, device, &cap_pos, &words, &n_pos)) { dlpack_release(cap_pos); return nullptr; }
+            const int64_t *pos = reinterpret_cast<const int64_t *>(words);
+            rc = single_dispatch(
+                device, v, [&](const uint8_t *p, uint64_t len) { return acx_match_at(a, p, len, nullptr, 1, pos, n_pos, flags, 0, &r); },
+                [&](const uint8_t *p, uint64_t len) { return acx_match_at_device(a, p, len, nullptr, 0, 0, pos, n_pos, flags, &r); });
+            if (rc == ACX_OK && v.on_device) { keep(&v.cap, 0); keep(&cap_pos, 2); }
+            dlpack_release(cap_pos);
+        } else {
+            std::vector<int64_t> pos;
+            if (!parse_positions(pos_o, &pos)) return nullptr;
+            const int codepoints = (utf8 && !v.is_ascii) ? 1 : 0;
+            rc = nogil([&] { return acx_match_at(a, v.p, v.len, nullptr, 1, pos.data(), (uint64_t)pos.size(), flags, codepoints, &r); });
+        }
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    return new_matches_at(r, device, inputs);
+}
+
+// match_prefix_batch(haystacks, overlapping=False, *, full=False, offsets=None, row_length=None): the anchors are the rows
+PyObject *match_prefix_batch(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool utf8 = utf8_of(self);
+    static const char *kw[] = {"haystacks", "overlapping", "full", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *ov = nullptr, *full_o = nullptr, *offsets = nullptr, *row_length = nullptr;
+    int overlapping = 0, full = 0;
+    if (!PyArg_ParseTupleAndKeywords(args, kwargs, "O|O$OOO:match_prefix_batch", const_cast<char **>(kw), &hay, &ov, &full_o, &offsets,
+                                     &row_length))
+        return nullptr;
+    if (ov && !parse_bool(ov, "overlapping", &overlapping)) return nullptr;
+    if (full_o && !parse_bool(full_o, "full", &full)) return nullptr;
+    const uint32_t flags = ACX_AT_ROW_STARTS | (overlapping ? ACX_AT_OVERLAPPING : 0u) | (full ? ACX_AT_FULL : 0u);
+    const int device = acx_automaton_device(a);
+    BatchInput in;
+    if (!batch_input(hay, offsets, row_length, utf8, device, &in)) return nullptr;
+    const int codepoints = (!in.tensor && utf8 && !in.seq.all_ascii) ? 1 : 0;
+    acx_at_t *r = nullptr;
+    const int rc = batch_dispatch(
+        device, in,
+        [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+            return acx_match_at(a, p, len, off, rows, nullptr, 0, flags, codepoints, &r);
+        },
+        [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_len) {
+            return acx_match_at_device(a, p, len, d_off, rows, row_len, nullptr, 0, flags, &r);
+        });
+    if (rc == BAD_OFFSETS) return nullptr;
+    if (rc != ACX_OK) return raise_acx(rc);
+    PyObject *inputs[3] = {nullptr, nullptr, nullptr};
+    if (in.on_device) { inputs[0] = in.cap; in.cap = nullptr; inputs[1] = in.cap_off; in.cap_off = nullptr; }
+    return new_matches_at(r, device, inputs);
+}
+
+// ---------------------------------------------------------------------------
 // split_rows(data, delimiter=b"\n") -> RowOffsets (acx_split_rows / acx_split_rows_device): a delimited buffer cut into rows.
 // A module function -- no automaton is involved.  A RowOffsets owns the acx_rows_t; .offsets is a Column with the lifetime
 // chain of a MatchColumns' columns, and what the _batch methods take as offsets=.
@@ -2619,6 +2823,26 @@ const PyMethodDef SHARED_METHODS[] = {
      "that do not rise give wrong labels, never a write outside the T entries.  The call returns with the labels still being "
      "made: the TokenLabels keeps the three input tensors alive until it goes, and they must not be written before an accessor "
      "of a column has returned."},
+    {"match_at", KW(match_at),
+     "match_at(haystack, positions, overlapping=False, *, offsets=None, row_length=None) -> MatchesAt\n\n[extension] the "
+     "crate's anchored search: for every position, the pattern that begins exactly there -- by the object's match kind: "
+     "Standard the shortest (then the lowest index), LeftmostFirst the lowest index (re.match of the alternation), "
+     "LeftmostLongest the longest -- as (pattern, end), or (-1, -1).  overlapping=True (Standard objects only): every such "
+     "pattern, ordered by end, then by index, with .row_offsets cutting them by position.  No search runs: a few bytes are "
+     "read per position.  positions: a sequence of ints or an int64 buffer within 0 .. len(haystack) (ValueError), any order, "
+     "repeats allowed; AhoCorasick: CHARACTER indexes in and out.  BytesAhoCorasick with a uint8 __dlpack__ tensor: positions "
+     "is ONE 1-D contiguous int64 __dlpack__ tensor of byte positions on the same device, and offsets / row_length cut the "
+     "tensor into rows as for mask_all_batch (split_rows(t).offsets included): a match never crosses its position's row.  On "
+     "the automaton's device everything stays in HBM; positions are then the caller's word -- one outside the data gives "
+     "(-1, -1) -- and the MatchesAt keeps the input tensors alive until it goes: they must not be written before an accessor "
+     "of a column has returned."},
+    {"match_prefix_batch", KW(match_prefix_batch),
+     "match_prefix_batch(haystacks, overlapping=False, *, full=False, offsets=None, row_length=None) -> MatchesAt\n\n"
+     "[extension] match_at at the start of every row, in one call: one (pattern, end) per row, end being the length of the "
+     "match (characters for AhoCorasick) -- prefix block lists, log levels, routing by key prefix.  full=True: only a pattern "
+     "that IS the row counts -- a dictionary lookup, strings to ids; every match kind then reports the lowest index.  "
+     "haystacks: a sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as "
+     "for filter_batch.  A tensor on the automaton's device stays in HBM, and so does the result."},
     {"find_whole_words_as_columns", KW(whole_words<0>),
      "find_whole_words_as_columns(haystack, overlapping=False, *, matchkind=MatchKind.LeftmostLongest, word_bytes=None) -> "
      "MatchColumns\n\n[extension] grep -w for the object's patterns: of all their occurrences those whose neighbour bytes "

@@ -276,6 +276,12 @@ struct Ctx {
 
 } // namespace acxh
 
+// the host compiler's output alone (acx_compile_host_ex): no device is involved
+struct ACX_HIDDEN acx_host_automaton {
+    acx::Automaton host;
+    uint32_t flags = 0; // ACX_BUILD_*: a case-insensitive one was compiled from the folded patterns
+};
+
 struct ACX_HIDDEN acx_automaton {
     acx::Automaton host;
     int device = 0;

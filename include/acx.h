@@ -54,6 +54,9 @@ extern "C" {
  *     eleventh addendum (additive as well): acx_tokens / acx_tokens_device / acx_tokens_host / acx_tokens_rows_device and the
  *     acx_token_labels_t accessors (acx_token_labels_count, _on_device, _pattern, _begin, _copy_pattern, _copy_begin,
  *     acx_free_token_labels);
+ *     twelfth addendum (additive as well): the anchored search -- acx_match_at / acx_match_at_device /
+ *     acx_match_at_into_device / acx_match_at_host and the acx_at_t accessors (acx_at_count, _entries, _on_device, _pattern,
+ *     _end, _row_offsets, _copy, acx_free_at);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -957,6 +960,72 @@ int acx_tokens_host(const acx_match_t *m, uint64_t n_m, const uint64_t *counts /
 int acx_tokens_rows_device(uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len,
                            const acx_match_t *d_records, uint64_t n, const uint64_t *d_counts, const int64_t *d_ts,
                            const int64_t *d_te, uint64_t n_tokens, int64_t *d_pattern, uint8_t *d_begin);
+
+/* ---- match at: "does a pattern begin exactly HERE" -- the crate's anchored search (Anchored::Yes, StartKind::Anchored), for
+ * a list of positions or for the start of every row: prefix classification of rows (block lists of URL schemes, log levels,
+ * routing by key prefix), whole-row dictionary lookup (the row IS a pattern: strings become ids without a hash table),
+ * dictionary entries that begin at a token start.  No find runs and no byte beyond the longest pattern is read per anchor.
+ * THE DEFINITION.  Patterns P_i; data h[0 .. len) (a case-insensitive handle compares every byte folded); anchors (p, L), a
+ * position and a limit with p <= L <= len.  The candidates of an anchor are C(p, L) = { (i, e) : e = p + len(P_i), e <= L,
+ * h[p .. e) == P_i }; p == L has none.  Not overlapping, by the handle's own match kind, one (pattern, end) per anchor or
+ * (-1, -1) when C is empty: Standard -- the smallest e, then the smallest i (the crate reports at the first match state);
+ * LeftmostFirst -- the smallest i (re.match of the alternation P_0|P_1|...); LeftmostLongest -- the largest e, then the
+ * smallest i.  ACX_AT_OVERLAPPING (Standard handles only, ACX_EOVERLAP otherwise, before any device state is touched): all
+ * of C, ordered by e ascending, then i ascending, as a CSR over the anchors -- anchor k's entries are row_offsets[k] ..
+ * row_offsets[k + 1] - 1.  ACX_AT_FULL (valid only with ACX_AT_ROW_STARTS, ACX_EINVAL otherwise): C is first restricted to
+ * e == L -- the row equals the pattern; every kind then reports the smallest i.
+ * ROWS.  One haystack: L = len.  Data cut by offsets, by uniform_len or by neither: the row of p is the LAST row r that
+ * begins at or before p and L is where row r + 1 begins (of several rows with one start all but the last are empty): a match
+ * never crosses a row, and `end` is a position in the data.  ACX_AT_ROW_STARTS: the anchors ARE the rows -- positions is NULL
+ * and ignored, there is one result per row, and `end` is local to the row: the length of the match.
+ * acx_match_at: host data (offsets: n_hay + 1 from 0 to len, or NULL: one haystack) and host positions, a host result.  The
+ * data and the positions are staged to the device, the same kernels run and the columns come back: there is no CPU matching
+ * route.  Before any device work: ACX_EINVAL for offsets that do not rise from 0 to len and for a position outside
+ * [0, units].  codepoints != 0: positions and ends are CHARACTER indexes of UTF-8 data (units: its characters; else: len).
+ * acx_match_at_device: everything in HBM on the automaton's device (d_offsets / uniform_len as for acx_find_device; neither:
+ * one row); d_positions: n_pos int64 words, 8-byte aligned.  It runs on the handle's context and stream and returns when the
+ * result's size is known; every accessor waits for the kernels, and d_hay, d_offsets and d_positions must stay valid until
+ * then.  Device positions are the caller's word, as offsets are: one outside [0, len] -- a negative one included -- gives
+ * (-1, -1) or no entry; nothing outside the data is read and nothing outside the outputs is written.  A case-insensitive
+ * handle folds the bytes it loads: no folded copy is made and the caller's memory is never written.  Positions need not be
+ * sorted and may repeat.  ACX_ETOOBIG: 2^32 anchors or more.
+ * acx_match_at_into_device: the raw form, not overlapping -- the two columns go to the caller's d_pattern and d_end (an int64
+ * word per anchor each, 8-byte aligned, in HBM on the automaton's device); exactly that many words are written, and both
+ * columns are complete when it returns.
+ * acx_match_at_host: host memory only, no device -- the definition walked over the compiled tables (first_child, in_byte,
+ * own_off, own_pid of acx_host_tables), for match_kind's rule.  Not a matching path of the library: it documents the walk and
+ * checks that the tables mean what the kernels assume.  Not overlapping: pattern, end: an entry per anchor.  Overlapping:
+ * row_offsets (anchors + 1 words) is written, and -- unless both are NULL: count only -- pattern and end take
+ * row_offsets[anchors] entries.  ACX_EINVAL for offsets that do not rise from 0 to len and positions outside [0, len].
+ * An empty part still has a valid, non-null address. */
+#define ACX_AT_OVERLAPPING 1u
+#define ACX_AT_FULL 2u
+#define ACX_AT_ROW_STARTS 4u
+#define ACX_AT_PATTERN 0     /* acx_at_copy: the parts of a result */
+#define ACX_AT_END 1
+#define ACX_AT_ROW_OFFSETS 2
+typedef struct acx_at acx_at_t;
+int acx_match_at(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one haystack */,
+                 uint64_t n_hay, const int64_t *positions, uint64_t n_pos, uint32_t flags, int codepoints, acx_at_t **out);
+int acx_match_at_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                        uint64_t uniform_len, const int64_t *d_positions /* int64, 8-byte aligned; NULL with ACX_AT_ROW_STARTS */,
+                        uint64_t n_pos, uint32_t flags, acx_at_t **out);
+int acx_match_at_into_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                             uint64_t uniform_len, const int64_t *d_positions, uint64_t n_pos, uint32_t flags,
+                             int64_t *d_pattern, int64_t *d_end);
+int acx_match_at_host(const acx_host_automaton_t *h, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one row */,
+                      uint64_t n_hay, const int64_t *positions, uint64_t n_pos, uint32_t flags, int match_kind, int64_t *pattern,
+                      int64_t *end, int64_t *row_offsets);
+uint64_t acx_at_count(const acx_at_t *r);   /* the anchors                                         */
+uint64_t acx_at_entries(const acx_at_t *r); /* the entries of the two columns (not overlapping: the anchors) */
+int acx_at_on_device(const acx_at_t *r);    /* 1: the columns are in HBM, 0: host memory           */
+/* host or device pointer by acx_at_on_device (entries int64 words; anchors + 1 words, NULL unless the call was overlapping);
+ * waits for the device stage.  NULL: the wait failed.  Valid until acx_free_at. */
+const int64_t *acx_at_pattern(const acx_at_t *r);
+const int64_t *acx_at_end(const acx_at_t *r);
+const int64_t *acx_at_row_offsets(const acx_at_t *r);
+int acx_at_copy(const acx_at_t *r, int which /* ACX_AT_PATTERN .. */, void *host_dst);
+void acx_free_at(acx_at_t *r);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
