@@ -26,6 +26,7 @@ from .ahocorasick_rs import (
     MatchSnippets,
     TokenLabels,
     MatchesAt,
+    Segments,
     RowOffsets,
     split_rows,
     ASCII_WORD_BYTES,
@@ -61,6 +62,8 @@ __all__ = [
     "TokenLabels",
     # Extension: the result of match_at / match_prefix_batch
     "MatchesAt",
+    # Extension: the result of segment / segment_batch
+    "Segments",
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",

@@ -31,6 +31,7 @@ try:
         MatchSnippets,
         TokenLabels,
         MatchesAt,
+        Segments,
         RowOffsets,
         split_rows,
         ASCII_WORD_BYTES,
@@ -69,6 +70,8 @@ __all__ = [
     "TokenLabels",
     # Extension: the result of match_at / match_prefix_batch
     "MatchesAt",
+    # Extension: the result of segment / segment_batch
+    "Segments",
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",

@@ -165,6 +165,22 @@ class MatchesAt:
     def __len__(self) -> int: ...  # the number of anchors
     def tolist(self) -> Any: ...  # list[tuple[int, int]] of (pattern, end), or -- overlapping -- one such list per anchor
 
+# extension: the result of segment / segment_batch -- the data cut into dictionary entries from left to right, where the chain
+# ran: at every position the pattern the object's match kind prefers there (what match_at reports), going on where it ended;
+# where no pattern begins the piece is an unknown unit with pattern -1 -- one byte, or (utf8) one whole UTF-8 character.  The
+# pieces of a row tile it exactly
+class Segments:
+    @property
+    def pattern(self) -> Column: ...  # len(self) int64 entries: the pattern of the piece, or -1
+    @property
+    def offsets(self) -> Column: ...  # len(self) + 1 int64 GLOBAL ascending boundaries, the last one the data's length: label_tokens_batch's token_offsets
+    @property
+    def row_offsets(self) -> Optional[Column]: ...  # segment_batch: len(haystacks) + 1 int64 entries that cut the pieces by row; else None
+    @property
+    def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
+    def __len__(self) -> int: ...  # the number of pieces
+    def tolist(self) -> Any: ...  # list[tuple[int, int, int]] of (pattern, start, end) local to the row, or one such list per row
+
 # extension: the result of split_rows -- the offsets that cut a delimited buffer into rows, where the data lies
 class RowOffsets:
     @property
@@ -327,6 +343,14 @@ class AhoCorasick:
         self, haystacks: Any, overlapping: bool = False, *, full: bool = False, offsets: Any = None,
         row_length: Optional[int] = None
     ) -> MatchesAt: ...
+    # extension: greedy tokenization by the dictionary (MaxMatch for a LeftmostLongest object, re.finditer of P_0|P_1|...|.
+    # for a LeftmostFirst one): the pieces as (pattern, start, end) in CHARACTERS; an unknown piece (pattern -1) is one
+    # character.  utf8: None or True (False: ValueError -- a str is cut at characters; anything else: TypeError).  Patterns
+    # longer than 256 bytes: ValueError.  No search runs
+    def segment(self, haystack: str, *, utf8: Optional[bool] = None) -> Segments: ...
+    def segment_batch(
+        self, haystacks: Any, *, utf8: Optional[bool] = None, offsets: Any = None, row_length: Optional[int] = None
+    ) -> Segments: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -467,4 +491,14 @@ class BytesAhoCorasick:
         self, haystacks: Any, overlapping: bool = False, *, full: bool = False, offsets: Any = None,
         row_length: Optional[int] = None
     ) -> MatchesAt: ...
+    # extension: greedy tokenization by the dictionary (MaxMatch for a LeftmostLongest object, re.finditer of P_0|P_1|...|.
+    # for a LeftmostFirst one).  haystack: one bytes-like or one uint8 __dlpack__ tensor; segment_batch takes its haystacks as
+    # filter_batch does, split_rows(t).offsets included, and a piece never crosses a row.  utf8 (None: False): an unknown
+    # piece is one whole UTF-8 character instead of one byte; anything but a bool or None: TypeError.  Patterns longer than
+    # 256 bytes: ValueError.  On the automaton's device everything stays in HBM -- .offsets is what label_tokens_batch takes
+    # as token_offsets -- and the Segments keeps the input tensors alive until it goes.  No search runs
+    def segment(self, haystack: Any, *, utf8: Optional[bool] = None) -> Segments: ...
+    def segment_batch(
+        self, haystacks: Any, *, utf8: Optional[bool] = None, offsets: Any = None, row_length: Optional[int] = None
+    ) -> Segments: ...
     def _info(self) -> dict[str, Any]: ...

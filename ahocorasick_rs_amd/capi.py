@@ -38,6 +38,8 @@ SNIP_DATA, SNIP_OFFSETS, SNIP_PATTERN, SNIP_LEAD, SNIP_ROW_OFFSETS = 0, 1, 2, 3,
 SNIPPET_UTF8 = 1  # acx_snippets* flags (ACX_SNIPPET_UTF8): the ends move inward to a character boundary
 AT_OVERLAPPING, AT_FULL, AT_ROW_STARTS = 1, 2, 4  # acx_match_at* flags (ACX_AT_*)
 AT_PATTERN, AT_END, AT_ROW_OFFSETS = 0, 1, 2  # acx_at_copy (ACX_AT_PATTERN ..)
+SEG_UTF8 = 1  # acx_segment* flags (ACX_SEG_UTF8): an unknown piece is a whole UTF-8 character
+SEG_PATTERN, SEG_OFFSETS, SEG_ROW_OFFSETS = 0, 1, 2  # acx_seg_copy (ACX_SEG_PATTERN ..)
 MASK_ZERO = 1  # acx_mask* flags (ACX_MASK_ZERO): uncovered bytes become 0 instead of the haystack's own
 ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
@@ -116,6 +118,7 @@ _RESULTS = {
     "filtered": (("rows", "bytes"), True), "scores": (("rows",), False), "masked": (("bytes", "rows"), False),
     "rows": (("count", "bytes"), None), "spans": (("count", "rows"), True), "snippets": (("count", "rows", "nbytes"), True),
     "token_labels": (("count",), None), "at": (("count", "entries"), None),
+    "seg": (("count", "rows"), None),
 }
 # Everything else, one row each: name -> arguments, or (arguments, what it returns) where that is no status.  (acx_version is
 # declared by lib() itself, ahead of the version check.)
@@ -218,6 +221,15 @@ _SINGLES = {
     "acx_at_end": ([vp], vp),
     "acx_at_row_offsets": ([vp], vp),
     "acx_at_copy": [vp, i32, vp],
+    # (no _PAIRS row: the host form alone takes `codepoints`)
+    "acx_segment": [vp, vp, u64, vp, u64, u32, i32, _out],
+    "acx_segment_device": [vp, vp, u64, vp, u64, u64, u32, _out],
+    "acx_segment_into_device": [vp, vp, u64, vp, u64, u64, u32, u64, vp, vp, vp, _u64p],
+    "acx_segment_host": [vp, vp, u64, vp, u64, u32, i32, u64, vp, vp, vp, _u64p],
+    "acx_seg_pattern": ([vp], vp),
+    "acx_seg_offsets": ([vp], vp),
+    "acx_seg_row_offsets": ([vp], vp),
+    "acx_seg_copy": [vp, i32, vp],
 }
 
 
@@ -1009,6 +1021,52 @@ def match_at_host(h: "HostAutomaton", hay, positions, *, offsets: Optional[Seque
     return pattern[:n], end[:n], ro
 
 
+class DeviceSegments(_Result):
+    """The result of Automaton.segment / segment_device (acx_seg_t): the pieces of a greedy segmentation by the dictionary --
+    pattern (count int64 words, -1: an unknown unit), offsets (count + 1 global boundaries, the last one the data's length)
+    and row_offsets (rows + 1: the pieces that begin before every row) -- in HBM (on_device) or in host memory.  pattern() /
+    offsets() / row_offsets() copy them out; the _ptr() forms are where they lie (all wait for the device stage)."""
+    _PREFIX = "seg"
+    count, rows = _Size("count"), _Size("rows")
+
+    def pattern_ptr(self) -> int:
+        return self._address("pattern")
+
+    def offsets_ptr(self) -> int:
+        return self._address("offsets")
+
+    def row_offsets_ptr(self) -> int:
+        return self._address("row_offsets")
+
+    def pattern(self) -> np.ndarray:
+        return self._copy_out("copy", self.count, np.int64, SEG_PATTERN)
+
+    def offsets(self) -> np.ndarray:
+        return self._copy_out("copy", self.count + 1, np.int64, SEG_OFFSETS)
+
+    def row_offsets(self) -> np.ndarray:
+        return self._copy_out("copy", self.rows + 1, np.int64, SEG_ROW_OFFSETS)
+
+
+def segment_host(h: "HostAutomaton", hay, *, offsets: Optional[Sequence[int]] = None, flags: int = 0,
+                 match_kind: int = MATCH_STANDARD) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """acx_segment_host: the definition of the greedy segmentation walked over a HostAutomaton's tables, no device involved.
+    hay: bytes-like; offsets: n + 1 from 0 to len(hay), or None (one row); flags: SEG_UTF8.  Returns (pattern, offsets,
+    row_offsets): T, T + 1 and rows + 1 int64 words.  ValueError for an unknown flag or offsets that do not rise from 0 to
+    len(hay) (code EINVAL) and for a pattern longer than 256 bytes (code ETOOBIG)."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(hay), dtype=np.uint8))
+    off = _u64(offsets)
+    n_hay = 0 if off is None else len(off) - 1
+    rows = n_hay if off is not None else 1
+    args = (h._h, a.ctypes.data if a.size else None, a.size, None if off is None else off.ctypes.data, n_hay, flags, match_kind)
+    n = ctypes.c_uint64(0)
+    _check(lib().acx_segment_host(*args, 0, None, None, None, ctypes.byref(n)))  # (count only)
+    t = int(n.value)
+    pattern, bounds, ro = np.zeros(t + 1, dtype=np.int64), np.zeros(t + 1, dtype=np.int64), np.zeros(rows + 1, dtype=np.int64)
+    _check(lib().acx_segment_host(*args, t + 1, pattern.ctypes.data, bounds.ctypes.data, ro.ctypes.data, ctypes.byref(n)))
+    return pattern[:t], bounds, ro
+
+
 class DeviceRows(_Result):
     """The result of split_rows / split_rows_device (acx_rows_t): the offsets that cut nbytes of delimited data into rows --
     rows + 1 int64 words from 0 to nbytes, in HBM (on_device, on `device`) or in host memory.  `rows` is valid at once;
@@ -1630,6 +1688,33 @@ class Automaton(_Handle):
         """the raw form: an int64 word per anchor at d_pattern and at d_end, complete when it returns"""
         _check(lib().acx_match_at_into_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len,
                                               d_positions or None, n_pos, flags, d_pattern or None, d_end or None))
+
+    # ---- greedy segmentation by the dictionary: MaxMatch on the device (acx_segment*)
+    def segment(self, haystacks: Optional[Sequence[bytes]], flags: int = 0, codepoints: bool = False, *,
+                single: Optional[bytes] = None) -> DeviceSegments:
+        """host data -- a sequence of rows, or single=...: one haystack that is no batch (offsets = NULL) -- a host result;
+        codepoints: the boundaries in characters (implies SEG_UTF8)"""
+        hay = _host_arg(haystacks, single, _SINGLE_OWN)
+        out = ctypes.c_void_p()
+        _check(lib().acx_segment(self._h, *hay[:4], flags, int(codepoints), ctypes.byref(out)))
+        return DeviceSegments(out.value)
+
+    def segment_device(self, d_ptr: int, nbytes: int, flags: int = 0, *, d_offsets: int = 0, n_hay: int = 0,
+                       uniform_len: int = 0) -> DeviceSegments:
+        """everything in HBM; the columns stay there"""
+        out = ctypes.c_void_p()
+        _check(lib().acx_segment_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, flags,
+                                        ctypes.byref(out)))
+        return DeviceSegments(out.value)
+
+    def segment_into_device(self, d_ptr: int, nbytes: int, cap: int, d_pattern: int, d_offsets_out: int, d_row_offsets: int,
+                            flags: int = 0, *, d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0) -> int:
+        """the raw form: T is returned; cap, cap + 1 and rows + 1 int64 words at the three addresses are written only when
+        T <= cap, and are complete when it returns"""
+        n = ctypes.c_uint64(0)
+        _check(lib().acx_segment_into_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, flags, cap,
+                                             d_pattern or None, d_offsets_out or None, d_row_offsets or None, ctypes.byref(n)))
+        return int(n.value)
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,
                  stream_offset: int = 0) -> None:

@@ -11,36 +11,15 @@
 #include <algorithm>
 
 #include "at.hpp"
-#include "fold.hpp"
+#include "at_walk.hpp"
 
 namespace acx {
 
 constexpr uint32_t AT_IPT = AT_TILE / AT_THREADS; // anchors of one thread in phases A and C
-constexpr uint32_t AT_NONE = 0xFFFFFFFFu;         // no pattern (OWN1_NONE, automaton.hpp, has the same value)
-constexpr uint32_t AT_MANY = 0xFFFFFFFEu;         // own1: several patterns end here (OWN1_MANY, automaton.hpp)
 constexpr int AT_MODE_WALK = 0, AT_MODE_COUNT = 1, AT_MODE_EMIT = 2;
 static_assert(AT_IPT * AT_THREADS == AT_TILE && AT_THREADS % 64 == 0, "whole waves, whole tiles");
 static_assert(AT_THREADS >= 256, "root_next is copied to LDS by the first 256 threads");
 static_assert(AT_TILE <= 65536, "a slot of the survivor list is 16 bits wide");
-
-// the child of s that byte b leads to, or 0
-__device__ inline uint32_t at_child(const AtTrie &T, uint32_t s, uint32_t b) {
-    uint32_t lo = T.first_child[s];
-    const uint32_t end = T.first_child[s + 1];
-    if (end - lo <= AT_PROBE) {
-        for (; lo < end; lo++) {
-            const uint32_t x = T.in_byte[lo];
-            if (x >= b) return x == b ? lo : 0u;
-        }
-        return 0u;
-    }
-    uint32_t hi = end;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (T.in_byte[mid] < b) lo = mid + 1; else hi = mid;
-    }
-    return lo < end && T.in_byte[lo] == b ? lo : 0u;
-}
 
 // where the row of position p < R.len ends, never past R.len (the offsets are the caller's word: the row index is clamped
 // into [0, R.n) before an offset is read; R.n > 0)
@@ -115,44 +94,27 @@ __global__ __launch_bounds__(AT_THREADS) void k_at(const AtTrie T, const uint8_t
         const uint32_t slot = s_list[j];
         const uint64_t p = s_pos[slot];
         const uint32_t lim = s_lim[slot];
-        uint32_t s = s_res[slot], d = 1;
+        const uint32_t s = s_res[slot];
         uint32_t best = AT_NONE, best_len = 0, cnt = 0;
         uint64_t w = 0, w_end = 0;
         if (MODE == AT_MODE_EMIT) {
             w = (uint64_t)base[tile + slot];
             w_end = (uint64_t)base[tile + slot + 1];
         }
-        for (;;) {
-            if ((T.sflags[s] & 1) && (!full || d == lim)) { // a pattern ends here (FULL: and the row does)
-                if (MODE == AT_MODE_WALK) {
-                    uint32_t pid = T.own1[s];
-                    if (pid == AT_MANY) pid = T.own_pid[T.own_off[s]];
-                    if (kind == ACX_MATCH_LEFTMOST_FIRST && !full) {
-                        if (pid < best) { best = pid; best_len = d; }
-                    } else {
-                        best = pid;
-                        best_len = d;
-                        if (kind == ACX_MATCH_STANDARD || full) break; // the first match state; FULL: the only depth
-                    }
-                } else {
-                    const uint32_t o0 = T.own_off[s], o1 = T.own_off[s + 1];
-                    if (MODE == AT_MODE_COUNT) {
-                        cnt += o1 - o0;
-                    } else {
-                        for (uint32_t o = o0; o < o1 && w < w_end; o++, w++) {
-                            pattern[w] = (int64_t)T.own_pid[o];
-                            end[w] = (int64_t)(row_starts ? (uint64_t)d : p + d);
-                        }
-                    }
+        at_path(T, hay, p, lim, s, fold, [&](uint32_t q, uint32_t d) { // a pattern ends at state q
+            if (full && d != lim) return true;                         // (FULL: and the row does)
+            if (MODE == AT_MODE_WALK) return at_pick(T, q, d, kind, full, best, best_len);
+            const uint32_t o0 = T.own_off[q], o1 = T.own_off[q + 1];
+            if (MODE == AT_MODE_COUNT) {
+                cnt += o1 - o0;
+            } else {
+                for (uint32_t o = o0; o < o1 && w < w_end; o++, w++) {
+                    pattern[w] = (int64_t)T.own_pid[o];
+                    end[w] = (int64_t)(row_starts ? (uint64_t)d : p + d);
                 }
             }
-            if (d >= lim) break;
-            const uint8_t b = hay[p + d]; // (p + d < p + lim <= L)
-            const uint32_t c = at_child(T, s, fold ? fold_byte(b) : b);
-            if (!c) break;
-            s = c;
-            d++;
-        }
+            return true;
+        });
         if (MODE == AT_MODE_WALK) {
             s_res[slot] = best;
             s_lim[slot] = best_len;

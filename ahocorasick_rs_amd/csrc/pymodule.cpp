@@ -887,6 +887,12 @@ struct MatchesAtObject : OwnerObject {
     // flight and its kernels read all three on the library's stream: the tensors stay the producer's until the result goes
     PyObject *inputs[3];
 };
+struct SegmentsObject : OwnerObject {
+    bool batch; // segment_batch: .row_offsets is a Column and tolist() gives one list per row
+    // the device route: the capsules of the haystack and its offsets.  The call returns with the emitting kernels in flight
+    // and they read both on the library's stream: the tensors stay the producer's until the result goes
+    PyObject *inputs[3];
+};
 enum { MR_OFFSETS = 0, MR_DATA = 1 };
 struct MaskedRowsObject : OwnerObject {
     bool utf8;                 // made by the str class
@@ -927,7 +933,7 @@ struct ResultType {
     PyTypeObject *type; // made by PyInit
     PyMethodDef methods[2];
 };
-enum { RT_MATCH_COLUMNS, RT_PATTERN_COUNTS, RT_FILTERED_ROWS, RT_ROW_SCORES, RT_MASKED_ROWS, RT_ROW_OFFSETS, RT_MATCH_SPANS, RT_MATCH_SNIPPETS, RT_TOKEN_LABELS, RT_MATCHES_AT, RT_COUNT };
+enum { RT_MATCH_COLUMNS, RT_PATTERN_COUNTS, RT_FILTERED_ROWS, RT_ROW_SCORES, RT_MASKED_ROWS, RT_ROW_OFFSETS, RT_MATCH_SPANS, RT_MATCH_SNIPPETS, RT_TOKEN_LABELS, RT_MATCHES_AT, RT_SEGMENTS, RT_COUNT };
 extern ResultType RESULT_TYPES[RT_COUNT];
 
 OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
@@ -1327,6 +1333,43 @@ void at_dealloc(PyObject *self) {
     for (PyObject *cap : inputs) dlpack_release(cap);
 }
 
+// Segments: list[tuple[int, int, int]] of (pattern, start, end) local to the row, or -- a batch -- one such list per row
+const void *seg_part(const acx_seg_t *r, int which) {
+    return which == ACX_SEG_PATTERN ? acx_seg_pattern(r) : which == ACX_SEG_OFFSETS ? acx_seg_offsets(r) : acx_seg_row_offsets(r);
+}
+uint64_t seg_part_len(const OwnerObject *o, int which, int *) {
+    const acx_seg_t *r = handle<acx_seg_t>(o);
+    if (which == ACX_SEG_PATTERN) return acx_seg_count(r);
+    if (which == ACX_SEG_OFFSETS) return acx_seg_count(r) + 1;
+    return static_cast<const SegmentsObject *>(o)->batch ? acx_seg_rows(r) + 1 : NO_PART;
+}
+PyObject *seg_tolist(PyObject *self, PyObject *) {
+    const acx_seg_t *r = handle<acx_seg_t>(self);
+    const uint64_t n = acx_seg_count(r), rows = acx_seg_rows(r);
+    std::vector<int64_t> pattern((size_t)n + 1), off((size_t)n + 1), ro((size_t)rows + 1);
+    const int rc = nogil([&] {
+        int rc = acx_seg_copy(r, ACX_SEG_PATTERN, pattern.data());
+        if (rc == ACX_OK) rc = acx_seg_copy(r, ACX_SEG_OFFSETS, off.data());
+        if (rc == ACX_OK) rc = acx_seg_copy(r, ACX_SEG_ROW_OFFSETS, ro.data());
+        return rc;
+    });
+    if (rc != ACX_OK) return raise_acx(rc);
+    // (a row's first piece begins where the row does: the pieces tile it)
+    uint64_t row = 0;
+    return rows_of(static_cast<SegmentsObject *>(owner_of(self))->batch ? &ro : nullptr, n, [&](uint64_t i) {
+        while (row + 1 < rows && (uint64_t)ro[(size_t)row + 1] <= i) row++;
+        while (row > 0 && (uint64_t)ro[(size_t)row] > i) row--;
+        const int64_t b = off[(size_t)ro[(size_t)row]];
+        return Py_BuildValue("(LLL)", (long long)pattern[(size_t)i], (long long)(off[(size_t)i] - b), (long long)(off[(size_t)i + 1] - b));
+    });
+}
+void seg_dealloc(PyObject *self) {
+    SegmentsObject *o = static_cast<SegmentsObject *>(owner_of(self));
+    PyObject *inputs[3] = {o->inputs[0], o->inputs[1], o->inputs[2]};
+    owner_dealloc(self); // (waits for the kernels: nothing reads the inputs after it)
+    for (PyObject *cap : inputs) dlpack_release(cap);
+}
+
 // RowScores and RowOffsets: their one part as list[int]
 uint64_t rs_part_len(const OwnerObject *o, int, int *) { return acx_scores_rows(handle<acx_scores_t>(o)); }
 uint64_t ro_part_len(const OwnerObject *o, int, int *) { return acx_rows_count(handle<acx_rows_t>(o)) + 1; }
@@ -1472,6 +1515,23 @@ ResultType RESULT_TYPES[RT_COUNT] = {
        "are anchor k's", part(ACX_AT_ROW_OFFSETS)},
       DEVICE_ATTR("columns are")},
      at_dealloc},
+    {"ahocorasick_rs.Segments", sizeof(SegmentsObject), owner_ops<acx_seg_t, acx_seg_on_device, seg_part, acx_free_seg>(),
+     seg_part_len, size_len<acx_seg_t, acx_seg_count>, seg_tolist,
+     "the pieces as list[tuple[int, int, int]] of (pattern, start, end) local to their row, or -- segment_batch -- one such "
+     "list per row (copies device columns to the host)",
+     "The result of segment / segment_batch: the data cut into dictionary entries from left to right.  .pattern is an int64 "
+     "Column of len(self) entries -- the pattern of every piece, or -1 for an unknown unit -- and .offsets an int64 Column of "
+     "len(self) + 1 GLOBAL ascending boundaries that ends at the data's length: what label_tokens_batch takes as "
+     "token_offsets.  .row_offsets (segment_batch) cuts the pieces by row.  All lie where the chain ran (.device).  Every "
+     "accessor of a column waits for the stage's last kernel first.",
+     {{"pattern", owner_get_part, nullptr, "Column of len(self) int64 entries: the pattern of the piece, or -1", part(ACX_SEG_PATTERN)},
+      {"offsets", owner_get_part, nullptr,
+       "Column of len(self) + 1 int64 entries: piece i is data[offsets[i]:offsets[i + 1]] (characters for a str)", part(ACX_SEG_OFFSETS)},
+      {"row_offsets", owner_get_part, nullptr,
+       "None for one haystack; for a batch a Column of len(haystacks) + 1 int64 entries: pieces row_offsets[h] .. "
+       "row_offsets[h + 1] - 1 are haystack h's", part(ACX_SEG_ROW_OFFSETS)},
+      DEVICE_ATTR("columns are")},
+     seg_dealloc},
 };
 #undef DEVICE_ATTR
 
@@ -2600,6 +2660,72 @@ PyObject *match_prefix_batch(PyObject *self, PyObject *args, PyObject *kwargs) {
 }
 
 // ---------------------------------------------------------------------------
+// greedy segmentation by the dictionary: segment / segment_batch -> Segments (acx_segment / acx_segment_device).  No find
+// runs.  A Segments owns the acx_seg_t; its parts are Columns with the lifetime chain of a MatchColumns' columns.
+// ---------------------------------------------------------------------------
+// segment(haystack, *, utf8=None) / segment_batch(haystacks, *, utf8=None, offsets=None, row_length=None).  utf8: an unknown
+// piece is a whole character (None: True for the str class, False for the bytes class).  A str is cut at characters and its
+// boundaries are CHARACTER indexes; a tensor on the automaton's device stays in HBM end to end.
+template <bool batch> PyObject *segment(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool str_class = utf8_of(self);
+    static const char *kw_s[] = {"haystack", "utf8", nullptr};
+    static const char *kw_b[] = {"haystacks", "utf8", "offsets", "row_length", nullptr};
+    PyObject *hay = nullptr, *utf8_o = nullptr, *offsets = nullptr, *row_length = nullptr;
+    if (batch ? !PyArg_ParseTupleAndKeywords(args, kwargs, "O|$OOO:segment_batch", const_cast<char **>(kw_b), &hay, &utf8_o, &offsets,
+                                             &row_length)
+              : !PyArg_ParseTupleAndKeywords(args, kwargs, "O|$O:segment", const_cast<char **>(kw_s), &hay, &utf8_o))
+        return nullptr;
+    int utf8 = str_class;
+    if (utf8_o && utf8_o != Py_None && !parse_bool(utf8_o, "utf8", &utf8)) return nullptr;
+    if (str_class && !utf8) {
+        PyErr_SetString(PyExc_ValueError, "a str is cut at characters: utf8=False needs a BytesAhoCorasick");
+        return nullptr;
+    }
+    const uint32_t flags = utf8 ? ACX_SEG_UTF8 : 0u;
+    const int device = acx_automaton_device(a);
+    acx_seg_t *r = nullptr;
+    PyObject *inputs[3] = {nullptr, nullptr, nullptr};
+    int rc;
+    if (batch) {
+        BatchInput in;
+        if (!batch_input(hay, offsets, row_length, str_class, device, &in)) return nullptr;
+        const int codepoints = (!in.tensor && str_class && !in.seq.all_ascii) ? 1 : 0;
+        rc = batch_dispatch(
+            device, in,
+            [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+                return acx_segment(a, p, len, off, rows, flags, codepoints, &r);
+            },
+            [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_len) {
+                return acx_segment_device(a, p, len, d_off, rows, row_len, flags, &r);
+            });
+        if (rc == BAD_OFFSETS) return nullptr;
+        if (rc == ACX_OK && in.on_device) { inputs[0] = in.cap; in.cap = nullptr; inputs[1] = in.cap_off; in.cap_off = nullptr; }
+    } else {
+        HaystackView v;
+        if (!haystack_view(hay, str_class, true, device, &v)) return nullptr;
+        if (v.cap && capsule_tensor(v.cap).ndim != 1) {
+            PyErr_SetString(PyExc_TypeError, "Only one-dimensional sequences are supported");
+            return nullptr;
+        }
+        const int codepoints = (str_class && !v.is_ascii) ? 1 : 0;
+        rc = single_dispatch(
+            device, v, [&](const uint8_t *p, uint64_t len) { return acx_segment(a, p, len, nullptr, 1, flags, codepoints, &r); },
+            [&](const uint8_t *p, uint64_t len) { return acx_segment_device(a, p, len, nullptr, 0, 0, flags, &r); });
+        if (rc == ACX_OK && v.on_device) { inputs[0] = v.cap; v.cap = nullptr; }
+    }
+    if (rc != ACX_OK) return raise_acx(rc);
+    OwnerObject *o = new_owner(RT_SEGMENTS, r, device); // (it frees r when the object cannot be made: the stage is waited for)
+    if (!o) {
+        for (PyObject *cap : inputs) dlpack_release(cap);
+        return nullptr;
+    }
+    static_cast<SegmentsObject *>(o)->batch = batch;
+    for (int k = 0; k < 3; k++) static_cast<SegmentsObject *>(o)->inputs[k] = inputs[k];
+    return reinterpret_cast<PyObject *>(o);
+}
+
+// ---------------------------------------------------------------------------
 // split_rows(data, delimiter=b"\n") -> RowOffsets (acx_split_rows / acx_split_rows_device): a delimited buffer cut into rows.
 // A module function -- no automaton is involved.  A RowOffsets owns the acx_rows_t; .offsets is a Column with the lifetime
 // chain of a MatchColumns' columns, and what the _batch methods take as offsets=.
@@ -2843,6 +2969,24 @@ const PyMethodDef SHARED_METHODS[] = {
      "that IS the row counts -- a dictionary lookup, strings to ids; every match kind then reports the lowest index.  "
      "haystacks: a sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as "
      "for filter_batch.  A tensor on the automaton's device stays in HBM, and so does the result."},
+    {"segment", KW(segment<false>),
+     "segment(haystack, *, utf8=None) -> Segments\n\n[extension] greedy tokenization by the dictionary: the haystack cut into "
+     "the object's patterns from left to right -- at every position the pattern the object's match kind prefers there (what "
+     "match_at reports: LeftmostLongest the longest, which makes this MaxMatch, WordPiece's inner loop and forward maximum "
+     "matching; LeftmostFirst the lowest index, re.finditer of P_0|P_1|...|.; Standard the shortest), going on where it ended.  "
+     "Where no pattern begins the piece is an unknown unit with pattern -1: one byte, or with utf8=True one whole UTF-8 "
+     "character (an ill-formed one: its lead byte and the continuation bytes that follow).  utf8=None: True for AhoCorasick, "
+     "False for BytesAhoCorasick; anything but a bool or None: TypeError.  The pieces tile the haystack.  No search runs, and "
+     "patterns longer than 256 bytes are refused (ValueError).  AhoCorasick: boundaries are CHARACTER indexes.  "
+     "BytesAhoCorasick with a uint8 __dlpack__ tensor on the automaton's device: everything stays in HBM, and the Segments keeps "
+     "the tensor alive until it goes: it must not be written before an accessor of a column has returned."},
+    {"segment_batch", KW(segment<true>),
+     "segment_batch(haystacks, *, utf8=None, offsets=None, row_length=None) -> Segments\n\n[extension] segment for every row in "
+     "one call: a piece never crosses a row, .offsets holds the GLOBAL boundaries of all pieces -- exactly what "
+     "label_tokens_batch takes as token_offsets for a tensor -- and .row_offsets cuts the pieces by row.  haystacks: a "
+     "sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "
+     "filter_batch (split_rows(t).offsets included).  A tensor on the automaton's device stays in HBM, and so does the result: "
+     "split_rows -> segment_batch -> label_tokens_batch / filter_batch runs without anything leaving the device."},
     {"find_whole_words_as_columns", KW(whole_words<0>),
      "find_whole_words_as_columns(haystack, overlapping=False, *, matchkind=MatchKind.LeftmostLongest, word_bytes=None) -> "
      "MatchColumns\n\n[extension] grep -w for the object's patterns: of all their occurrences those whose neighbour bytes "

@@ -57,6 +57,9 @@ extern "C" {
  *     twelfth addendum (additive as well): the anchored search -- acx_match_at / acx_match_at_device /
  *     acx_match_at_into_device / acx_match_at_host and the acx_at_t accessors (acx_at_count, _entries, _on_device, _pattern,
  *     _end, _row_offsets, _copy, acx_free_at);
+ *     thirteenth addendum (additive as well): greedy segmentation by the dictionary -- acx_segment / acx_segment_device /
+ *     acx_segment_into_device / acx_segment_host and the acx_seg_t accessors (acx_seg_count, _rows, _on_device, _pattern,
+ *     _offsets, _row_offsets, _copy, acx_free_seg);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -1026,6 +1029,65 @@ const int64_t *acx_at_end(const acx_at_t *r);
 const int64_t *acx_at_row_offsets(const acx_at_t *r);
 int acx_at_copy(const acx_at_t *r, int which /* ACX_AT_PATTERN .. */, void *host_dst);
 void acx_free_at(acx_at_t *r);
+
+/* ---- segment: greedy longest-match tokenization -- cut the data into dictionary entries from left to right, always the entry
+ * the handle's match kind prefers at the current position, and go on where it ended.  A LeftmostLongest handle gives MaxMatch
+ * (WordPiece's inner loop, forward maximum matching of CJK text, any vocabulary-driven tokenizer); a LeftmostFirst one gives
+ * re.finditer of P_0|P_1|...|. .  No find runs.
+ * THE DEFINITION.  Patterns P_i; data h[0 .. len) cut into rows (offsets, uniform_len, or neither: one row); a
+ * case-insensitive handle compares every byte folded.  For a row [b, L) the pieces are built by a loop: p = b; while p < L:
+ * (1) (i, e) = the non-overlapping acx_match_at result of the anchor (p, L) under the handle's own match kind -- a match never
+ * crosses the row; (2) a match: the piece is (i, p, e) and p = e; (3) none: the piece is (-1, p, p + u) and p = p + u, u
+ * being the unknown unit: 1 byte, or with ACX_SEG_UTF8 the length the lead byte h[p] announces -- 2, 3, 4 for 0xC0..0xDF,
+ * 0xE0..0xEF, 0xF0..0xF7, 1 for everything else, a stray continuation byte included -- shortened to the run of continuation
+ * bytes (0x80..0xBF) that actually follows, and clipped to L.  The pieces of a row tile it exactly; an empty row has none.
+ * THE RESULT, three parts: pattern -- T int64 words, the pattern or -1; offsets -- T + 1 int64 words, the GLOBAL ascending piece
+ * boundaries, offsets[T] = len (the token boundaries acx_tokens_device takes as d_ts = offsets, d_te = offsets + 1);
+ * row_offsets -- rows + 1 int64 words, entry r the number of pieces that begin before row r does, the last one T.  There is
+ * no overlapping form: the chain is defined by one choice per position.
+ * acx_segment: host data and host offsets (n_hay + 1 from 0 to len, or NULL: one haystack), a host result.  The data is
+ * staged to the device, the same kernels run and the block comes back: there is no CPU matching route.  codepoints != 0
+ * implies ACX_SEG_UTF8, and `offsets` come back as CHARACTER indexes of UTF-8 data, converted on the host.
+ * acx_segment_device: everything in HBM on the automaton's device (d_offsets / uniform_len as for acx_find_device; neither:
+ * one row).  It runs on the handle's context and stream and returns when T is known -- 8 bytes cross the bus; every accessor
+ * waits for the kernels, and d_hay and d_offsets must stay valid until then.  Device offsets are the caller's word: wrong
+ * ones give wrong pieces, never a read outside the data or a write outside the result.  A case-insensitive handle folds the
+ * bytes it loads: no folded copy is made and the caller's memory is never written.
+ * acx_segment_into_device: the raw synchronous form -- d_pattern (cap words), d_offsets_out (cap + 1 words) and d_row_offsets
+ * (rows + 1 words), int64, 8-byte aligned, in HBM on the automaton's device.  *n_pieces is always T; the three are written
+ * only when T <= cap, exactly T, T + 1 and rows + 1 words, and are complete when it returns.
+ * acx_segment_host: host memory only, no device -- the definition walked over the compiled tables (first_child, in_byte,
+ * own_off, own_pid of acx_host_tables), for match_kind's rule.  Not a matching path of the library: it documents the chain and
+ * checks the kernels.  Same outputs and the same cap rule as the raw form (cap = 0: count only, the three may be NULL).
+ * Refusals, before any device work and in this order: ACX_EINVAL -- unknown flags, host offsets that do not rise from 0 to
+ * len; ACX_ETOOBIG -- a handle with a pattern longer than 256 bytes (dictionary entries are words: the longest step of the
+ * chain is the width of the per-tile entry maps); ACX_ETOOBIG -- more than 2^31 - 1 tiles of 4096 bytes, or 2^38 rows.
+ * An empty part still has a valid, non-null address. */
+#define ACX_SEG_UTF8 1u
+#define ACX_SEG_PATTERN 0     /* acx_seg_copy: the parts of a result */
+#define ACX_SEG_OFFSETS 1
+#define ACX_SEG_ROW_OFFSETS 2
+typedef struct acx_seg acx_seg_t;
+int acx_segment(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one haystack */,
+                uint64_t n_hay, uint32_t flags, int codepoints, acx_seg_t **out);
+int acx_segment_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                       uint64_t uniform_len, uint32_t flags, acx_seg_t **out);
+int acx_segment_into_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                            uint64_t uniform_len, uint32_t flags, uint64_t cap, int64_t *d_pattern, int64_t *d_offsets_out,
+                            int64_t *d_row_offsets, uint64_t *n_pieces);
+int acx_segment_host(const acx_host_automaton_t *h, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one row */,
+                     uint64_t n_hay, uint32_t flags, int match_kind, uint64_t cap, int64_t *pattern, int64_t *offsets_out,
+                     int64_t *row_offsets, uint64_t *n_pieces);
+uint64_t acx_seg_count(const acx_seg_t *r); /* T: the pieces                                      */
+uint64_t acx_seg_rows(const acx_seg_t *r);  /* the rows (one haystack that is no batch: 1)        */
+int acx_seg_on_device(const acx_seg_t *r);  /* 1: the columns are in HBM, 0: host memory          */
+/* host or device pointer by acx_seg_on_device (T, T + 1 and rows + 1 int64 words); waits for the device stage.  NULL: the wait
+ * failed.  Valid until acx_free_seg. */
+const int64_t *acx_seg_pattern(const acx_seg_t *r);
+const int64_t *acx_seg_offsets(const acx_seg_t *r);
+const int64_t *acx_seg_row_offsets(const acx_seg_t *r);
+int acx_seg_copy(const acx_seg_t *r, int which /* ACX_SEG_PATTERN .. */, void *host_dst);
+void acx_free_seg(acx_seg_t *r);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
