@@ -27,9 +27,12 @@ from .ahocorasick_rs import (
     TokenLabels,
     MatchesAt,
     Segments,
+    WordPieces,
     RowOffsets,
     split_rows,
     ASCII_WORD_BYTES,
+    ASCII_WHITESPACE,
+    ASCII_PUNCTUATION,
 )
 
 __acx_amd__ = True
@@ -64,11 +67,16 @@ __all__ = [
     "MatchesAt",
     # Extension: the result of segment / segment_batch
     "Segments",
+    # Extension: the result of wordpiece / wordpiece_batch
+    "WordPieces",
     # Extension: a delimited buffer cut into the rows the _batch methods take (offsets=), and its result
     "split_rows",
     "RowOffsets",
     # Extension: the default word set of find_whole_words_as_columns / _batch and filter_whole_words_batch
     "ASCII_WORD_BYTES",
+    # Extension: the default separators of wordpiece / wordpiece_batch, and BertTokenizer's isolated bytes
+    "ASCII_WHITESPACE",
+    "ASCII_PUNCTUATION",
     # Deprecated:
     "MATCHKIND_STANDARD",
     "MATCHKIND_LEFTMOST_FIRST",

@@ -24,9 +24,9 @@ LIB = os.path.join(HERE, "libacx_hip.so")
 EXT = os.path.join(HERE, "ahocorasick_rs" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 
 # the one list of what libacx_hip.so is compiled from (tools/build_variant.sh asks for it: --print-sources)
-LIB_SOURCES = ["kernels.hip", "replace.hip", "fold.hip", "summary.hip", "columns.hip", "tally.hip", "filter.hip", "score.hip", "mask.hip", "rows.hip", "spans.hip", "snippets.hip", "words.hip", "tokens.hip", "at.hip", "seg.hip", "acx_api.cpp", "workspace.cpp", "small_calls.cpp", "find_attempts.cpp",
-               "find_pipeline.cpp", "build_upload.cpp", "result_block.cpp", "replace_api.cpp", "summary_api.cpp", "columns_api.cpp", "tally_api.cpp", "filter_api.cpp", "score_api.cpp", "mask_api.cpp", "rows_api.cpp", "spans_api.cpp", "snippets_api.cpp", "words_api.cpp", "tokens_api.cpp", "at_api.cpp", "seg_api.cpp", "automaton.cpp", "comm.cpp"]
-LIB_HEADERS = ["kernels.hpp", "k1b_bounds.hpp", "stage_device.hpp", "replace.hpp", "fold.hpp", "summary.hpp", "columns.hpp", "tally.hpp", "filter.hpp", "score.hpp", "mask.hpp", "rows.hpp", "spans.hpp", "snippets.hpp", "words.hpp", "tokens.hpp", "at.hpp", "at_walk.hpp", "seg.hpp", "host_trie.hpp", "automaton.hpp", "device_types.hpp", "host_common.hpp", "workspace.hpp",
+LIB_SOURCES = ["kernels.hip", "replace.hip", "fold.hip", "summary.hip", "columns.hip", "tally.hip", "filter.hip", "score.hip", "mask.hip", "rows.hip", "spans.hip", "snippets.hip", "words.hip", "tokens.hip", "at.hip", "seg.hip", "wp.hip", "acx_api.cpp", "workspace.cpp", "small_calls.cpp", "find_attempts.cpp",
+               "find_pipeline.cpp", "build_upload.cpp", "result_block.cpp", "replace_api.cpp", "summary_api.cpp", "columns_api.cpp", "tally_api.cpp", "filter_api.cpp", "score_api.cpp", "mask_api.cpp", "rows_api.cpp", "spans_api.cpp", "snippets_api.cpp", "words_api.cpp", "tokens_api.cpp", "at_api.cpp", "seg_api.cpp", "wp_api.cpp", "automaton.cpp", "comm.cpp"]
+LIB_HEADERS = ["kernels.hpp", "k1b_bounds.hpp", "stage_device.hpp", "replace.hpp", "fold.hpp", "summary.hpp", "columns.hpp", "tally.hpp", "filter.hpp", "score.hpp", "mask.hpp", "rows.hpp", "spans.hpp", "snippets.hpp", "words.hpp", "tokens.hpp", "at.hpp", "at_walk.hpp", "seg.hpp", "wp.hpp", "host_trie.hpp", "automaton.hpp", "device_types.hpp", "host_common.hpp", "workspace.hpp",
                "small_calls.hpp", "find_attempts.hpp", "find_policy.hpp", "find_pipeline.hpp", "result_block.hpp", os.path.join(INCLUDE, "acx.h")]
 EXT_SOURCES = ["pymodule.cpp"]
 

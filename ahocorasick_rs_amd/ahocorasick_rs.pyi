@@ -181,6 +181,25 @@ class Segments:
     def __len__(self) -> int: ...  # the number of pieces
     def tolist(self) -> Any: ...  # list[tuple[int, int, int]] of (pattern, start, end) local to the row, or one such list per row
 
+# extension: the result of wordpiece / wordpiece_batch -- the words of the data cut into vocabulary entries, where the chains
+# ran: a word's first piece is looked up as it stands, the following ones behind the continuation prefix; a word that is too
+# long or cannot be cut completely is ONE piece with unk_id
+class WordPieces:
+    @property
+    def id(self) -> Column: ...  # len(self) int64 entries: the pattern of the piece, or unk_id
+    @property
+    def start(self) -> Column: ...  # len(self) int64 GLOBAL positions, strictly ascending (characters for a str)
+    @property
+    def end(self) -> Column: ...  # len(self) int64 GLOBAL positions
+    @property
+    def first(self) -> Column: ...  # len(self) uint8 entries: 1 iff the piece is the first of its word
+    @property
+    def row_offsets(self) -> Optional[Column]: ...  # wordpiece_batch: len(haystacks) + 1 int64 entries that cut the pieces by row; else None
+    @property
+    def device(self) -> Optional[int]: ...  # None: host memory; otherwise the HIP ordinal
+    def __len__(self) -> int: ...  # the number of pieces
+    def tolist(self) -> Any: ...  # list[tuple[int, int, int, int]] of (id, start, end, first) local to the row, or one such list per row
+
 # extension: the result of split_rows -- the offsets that cut a delimited buffer into rows, where the data lies
 class RowOffsets:
     @property
@@ -201,6 +220,11 @@ def split_rows(data: Any, delimiter: Any = b"\n") -> RowOffsets: ...
 
 # extension: the default word set of the find_whole_words_* methods, ASCII [0-9A-Za-z_]
 ASCII_WORD_BYTES: bytes
+
+# extension: the default separators of wordpiece / wordpiece_batch (b" \t\n\r\x0b\x0c"), and the 32 ASCII bytes BERT's
+# _is_punctuation accepts (33-47, 58-64, 91-96, 123-126): isolated=ASCII_PUNCTUATION is the BertTokenizer recipe
+ASCII_WHITESPACE: bytes
+ASCII_PUNCTUATION: bytes
 
 class AhoCorasick:
     def __init__(
@@ -351,6 +375,21 @@ class AhoCorasick:
     def segment_batch(
         self, haystacks: Any, *, utf8: Optional[bool] = None, offsets: Any = None, row_length: Optional[int] = None
     ) -> Segments: ...
+    # extension: WordPiece tokenization by the dictionary -- the patterns are the vocabulary as a vocab.txt lists it.  A byte
+    # in separators (None: ASCII_WHITESPACE) belongs to no word, a byte in isolated (None: none) is a word by itself, every
+    # other run is a word; its first piece is looked up as it stands, the following ones behind continuation_prefix, each
+    # the entry the object's match kind prefers (LeftmostLongest: BERT's WordpieceTokenizer, the limit counted in bytes).  A
+    # word longer than max_word_bytes or with a step that finds nothing is ONE piece with unk_id.  The sets and the prefix:
+    # bytes-like or str, the sets ASCII (ValueError otherwise; a byte in both: ValueError).  max_word_bytes: an int in
+    # range(1, 1025), unk_id: an int64 (TypeError for a bool or a non-int, ValueError out of range).  Positions in CHARACTERS
+    def wordpiece(
+        self, haystack: str, *, continuation_prefix: Any = "##", separators: Any = None, isolated: Any = None,
+        max_word_bytes: int = 100, unk_id: int = -1
+    ) -> WordPieces: ...
+    def wordpiece_batch(
+        self, haystacks: Any, *, continuation_prefix: Any = "##", separators: Any = None, isolated: Any = None,
+        max_word_bytes: int = 100, unk_id: int = -1, offsets: Any = None, row_length: Optional[int] = None
+    ) -> WordPieces: ...
     def _info(self) -> dict[str, Any]: ...
 
 class BytesAhoCorasick:
@@ -501,4 +540,16 @@ class BytesAhoCorasick:
     def segment_batch(
         self, haystacks: Any, *, utf8: Optional[bool] = None, offsets: Any = None, row_length: Optional[int] = None
     ) -> Segments: ...
+    # extension: WordPiece tokenization by the dictionary, as AhoCorasick.wordpiece, on bytes.  haystack: one bytes-like or one
+    # uint8 __dlpack__ tensor; wordpiece_batch takes its haystacks as segment_batch does, split_rows(t).offsets included, and
+    # a word never crosses a row.  The sets and the prefix are bytes-like (a str: TypeError).  On the automaton's device
+    # everything stays in HBM, and the WordPieces keeps the input tensors alive until it goes.  No search runs
+    def wordpiece(
+        self, haystack: Any, *, continuation_prefix: Any = b"##", separators: Any = None, isolated: Any = None,
+        max_word_bytes: int = 100, unk_id: int = -1
+    ) -> WordPieces: ...
+    def wordpiece_batch(
+        self, haystacks: Any, *, continuation_prefix: Any = b"##", separators: Any = None, isolated: Any = None,
+        max_word_bytes: int = 100, unk_id: int = -1, offsets: Any = None, row_length: Optional[int] = None
+    ) -> WordPieces: ...
     def _info(self) -> dict[str, Any]: ...

@@ -40,6 +40,9 @@ AT_OVERLAPPING, AT_FULL, AT_ROW_STARTS = 1, 2, 4  # acx_match_at* flags (ACX_AT_
 AT_PATTERN, AT_END, AT_ROW_OFFSETS = 0, 1, 2  # acx_at_copy (ACX_AT_PATTERN ..)
 SEG_UTF8 = 1  # acx_segment* flags (ACX_SEG_UTF8): an unknown piece is a whole UTF-8 character
 SEG_PATTERN, SEG_OFFSETS, SEG_ROW_OFFSETS = 0, 1, 2  # acx_seg_copy (ACX_SEG_PATTERN ..)
+WP_WORD, WP_SPACE, WP_ALONE = 0, 1, 2  # acx_wordpiece*: the classes of the byte values (ACX_WP_WORD ..)
+WP_MAX_WORD = 1024  # ... and the largest max_word (ACX_WP_MAX_WORD)
+WP_ID, WP_START, WP_END, WP_FIRST, WP_ROW_OFFSETS = 0, 1, 2, 3, 4  # acx_wp_copy (ACX_WP_ID ..)
 MASK_ZERO = 1  # acx_mask* flags (ACX_MASK_ZERO): uncovered bytes become 0 instead of the haystack's own
 ABI_VERSION = 11  # ACX_VERSION of include/acx.h this binding was written against
 
@@ -118,7 +121,7 @@ _RESULTS = {
     "filtered": (("rows", "bytes"), True), "scores": (("rows",), False), "masked": (("bytes", "rows"), False),
     "rows": (("count", "bytes"), None), "spans": (("count", "rows"), True), "snippets": (("count", "rows", "nbytes"), True),
     "token_labels": (("count",), None), "at": (("count", "entries"), None),
-    "seg": (("count", "rows"), None),
+    "seg": (("count", "rows"), None), "wp": (("count", "rows"), None),
 }
 # Everything else, one row each: name -> arguments, or (arguments, what it returns) where that is no status.  (acx_version is
 # declared by lib() itself, ahead of the version check.)
@@ -230,6 +233,16 @@ _SINGLES = {
     "acx_seg_offsets": ([vp], vp),
     "acx_seg_row_offsets": ([vp], vp),
     "acx_seg_copy": [vp, i32, vp],
+    "acx_wordpiece": [vp, vp, u64, vp, u64, vp, vp, u64, u64, i64, u32, i32, _out],
+    "acx_wordpiece_device": [vp, vp, u64, vp, u64, u64, vp, vp, u64, u64, i64, u32, _out],
+    "acx_wordpiece_into_device": [vp, vp, u64, vp, u64, u64, vp, vp, u64, u64, i64, u32, u64, vp, vp, vp, vp, vp, _u64p],
+    "acx_wordpiece_host": [vp, vp, u64, vp, u64, vp, vp, u64, u64, i64, u32, i32, u64, vp, vp, vp, vp, vp, _u64p],
+    "acx_wp_id": ([vp], vp),
+    "acx_wp_start": ([vp], vp),
+    "acx_wp_end": ([vp], vp),
+    "acx_wp_first": ([vp], vp),
+    "acx_wp_row_offsets": ([vp], vp),
+    "acx_wp_copy": [vp, i32, vp],
 }
 
 
@@ -1067,6 +1080,99 @@ def segment_host(h: "HostAutomaton", hay, *, offsets: Optional[Sequence[int]] = 
     return pattern[:t], bounds, ro
 
 
+ASCII_WHITESPACE = b" \t\n\r\x0b\x0c"  # the default separators of wordpiece: what bytes.split() splits at
+# the 32 ASCII bytes BERT's _is_punctuation accepts: 33-47, 58-64, 91-96, 123-126 (isolated=ASCII_PUNCTUATION: BertTokenizer)
+ASCII_PUNCTUATION = bytes(list(range(33, 48)) + list(range(58, 65)) + list(range(91, 97)) + list(range(123, 127)))
+
+
+def wp_classes(separators=None, isolated=None) -> np.ndarray:
+    """the 256 classes acx_wordpiece* take: WP_SPACE for the byte values in `separators` (None: ASCII_WHITESPACE), WP_ALONE
+    for those in `isolated` (None: none), WP_WORD for the rest.  Both bytes-like (a str is a TypeError); a byte value in
+    both is a ValueError."""
+    sets = []
+    for name, given, default in (("separators", separators, ASCII_WHITESPACE), ("isolated", isolated, b"")):
+        if isinstance(given, str):
+            raise TypeError(f"{name} must be bytes-like, not str")
+        sets.append(frozenset(bytes(default if given is None else given)))
+    both = sets[0] & sets[1]
+    if both:
+        raise ValueError(f"byte value {min(both)} is a separator and isolated")
+    cls = np.full(256, WP_WORD, dtype=np.uint8)
+    cls[list(sets[0])] = WP_SPACE
+    cls[list(sets[1])] = WP_ALONE
+    return cls
+
+
+def _wp_args(cls, prefix, max_word: int, unk_id: int) -> tuple:
+    """(cls, prefix, prefix_len, max_word, unk_id, flags) of an acx_wordpiece* call, with what must stay alive behind it"""
+    c = np.ascontiguousarray(np.asarray(cls, dtype=np.uint8).reshape(-1))
+    if c.size != 256:
+        raise ValueError("cls needs 256 entries")
+    pre = np.frombuffer(bytes(prefix) + b"\0", dtype=np.uint8)
+    return c.ctypes.data, pre.ctypes.data, len(pre) - 1, max_word, unk_id, 0, c, pre
+
+
+class DeviceWordPieces(_Result):
+    """The result of Automaton.wordpiece / wordpiece_device (acx_wp_t): the pieces of a WordPiece tokenization by the
+    dictionary -- id, start, end (count int64 words each, global positions) and first (count bytes: 1 on the first piece of
+    its word) and row_offsets (rows + 1: the pieces that begin before every row) -- in HBM (on_device) or in host memory.
+    id() .. row_offsets() copy them out; the _ptr() forms are where they lie (all wait for the device stage)."""
+    _PREFIX = "wp"
+    count, rows = _Size("count"), _Size("rows")
+
+    def id_ptr(self) -> int:
+        return self._address("id")
+
+    def start_ptr(self) -> int:
+        return self._address("start")
+
+    def end_ptr(self) -> int:
+        return self._address("end")
+
+    def first_ptr(self) -> int:
+        return self._address("first")
+
+    def row_offsets_ptr(self) -> int:
+        return self._address("row_offsets")
+
+    def id(self) -> np.ndarray:
+        return self._copy_out("copy", self.count, np.int64, WP_ID)
+
+    def start(self) -> np.ndarray:
+        return self._copy_out("copy", self.count, np.int64, WP_START)
+
+    def end(self) -> np.ndarray:
+        return self._copy_out("copy", self.count, np.int64, WP_END)
+
+    def first(self) -> np.ndarray:
+        return self._copy_out("copy", self.count, np.uint8, WP_FIRST)
+
+    def row_offsets(self) -> np.ndarray:
+        return self._copy_out("copy", self.rows + 1, np.int64, WP_ROW_OFFSETS)
+
+
+def wordpiece_host(h: "HostAutomaton", hay, cls, *, prefix=b"##", max_word: int = 100, unk_id: int = -1,
+                   offsets: Optional[Sequence[int]] = None, match_kind: int = MATCH_LEFTMOST_LONGEST):
+    """acx_wordpiece_host: the definition of the WordPiece tokenization walked over a HostAutomaton's tables, no device
+    involved.  hay: bytes-like; cls: 256 classes (wp_classes); offsets: n + 1 from 0 to len(hay), or None (one row).  Returns
+    (id, start, end, first, row_offsets): T, T, T int64 words, T bytes and rows + 1 int64 words.  ValueError (code EINVAL) for
+    a class above 2, max_word outside 1 .. WP_MAX_WORD or offsets that do not rise from 0 to len(hay)."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(hay), dtype=np.uint8))
+    off = _u64(offsets)
+    n_hay = 0 if off is None else len(off) - 1
+    rows = n_hay if off is not None else 1
+    w = _wp_args(cls, prefix, max_word, unk_id)
+    args = (h._h, a.ctypes.data if a.size else None, a.size, None if off is None else off.ctypes.data, n_hay, *w[:6], match_kind)
+    n = ctypes.c_uint64(0)
+    _check(lib().acx_wordpiece_host(*args, 0, None, None, None, None, None, ctypes.byref(n)))  # (count only)
+    t = int(n.value)
+    ids, start, end = (np.zeros(t + 1, dtype=np.int64) for _ in range(3))
+    first, ro = np.zeros(t + 1, dtype=np.uint8), np.zeros(rows + 1, dtype=np.int64)
+    _check(lib().acx_wordpiece_host(*args, t + 1, ids.ctypes.data, start.ctypes.data, end.ctypes.data, first.ctypes.data,
+                                    ro.ctypes.data, ctypes.byref(n)))
+    return ids[:t], start[:t], end[:t], first[:t], ro
+
+
 class DeviceRows(_Result):
     """The result of split_rows / split_rows_device (acx_rows_t): the offsets that cut nbytes of delimited data into rows --
     rows + 1 int64 words from 0 to nbytes, in HBM (on_device, on `device`) or in host memory.  `rows` is valid at once;
@@ -1714,6 +1820,38 @@ class Automaton(_Handle):
         n = ctypes.c_uint64(0)
         _check(lib().acx_segment_into_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, flags, cap,
                                              d_pattern or None, d_offsets_out or None, d_row_offsets or None, ctypes.byref(n)))
+        return int(n.value)
+
+    # ---- WordPiece tokenization by the dictionary on the device (acx_wordpiece*)
+    def wordpiece(self, haystacks: Optional[Sequence[bytes]], cls, *, prefix=b"##", max_word: int = 100, unk_id: int = -1,
+                  codepoints: bool = False, single: Optional[bytes] = None) -> DeviceWordPieces:
+        """host data -- a sequence of rows, or single=...: one haystack that is no batch (offsets = NULL) -- a host result;
+        cls: 256 classes (wp_classes); codepoints: start and end in characters"""
+        hay = _host_arg(haystacks, single, _SINGLE_OWN)
+        w = _wp_args(cls, prefix, max_word, unk_id)
+        out = ctypes.c_void_p()
+        _check(lib().acx_wordpiece(self._h, *hay[:4], *w[:6], int(codepoints), ctypes.byref(out)))
+        return DeviceWordPieces(out.value)
+
+    def wordpiece_device(self, d_ptr: int, nbytes: int, cls, *, prefix=b"##", max_word: int = 100, unk_id: int = -1,
+                         d_offsets: int = 0, n_hay: int = 0, uniform_len: int = 0) -> DeviceWordPieces:
+        """everything in HBM; the columns stay there"""
+        w = _wp_args(cls, prefix, max_word, unk_id)
+        out = ctypes.c_void_p()
+        _check(lib().acx_wordpiece_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, *w[:6],
+                                          ctypes.byref(out)))
+        return DeviceWordPieces(out.value)
+
+    def wordpiece_into_device(self, d_ptr: int, nbytes: int, cls, cap: int, d_id: int, d_start: int, d_end: int, d_first: int,
+                              d_row_offsets: int, *, prefix=b"##", max_word: int = 100, unk_id: int = -1, d_offsets: int = 0,
+                              n_hay: int = 0, uniform_len: int = 0) -> int:
+        """the raw form: T is returned; T entries at each of the four columns and rows + 1 int64 words at d_row_offsets are
+        written only when cap != 0 and T <= cap, and are complete when it returns; cap = 0: the count pass alone"""
+        w = _wp_args(cls, prefix, max_word, unk_id)
+        n = ctypes.c_uint64(0)
+        _check(lib().acx_wordpiece_into_device(self._h, d_ptr or None, nbytes, d_offsets or None, n_hay, uniform_len, *w[:6], cap,
+                                               d_id or None, d_start or None, d_end or None, d_first or None,
+                                               d_row_offsets or None, ctypes.byref(n)))
         return int(n.value)
 
     def generate(self, d_ptr: int, nbytes: int, kind: int, seed: int,

@@ -893,6 +893,17 @@ struct SegmentsObject : OwnerObject {
     // and they read both on the library's stream: the tensors stay the producer's until the result goes
     PyObject *inputs[3];
 };
+struct WordPiecesObject : OwnerObject {
+    bool batch; // wordpiece_batch: .row_offsets is a Column and tolist() gives one list per row
+    // where every row begins, for tolist()'s local positions -- one of three: the host routes' row begins in the result's
+    // unit (rows + 1 entries), a row length, or the device offsets (inputs[1] keeps them alive)
+    std::vector<int64_t> *row_begin;
+    uint64_t row_length;
+    const uint64_t *d_off;
+    // the device route: the capsules of the haystack and its offsets.  The call returns with the emitting kernels in flight
+    // and they read both on the library's stream: the tensors stay the producer's until the result goes
+    PyObject *inputs[3];
+};
 enum { MR_OFFSETS = 0, MR_DATA = 1 };
 struct MaskedRowsObject : OwnerObject {
     bool utf8;                 // made by the str class
@@ -933,7 +944,7 @@ struct ResultType {
     PyTypeObject *type; // made by PyInit
     PyMethodDef methods[2];
 };
-enum { RT_MATCH_COLUMNS, RT_PATTERN_COUNTS, RT_FILTERED_ROWS, RT_ROW_SCORES, RT_MASKED_ROWS, RT_ROW_OFFSETS, RT_MATCH_SPANS, RT_MATCH_SNIPPETS, RT_TOKEN_LABELS, RT_MATCHES_AT, RT_SEGMENTS, RT_COUNT };
+enum { RT_MATCH_COLUMNS, RT_PATTERN_COUNTS, RT_FILTERED_ROWS, RT_ROW_SCORES, RT_MASKED_ROWS, RT_ROW_OFFSETS, RT_MATCH_SPANS, RT_MATCH_SNIPPETS, RT_TOKEN_LABELS, RT_MATCHES_AT, RT_SEGMENTS, RT_WORD_PIECES, RT_COUNT };
 extern ResultType RESULT_TYPES[RT_COUNT];
 
 OwnerObject *owner_of(PyObject *s) { return reinterpret_cast<OwnerObject *>(s); }
@@ -1370,6 +1381,54 @@ void seg_dealloc(PyObject *self) {
     for (PyObject *cap : inputs) dlpack_release(cap);
 }
 
+// WordPieces: list[tuple[int, int, int, int]] of (id, start, end, first) local to the row, or -- a batch -- one such list per row
+const void *wp_part(const acx_wp_t *r, int which) {
+    return which == ACX_WP_ID ? acx_wp_id(r) : which == ACX_WP_START ? acx_wp_start(r) : which == ACX_WP_END ? acx_wp_end(r)
+           : which == ACX_WP_FIRST ? (const void *)acx_wp_first(r) : acx_wp_row_offsets(r);
+}
+uint64_t wp_part_len(const OwnerObject *o, int which, int *elem) {
+    const acx_wp_t *r = handle<acx_wp_t>(o);
+    *elem = which == ACX_WP_FIRST;
+    if (which != ACX_WP_ROW_OFFSETS) return acx_wp_count(r);
+    return static_cast<const WordPiecesObject *>(o)->batch ? acx_wp_rows(r) + 1 : NO_PART;
+}
+PyObject *wp_tolist(PyObject *self, PyObject *) {
+    const acx_wp_t *r = handle<acx_wp_t>(self);
+    const WordPiecesObject *o = static_cast<WordPiecesObject *>(owner_of(self));
+    const uint64_t n = acx_wp_count(r), rows = acx_wp_rows(r);
+    std::vector<int64_t> id((size_t)n + 1), start((size_t)n + 1), end((size_t)n + 1), ro((size_t)rows + 1), begin((size_t)rows + 1, 0);
+    std::vector<uint8_t> first((size_t)n + 1);
+    const int rc = nogil([&] {
+        int rc = acx_wp_copy(r, ACX_WP_ID, id.data());
+        if (rc == ACX_OK) rc = acx_wp_copy(r, ACX_WP_START, start.data());
+        if (rc == ACX_OK) rc = acx_wp_copy(r, ACX_WP_END, end.data());
+        if (rc == ACX_OK) rc = acx_wp_copy(r, ACX_WP_FIRST, first.data());
+        if (rc == ACX_OK) rc = acx_wp_copy(r, ACX_WP_ROW_OFFSETS, ro.data());
+        if (rc == ACX_OK && o->batch && !o->row_begin && !o->row_length && o->d_off)
+            rc = acx_device_download(begin.data(), o->d_off, (rows + 1) * 8);
+        return rc;
+    });
+    if (rc != ACX_OK) return raise_acx(rc);
+    if (o->batch && o->row_begin) begin = *o->row_begin;
+    else if (o->batch && o->row_length)
+        for (uint64_t h = 0; h <= rows; h++) begin[(size_t)h] = (int64_t)(h * o->row_length);
+    uint64_t row = 0;
+    return rows_of(o->batch ? &ro : nullptr, n, [&](uint64_t i) {
+        while (row + 1 < rows && (uint64_t)ro[(size_t)row + 1] <= i) row++;
+        while (row > 0 && (uint64_t)ro[(size_t)row] > i) row--;
+        const int64_t b = begin[(size_t)row];
+        return Py_BuildValue("(LLLi)", (long long)id[(size_t)i], (long long)(start[(size_t)i] - b), (long long)(end[(size_t)i] - b),
+                             (int)first[(size_t)i]);
+    });
+}
+void wp_dealloc(PyObject *self) {
+    WordPiecesObject *o = static_cast<WordPiecesObject *>(owner_of(self));
+    delete o->row_begin;
+    PyObject *inputs[3] = {o->inputs[0], o->inputs[1], o->inputs[2]};
+    owner_dealloc(self); // (waits for the kernels: nothing reads the inputs after it)
+    for (PyObject *cap : inputs) dlpack_release(cap);
+}
+
 // RowScores and RowOffsets: their one part as list[int]
 uint64_t rs_part_len(const OwnerObject *o, int, int *) { return acx_scores_rows(handle<acx_scores_t>(o)); }
 uint64_t ro_part_len(const OwnerObject *o, int, int *) { return acx_rows_count(handle<acx_rows_t>(o)) + 1; }
@@ -1532,6 +1591,23 @@ ResultType RESULT_TYPES[RT_COUNT] = {
        "row_offsets[h + 1] - 1 are haystack h's", part(ACX_SEG_ROW_OFFSETS)},
       DEVICE_ATTR("columns are")},
      seg_dealloc},
+    {"ahocorasick_rs.WordPieces", sizeof(WordPiecesObject), owner_ops<acx_wp_t, acx_wp_on_device, wp_part, acx_free_wp>(),
+     wp_part_len, size_len<acx_wp_t, acx_wp_count>, wp_tolist,
+     "the pieces as list[tuple[int, int, int, int]] of (id, start, end, first) local to their row, or -- wordpiece_batch -- one "
+     "such list per row (copies device columns to the host)",
+     "The result of wordpiece / wordpiece_batch: the words of the data cut into vocabulary entries.  .id, .start and .end are "
+     "int64 Columns of len(self) entries -- the pattern of every piece, or unk_id, and its GLOBAL positions -- and .first a "
+     "uint8 Column: 1 on the first piece of its word.  .row_offsets (wordpiece_batch) cuts the pieces by row.  All lie where "
+     "the chains ran (.device).  Every accessor of a column waits for the stage's last kernel first.",
+     {{"id", owner_get_part, nullptr, "Column of len(self) int64 entries: the pattern of the piece, or unk_id", part(ACX_WP_ID)},
+      {"start", owner_get_part, nullptr, "Column of len(self) int64 entries: where the piece begins (characters for a str)", part(ACX_WP_START)},
+      {"end", owner_get_part, nullptr, "Column of len(self) int64 entries: where the piece ends (characters for a str)", part(ACX_WP_END)},
+      {"first", owner_get_part, nullptr, "Column of len(self) uint8 entries: 1 iff the piece is the first of its word", part(ACX_WP_FIRST)},
+      {"row_offsets", owner_get_part, nullptr,
+       "None for one haystack; for a batch a Column of len(haystacks) + 1 int64 entries: pieces row_offsets[h] .. "
+       "row_offsets[h + 1] - 1 are haystack h's", part(ACX_WP_ROW_OFFSETS)},
+      DEVICE_ATTR("columns are")},
+     wp_dealloc},
 };
 #undef DEVICE_ATTR
 
@@ -2726,6 +2802,192 @@ template <bool batch> PyObject *segment(PyObject *self, PyObject *args, PyObject
 }
 
 // ---------------------------------------------------------------------------
+// WordPiece tokenization by the dictionary: wordpiece / wordpiece_batch -> WordPieces (acx_wordpiece / acx_wordpiece_device).
+// No find runs.  A WordPieces owns the acx_wp_t; its parts are Columns with the lifetime chain of a MatchColumns' columns.
+// ---------------------------------------------------------------------------
+constexpr char ASCII_WHITESPACE[] = " \t\n\r\x0b\x0c";
+constexpr char ASCII_PUNCTUATION[] = "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~";
+
+struct WordPieceArgs {
+    uint8_t cls[256];
+    std::string prefix;
+    uint64_t max_word = 100;
+    int64_t unk_id = -1;
+};
+
+// a set of byte values or the continuation prefix: None (the default), a bytes-like or -- the str class -- a str, which for
+// a set must be ASCII (a UTF-8 character is never split); sets the exception
+bool parse_wp_bytes(PyObject *o, const char *name, bool str_class, bool ascii_only, const char *dflt, std::string *out) {
+    if (!o || o == Py_None) { *out = dflt; return true; }
+    if (PyUnicode_Check(o)) {
+        if (!str_class) {
+            PyErr_Format(PyExc_TypeError, "argument '%s': a bytes-like object is needed, not 'str'", name);
+            return false;
+        }
+        if (ascii_only && !PyUnicode_IS_ASCII(o)) {
+            PyErr_Format(PyExc_ValueError, "%s must be ASCII: a UTF-8 character is never split", name);
+            return false;
+        }
+        Py_ssize_t len;
+        const char *s = PyUnicode_AsUTF8AndSize(o, &len);
+        if (!s) return false;
+        out->assign(s, (size_t)len);
+        return true;
+    }
+    Py_buffer view;
+    if (!get_bytes_view(o, &view)) return false;
+    out->assign(static_cast<const char *>(view.buf), (size_t)view.len);
+    PyBuffer_Release(&view);
+    return true;
+}
+
+// the keyword arguments of wordpiece / wordpiece_batch (each may be null or None: its default); sets the exception
+bool parse_wordpiece_args(bool str_class, PyObject *prefix, PyObject *separators, PyObject *isolated, PyObject *max_word,
+                          PyObject *unk_id, WordPieceArgs *A) {
+    std::string sep, alone;
+    if (!parse_wp_bytes(prefix, "continuation_prefix", str_class, false, "##", &A->prefix)) return false;
+    if (!parse_wp_bytes(separators, "separators", str_class, true, ASCII_WHITESPACE, &sep)) return false;
+    if (!parse_wp_bytes(isolated, "isolated", str_class, true, "", &alone)) return false;
+    std::memset(A->cls, ACX_WP_WORD, 256);
+    for (const char c : sep) A->cls[(uint8_t)c] = ACX_WP_SPACE;
+    for (const char c : alone) {
+        if (A->cls[(uint8_t)c] == ACX_WP_SPACE) {
+            PyErr_Format(PyExc_ValueError, "byte value %d is in separators and in isolated", (int)(uint8_t)c);
+            return false;
+        }
+        A->cls[(uint8_t)c] = ACX_WP_ALONE;
+    }
+    if (max_word && max_word != Py_None) {
+        long long v;
+        int overflow;
+        if (!parse_int(max_word, "max_word_bytes", &v, &overflow)) return false;
+        if (overflow || v < 1 || v > (long long)ACX_WP_MAX_WORD) {
+            PyErr_Format(PyExc_ValueError, "max_word_bytes must be in range(1, %u)", ACX_WP_MAX_WORD + 1);
+            return false;
+        }
+        A->max_word = (uint64_t)v;
+    }
+    if (unk_id && unk_id != Py_None) {
+        long long v;
+        int overflow;
+        if (!parse_int(unk_id, "unk_id", &v, &overflow)) return false;
+        if (overflow) {
+            PyErr_SetString(PyExc_ValueError, "unk_id must be in range(-2**63, 2**63)");
+            return false;
+        }
+        A->unk_id = (int64_t)v;
+    }
+    return true;
+}
+
+// the checks above without an automaton (the CPU tests; a module function): (cls, prefix, max_word_bytes, unk_id)
+PyObject *mod_wordpiece_args(PyObject *, PyObject *args) {
+    PyObject *utf8 = nullptr, *prefix = nullptr, *sep = nullptr, *alone = nullptr, *max_word = nullptr, *unk_id = nullptr;
+    if (!PyArg_ParseTuple(args, "O|OOOOO:_wordpiece_args", &utf8, &prefix, &sep, &alone, &max_word, &unk_id)) return nullptr;
+    WordPieceArgs A;
+    if (!parse_wordpiece_args(PyObject_IsTrue(utf8) == 1, prefix, sep, alone, max_word, unk_id, &A)) return nullptr;
+    return Py_BuildValue("(y#y#KL)", reinterpret_cast<const char *>(A.cls), (Py_ssize_t)256, A.prefix.data(), (Py_ssize_t)A.prefix.size(),
+                         (unsigned long long)A.max_word, (long long)A.unk_id);
+}
+
+// the row begins of a host batch in the result's unit: bytes, or -- chars -- the characters that begin before each
+std::vector<int64_t> *host_row_begins(const uint8_t *p, const uint64_t *off, uint64_t rows, bool chars) {
+    std::vector<int64_t> *b = new (std::nothrow) std::vector<int64_t>();
+    if (!b) return nullptr;
+    try {
+        b->resize((size_t)rows + 1);
+    } catch (...) { delete b; return nullptr; }
+    uint64_t at = 0, n = 0;
+    for (uint64_t r = 0; r <= rows; r++) {
+        if (chars)
+            for (; at < off[r]; at++) n += (p[at] & 0xC0) != 0x80;
+        (*b)[(size_t)r] = (int64_t)(chars ? n : off[r]);
+    }
+    return b;
+}
+
+// wordpiece(haystack, *, continuation_prefix="##", separators=None, isolated=None, max_word_bytes=100, unk_id=-1) /
+// wordpiece_batch(haystacks, *, ..., offsets=None, row_length=None).  A str's positions are CHARACTER indexes (the host route);
+// a tensor on the automaton's device stays in HBM end to end.
+template <bool batch> PyObject *wordpiece(PyObject *self, PyObject *args, PyObject *kwargs) {
+    acx_automaton_t *a = ac_of(self);
+    const bool str_class = utf8_of(self);
+    static const char *kw_s[] = {"haystack", "continuation_prefix", "separators", "isolated", "max_word_bytes", "unk_id", nullptr};
+    static const char *kw_b[] = {"haystacks", "continuation_prefix", "separators", "isolated", "max_word_bytes", "unk_id", "offsets",
+                                 "row_length", nullptr};
+    PyObject *hay = nullptr, *prefix = nullptr, *sep = nullptr, *alone = nullptr, *max_word = nullptr, *unk_id = nullptr,
+             *offsets = nullptr, *row_length = nullptr;
+    if (batch ? !PyArg_ParseTupleAndKeywords(args, kwargs, "O|$OOOOOOO:wordpiece_batch", const_cast<char **>(kw_b), &hay, &prefix, &sep,
+                                             &alone, &max_word, &unk_id, &offsets, &row_length)
+              : !PyArg_ParseTupleAndKeywords(args, kwargs, "O|$OOOOO:wordpiece", const_cast<char **>(kw_s), &hay, &prefix, &sep, &alone,
+                                             &max_word, &unk_id))
+        return nullptr;
+    WordPieceArgs A;
+    if (!parse_wordpiece_args(str_class, prefix, sep, alone, max_word, unk_id, &A)) return nullptr;
+    const uint8_t *pre = reinterpret_cast<const uint8_t *>(A.prefix.data());
+    const uint64_t pre_len = A.prefix.size();
+    const int device = acx_automaton_device(a);
+    acx_wp_t *r = nullptr;
+    PyObject *inputs[3] = {nullptr, nullptr, nullptr};
+    std::vector<int64_t> *row_begin = nullptr;
+    uint64_t row_len_kept = 0;
+    const uint64_t *d_off_kept = nullptr;
+    int rc;
+    if (batch) {
+        BatchInput in;
+        if (!batch_input(hay, offsets, row_length, str_class, device, &in)) return nullptr;
+        const int codepoints = (!in.tensor && str_class && !in.seq.all_ascii) ? 1 : 0;
+        bool no_memory = false;
+        rc = batch_dispatch(
+            device, in,
+            [&](const uint8_t *p, uint64_t len, const uint64_t *off, uint64_t rows) {
+                row_begin = host_row_begins(p, off, rows, codepoints != 0);
+                if (!row_begin) { no_memory = true; return (int)ACX_ENOMEM; }
+                return acx_wordpiece(a, p, len, off, rows, A.cls, pre, pre_len, A.max_word, A.unk_id, 0, codepoints, &r);
+            },
+            [&](const uint8_t *p, uint64_t len, const uint64_t *d_off, uint64_t rows, uint64_t row_len) {
+                row_len_kept = row_len;
+                d_off_kept = d_off;
+                return acx_wordpiece_device(a, p, len, d_off, rows, row_len, A.cls, pre, pre_len, A.max_word, A.unk_id, 0, &r);
+            });
+        if (rc == BAD_OFFSETS) return nullptr;
+        if (no_memory) return PyErr_NoMemory();
+        if (rc == ACX_OK && in.on_device) { inputs[0] = in.cap; in.cap = nullptr; inputs[1] = in.cap_off; in.cap_off = nullptr; }
+    } else {
+        HaystackView v;
+        if (!haystack_view(hay, str_class, true, device, &v)) return nullptr;
+        if (v.cap && capsule_tensor(v.cap).ndim != 1) {
+            PyErr_SetString(PyExc_TypeError, "Only one-dimensional sequences are supported");
+            return nullptr;
+        }
+        const int codepoints = (str_class && !v.is_ascii) ? 1 : 0;
+        rc = single_dispatch(
+            device, v,
+            [&](const uint8_t *p, uint64_t len) {
+                return acx_wordpiece(a, p, len, nullptr, 1, A.cls, pre, pre_len, A.max_word, A.unk_id, 0, codepoints, &r);
+            },
+            [&](const uint8_t *p, uint64_t len) {
+                return acx_wordpiece_device(a, p, len, nullptr, 0, 0, A.cls, pre, pre_len, A.max_word, A.unk_id, 0, &r);
+            });
+        if (rc == ACX_OK && v.on_device) { inputs[0] = v.cap; v.cap = nullptr; }
+    }
+    if (rc != ACX_OK) { delete row_begin; return raise_acx(rc); }
+    OwnerObject *o = new_owner(RT_WORD_PIECES, r, device); // (it frees r when the object cannot be made: the stage is waited for)
+    if (!o) {
+        delete row_begin;
+        for (PyObject *cap : inputs) dlpack_release(cap);
+        return nullptr;
+    }
+    WordPiecesObject *w = static_cast<WordPiecesObject *>(o);
+    w->batch = batch;
+    w->row_begin = row_begin;
+    w->row_length = row_len_kept;
+    w->d_off = d_off_kept;
+    for (int k = 0; k < 3; k++) w->inputs[k] = inputs[k];
+    return reinterpret_cast<PyObject *>(o);
+}
+
+// ---------------------------------------------------------------------------
 // split_rows(data, delimiter=b"\n") -> RowOffsets (acx_split_rows / acx_split_rows_device): a delimited buffer cut into rows.
 // A module function -- no automaton is involved.  A RowOffsets owns the acx_rows_t; .offsets is a Column with the lifetime
 // chain of a MatchColumns' columns, and what the _batch methods take as offsets=.
@@ -2987,6 +3249,24 @@ const PyMethodDef SHARED_METHODS[] = {
      "sequence, or ONE 1-D contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for "
      "filter_batch (split_rows(t).offsets included).  A tensor on the automaton's device stays in HBM, and so does the result: "
      "split_rows -> segment_batch -> label_tokens_batch / filter_batch runs without anything leaving the device."},
+    {"wordpiece", KW(wordpiece<false>),
+     "wordpiece(haystack, *, continuation_prefix=\"##\", separators=None, isolated=None, max_word_bytes=100, unk_id=-1) -> "
+     "WordPieces\n\n[extension] WordPiece tokenization by the dictionary, on the device.  The patterns are the vocabulary as a "
+     "vocab.txt lists it: whole-word entries as they are, continuation entries with the prefix.  The haystack is cut into "
+     "words -- a byte in separators (None: ASCII_WHITESPACE) belongs to no word, a byte in isolated (None: none; "
+     "ASCII_PUNCTUATION is BertTokenizer's) is a word by itself, every other run of bytes is a word -- and every word into "
+     "the entries the automaton's matchkind prefers, the first one looked up as it stands, the following ones behind the "
+     "prefix.  A word longer than max_word_bytes, or one in which a step finds no entry, is ONE piece with unk_id.  With "
+     "MatchKind.LeftmostLongest this is BERT's WordpieceTokenizer over text.split(), the word limit counted in bytes.  The "
+     "ids are pattern indexes.  Both sets are bytes-like; for AhoCorasick they and the prefix may be str, the sets ASCII.  "
+     "AhoCorasick: a str, positions in characters.  BytesAhoCorasick: a bytes-like, or a uint8 __dlpack__ tensor on the "
+     "automaton's device: everything stays in HBM, and the WordPieces keeps the tensor alive."},
+    {"wordpiece_batch", KW(wordpiece<true>),
+     "wordpiece_batch(haystacks, *, continuation_prefix=\"##\", separators=None, isolated=None, max_word_bytes=100, unk_id=-1, "
+     "offsets=None, row_length=None) -> WordPieces\n\n[extension] wordpiece for every row in one call: a word never crosses a "
+     "row, .start and .end hold GLOBAL positions and .row_offsets cuts the pieces by row.  haystacks: a sequence, or ONE 1-D "
+     "contiguous uint8 __dlpack__ tensor cut by exactly one of offsets and row_length, as for segment_batch "
+     "(split_rows(t).offsets included).  A tensor on the automaton's device stays in HBM, and so does the result."},
     {"find_whole_words_as_columns", KW(whole_words<0>),
      "find_whole_words_as_columns(haystack, overlapping=False, *, matchkind=MatchKind.LeftmostLongest, word_bytes=None) -> "
      "MatchColumns\n\n[extension] grep -w for the object's patterns: of all their occurrences those whose neighbour bytes "
@@ -3067,6 +3347,10 @@ PyMethodDef module_methods[] = {
      "_mask_fill(fill, text) -> int: the fill byte mask_all takes from `fill` (text: the str class's rule), or its error"},
     {"_spans_gap", mod_spans_gap, METH_O,
      "_spans_gap(gap) -> int: the gap cover_spans takes from its `gap` argument, or its error"},
+    {"_wordpiece_args", mod_wordpiece_args, METH_VARARGS,
+     "_wordpiece_args(str_class, continuation_prefix=None, separators=None, isolated=None, max_word_bytes=None, unk_id=None) -> "
+     "(cls, prefix, max_word_bytes, unk_id): what wordpiece takes from its keyword arguments -- the 256 byte classes (0 word, "
+     "1 separator, 2 isolated), the prefix's bytes and the two ints -- or their error"},
     {"_snippets_context", mod_snippets_context, METH_O,
      "_snippets_context(context) -> int: the budget find_matches_as_snippets takes from its `context` argument, or its error"},
     {"_mask_per_character", mod_mask_per_character, METH_VARARGS,
@@ -3112,6 +3396,8 @@ extern "C" __attribute__((visibility("default"))) PyObject *PyInit_ahocorasick_r
         "Search for multiple pattern bytes against a single bytes haystack.\n\n"
         "BytesAhoCorasick(patterns, matchkind=MatchKind.Standard, implementation=None, ascii_case_insensitive=False)", BAC_METHODS);
     ok = ok && PyModule_AddObject(m, "ASCII_WORD_BYTES", PyBytes_FromString(ASCII_WORD_BYTES)) == 0;
+    ok = ok && PyModule_AddObject(m, "ASCII_WHITESPACE", PyBytes_FromString(ASCII_WHITESPACE)) == 0;
+    ok = ok && PyModule_AddObject(m, "ASCII_PUNCTUATION", PyBytes_FromString(ASCII_PUNCTUATION)) == 0;
     if (!ok) { Py_DECREF(m); return nullptr; }
     return m;
 }

@@ -43,9 +43,18 @@ void BufCache::release_locked(void *p, int dev) {
     free_list.push_back({p, bytes, dev});
     cached += bytes;
 }
+// Has the event not fired yet?  Every other answer counts as fired.  A query that fails in another way -- the runtime refuses
+// an event whose stream has gone with its handle -- must not stay behind as the thread's sticky last error: the check behind
+// the next kernel launch would report it as that launch's.
+static bool event_pending(hipEvent_t ev) {
+    const hipError_t e = hipEventQuery(ev);
+    if (e == hipErrorNotReady) return true;
+    if (e != hipSuccess) (void)hipGetLastError();
+    return false;
+}
 void BufCache::sweep_locked() {
     for (size_t i = 0; i < deferred.size();) {
-        if (hipEventQuery(deferred[i].ev) == hipErrorNotReady) { i++; continue; }
+        if (event_pending(deferred[i].ev)) { i++; continue; }
         g_events.put(deferred[i].dev, deferred[i].ev);
         release_locked(deferred[i].p, deferred[i].dev);
         if (deferred[i].p2) release_locked(deferred[i].p2, deferred[i].dev);
@@ -102,7 +111,7 @@ void BufCache::put(void *p, int dev, hipEvent_t ev, void *p2) {
     if (!p) { g_events.put(dev, ev); return; }
     std::lock_guard<std::mutex> lk(mu);
     if (ev) {
-        if (hipEventQuery(ev) == hipErrorNotReady) { deferred.push_back({p, p2, dev, ev}); return; }
+        if (event_pending(ev)) { deferred.push_back({p, p2, dev, ev}); return; }
         g_events.put(dev, ev);
     }
     release_locked(p, dev);

@@ -60,6 +60,9 @@ extern "C" {
  *     thirteenth addendum (additive as well): greedy segmentation by the dictionary -- acx_segment / acx_segment_device /
  *     acx_segment_into_device / acx_segment_host and the acx_seg_t accessors (acx_seg_count, _rows, _on_device, _pattern,
  *     _offsets, _row_offsets, _copy, acx_free_seg);
+ *     fourteenth addendum (additive as well): WordPiece tokenization by the dictionary -- acx_wordpiece /
+ *     acx_wordpiece_device / acx_wordpiece_into_device / acx_wordpiece_host and the acx_wp_t accessors (acx_wp_count, _rows,
+ *     _on_device, _id, _start, _end, _first, _row_offsets, _copy, acx_free_wp);
  * 10: acx_replace / acx_replace_device / acx_splice_host and the acx_replaced_t accessors added; acx_path_stats gained [12];
  * 9: acx_path_stats gained [10], [11] (round 6: launches of a context's resident K0; mid-size host haystacks read in place);
  * 8: acx_path_stats gained [9] (round 6: calls repeated with the wide form of the sparse path's post stage);
@@ -1088,6 +1091,86 @@ const int64_t *acx_seg_offsets(const acx_seg_t *r);
 const int64_t *acx_seg_row_offsets(const acx_seg_t *r);
 int acx_seg_copy(const acx_seg_t *r, int which /* ACX_SEG_PATTERN .. */, void *host_dst);
 void acx_free_seg(acx_seg_t *r);
+
+/* ---- wordpiece: WordPiece tokenization by the dictionary -- the data is cut into words by a class per byte value and every
+ * word into vocabulary entries, continuation entries behind the first one; a word that cannot be cut completely is ONE
+ * unknown piece.  No find runs.
+ * THE DEFINITION.  Patterns P_i: the vocabulary exactly as a vocab.txt lists it, whole-word entries as they are, continuation
+ * entries with the prefix.  A continuation prefix C (prefix, prefix_len): any bytes, possibly none.  Data h[0 .. len) cut into
+ * rows (offsets, uniform_len, or neither: one row).  cls[256]: a class per byte VALUE -- ACX_WP_WORD, ACX_WP_SPACE (a
+ * separator: it belongs to no word and yields no piece) or ACX_WP_ALONE (a byte that is a word by itself, such as
+ * punctuation).  M = max_word, 1 <= M <= ACX_WP_MAX_WORD.  unk_id: any int64.  A case-insensitive handle compares pattern
+ * bytes folded; cls is applied to the caller's raw byte.
+ * The words of a row [b, L): every ALONE byte is a word of one byte, every maximal run of WORD bytes inside the row is a word;
+ * a word never crosses a row.  Equivalently p starts a word iff cls[h[p]] != SPACE and p == b, or cls[h[p]] == ALONE, or
+ * cls[h[p - 1]] != WORD.
+ * The pieces of a word [ws, we): (1) we - ws > M: ONE piece (unk_id, ws, we).  (2) Otherwise p = ws; while p < we the
+ * candidates at p are -- at p == ws every (i, e) with e = p + len(P_i) <= we and h[p .. e) == P_i (acx_match_at's candidates
+ * of the anchor (p, we), entries that begin with C included); at p > ws every (i, e) such that P_i begins with C,
+ * len(P_i) > len(C), e = p + len(P_i) - len(C) <= we and h[p .. e) == P_i[len(C):] (a pattern equal to C itself is never a
+ * continuation piece).  One candidate is picked by the handle's own match kind exactly as for acx_match_at: Standard the
+ * smallest e, then the smallest i; LeftmostFirst the smallest i; LeftmostLongest the largest e, then the smallest i.  No
+ * candidate: the WHOLE word is ONE piece (unk_id, ws, we), the pieces found before it are withdrawn.  Otherwise the piece is
+ * (i, p, e) and p = e.  With LeftmostLongest and whitespace as the separators this is BERT's WordpieceTokenizer.tokenize
+ * applied to text.split(), except that the word limit is counted in bytes.
+ * THE RESULT, four columns of T entries in data order: id (int64), start and end (int64 GLOBAL byte positions, start strictly
+ * ascending), first (uint8: 1 on the first piece of its word); and row_offsets -- rows + 1 int64 words, entry r the number of
+ * pieces that begin before row r does, the last one T.  There is no overlapping form.
+ * acx_wordpiece: host data and host offsets (n_hay + 1 from 0 to len, or NULL: one haystack), a host result.  The data is
+ * staged to the device, the same kernels run and the block comes back: there is no CPU matching route.  codepoints != 0:
+ * start and end come back as CHARACTER indexes of UTF-8 data, converted on the host.
+ * acx_wordpiece_device: everything in HBM on the automaton's device (d_offsets / uniform_len as for acx_find_device; neither:
+ * one row).  It runs on the handle's context and stream and returns when T is known -- 8 bytes cross the bus; every accessor
+ * waits for the kernels, and d_hay and d_offsets must stay valid until then.  Device offsets are the caller's word: wrong
+ * ones give wrong pieces, never a read outside the data or a write outside the result.  cls and prefix are host memory,
+ * read before the call returns.
+ * acx_wordpiece_into_device: the raw synchronous form -- d_id, d_start, d_end (cap int64 words each, 8-byte aligned), d_first
+ * (cap bytes) and d_row_offsets (rows + 1 int64 words) in HBM on the automaton's device.  *n_pieces is always T; the five are
+ * written only when cap != 0 and T <= cap, exactly T, T, T, T and rows + 1 entries, and are complete when it returns.
+ * cap = 0 runs the count pass alone: nothing is written and the five may be NULL.
+ * acx_wordpiece_host: host memory only, no device -- the definition walked over the compiled tables (first_child, in_byte,
+ * own_off, own_pid of acx_host_tables), for match_kind's rule.  Not a matching path of the library: it documents the pieces
+ * and checks the kernels.  Same outputs and the same cap rule as the raw form.
+ * Refusals, before any device work and in this order: ACX_EINVAL -- unknown flags (none is defined), a cls value above 2,
+ * max_word outside 1 .. ACX_WP_MAX_WORD, host offsets that do not rise from 0 to len; ACX_ETOOBIG -- more than 2^31 - 1 tiles
+ * of 4096 bytes, or 2^38 rows.  Pattern length is not limited: a pattern longer than the word cannot match.  A prefix whose
+ * path is not in the trie is valid: no continuation ever matches.  An empty part still has a valid, non-null address. */
+#define ACX_WP_WORD 0         /* cls: the classes of the byte values */
+#define ACX_WP_SPACE 1
+#define ACX_WP_ALONE 2
+#define ACX_WP_MAX_WORD 1024u /* the largest max_word */
+#define ACX_WP_ID 0           /* acx_wp_copy: the parts of a result */
+#define ACX_WP_START 1
+#define ACX_WP_END 2
+#define ACX_WP_FIRST 3
+#define ACX_WP_ROW_OFFSETS 4
+typedef struct acx_wp acx_wp_t;
+int acx_wordpiece(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one haystack */,
+                  uint64_t n_hay, const uint8_t *cls /* 256 */, const uint8_t *prefix, uint64_t prefix_len, uint64_t max_word,
+                  int64_t unk_id, uint32_t flags, int codepoints, acx_wp_t **out);
+int acx_wordpiece_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                         uint64_t uniform_len, const uint8_t *cls /* 256 */, const uint8_t *prefix, uint64_t prefix_len,
+                         uint64_t max_word, int64_t unk_id, uint32_t flags, acx_wp_t **out);
+int acx_wordpiece_into_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
+                              uint64_t uniform_len, const uint8_t *cls /* 256 */, const uint8_t *prefix, uint64_t prefix_len,
+                              uint64_t max_word, int64_t unk_id, uint32_t flags, uint64_t cap, int64_t *d_id, int64_t *d_start,
+                              int64_t *d_end, uint8_t *d_first, int64_t *d_row_offsets, uint64_t *n_pieces);
+int acx_wordpiece_host(const acx_host_automaton_t *h, const uint8_t *hay, uint64_t len, const uint64_t *offsets /* NULL: one row */,
+                       uint64_t n_hay, const uint8_t *cls /* 256 */, const uint8_t *prefix, uint64_t prefix_len, uint64_t max_word,
+                       int64_t unk_id, uint32_t flags, int match_kind, uint64_t cap, int64_t *id, int64_t *start, int64_t *end,
+                       uint8_t *first, int64_t *row_offsets, uint64_t *n_pieces);
+uint64_t acx_wp_count(const acx_wp_t *r); /* T: the pieces                                      */
+uint64_t acx_wp_rows(const acx_wp_t *r);  /* the rows (one haystack that is no batch: 1)        */
+int acx_wp_on_device(const acx_wp_t *r);  /* 1: the columns are in HBM, 0: host memory          */
+/* host or device pointer by acx_wp_on_device (T int64 words three times, T bytes, rows + 1 int64 words); waits for the device
+ * stage.  NULL: the wait failed.  Valid until acx_free_wp. */
+const int64_t *acx_wp_id(const acx_wp_t *r);
+const int64_t *acx_wp_start(const acx_wp_t *r);
+const int64_t *acx_wp_end(const acx_wp_t *r);
+const uint8_t *acx_wp_first(const acx_wp_t *r);
+const int64_t *acx_wp_row_offsets(const acx_wp_t *r);
+int acx_wp_copy(const acx_wp_t *r, int which /* ACX_WP_ID .. */, void *host_dst);
+void acx_free_wp(acx_wp_t *r);
 
 /* ---- measurement hooks (HIP events on the library's stream) ---- */
 /* on = 0: off; 1: every call carries the event pair around its scan kernel; N > 1: every N-th call of
