@@ -129,8 +129,14 @@ class Oracle:
         arr = self._run(lib().aco_find_str, b, extra=(1 if overlapping else 0,))
         return [tuple(int(x) for x in r) for r in arr]
 
-    def count(self, hay) -> int:
+    def count(self, hay, overlapping: bool = False) -> int:
+        """how many rows find_raw would give, without building them"""
         h = _as_u8(hay)
+        if overlapping:
+            r = lib().aco_find_overlapping_iter(self._h, h.ctypes.data if len(h) else None, len(h), None, 0)
+            if r < 0:
+                raise ValueError("overlapping search unsupported for this match kind")
+            return int(r)
         return int(lib().aco_count_iter(self._h, h.ctypes.data, len(h)))
 
 

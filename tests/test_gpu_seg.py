@@ -3,7 +3,8 @@ raw form at the seams of its kernels -- data lengths around the tile, the fan of
 chains that never converge, so that every entry offset of a tile is really taken; matches that cross a tile boundary by one
 byte and by E - 1 bytes and end exactly on it; the longest pattern the stage takes; row starts at both ends of a tile and runs
 of empty rows across a boundary and at the end of the data; the three row cuts; tiles in which no byte, every byte and one
-byte per wave survives the first-byte test; a 4-byte character across a boundary; every alignment of the data -- with guard
+byte per wave survives the first-byte test; a node at depth 2 with AT_PROBE children and with one more, at every outcome of
+at_child's probe and search; a root with 256 children and an entry that stands four times in the list; a 4-byte character across a boundary; every alignment of the data -- with guard
 bytes around all three outputs and every input verified unwritten; the kinds and routes through the C ABI, against
 acx_segment_host and the definition; the Python methods with bytes, str (characters), sequences and tensors in HBM, torch as the
 consumer and label_tokens_batch as the next stage.  Expected values come from the loop of the definition restated below in
@@ -312,6 +313,70 @@ def test_raw_no_byte_every_byte_and_one_byte_per_wave_survive_the_first_byte():
         alone = bytearray(b"z" * n)
         alone[TILE - 1] = ord("a")  # a survivor whose walk finds nothing: the unknown unit behind the walk
         check_raw([b"ab"], kind, bytes(alone), what="a walk without a match")
+
+
+PROBE = hip_constants("at.hpp", ("AT_PROBE",))["AT_PROBE"]  # children up to which at_child probes a node linearly
+
+
+def deep_node(m, head=b"qw"):
+    """patterns that put a node with exactly m children at depth len(head) -- child bytes 0x30, 0x34, .. -- and behind every
+    child a short and a long pattern, in either index order: the three kinds pick differently, and all of them search the node"""
+    pats = []
+    for k in range(m):
+        c = head + bytes([0x30 + 4 * k])
+        pats += [c + b"xy", c] if k % 2 else [c, c + b"xy"]
+    return pats
+
+
+def deep_probes(m):
+    """a byte for the node's first, a middle and its last child; one below the first, between two and above the last"""
+    child = [0x30 + 4 * k for k in range(m)]
+    return [child[0], child[m // 2], child[-1]], [child[0] - 1, child[1] + 1, child[-1] + 1]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("m", [PROBE, PROBE + 1])
+def test_raw_a_node_at_depth_2_with_probe_and_one_more_children(kind, m):
+    """at_child below depth 1 inside k_seg: the linear probe at AT_PROBE children, the binary search at one more -- every
+    outcome of either, and one walk that reads the node's byte from the last byte of a tile and one from the next tile"""
+    pats = deep_node(m)
+    hits, misses = deep_probes(m)
+    hay = bytearray(b"." * (2 * TILE + 40))
+    for k, b in enumerate(hits + misses):
+        hay[3 + 7 * k:8 + 7 * k] = b"qw" + bytes([b]) + b"xy"
+    hay[TILE - 3:TILE + 2] = b"qw" + bytes([hits[2]]) + b"xy"          # the node's byte is the tile's last one
+    hay[2 * TILE - 2:2 * TILE + 3] = b"qw" + bytes([hits[1]]) + b"xy"  # ... and the next tile's first one
+    want = check_raw(pats, kind, bytes(hay), what=(m, "one row"))
+    at = {int(p): int(i) for i, p in zip(want[0], want[1][:-1])}
+    for k, b in enumerate(hits):
+        child = (b - 0x30) // 4
+        short, long_ = (2 * child + 1, 2 * child) if child % 2 else (2 * child, 2 * child + 1)
+        assert at[3 + 7 * k] == {STD: short, LF: min(short, long_), LL: long_}[kind], (m, k)
+    assert [at[3 + 7 * k] for k in range(3, 6)] == [-1, -1, -1] and at[TILE - 3] >= 0 and at[2 * TILE - 2] >= 0
+    assert (want[0] >= 0).sum() == 5
+    check_raw(pats, kind, bytes(hay), offsets=[0, 8, TILE - 1, TILE, 2 * TILE, len(hay)], what=(m, "rows"))  # rows cut both tile walks short
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_raw_a_root_with_256_children_and_an_entry_four_times(kind):
+    """every first byte survives the first-byte test; "dup!" stands four times in the pattern list (own1 says "many": the first of
+    the state's list is read) behind an extension of it with a lower index: the lowest of the four comes back under every kind"""
+    fan = [bytes([b]) + b"z" for b in range(256)]
+    pats = fan[:100] + [b"dup!x"] + fan[100:200] + [b"dup!", b"dup!"] + fan[200:] + [b"dup!", b"dup!"]
+    low = pats.index(b"dup!")
+    assert pats.count(b"dup!") == 4 and len({p[0] for p in pats}) == 256
+    hay = bytearray(b"".join(bytes([b]) + b"z" for b in (0, 1, 0x64, 0x7F, 0x80, 0xFF)) + b"dup!dup!?dup!xdu" + bytes(range(256)))
+    hay += b"." * (TILE - 2 - len(hay)) + b"dup!dup!"
+    want = check_raw(pats, kind, bytes(hay), what="256 children")
+    at = {int(p): int(i) for i, p in zip(want[0], want[1][:-1])}
+    assert at[12] == low and at[16] == low and at[TILE - 2] == low and at[TILE + 2] == low
+    assert at[21] == {STD: low, LF: pats.index(b"dup!x"), LL: pats.index(b"dup!x")}[kind]
+    assert [at[2 * k] for k in range(6)] == [pats.index(bytes([b]) + b"z") for b in (0, 1, 0x64, 0x7F, 0x80, 0xFF)]
+    a = capi.Automaton(pats, kind)
+    try:
+        check_raw(pats, kind, bytes(hay), automaton=a, offsets=[0, 14, 15, TILE, len(hay)], what="256 children, rows")
+    finally:
+        a.close()
 
 
 @pytest.mark.parametrize("utf8", [False, True])

@@ -2,7 +2,9 @@
 wordpiece_batch): the raw form at the seams of its kernels -- data lengths around the tile; words that start on a tile's last
 byte, end on its end, continue into the next tile or start on its first byte; words longer than a tile, whose end comes from
 the carry, ended by a separator and by a row start; tiles with no word, a word per byte and a word per wave; words of M and
-M + 1 bytes, M = WP_MAX_WORD, a pattern longer than M; row starts at both ends of a tile, runs of empty rows, the three row
+M + 1 bytes, M = WP_MAX_WORD, a pattern longer than M; a node at depth 2 -- under the root and under C's node -- with AT_PROBE
+children and with one more, at every outcome of at_child's probe and search; C's node with AT_PROBE, one more and 256 children;
+a root with 256 children and an entry that stands four times in the list; row starts at both ends of a tile, runs of empty rows, the three row
 cuts; every alignment of the data; caps; more tiles than one block of the library's scan -- with 64 guard bytes around all
 five outputs and every input verified unwritten; the kinds and routes through the C ABI against acx_wordpiece_host and the
 definition; the Python methods with bytes, str (characters), sequences and tensors in HBM, torch as the consumer.
@@ -220,6 +222,105 @@ def test_raw_words_of_m_and_m_plus_one_bytes(kind, M):
     for p, w in words:
         one = [x for x in got if x[1] == p and x[3] == 1]
         assert len(one) == 1 and (one[0][0] == -9) == (len(w) > M), (p, len(w), one)
+
+
+PROBE = hip_constants("at.hpp", ("AT_PROBE",))["AT_PROBE"]  # children up to which at_child probes a node linearly
+
+
+def deep_node(m, head):
+    """entries that put a node with exactly m children at depth len(head) -- child bytes 0x30, 0x34, .. -- and behind every
+    child a short and a long entry, in either index order: the three kinds pick differently, and all of them search the node"""
+    pats = []
+    for k in range(m):
+        c = head + bytes([0x30 + 4 * k])
+        pats += [c + b"xy", c] if k % 2 else [c, c + b"xy"]
+    return pats
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("m", [PROBE, PROBE + 1])
+def test_raw_a_node_at_depth_2_with_probe_and_one_more_children(kind, m):
+    """at_child below depth 1 inside k_wp, on the first piece's walk (the node of "qw") and on a continuation's (the node of
+    "##qw", two levels below C's): the linear probe at AT_PROBE children, the binary search at one more, at the first, a middle
+    and the last child, below, between and above them; one word reads the node's byte from the last byte of a tile, one from the
+    next tile"""
+    vocab = deep_node(m, b"qw") + [b"a", b"##xy"] + deep_node(m, b"##qw")
+    child = [0x30 + 4 * k for k in range(m)]
+    hits, misses = [child[0], child[m // 2], child[-1]], [child[0] - 1, child[1] + 1, child[-1] + 1]
+    words = [(3 + 16 * k, b"qw" + bytes([b]) + b"xy") for k, b in enumerate(hits + misses)]
+    words += [(11 + 16 * k, b"aqw" + bytes([b]) + b"xy") for k, b in enumerate(hits + misses)]
+    words += [(TILE - 3, b"qw" + bytes([hits[2]]) + b"xy"), (2 * TILE - 2, b"qw" + bytes([hits[1]]) + b"xy"),
+              (3 * TILE - 4, b"aqw" + bytes([hits[0]]) + b"xy"), (4 * TILE - 3, b"aqw" + bytes([hits[2]]) + b"xy")]
+    want = check_raw(vocab, kind, planted(4 * TILE + 40, words), what=m)
+    got = pieces(want)
+    n = 2 * m  # (the entries of "qw": 0 .. 2m - 1; "a", "##xy"; those of "##qw" from 2m + 2)
+    for k, b in enumerate(hits):
+        c = (b - 0x30) // 4
+        short, long_ = (2 * c + 1, 2 * c) if c % 2 else (2 * c, 2 * c + 1)
+        whole = [(long_, 0, 5)] if kind == LL or (kind == LF and long_ < short) else [(short, 0, 3), (n + 1, 3, 5)]
+        p = 3 + 16 * k
+        assert [x for x in got if p <= x[1] < p + 5] == [(i, p + s, p + e, int(s == 0)) for i, s, e in whole], (m, k)
+        p = 11 + 16 * k
+        assert [x for x in got if p <= x[1] < p + 6] == [(n, p, p + 1, 1)] + [(i + n + 2 if i < n else i, p + 1 + s, p + 1 + e, 0) for i, s, e in whole], (m, k)
+    for k in range(3, 6):
+        assert (-1, 3 + 16 * k, 8 + 16 * k, 1) in got and (-1, 11 + 16 * k, 17 + 16 * k, 1) in got, (m, k)
+    assert not any(x[0] == -1 and x[1] > TILE - 8 for x in got) and sum(x[3] for x in got) == 16
+
+
+def fan_of(prefix, children):
+    return [prefix + bytes([b]) for b in children]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("m", [PROBE, PROBE + 1, 256])
+def test_raw_the_node_of_the_prefix_with_probe_one_more_and_256_children(kind, m):
+    """cont_next is filled by 256 at_child calls on C's node: a vocabulary with C + b for m byte values b -- every byte value
+    whose class is WORD among them when m == 256 -- and a word whose every continuation byte takes a different child"""
+    word_bytes = [b for b in range(256) if CLS[b] == wpd.WORD]
+    children = list(range(256)) if m == 256 else [0x31 + 5 * k for k in range(m)]
+    assert set(children) <= set(word_bytes) or m == 256
+    vocab = [b"a", b"##"] + fan_of(b"##", children)
+    inside = [b for b in children if CLS[b] == wpd.WORD]
+    every = b"a" + bytes(inside)                      # every continuation byte takes a different child
+    back = b"a" + bytes(inside[::-1])
+    edges = [b"a" + bytes([inside[0], inside[len(inside) // 2], inside[-1]])]
+    misses = [] if m == 256 else [b"a" + bytes([children[0] - 1]), b"a" + bytes([children[1] + 1]), b"a" + bytes([children[-1] + 1]),
+                                  b"a" + bytes([children[0], children[-1] + 1])]
+    words, p = [], 5
+    for w in [every, back] + edges + misses + [b"##", b"a##"]:
+        words.append((p, w))
+        p += len(w) + 2
+    words += [(TILE - 2, edges[0]), (2 * TILE - 1, edges[0])]
+    want = check_raw(vocab, kind, planted(2 * TILE + 30, words), M=MAX_WORD, what=m)
+    got = pieces(want)
+    assert [x[0] for x in got if 5 <= x[1] < 5 + len(every)] == [0] + [2 + children.index(b) for b in inside], m
+    assert sum(x[0] == -1 for x in got) == len(misses) + (m != 256) and (1, words[-4][0], words[-4][0] + 2, 1) in got, m
+    a3 = words[-3][0]  # "a##": "a", then C + "#" twice -- when "#" is a child of C's node
+    assert [x for x in got if a3 <= x[1] < a3 + 3] == ([(0, a3, a3 + 1, 1), (2 + 35, a3 + 1, a3 + 2, 0), (2 + 35, a3 + 2, a3 + 3, 0)] if m == 256
+                                                       else [(-1, a3, a3 + 3, 1)])
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_raw_a_root_with_256_children_and_an_entry_four_times(kind):
+    """every first byte of a word has a depth-1 state; "dup" and "##dup" stand four times each in the vocabulary (own1 says
+    "many": the first of the state's list is read) behind an extension of each with a lower index: the lowest of the four comes
+    back under every kind"""
+    fan = [bytes([b]) + b"z" for b in range(256)]
+    vocab = fan[:100] + [b"dup!", b"##dup!"] + fan[100:200] + [b"dup", b"##dup", b"dup", b"##dup"] + fan[200:] + [b"dup", b"##dup", b"dup", b"##dup"]
+    assert vocab.count(b"dup") == 4 == vocab.count(b"##dup") and len({v[0] for v in vocab}) == 256
+    cls = wpd.classes(b" \n")
+    low, low_c = vocab.index(b"dup"), vocab.index(b"##dup")
+    words = [(3, b"dup"), (8, b"dupdup"), (16, b"dup!dup!"), (26, b"dupdupdup"), (40, b"\x00z"), (44, b"\xffz"), (48, b"\x80z\x7fz"),
+             (TILE - 2, b"dupdup"), (2 * TILE - 4, b"dupdup")]
+    want = check_raw(vocab, kind, planted(2 * TILE + 20, words), cls, what="256 children")
+    got = pieces(want)
+    assert [x for x in got if 3 <= x[1] < 14] == [(low, 3, 6, 1), (low, 8, 11, 1), (low_c, 11, 14, 0)]
+    assert [x[0] for x in got if 26 <= x[1] < 35] == [low, low_c, low_c]
+    assert [x for x in got if x[1] >= TILE - 2] == [(low, TILE - 2, TILE + 1, 1), (low_c, TILE + 1, TILE + 4, 0),
+                                                   (low, 2 * TILE - 4, 2 * TILE - 1, 1), (low_c, 2 * TILE - 1, 2 * TILE + 2, 0)]
+    # "dup!dup!": Standard stops at "dup" and has no "##!" to go on with; the others take the extension, whose index is lower
+    assert [x[0] for x in got if 16 <= x[1] < 24] == ([-1] if kind == STD else [vocab.index(b"dup!"), vocab.index(b"##dup!")])
+    assert (0, 40, 42, 1) in got and (vocab.index(b"\xffz"), 44, 46, 1) in got and (-1, 48, 52, 1) in got
 
 
 @pytest.mark.parametrize("kind", KINDS)

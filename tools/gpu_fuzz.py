@@ -10,9 +10,14 @@ usage: gpu_fuzz.py [seconds] [seed]   -- prints one line per case, exits non-zer
        gpu_fuzz.py summary [n] [seed] [--plan-only]   -- the summaries (plan_summary / run_summary below): acx_summarize on the
        host and the device route, batches, acx_summarize_device in its three forms at odd and even pointer residues, both
        build flags, every match kind, overlapping counts, code points; each against the oracle's matches reduced in Python.
+       gpu_fuzz.py walk [n] [seed] [--plan-only]   -- the anchored walkers (plan_walk / run_walk below): match_at, segment and
+       wordpiece through every way in (host input, one haystack, a uniform and a ragged cut in HBM, row starts, the raw
+       *_into_device forms), every match kind, both build flags, forced kernels, compressed-only handles, pointer residues;
+       each against reference_walk -- the oracle's overlapping rows and numpy -- and so is the host form over the same inputs.
 tests/test_gpu_fuzz.py runs a bounded, seeded slice of it (fuzz(budget, seed, max_size_log2)) under -m gpu,
 tests/test_gpu_fuzz_surface.py a fixed number of surface cases; tests/test_fuzz_plan_cpu.py checks what that plan covers;
-tests/test_gpu_summary.py a slice of the summary cases, tests/test_summary_cpu.py what their plan covers.
+tests/test_gpu_summary.py a slice of the summary cases, tests/test_summary_cpu.py what their plan covers;
+tests/test_gpu_fuzz_walk.py runs the walk plan, tests/test_fuzz_walk_plan_cpu.py checks its reference and what it covers.
 UTF-8 cases only ever hold patterns made of whole characters (a str pattern cannot end inside one:
 the precondition of codepoints = 1, include/acx.h)."""
 import os, random, sys, time
@@ -604,7 +609,587 @@ def run_summary(cases):
 SUMMARY_N, SUMMARY_SEED = 72, 20261017  # what tests/test_gpu_summary.py runs a slice of and tests/test_summary_cpu.py checks
 
 
+# ---------------------------------------------------------------------------
+# the anchored walkers (match_at, segment, wordpiece): a plan of their own, and a reference from the oracle's overlapping rows
+# ---------------------------------------------------------------------------
+WALK_OPS = ("match_at_host", "match_at_device_one", "match_at_device_uniform", "match_at_device_ragged", "match_at_rows_uniform",
+            "match_at_rows_ragged", "segment_host", "segment_device_one", "segment_device_uniform", "segment_device_ragged",
+            "wordpiece_host", "wordpiece_device_one", "wordpiece_device_uniform", "wordpiece_device_ragged")
+WALK_SIZE_LOG2 = SURFACE_SIZE_LOG2  # the data of a walk case: at most 2^20 bytes
+WALK_MAX_WORDS = (1, 7, 100, 1024)  # (the last one is WP_MAX_WORD, wp.hpp)
+WP_WORD, WP_SPACE, WP_ALONE = 0, 1, 2
+WALK_COLUMNS = {"match_at": ("pattern", "end", "row_offsets"), "segment": ("pattern", "offsets", "row_offsets"),
+                "wordpiece": ("id", "start", "end", "first", "row_offsets")}
+
+
+def walk_feature(op: str) -> str:
+    return "match_at" if op.startswith("match_at") else op.split("_")[0]
+
+
+def _walk_shape(op: str, host_rows: bool) -> str:
+    """_cut()'s name for the rows of the case"""
+    if op.endswith("_host"):
+        return "find_batch" if host_rows else "find"
+    return "find_device_" + op.rsplit("_", 1)[1]
+
+
+class _Cands:
+    """candidates (pattern, start, end) of every start at once, ordered by (start, end, pattern); lo[p] .. lo[p + 1]: those of p"""
+
+    def __init__(self, pid, s, e, n):
+        o = np.lexsort((pid, e, s))
+        self.pid, self.s, self.e, self.n = pid[o], s[o], e[o], n
+        self.lo = np.searchsorted(self.s, np.arange(n + 2))
+
+    def keep(self, mask):
+        return _Cands(self.pid[mask], self.s[mask], self.e[mask], self.n)
+
+    def pick(self, kind):
+        """the candidate the kind keeps of every start -> (pattern, end) over 0 .. n, -1 where there is none: one lexsort and
+        the first of every group of one start"""
+        pid, s, e = self.pid, self.s, self.e
+        o = np.lexsort({0: (pid, e, s), 1: (pid, s), 2: (pid, -e, s), "lowest": (pid, s)}[kind])
+        first = np.ones(len(o), dtype=bool)
+        first[1:] = s[o][1:] != s[o][:-1]
+        o = o[first]
+        bp, be = np.full(self.n + 1, -1, np.int64), np.full(self.n + 1, -1, np.int64)
+        bp[s[o]], be[s[o]] = pid[o], e[o]
+        return bp, be
+
+    def stepper(self, kind):
+        """-> step(p, limit): the candidate of start p among those that end at or before limit, or None -- for the chains,
+        whose limit (a word's end) differs from start to start; plain lists and one bisection per step"""
+        from bisect import bisect_right
+        lo, E, PID, m = self.lo.tolist(), self.e.tolist(), self.pid.tolist(), len(self.pid)
+        at = None
+        if kind == 2 and m:  # the largest end: the first of the last (start, end) group
+            new = np.ones(m, dtype=bool)
+            new[1:] = (self.s[1:] != self.s[:-1]) | (self.e[1:] != self.e[:-1])
+            at = np.maximum.accumulate(np.where(new, np.arange(m), 0)).tolist()
+        elif kind == 1 and m:  # the smallest pattern so far within the start: a running minimum that starts again per start
+            new = np.ones(m, dtype=bool)
+            new[1:] = self.s[1:] != self.s[:-1]
+            down = (int(new.sum()) - np.cumsum(new)) * (int(self.pid.max()) + 1)  # (later starts lie lower: no minimum carries over)
+            at = (np.minimum.accumulate((self.pid + down) * (m + 1) + np.arange(m)) % (m + 1)).tolist()
+
+        def step(p, limit):
+            a, b = lo[p], lo[p + 1]
+            if a == b or E[a] > limit:
+                return None
+            k = a if at is None else at[bisect_right(E, limit, a, b) - 1]
+            return PID[k], E[k]
+        return step
+
+
+def _walk_ctx(c: dict, limit: int = SURFACE_ROWS):
+    """the data of the case, its row bounds and the candidate sets C(p, L) of at.hpp's definition -- or None when the oracle
+    would give more than `limit` rows"""
+    fold = (lambda b: b.translate(FOLD)) if c["ci"] else (lambda b: b)
+    whole = b"".join(c["hays"])
+    n = len(whole)
+    bounds = np.cumsum([0] + [len(h) for h in c["hays"]]).astype(np.int64)
+    data, rows = fold(whole), 0
+
+    def cands(pats, index=None):
+        nonlocal rows
+        if not pats or rows > limit:
+            return _Cands(*(np.zeros(0, np.int64),) * 3, n)
+        o = Oracle([fold(p) for p in pats], 0, KIND_DFA)
+        rows += o.count(data, overlapping=True)
+        if rows > limit:
+            return _Cands(*(np.zeros(0, np.int64),) * 3, n)
+        w = o.find_raw(data, overlapping=True).astype(np.int64).reshape(-1, 3)
+        pid, s, e = w[:, 0], w[:, 1], w[:, 2]
+        if index is not None:
+            pid = np.asarray(index, dtype=np.int64)[pid]
+        keep = e <= bounds[np.searchsorted(bounds, s, side="right")]  # (the row of s is the LAST one that begins at or before it)
+        return _Cands(pid[keep], s[keep], e[keep], n)
+
+    ctx = {"whole": whole, "n": n, "bounds": bounds, "all": cands(c["pats"])}
+    if walk_feature(c["op"]) == "wordpiece":
+        C = fold(c["prefix"])
+        index = [i for i, p in enumerate(c["pats"]) if fold(p).startswith(C) and len(p) > len(C)]
+        ctx["cont"] = cands([c["pats"][i][len(C):] for i in index], index)
+    ctx["rows"] = rows
+    return None if rows > limit else ctx
+
+
+def _utf8_units(raw, limit):
+    """seg.hpp's unknown unit of every position, from the raw bytes: the length the lead byte announces, shortened to the
+    continuation bytes that follow inside the row (limit: the row end of every position)"""
+    n = len(raw)
+    want = np.where((raw >= 0xC0) & (raw <= 0xDF), 2, np.where((raw >= 0xE0) & (raw <= 0xEF), 3, np.where((raw >= 0xF0) & (raw <= 0xF7), 4, 1)))
+    cont = np.concatenate([(raw >= 0x80) & (raw <= 0xBF), np.zeros(4, dtype=bool)])
+    p = np.arange(n)
+    u, run = np.ones(n, np.int64), np.ones(n, dtype=bool)
+    for k in (1, 2, 3):
+        run = run & cont[p + k] & (p + k < limit) & (want > k)
+        u += run
+    return u
+
+
+def reference_walk(c: dict, positions="own", ctx=None) -> dict:
+    """What a walk case must give -- the columns of WALK_COLUMNS[feature] -- without capi and without a GPU.
+
+    The candidate sets C(p, L) of at.hpp come from ONE Standard oracle over the (folded) patterns: its overlapping rows over
+    the (folded) data, grouped by start, and restricted to those that end inside the row of their start.  The overlapping
+    search reports, at a match state, EVERY pattern of the state's list in index order (ac_oracle.c, aco_find_overlapping_iter;
+    add_match appends at the tail) -- so of identical patterns each one has a row of its own, with its own index, (start, end)
+    equal.  Nothing needs to be added for them: the overlapping form lists them all by (end, index), and the picks order by
+    index last, so the lowest index of identical patterns wins.
+      match_at   the pick of the kind per start (a lexsort and the first of each start's group), read at the anchors; a
+                 position outside the data, or an empty row, has none; FULL keeps end == L first.  Row starts: end is a length.
+      segment    the same pick per start gives every position its step -- the match length, or seg.hpp's unknown unit from the
+                 RAW bytes -- and the chain is a plain loop, one step per piece.
+      wordpiece  the words from cls as wp.hpp states them (vectorised); at a word's start the candidates of the whole
+                 vocabulary, behind it those of a second oracle over the entries that begin with C and are longer, C stripped,
+                 mapped back to their index (an empty C: every entry), both restricted to the word's end; a word longer than M
+                 or with a step without a candidate is ONE unknown piece.
+    positions: the case's own, or another array (the host form refuses those outside the data)."""
+    ctx = ctx or _walk_ctx(c, 1 << 62)
+    n, bounds, cd, feature = ctx["n"], ctx["bounds"], ctx["all"], walk_feature(c["op"])
+    if feature == "match_at":
+        pos = c["positions"] if isinstance(positions, str) else positions
+        if pos is None:  # the rows are the anchors
+            p, L = bounds[:-1], bounds[1:]
+            valid, local = L > p, p
+        else:
+            pos = np.asarray(pos, dtype=np.int64)
+            valid = (pos >= 0) & (pos < n)
+            p = np.where(valid, pos, n)
+            local = 0
+        if c["full"]:
+            cd = cd.keep(cd.e == bounds[np.searchsorted(bounds, cd.s, side="right")])
+        if not c["ov"]:
+            bp, be = cd.pick("lowest" if c["full"] else c["mk"])
+            pat = np.where(valid, bp[p], -1)
+            return {"pattern": pat, "end": np.where(pat >= 0, be[p] - local, -1)}
+        k = np.where(valid, cd.lo[p + 1] - cd.lo[p], 0)
+        ro = np.concatenate([[0], np.cumsum(k)]).astype(np.int64)
+        at = np.repeat(cd.lo[p], k) + np.arange(ro[-1]) - np.repeat(ro[:-1], k)
+        return {"pattern": cd.pid[at], "end": cd.e[at] - (np.repeat(local, k) if pos is None else 0), "row_offsets": ro}
+    raw = np.frombuffer(ctx["whole"], dtype=np.uint8)
+    if feature == "segment":
+        bp, be = cd.pick(c["mk"])
+        at = np.arange(n)
+        limit = bounds[np.searchsorted(bounds, at, side="right")] if n else at
+        unit = _utf8_units(raw, limit) if c["utf8"] else np.ones(n, np.int64)
+        step = np.where(bp[:n] >= 0, be[:n] - at, unit).tolist()
+        starts, p = [], 0
+        while p < n:
+            starts.append(p)
+            p += step[p]
+        starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+        return {"pattern": bp[starts], "offsets": np.concatenate([starts, [n]]).astype(np.int64),
+                "row_offsets": np.searchsorted(starts, bounds, side="left").astype(np.int64)}
+    cls, M, unk = np.asarray(c["cls"], dtype=np.uint8), c["max_word"], c["unk_id"]
+    k = cls[raw]
+    row_start = np.zeros(n + 1, dtype=bool)
+    row_start[bounds] = True
+    row_start = row_start[:n]
+    start = (k != WP_SPACE) & (row_start | (k == WP_ALONE) | ~np.concatenate([[False], k[:-1] == WP_WORD]))
+    nextb = np.concatenate([np.minimum.accumulate(np.where((k != WP_WORD) | row_start, np.arange(n), n)[::-1])[::-1], [n]])
+    ws = np.flatnonzero(start)
+    we = np.where(k[ws] == WP_ALONE, ws + 1, nextb[ws + 1])
+    first_step, next_step = cd.stepper(c["mk"]), ctx["cont"].stepper(c["mk"])
+    out = []
+    for a, b in zip(ws.tolist(), we.tolist()):
+        pieces, p = [], a
+        if b - a <= M:
+            r = first_step(a, b)
+            while r is not None:
+                pieces.append((r[0], p, r[1], int(p == a)))
+                p = r[1]
+                if p == b:
+                    break
+                r = next_step(p, b)
+        out += pieces if p == b else [(unk, a, b, 1)]
+    col = lambda j, t: np.asarray([x[j] for x in out], dtype=t).reshape(-1)
+    ref = {"id": col(0, np.int64), "start": col(1, np.int64), "end": col(2, np.int64), "first": col(3, np.uint8)}
+    ref["row_offsets"] = np.searchsorted(ref["start"], bounds, side="left").astype(np.int64)
+    return ref
+
+
+def _wp_vocabulary(pats, alpha: bytes, utf8: bool):
+    """-> (the vocabulary, C, whether C is an entry): make_case()'s patterns with the drawn prefix in front of a drawn half"""
+    how = rng.choice(["##", "", "@", "own", "none"])
+    if how == "own":
+        C = rng.choice(["é", "☃", "a☃"]).encode() if utf8 else bytes(rng.choice(alpha) for _ in range(2))
+    elif how == "none":
+        C = next(x for x in (b"\x01\x02", b"~^", b"\x7f\x00\x7f", b"\x02\x01\x7f\x01") if not any(p.translate(FOLD).startswith(x) for p in pats))
+    else:
+        C = how.encode()
+    vocab = [C + p if how != "none" and rng.random() < 0.5 else p for p in pats]
+    own = bool(C) and how != "none" and rng.random() < 0.35
+    if own:
+        vocab.append(C)
+    return vocab, C, own
+
+
+def _wp_classes(alpha: bytes):
+    """one or two byte values of the alphabet are SPACE beside 32 and 10, one or two ALONE (a comma where the alphabet is too small)"""
+    values = sorted(set(alpha) - {32, 10})
+    special = rng.sample(values, min(rng.randint(2, 4), len(values) // 4 * 2))
+    cls = np.zeros(256, dtype=np.uint8)
+    cls[[32, 10] + special[:len(special) // 2]] = WP_SPACE
+    cls[special[len(special) // 2:] or [44]] = WP_ALONE
+    return cls
+
+
+def _wp_text(hay: bytes, vocab, C: bytes, own: bool, cls, M: int) -> bytes:
+    """separators written into the haystack at drawn distances -- mostly 1 to 12 bytes, now and then more than M (the stretch
+    cleared of separators), now and then two in a row -- and words made of entries behind some of them"""
+    a = np.frombuffer(hay, dtype=np.uint8).copy()
+    n = len(a)
+    seps = [int(b) for b in np.flatnonzero(cls != WP_WORD)]
+    spaces = [int(b) for b in np.flatnonzero(cls == WP_SPACE)]
+    word_byte = next(b for b in list(hay[:64]) + list(range(97, 123)) if cls[b] == WP_WORD)
+    cont = [x[len(C):] for x in vocab if x.startswith(C) and len(x) > len(C)]
+    p = 0
+    while p < n:
+        r = rng.random()
+        gap = rng.randint(1, 12) if r < 0.93 else 0 if r < 0.985 else M + rng.randint(1, 40)
+        if gap > M:
+            part = a[p:p + gap]
+            part[cls[part] != WP_WORD] = word_byte
+        elif gap and rng.random() < 0.4:
+            word = C if own and rng.random() < 0.2 else rng.choice(vocab)
+            for _ in range(rng.choice([0, 0, 1, 2, 3]) if cont else 0):
+                word = word + rng.choice(cont)
+            word = np.frombuffer(word, dtype=np.uint8)[:n - p]
+            a[p:p + len(word)] = word
+            gap = len(word)
+        p += gap
+        if p < n:
+            a[p] = rng.choice(spaces if rng.random() < 0.8 else seps)
+            p += 1
+    return a.tobytes()
+
+
+def plan_walk(n_cases: int, seed: int, size_log2: float = WALK_SIZE_LOG2, pat_log10: float = SURFACE_PAT_LOG10):
+    """-> n_cases cases over the three anchored walkers, every way in (WALK_OPS); deterministic in (n_cases, seed); no GPU and
+    no capi.Automaton.  Built as plan_summary builds its cases -- make_case()'s shapes with the surface's caps (the data at most
+    2^WALK_SIZE_LOG2 bytes), the op, the match kind and the build flag dealt from a deck, the generator borrowed and put back, a
+    haystack halved until the oracle gives at most SURFACE_ROWS overlapping rows over it.  One device op of every block calls
+    the raw *_into_device form, one op of every block runs on a handle kept in compressed form only.  A pattern set over all
+    byte values also gets an entry per first byte: a root with 256 children.  size_log2, pat_log10: smaller caps, for the
+    cross-check of the reference against the per-pattern brute forces (tests/test_fuzz_walk_plan_cpu.py)."""
+    global rng, MAX_SIZE_LOG2
+    saved = (rng, MAX_SIZE_LOG2)
+    rng, MAX_SIZE_LOG2 = random.Random(seed), size_log2
+    cases, k = [], len(WALK_OPS)
+    try:
+        order, raw_j, compressed_j = [], 0, 0
+        while len(cases) < n_cases:
+            i = len(cases)
+            if i % k == 0:
+                order = list(range(k))
+                rng.shuffle(order)
+                raw_j = rng.choice([j for j in range(k) if not WALK_OPS[j].endswith("_host")])
+                compressed_j = rng.randrange(k)
+            j = order[i % k]
+            deal = (i // k + j) % 6
+            op, mk, ci = WALK_OPS[j], deal % 3, deal >= 3
+            feature = walk_feature(op)
+            name, kind, pats, hay = make_case(pat_log10)
+            utf8 = name == "utf8"
+            alpha = dict(ALPHAS)[name] or UNI.encode()
+            c = {"i": i, "op": op, "name": name, "kind": kind, "mk": mk, "ci": ci, "kernel": rng.choice([None, 1, 2]),
+                 "off": rng.randrange(16), "raw": j == raw_j, "compressed": j == compressed_j,
+                 "shape": _walk_shape(op, rng.random() < 0.6)}
+            fan = [bytes([b]) + bytes(rng.choice(alpha) for _ in range(rng.randint(0, 3))) for b in range(256)] if name == "bytes" else []
+            if feature != "wordpiece":
+                pats = pats + fan
+            if ci:
+                pats = [_upper_some(p, rng.randrange(1 << 30)) for p in pats]
+                hay = _upper_some(hay, rng.randrange(1 << 30))
+            if feature == "match_at":
+                c["row_starts"] = "_rows_" in op or (c["shape"] == "find_batch" and rng.random() < 0.3)
+                c["ov"] = mk == 0 and not c["raw"] and rng.random() < 0.5
+                c["full"] = c["row_starts"] and rng.random() < 0.5
+            elif feature == "segment":
+                c["utf8"] = rng.random() < (0.7 if utf8 else 0.5 if name == "bytes" else 0.2)
+            else:
+                pats, c["prefix"], c["prefix_is_entry"] = _wp_vocabulary(pats, alpha, utf8)
+                pats = pats + fan  # (behind the prefixes: the root keeps all 256)
+                c["max_word"], c["unk_id"] = rng.choice(WALK_MAX_WORDS), rng.choice([-1, -1, 0, 1 << 40])
+                c["cls"] = _wp_classes(alpha)
+                hay = _wp_text(hay, pats, c["prefix"], c["prefix_is_entry"], c["cls"], c["max_word"])
+            c["pats"] = pats
+            cut_state = rng.getstate()
+            while True:
+                rng.setstate(cut_state)
+                c["hays"], c["uniform_len"] = _cut(hay, utf8, c["shape"])
+                if feature == "match_at" and c["full"]:  # rows that ARE a pattern, and one that is a byte longer
+                    if c["uniform_len"]:
+                        fits = [p for p in pats if len(p) == c["uniform_len"]]
+                        for r in range(0, len(c["hays"]), 5):
+                            if fits:
+                                c["hays"][r] = rng.choice(fits)
+                    else:
+                        for x in [rng.choice(pats) for _ in range(3)] + [rng.choice(pats) + rng.choice(pats)[:1]]:
+                            c["hays"].insert(rng.randrange(len(c["hays"]) + 1), x)
+                ctx = _walk_ctx(c)
+                if ctx is not None:
+                    break
+                hay = hay[:_char_start(hay, len(hay) // 2)] if utf8 else hay[:len(hay) // 2]
+            c["rows"] = ctx["rows"]
+            if feature == "match_at":
+                c["positions"] = None if c["row_starts"] else _walk_positions(c, ctx)
+            c["pieces"] = len(next(iter(reference_walk(c, ctx=ctx).values())))
+            cases.append(c)
+    finally:
+        rng, MAX_SIZE_LOG2 = saved
+    return cases
+
+
+def _walk_positions(c: dict, ctx: dict):
+    """about one anchor per 4 to 64 bytes, unsorted and with repeats, half of them where candidates begin; the last byte of
+    rows, the start of empty rows, len -- and for device inputs a few beyond len and negative"""
+    n, bounds = ctx["n"], ctx["bounds"]
+    g = np.random.default_rng(rng.randrange(1 << 30))
+    count = int(n / 2 ** rng.uniform(2, 6)) + rng.randint(0, 3)
+    pos = g.integers(0, max(n, 1), size=count)
+    begins, many = np.unique(ctx["all"].s), np.flatnonzero(np.diff(ctx["all"].lo) >= 2)
+    if len(begins):
+        pos[:count // 2] = g.choice(begins, size=count // 2)
+    if len(many):  # (... a part of them where several do)
+        pos[:count // 6 + 1] = g.choice(many, size=count // 6 + 1)
+    pos[count - count // 8:] = pos[:count // 8]
+    lens = np.diff(bounds)
+    ends, empty = bounds[1:][lens > 0] - 1, bounds[:-1][lens == 0]
+    extra = [g.choice(x, size=min(k, len(x))) if len(x) else [] for x, k in ((ends, 8), (empty, 4))] + [[n, n]]
+    if not c["op"].endswith("_host"):
+        extra.append([n + 1, n + 5, -1, -(1 << 62), 1 << 62, -n - 1])
+    pos = np.concatenate([pos] + [np.asarray(x, dtype=np.int64) for x in extra]).astype(np.int64)
+    return pos[g.permutation(len(pos))]
+
+
+def walk_digest(cases) -> str:
+    import hashlib
+    h = hashlib.sha256()
+    for c in cases:
+        h.update(repr([(k, c[k] if not isinstance(c[k], np.ndarray) else c[k].tolist()) for k in sorted(c) if k not in ("pats", "hays")]).encode())
+        for part in (c["pats"], c["hays"]):
+            h.update(repr([len(x) for x in part]).encode())
+            h.update(b"".join(part))
+    return h.hexdigest()
+
+
+def walk_coverage_table(cases) -> str:
+    lines = [f"{len(cases)} cases; most oracle rows {max(c['rows'] for c in cases)} (limit {SURFACE_ROWS}), most data bytes "
+             f"{max(sum(len(h) for h in c['hays']) for c in cases)}",
+             f"{'op':26s} {'n':>3s}  ci=0 ci=1   mk0 mk1 mk2  odd even  empty-row  raw compressed"]
+    for op in WALK_OPS:
+        cs = [c for c in cases if c["op"] == op]
+        lines.append(f"{op:26s} {len(cs):3d}  {sum(not c['ci'] for c in cs):4d} {sum(c['ci'] for c in cs):4d}   "
+                     + " ".join(f"{sum(c['mk'] == k for c in cs):3d}" for k in range(3))
+                     + f"  {sum(c['off'] % 2 for c in cs):3d} {sum(1 - c['off'] % 2 for c in cs):4d}  "
+                     + f"{sum(any(len(h) == 0 for h in c['hays']) for c in cs):9d}  {sum(c['raw'] for c in cs):3d} {sum(c['compressed'] for c in cs):10d}")
+    for c in cases:
+        lines.append(f"  case {c['i']:3d} {_walk_tag(c)}")
+    return "\n".join(lines)
+
+
+def _walk_tag(c: dict) -> str:
+    what = {"match_at": lambda: f"ov {int(c['ov'])} full {int(c['full'])} anchors {len(c['hays']) if c['positions'] is None else len(c['positions'])}",
+            "segment": lambda: f"utf8 {int(c['utf8'])}",
+            "wordpiece": lambda: f"C {c['prefix']!r}{'*' if c['prefix_is_entry'] else ''} M {c['max_word']}"}[walk_feature(c["op"])]()
+    return (f"{c['op']:24s} {c['name']:7s} {c['kind']:8s} pats {len(c['pats']):5d} hays {len(c['hays']):6d} bytes "
+            f"{sum(len(h) for h in c['hays']):7d} mk {c['mk']} ci {int(c['ci'])} off {c['off']:2d} kernel {c['kernel']} "
+            f"{'raw ' if c['raw'] else ''}{'compressed ' if c['compressed'] else ''}{what} rows {c['rows']} out {c['pieces']}")
+
+
+def walk_difference(feature: str, got: dict, want: dict):
+    """-> None, or the first difference as text: feature, column, index, got and want"""
+    for name in WALK_COLUMNS[feature]:
+        g, w = got.get(name), want.get(name)
+        if g is None and w is None:
+            continue
+        if g is None or w is None:
+            return f"{feature} {name}: {'missing' if g is None else 'present'}, the reference has {'none' if w is None else len(w)}"
+        g, w = np.asarray(g), np.asarray(w)
+        m = min(len(g), len(w))
+        bad = np.flatnonzero(g[:m].astype(np.int64) != w[:m].astype(np.int64))
+        if len(bad) or len(g) != len(w):
+            i = int(bad[0]) if len(bad) else m
+            return (f"{feature} {name}[{i}]: got {int(g[i]) if i < len(g) else None} want {int(w[i]) if i < len(w) else None} "
+                    f"({len(g)} entries, the reference has {len(w)})")
+    return None
+
+
+def walk_host_form(c: dict, ctx: dict, ref: dict):
+    """the host form (acx_match_at_host / acx_segment_host / acx_wordpiece_host: the definition walked over the compiled
+    tables, no device) over the same inputs -> None, or its first difference from the reference"""
+    feature, whole = walk_feature(c["op"]), ctx["whole"]
+    offsets = None if c["shape"] == "find" or c["shape"].endswith("_one") else ctx["bounds"]
+    h = capi.HostAutomaton(c["pats"], c["mk"], capi.BUILD_ASCII_CASE_INSENSITIVE if c["ci"] else 0)
+    try:
+        if feature == "match_at":
+            pos = c["positions"]
+            if pos is not None:  # (it refuses a position outside the data)
+                pos = pos[(pos >= 0) & (pos <= len(whole))]
+                ref = reference_walk(c, pos, ctx)
+            flags = (capi.AT_OVERLAPPING if c["ov"] else 0) | (capi.AT_FULL if c["full"] else 0) | (capi.AT_ROW_STARTS if pos is None else 0)
+            got = capi.match_at_host(h, whole, pos, offsets=offsets, flags=flags, match_kind=c["mk"])
+        elif feature == "segment":
+            got = capi.segment_host(h, whole, offsets=offsets, flags=capi.SEG_UTF8 if c["utf8"] else 0, match_kind=c["mk"])
+        else:
+            got = capi.wordpiece_host(h, whole, c["cls"], prefix=c["prefix"], max_word=c["max_word"], unk_id=c["unk_id"],
+                                      offsets=offsets, match_kind=c["mk"])
+    finally:
+        h.close()
+    return walk_difference(feature, dict(zip(WALK_COLUMNS[feature], got)), ref)
+
+
+def _run_walk_case(a, c: dict, ctx: dict, ref: dict):
+    """-> None, or the first difference as text"""
+    feature, whole, bounds, off, L = walk_feature(c["op"]), ctx["whole"], ctx["bounds"], c["off"], c["uniform_len"]
+    names, rows = WALK_COLUMNS[feature], len(c["hays"])
+    ragged = c["shape"] in BATCH_OPS
+    if feature == "match_at":
+        pos = c["positions"]
+        flags = (capi.AT_OVERLAPPING if c["ov"] else 0) | (capi.AT_FULL if c["full"] else 0) | (capi.AT_ROW_STARTS if pos is None else 0)
+    elif feature == "segment":
+        flags = capi.SEG_UTF8 if c["utf8"] else 0
+    else:
+        kw = {"prefix": c["prefix"], "max_word": c["max_word"], "unk_id": c["unk_id"]}
+    if c["op"].endswith("_host"):  # host input: a sequence of rows, or one haystack that is no batch
+        hay = (c["hays"], None) if c["shape"] == "find_batch" else (None, whole)
+        if feature == "match_at":
+            r = a.match_at(hay[0], pos, flags, single=hay[1])
+        elif feature == "segment":
+            r = a.segment(hay[0], flags, single=hay[1])
+        else:
+            r = a.wordpiece(hay[0], c["cls"], single=hay[1], **kw)
+        try:
+            if r.on_device:
+                return "a host input gave a result on the device"
+            return walk_difference(feature, {name: getattr(r, name)() for name in names}, ref)
+        finally:
+            r.free()
+    if c["raw"]:  # the *_into_device form, its outputs between guard bytes (the feature's own test file has the frame)
+        cut = {"offsets": bounds if ragged else None, "uniform": L}
+        if feature == "match_at":
+            from test_gpu_at import run_raw
+            got = run_raw(a, whole, pos, flags=flags & capi.AT_FULL, base_res=off, out_res=off & 1, **cut)
+            return walk_difference(feature, dict(zip(names, got)), ref)
+        T = len(ref[names[0]])
+        if feature == "segment":
+            from test_gpu_seg import run_raw
+            got_T, out = run_raw(a, whole, T, flags=flags, base_res=off, **cut)
+            if got_T != T:
+                return f"segment: {got_T} pieces, the reference has {T}"
+            return walk_difference(feature, dict(zip(names, [o.view(np.int64) for o in out])), ref)
+        from test_gpu_wp import GUARD, run_raw
+        got_T, got, sizes = run_raw(a, whole, c["cls"], max(T, 1), prefix=c["prefix"], M=c["max_word"], unk=c["unk_id"], base_res=off, **cut)
+        if got_T != T:
+            return f"wordpiece: {got_T} pieces, the reference has {T}"
+        out = {}
+        for g, size, name in zip(got, sizes, names):
+            used = ref[name].nbytes
+            if not ((g[:64] == GUARD).all() and (g[64 + used:] == GUARD).all()):
+                return f"wordpiece {name}: a byte around its {used} bytes was written"
+            out[name] = g[64:64 + used].copy().view(ref[name].dtype)
+        return walk_difference(feature, out, ref)
+    bufs, r = [], None
+    try:
+        bufs.append(_on_device(whole, off))
+        seg = {}
+        if L:
+            seg = {"n_hay": rows, "uniform_len": L}
+        elif ragged:
+            bufs.append(capi.DeviceBuffer(bounds.nbytes).upload(bounds.astype(np.uint64).view(np.uint8)))
+            seg = {"n_hay": rows, "d_offsets": bufs[-1].ptr}
+        if feature == "match_at":
+            d_pos, n_pos = 0, 0
+            if pos is not None:
+                bufs.append(capi.DeviceBuffer(8 * len(pos) + 16))
+                if len(pos):
+                    bufs[-1].upload(pos.view(np.uint8))
+                d_pos, n_pos, at_pos = bufs[-1].ptr, len(pos), bufs[-1]
+            r = a.match_at_device(bufs[0].ptr + off, len(whole), d_pos, n_pos, flags, **seg)
+        elif feature == "segment":
+            r = a.segment_device(bufs[0].ptr + off, len(whole), flags, **seg)
+        else:
+            r = a.wordpiece_device(bufs[0].ptr + off, len(whole), c["cls"], **seg, **kw)
+        if not r.on_device:
+            return "a device input gave a result on the host"
+        got = {name: getattr(r, name)() for name in names}
+        if not np.array_equal(bufs[0].download(off + len(whole)), np.frombuffer(bytes(off) + whole, dtype=np.uint8)):
+            return "the caller's device buffer was written"
+        if ragged and not L and not np.array_equal(bufs[1].download(bounds.nbytes).view(np.uint64), bounds.astype(np.uint64)):
+            return "the caller's offsets were written"
+        if feature == "match_at" and pos is not None and len(pos) and not np.array_equal(at_pos.download(8 * len(pos)).view(np.int64), pos):
+            return "the caller's positions were written"
+        return walk_difference(feature, got, ref)
+    finally:
+        if r is not None:
+            r.free()
+        for b in bufs:
+            b.free()
+
+
+def run_walk(cases):
+    """-> (ran, failures, skipped, build_errors), as run_surface: every case through the C ABI against reference_walk(case), and
+    the host form over the same inputs against it too -- when the two differ, that shows which side is wrong.  One line per
+    case, the first difference (feature, column, index, got, want) of a case that fails."""
+    ran = fails = skipped = build_errors = 0
+    for c in cases:
+        tag = f"{c['i']:3d} {_walk_tag(c)}"
+        if c["rows"] > ROW_LIMIT:
+            print("skip", tag, flush=True)
+            skipped += 1
+            continue
+        before = os.environ.get("ACX_DENSE_LIMIT")
+        if c["compressed"]:
+            os.environ["ACX_DENSE_LIMIT"] = "0"
+        try:
+            a = capi.Automaton(c["pats"], c["mk"], kernel=c["kernel"], ascii_case_insensitive=c["ci"])
+        except (capi.AcxError, ValueError, MemoryError) as e:
+            print("FAIL", tag, "build error:", e, flush=True)
+            build_errors += 1; fails += 1
+            continue
+        finally:
+            if c["compressed"]:
+                os.environ.pop("ACX_DENSE_LIMIT")
+                if before is not None:
+                    os.environ["ACX_DENSE_LIMIT"] = before
+        t0 = time.time()
+        ctx = _walk_ctx(c, 1 << 62)
+        ref = reference_walk(c, ctx=ctx)
+        diffs = []
+        if c["compressed"] and a.info.table_bytes != 0:
+            diffs.append("the handle was to be kept in compressed form only and has a dense table")
+        for leg, run in (("the library", lambda: _run_walk_case(a, c, ctx, ref)), ("the host form", lambda: walk_host_form(c, ctx, ref))):
+            try:
+                d = run()
+            except (capi.AcxError, ValueError, MemoryError, AssertionError) as e:
+                d = f"error: {e}"
+            if d:
+                diffs.append(f"{leg}: {d}")
+        a.close()
+        ran += 1
+        print(f"{'FAIL' if diffs else 'ok  '} {tag} {time.time() - t0:.2f} s", flush=True)
+        for d in diffs:
+            print("    ", d, flush=True)
+        fails += bool(diffs)
+    return ran, fails, skipped, build_errors
+
+
+WALK_N, WALK_SEED = 140, 20261025  # what tests/test_gpu_fuzz_walk.py runs and tests/test_fuzz_walk_plan_cpu.py checks
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "walk":
+        args = [x for x in sys.argv[2:] if x != "--plan-only"]
+        plan = plan_walk(int(args[0]) if args else WALK_N, int(args[1]) if len(args) > 1 else WALK_SEED)
+        print(walk_coverage_table(plan), flush=True)
+        if "--plan-only" in sys.argv:
+            sys.exit(0)
+        ran, n_fails, skipped, build_errors = run_walk(plan)
+        print(f"{ran} cases ran, {n_fails} failures, {skipped} skipped, {build_errors} build errors")
+        sys.exit(1 if n_fails or skipped else 0)
     if len(sys.argv) > 1 and sys.argv[1] == "summary":
         args = [x for x in sys.argv[2:] if x != "--plan-only"]
         plan = plan_summary(int(args[0]) if args else SUMMARY_N, int(args[1]) if len(args) > 1 else SUMMARY_SEED)
