@@ -130,7 +130,8 @@ inline bool leave_wide(const Limits &L, bool wide, uint64_t n_hot, uint64_t n_ra
 struct Hold {
     int calls;  // Ctx::dense_hold
     bool input; // Ctx::hold_dense_input: the INPUT was dense (the hold ends with the first call that is not) -- or the sparse
-                // kernels gave up for another reason (counted down: one failed attempt in nine calls)
+                // kernels gave up for another reason (counted down, first by the dense attempt of the call that gave up: one
+                // failed attempt in eight calls)
 };
 constexpr int HOLD_CALLS = 8;
 constexpr Hold hold_dense_input() { return Hold{HOLD_CALLS, true}; } // dense_everywhere, and below
