@@ -51,7 +51,7 @@ __global__ __launch_bounds__(AT_THREADS) void k_at(const AtTrie T, const uint8_t
     if (tid == 0) s_n = 0;
     __syncthreads();
 
-    // ---- A: position, limit, first byte; the survivors into the list
+    // ---- A: position, limit, first byte; the survivors into the list (walk_push)
 #pragma unroll
     for (uint32_t k = 0; k < AT_IPT; k++) {
         const uint32_t slot = k * AT_THREADS + tid;
@@ -77,14 +77,7 @@ __global__ __launch_bounds__(AT_THREADS) void k_at(const AtTrie T, const uint8_t
         s_pos[slot] = p;
         s_lim[slot] = survive ? (uint32_t)std::min<uint64_t>(L - p, 0xFFFFFFFFull) : 0u;
         s_res[slot] = survive ? s1 : (MODE == AT_MODE_WALK ? AT_NONE : 0u);
-        const uint64_t mask = __ballot(survive);
-        if (mask) { // (wave-uniform)
-            const int leader = __ffsll((unsigned long long)mask) - 1;
-            uint32_t at = 0;
-            if ((int)lane == leader) at = atomicAdd(&s_n, (uint32_t)__popcll(mask));
-            at = __shfl(at, leader);
-            if (survive) s_list[at + (uint32_t)__popcll(mask & ((1ull << lane) - 1))] = (uint16_t)slot;
-        }
+        walk_push(survive, slot, lane, &s_n, s_list);
     }
     __syncthreads();
 
@@ -140,6 +133,20 @@ __global__ __launch_bounds__(AT_THREADS) void k_at(const AtTrie T, const uint8_t
             counts[idx] = r;
         }
     }
+}
+
+// a thread per row (and one more): the pieces that begin before the row does, clamped into [0, total]
+__global__ __launch_bounds__(AT_THREADS) void k_piece_rows(const RowCut R, const int64_t *__restrict__ starts, const uint64_t total,
+                                                           int64_t *__restrict__ row_offsets) {
+    const uint64_t r = (uint64_t)blockIdx.x * AT_THREADS + threadIdx.x;
+    if (r > R.n) return;
+    row_offsets[r] = (int64_t)(r == R.n ? total : std::min<uint64_t>(count_lt(starts, total, row_begin(R, r)), total));
+}
+
+hipError_t piece_rows(const RowCut &R, const int64_t *starts, uint64_t total, int64_t *row_offsets, hipStream_t st) {
+    if (!row_offsets || R.n >= (1ull << 38)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_piece_rows, dim3((uint32_t)tiles_of(R.n + 1, AT_THREADS)), dim3(AT_THREADS), 0, st, R, starts, total, row_offsets);
+    return hipGetLastError();
 }
 
 namespace {

@@ -30,7 +30,7 @@
 //   A. every thread takes AT_TILE / AT_THREADS anchors of its workgroup's tile, AT_THREADS apart (the positions are read by
 //      coalesced 8-byte loads): position, limit (two words of the offsets, a multiplication, or count_le over the offsets),
 //      the first byte through root_next -- 1 KiB copied to LDS.  Most anchors die there.  The survivors' slots are compacted
-//      into a list in LDS (a ballot per wave, one LDS atomic per wave).
+//      into a list in LDS (walk_push, at_walk.hpp: a ballot per wave, one LDS atomic per wave).
 //   B. the threads take survivors from the list, so that the walking lanes are dense: children of s are the ids
 //      [first_child[s], first_child[s + 1]) with in_byte ascending -- a linear probe up to AT_PROBE children, a binary search
 //      beyond (a root-like node has up to 256); haystack bytes by byte loads, folded in the load for a case-insensitive
@@ -87,5 +87,10 @@ hipError_t at_count(const AtTrie &T, const uint8_t *hay, const RowCut &R, const 
 // entries base[i] .. base[i + 1] - 1 and never one at or past base[i + 1]
 hipError_t at_emit(const AtTrie &T, const uint8_t *hay, const RowCut &R, const int64_t *pos, uint64_t A, uint32_t flags,
                    const int64_t *base, int64_t *pattern, int64_t *end, hipStream_t st);
+
+// The row offsets of a result whose pieces lie in data order (the segmenter's, WordPiece's): row_offsets[r], r = 0 .. R.n, is
+// count_lt(starts, total, row_begin(r)) clamped into [0, total], the last one total.  starts: total ascending int64 words
+// (none read when total == 0); row_offsets: R.n + 1 words, 8-byte aligned; R.n < 2^38.  One kernel, a thread per entry.
+hipError_t piece_rows(const RowCut &R, const int64_t *starts, uint64_t total, int64_t *row_offsets, hipStream_t st);
 
 } // namespace acx

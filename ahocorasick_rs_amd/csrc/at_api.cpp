@@ -1,6 +1,8 @@
 // at_api.cpp -- the anchored search, "does a pattern begin exactly HERE" (at.hpp has the definition): the host form of the
 // definition, the device stage, the acx_match_at* entry points and the accessors of their result.  No find runs: the walk
-// reads the trie edges and the own lists every handle has, and a few haystack bytes per anchor.
+// reads the trie edges and the own lists every handle has, and a few haystack bytes per anchor.  The entries' preambles, the
+// two-pass frame, the staged route and the host twin are the walkers' shared ones (result_block.hpp), the match kind's choice
+// on the host is HostTrie::pick.
 #include "at.hpp"
 #include "host_trie.hpp"
 #include "replace.hpp"
@@ -22,6 +24,7 @@ struct ACX_HIDDEN acx_at : ResultBlock {
     int64_t *pattern() const { return at<int64_t>(PATTERN); }
     int64_t *end() const { return at<int64_t>(END); }
     int64_t *row_offsets() const { return at<int64_t>(ROW_OFFSETS); }
+    void shaped_like(const acx_at &D) { anchors = D.anchors; entries = D.entries; overlapping = D.overlapping; }
 };
 
 namespace {
@@ -42,46 +45,6 @@ uint32_t kernel_flags(const acx_automaton *a, uint32_t flags) {
            (folds(a) ? acx::AT_FOLD : 0u);
 }
 
-// The device stage on stream st into Z (anchors and overlapping set, no block yet).  d_pos: Z->anchors words (null with
-// ACX_AT_ROW_STARTS).  Overlapping: the stream is waited for once -- the total, 8 bytes, sizes the block.  *temp: the
-// stage's temporaries, one block of the buffer cache (or null) -- the caller's to return, behind the stage's kernels.
-int at_stage(acx_automaton *a, hipStream_t st, const uint8_t *d_hay, const acx::RowCut &R, const int64_t *d_pos, uint32_t flags,
-             acx_at *Z, void **temp) {
-    const uint64_t A = Z->anchors;
-    const acx::AtTrie T = acx::at_trie(a->dev); // (the whole own lists: an overlapping call reports every copy)
-    const uint32_t kf = kernel_flags(a, flags);
-    int rc;
-    if (!Z->overlapping) {
-        Z->entries = A;
-        if ((rc = Z->alloc()) != ACX_OK) return rc;
-        if (A) HIPCHK(acx::at_walk(T, d_hay, R, d_pos, A, a->host.match_kind, kf, Z->pattern(), Z->end(), st));
-        return ACX_OK;
-    }
-    if (!A) {
-        Z->entries = 0;
-        if ((rc = Z->alloc()) != ACX_OK) return rc;
-        HIPCHK(hipMemsetAsync(Z->row_offsets(), 0, 8, st));
-        return ACX_OK;
-    }
-    // [counts: A][base: A + 1][scan], every part 256-byte aligned
-    Carver C;
-    const uint64_t o_counts = C.part(A), o_base = C.part(A + 1), o_scan = C.part(replace_scan_words(A));
-    HIPCHK(g_bufs.get(temp, C.bytes(), a->device));
-    uint64_t *b = (uint64_t *)*temp;
-    int64_t *base = (int64_t *)(b + o_base);
-    HIPCHK(acx::at_count(T, d_hay, R, d_pos, A, kf, b + o_counts, st));
-    HIPCHK(acx::replace_scan(nullptr, nullptr, b + o_counts, A, base, b + o_scan, st));
-    uint64_t total = 0; // all that crosses the bus
-    HIPCHK(hipMemcpyAsync(&total, base + A, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (total >= (1ull << 60)) return fail(ACX_EDEVICE, "the anchors' counts do not sum to a size");
-    Z->entries = total;
-    if ((rc = Z->alloc()) != ACX_OK) return rc;
-    HIPCHK(hipMemcpyAsync(Z->row_offsets(), base, (A + 1) * 8, hipMemcpyDeviceToDevice, st));
-    if (total) HIPCHK(acx::at_emit(T, d_hay, R, d_pos, A, kf, base, Z->pattern(), Z->end(), st));
-    return ACX_OK;
-}
-
 // the anchors of a call: the rows, or the positions
 int anchors_of(uint32_t flags, const acx::RowCut &R, uint64_t n_pos, uint64_t *A) {
     *A = (flags & ACX_AT_ROW_STARTS) ? R.n : n_pos;
@@ -89,14 +52,17 @@ int anchors_of(uint32_t flags, const acx::RowCut &R, uint64_t n_pos, uint64_t *A
 }
 
 // The device route under a lease: the stage on the context's stream, a device result.  Returns when the result's size is
-// known, with the stage in flight (Z->done).  d_hay, the offsets and d_pos must stay valid until then; t2: a second
-// temporary of the caller's that goes back to the cache behind the kernels (the staged positions), or null.
+// known, with the stage in flight (Z->done).  d_hay, the offsets and d_pos (n_pos words; null with ACX_AT_ROW_STARTS) must
+// stay valid until then; t2: a second temporary of the caller's that goes back to the cache behind the kernels (the staged
+// positions), or null.
+// Not overlapping: an entry per anchor, nothing to count.  Overlapping: two passes (two_pass) -- at_count, the library's scan,
+// the total, 8 bytes, crosses the bus; at_emit walks again -- over one block of the cache: [counts: A][base: A + 1][scan].
 int run_at(acx_automaton *a, Ctx *c, const uint8_t *d_hay, uint64_t len, const Segments &G, const int64_t *d_pos, uint64_t n_pos,
            uint32_t flags, void *t2, acx_at **out) {
     *out = nullptr;
     const acx::RowCut R = row_cut(G, len);
     uint64_t A = 0;
-    int rc = anchors_of(flags, R, n_pos, &A);
+    const int rc = anchors_of(flags, R, n_pos, &A);
     acx_at *Z = rc == ACX_OK ? new_result<acx_at>(a->device, true) : nullptr;
     if (!Z) {
         if (t2) (void)hipStreamSynchronize(c->stream); // (the copy that fills it)
@@ -105,12 +71,36 @@ int run_at(acx_automaton *a, Ctx *c, const uint8_t *d_hay, uint64_t len, const S
     }
     Z->anchors = A;
     Z->overlapping = (flags & ACX_AT_OVERLAPPING) != 0;
-    void *temp = nullptr;
-    const int queued = at_stage(a, c->stream, d_hay, R, d_pos, flags, Z, &temp);
-    rc = retire_find(queued, c->stream, nullptr, Z, temp, t2);
-    if (rc != ACX_OK) { free_result(Z); return rc; }
-    *out = Z;
-    return ACX_OK;
+    const acx::AtTrie T = acx::at_trie(a->dev); // (the whole own lists: an overlapping call reports every copy)
+    const uint32_t kf = kernel_flags(a, flags);
+    const bool counted = Z->overlapping && A;
+    Carver C;
+    const uint64_t o_counts = C.part(A), o_base = C.part(A + 1), o_scan = C.part(replace_scan_words(A));
+    return two_pass(
+        c->stream, Z, &Z->entries, t2, out,
+        [&](hipStream_t st, void **temp, uint64_t *total) -> int {
+            *total = Z->overlapping ? 0 : A;
+            if (!counted) return ACX_OK;
+            HIPCHK(g_bufs.get(temp, C.bytes(), a->device));
+            uint64_t *b = (uint64_t *)*temp;
+            HIPCHK(acx::at_count(T, d_hay, R, d_pos, A, kf, b + o_counts, st));
+            HIPCHK(acx::replace_scan(nullptr, nullptr, b + o_counts, A, (int64_t *)(b + o_base), b + o_scan, st));
+            HIPCHK(hipMemcpyAsync(total, b + o_base + A, 8, hipMemcpyDeviceToHost, st)); // all that crosses the bus
+            HIPCHK(hipStreamSynchronize(st));
+            return *total >= (1ull << 60) ? fail(ACX_EDEVICE, "the anchors' counts do not sum to a size") : ACX_OK;
+        },
+        [&](hipStream_t st, void *temp, uint64_t total) -> int {
+            if (!Z->overlapping) {
+                if (A) HIPCHK(acx::at_walk(T, d_hay, R, d_pos, A, a->host.match_kind, kf, Z->pattern(), Z->end(), st));
+            } else if (!A) {
+                HIPCHK(hipMemsetAsync(Z->row_offsets(), 0, 8, st));
+            } else {
+                const int64_t *base = (const int64_t *)temp + o_base;
+                HIPCHK(hipMemcpyAsync(Z->row_offsets(), base, (A + 1) * 8, hipMemcpyDeviceToDevice, st));
+                if (total) HIPCHK(acx::at_emit(T, d_hay, R, d_pos, A, kf, base, Z->pattern(), Z->end(), st));
+            }
+            return ACX_OK;
+        });
 }
 
 } // namespace
@@ -120,21 +110,17 @@ extern "C" {
 int acx_match_at_host(const acx_host_automaton_t *h, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
                       const int64_t *positions, uint64_t n_pos, uint32_t flags, int match_kind, int64_t *pattern, int64_t *end,
                       int64_t *row_offsets) {
-    if (!h) return fail(ACX_EINVAL, "null argument");
-    int rc = at_flags(flags);
-    if (rc != ACX_OK) return rc;
-    if (match_kind < ACX_MATCH_STANDARD || match_kind > ACX_MATCH_LEFTMOST_LONGEST) return fail(ACX_EINVAL, "unknown match kind");
     const bool overlapping = (flags & ACX_AT_OVERLAPPING) != 0, full = (flags & ACX_AT_FULL) != 0,
                row_starts = (flags & ACX_AT_ROW_STARTS) != 0;
-    if (overlapping && (match_kind != ACX_MATCH_STANDARD || h->host.match_kind != ACX_MATCH_STANDARD))
-        return fail(ACX_EOVERLAP, "an overlapping search needs match kind Standard");
-    if (len && !hay) return fail(ACX_EINVAL, "null argument");
-    if (!offsets) {
-        if (n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
-        n_hay = 1;
-    } else if ((rc = offsets_span(offsets, n_hay, len)) != ACX_OK) {
-        return rc;
-    }
+    const int rc = host_form_args(
+        h != nullptr, [&] { return at_flags(flags); }, match_kind,
+        [&] {
+            return overlapping && (match_kind != ACX_MATCH_STANDARD || h->host.match_kind != ACX_MATCH_STANDARD)
+                       ? fail(ACX_EOVERLAP, "an overlapping search needs match kind Standard")
+                       : ACX_OK;
+        },
+        hay, len, offsets, &n_hay);
+    if (rc != ACX_OK) return rc;
     const uint64_t A = row_starts ? n_hay : n_pos;
     if (!row_starts && n_pos && !positions) return fail(ACX_EINVAL, "null argument");
     if (overlapping ? !row_offsets || (!pattern != !end) : A && (!pattern || !end)) return fail(ACX_EINVAL, "null argument");
@@ -157,7 +143,7 @@ int acx_match_at_host(const acx_host_automaton_t *h, const uint8_t *hay, uint64_
         const uint64_t origin = row_starts ? p : 0; // `end` is local to the row for row starts
         if (overlapping) {
             row_offsets[i] = (int64_t)w;
-            T.walk(hay, p, L, [&](uint32_t s, uint64_t d) {
+            T.walk(hay, p, L, 0, [&](uint32_t s, uint64_t d) {
                 if (full && p + d != L) return true;
                 for (uint32_t o = H.own_off[s]; o < H.own_off[s + 1]; o++, w++)
                     if (pattern) { pattern[w] = (int64_t)H.own_pid[o]; end[w] = (int64_t)(p + d - origin); }
@@ -165,17 +151,9 @@ int acx_match_at_host(const acx_host_automaton_t *h, const uint8_t *hay, uint64_
             });
             continue;
         }
-        int64_t best = -1, best_end = -1;
-        T.walk(hay, p, L, [&](uint32_t s, uint64_t d) {
-            if (full && p + d != L) return true;
-            const int64_t pid = (int64_t)H.own_pid[H.own_off[s]]; // (the lists are in id order)
-            if (match_kind == ACX_MATCH_LEFTMOST_FIRST && !full && best >= 0 && best < pid) return true;
-            best = pid;
-            best_end = (int64_t)(p + d - origin);
-            return !(match_kind == ACX_MATCH_STANDARD || full);
-        });
-        pattern[i] = best;
-        end[i] = best_end;
+        uint64_t e;
+        const bool found = T.pick(hay, p, L, 0, match_kind, full, &pattern[i], &e);
+        end[i] = found ? (int64_t)(e - origin) : -1;
     }
     if (overlapping) row_offsets[A] = (int64_t)w;
     return ACX_OK;
@@ -188,18 +166,17 @@ int acx_match_at_device(acx_automaton_t *a, const void *d_hay, uint64_t len, con
     int rc = at_flags(flags);
     if (rc == ACX_OK && (flags & ACX_AT_OVERLAPPING)) rc = check_overlapping(a); // (the error, no device state)
     if (rc != ACX_OK) return rc;
-    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
-    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
     const bool row_starts = (flags & ACX_AT_ROW_STARTS) != 0;
-    if (!row_starts && n_pos && !d_positions) return fail(ACX_EINVAL, "null argument");
-    if (((uintptr_t)d_positions | (uintptr_t)d_offsets) & 7) return fail(ACX_EINVAL, "positions and offsets must be 8-byte aligned");
-    if (!row_starts && n_pos >= acx::AT_MAX_ANCHORS) return too_many_anchors();
     Segments G;
-    if ((rc = make_segments(d_offsets, n_hay, uniform_len, len, &G)) != ACX_OK) return rc;
-    Lease lease(a);
-    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    // (a case-insensitive handle folds in the walk's loads: no folded copy of the data)
-    return run_at(a, lease.c, (const uint8_t *)d_hay, len, G, row_starts ? nullptr : d_positions, n_pos, flags, nullptr, out);
+    rc = walk_device_args(d_hay, len, d_offsets, n_hay, uniform_len, [&] {
+        if (!row_starts && n_pos && !d_positions) return fail(ACX_EINVAL, "null argument");
+        if (((uintptr_t)d_positions | (uintptr_t)d_offsets) & 7) return fail(ACX_EINVAL, "positions and offsets must be 8-byte aligned");
+        return !row_starts && n_pos >= acx::AT_MAX_ANCHORS ? too_many_anchors() : ACX_OK;
+    }, &G);
+    if (rc != ACX_OK) return rc;
+    return leased(a, [&](Ctx *c) {
+        return run_at(a, c, (const uint8_t *)d_hay, len, G, row_starts ? nullptr : d_positions, n_pos, flags, nullptr, out);
+    });
 }
 
 int acx_match_at_into_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
@@ -209,27 +186,27 @@ int acx_match_at_into_device(acx_automaton_t *a, const void *d_hay, uint64_t len
     int rc = at_flags(flags);
     if (rc != ACX_OK) return rc;
     if (flags & ACX_AT_OVERLAPPING) return fail(ACX_EINVAL, "the raw form is not overlapping: its columns have an entry per anchor");
-    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
-    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
     const bool row_starts = (flags & ACX_AT_ROW_STARTS) != 0;
-    if (!row_starts && n_pos && !d_positions) return fail(ACX_EINVAL, "null argument");
-    if (((uintptr_t)d_positions | (uintptr_t)d_offsets | (uintptr_t)d_pattern | (uintptr_t)d_end) & 7)
-        return fail(ACX_EINVAL, "positions, offsets and both columns must be 8-byte aligned");
     Segments G;
-    if ((rc = make_segments(d_offsets, n_hay, uniform_len, len, &G)) != ACX_OK) return rc;
+    rc = walk_device_args(d_hay, len, d_offsets, n_hay, uniform_len, [&] {
+        if (!row_starts && n_pos && !d_positions) return fail(ACX_EINVAL, "null argument");
+        return (((uintptr_t)d_positions | (uintptr_t)d_offsets | (uintptr_t)d_pattern | (uintptr_t)d_end) & 7)
+                   ? fail(ACX_EINVAL, "positions, offsets and both columns must be 8-byte aligned")
+                   : ACX_OK;
+    }, &G);
+    if (rc != ACX_OK) return rc;
     const acx::RowCut R = row_cut(G, len);
     uint64_t A = 0;
     if ((rc = anchors_of(flags, R, n_pos, &A)) != ACX_OK) return rc;
     if (!A) return ACX_OK; // (no entry to write)
     if (!d_pattern || !d_end) return fail(ACX_EINVAL, "null argument");
-    Lease lease(a);
-    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    const hipStream_t st = lease.c->stream;
-    const hipError_t e = acx::at_walk(acx::at_trie(a->dev), (const uint8_t *)d_hay, R, row_starts ? nullptr : d_positions, A,
-                                      a->host.match_kind, kernel_flags(a, flags), d_pattern, d_end, st);
-    const hipError_t s = hipStreamSynchronize(st); // (complete when it returns, whatever the launch said)
-    if (e != hipSuccess) return hipfail(e, "at_walk");
-    return s == hipSuccess ? ACX_OK : hipfail(s, "hipStreamSynchronize");
+    return leased(a, [&](Ctx *c) {
+        const hipError_t e = acx::at_walk(acx::at_trie(a->dev), (const uint8_t *)d_hay, R, row_starts ? nullptr : d_positions, A,
+                                          a->host.match_kind, kernel_flags(a, flags), d_pattern, d_end, c->stream);
+        const hipError_t s = hipStreamSynchronize(c->stream); // (complete when it returns, whatever the launch said)
+        if (e != hipSuccess) return hipfail(e, "at_walk");
+        return s == hipSuccess ? ACX_OK : hipfail(s, "hipStreamSynchronize");
+    });
 }
 
 int acx_match_at(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
@@ -239,14 +216,8 @@ int acx_match_at(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uin
     int rc = at_flags(flags);
     if (rc == ACX_OK && (flags & ACX_AT_OVERLAPPING)) rc = check_overlapping(a); // (the error, no device state)
     if (rc != ACX_OK) return rc;
-    if (len && !hay) return fail(ACX_EINVAL, "null haystack");
+    if ((rc = host_rows(hay, len, offsets, &n_hay, "null haystack")) != ACX_OK) return rc;
     const bool batch = offsets != nullptr, row_starts = (flags & ACX_AT_ROW_STARTS) != 0;
-    if (!batch) {
-        if (n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
-        n_hay = 1;
-    } else if ((rc = offsets_span(offsets, n_hay, len)) != ACX_OK) {
-        return rc;
-    }
     if (!row_starts && n_pos && !positions) return fail(ACX_EINVAL, "null argument");
     if (!row_starts && n_pos >= acx::AT_MAX_ANCHORS) return too_many_anchors();
     // positions in the caller's unit -> bytes (codepoints: characters, a byte that continues none begins one)
@@ -266,11 +237,7 @@ int acx_match_at(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uin
     // the data (and, for a batch, its offsets) through the context's staging buffers, the positions through a block of the
     // buffer cache; the same kernels; the block comes home in one copy
     acx_at *D = nullptr;
-    {
-        Lease lease(a);
-        Ctx *c = lease.c;
-        if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-        if ((rc = stage_host(a, c, hay, len, batch ? offsets : nullptr, batch ? n_hay + 1 : 0, false)) != ACX_OK) return rc;
+    rc = staged_walk(a, hay, len, offsets, n_hay, &D, [&](Ctx *c, const Segments &G, acx_at **dev) -> int {
         void *d_pos = nullptr;
         if (!pos.empty()) {
             HIPCHK(g_bufs.get(&d_pos, pos.size() * 8, a->device));
@@ -281,20 +248,11 @@ int acx_match_at(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uin
                 return hipfail(e, "hipMemcpyAsync");
             }
         }
-        const Segments G = batch ? Segments{c->ws.offsets, n_hay, 0} : Segments{nullptr, 1, 0};
-        rc = run_at(a, c, c->ws.hay, len, G, (const int64_t *)d_pos, n_pos, flags, d_pos, &D);
-        if (rc == ACX_OK) rc = D->wait(); // (the staging buffers are the context's, pos is this call's)
-        else (void)hipStreamSynchronize(c->stream);
-    }
-    acx_at *Z = rc == ACX_OK ? new_result<acx_at>(a->device, false) : nullptr;
-    if (Z) {
-        Z->anchors = D->anchors;
-        Z->entries = D->entries;
-        Z->overlapping = D->overlapping;
-        if ((rc = Z->alloc()) != ACX_OK) { free_result(Z); free_result(D); return rc; }
-    }
-    if ((rc = copy_down(rc, D, Z, D ? D->block_bytes : 0, "the match-at result's copy", out)) != ACX_OK) return rc;
+        return run_at(a, c, c->ws.hay, len, G, (const int64_t *)d_pos, n_pos, flags, d_pos, dev); // (pos is this call's)
+    });
+    if ((rc = host_twin(rc, D, "the match-at result's copy", out)) != ACX_OK) return rc;
     if (!codepoints) return ACX_OK;
+    acx_at *Z = *out;
     // ends in characters: an entry's anchor gives the row start that a local end counts from
     int64_t *pat = Z->pattern(), *end = Z->end();
     const int64_t *ro = Z->overlapping ? Z->row_offsets() : nullptr;

@@ -1,6 +1,7 @@
-// host_trie.hpp -- the host form of the anchored walk (at.hpp has the definition), for acx_match_at_host and
-// acx_segment_host: the compiled tables walked from the root along goto edges only, and the characters of a host haystack
-// for the entry points that speak in code points.  Host code only.
+// host_trie.hpp -- the host form of the anchored walk (at.hpp has the definition), for acx_match_at_host, acx_segment_host
+// and acx_wordpiece_host: the compiled tables walked from the root or from a node along goto edges only, the match kind's
+// choice among the candidates on that path (pick), and the characters of a host haystack for the entry points that speak in
+// code points.  Host code only.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -22,10 +23,11 @@ struct HostTrie {
         }
         return lo < end && A.in_byte[lo] == b ? lo : 0u;
     }
-    // every state with own patterns on the path from the root along h[p .. L), by depth: visit(state, depth) -> go on?
+    // every state with own patterns on the path from `node` (0: the root) along h[p .. L), by the depth below the node:
+    // visit(state, depth) -> go on?
     template <class Visit>
-    void walk(const uint8_t *h, uint64_t p, uint64_t L, Visit &&visit) const {
-        uint32_t s = 0;
+    void walk(const uint8_t *h, uint64_t p, uint64_t L, uint32_t node, Visit &&visit) const {
+        uint32_t s = node;
         for (uint64_t d = 0; p + d < L;) {
             const uint8_t b = h[p + d];
             s = child(s, fold ? acx::fold_byte(b) : b);
@@ -33,6 +35,24 @@ struct HostTrie {
             d++;
             if (A.own_off[s + 1] > A.own_off[s] && !visit(s, d)) return;
         }
+    }
+    // The match kind's choice, stated once: the candidate `kind` keeps among the patterns that go on from `node` with
+    // h[p .. L) -- match_at's result of the anchor (p, L) when node is the root; full: only candidates that end at L count,
+    // and the first of them is the answer.  false: no candidate; *end: where the kept one ends.
+    bool pick(const uint8_t *h, uint64_t p, uint64_t L, uint32_t node, int kind, bool full, int64_t *pid, uint64_t *end) const {
+        int64_t best = -1;
+        uint64_t best_end = 0;
+        walk(h, p, L, node, [&](uint32_t s, uint64_t d) {
+            if (full && p + d != L) return true;
+            const int64_t i = (int64_t)A.own_pid[A.own_off[s]]; // (the lists are in id order)
+            if (kind == ACX_MATCH_LEFTMOST_FIRST && !full && best >= 0 && best < i) return true;
+            best = i;
+            best_end = p + d;
+            return !(kind == ACX_MATCH_STANDARD || full);
+        });
+        *pid = best;
+        *end = best_end;
+        return best >= 0;
     }
 };
 

@@ -1,7 +1,8 @@
 // result_block.hpp -- what the stages behind the find pipeline (summaries, splice, columns, tally, row filter, scores) share: the
 // owner of a result's memory and the table of its parts, the layout of its block, the frame from a find to a stage's result
 // (find_stage) and its end (retire_find), the owner of the host route's records (HostFind), the checks of a stage's
-// arguments and the frames of its entry points.
+// arguments and the frames of its entry points -- and, at the end, the frames of the stages that run no find (the walkers:
+// at_api.cpp, seg_api.cpp, wp_api.cpp).
 // The stages' middles are their own (summary_api.cpp .. filter_api.cpp); no kernel includes this.
 #pragma once
 #include <initializer_list>
@@ -91,16 +92,7 @@ const void *part_ptr(const ResultBlock *R, int which, int n);
 // this form lacks (missing), bytes to copy and nowhere to ("null argument").  The texts are the result type's own.
 int part_copy(const ResultBlock *R, int which, int n, void *host_dst, const char *no_such, const char *missing = nullptr);
 
-// Carves one block of the cache into a stage's temporaries, in words: every part 256 bytes behind the previous one.
-struct Carver {
-    uint64_t at = 0;
-    uint64_t part(uint64_t words) {
-        const uint64_t here = at;
-        at += (words + 31) / 32 * 32;
-        return here;
-    }
-    uint64_t bytes() const { return std::max<uint64_t>(at, 32) * 8; }
-};
+using acx::Carver; // (stage_device.hpp: the walkers' plans carve with it too)
 
 // The end of a stage behind a find, whatever its outcome `rc`.  st: the stream the find and the stage ran on; r: the find's
 // result (null: an empty batch; a stage that keeps the counts has taken them out of r); R: the stage's result; t1, t2: the
@@ -339,6 +331,111 @@ int copy_down(int rc, T *D, T *R, uint64_t bytes, const char *what, T **out) {
     if (rc != ACX_OK) { free_result(R); return rc; }
     *out = R;
     return ACX_OK;
+}
+
+// ---- The stages that run NO find: the walkers (at_api.cpp, seg_api.cpp, wp_api.cpp).  They fold in
+// their loads, so none of these frames makes a folded copy: device_call and staged_call above are not theirs. ----
+
+// A host entry's haystack and offsets: bytes need an address (the refusal's text is the entry's), no offsets is ONE haystack
+// (*n_hay becomes 1), offsets rise from 0 to len.
+inline int host_rows(const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t *n_hay, const char *null_hay) {
+    if (len && !hay) return fail(ACX_EINVAL, null_hay);
+    if (offsets) return offsets_span(offsets, *n_hay, len);
+    if (*n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
+    *n_hay = 1;
+    return ACX_OK;
+}
+
+// What a *_host form refuses first, in this order: a null handle (`handles`: every pointer the form cannot do without),
+// flags() -- the form's own flags and values --, the match kind, kind() -- what the form asks of the kind --, host_rows.
+inline int any_kind() { return ACX_OK; }
+template <class Flags, class Kind>
+int host_form_args(bool handles, Flags &&flags, int match_kind, Kind &&kind, const uint8_t *hay, uint64_t len, const uint64_t *offsets,
+                   uint64_t *n_hay) {
+    if (!handles) return fail(ACX_EINVAL, "null argument");
+    int rc = flags();
+    if (rc != ACX_OK) return rc;
+    if (match_kind < ACX_MATCH_STANDARD || match_kind > ACX_MATCH_LEFTMOST_LONGEST) return fail(ACX_EINVAL, "unknown match kind");
+    if ((rc = kind()) != ACX_OK) return rc;
+    return host_rows(hay, len, offsets, n_hay, "null argument");
+}
+
+// What a *_device / *_into_device entry refuses behind its own flags and values: a null haystack, offsets beside a row
+// length, own() -- the entry's pointers and their alignment, in the entry's order --, then the segments' checks.  What the
+// entry refuses by sizes follows the call; then the lease (leased).
+template <class Own>
+int walk_device_args(const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay, uint64_t uniform_len, Own &&own,
+                     Segments *G) {
+    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
+    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
+    const int rc = own();
+    return rc != ACX_OK ? rc : make_segments(d_offsets, n_hay, uniform_len, len, G);
+}
+template <class Run>
+int leased(acx_automaton *a, Run &&run) {
+    Lease lease(a);
+    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
+    return run(lease.c);
+}
+
+// The two-pass frame of a stage whose result is sized by a count, behind a lease, on st:
+//   count(st, &temp, &total)  queues the counting pass and reads the total back: st has been waited for when it returns;
+//                             *temp: the stage's scratch, one block of the buffer cache, named as soon as it exists;
+//   Z->alloc()                Z: the stage's result, its shaping fields set but for the one `total` points to;
+//   emit(st, temp, total)     queues the emitting pass into Z's parts;
+// and retire_find ends the stage whatever the outcome, with temp and t2 (a temporary of the caller's that the kernels read,
+// or null).  Returns with the emitting pass in flight (Z->done).  *out: Z, which is freed on failure.
+template <class T, class Count, class Emit>
+int two_pass(hipStream_t st, T *Z, uint64_t *total, void *t2, T **out, Count &&count, Emit &&emit) {
+    *out = nullptr;
+    void *temp = nullptr;
+    int queued = count(st, &temp, total);
+    if (queued == ACX_OK) queued = Z->alloc();
+    if (queued == ACX_OK) queued = emit(st, temp, *total);
+    const int rc = retire_find(queued, st, nullptr, Z, temp, t2);
+    if (rc != ACX_OK) { free_result(Z); return rc; }
+    *out = Z;
+    return ACX_OK;
+}
+// ... and its twin without a result block, for the raw *_into_device entries: the count, the emitting pass into the caller's
+// columns if the total fits `cap`, then st is waited for -- complete when it returns, whatever the launches said -- and the
+// scratch goes back to the cache.  The passes' error comes first.
+template <class Count, class Emit>
+int two_pass_raw(int device, hipStream_t st, uint64_t cap, uint64_t *total, Count &&count, Emit &&emit) {
+    void *temp = nullptr;
+    int rc = count(st, &temp, total);
+    if (rc == ACX_OK && *total <= cap) rc = emit(st, temp, *total);
+    const hipError_t s = hipStreamSynchronize(st);
+    g_bufs.put(temp, device);
+    if (rc != ACX_OK) return rc;
+    return s == hipSuccess ? ACX_OK : hipfail(s, "hipStreamSynchronize");
+}
+
+// The staged device route of a host entry point, staged_call's mirror: the lease, the haystacks (and, for a batch, their
+// offsets) staged as they are; then run(ctx, segments, D) makes the device result *D from ctx->ws.hay, and the frame waits for
+// it under the lease (the staging buffers are the context's).  No batch: ONE haystack, no offsets.
+template <class T, class Run>
+int staged_walk(acx_automaton *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, T **D, Run &&run) {
+    Lease lease(a);
+    Ctx *c = lease.c;
+    if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
+    int rc = stage_host(a, c, hay, len, offsets, offsets ? n_hay + 1 : 0, false);
+    if (rc != ACX_OK) return rc;
+    rc = run(c, offsets ? Segments{c->ws.offsets, n_hay, 0} : Segments{nullptr, 1, 0}, D);
+    if (rc == ACX_OK) return (*D)->wait();
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+// ... and its end, whatever staged_walk returned (rc; D: the device result, null on failure): the host twin of D -- a new
+// result, shaped like D (T::shaped_like), allocated -- filled by copy_down.
+template <class T>
+int host_twin(int rc, T *D, const char *what, T **out) {
+    T *Z = rc == ACX_OK ? new_result<T>(D->device, false) : nullptr;
+    if (Z) {
+        Z->shaped_like(*D);
+        if ((rc = Z->alloc()) != ACX_OK) { free_result(Z); free_result(D); return rc; }
+    }
+    return copy_down(rc, D, Z, D ? D->block_bytes : 0, what, out);
 }
 
 } // namespace acxh

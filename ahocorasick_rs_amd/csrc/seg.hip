@@ -1,6 +1,7 @@
 // seg.hip -- the segmenter's kernels behind acx_segment / acx_segment_device / acx_segment_into_device (seg.hpp has the
 // definition and says what each kernel computes).  The find pipeline (kernels.hip) and the post-find stages are not touched:
-// the walk is k_at's (at_walk.hpp) over tables every handle has.
+// the walk is k_at's over tables every handle has, and the workgroup's steps around it -- the row marks, the suffix minimum, the
+// survivors' list, the rank -- are the walkers' shared ones (at_walk.hpp).
 //
 // RELIED ON: k_seg<COUNT> and k_seg<EMIT> compute the same step[] from the same bytes, so the ranks of the emit pass add up
 // to the counts the tree was built from.  A caller who writes the data between the two gets wrong pieces, but no store at or
@@ -18,7 +19,6 @@ namespace acx {
 constexpr uint32_t SEG_BPT = SEG_TILE / SEG_THREADS; // consecutive bytes of one thread in the limits and in the ranking
 constexpr uint32_t SEG_IPT = SEG_TILE / SEG_THREADS; // bytes of one thread, SEG_THREADS apart, in phase A's loads
 constexpr uint32_t SEG_WAVES = SEG_THREADS / 64;
-constexpr uint32_t SEG_FAR = 0xFFFFFFFFu;            // no mark behind this byte inside the tile
 constexpr int SEG_MODE_COUNT = 0, SEG_MODE_EMIT = 1;
 static_assert(SEG_THREADS == 256, "root_next is copied to LDS a word per thread; the entry map has a thread per entry");
 static_assert(SEG_BPT == 16, "a word of the bitmap holds the bits of two threads");
@@ -33,8 +33,6 @@ __device__ inline uint32_t seg_unit(const uint8_t *__restrict__ hay, uint64_t p,
     while (u < want && u < lim && (hay[p + u] & 0xC0) == 0x80) u++; // (p + u < p + lim <= L)
     return u;
 }
-
-__device__ inline void seg_mark(uint32_t *bits, uint32_t q) { atomicOr(&bits[q >> 5], 1u << (q & 31)); }
 
 // COUNT: map0[tile * E + e] = pieces << 16 | exit.  EMIT: entry0 / base0: the tile's true entry and the index of its first
 // piece; pattern, offsets: the result's columns, sized by `total`.
@@ -61,48 +59,21 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg(const AtTrie T, const uint8
     s_root[tid] = T.root_next[tid];
     if (tid < SEG_TILE / 32) s_bits[tid] = 0;
     if (tid == 0) s_n = 0;
-    if (R.off) { // the offsets inside the tile are those of index [s_cut[0], s_cut[1])
-        if (tid == 0) s_cut[0] = count_le(R.off, R.n + 1, tile);
-        if (tid == 64) s_cut[1] = count_lt(R.off, R.n + 1, tile_end);
-    }
+    walk_row_range<false>(R, tile, tile_end, tid, s_cut);
     __syncthreads();
 
-    // ---- A: the row starts inside the tile as marks; `tail`: where the row of a byte without a mark behind it ends
-    uint64_t tail = R.len;
-    if (R.off) {
-        const uint64_t a = s_cut[0], b = s_cut[1]; // (both <= R.n + 1: every index read is the offsets')
-        for (uint64_t i = a + tid; i < b; i += SEG_THREADS) {
-            const uint64_t v = R.off[i];
-            if (v > tile && v < tile_end) seg_mark(s_bits, (uint32_t)(v - tile));
-        }
-        if (b <= R.n) tail = std::min<uint64_t>(R.off[b], R.len);
-    } else if (R.uniform_len) {
-        const uint64_t u = R.uniform_len, first = (tile / u + 1) * u; // the first row start behind the tile's first byte
-        if (u >= SEG_TILE) {
-            if (tid == 0 && first > tile && first < tile_end) seg_mark(s_bits, (uint32_t)(first - tile));
-        } else {
-            for (uint64_t v = first + tid * u; v < tile_end; v += SEG_THREADS * u) seg_mark(s_bits, (uint32_t)(v - tile));
-        }
-        tail = std::min<uint64_t>(((tile_end - 1) / u + 1) * u, R.len);
-    }
+    // ---- A: the row starts strictly behind the tile's first byte as marks (walk_row_marks); `tail`: where the row of a byte
+    // without a mark behind it ends
+    const uint64_t tail = walk_row_marks<false, SEG_THREADS, SEG_TILE>(R, tile, tile_end, tid, s_cut, s_bits);
     __syncthreads();
 
-    // ... every thread's first mark, a suffix minimum over the workgroup, and the limit of each of its 16 bytes
+    // ... every thread's first mark, a suffix minimum over the workgroup (walk_behind), and the limit of each of its 16 bytes
     {
         const uint32_t q0 = tid * SEG_BPT;
         const uint32_t bits = (s_bits[tid >> 1] >> (16 * (tid & 1))) & 0xFFFFu;
-        uint32_t v = bits ? q0 + (uint32_t)__builtin_ctz(bits) : SEG_FAR;
-#pragma unroll
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_down(v, d);
-            if (lane + d < 64) v = std::min(v, o);
-        }
-        if (lane == 0) s_w[wave] = v;
-        uint32_t behind = __shfl_down(v, 1); // the first mark behind this thread's bytes
-        if (lane == 63) behind = SEG_FAR;
+        uint32_t behind = walk_behind_wave(bits ? q0 + (uint32_t)__builtin_ctz(bits) : WALK_FAR, lane, wave, s_w);
         __syncthreads();
-#pragma unroll
-        for (uint32_t w = 0; w < SEG_WAVES; w++) behind = w > wave ? std::min(behind, s_w[w]) : behind;
+        behind = walk_behind<SEG_WAVES>(behind, wave, s_w); // the first mark behind this thread's bytes
 #pragma unroll
         for (uint32_t j = 0; j < SEG_BPT; j++) {
             const uint32_t q = q0 + j;
@@ -112,7 +83,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg(const AtTrie T, const uint8
                 const uint32_t next = m ? q + 1 + (uint32_t)__builtin_ctz(m) : behind;
                 const uint64_t p = tile + q;
                 // (a mark lies inside the data; tail <= len; wrong offsets may leave tail <= p: one byte, p + 1 <= len)
-                lim = next != SEG_FAR ? next - q : tail > p ? (uint32_t)std::min<uint64_t>(tail - p, 65535) : 1u;
+                lim = next != WALK_FAR ? next - q : tail > p ? (uint32_t)std::min<uint64_t>(tail - p, 65535) : 1u;
             }
             s_step[q] = (uint16_t)lim;
         }
@@ -120,7 +91,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg(const AtTrie T, const uint8
     __syncthreads();
     if (MODE == SEG_MODE_EMIT && tid < SEG_TILE / 32) s_bits[tid] = 0; // (the marks are spent: the flags of the piece starts)
 
-    // ... the first byte of every position; the survivors into the list
+    // ... the first byte of every position; the survivors into the list (walk_push)
 #pragma unroll
     for (uint32_t k = 0; k < SEG_IPT; k++) {
         const uint32_t slot = k * SEG_THREADS + tid;
@@ -135,25 +106,18 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg(const AtTrie T, const uint8
         }
         const bool survive = s1 != 0;
         s_pid[slot] = survive ? s1 : AT_NONE;
-        const uint64_t mask = __ballot(survive);
-        if (mask) { // (wave-uniform)
-            const int leader = __ffsll((unsigned long long)mask) - 1;
-            uint32_t at = 0;
-            if ((int)lane == leader) at = atomicAdd(&s_n, (uint32_t)__popcll(mask));
-            at = __shfl(at, leader);
-            if (survive) s_list[at + (uint32_t)__popcll(mask & ((1ull << lane) - 1))] = (uint16_t)slot;
-        }
+        walk_push(survive, slot, lane, &s_n, s_list);
     }
     __syncthreads();
 
-    // ... the walks, a survivor per lane: the match kind's choice, or the unknown unit
+    // ... the walks, a survivor per lane: the match kind's choice (at_best), or the unknown unit
     const uint32_t n_live = s_n; // (<= SEG_TILE: every slot is listed at most once)
     for (uint32_t j = tid; j < n_live; j += SEG_THREADS) {
         const uint32_t slot = s_list[j];
         const uint64_t p = tile + slot;
         const uint32_t lim = s_step[slot];
-        uint32_t best = AT_NONE, best_len = 0;
-        at_path(T, hay, p, lim, s_pid[slot], fold, [&](uint32_t q, uint32_t d) { return at_pick(T, q, d, kind, false, best, best_len); });
+        uint32_t best, best_len;
+        at_best(T, hay, p, lim, s_pid[slot], fold, kind, best, best_len);
         if (best == AT_NONE) best_len = seg_unit(hay, p, lim, hay[p], utf8);
         s_step[slot] = (uint16_t)best_len; // (1 <= best_len <= min(lim, E))
         s_pid[slot] = best;
@@ -198,7 +162,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg(const AtTrie T, const uint8
     // ---- EMIT: the piece starts are the positions on the chain from the true entry.  Round k holds every position's
     // 2^k-th successor; the marked positions mark theirs, which doubles the marked stretch of the chain (a position marked
     // in the same round may mark too: its successor is on the chain as well); then the successors are squared into the other
-    // buffer.  The workgroup ranks the marks and stores.
+    // buffer.  The workgroup ranks the marks (walk_rank) and stores.
     const uint32_t q0 = tid * SEG_BPT;
     {
 #pragma unroll
@@ -217,7 +181,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg(const AtTrie T, const uint8
             more = 0;
             for (uint32_t m = (s_bits[tid >> 1] >> (16 * (tid & 1))) & 0xFFFFu; m; m &= m - 1) {
                 const uint32_t t = s_half[cur][q0 + (uint32_t)__builtin_ctz(m)];
-                if (t < in_tile) seg_mark(s_bits, t);
+                if (t < in_tile) walk_mark(s_bits, t);
             }
 #pragma unroll
             for (uint32_t k = 0; k < SEG_IPT; k++) {
@@ -232,18 +196,9 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg(const AtTrie T, const uint8
     }
     const uint32_t bits = (s_bits[tid >> 1] >> (16 * (tid & 1))) & 0xFFFFu;
     const uint32_t c = (uint32_t)__popc(bits);
-    uint32_t inc = c;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(inc, d);
-        if (lane >= d) inc += up;
-    }
-    if (lane == 63) s_w[wave] = inc; // (s_w's minima were read before the barriers above)
+    const uint32_t inc = walk_rank_wave(c, lane, wave, s_w); // (s_w's minima were read before the barriers above)
     __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < SEG_WAVES; w++) before += w < wave ? s_w[w] : 0;
-    uint64_t at = base0[blockIdx.x] + before + inc - c; // the rank of this thread's first piece
+    uint64_t at = base0[blockIdx.x] + walk_rank<SEG_WAVES>(inc, c, wave, s_w); // the rank of this thread's first piece
     for (uint32_t t = bits; t; t &= t - 1, at++) {
         const uint32_t q = q0 + (uint32_t)__builtin_ctz(t);
         if (at >= total) break;
@@ -312,13 +267,6 @@ __global__ __launch_bounds__(SEG_THREADS) void k_seg_resolve(const uint32_t *__r
     }
 }
 
-__global__ __launch_bounds__(SEG_THREADS) void k_seg_rows(const RowCut R, const int64_t *__restrict__ offsets, const uint64_t total,
-                                                          int64_t *__restrict__ row_offsets) {
-    const uint64_t r = (uint64_t)blockIdx.x * SEG_THREADS + threadIdx.x;
-    if (r > R.n) return;
-    row_offsets[r] = (int64_t)(r == R.n ? total : std::min<uint64_t>(count_lt(offsets, total, row_begin(R, r)), total));
-}
-
 namespace {
 inline uint32_t *u32_at(uint64_t *scratch, uint64_t word) { return (uint32_t *)(scratch + word); }
 inline dim3 grid_of(uint64_t threads) { return dim3((uint32_t)tiles_of(threads, SEG_THREADS)); }
@@ -346,12 +294,6 @@ hipError_t seg_count(const AtTrie &T, const uint8_t *hay, const RowCut &R, int k
     return hipGetLastError();
 }
 
-hipError_t seg_rows(const RowCut &R, const int64_t *offsets, uint64_t total, int64_t *row_offsets, hipStream_t st) {
-    if (!row_offsets || R.n >= (1ull << 38)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_seg_rows, grid_of(R.n + 1), dim3(SEG_THREADS), 0, st, R, offsets, total, row_offsets);
-    return hipGetLastError();
-}
-
 hipError_t seg_emit(const AtTrie &T, const uint8_t *hay, const RowCut &R, int kind, uint32_t flags, const SegPlan &P,
                     uint64_t *scratch, uint64_t total, int64_t *pattern, int64_t *offsets, int64_t *row_offsets, hipStream_t st) {
     if (!plan_ok(P, R, hay, scratch) || !pattern || !offsets) return hipErrorInvalidValue;
@@ -370,7 +312,7 @@ hipError_t seg_emit(const AtTrie &T, const uint8_t *hay, const RowCut &R, int ki
     hipLaunchKernelGGL(k_seg<SEG_MODE_EMIT>, dim3((uint32_t)P.ntiles), dim3(SEG_THREADS), 0, st, T, hay, R, kind, flags, P.E, nullptr,
                        u32_at(scratch, P.entry[0]), scratch + P.base[0], total, pattern, offsets);
     const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : seg_rows(R, offsets, total, row_offsets, st);
+    return e != hipSuccess ? e : piece_rows(R, offsets, total, row_offsets, st);
 }
 
 } // namespace acx

@@ -24,10 +24,11 @@
 // THE KERNELS, all on the caller's stream; 64-bit positions in the data, 32-bit ones within a tile; plain vector stores, no
 // atomics on global memory; no workgroup waits for another and no serial loop runs over all tiles:
 //   k_seg<COUNT>  a workgroup per tile of SEG_TILE bytes.
-//     A. step[q], pid[q] for EVERY byte q of the tile, in LDS: the row limit (the row starts inside the tile are marked in a
-//        bitmap, every thread takes the first mark of its 16 bytes and a suffix minimum runs over the workgroup), the first
-//        byte through root_next in LDS, the survivors compacted into a list, walked by dense lanes with the walk of k_at
-//        (at_walk.hpp) -- it may read beyond the tile, up to the row's end.  step is the match length or u: at least 1, and
+//     A. step[q], pid[q] for EVERY byte q of the tile, in LDS: the row limit (the row starts behind the tile's first byte are
+//        marked in a bitmap, every thread takes the first mark of its 16 bytes and a suffix minimum runs over the workgroup),
+//        the first byte through root_next in LDS, the survivors compacted into a list, walked by dense lanes with the walk
+//        of k_at -- it may read beyond the tile, up to the row's end.  The marks, the minimum, the list and the walk are
+//        at_walk.hpp's: walk_row_marks<false>, walk_behind, walk_push, at_best.  step is the match length or u: at least 1, and
 //        p + step never passes the row's end.
 //     B. the ENTRY MAP: a chain that enters the tile lands at a tile offset e < E (E: the largest step -- max_pattern_len,
 //        at least 4 with SEG_UTF8); the map says where in the next tile the chain from e lands and how many pieces it began
@@ -44,10 +45,11 @@
 //   k_seg<EMIT>   phase A again (as at_emit walks again); the piece starts are the positions on the chain from the tile's
 //     true entry: round k holds every position's 2^k-th successor (two 16-bit buffers swing), the flagged positions flag
 //     theirs -- the flagged stretch of the chain doubles -- and the successors are squared; 13 rounds at most.  The
-//     workgroup ranks the flags (popcounts in the lane, a scan across the wave, the waves' sums through LDS: rows.hip's
-//     form) and stores offsets[base + rank] and pattern[base + rank]: every entry is written by exactly one thread, none
-//     at or beyond T.  One thread stores offsets[T] = len.
-//   k_seg_rows    a thread per row: row_offsets[r] = count_lt(offsets, T, row_begin(r)), clamped into [0, T].
+//     workgroup ranks the flags (popcounts in the lane, then walk_rank of at_walk.hpp: a scan across the wave, the waves'
+//     sums through LDS) and stores offsets[base + rank] and pattern[base + rank]: every entry is written by exactly one
+//     thread, none at or beyond T.  One thread stores offsets[T] = len.
+//   k_piece_rows  (at.hip, piece_rows) a thread per row: row_offsets[r] = count_lt(offsets, T, row_begin(r)), clamped into
+//     [0, T].
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -93,25 +95,21 @@ inline SegPlan seg_plan(uint64_t len, uint32_t max_len, uint32_t flags) {
     P.ntiles = tiles_of(len, SEG_TILE);
     P.E = max_len > 1 ? max_len : 1;
     if ((flags & SEG_UTF8) && P.E < 4) P.E = 4;
-    auto part = [&](uint64_t words) {
-        const uint64_t here = P.words;
-        P.words += (words + 31) / 32 * 32;
-        return here;
-    };
+    Carver C;
     P.n[0] = P.ntiles;
-    P.map0 = part((P.ntiles * P.E + 1) / 2);
-    P.entry[0] = part((P.ntiles + 1) / 2);
-    P.base[0] = part(P.ntiles);
+    P.map0 = C.part((P.ntiles * P.E + 1) / 2);
+    P.entry[0] = C.part((P.ntiles + 1) / 2);
+    P.base[0] = C.part(P.ntiles);
     for (int l = 1; l < SEG_MAX_LEVELS && P.ntiles; l++) {
         P.n[l] = tiles_of(P.n[l - 1], SEG_FAN);
-        P.exits[l] = part((P.n[l] * P.E + 1) / 2);
-        P.counts[l] = part(P.n[l] * P.E);
-        P.entry[l] = part((P.n[l] + 1) / 2);
-        P.base[l] = part(P.n[l]);
+        P.exits[l] = C.part((P.n[l] * P.E + 1) / 2);
+        P.counts[l] = C.part(P.n[l] * P.E);
+        P.entry[l] = C.part((P.n[l] + 1) / 2);
+        P.base[l] = C.part(P.n[l]);
         P.levels = l;
         if (P.n[l] == 1) break;
     }
-    if (!P.words) P.words = 32;
+    P.words = C.words();
     return P;
 }
 
@@ -120,11 +118,9 @@ inline SegPlan seg_plan(uint64_t len, uint32_t max_len, uint32_t flags) {
 hipError_t seg_count(const AtTrie &T, const uint8_t *hay, const RowCut &R, int kind, uint32_t flags, const SegPlan &P,
                      uint64_t *scratch, hipStream_t st);
 inline const uint64_t *seg_total(const SegPlan &P, const uint64_t *scratch) { return scratch + P.counts[P.levels]; }
-// ... and from there, over the SAME inputs: the down-sweep, k_seg<EMIT> and k_seg_rows.  total: what seg_total gave;
+// ... and from there, over the SAME inputs: the down-sweep, k_seg<EMIT> and piece_rows.  total: what seg_total gave;
 // pattern: total words, offsets: total + 1 words, row_offsets: R.n + 1 words, 8-byte aligned; every entry is written.
 hipError_t seg_emit(const AtTrie &T, const uint8_t *hay, const RowCut &R, int kind, uint32_t flags, const SegPlan &P,
                     uint64_t *scratch, uint64_t total, int64_t *pattern, int64_t *offsets, int64_t *row_offsets, hipStream_t st);
-// the rows alone (len == 0: no piece; offsets[0] = 0 is the caller's to store): row_offsets[0 .. R.n] from offsets[0 .. total)
-hipError_t seg_rows(const RowCut &R, const int64_t *offsets, uint64_t total, int64_t *row_offsets, hipStream_t st);
 
 } // namespace acx

@@ -1,6 +1,7 @@
 // seg_api.cpp -- greedy segmentation by the dictionary (seg.hpp has the definition): the host form of the definition, the
 // device stage, the acx_segment* entry points and the accessors of their result.  No find runs: the chain reads the trie
-// edges and the own lists every handle has.
+// edges and the own lists every handle has.  The entries' preambles, the two-pass frames, the staged route and the host twin
+// are the walkers' shared ones (result_block.hpp), the match kind's choice on the host is HostTrie::pick.
 #include "seg.hpp"
 #include "host_trie.hpp"
 #include "result_block.hpp"
@@ -17,6 +18,7 @@ struct ACX_HIDDEN acx_seg : ResultBlock {
     int64_t *pattern() const { return at<int64_t>(PATTERN); }
     int64_t *offsets() const { return at<int64_t>(OFFSETS); }
     int64_t *row_offsets() const { return at<int64_t>(ROW_OFFSETS); }
+    void shaped_like(const acx_seg &D) { pieces = D.pieces; rows = D.rows; }
 };
 
 namespace {
@@ -34,70 +36,50 @@ uint32_t kernel_flags(const acx_automaton *a, uint32_t flags) {
     return ((flags & ACX_SEG_UTF8) ? acx::SEG_UTF8 : 0u) | (folds(a) ? acx::SEG_FOLD : 0u);
 }
 
-// The counting half of the device stage on st: k_seg<COUNT>, the tree, and T -- 8 bytes cross the bus, the stream is waited
-// for.  *temp: the stage's scratch, one block of the buffer cache -- the caller's to return, behind the stage's kernels.
-int seg_count_stage(acx_automaton *a, hipStream_t st, const uint8_t *d_hay, const acx::RowCut &R, uint32_t kf, acx::SegPlan *P,
-                    void **temp, uint64_t *total) {
-    *total = 0;
-    if (!R.len) return ACX_OK;
-    *P = acx::seg_plan(R.len, a->host.max_len, kf);
-    HIPCHK(g_bufs.get(temp, P->words * 8, a->device));
-    uint64_t *scratch = (uint64_t *)*temp;
-    HIPCHK(acx::seg_count(acx::at_trie(a->dev), d_hay, R, a->host.match_kind, kf, *P, scratch, st));
-    HIPCHK(hipMemcpyAsync(total, acx::seg_total(*P, scratch), 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (*total > R.len) return fail(ACX_EDEVICE, "the tiles' counts do not sum to a number of pieces");
-    return ACX_OK;
-}
+// The device stage on st as the two passes of two_pass / two_pass_raw.  count: k_seg<COUNT>, the tree, and T -- 8 bytes cross
+// the bus, the stream is waited for; *temp: the stage's scratch, one block of the buffer cache.  emit: into columns sized by
+// `total`, every word of the three is written.
+struct SegStage {
+    acx_automaton *a;
+    const uint8_t *d_hay;
+    acx::RowCut R;
+    uint32_t kf;
+    acx::SegPlan P{};
 
-// ... and the emitting half into columns sized by `total`: every word of the three is written
-int seg_emit_stage(acx_automaton *a, hipStream_t st, const uint8_t *d_hay, const acx::RowCut &R, uint32_t kf, const acx::SegPlan &P,
-                   void *temp, uint64_t total, int64_t *pattern, int64_t *offsets, int64_t *row_offsets) {
-    if (!R.len) { // no piece: offsets[0] = len = 0, every row begins at piece 0
-        HIPCHK(hipMemsetAsync(offsets, 0, 8, st));
-        HIPCHK(hipMemsetAsync(row_offsets, 0, (R.n + 1) * 8, st));
+    int count(hipStream_t st, void **temp, uint64_t *total) {
+        *total = 0;
+        if (!R.len) return ACX_OK;
+        P = acx::seg_plan(R.len, a->host.max_len, kf);
+        HIPCHK(g_bufs.get(temp, P.words * 8, a->device));
+        uint64_t *scratch = (uint64_t *)*temp;
+        HIPCHK(acx::seg_count(acx::at_trie(a->dev), d_hay, R, a->host.match_kind, kf, P, scratch, st));
+        HIPCHK(hipMemcpyAsync(total, acx::seg_total(P, scratch), 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return *total > R.len ? fail(ACX_EDEVICE, "the tiles' counts do not sum to a number of pieces") : ACX_OK;
+    }
+    int emit(hipStream_t st, void *temp, uint64_t total, int64_t *pattern, int64_t *offsets, int64_t *row_offsets) const {
+        if (!R.len) { // no piece: offsets[0] = len = 0, every row begins at piece 0
+            HIPCHK(hipMemsetAsync(offsets, 0, 8, st));
+            HIPCHK(hipMemsetAsync(row_offsets, 0, (R.n + 1) * 8, st));
+            return ACX_OK;
+        }
+        HIPCHK(acx::seg_emit(acx::at_trie(a->dev), d_hay, R, a->host.match_kind, kf, P, (uint64_t *)temp, total, pattern, offsets,
+                             row_offsets, st));
         return ACX_OK;
     }
-    HIPCHK(acx::seg_emit(acx::at_trie(a->dev), d_hay, R, a->host.match_kind, kf, P, (uint64_t *)temp, total, pattern, offsets,
-                         row_offsets, st));
-    return ACX_OK;
-}
+};
 
 // The device route under a lease: the stage on the context's stream, a device result.  Returns when T is known, with the
 // emitting half in flight (Z->done).  d_hay and the offsets must stay valid until then.
 int run_seg(acx_automaton *a, Ctx *c, const uint8_t *d_hay, uint64_t len, const Segments &G, uint32_t flags, acx_seg **out) {
     *out = nullptr;
-    const acx::RowCut R = row_cut(G, len);
+    SegStage S{a, d_hay, row_cut(G, len), kernel_flags(a, flags)};
     acx_seg *Z = new_result<acx_seg>(a->device, true);
     if (!Z) return ACX_ENOMEM;
-    Z->rows = R.n;
-    const uint32_t kf = kernel_flags(a, flags);
-    acx::SegPlan P;
-    void *temp = nullptr;
-    int queued = seg_count_stage(a, c->stream, d_hay, R, kf, &P, &temp, &Z->pieces);
-    if (queued == ACX_OK) queued = Z->alloc();
-    if (queued == ACX_OK) queued = seg_emit_stage(a, c->stream, d_hay, R, kf, P, temp, Z->pieces, Z->pattern(), Z->offsets(), Z->row_offsets());
-    const int rc = retire_find(queued, c->stream, nullptr, Z, temp);
-    if (rc != ACX_OK) { free_result(Z); return rc; }
-    *out = Z;
-    return ACX_OK;
-}
-
-// the host form of step 1: the match_at result of the anchor (p, L) under `kind`; false: no pattern begins at p
-bool host_pick(const HostTrie &T, const uint8_t *h, uint64_t p, uint64_t L, int kind, int64_t *pid, uint64_t *end) {
-    const acx::Automaton &H = T.A;
-    int64_t best = -1;
-    uint64_t best_end = 0;
-    T.walk(h, p, L, [&](uint32_t s, uint64_t d) {
-        const int64_t i = (int64_t)H.own_pid[H.own_off[s]]; // (the lists are in id order)
-        if (kind == ACX_MATCH_LEFTMOST_FIRST && best >= 0 && best < i) return true;
-        best = i;
-        best_end = p + d;
-        return kind != ACX_MATCH_STANDARD;
-    });
-    *pid = best;
-    *end = best_end;
-    return best >= 0;
+    Z->rows = S.R.n;
+    return two_pass(
+        c->stream, Z, &Z->pieces, nullptr, out, [&](hipStream_t st, void **temp, uint64_t *total) { return S.count(st, temp, total); },
+        [&](hipStream_t st, void *temp, uint64_t total) { return S.emit(st, temp, total, Z->pattern(), Z->offsets(), Z->row_offsets()); });
 }
 
 // ... and of step 3: the unknown unit at p < L
@@ -117,18 +99,9 @@ extern "C" {
 int acx_segment_host(const acx_host_automaton_t *h, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay,
                      uint32_t flags, int match_kind, uint64_t cap, int64_t *pattern, int64_t *offsets_out, int64_t *row_offsets,
                      uint64_t *n_pieces) {
-    if (!h || !n_pieces) return fail(ACX_EINVAL, "null argument");
-    *n_pieces = 0;
-    int rc = seg_flags(flags);
+    if (n_pieces) *n_pieces = 0;
+    int rc = host_form_args(h && n_pieces, [&] { return seg_flags(flags); }, match_kind, any_kind, hay, len, offsets, &n_hay);
     if (rc != ACX_OK) return rc;
-    if (match_kind < ACX_MATCH_STANDARD || match_kind > ACX_MATCH_LEFTMOST_LONGEST) return fail(ACX_EINVAL, "unknown match kind");
-    if (len && !hay) return fail(ACX_EINVAL, "null argument");
-    if (!offsets) {
-        if (n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
-        n_hay = 1;
-    } else if ((rc = offsets_span(offsets, n_hay, len)) != ACX_OK) {
-        return rc;
-    }
     if (cap && (!pattern || !offsets_out || !row_offsets)) return fail(ACX_EINVAL, "null argument");
     if ((rc = seg_sizes(h->host.max_len, len, n_hay)) != ACX_OK) return rc;
     const HostTrie T{h->host, (h->flags & ACX_BUILD_ASCII_CASE_INSENSITIVE) != 0};
@@ -142,7 +115,7 @@ int acx_segment_host(const acx_host_automaton_t *h, const uint8_t *hay, uint64_t
             for (uint64_t p = b; p < L; t++) {
                 int64_t pid;
                 uint64_t e;
-                if (!host_pick(T, hay, p, L, match_kind, &pid, &e)) e = p + host_unit(hay, p, L, utf8);
+                if (!T.pick(hay, p, L, 0, match_kind, false, &pid, &e)) e = p + host_unit(hay, p, L, utf8);
                 if (pass) { pattern[t] = pid; offsets_out[t] = (int64_t)p; }
                 p = e;
             }
@@ -160,16 +133,11 @@ int acx_segment_device(acx_automaton_t *a, const void *d_hay, uint64_t len, cons
     *out = nullptr;
     int rc = seg_flags(flags);
     if (rc != ACX_OK) return rc;
-    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
-    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
-    if ((uintptr_t)d_offsets & 7) return fail(ACX_EINVAL, "offsets must be 8-byte aligned");
     Segments G;
-    if ((rc = make_segments(d_offsets, n_hay, uniform_len, len, &G)) != ACX_OK) return rc;
-    if ((rc = seg_sizes(a->host.max_len, len, rows_of(G).n)) != ACX_OK) return rc;
-    Lease lease(a);
-    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    // (a case-insensitive handle folds in the walk's loads: no folded copy of the data)
-    return run_seg(a, lease.c, (const uint8_t *)d_hay, len, G, flags, out);
+    rc = walk_device_args(d_hay, len, d_offsets, n_hay, uniform_len,
+                          [&] { return (uintptr_t)d_offsets & 7 ? fail(ACX_EINVAL, "offsets must be 8-byte aligned") : ACX_OK; }, &G);
+    if (rc != ACX_OK || (rc = seg_sizes(a->host.max_len, len, rows_of(G).n)) != ACX_OK) return rc;
+    return leased(a, [&](Ctx *c) { return run_seg(a, c, (const uint8_t *)d_hay, len, G, flags, out); });
 }
 
 int acx_segment_into_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
@@ -179,28 +147,20 @@ int acx_segment_into_device(acx_automaton_t *a, const void *d_hay, uint64_t len,
     *n_pieces = 0;
     int rc = seg_flags(flags);
     if (rc != ACX_OK) return rc;
-    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
-    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
-    if (((uintptr_t)d_offsets | (uintptr_t)d_pattern | (uintptr_t)d_offsets_out | (uintptr_t)d_row_offsets) & 7)
-        return fail(ACX_EINVAL, "offsets and the three columns must be 8-byte aligned");
-    if (!d_offsets_out || !d_row_offsets || (cap && !d_pattern)) return fail(ACX_EINVAL, "null argument");
     Segments G;
-    if ((rc = make_segments(d_offsets, n_hay, uniform_len, len, &G)) != ACX_OK) return rc;
-    const acx::RowCut R = row_cut(G, len);
-    if ((rc = seg_sizes(a->host.max_len, len, R.n)) != ACX_OK) return rc;
-    Lease lease(a);
-    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    const hipStream_t st = lease.c->stream;
-    const uint32_t kf = kernel_flags(a, flags);
-    acx::SegPlan P;
-    void *temp = nullptr;
-    rc = seg_count_stage(a, st, (const uint8_t *)d_hay, R, kf, &P, &temp, n_pieces);
-    if (rc == ACX_OK && *n_pieces <= cap)
-        rc = seg_emit_stage(a, st, (const uint8_t *)d_hay, R, kf, P, temp, *n_pieces, d_pattern, d_offsets_out, d_row_offsets);
-    const hipError_t s = hipStreamSynchronize(st); // (complete when it returns, whatever the launches said)
-    g_bufs.put(temp, a->device);
+    rc = walk_device_args(d_hay, len, d_offsets, n_hay, uniform_len, [&] {
+        if (((uintptr_t)d_offsets | (uintptr_t)d_pattern | (uintptr_t)d_offsets_out | (uintptr_t)d_row_offsets) & 7)
+            return fail(ACX_EINVAL, "offsets and the three columns must be 8-byte aligned");
+        return !d_offsets_out || !d_row_offsets || (cap && !d_pattern) ? fail(ACX_EINVAL, "null argument") : ACX_OK;
+    }, &G);
     if (rc != ACX_OK) return rc;
-    return s == hipSuccess ? ACX_OK : hipfail(s, "hipStreamSynchronize");
+    SegStage S{a, (const uint8_t *)d_hay, row_cut(G, len), kernel_flags(a, flags)};
+    if ((rc = seg_sizes(a->host.max_len, len, S.R.n)) != ACX_OK) return rc;
+    return leased(a, [&](Ctx *c) {
+        return two_pass_raw(
+            a->device, c->stream, cap, n_pieces, [&](hipStream_t st, void **temp, uint64_t *total) { return S.count(st, temp, total); },
+            [&](hipStream_t st, void *temp, uint64_t total) { return S.emit(st, temp, total, d_pattern, d_offsets_out, d_row_offsets); });
+    });
 }
 
 int acx_segment(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, uint32_t flags,
@@ -210,36 +170,16 @@ int acx_segment(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint
     int rc = seg_flags(flags);
     if (rc != ACX_OK) return rc;
     if (codepoints) flags |= ACX_SEG_UTF8;
-    if (len && !hay) return fail(ACX_EINVAL, "null haystack");
-    const bool batch = offsets != nullptr;
-    if (!batch) {
-        if (n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
-        n_hay = 1;
-    } else if ((rc = offsets_span(offsets, n_hay, len)) != ACX_OK) {
-        return rc;
-    }
+    if ((rc = host_rows(hay, len, offsets, &n_hay, "null haystack")) != ACX_OK) return rc;
     if ((rc = seg_sizes(a->host.max_len, len, n_hay)) != ACX_OK) return rc;
     // the data (and, for a batch, its offsets) through the context's staging buffers; the same kernels; the block comes home
     // in one copy
     acx_seg *D = nullptr;
-    {
-        Lease lease(a);
-        Ctx *c = lease.c;
-        if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-        if ((rc = stage_host(a, c, hay, len, batch ? offsets : nullptr, batch ? n_hay + 1 : 0, false)) != ACX_OK) return rc;
-        const Segments G = batch ? Segments{c->ws.offsets, n_hay, 0} : Segments{nullptr, 1, 0};
-        rc = run_seg(a, c, c->ws.hay, len, G, flags, &D);
-        if (rc == ACX_OK) rc = D->wait(); // (the staging buffers are the context's)
-        else (void)hipStreamSynchronize(c->stream);
-    }
-    acx_seg *Z = rc == ACX_OK ? new_result<acx_seg>(a->device, false) : nullptr;
-    if (Z) {
-        Z->pieces = D->pieces;
-        Z->rows = D->rows;
-        if ((rc = Z->alloc()) != ACX_OK) { free_result(Z); free_result(D); return rc; }
-    }
-    if ((rc = copy_down(rc, D, Z, D ? D->block_bytes : 0, "the segments' copy", out)) != ACX_OK) return rc;
+    rc = staged_walk(a, hay, len, offsets, n_hay, &D,
+                     [&](Ctx *c, const Segments &G, acx_seg **dev) { return run_seg(a, c, c->ws.hay, len, G, flags, dev); });
+    if ((rc = host_twin(rc, D, "the segments' copy", out)) != ACX_OK) return rc;
     if (!codepoints) return ACX_OK;
+    acx_seg *Z = *out;
     // boundaries in characters: the characters that begin before each
     std::vector<uint64_t> cs;
     if ((rc = char_starts(hay, len, &cs)) != ACX_OK) { free_result(Z); *out = nullptr; return rc; }

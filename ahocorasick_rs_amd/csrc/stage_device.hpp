@@ -1,6 +1,7 @@
 // stage_device.hpp -- what the device stages behind the find pipeline (replace, filter, score, mask, spans, snippets) share:
 // how a byte range is cut into rows, the searches in an ascending array, the funnel shift of the gathers, and the bounds of
-// a tile -- of the output's bytes, or of the records -- with the size of the scratch that holds them.  Everything here is
+// a tile -- of the output's bytes, or of the records -- with the size of the scratch that holds them, and the carver of a
+// stage's temporaries (the walkers' plans, at.hpp .. wp.hpp, use it as the stages' API units do).  Everything here is
 // inline or constexpr: any number of units include it, and a .cpp takes the struct and the sizes (the device functions are
 // the HIP compiler's).
 #pragma once
@@ -25,6 +26,19 @@ struct RowCut {
 constexpr uint64_t tiles_of(uint64_t n, uint64_t tile) { return (n + tile - 1) / tile; }
 constexpr uint64_t out_tile_words(uint64_t total, uint64_t tile) { return 2 * (tiles_of(total, tile) + 1); }
 constexpr uint64_t rec_tile_words(uint64_t n, uint64_t tile) { return 2 * tiles_of(n, tile); }
+
+// Carves one block of the buffer cache into a stage's temporaries, in u64 words: every part a multiple of 256 bytes behind the
+// previous one, the block at least 256 bytes.
+struct Carver {
+    uint64_t at = 0;
+    uint64_t part(uint64_t words) {
+        const uint64_t here = at;
+        at += (words + 31) / 32 * 32;
+        return here;
+    }
+    uint64_t words() const { return std::max<uint64_t>(at, 32); }
+    uint64_t bytes() const { return words() * 8; }
+};
 
 #ifdef __HIPCC__
 

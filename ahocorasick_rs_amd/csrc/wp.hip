@@ -1,6 +1,7 @@
 // wp.hip -- the WordPiece kernels behind acx_wordpiece / acx_wordpiece_device / acx_wordpiece_into_device (wp.hpp has the
 // definition and says what each kernel computes).  The find pipeline (kernels.hip), the post-find stages and the segmenter
-// (seg.hip) are not touched: the walk is k_at's (at_walk.hpp) over tables every handle has, the scan is replace_scan's.
+// (seg.hip) are not touched: the walk is k_at's over tables every handle has, the workgroup's steps around it -- the row marks,
+// the suffix minimum, the ranks -- are the walkers' shared ones (at_walk.hpp), the scan over the tiles is replace_scan's.
 //
 // RELIED ON: k_wp<COUNT> and k_wp<EMIT> compute the same words and the same piece counts from the same bytes, so the bases of
 // the emit pass add up to the counts the scan was made from.  A caller who writes the data between the two gets wrong pieces,
@@ -18,8 +19,7 @@ namespace acx {
 
 constexpr uint32_t WP_BPT = WP_TILE / WP_THREADS; // consecutive bytes of one thread
 constexpr uint32_t WP_WAVES = WP_THREADS / 64;
-constexpr uint32_t WP_FAR = 0xFFFFFFFFu;          // no boundary behind this byte inside the tile
-constexpr uint32_t WP_FAR16 = 0xFFFFu;            // ... as a word's end in LDS
+constexpr uint32_t WP_FAR16 = 0xFFFFu;            // no boundary behind this byte inside the tile (WALK_FAR), as a word's end in LDS
 constexpr uint32_t WP_UNK = 0x8000u;              // a word's count in LDS: the word is one unknown piece
 constexpr uint64_t WP_NONE = ~0ull;               // bound[tile]: the tile has no boundary
 constexpr uint64_t WP_PIECE = (uint64_t)WP_CARRY_THREADS * WP_CARRY_PER; // the tiles of one step of k_wp_carry
@@ -28,8 +28,6 @@ static_assert(WP_THREADS == 256, "root_next and cont_next are filled a word per 
 static_assert(WP_BPT == 16, "a thread's bytes are one 16-byte load; a word of the bitmap holds the bits of two threads");
 static_assert(WP_TILE + WP_MAX_WORD < WP_UNK && WP_TILE < WP_FAR16, "slots, ends, counts and bases are 16 bits wide");
 static_assert((WP_CARRY_THREADS & (WP_CARRY_THREADS - 1)) == 0, "the carry's doubling steps");
-
-__device__ inline void wp_mark(uint32_t *bits, uint32_t q) { atomicOr(&bits[q >> 5], 1u << (q & 31)); }
 
 // the 16 bytes at data position P, hay + P being 16-byte aligned; a position outside [0, len) is not read and gives 0
 __device__ inline uint4 wp_granule(const uint8_t *__restrict__ hay, uint64_t len, int64_t P) {
@@ -59,8 +57,8 @@ __device__ inline uint32_t wp_chain(const AtTrie &T, const uint8_t *__restrict__
         const uint32_t fb = fold ? fold_byte(b) : b;
         const uint32_t s = p == ws ? s_root[fb] : s_cont[fb];
         if (!s) return 0;
-        uint32_t best = AT_NONE, best_len = 0;
-        at_path(T, hay, p, (uint32_t)(we - p), s, fold, [&](uint32_t q, uint32_t d) { return at_pick(T, q, d, kind, false, best, best_len); });
+        uint32_t best, best_len;
+        at_best(T, hay, p, (uint32_t)(we - p), s, fold, kind, best, best_len);
         if (best == AT_NONE) return 0;
         if (STORE && at + k < total) {
             id[at + k] = (int64_t)best;
@@ -106,31 +104,12 @@ __global__ __launch_bounds__(WP_THREADS) void k_wp(const AtTrie T, const uint8_t
         s_cls[tid] = w;
     }
     if (tid < WP_TILE / 32) s_bits[tid] = 0;
-    if (R.off) { // the offsets inside the tile are those of index [s_cut[0], s_cut[1])
-        if (tid == 0) s_cut[0] = count_lt(R.off, R.n + 1, tile);
-        if (tid == 64) s_cut[1] = count_lt(R.off, R.n + 1, tile_end);
-    }
+    walk_row_range<true>(R, tile, tile_end, tid, s_cut);
     __syncthreads();
 
-    // ---- A: the row starts inside the tile as marks; `tail`: where the row of a byte without a mark behind it ends
-    uint64_t tail = R.len;
-    if (blockIdx.x == 0 && tid == 0) wp_mark(s_bits, 0); // (the data begins a row, whatever the offsets say)
-    if (R.off) {
-        const uint64_t a = s_cut[0], b = s_cut[1]; // (both <= R.n + 1: every index read is the offsets')
-        for (uint64_t i = a + tid; i < b; i += WP_THREADS) {
-            const uint64_t v = R.off[i];
-            if (v >= tile && v < tile_end) wp_mark(s_bits, (uint32_t)(v - tile));
-        }
-        if (b <= R.n) tail = std::min<uint64_t>(R.off[b], R.len);
-    } else if (R.uniform_len) {
-        const uint64_t u = R.uniform_len, first_row = (tile + u - 1) / u * u; // the first row start at or behind the tile's first byte
-        if (u >= WP_TILE) {
-            if (tid == 0 && first_row < tile_end) wp_mark(s_bits, (uint32_t)(first_row - tile));
-        } else {
-            for (uint64_t v = first_row + tid * u; v < tile_end; v += WP_THREADS * u) wp_mark(s_bits, (uint32_t)(v - tile));
-        }
-        tail = std::min<uint64_t>(((tile_end - 1) / u + 1) * u, R.len);
-    }
+    // ---- A: the row starts at or behind the tile's first byte as marks, the data's first byte among them (walk_row_marks);
+    // `tail`: where the row of a byte without a mark behind it ends
+    const uint64_t tail = walk_row_marks<true, WP_THREADS, WP_TILE>(R, tile, tile_end, tid, s_cut, s_bits);
 
     // ... the thread's 16 bytes and their classes as bit masks (bit j: byte q0 + j)
     const uint32_t q0 = tid * WP_BPT;
@@ -166,38 +145,27 @@ __global__ __launch_bounds__(WP_THREADS) void k_wp(const AtTrie T, const uint8_t
     const uint32_t bnd = (~wordb | rowb) & 0xFFFFu; // the boundaries; a slot behind the data is one
     const uint32_t startb = valid & ~spaceb & (rowb | aloneb | ~((wordb << 1) | prevw));
 
-    // ... every thread's first boundary, a suffix minimum over the workgroup; the word starts ranked in position order
-    uint32_t fbv = bnd ? q0 + (uint32_t)__builtin_ctz(bnd) : WP_FAR;
+    // ... every thread's first boundary, a suffix minimum over the workgroup (walk_behind); the word starts ranked in position
+    // order (walk_rank); both around one barrier
     const uint32_t c = (uint32_t)__popc(startb);
-    uint32_t inc = c;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_down(fbv, d);
-        if (lane + d < 64) fbv = std::min(fbv, o);
-        const uint32_t up = __shfl_up(inc, d);
-        if (lane >= d) inc += up;
-    }
-    if (lane == 0) s_wmin[wave] = fbv;
-    if (lane == 63) s_wsum[wave] = inc;
-    uint32_t behind = __shfl_down(fbv, 1); // the first boundary behind this thread's bytes
-    if (lane == 63) behind = WP_FAR;
+    uint32_t behind = walk_behind_wave(bnd ? q0 + (uint32_t)__builtin_ctz(bnd) : WALK_FAR, lane, wave, s_wmin);
+    const uint32_t inc = walk_rank_wave(c, lane, wave, s_wsum);
     __syncthreads();
-    uint32_t before = 0, n_words = 0, tile_first = WP_FAR;
+    behind = walk_behind<WP_WAVES>(behind, wave, s_wmin); // the first boundary behind this thread's bytes
+    uint32_t n_words = 0, tile_first = WALK_FAR;
 #pragma unroll
     for (uint32_t w = 0; w < WP_WAVES; w++) {
-        behind = w > wave ? std::min(behind, s_wmin[w]) : behind;
-        before += w < wave ? s_wsum[w] : 0u;
         n_words += s_wsum[w];
         tile_first = std::min(tile_first, s_wmin[w]);
     }
     {
-        uint32_t k = before + inc - c;
+        uint32_t k = walk_rank<WP_WAVES>(inc, c, wave, s_wsum);
         for (uint32_t m = startb; m; m &= m - 1, k++) {
             const uint32_t j = (uint32_t)__builtin_ctz(m), q = q0 + j;
             const uint32_t later = bnd >> (j + 1);
             const uint32_t e = (aloneb >> j) & 1u ? q + 1 : later ? q + 1 + (uint32_t)__builtin_ctz(later) : behind;
             s_list[k] = (uint16_t)q; // (k < n_words <= WP_TILE: the ranks of distinct slots)
-            s_wend[k] = (uint16_t)(e == WP_FAR ? WP_FAR16 : e);
+            s_wend[k] = (uint16_t)(e == WALK_FAR ? WP_FAR16 : e);
         }
     }
     __syncthreads();
@@ -239,27 +207,20 @@ __global__ __launch_bounds__(WP_THREADS) void k_wp(const AtTrie T, const uint8_t
             uint32_t sum = 0;
             for (uint32_t w = 0; w < WP_WAVES; w++) sum += s_wsum[w];
             counts[blockIdx.x] = sum;
-            bound[blockIdx.x] = tile_first == WP_FAR ? WP_NONE : tile + tile_first;
+            bound[blockIdx.x] = tile_first == WALK_FAR ? WP_NONE : tile + tile_first;
         }
         return;
     }
 
-    // ---- EMIT: the words' bases -- every thread sums 16 consecutive words of the list, the sums are scanned -- and the stores
+    // ---- EMIT: the words' bases -- every thread sums 16 consecutive words of the list, the sums are ranked (walk_rank) -- and
+    // the stores
     __syncthreads();
     {
         uint32_t sum = 0;
         for (uint32_t k = 0; k < WP_BPT; k++) sum += q0 + k < n_words ? (s_cnt[q0 + k] & (WP_UNK - 1u)) : 0u;
-        uint32_t run = sum;
-#pragma unroll
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(run, d);
-            if (lane >= d) run += up;
-        }
-        if (lane == 63) s_wsum[wave] = run;
+        const uint32_t run = walk_rank_wave(sum, lane, wave, s_wsum);
         __syncthreads();
-        uint32_t at = run - sum;
-#pragma unroll
-        for (uint32_t w = 0; w < WP_WAVES; w++) at += w < wave ? s_wsum[w] : 0u;
+        uint32_t at = walk_rank<WP_WAVES>(run, sum, wave, s_wsum);
         for (uint32_t k = 0; k < WP_BPT && q0 + k < n_words; k++) {
             s_base[q0 + k] = (uint16_t)at; // (at most WP_TILE + WP_MAX_WORD)
             at += s_cnt[q0 + k] & (WP_UNK - 1u);
@@ -323,28 +284,16 @@ __global__ __launch_bounds__(WP_CARRY_THREADS) void k_wp_carry(const uint64_t *_
     }
 }
 
-__global__ __launch_bounds__(WP_THREADS) void k_wp_rows(const RowCut R, const int64_t *__restrict__ start, const uint64_t total,
-                                                        int64_t *__restrict__ row_offsets) {
-    const uint64_t r = (uint64_t)blockIdx.x * WP_THREADS + threadIdx.x;
-    if (r > R.n) return;
-    row_offsets[r] = (int64_t)(r == R.n ? total : std::min<uint64_t>(count_lt(start, total, row_begin(R, r)), total));
-}
-
 WpPlan wp_plan(uint64_t len) {
     WpPlan P;
     P.ntiles = tiles_of(len, WP_TILE);
-    P.words = 0;
-    auto part = [&](uint64_t words) {
-        const uint64_t here = P.words;
-        P.words += (words + 31) / 32 * 32;
-        return here;
-    };
-    P.counts = part(P.ntiles);
-    P.bound = part(P.ntiles);
-    P.carry = part(P.ntiles);
-    P.base = part(P.ntiles + 1);
-    P.scan = part(replace_scan_words(P.ntiles));
-    if (!P.words) P.words = 32;
+    Carver C;
+    P.counts = C.part(P.ntiles);
+    P.bound = C.part(P.ntiles);
+    P.carry = C.part(P.ntiles);
+    P.base = C.part(P.ntiles + 1);
+    P.scan = C.part(replace_scan_words(P.ntiles));
+    P.words = C.words();
     return P;
 }
 
@@ -369,19 +318,13 @@ hipError_t wp_count(const AtTrie &T, const uint8_t *hay, const RowCut &R, const 
     return hipGetLastError();
 }
 
-hipError_t wp_rows(const RowCut &R, const int64_t *start, uint64_t total, int64_t *row_offsets, hipStream_t st) {
-    if (!row_offsets || R.n >= (1ull << 38)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_wp_rows, dim3((uint32_t)tiles_of(R.n + 1, WP_THREADS)), dim3(WP_THREADS), 0, st, R, start, total, row_offsets);
-    return hipGetLastError();
-}
-
 hipError_t wp_emit(const AtTrie &T, const uint8_t *hay, const RowCut &R, const WpArgs &A, const WpPlan &P, const uint64_t *scratch,
                    uint64_t total, int64_t *id, int64_t *start, int64_t *end, uint8_t *first, int64_t *row_offsets, hipStream_t st) {
     if (!plan_ok(P, R, A, hay, scratch) || !id || !start || !end || !first) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_wp<WP_MODE_EMIT>, dim3((uint32_t)P.ntiles), dim3(WP_THREADS), 0, st, T, hay, R, A, nullptr, nullptr,
                        (const int64_t *)(scratch + P.base), scratch + P.carry, total, id, start, end, first);
     const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? e : wp_rows(R, start, total, row_offsets, st);
+    return e != hipSuccess ? e : piece_rows(R, start, total, row_offsets, st);
 }
 
 } // namespace acx

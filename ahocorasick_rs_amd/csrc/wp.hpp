@@ -37,16 +37,17 @@
 //   k_wp<COUNT>
 //     A. every thread loads its 16 consecutive bytes (16-byte loads where the aligned 16 bytes lie inside the data, guarded
 //        byte loads at the data's two ends) and classifies them through cls in LDS.  The row starts inside the tile are
-//        marked in a bitmap in LDS (two bounded searches for offsets, the multiples for a row length).  A BOUNDARY is a byte
-//        that is not WORD, or a row start.  The word-start flags are ranked in position order (popcounts in the lane, a scan
-//        across the wave, the waves' sums through LDS: rows.hip's form) and the word starts go into a list in LDS: the
-//        walking lanes are dense and the list order is the output order.  A suffix minimum of every thread's first boundary
-//        over the workgroup gives every word start its end when that end lies inside the tile.
+//        marked in a bitmap in LDS (walk_row_marks<true> of at_walk.hpp: two bounded searches for offsets, the multiples for
+//        a row length).  A BOUNDARY is a byte that is not WORD, or a row start.  The word-start flags are ranked in position
+//        order (popcounts in the lane, then walk_rank: a scan across the wave, the waves' sums through LDS) and the word
+//        starts go into a list in LDS: the walking lanes are dense and the list order is the output order.  A suffix minimum
+//        of every thread's first boundary over the workgroup (walk_behind) gives every word start its end when that end lies
+//        inside the tile.
 //     B. the threads take words from the list.  A word with no boundary behind it in the tile (at most the tile's last one)
 //        scans forward at most M + 1 bytes from its start, clamped to the row's end and len: that decides length > M.
 //        Otherwise the lane walks the chain: the first step through root_next, continuation steps through cont_next -- the
 //        children of C's trie node, 1 KiB filled once per workgroup by 256 at_child calls -- and after the first byte the
-//        walk is at_path / at_pick of at_walk.hpp unchanged: depths count haystack bytes, lim = we - p, the handle folds in
+//        walk is at_best of at_walk.hpp (at_path with at_pick) unchanged: depths count haystack bytes, lim = we - p, the handle folds in
 //        the load.  The word's piece count goes to LDS: 1 if the word is too long or any step finds nothing.
 //     C. counts[tile] = the tile's pieces; bound[tile] = the position of the tile's first boundary, or "none".
 //   replace_scan turns counts into bases; T crosses the bus: 8 bytes.
@@ -56,7 +57,8 @@
 //   k_wp<EMIT>  A and B again (as at_emit walks again); an exclusive scan of the words' piece counts over the workgroup gives
 //     every word its base; the walking lane walks its word once more and stores id, start, end and first at
 //     base .. base + n - 1, never at or behind T.
-//   k_wp_rows   a thread per row: row_offsets[r] = count_lt(start, T, row_begin(r)), clamped into [0, T].
+//   k_piece_rows  (at.hip, piece_rows) a thread per row: row_offsets[r] = count_lt(start, T, row_begin(r)), clamped into
+//     [0, T].
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -117,11 +119,9 @@ WpPlan wp_plan(uint64_t len);
 hipError_t wp_count(const AtTrie &T, const uint8_t *hay, const RowCut &R, const WpArgs &A, const WpPlan &P, uint64_t *scratch,
                     hipStream_t st);
 inline const uint64_t *wp_total(const WpPlan &P, const uint64_t *scratch) { return scratch + P.base + P.ntiles; }
-// ... and from there, over the SAME inputs: k_wp<EMIT> and k_wp_rows.  total: what wp_total gave; id, start, end: total int64
+// ... and from there, over the SAME inputs: k_wp<EMIT> and piece_rows.  total: what wp_total gave; id, start, end: total int64
 // words, 8-byte aligned; first: total bytes; row_offsets: R.n + 1 words; every entry is written.
 hipError_t wp_emit(const AtTrie &T, const uint8_t *hay, const RowCut &R, const WpArgs &A, const WpPlan &P, const uint64_t *scratch,
                    uint64_t total, int64_t *id, int64_t *start, int64_t *end, uint8_t *first, int64_t *row_offsets, hipStream_t st);
-// the rows alone (R.len == 0: no piece): row_offsets[0 .. R.n] from start[0 .. total)
-hipError_t wp_rows(const RowCut &R, const int64_t *start, uint64_t total, int64_t *row_offsets, hipStream_t st);
 
 } // namespace acx

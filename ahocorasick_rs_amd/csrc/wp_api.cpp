@@ -1,6 +1,7 @@
 // wp_api.cpp -- WordPiece tokenization by the dictionary (wp.hpp has the definition): the host form of the definition, the
 // device stage, the acx_wordpiece* entry points and the accessors of their result.  No find runs: the chains read the trie
-// edges and the own lists every handle has.
+// edges and the own lists every handle has.  The entries' preambles, the two-pass frames, the staged route and the host twin
+// are the walkers' shared ones (result_block.hpp), the match kind's choice on the host is HostTrie::pick.
 #include "wp.hpp"
 #include "host_trie.hpp"
 #include "result_block.hpp"
@@ -20,6 +21,7 @@ struct ACX_HIDDEN acx_wp : ResultBlock {
     int64_t *end() const { return at<int64_t>(END); }
     uint8_t *first() const { return at<uint8_t>(FIRST); }
     int64_t *row_offsets() const { return at<int64_t>(ROW_OFFSETS); }
+    void shaped_like(const acx_wp &D) { pieces = D.pieces; rows = D.rows; }
 };
 
 namespace {
@@ -57,78 +59,53 @@ acx::WpArgs kernel_args(const acx_automaton *a, const uint8_t *cls, const uint8_
                        a->host.match_kind, unk_id};
 }
 
-// The counting half of the device stage on st: k_wp<COUNT>, the scan, the carry, and T -- 8 bytes cross the bus, the stream
-// is waited for.  *temp: the stage's scratch, one block of the buffer cache -- the caller's to return, behind the kernels.
-int wp_count_stage(acx_automaton *a, hipStream_t st, const uint8_t *d_hay, const acx::RowCut &R, const acx::WpArgs &A, acx::WpPlan *P,
-                   void **temp, uint64_t *total) {
-    *total = 0;
-    if (!R.len) return ACX_OK;
-    *P = acx::wp_plan(R.len);
-    HIPCHK(g_bufs.get(temp, P->words * 8, a->device));
-    uint64_t *scratch = (uint64_t *)*temp;
-    HIPCHK(acx::wp_count(acx::at_trie(a->dev), d_hay, R, A, *P, scratch, st));
-    HIPCHK(hipMemcpyAsync(total, acx::wp_total(*P, scratch), 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (*total > R.len) return fail(ACX_EDEVICE, "the tiles' counts do not sum to a number of pieces");
-    return ACX_OK;
-}
+// The device stage on st as the two passes of two_pass / two_pass_raw.  count: k_wp<COUNT>, the scan, the carry, and T -- 8
+// bytes cross the bus, the stream is waited for; *temp: the stage's scratch, one block of the buffer cache.  emit: into
+// columns sized by `total`, every entry of the five is written.
+struct WpStage {
+    acx_automaton *a;
+    const uint8_t *d_hay;
+    acx::RowCut R;
+    acx::WpArgs A;
+    acx::WpPlan P{};
 
-// ... and the emitting half into columns sized by `total`: every entry of the five is written
-int wp_emit_stage(acx_automaton *a, hipStream_t st, const uint8_t *d_hay, const acx::RowCut &R, const acx::WpArgs &A, const acx::WpPlan &P,
-                  void *temp, uint64_t total, int64_t *id, int64_t *start, int64_t *end, uint8_t *first, int64_t *row_offsets) {
-    if (!R.len) { // no piece: every row begins at piece 0
-        HIPCHK(hipMemsetAsync(row_offsets, 0, (R.n + 1) * 8, st));
+    int count(hipStream_t st, void **temp, uint64_t *total) {
+        *total = 0;
+        if (!R.len) return ACX_OK;
+        P = acx::wp_plan(R.len);
+        HIPCHK(g_bufs.get(temp, P.words * 8, a->device));
+        uint64_t *scratch = (uint64_t *)*temp;
+        HIPCHK(acx::wp_count(acx::at_trie(a->dev), d_hay, R, A, P, scratch, st));
+        HIPCHK(hipMemcpyAsync(total, acx::wp_total(P, scratch), 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return *total > R.len ? fail(ACX_EDEVICE, "the tiles' counts do not sum to a number of pieces") : ACX_OK;
+    }
+    int emit(hipStream_t st, void *temp, uint64_t total, int64_t *id, int64_t *start, int64_t *end, uint8_t *first,
+             int64_t *row_offsets) const {
+        if (!R.len) { // no piece: every row begins at piece 0
+            HIPCHK(hipMemsetAsync(row_offsets, 0, (R.n + 1) * 8, st));
+        } else if (!total) { // (no word in the data: the columns are empty and may have no address)
+            HIPCHK(acx::piece_rows(R, start, 0, row_offsets, st));
+        } else {
+            HIPCHK(acx::wp_emit(acx::at_trie(a->dev), d_hay, R, A, P, (const uint64_t *)temp, total, id, start, end, first, row_offsets, st));
+        }
         return ACX_OK;
     }
-    if (!total) { // (no word in the data: the columns are empty and may have no address)
-        HIPCHK(acx::wp_rows(R, start, 0, row_offsets, st));
-        return ACX_OK;
-    }
-    HIPCHK(acx::wp_emit(acx::at_trie(a->dev), d_hay, R, A, P, (const uint64_t *)temp, total, id, start, end, first, row_offsets, st));
-    return ACX_OK;
-}
+};
 
 // The device route under a lease: the stage on the context's stream, a device result.  Returns when T is known, with the
 // emitting half in flight (Z->done).  d_hay and the offsets must stay valid until then.
 int run_wp(acx_automaton *a, Ctx *c, const uint8_t *d_hay, uint64_t len, const Segments &G, const acx::WpArgs &A, acx_wp **out) {
     *out = nullptr;
-    const acx::RowCut R = row_cut(G, len);
+    WpStage S{a, d_hay, row_cut(G, len), A};
     acx_wp *Z = new_result<acx_wp>(a->device, true);
     if (!Z) return ACX_ENOMEM;
-    Z->rows = R.n;
-    acx::WpPlan P;
-    void *temp = nullptr;
-    int queued = wp_count_stage(a, c->stream, d_hay, R, A, &P, &temp, &Z->pieces);
-    if (queued == ACX_OK) queued = Z->alloc();
-    if (queued == ACX_OK)
-        queued = wp_emit_stage(a, c->stream, d_hay, R, A, P, temp, Z->pieces, Z->id(), Z->start(), Z->end(), Z->first(), Z->row_offsets());
-    const int rc = retire_find(queued, c->stream, nullptr, Z, temp);
-    if (rc != ACX_OK) { free_result(Z); return rc; }
-    *out = Z;
-    return ACX_OK;
-}
-
-// the host form of one step: the candidate `kind` keeps among the patterns that go on from `node` with h[p .. we); false: none
-bool host_step(const HostTrie &T, const uint8_t *h, uint64_t p, uint64_t we, uint32_t node, int kind, int64_t *pid, uint64_t *end) {
-    const acx::Automaton &H = T.A;
-    int64_t best = -1;
-    uint64_t best_end = 0;
-    uint32_t s = node;
-    for (uint64_t d = 0; s != acx::WP_NO_NODE && p + d < we;) {
-        const uint8_t b = h[p + d];
-        s = T.child(s, T.fold ? acx::fold_byte(b) : b);
-        if (!s) break;
-        d++;
-        if (H.own_off[s + 1] == H.own_off[s]) continue;
-        const int64_t i = (int64_t)H.own_pid[H.own_off[s]]; // (the lists are in id order)
-        if (kind == ACX_MATCH_LEFTMOST_FIRST && best >= 0 && best < i) continue;
-        best = i;
-        best_end = p + d;
-        if (kind == ACX_MATCH_STANDARD) break;
-    }
-    *pid = best;
-    *end = best_end;
-    return best >= 0;
+    Z->rows = S.R.n;
+    return two_pass(
+        c->stream, Z, &Z->pieces, nullptr, out, [&](hipStream_t st, void **temp, uint64_t *total) { return S.count(st, temp, total); },
+        [&](hipStream_t st, void *temp, uint64_t total) {
+            return S.emit(st, temp, total, Z->id(), Z->start(), Z->end(), Z->first(), Z->row_offsets());
+        });
 }
 
 struct Piece {
@@ -144,18 +121,10 @@ int acx_wordpiece_host(const acx_host_automaton_t *h, const uint8_t *hay, uint64
                        const uint8_t *cls, const uint8_t *prefix, uint64_t prefix_len, uint64_t max_word, int64_t unk_id,
                        uint32_t flags, int match_kind, uint64_t cap, int64_t *id, int64_t *start, int64_t *end, uint8_t *first,
                        int64_t *row_offsets, uint64_t *n_pieces) {
-    if (!h || !n_pieces) return fail(ACX_EINVAL, "null argument");
-    *n_pieces = 0;
-    int rc = wp_values(flags, cls, prefix, prefix_len, max_word);
+    if (n_pieces) *n_pieces = 0;
+    int rc = host_form_args(h && n_pieces, [&] { return wp_values(flags, cls, prefix, prefix_len, max_word); }, match_kind, any_kind,
+                            hay, len, offsets, &n_hay);
     if (rc != ACX_OK) return rc;
-    if (match_kind < ACX_MATCH_STANDARD || match_kind > ACX_MATCH_LEFTMOST_LONGEST) return fail(ACX_EINVAL, "unknown match kind");
-    if (len && !hay) return fail(ACX_EINVAL, "null argument");
-    if (!offsets) {
-        if (n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
-        n_hay = 1;
-    } else if ((rc = offsets_span(offsets, n_hay, len)) != ACX_OK) {
-        return rc;
-    }
     if (cap && (!id || !start || !end || !first || !row_offsets)) return fail(ACX_EINVAL, "null argument");
     if ((rc = wp_sizes(len, n_hay)) != ACX_OK) return rc;
     const HostTrie T{h->host, (h->flags & ACX_BUILD_ASCII_CASE_INSENSITIVE) != 0};
@@ -181,7 +150,8 @@ int acx_wordpiece_host(const acx_host_automaton_t *h, const uint8_t *hay, uint64
                 for (uint64_t q = ws; known && q < we;) {
                     int64_t pid;
                     uint64_t e;
-                    known = host_step(T, hay, q, we, q == ws ? 0u : cnode, match_kind, &pid, &e);
+                    // (a continuation goes on from C's node; none, when that is not in the trie)
+                    known = (q == ws || cnode != acx::WP_NO_NODE) && T.pick(hay, q, we, q == ws ? 0u : cnode, match_kind, false, &pid, &e);
                     if (known) word.push_back(Piece{pid, q, e}); // (at most max_word pieces: no allocation)
                     q = e;
                 }
@@ -211,16 +181,13 @@ int acx_wordpiece_device(acx_automaton_t *a, const void *d_hay, uint64_t len, co
     *out = nullptr;
     int rc = wp_values(flags, cls, prefix, prefix_len, max_word);
     if (rc != ACX_OK) return rc;
-    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
-    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
-    if ((uintptr_t)d_offsets & 7) return fail(ACX_EINVAL, "offsets must be 8-byte aligned");
     Segments G;
-    if ((rc = make_segments(d_offsets, n_hay, uniform_len, len, &G)) != ACX_OK) return rc;
-    if ((rc = wp_sizes(len, rows_of(G).n)) != ACX_OK) return rc;
-    Lease lease(a);
-    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    // (a case-insensitive handle folds in the walk's loads: no folded copy of the data)
-    return run_wp(a, lease.c, (const uint8_t *)d_hay, len, G, kernel_args(a, cls, prefix, prefix_len, max_word, unk_id), out);
+    rc = walk_device_args(d_hay, len, d_offsets, n_hay, uniform_len,
+                          [&] { return (uintptr_t)d_offsets & 7 ? fail(ACX_EINVAL, "offsets must be 8-byte aligned") : ACX_OK; }, &G);
+    if (rc != ACX_OK || (rc = wp_sizes(len, rows_of(G).n)) != ACX_OK) return rc;
+    return leased(a, [&](Ctx *c) {
+        return run_wp(a, c, (const uint8_t *)d_hay, len, G, kernel_args(a, cls, prefix, prefix_len, max_word, unk_id), out);
+    });
 }
 
 int acx_wordpiece_into_device(acx_automaton_t *a, const void *d_hay, uint64_t len, const uint64_t *d_offsets, uint64_t n_hay,
@@ -231,28 +198,21 @@ int acx_wordpiece_into_device(acx_automaton_t *a, const void *d_hay, uint64_t le
     *n_pieces = 0;
     int rc = wp_values(flags, cls, prefix, prefix_len, max_word);
     if (rc != ACX_OK) return rc;
-    if (len && !d_hay) return fail(ACX_EINVAL, "null haystack");
-    if (d_offsets && uniform_len) return fail(ACX_EINVAL, "offsets and uniform_len exclude one another");
-    if (((uintptr_t)d_offsets | (uintptr_t)d_id | (uintptr_t)d_start | (uintptr_t)d_end | (uintptr_t)d_row_offsets) & 7)
-        return fail(ACX_EINVAL, "offsets and the four int64 columns must be 8-byte aligned");
-    if (cap && (!d_id || !d_start || !d_end || !d_first || !d_row_offsets)) return fail(ACX_EINVAL, "null argument");
     Segments G;
-    if ((rc = make_segments(d_offsets, n_hay, uniform_len, len, &G)) != ACX_OK) return rc;
-    const acx::RowCut R = row_cut(G, len);
-    if ((rc = wp_sizes(len, R.n)) != ACX_OK) return rc;
-    Lease lease(a);
-    if (!lease.c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-    const hipStream_t st = lease.c->stream;
-    const acx::WpArgs A = kernel_args(a, cls, prefix, prefix_len, max_word, unk_id);
-    acx::WpPlan P;
-    void *temp = nullptr;
-    rc = wp_count_stage(a, st, (const uint8_t *)d_hay, R, A, &P, &temp, n_pieces);
-    if (rc == ACX_OK && cap && *n_pieces <= cap)
-        rc = wp_emit_stage(a, st, (const uint8_t *)d_hay, R, A, P, temp, *n_pieces, d_id, d_start, d_end, d_first, d_row_offsets);
-    const hipError_t s = hipStreamSynchronize(st); // (complete when it returns, whatever the launches said)
-    g_bufs.put(temp, a->device);
-    if (rc != ACX_OK) return rc;
-    return s == hipSuccess ? ACX_OK : hipfail(s, "hipStreamSynchronize");
+    rc = walk_device_args(d_hay, len, d_offsets, n_hay, uniform_len, [&] {
+        if (((uintptr_t)d_offsets | (uintptr_t)d_id | (uintptr_t)d_start | (uintptr_t)d_end | (uintptr_t)d_row_offsets) & 7)
+            return fail(ACX_EINVAL, "offsets and the four int64 columns must be 8-byte aligned");
+        return cap && (!d_id || !d_start || !d_end || !d_first || !d_row_offsets) ? fail(ACX_EINVAL, "null argument") : ACX_OK;
+    }, &G);
+    if (rc != ACX_OK || (rc = wp_sizes(len, rows_of(G).n)) != ACX_OK) return rc;
+    return leased(a, [&](Ctx *c) {
+        WpStage S{a, (const uint8_t *)d_hay, row_cut(G, len), kernel_args(a, cls, prefix, prefix_len, max_word, unk_id)};
+        return two_pass_raw(
+            a->device, c->stream, cap, n_pieces, [&](hipStream_t st, void **temp, uint64_t *total) { return S.count(st, temp, total); },
+            [&](hipStream_t st, void *temp, uint64_t total) { // (cap == 0: a count alone, the columns may have no address)
+                return cap ? S.emit(st, temp, total, d_id, d_start, d_end, d_first, d_row_offsets) : ACX_OK;
+            });
+    });
 }
 
 int acx_wordpiece(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const uint64_t *offsets, uint64_t n_hay, const uint8_t *cls,
@@ -262,36 +222,17 @@ int acx_wordpiece(acx_automaton_t *a, const uint8_t *hay, uint64_t len, const ui
     *out = nullptr;
     int rc = wp_values(flags, cls, prefix, prefix_len, max_word);
     if (rc != ACX_OK) return rc;
-    if (len && !hay) return fail(ACX_EINVAL, "null haystack");
-    const bool batch = offsets != nullptr;
-    if (!batch) {
-        if (n_hay > 1) return fail(ACX_EINVAL, "several haystacks need offsets");
-        n_hay = 1;
-    } else if ((rc = offsets_span(offsets, n_hay, len)) != ACX_OK) {
-        return rc;
-    }
+    if ((rc = host_rows(hay, len, offsets, &n_hay, "null haystack")) != ACX_OK) return rc;
     if ((rc = wp_sizes(len, n_hay)) != ACX_OK) return rc;
     // the data (and, for a batch, its offsets) through the context's staging buffers; the same kernels; the block comes home
     // in one copy
     acx_wp *D = nullptr;
-    {
-        Lease lease(a);
-        Ctx *c = lease.c;
-        if (!c) return fail(ACX_EDEVICE, "could not create a stream for the call");
-        if ((rc = stage_host(a, c, hay, len, batch ? offsets : nullptr, batch ? n_hay + 1 : 0, false)) != ACX_OK) return rc;
-        const Segments G = batch ? Segments{c->ws.offsets, n_hay, 0} : Segments{nullptr, 1, 0};
-        rc = run_wp(a, c, c->ws.hay, len, G, kernel_args(a, cls, prefix, prefix_len, max_word, unk_id), &D);
-        if (rc == ACX_OK) rc = D->wait(); // (the staging buffers are the context's)
-        else (void)hipStreamSynchronize(c->stream);
-    }
-    acx_wp *Z = rc == ACX_OK ? new_result<acx_wp>(a->device, false) : nullptr;
-    if (Z) {
-        Z->pieces = D->pieces;
-        Z->rows = D->rows;
-        if ((rc = Z->alloc()) != ACX_OK) { free_result(Z); free_result(D); return rc; }
-    }
-    if ((rc = copy_down(rc, D, Z, D ? D->block_bytes : 0, "the word pieces' copy", out)) != ACX_OK) return rc;
+    rc = staged_walk(a, hay, len, offsets, n_hay, &D, [&](Ctx *c, const Segments &G, acx_wp **dev) {
+        return run_wp(a, c, c->ws.hay, len, G, kernel_args(a, cls, prefix, prefix_len, max_word, unk_id), dev);
+    });
+    if ((rc = host_twin(rc, D, "the word pieces' copy", out)) != ACX_OK) return rc;
     if (!codepoints) return ACX_OK;
+    acx_wp *Z = *out;
     // positions in characters: the characters that begin before each
     std::vector<uint64_t> cs;
     if ((rc = char_starts(hay, len, &cs)) != ACX_OK) { free_result(Z); *out = nullptr; return rc; }

@@ -151,9 +151,12 @@ def run_raw(a, hay, cap, *, offsets=None, uniform=0, flags=0, base_res=0):
     return T, out
 
 
-def check_raw(patterns, kind, hay, *, offsets=None, uniform=0, utf8=False, fold=False, what=None, automaton=None, base_res=0):
+def check_raw(patterns, kind, hay, *, offsets=None, uniform=0, utf8=False, fold=False, what=None, automaton=None, base_res=0,
+              want=None):
+    """want: the expected columns when they are not the definition's (the host form's)"""
     cut = offsets if offsets is not None else (np.arange(0, len(hay) + 1, uniform) if uniform else None)
-    want = definition(patterns, hay, kind, offsets=cut, utf8=utf8, fold=fold)
+    if want is None:
+        want = definition(patterns, hay, kind, offsets=cut, utf8=utf8, fold=fold)
     a = automaton or capi.Automaton(patterns, kind, ascii_case_insensitive=fold)
     try:
         T, out = run_raw(a, hay, len(want[0]), offsets=offsets, uniform=uniform, flags=UTF8 if utf8 else 0, base_res=base_res)
@@ -295,6 +298,20 @@ def test_raw_the_three_row_cuts(kind, form):
         check_raw(MIXED, kind, hay[:2 * TILE], uniform=TILE, what=(form, "whole tiles"))
     else:
         check_raw(MIXED, kind, hay, what=form)
+
+
+@pytest.mark.parametrize("u", [1, 16, TILE - 1, TILE, TILE + 1, 2 * TILE])
+def test_raw_rows_of_one_length_that_begin_on_before_and_behind_a_tile_boundary(u):
+    """Exactly u * n bytes, n the smallest number of rows that gives more than two tiles (3 for the three lengths around the
+    tile): row starts fall on a tile's first byte, one byte before it and one byte behind it -- the marks of k_seg leave out
+    the one ON the first byte.  Dictionary words among x, y and z, which no entry begins with; against acx_segment_host over
+    the same cut written as offsets, entry for entry."""
+    n = {1: 2 * TILE + 1, 16: 2 * TILE // 16 + 1, 2 * TILE: 2}.get(u, 3)
+    assert u * n > 2 * TILE
+    hay = planted(u * n, u, every=5)
+    want = host_chain(MIXED, hay, LL, offsets=np.arange(n + 1, dtype=np.uint64) * u)
+    assert len(want[2]) == n + 1 and (want[0] == -1).any() and (want[0] >= 0).any()
+    check_raw(MIXED, LL, hay, uniform=u, what=("row length", u), want=want)
 
 
 def test_raw_no_byte_every_byte_and_one_byte_per_wave_survive_the_first_byte():

@@ -117,9 +117,11 @@ def run_raw(a, hay, cls, cap, *, prefix=b"##", M=100, unk=-1, offsets=None, unif
 
 
 def check_raw(patterns, kind, hay, cls=CLS, *, prefix=b"##", M=100, unk=-1, offsets=None, uniform=0, fold=False, what=None,
-              automaton=None, base_res=0):
+              automaton=None, base_res=0, want=None):
+    """want: the expected columns when they are not the definition's (the host form's)"""
     cut = offsets if offsets is not None else (np.arange(0, len(hay) + 1, uniform) if uniform else None)
-    want = wpd.definition(patterns, hay, kind, cls, prefix=prefix, M=M, unk=unk, offsets=cut, fold=fold)
+    if want is None:
+        want = wpd.definition(patterns, hay, kind, cls, prefix=prefix, M=M, unk=unk, offsets=cut, fold=fold)
     a = automaton or capi.Automaton(patterns, kind, ascii_case_insensitive=fold)
     try:
         cap = max(len(want[0]), 1)  # (cap 0 is the count pass alone)
@@ -339,6 +341,25 @@ def test_raw_row_starts_and_empty_rows(kind):
         m = n // u * u
         check_raw(VOCAB, kind, dense[:m], uniform=u, what=("row length", u))
     check_raw(VOCAB, kind, dense, what="neither")
+
+
+@pytest.mark.parametrize("u", [1, 16, TILE - 1, TILE, TILE + 1, 2 * TILE])
+def test_raw_rows_of_one_length_that_begin_on_before_and_behind_a_tile_boundary(u):
+    """Exactly u * n bytes, n the smallest number of rows that gives more than two tiles (3 for the three lengths around the
+    tile): row starts fall on a tile's first byte, one byte before it and one byte behind it -- the marks of k_wp include the
+    one ON the first byte.  Dense words over the vocabulary's letters with a "d" now and then, which no entry begins with, so
+    that the row starts cut words; against acx_wordpiece_host over the same cut written as offsets, entry for entry."""
+    n = {1: 2 * TILE + 1, 16: 2 * TILE // 16 + 1, 2 * TILE: 2}.get(u, 3)
+    assert u * n > 2 * TILE
+    hay = text(u * n, u, space=0.02)
+    h = capi.HostAutomaton(VOCAB, LL, 0)
+    try:
+        want = capi.wordpiece_host(h, hay, CLS, offsets=np.arange(n + 1, dtype=np.uint64) * u, match_kind=LL, prefix=b"##",
+                                   max_word=100, unk_id=-1)
+    finally:
+        h.close()
+    assert len(want[4]) == n + 1 and (want[0] == -1).any() and (want[0] >= 0).any()
+    check_raw(VOCAB, LL, hay, uniform=u, what=("row length", u), want=want)
 
 
 def test_raw_every_alignment_of_the_data():
